@@ -12,6 +12,8 @@ Prints ONE JSON line (rank 0).  Extra blocks:
                   divided by its average launch duration, measured in this process with HIP events on the launch stream
   cpu_baseline -- the oracle (PyTorch-CPU fp32 restatement, kind "port") timed on the host cores on a bounded sample
   parity       -- GPU fp16 vs CPU fp32 on the first guided UNet evaluation of this very run
+  dump_outputs -- with --dump-outputs DIR: the files written there (the last timed step's images; the inputs -- weights,
+                  token ids, the step's x_T -- depend on the arguments only, so two builds can be compared file for file)
 """
 import argparse
 import json
@@ -93,7 +95,30 @@ def parse():
                     '(exchange per UNet evaluation); even --gpus only; value counts one image per PAIR')
     ap.add_argument('--per-step-launches', action='store_true', help='drive the sampler loop from Python (one graph replay per UNet '
                     'evaluation + small launches) instead of replaying the whole trajectory as one device graph')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write the uint8 images the last timed step returned '
+                    '(every rank\'s, in rank order) as float32 to DIR/images.npy, so that two builds can be compared output for output')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, name, a):
+    """a (host array) -> out_dir/<name>.npy as float32; above DUMP_LIMIT_BYTES a fixed seeded sample of its flattened
+    elements goes to <name>.npy and their flat indices to <name>_index.npy (float64, exact).  Returns the files written."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.asarray(a, dtype=np.float32)
+    files = {name: a}
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // 12                   # 4 bytes of value + 8 bytes of index per sampled element
+        idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+        files = {name: a.reshape(-1)[idx], name + '_index': idx.astype(np.float64)}
+    for k, v in files.items():
+        np.save(os.path.join(out_dir, k + '.npy'), v)
+    return {k: list(v.shape) for k, v in files.items()}
 
 
 def spawn_ranks(n, argv):
@@ -218,6 +243,16 @@ def main():
         img = one_image()
     barrier()
     elapsed = time.perf_counter() - t0
+    last_images = None
+    if args.dump_outputs:
+        # what the caller of the timed path received in the last timed step, copied off the device before anything else runs
+        last_images = img.contiguous()
+        if dist is not None:
+            mine = last_images if dist.get_backend() != 'gloo' else last_images.cpu()
+            parts = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(parts, mine)
+            last_images = torch.cat(parts[::2] if args.cfg_split else parts)   # both ranks of a cfg-split pair hold the same images
+        last_images = last_images.cpu().numpy()
     rccl = None
     if dist is not None:
         # what the driver needs to confirm the collective really spanned N ranks: every rank's own time and device, gathered
@@ -368,6 +403,8 @@ def main():
             z_gpu = pipe.sample_plms(ctx2, x_T, steps=20, guidance=7.5)
             out.update(cpu_baseline_and_parity(pipe, sds, x_T, ctx2, e_gpu=pipe._eps(x_T, temb[0], 7.5, 1),
                                                img_gpu=pipe.decode(z_gpu, mode=1), z_gpu=z_gpu))
+        if last_images is not None:
+            out['dump_outputs'] = {'dir': args.dump_outputs, 'files': dump_outputs(args.dump_outputs, 'images', last_images)}
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

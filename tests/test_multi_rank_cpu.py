@@ -56,9 +56,12 @@ def test_plms_schedule_indexing_exact():
     assert np.array_equal(scaled_linear_alphas_cumprod(), ac)
     assert np.array_equal(s.alphas, ac[s.timesteps]) and s.alphas_prev[0] == ac[0] and np.array_equal(s.alphas_prev[1:], ac[s.timesteps[:-1]])
     c = s.coef(19)
-    a_t = torch.full((1,), float(ac[951])); a_prev = torch.full((1,), float(ac[901]))
-    assert c['sqrt_at'] == float(a_t.sqrt()) and c['sqrt_a_prev'] == float(a_prev.sqrt())
-    assert c['dir_coef'] == float((1. - a_prev).sqrt()) and c['sqrt_one_minus_at'] == float(np.sqrt(1. - torch.from_numpy(ac)[951:952])[0])
+    # yardstick: the correctly rounded fp32 square root (the float64 root of an fp32 value, rounded to fp32); torch's CPU
+    # sqrt is one ulp off on some hosts, so it cannot serve as the bit-exact reference
+    sqrt32 = lambda v: float(np.float32(np.sqrt(np.float64(np.float32(v)))))
+    a_t, a_prev = ac[951], ac[901]
+    assert c['sqrt_at'] == sqrt32(a_t) and c['sqrt_a_prev'] == sqrt32(a_prev)
+    assert c['dir_coef'] == sqrt32(np.float32(1.) - a_prev) and c['sqrt_one_minus_at'] == sqrt32(np.float32(1.) - a_t)
     assert PLMS_ORDERS[3] == ((55.0, -59.0, 37.0, -9.0), 24.0)
     s50 = PlmsSchedule(50)
     assert s50.timesteps[0] == 1 and s50.timesteps[-1] == 981 and s50.steps == 50

@@ -22,7 +22,9 @@ def _runtime():
 @pytest.mark.skipif(_runtime() is None, reason='clang AddressSanitizer runtime not found')
 def test_host_tests_pass_under_asan_and_ubsan():
     subprocess.check_call(['make', '-C', PKG, '-j8', 'all', 'asan'], stdout=subprocess.DEVNULL)
-    env = dict(os.environ, SDOD_LIBSDOD='libsdod_asan.so', LD_PRELOAD=_runtime(),
+    # host code only: the instrumented processes see no GPU, also where one is present (there torch's GPU initialisation
+    # fails under the preloaded ASan runtime, and a sanitized process has no business on a shared device anyway)
+    env = dict(os.environ, SDOD_LIBSDOD='libsdod_asan.so', LD_PRELOAD=_runtime(), HIP_VISIBLE_DEVICES='-1', CUDA_VISIBLE_DEVICES='-1',
                ASAN_OPTIONS='detect_leaks=0:halt_on_error=1:abort_on_error=1',      # CPython itself "leaks" at exit
                UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1')
     probe = subprocess.run([sys.executable, '-c', 'import sys; sys.path.insert(0, %r); from sdod.amd import _lib; '
