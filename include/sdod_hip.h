@@ -166,16 +166,19 @@ SDOD_API int sdod_gemm_time_cold(const sdod_gemm_desc* d, void* stream, int iter
  * later sdod_group_norm_nhwc / sdod_graph_execute on that device return LIBSDOD_RUNTIME_ERROR until the owner has re-zeroed
  * the workspace and called sdod_group_norm_clear_error(). */
 SDOD_API size_t sdod_group_norm_workspace_bytes(int n, int groups);
-/* byte offsets of the workspace's parts for (n, groups): barrier lines, partial sums, statistics, pilot shifts, end */
+/* byte offsets of the workspace's parts for (n, groups): barrier lines, partial statistics, collapsed statistics, a reserved
+ * [n][groups] float region (unused), end */
 SDOD_API int sdod_group_norm_layout(int n, int groups, size_t* sync_off, size_t* partial_off, size_t* stats_off, size_t* shift_off,
                                     size_t* end_off);
 /* 0, or LIBSDOD_RUNTIME_ERROR once a one-launch GroupNorm on the current device has timed out at its grid barrier (sticky) */
 SDOD_API int sdod_group_norm_status(void);
 SDOD_API int sdod_group_norm_clear_error(void);
-/* 1 = the single-launch kernel (whole image x channel set in LDS) handles this shape, 2 = statistics + apply launches */
+/* 1 = a single-launch kernel handles this shape, 2 = statistics + apply launches, 0 = no NHWC kernel takes it */
 SDOD_API int sdod_group_norm_launches(int hw, int c, int groups, int dtype);
 /* which kernel the call below launches for this shape: 0 = one-launch grid-barrier kernel (maps >= 5 MB), 1 = one launch, a
- * workgroup per (image, group), 2 = one launch, small-map LDS kernel, 3 = statistics + apply launches; -1 = bad shape */
+ * workgroup per (image, group), 2 = one launch, small-map LDS kernel, 3 = statistics + apply launches; -1 = no kernel takes it
+ * (a bad shape, or channels too many for the kernels' tables): the call below then returns LIBSDOD_INVALID_ARGUMENT before any
+ * launch, and sdod_group_norm_nchw takes the operator (it has no channel limit) */
 SDOD_API int sdod_group_norm_path(int n, int hw, int c0, int c1, int groups, int dtype);
 SDOD_API int sdod_group_norm_nhwc(const void* x, const void* x2, void* y, const float* weight, const float* bias,
                                   int n, int hw, int c0, int c1, int groups, float eps, int silu, int dtype,

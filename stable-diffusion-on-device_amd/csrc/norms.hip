@@ -9,11 +9,11 @@
 // HBM-bound design: in NHWC a group's data is a strided set of short channel runs, so a block-per-(n,g)
 // kernel would read 20..160-byte fragments.  Instead the statistics pass reads whole pixel rows (fully
 // coalesced 16-byte lanes, many workgroups), every thread owning a fixed 8-channel chunk and keeping
-// per-channel shifted sums in registers; per-group partials go through LDS to a small fp32 scratch.
+// per-channel running moments in registers; per-group partials go through LDS to a small fp32 scratch.
 // The apply pass first reduces those partials to mean/rstd per (n,g) (fixed order, one wave per group -- cheaper than
 // a third launch), then runs as a vectorised elementwise kernel whose per-channel scale/shift live in LDS, with SiLU fused (every ResBlock site) and the
-// channel concat of the UNet skip connections folded into the reads.  Sums are shifted by a per-group
-// pilot value (first element of the group) so E[x^2]-E[x]^2 cancellation stays harmless in fp32.
+// channel concat of the UNet skip connections folded into the reads.  Statistics are (mean, M2) partials combined without
+// cancellation (GnMom below), so neither an outlier nor a large common offset of the data costs fp32 accuracy.
 // Algorithmic bytes: N*HW*C*sizeof(T) read twice + written once (the second read is L2/MALL resident).
 #include "common.h"
 #include "sdod_hip.h"
@@ -23,6 +23,25 @@
 #include <cstdlib>
 
 namespace {
+
+// Statistics without cancellation.  A partial of n values carries its mean m and its centred second moment M2 = sum (x - m)^2,
+// computed exactly (two passes) where the values are resident, else from sums shifted by one of the partial's own values
+// (Welford on the statistics pass of path 3; per-thread pilots in the grid kernel and the lean pair).  Partials combine either pairwise (Chan et al.:
+// gn_merge) or, for a whole list at once, with two plain sums: mean = sum n_i m_i / N, M2 = sum M2_i + n_i (m_i - mean)^2.
+// Every term of the second sum is non-negative, so no single value -- an outlier at a slab's first element included -- and no
+// common offset of the data can cancel the variance away (E[x^2] - E[x]^2 in fp32 can, however it is shifted).
+struct GnMom {
+    float n, mean, m2;
+};
+SDOD_DEVICE GnMom gn_merge(GnMom a, const GnMom& b) {
+    if (b.n == 0.f) return a;
+    if (a.n == 0.f) return b;
+    const float n = a.n + b.n, d = b.mean - a.mean, f = b.n / n;
+    a.mean += d * f;
+    a.m2 += b.m2 + d * d * a.n * f;
+    a.n = n;
+    return a;
+}
 
 template <typename T>
 struct Chunk8;
@@ -60,10 +79,8 @@ struct GnP {
     void* y;
     const float* w;
     const float* b;
-    float* partial; // [N][nchunks][G][2]
-    float* stats;   // [N][G][2] mean, rstd
-    float* shift;   // [N][G] pilot value of every group, written by the statistics pass (the apply pass must not re-read x:
-                    // with y == x another workgroup may already have overwritten pixel 0)
+    float* partial; // [N][nchunks][G][2] mean, M2 of every statistics chunk
+    float* stats;   // [N][G][2] the same, collapsed over the chunks (very large maps)
     void* sync;     // grid-barrier words of the one-launch kernel for big maps (zeroed once by the workspace's owner)
     int N, HW, C0, C1, C, G, Cg;
     float eps;
@@ -79,6 +96,12 @@ SDOD_DEVICE const T* gn_src(const GnP& p, int n, int pix, int c) {
     return reinterpret_cast<const T*>(p.x1) + ((size_t)n * p.HW + pix) * p.C1 + (c - p.C0);
 }
 
+// pixels of statistics chunk `ch` (the last chunk may be short)
+SDOD_DEVICE float gn_chunk_pixels(int ch, int ppc, int hw) { return (float)(min(hw, (ch + 1) * ppc) - ch * ppc); }
+
+// Statistics: per thread and channel a running (mean, M2) over the pixels the thread visits (Welford: one reciprocal per pixel
+// serves all of the thread's channels), then per group the two-sum combination over the chunk's threads and channels; the
+// chunk's (mean, M2) of every group goes to the workspace.
 template <typename T, int NPASS>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const GnP p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -89,19 +112,18 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnP p) {
     const int pix_begin = chunk_id * p.pix_per_chunk;
     const int pix_end = min(p.HW, pix_begin + p.pix_per_chunk);
 
-    float s1[NPASS][8], s2[NPASS][8], shift[NPASS][8];
+    float mu[NPASS][8], m2[NPASS][8];
 #pragma unroll
-    for (int ps = 0; ps < NPASS; ++ps) {
-        const int c0 = (cx + ps * p.cpp) * 8;
+    for (int ps = 0; ps < NPASS; ++ps)
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            s1[ps][e] = 0.f;
-            s2[ps][e] = 0.f;
-            const int g = (c0 + e) / p.Cg;
-            shift[ps][e] = (float)*gn_src<T>(p, n, 0, g * p.Cg);
+            mu[ps][e] = 0.f;
+            m2[ps][e] = 0.f;
         }
-    }
+    float cnt = 0.f;
     for (int pix = pix_begin + py; pix < pix_end; pix += p.pp) {
+        cnt += 1.f;
+        const float r = 1.f / cnt;
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
             const int c0 = (cx + ps * p.cpp) * 8;
@@ -109,9 +131,9 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnP p) {
             Chunk8<T>::load(gn_src<T>(p, n, pix, c0), v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float d = v[e] - shift[ps][e];
-                s1[ps][e] += d;
-                s2[ps][e] += d * d;
+                const float d = v[e] - mu[ps][e];
+                mu[ps][e] += d * r;
+                m2[ps][e] += d * (v[e] - mu[ps][e]);
             }
         }
     }
@@ -120,45 +142,64 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnP p) {
         const int c0 = (cx + ps * p.cpp) * 8;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            red[((size_t)py * p.C + c0 + e) * 2 + 0] = s1[ps][e];
-            red[((size_t)py * p.C + c0 + e) * 2 + 1] = s2[ps][e];
+            red[((size_t)py * p.C + c0 + e) * 2 + 0] = mu[ps][e];
+            red[((size_t)py * p.C + c0 + e) * 2 + 1] = m2[ps][e];
         }
     }
     __syncthreads();
     const int tid = py * blockDim.x + cx;
     const int nthreads = blockDim.x * blockDim.y;
+    const int npix = pix_end - pix_begin;
     for (int g = tid; g < p.G; g += nthreads) {
-        float a = 0.f, b = 0.f;
-        for (int q = 0; q < p.pp; ++q)
+        float s = 0.f;
+        for (int q = 0; q < p.pp; ++q) {
+            const float nq = (float)max(0, (npix - q + p.pp - 1) / p.pp); // pixels row q of the workgroup visited
+            for (int c = g * p.Cg; c < (g + 1) * p.Cg; ++c) s += nq * red[((size_t)q * p.C + c) * 2 + 0];
+        }
+        const float mean = s / ((float)npix * (float)p.Cg);
+        float b = 0.f;
+        for (int q = 0; q < p.pp; ++q) {
+            const float nq = (float)max(0, (npix - q + p.pp - 1) / p.pp);
             for (int c = g * p.Cg; c < (g + 1) * p.Cg; ++c) {
-                a += red[((size_t)q * p.C + c) * 2 + 0];
-                b += red[((size_t)q * p.C + c) * 2 + 1];
+                const float d = red[((size_t)q * p.C + c) * 2 + 0] - mean;
+                b += red[((size_t)q * p.C + c) * 2 + 1] + nq * d * d;
             }
+        }
         float* dst = p.partial + (((size_t)n * p.nchunks + chunk_id) * p.G + g) * 2;
-        dst[0] = a;
+        dst[0] = mean;
         dst[1] = b;
-        if (chunk_id == 0) p.shift[(size_t)n * p.G + g] = (float)*gn_src<T>(p, n, 0, g * p.Cg);
     }
+}
+
+// (mean, M2) of group g of image n over the chunk partials [n][nchunks][G][2]: the lanes of a wave stride over the chunks,
+// two wave sums (fixed order: bit-reproducible).  Every lane gets the result.
+SDOD_DEVICE GnMom gn_combine_chunks(const float* partial, int n, int g, int nchunks, int G, int ppc, int hw, int cg) {
+    const int lane = threadIdx.x & 63;
+    float s = 0.f;
+    for (int ch = lane; ch < nchunks; ch += 64)
+        s += gn_chunk_pixels(ch, ppc, hw) * (float)cg * partial[(((size_t)n * nchunks + ch) * G + g) * 2];
+    const float cnt = (float)hw * (float)cg;
+    const float mean = wave_sum(s) / cnt;
+    float b = 0.f;
+    for (int ch = lane; ch < nchunks; ch += 64) {
+        const float* src = partial + (((size_t)n * nchunks + ch) * G + g) * 2;
+        const float d = src[0] - mean;
+        b += src[1] + gn_chunk_pixels(ch, ppc, hw) * (float)cg * d * d;
+    }
+    return {cnt, mean, wave_sum(b)};
 }
 
 // Large maps (VAE 256^2 / 512^2 levels) need hundreds of statistics workgroups to stream at HBM rate; their partials are
 // collapsed to one entry per (n, group) by this small kernel so that the apply pass keeps reading a short list.
-__global__ __launch_bounds__(256) void gn_collapse_kernel(const float* partial, float* collapsed, int nchunks, int G) {
+__global__ __launch_bounds__(256) void gn_collapse_kernel(const float* partial, float* collapsed, int nchunks, int G, int ppc, int hw,
+                                                          int cg) {
     const int n = blockIdx.y;
-    const int lane = threadIdx.x & 63;
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (g >= G) return;
-    float a = 0.f, b = 0.f;
-    for (int ch = lane; ch < nchunks; ch += 64) {
-        const float* src = partial + (((size_t)n * nchunks + ch) * G + g) * 2;
-        a += src[0];
-        b += src[1];
-    }
-    a = wave_sum(a);
-    b = wave_sum(b);
-    if (lane == 0) {
-        collapsed[((size_t)n * G + g) * 2 + 0] = a;
-        collapsed[((size_t)n * G + g) * 2 + 1] = b;
+    const GnMom m = gn_combine_chunks(partial, n, g, nchunks, G, ppc, hw, cg);
+    if ((threadIdx.x & 63) == 0) {
+        collapsed[((size_t)n * G + g) * 2 + 0] = m.mean;
+        collapsed[((size_t)n * G + g) * 2 + 1] = m.m2;
     }
 }
 
@@ -172,27 +213,11 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnP p) {
     const int n = blockIdx.y;
     // finalize the statistics here (every workgroup redoes this small, fixed-order reduction; it costs less than the
     // extra launch a separate finalize kernel would): one wave per group, lanes stride over the chunk partials
-    {
-        const int lane = threadIdx.x & 63;
-        for (int g = threadIdx.x >> 6; g < p.G; g += blockDim.x >> 6) {
-            float a = 0.f, b = 0.f;
-            for (int ch = lane; ch < p.nchunks; ch += 64) {
-                const float* src = p.partial + (((size_t)n * p.nchunks + ch) * p.G + g) * 2;
-                a += src[0];
-                b += src[1];
-            }
-            a = wave_sum(a);
-            b = wave_sum(b);
-            if (lane == 0) {
-                const float cnt = (float)p.HW * (float)p.Cg;
-                const float shift = p.shift[(size_t)n * p.G + g];
-                const float icnt = __builtin_amdgcn_rcpf(cnt);
-                const float md = a * icnt;
-                float var = b * icnt - md * md;
-                var = var < 0.f ? 0.f : var;
-                gm[g] = shift + md;
-                gr[g] = rsqrt_fast(var + p.eps);
-            }
+    for (int g = threadIdx.x >> 6; g < p.G; g += blockDim.x >> 6) {
+        const GnMom m = gn_combine_chunks(p.partial, n, g, p.nchunks, p.G, p.pix_per_chunk, p.HW, p.Cg);
+        if ((threadIdx.x & 63) == 0) {
+            gm[g] = m.mean;
+            gr[g] = rsqrt_fast(m.m2 / m.n + p.eps);
         }
     }
     __syncthreads();
@@ -262,10 +287,33 @@ __global__ __launch_bounds__(NT) void gn_small_kernel(const GnP p, int sw) {
     unsigned char* gidx = reinterpret_cast<unsigned char*>(red + NWV * 8);
     for (int c = tid; c < sw; c += NT) gidx[c] = (unsigned char)(c / p.Cg);
     __syncthreads();
-    const int ng = sw / p.Cg; // <= 4 for every SD channel count (asserted on the host)
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f}, shf[4];
+    // exact two-pass statistics over the slab in LDS: group sums -> means, then the squared deviations from them
+    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f}, mu[4];
+    for (int i = tid; i < total; i += NT) {
+        const int pix = i / cps, cc = i - pix * cps;
+        float v[8];
+        Chunk8<T>::load(slab + (size_t)pix * sw + cc * 8, v);
 #pragma unroll
-    for (int gi = 0; gi < 4; ++gi) shf[gi] = gi < ng ? (float)slab[gi * p.Cg] : 0.f; // pilot shift: first element of the group
+        for (int e = 0; e < 8; ++e) {
+            const int g = gidx[cc * 8 + e];
+#pragma unroll
+            for (int gi = 0; gi < 4; ++gi) s1[gi] += g == gi ? v[e] : 0.f;
+        }
+    }
+#pragma unroll
+    for (int gi = 0; gi < 4; ++gi) {
+        s1[gi] = wave_sum(s1[gi]);
+        if (lane == 0) red[(wave * 4 + gi) * 2 + 0] = s1[gi];
+    }
+    __syncthreads();
+    const float inv_cnt = 1.0f / ((float)p.HW * (float)p.Cg);
+#pragma unroll
+    for (int gi = 0; gi < 4; ++gi) { // <= 4 groups per channel set (sw / Cg, asserted on the host)
+        float a = 0.f;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) a += red[(w * 4 + gi) * 2 + 0];
+        mu[gi] = a * inv_cnt;
+    }
     for (int i = tid; i < total; i += NT) {
         const int pix = i / cps, cc = i - pix * cps;
         float v[8];
@@ -275,36 +323,26 @@ __global__ __launch_bounds__(NT) void gn_small_kernel(const GnP p, int sw) {
             const int g = gidx[cc * 8 + e];
 #pragma unroll
             for (int gi = 0; gi < 4; ++gi) {
-                const float d = g == gi ? v[e] - shf[gi] : 0.f;
-                s1[gi] += d;
+                const float d = g == gi ? v[e] - mu[gi] : 0.f;
                 s2[gi] += d * d;
             }
         }
     }
 #pragma unroll
     for (int gi = 0; gi < 4; ++gi) {
-        s1[gi] = wave_sum(s1[gi]);
         s2[gi] = wave_sum(s2[gi]);
-        if (lane == 0) {
-            red[(wave * 4 + gi) * 2 + 0] = s1[gi];
-            red[(wave * 4 + gi) * 2 + 1] = s2[gi];
-        }
+        if (lane == 0) red[(wave * 4 + gi) * 2 + 1] = s2[gi];
     }
     __syncthreads();
-    const float inv_cnt = 1.0f / ((float)p.HW * (float)p.Cg);
     for (int c = tid; c < sw; c += NT) {
         const int gi = gidx[c];
-        float a = 0.f, b = 0.f;
+        float b = 0.f;
 #pragma unroll
-        for (int w = 0; w < NWV; ++w) {
-            a += red[(w * 4 + gi) * 2 + 0];
-            b += red[(w * 4 + gi) * 2 + 1];
-        }
-        const float md = a * inv_cnt;
-        float var = b * inv_cnt - md * md;
-        var = var < 0.f ? 0.f : var;
-        const float mean = (float)slab[gi * p.Cg] + md;
-        const float rstd = rsqrt_fast(var + p.eps);
+        for (int w = 0; w < NWV; ++w) b += red[(w * 4 + gi) * 2 + 1];
+        float mean = mu[0];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) mean = gi == q ? mu[q] : mean; // (no dynamic index into a register array)
+        const float rstd = rsqrt_fast(b * inv_cnt + p.eps);
         const int ch = cbase + c;
         const float w = c == tid ? pw : (p.w ? p.w[ch] : 1.0f), bb = c == tid ? pb : (p.b ? p.b[ch] : 0.0f);
         sc[c] = rstd * w;
@@ -634,7 +672,7 @@ static bool gn_group_try(const GnP& p, const GnRed* red, hipStream_t st) {
 // 20 of every 640 bytes, so that kernel fetches 6x the bytes it uses): both passes read whole pixel rows (16-byte lanes,
 // every CU busy), thread t owns chunk t % cp of the row (its 8 channels, their <= 2 groups and their affine parameters
 // are fixed), all loads of a pass are issued before the first use, and both reductions run in a fixed order
-// (bit-reproducible).  Statistics: shifted sums per (image, pixel chunk, group) -> workspace; apply: every workgroup
+// (bit-reproducible).  Statistics: (mean, M2) per (image, pixel chunk, group) -> workspace; apply: every workgroup
 // re-reduces the short partial list (8 lanes per group + shuffles), builds scale / shift in LDS and streams its pixels.
 struct Gn2P {
     const f16* x0;
@@ -642,8 +680,7 @@ struct Gn2P {
     f16* y;
     const float* w;
     const float* b;
-    float* partial; // [N][nchunks][G][2]
-    float* shift;   // [N][G]
+    float* partial; // [N][nchunks][G][2]: mean, M2
     int HW, C0, C1, C, G, Cg, cp, rp; // cp = 16-byte chunks per pixel row, rp = pixel rows per pass (256 / cp)
     int nchunks, ppc;                 // statistics pass: pixel chunks per image, pixels per chunk
     int ppb;                          // apply pass: pixels per workgroup
@@ -655,6 +692,96 @@ SDOD_DEVICE const f16* gn2_src(const Gn2P& p, size_t row, int c) {
     return c < p.C0 ? p.x0 + row * p.C0 + c : p.x1 + row * p.C1 + (c - p.C0);
 }
 
+// Moments of the <= 2 groups of a thread's 8-channel chunk (A: channels [0, eb), B: the rest) over the vectors it holds, in
+// one pass of sums shifted by the thread's OWN first value of each group (taken from the first batch): the rounding of
+// sum d^2 - (sum d)^2 / k is then at most ~k * 2^-24 of the thread's M2 (k = the thread's values, <= 1024), and an outlier only
+// weighs on the thread that holds it.  (An exact second pass over the registers, or a pairwise merge per batch, doubles the
+// live registers of the one-launch grid kernel.)
+struct GnThreadSums {
+    float pa = 0.f, pb = 0.f, a1 = 0.f, a2 = 0.f, b1 = 0.f, b2 = 0.f;
+    int n = 0; // vectors (pixels) added
+};
+// add K vectors, of which the first nk are pixels of the thread; `first`: the thread's first batch (its pilots)
+template <int K>
+SDOD_DEVICE void gn_thread_add(GnThreadSums& t, const f16x8 (&v)[K], int nk, int eb, bool first) {
+    if (first) {
+        t.pa = (float)v[0][0];
+#pragma unroll
+        for (int e = 1; e < 8; ++e) t.pb = e == eb ? (float)v[0][e] : t.pb; // (no dynamic index into a register vector)
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const bool inA = e < eb;
+            const float d = k < nk ? (float)v[k][e] - (inA ? t.pa : t.pb) : 0.f;
+            t.a1 += inA ? d : 0.f; t.a2 += inA ? d * d : 0.f;
+            t.b1 += inA ? 0.f : d; t.b2 += inA ? 0.f : d * d;
+        }
+    t.n += nk;
+}
+// -> red[0..3] = mean, M2 of group A, then of group B
+SDOD_DEVICE void gn_thread_moments(const GnThreadSums& t, int eb, float* red) {
+    const float na = (float)(t.n * eb), nb = (float)(t.n * (8 - eb));
+    const float ma = na > 0.f ? t.a1 / na : 0.f, mb = nb > 0.f ? t.b1 / nb : 0.f;
+    red[0] = t.pa + ma;
+    red[1] = fmaxf(0.f, t.a2 - t.a1 * ma);
+    red[2] = t.pb + mb;
+    red[3] = fmaxf(0.f, t.b2 - t.b1 * mb);
+}
+
+// (mean, M2) of group g over a workgroup's per-thread moments in LDS: red[tid * 4] = mean, M2 of the thread's first group, then
+// of its second; thread tid = r * cp + j owns 16-byte chunk j of pixel rows r, r + rp, ... of the workgroup's npix pixels.
+// The 16 lanes l of an aligned lane group share the group's entries (chunks x rows) and combine them with two group sums
+// (fixed order); every lane gets the result.
+SDOD_DEVICE GnMom gn_rows_combine16(const float* red, int g, int l, int cg, int cp, int rp, int npix) {
+    const int j0 = (g * cg) >> 3, j1 = ((g + 1) * cg - 1) >> 3;
+    const int ne = (j1 - j0 + 1) * rp;
+    const int full = npix / rp, rem = npix - full * rp; // row r covered full + (r < rem) pixels
+    const float cnt = (float)max(npix, 0) * (float)cg;
+    float s = 0.f, m2 = 0.f;
+    for (int pass = 0; pass < 2; ++pass) {
+        const float mean = pass ? s / cnt : 0.f;
+        float acc = 0.f;
+        for (int e = l; e < ne && npix > 0; e += 16) {
+            const int jj = j0 + e / rp, r = e - (jj - j0) * rp;
+            const int first = (jj * 8) / cg;          // group of the chunk's first channel
+            const int slot = first == g ? 0 : 2;      // else g is the chunk's second group
+            const int eb = min(8, (first + 1) * cg - jj * 8);
+            const float nr = (float)(full + (r < rem ? 1 : 0)) * (float)(slot == 0 ? eb : 8 - eb);
+            const float* en = red + (r * cp + jj) * 4 + slot;
+            if (pass == 0) acc += nr * en[0];
+            else {
+                const float d = en[0] - mean;
+                acc += en[1] + nr * d * d;
+            }
+        }
+        acc = group_sum<16>(acc);
+        if (pass == 0) s = acc;
+        else m2 = acc;
+    }
+    return {cnt, npix > 0 ? s / cnt : 0.f, m2};
+}
+
+// running sums of (n, mean, M2) partials shifted by the first partial's mean (one division at the end, not one per partial): a
+// partial's mean averages many values, so the partials' means are close to each other and the shift costs no accuracy
+struct GnPartialSums {
+    float n = 0.f, ref = 0.f, s1 = 0.f, s2 = 0.f;
+    SDOD_DEVICE void add(float ni, float mean, float m2) {
+        if (ni == 0.f) return;
+        if (n == 0.f) ref = mean;
+        const float d = mean - ref;
+        n += ni;
+        s1 += ni * d;
+        s2 += m2 + ni * d * d;
+    }
+    SDOD_DEVICE GnMom moments() const {
+        if (n == 0.f) return {0.f, 0.f, 0.f};
+        const float md = s1 / n;
+        return {n, ref + md, fmaxf(0.f, s2 - s1 * md)};
+    }
+};
+
 __global__ __launch_bounds__(256) void gn2_stats_kernel(const Gn2P p) {
     __shared__ float red[256 * 4];
     const int n = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
@@ -664,47 +791,29 @@ __global__ __launch_bounds__(256) void gn2_stats_kernel(const Gn2P p) {
     const int gA = c0 / p.Cg;
     const int eb = min(8, (gA + 1) * p.Cg - c0); // channels [0, eb) of the chunk belong to group gA, the rest to gA + 1
     const size_t row0 = (size_t)n * p.HW;
-    const float shA = (float)*gn2_src(p, row0, gA * p.Cg);
-    const float shB = eb < 8 ? (float)*gn2_src(p, row0, (gA + 1) * p.Cg) : 0.f;
-    const int pix_end = min(p.HW, (chunk + 1) * p.ppc);
-    float a1 = 0.f, a2 = 0.f, b1 = 0.f, b2 = 0.f;
-    for (int pix0 = chunk * p.ppc + r0; pix0 < pix_end; pix0 += 8 * p.rp) { // one trip for the UNet's maps (ppc <= 8 rp)
+    const int pix_begin = chunk * p.ppc, pix_end = min(p.HW, (chunk + 1) * p.ppc);
+    GnThreadSums ts;
+    for (int pix0 = pix_begin + r0; pix0 < pix_end; pix0 += 8 * p.rp) { // one trip for the UNet's maps (ppc <= 8 rp)
         f16x8 v[8];
+        int nk = 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int pix = pix0 + k * p.rp;
-            v[k] = (active && pix < pix_end) ? ldg8(gn2_src(p, row0 + pix, c0)) : zero8();
+            const bool ok = active && pix < pix_end;
+            v[k] = ok ? ldg8(gn2_src(p, row0 + pix, c0)) : zero8();
+            nk = ok ? k + 1 : nk;
         }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const bool ok = active && (pix0 + k * p.rp) < pix_end;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const bool inA = e < eb;
-                const float d = ok ? (float)v[k][e] - (inA ? shA : shB) : 0.f;
-                a1 += inA ? d : 0.f; a2 += inA ? d * d : 0.f;
-                b1 += inA ? 0.f : d; b2 += inA ? 0.f : d * d;
-            }
-        }
+        gn_thread_add<8>(ts, v, nk, eb, pix0 == pix_begin + r0);
     }
-    red[tid * 4 + 0] = a1; red[tid * 4 + 1] = a2; red[tid * 4 + 2] = b1; red[tid * 4 + 3] = b2;
+    gn_thread_moments(ts, eb, red + tid * 4);
     __syncthreads();
-    if (tid < p.G) {
-        const int g = tid;
-        const int j0 = (g * p.Cg) >> 3, j1 = ((g + 1) * p.Cg - 1) >> 3;
-        float s1 = 0.f, s2 = 0.f;
-        for (int jj = j0; jj <= j1; ++jj) {
-            const int first = (jj * 8) / p.Cg;      // group of the chunk's first channel
-            const int slot = first == g ? 0 : 2;    // else g is the chunk's second group
-            for (int r = 0; r < p.rp; ++r) {
-                s1 += red[(r * p.cp + jj) * 4 + slot];
-                s2 += red[(r * p.cp + jj) * 4 + slot + 1];
-            }
+    for (int g = tid >> 4; g < p.G; g += 16) {
+        const GnMom m = gn_rows_combine16(red, g, tid & 15, p.Cg, p.cp, p.rp, pix_end - pix_begin);
+        if ((tid & 15) == 0) {
+            float* dst = p.partial + (((size_t)n * p.nchunks + chunk) * p.G + g) * 2;
+            dst[0] = m.mean;
+            dst[1] = m.m2;
         }
-        float* dst = p.partial + (((size_t)n * p.nchunks + chunk) * p.G + g) * 2;
-        dst[0] = s1;
-        dst[1] = s2;
-        if (chunk == 0) p.shift[(size_t)n * p.G + g] = (float)*gn2_src(p, row0, g * p.Cg);
     }
 }
 
@@ -715,25 +824,22 @@ __global__ __launch_bounds__(256) void gn2_apply_kernel(const Gn2P p) {
     float* gm = sh + p.C;
     float* gr = gm + p.G;
     const int n = blockIdx.y, tid = threadIdx.x;
-    // (1) mean / rstd of every group from the per-chunk partials: 8 lanes per group, fixed order
+    // (1) mean / rstd of every group from the per-chunk (mean, M2): 8 lanes per group, fixed order
     for (int g = tid >> 3; g < p.G; g += 32) {
         const int l = tid & 7;
-        float a = 0.f, b = 0.f;
+        GnPartialSums ps;
         for (int ch = l; ch < p.nchunks; ch += 8) {
             const float* src = p.partial + (((size_t)n * p.nchunks + ch) * p.G + g) * 2;
-            a += src[0];
-            b += src[1];
+            ps.add((float)(min(p.HW, (ch + 1) * p.ppc) - ch * p.ppc) * (float)p.Cg, src[0], src[1]);
         }
-        a = oct_sum(a);
-        b = oct_sum(b);
+        const GnMom m = ps.moments();
+        const float cnt = (float)p.HW * (float)p.Cg;
+        const float mean = oct_sum(m.n * m.mean) / cnt;
+        const float d = m.mean - mean;
+        const float m2 = oct_sum(m.m2 + m.n * d * d);
         if (l == 0) {
-            const float cnt = (float)p.HW * (float)p.Cg;
-            const float icnt = __builtin_amdgcn_rcpf(cnt);
-            const float md = a * icnt;
-            float var = b * icnt - md * md;
-            var = var < 0.f ? 0.f : var;
-            gm[g] = p.shift[(size_t)n * p.G + g] + md;
-            gr[g] = rsqrt_fast(var + p.eps);
+            gm[g] = mean;
+            gr[g] = rsqrt_fast(m2 / cnt + p.eps);
         }
     }
     __syncthreads();
@@ -791,7 +897,7 @@ static bool gn2_fits(int c0, int c1, int groups) {
 static void gn2_launch(const GnP& q, hipStream_t st) {
     Gn2P p{};
     p.x0 = (const f16*)q.x0; p.x1 = (const f16*)q.x1; p.y = (f16*)q.y; p.w = q.w; p.b = q.b;
-    p.partial = q.partial; p.shift = q.shift;
+    p.partial = q.partial;
     p.HW = q.HW; p.C0 = q.C0; p.C1 = q.C1; p.C = q.C; p.G = q.G; p.Cg = q.Cg; p.eps = q.eps; p.silu = q.silu;
     p.cp = q.C / 8;
     p.rp = 256 / p.cp;
@@ -820,7 +926,7 @@ constexpr int GN_MAX_CHUNKS_GRID = 256;
 //   N*G = 64 workgroups (18-33 us for 10-30 MB); two launches that each read whole rows pay the launch + first-byte latency
 //   twice (the lean pair above: no faster).  Here one launch covers the chip with one workgroup per CU, image n owning
 //   wpi = (#CUs / N) of them; a workgroup loads its ppw pixels x C channels into REGISTERS (16-byte lanes, all loads in
-//   flight at once), reduces shifted sums per group, publishes them, meets the other workgroups at a grid barrier, reduces
+//   flight at once), reduces (mean, M2) per group, publishes them, meets the other workgroups at a grid barrier, reduces
 //   the wpi partials of its image in a fixed order (bit-reproducible), and normalises + stores from the registers.
 //   HBM/L2 traffic: x once, y once.
 //   Grid barrier: a small counter tree + generation words in the caller's workspace (sdod_group_norm_workspace_bytes;
@@ -867,49 +973,32 @@ __global__ __launch_bounds__(512) void gn_grid_kernel(const GnGridP p) {
     const size_t row0 = (size_t)n * p.HW;
     auto src = [&](size_t row, int c) { return c < p.C0 ? p.x0 + row * p.C0 + c : p.x1 + row * p.C1 + (c - p.C0); };
     const int pix_begin = wi * p.ppw, pix_end = min(p.HW, pix_begin + p.ppw);
-    // pilot shift: the image's first pixel (read by every workgroup before any of them stores: y may be x)
-    const float shA = active ? (float)*src(row0, gA * p.Cg) : 0.f;
-    const float shB = (active && eb < 8) ? (float)*src(row0, (gA + 1) * p.Cg) : 0.f;
-    float pilot = 0.f;
-    if (tid < p.G) pilot = (float)*src(row0, tid * p.Cg);
     // nloop == 1: the workgroup's pixels stay in registers between the two phases.  nloop > 1 (the VAE's 512x512 maps: more than
     // KMAX vectors per thread): the statistics phase streams them KMAX at a time and the apply phase reads them again -- from
     // the Infinity Cache, which holds the whole map -- still ONE launch instead of the statistics + apply pair.
+    // Statistics: per-thread moments of the registers (gn_thread_add / gn_thread_moments), then per group over the workgroup
+    // (gn_rows_combine16); the workgroup publishes (mean, M2) of each group of its image.
     const int nloop = p.nloop;
     f16x8 v[KMAX];
-    float a1 = 0.f, a2 = 0.f, b1 = 0.f, b2 = 0.f;
+    GnThreadSums ts;
     for (int l = 0; l < nloop; ++l) {
+        int nk = 0;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
             const int pix = pix_begin + r0 + (l * KMAX + k) * p.rp;
-            v[k] = (active && pix < pix_end) ? ldg8(src(row0 + pix, c0)) : zero8();
+            const bool ok = active && pix < pix_end;
+            v[k] = ok ? ldg8(src(row0 + pix, c0)) : zero8();
+            nk = ok ? k + 1 : nk;
         }
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-            const bool ok = active && (pix_begin + r0 + (l * KMAX + k) * p.rp) < pix_end;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const bool inA = e < eb;
-                const float d = ok ? (float)v[k][e] - (inA ? shA : shB) : 0.f;
-                a1 += inA ? d : 0.f; a2 += inA ? d * d : 0.f;
-                b1 += inA ? 0.f : d; b2 += inA ? 0.f : d * d;
-            }
-        }
+        gn_thread_add<KMAX>(ts, v, nk, eb, l == 0);
     }
-    red[tid * 4 + 0] = a1; red[tid * 4 + 1] = a2; red[tid * 4 + 2] = b1; red[tid * 4 + 3] = b2;
+    gn_thread_moments(ts, eb, red + tid * 4);
     __syncthreads();
-    if (tid < p.G) {
-        const int g = tid;
-        const int j0 = (g * p.Cg) >> 3, j1 = ((g + 1) * p.Cg - 1) >> 3;
-        float s1 = 0.f, s2 = 0.f;
-        for (int jj = j0; jj <= j1; ++jj) {
-            const int first = (jj * 8) / p.Cg;      // group of the chunk's first channel
-            const int slot = first == g ? 0 : 2;    // else g is the chunk's second group
-            for (int r = 0; r < p.rp; ++r) {
-                s1 += red[(r * p.cp + jj) * 4 + slot];
-                s2 += red[(r * p.cp + jj) * 4 + slot + 1];
-            }
-        }
+    // 16 lanes per group (G <= 32: every group has its lanes); lanes of no group read nothing (npix 0)
+    const GnMom mg = gn_rows_combine16(red, tid >> 4, tid & 15, p.Cg, p.cp, p.rp, (tid >> 4) < p.G ? pix_end - pix_begin : 0);
+    if ((tid & 15) == 0 && (tid >> 4) < p.G) {
+        const int g = tid >> 4;
+        const float s1 = mg.mean, s2 = mg.m2;
         // cross-XCD hand-off WITHOUT fences (an agent-scope release writes back the whole L2 -- the previous GEMM's output --
         // and cost ~35 us here): the payload is stored write-through (sc1: 8-byte agent-scope atomics, both sides), every storing
         // wave waits for its stores, then ONE lane signals; readers poll the generation word with sc1 loads and read the
@@ -962,34 +1051,31 @@ __global__ __launch_bounds__(512) void gn_grid_kernel(const GnGridP p) {
         }
     }
     __syncthreads();
-    // ---- mean / rstd of every group of this image: 16 lanes per group, fixed order
+    // ---- mean / rstd of every group of this image: 16 lanes per group, each sums its workgroups' (mean, M2) shifted by the
+    // first one (GnPartialSums), then two sums over the 16 lanes; fixed order
     {
         const int g = tid >> 4, l = tid & 15;
-        float a = 0.f, b = 0.f;
+        GnPartialSums ps;
         if (g < p.G) {
             for (int ch = l; ch < p.wpi; ch += 16) {
                 const unsigned long long bits = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p.partial) + ((size_t)n * p.wpi + ch) * p.G + g,
                                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 float2 pr;
                 __builtin_memcpy(&pr, &bits, 8);
-                a += pr.x;
-                b += pr.y;
+                const int np = min(p.HW, (ch + 1) * p.ppw) - ch * p.ppw; // may be <= 0: a workgroup past the image's last pixel
+                ps.add((float)max(0, np) * (float)p.Cg, pr.x, pr.y);
             }
         }
-        a = group_sum<16>(a);
-        b = group_sum<16>(b);
+        const GnMom m = ps.moments();
+        const float cnt = (float)p.HW * (float)p.Cg;
+        const float mean = group_sum<16>(m.n * m.mean) / cnt;
+        const float d = m.mean - mean;
+        const float m2 = group_sum<16>(m.m2 + m.n * d * d);
         if (g < p.G && l == 0) {
-            const float cnt = (float)p.HW * (float)p.Cg;
-            const float icnt = __builtin_amdgcn_rcpf(cnt);
-            const float md = a * icnt;
-            float var = b * icnt - md * md;
-            var = var < 0.f ? 0.f : var;
-            gm[g] = md; // + pilot, added below by the thread that holds it
-            gr[g] = rsqrt_fast(var + p.eps);
+            gm[g] = mean;
+            gr[g] = rsqrt_fast(m2 / cnt + p.eps);
         }
     }
-    __syncthreads();
-    if (tid < p.G) gm[tid] += pilot;
     __syncthreads();
     for (int c = tid; c < p.C; c += 512) {
         const int g = c / p.Cg;
@@ -1147,25 +1233,40 @@ static int gn_path_override() {
     }();
     return v;
 }
-static bool gn_prefer_pair(const GnP& p) {
+static bool gn_prefer_pair() {
     if (gn_path_override() == 1) return false;
     // Measured on MI355X (profiles/r02_gn_bench.txt): the pair is no faster than the group kernel where it was meant to win
     // (64x64 x 320 channels: 18.9 vs 18.4 us) and 2-3x slower on small maps, so it is never chosen by default.
     return gn_path_override() == 2;
 }
 
+// the statistics + apply pair: a thread owns 8 channels of every pass over a pixel row, <= 2 passes of <= 256 threads
+static bool gn_pair_fits(int c) {
+    const int cp = c / 8, npass = (cp + 255) / 256;
+    return c % 8 == 0 && npass <= 2 && cp % npass == 0;
+}
+
+// THE plan of sdod_group_norm_nhwc, also what sdod_group_norm_path reports: 0 = the one-launch grid-barrier kernel (fp16 maps
+// >= 5 MB), 1 = the (image, group) kernel (fp16), 2 = the small-map LDS kernel, 3 = statistics + apply (the lean fp16 pair
+// under SDOD_GN_PATH=two), -1 = no kernel takes the shape (the entry point refuses it before any launch)
+static int gn_plan(int n, int hw, int c0, int c1, int groups, int dtype) {
+    const int c = c0 + c1;
+    if (n <= 0 || hw <= 0 || c0 <= 0 || c1 < 0 || groups <= 0 || c % groups || c0 % 8 || c1 % 8) return -1;
+    if (dtype != SDOD_F16 && dtype != SDOD_F32) return -1;
+    const bool h = dtype == SDOD_F16;
+    if (h && groups <= 32 && gn2_fits(c0, c1, groups) && gn_prefer_pair()) return 3;
+    if (h && gn_path_override() == 0 && gn_grid_plan(n, hw, c0, c1, groups, nullptr)) return 0;
+    if (h && gn_group_plan(hw, c0, c1, c / groups, false).v) return 1;
+    if (gn_small_fits(hw, c, c / groups, h ? 2 : 4)) return 2;
+    return gn_pair_fits(c) ? 3 : -1;
+}
+
+// path 3: statistics (+ collapse) + apply
 template <typename T>
-void gn_launch(GnP& p, hipStream_t st) {
-    if (sizeof(T) == 2 && p.G <= 32 && gn2_fits(p.C0, p.C1, p.G) && gn_prefer_pair(p)) {
-        gn2_launch(p, st);
-        return;
-    }
-    if (sizeof(T) == 2 && gn_path_override() == 0 && gn_grid_try(p, st)) return;
-    if (sizeof(T) == 2 && gn_group_try(p, nullptr, st)) return;
-    if (gn_try_small<T>(p, st)) return;
+bool gn_pair_launch(GnP& p, hipStream_t st) {
+    if (!gn_pair_fits(p.C)) return false;
     const int cp = p.C / 8;
     p.npass = (cp + 255) / 256;
-    SDOD_REQUIRE(p.npass <= 2 && cp % p.npass == 0, "unsupported channel count for GroupNorm");
     p.cpp = cp / p.npass;
     p.pp = 256 / p.cpp;
     if (p.pp < 1) p.pp = 1;
@@ -1178,10 +1279,12 @@ void gn_launch(GnP& p, hipStream_t st) {
         SDOD_LAUNCH((gn_stats_kernel<T, 2>), sgrid, sblock, smem_stats, st, p);
     SDOD_HIP_CHECK(hipGetLastError());
     if (p.nchunks > GN_INLINE_CHUNKS) {
-        SDOD_LAUNCH(gn_collapse_kernel, dim3((p.G + 3) / 4, p.N), dim3(256), 0, st, p.partial, p.stats, p.nchunks, p.G);
+        SDOD_LAUNCH(gn_collapse_kernel, dim3((p.G + 3) / 4, p.N), dim3(256), 0, st, p.partial, p.stats, p.nchunks, p.G, p.pix_per_chunk,
+                    p.HW, p.Cg);
         SDOD_HIP_CHECK(hipGetLastError());
         p.partial = p.stats; // [N][1][G][2]
         p.nchunks = 1;
+        p.pix_per_chunk = p.HW;
     }
     const size_t total = (size_t)p.HW * cp;
     int bx = (int)((total + 255) / 256);
@@ -1189,6 +1292,26 @@ void gn_launch(GnP& p, hipStream_t st) {
     if (bx > cap) bx = cap;
     SDOD_LAUNCH((gn_apply_kernel<T>), dim3(bx, p.N), dim3(256), ((size_t)p.C * 2 + (size_t)p.G * 2) * sizeof(float), st, p);
     SDOD_HIP_CHECK(hipGetLastError());
+    return true;
+}
+
+template <typename T>
+void gn_launch(GnP& p, int path, hipStream_t st) {
+    bool launched = false;
+    switch (path) {
+    case 0: launched = sizeof(T) == 2 && gn_grid_try(p, st); break;
+    case 1: launched = sizeof(T) == 2 && gn_group_try(p, nullptr, st); break;
+    case 2: launched = gn_try_small<T>(p, st); break;
+    case 3:
+        if (sizeof(T) == 2 && p.G <= 32 && gn2_fits(p.C0, p.C1, p.G) && gn_prefer_pair()) {
+            gn2_launch(p, st);
+            launched = true;
+        } else {
+            launched = gn_pair_launch<T>(p, st);
+        }
+        break;
+    }
+    SDOD_REQUIRE(launched, "internal error: the GroupNorm plan chose a kernel that does not take the shape");
 }
 
 constexpr int GN_MAX_CHUNKS = 1024;
@@ -1321,7 +1444,7 @@ __global__ __launch_bounds__(256) void compose_linear_kernel(const f16* __restri
 // fp16 / bf16 / fp32.
 //   * slabs up to 32 Ki elements: ONE launch, a 512-thread workgroup per (image, group) holds its slab in registers (read
 //     once), exact two-pass mean / variance by block reductions, normalise (+ SiLU) + store;
-//   * bigger slabs: statistics launch (grid: slabs x chunks, shifted sums, one partial per workgroup -- no atomics, fixed
+//   * bigger slabs: statistics launch (grid: slabs x chunks, (mean, M2) of each chunk -- no atomics, fixed
 //     reduction order) + apply launch (every workgroup re-reduces the <= 64 partials of its slab).
 struct GnNchwP {
     const void* x;
@@ -1474,58 +1597,80 @@ __global__ __launch_bounds__(512) void gn_nchw_one_kernel(const GnNchwP p) {
     }
 }
 
+// Big slabs: grid (slabs, chunks), so that every slab count the entry point admits fits grid.x.  The statistics workgroup
+// of a chunk leaves (mean, M2) of its chunk in the workspace: each thread takes its elements 8 steps at a time, in registers,
+// and folds their exact two-pass moments into its own (gn_merge); the threads' moments then combine by two block sums.
+// Nothing of x but the chunk itself is read, so y may be x: the apply pass needs no element another workgroup writes.
 template <typename T, bool VEC>
 __global__ __launch_bounds__(512) void gn_nchw_stats_kernel(const GnNchwP p) {
     __shared__ float red[8];
-    const long long slab = blockIdx.y;
+    constexpr int W = VEC ? 8 : 1, KB = 8; // elements per step, steps per batch
+    const long long slab = blockIdx.x;
     const long long base = slab * p.L;
-    const long long i0 = (long long)blockIdx.x * p.per_chunk, i1 = min(p.L, i0 + p.per_chunk);
-    const float shift = NchwIo<T>::ld(p.x, base); // pilot: the slab's first element (shifted sums keep fp32 accurate)
-    float s1 = 0.f, s2 = 0.f;
-    if constexpr (VEC) { // per_chunk is a multiple of 8
-        for (long long i = i0 + (long long)threadIdx.x * 8; i < i1; i += 512 * 8) {
-            float v[8];
-            NchwIo<T>::ld8(p.x, base + i, v);
+    const long long i0 = (long long)blockIdx.y * p.per_chunk, i1 = min(p.L, i0 + p.per_chunk);
+    GnMom acc = {0.f, 0.f, 0.f};
+    for (long long ib = i0 + (long long)threadIdx.x * W; ib < i1; ib += (long long)KB * 512 * W) {
+        float v[KB][W];
+        int nk = 0; // steps of this batch inside the chunk (a prefix: per_chunk is a multiple of 8)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float d = v[e] - shift;
-                s1 += d;
-                s2 += d * d;
+        for (int k = 0; k < KB; ++k) {
+            const long long i = ib + (long long)k * 512 * W;
+            if (i < i1) {
+                if constexpr (VEC) NchwIo<T>::ld8(p.x, base + i, v[k]);
+                else v[k][0] = NchwIo<T>::ld(p.x, base + i);
+                nk = k + 1;
+            } else {
+#pragma unroll
+                for (int e = 0; e < W; ++e) v[k][e] = 0.f;
             }
         }
-    } else {
-        for (long long i = i0 + threadIdx.x; i < i1; i += 512) {
-            const float d = NchwIo<T>::ld(p.x, base + i) - shift;
-            s1 += d;
-            s2 += d * d;
-        }
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < KB; ++k)
+#pragma unroll
+            for (int e = 0; e < W; ++e) s += v[k][e];
+        GnMom b;
+        b.n = (float)(nk * W);
+        b.mean = s / b.n;
+        b.m2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < KB; ++k)
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const float d = k < nk ? v[k][e] - b.mean : 0.f;
+                b.m2 += d * d;
+            }
+        acc = gn_merge(acc, b);
     }
-    s1 = block_sum_512(s1, red);
-    s2 = block_sum_512(s2, red);
+    const float cnt = (float)(i1 - i0);
+    const float mean = block_sum_512(acc.n * acc.mean, red) / cnt;
+    const float d = acc.mean - mean;
+    const float m2 = block_sum_512(acc.m2 + acc.n * d * d, red);
     if (threadIdx.x == 0) {
-        float* dst = p.partial + (slab * p.chunks + blockIdx.x) * 2;
-        dst[0] = s1;
-        dst[1] = s2;
+        float* dst = p.partial + (slab * p.chunks + blockIdx.y) * 2;
+        dst[0] = mean;
+        dst[1] = m2;
     }
 }
 
 template <typename T, bool VEC>
 __global__ __launch_bounds__(512) void gn_nchw_apply_kernel(const GnNchwP p) {
-    const long long slab = blockIdx.y;
+    const long long slab = blockIdx.x;
     const int g = (int)(slab % p.G);
     const long long base = slab * p.L;
-    float s1 = 0.f, s2 = 0.f;
-    for (int c = 0; c < p.chunks; ++c) { // every thread, same order: bit-reproducible
-        const float* src = p.partial + (slab * p.chunks + c) * 2;
-        s1 += src[0];
-        s2 += src[1];
+    // the slab's moments from its chunks' (mean, M2): every thread, same order (bit-reproducible), two plain sums
+    const float* part = p.partial + slab * p.chunks * 2;
+    auto chunk_n = [&](int c) { return (float)(min(p.L, (long long)(c + 1) * p.per_chunk) - (long long)c * p.per_chunk); };
+    float s = 0.f;
+    for (int c = 0; c < p.chunks; ++c) s += chunk_n(c) * part[c * 2];
+    const float mean = s / (float)p.L;
+    float m2 = 0.f;
+    for (int c = 0; c < p.chunks; ++c) {
+        const float d = part[c * 2] - mean;
+        m2 += part[c * 2 + 1] + chunk_n(c) * d * d;
     }
-    const float shift = NchwIo<T>::ld(p.x, base);
-    const float md = s1 / (float)p.L;
-    float var = s2 / (float)p.L - md * md;
-    var = var < 0.f ? 0.f : var;
-    const float mean = shift + md, rstd = rsqrt_fast(var + p.eps);
-    const long long i0 = (long long)blockIdx.x * p.per_chunk, i1 = min(p.L, i0 + p.per_chunk);
+    const float rstd = rsqrt_fast(m2 / (float)p.L + p.eps);
+    const long long i0 = (long long)blockIdx.y * p.per_chunk, i1 = min(p.L, i0 + p.per_chunk);
     if constexpr (VEC) {
         for (long long i = i0 + (long long)threadIdx.x * 8; i < i1; i += 512 * 8) {
             float v[8];
@@ -1560,9 +1705,9 @@ static void gn_nchw_launch_v(const GnNchwP& p, long long slabs, hipStream_t st) 
         SDOD_HIP_CHECK(hipGetLastError());
         return;
     }
-    SDOD_LAUNCH((gn_nchw_stats_kernel<T, VEC>), dim3(p.chunks, (unsigned)slabs), dim3(512), 0, st, p);
+    SDOD_LAUNCH((gn_nchw_stats_kernel<T, VEC>), dim3((unsigned)slabs, p.chunks), dim3(512), 0, st, p);
     SDOD_HIP_CHECK(hipGetLastError());
-    SDOD_LAUNCH((gn_nchw_apply_kernel<T, VEC>), dim3(p.chunks, (unsigned)slabs), dim3(512), 0, st, p);
+    SDOD_LAUNCH((gn_nchw_apply_kernel<T, VEC>), dim3((unsigned)slabs, p.chunks), dim3(512), 0, st, p);
     SDOD_HIP_CHECK(hipGetLastError());
 }
 
@@ -1597,23 +1742,13 @@ extern "C" int sdod_ln_fold_f16(void* w, int n, int k, int ldw, const float* gam
 }
 
 extern "C" int sdod_group_norm_launches(int hw, int c, int groups, int dtype) {
-    if (hw <= 0 || c <= 0 || groups <= 0 || c % groups) return 0;
-    if (dtype == SDOD_F16 && groups <= 32 && gn2_fits(c, 0, groups) && gn_path_override() == 2) return 2;
-    if (dtype == SDOD_F16 && c % 8 == 0 && gn_group_plan(hw, c, 0, c / groups, false).v && gn_path_override() != 2) return 1;
-    if (dtype == SDOD_F16 && gn_path_override() == 0 && gn_grid_plan(2, hw, c, 0, groups, nullptr)) return 1;
-    return gn_small_fits(hw, c, c / groups, dtype == SDOD_F16 ? 2 : 4) ? 1 : 2; // (+1 collapse launch on very large maps)
+    const int path = gn_plan(2, hw, c, 0, groups, dtype);
+    return path < 0 ? 0 : path == 3 ? 2 : 1; // (+1 collapse launch on very large maps)
 }
 
 // which kernel sdod_group_norm_nhwc launches for this shape: 0 = the one-launch grid-barrier kernel (big maps), 1 = the (image,
-// group) one-launch kernel, 2 = the small-map LDS kernel, 3 = statistics + apply (two or three launches)
-extern "C" int sdod_group_norm_path(int n, int hw, int c0, int c1, int groups, int dtype) {
-    const int c = c0 + c1;
-    if (n <= 0 || hw <= 0 || c <= 0 || groups <= 0 || c % groups) return -1;
-    if (dtype == SDOD_F16 && groups <= 32 && gn2_fits(c0, c1, groups) && gn_path_override() == 2) return 3;
-    if (dtype == SDOD_F16 && gn_path_override() == 0 && gn_grid_plan(n, hw, c0, c1, groups, nullptr)) return 0;
-    if (dtype == SDOD_F16 && c0 % 8 == 0 && c1 % 8 == 0 && gn_group_plan(hw, c0, c1, c / groups, false).v && gn_path_override() != 2) return 1;
-    return gn_small_fits(hw, c, c / groups, dtype == SDOD_F16 ? 2 : 4) ? 2 : 3;
-}
+// group) one-launch kernel, 2 = the small-map LDS kernel, 3 = statistics + apply (two or three launches), -1 = none (refused)
+extern "C" int sdod_group_norm_path(int n, int hw, int c0, int c1, int groups, int dtype) { return gn_plan(n, hw, c0, c1, groups, dtype); }
 
 extern "C" int sdod_group_norm_reduce_ok(int hw, int c0, int c1, int groups) {
     if (hw <= 0 || c0 <= 0 || c1 < 0 || groups <= 0 || (c0 + c1) % groups || c0 % 8 || c1 % 8) return 0;
@@ -1650,7 +1785,8 @@ extern "C" int sdod_group_norm_reduce_nhwc(const sdod_gn_reduce* red, const void
 // Workspace layout (floats): [0, GN_SYNC_FLOATS) the grid barrier's 25 counter lines + the sticky timeout word (line 25), at a
 // FIXED offset in front of everything else, so that no (n, groups) layout of the partials of one call can reach the barrier
 // words another call's layout uses (one grow-only workspace serves every shape of a process); then partial
-// [n][GN_MAX_CHUNKS][groups][2], stats [n][groups][2], shift [n][groups].
+// [n][GN_MAX_CHUNKS][groups][2], stats [n][groups][2], and [n][groups] floats no kernel uses any more (they held the pilot
+// shifts of the earlier shifted-sum statistics; kept so that the layout and the workspace size stay as published).
 constexpr size_t GN_SYNC_FLOATS = 1024;
 extern "C" size_t sdod_group_norm_workspace_bytes(int n, int groups) {
     if (n <= 0 || groups <= 0) return 0;
@@ -1694,6 +1830,9 @@ extern "C" int sdod_group_norm_nhwc(const void* x, const void* x2, void* y, cons
     SDOD_REQUIRE(c0 % 8 == 0 && c1 % 8 == 0, "channel counts must be multiples of 8");
     SDOD_REQUIRE((weight == nullptr) == (bias == nullptr), "weight and bias must both be given or both be null");
     SDOD_REQUIRE(dtype == SDOD_F16 || dtype == SDOD_F32, "dtype must be SDOD_F16 or SDOD_F32");
+    const int path = gn_plan(n, hw, c0, c1, groups, dtype);
+    SDOD_REQUIRE(path >= 0, "unsupported channel count for GroupNorm: no NHWC kernel takes (C, groups) = (" + std::to_string(c) + ", " +
+                                std::to_string(groups) + ") at this map size (sdod_group_norm_path reports -1; use sdod_group_norm_nchw)");
     GnP p{};
     p.x0 = x; p.x1 = x2; p.y = y; p.w = weight; p.b = bias;
     p.N = n; p.HW = hw; p.C0 = c0; p.C1 = c1; p.C = c; p.G = groups; p.Cg = c / groups;
@@ -1716,10 +1855,9 @@ extern "C" int sdod_group_norm_nhwc(const void* x, const void* x2, void* y, cons
     p.sync = workspace; // 26 lines of 128 bytes at the fixed front of the workspace (sdod_group_norm_workspace_bytes)
     p.partial = (float*)workspace + GN_SYNC_FLOATS;
     p.stats = p.partial + (size_t)n * GN_MAX_CHUNKS * groups * 2;
-    p.shift = p.stats + (size_t)n * groups * 2;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == SDOD_F16) gn_launch<f16>(p, st);
-    else gn_launch<float>(p, st);
+    if (dtype == SDOD_F16) gn_launch<f16>(p, path, st);
+    else gn_launch<float>(p, path, st);
     return 0;
     SDOD_CATCH
 }

@@ -31,6 +31,16 @@ def _req(t, dtype=None, name='tensor'):
     return t
 
 
+def _affine(weight, bias, c, device):
+    """fp32 weight and bias for the kernels, which take both or neither: a missing one of the two becomes ones / zeros on the
+    device (F.group_norm accepts either alone)."""
+    if weight is None and bias is None:
+        return None, None
+    weight = torch.ones(c, dtype=torch.float32, device=device) if weight is None else weight.detach().to(torch.float32).contiguous()
+    bias = torch.zeros(c, dtype=torch.float32, device=device) if bias is None else bias.detach().to(torch.float32).contiguous()
+    return weight, bias
+
+
 _ws = {}
 
 
@@ -170,8 +180,7 @@ def group_norm_reduce(desc, n, hw, groups, weight=None, bias=None, eps=1e-5, sil
     c1 = x2.shape[-1] if x2 is not None else 0
     dev = desc._keep[0].device
     y = torch.empty((n, hw, c0 + c1), dtype=torch.float16, device=dev)
-    if weight is not None:
-        weight = weight.detach().to(torch.float32).contiguous(); bias = bias.detach().to(torch.float32).contiguous()
+    weight, bias = _affine(weight, bias, c0 + c1, dev)
     check(lib.sdod_group_norm_reduce_nhwc(ctypes.byref(red), _p(x2), _p(y), _p(weight), _p(bias), n, hw, c0, c1, groups, eps,
                                           1 if silu else 0, _stream()))
     return y
@@ -189,8 +198,7 @@ def group_norm_nhwc(x, groups, weight=None, bias=None, eps=1e-5, silu=False, x2=
         _req(x2, x.dtype, 'x2'); c1 = x2.shape[-1]
     if out is None:
         out = torch.empty(x.shape[:-1] + (c0 + c1,), dtype=x.dtype, device=x.device)
-    if weight is not None:
-        weight = weight.detach().to(torch.float32).contiguous(); bias = bias.detach().to(torch.float32).contiguous()
+    weight, bias = _affine(weight, bias, c0 + c1, x.device)
     ws = workspace(lib.sdod_group_norm_workspace_bytes(n, groups), x.device, 'gn')
     check(lib.sdod_group_norm_nhwc(_p(x), _p(x2), _p(out), _p(weight), _p(bias), n, hw, c0, c1, groups, eps,
                                    1 if silu else 0, 0 if x.dtype == torch.float16 else 1, _p(ws), _stream()))
@@ -200,31 +208,52 @@ def group_norm_nhwc(x, groups, weight=None, bias=None, eps=1e-5, silu=False, x2=
 _NCHW_DTYPES = {torch.float16: 0, torch.float32: 1, torch.bfloat16: 3}
 
 
-def group_norm_nchw(x, groups, weight=None, bias=None, eps=1e-5, silu=False):
+def group_norm_nchw(x, groups, weight=None, bias=None, eps=1e-5, silu=False, out=None):
     """torch-semantics entry used by sdod.EfficientGN: x is [N, C, *] fp16 / bf16 / fp32; returns a tensor of the same shape
-    and memory format.  No layout copy on either side: a channels_last tensor whose channel count the NHWC kernels take IS
-    their layout (the permute is a view); anything else that is dense goes to the NCHW kernel, where a group is one contiguous
-    slab (any channel count); only a tensor that is neither is made contiguous first."""
+    and memory format.  No layout copy where it can be avoided: a channels_last tensor whose shape an NHWC kernel takes
+    (sdod_group_norm_path >= 0) IS their layout (the permute is a view); anything else that is dense goes to the NCHW kernel,
+    where a group is one contiguous slab (any channel count).  A tensor that is neither -- and a channels_last tensor that no
+    NHWC kernel takes (too many channels for their LDS tables) -- is made contiguous first, and a channels_last result is
+    given back in channels_last.  `out` (optional): a tensor of x's shape, dtype and memory format to write, which may be x."""
     if x.dtype not in _NCHW_DTYPES:
         raise TypeError('EfficientGN HIP kernels support float16, bfloat16 and float32')
     n, c = x.shape[0], x.shape[1]
     x = x.detach()
+    lib = _lib.hip()
     if (x.dim() == 4 and c % 8 == 0 and x.dtype != torch.bfloat16 and not x.is_contiguous()
             and x.is_contiguous(memory_format=torch.channels_last)):
-        y = group_norm_nhwc(x.permute(0, 2, 3, 1), groups, weight, bias, eps, silu)     # [N, H, W, C] view -> NHWC kernels
-        return y.permute(0, 3, 1, 2)                                                      # logical NCHW, channels_last strides
-    lib = _lib.hip()
+        hw = x.shape[2] * x.shape[3]
+        if lib.sdod_group_norm_path(n, hw, c, 0, groups, 0 if x.dtype == torch.float16 else 1) >= 0:
+            o = None
+            if out is not None:
+                if not (out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous(memory_format=torch.channels_last)):
+                    raise ValueError('out must match x in shape, dtype and memory format')
+                o = out.permute(0, 2, 3, 1)
+            y = group_norm_nhwc(x.permute(0, 2, 3, 1), groups, weight, bias, eps, silu, out=o)  # [N, H, W, C] view -> NHWC kernels
+            return y.permute(0, 3, 1, 2)                                                      # logical NCHW, channels_last strides
+    back_to_cl = False
     if not x.is_contiguous():
+        back_to_cl = x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
         x = x.contiguous()
     _req(x, None, 'x')
-    out = torch.empty_like(x)
-    if weight is not None:
-        weight = weight.detach().to(torch.float32).contiguous(); bias = bias.detach().to(torch.float32).contiguous()
+    dst = torch.empty_like(x)
+    if out is not None:
+        if out.shape != x.shape or out.dtype != x.dtype:
+            raise ValueError('out must match x in shape and dtype')
+        if out.is_contiguous():
+            dst = out
+        elif not (back_to_cl and out.is_contiguous(memory_format=torch.channels_last)):
+            raise ValueError('out must have the memory format of x')
+    weight, bias = _affine(weight, bias, c, x.device)
     spatial = x.numel() // (n * c)
     ws = workspace(lib.sdod_group_norm_nchw_workspace_bytes(n, groups), x.device, 'gn_nchw')
-    check(lib.sdod_group_norm_nchw(_p(x), _p(out), _p(weight), _p(bias), n, c, spatial, groups, eps, 1 if silu else 0,
+    check(lib.sdod_group_norm_nchw(_p(x), _p(dst), _p(weight), _p(bias), n, c, spatial, groups, eps, 1 if silu else 0,
                                    _NCHW_DTYPES[x.dtype], _p(ws), _stream()))
-    return out
+    if back_to_cl:
+        if out is not None and dst is not out:
+            return out.copy_(dst)
+        return dst.contiguous(memory_format=torch.channels_last)
+    return dst
 
 
 def ln_fold(w, gamma, beta, bias=None):

@@ -13,7 +13,8 @@ What differs, on purpose:
     F.group_norm exactly as the reference's forward does (:11-12).
     NCHW-contiguous inputs (torch's default) run the NCHW kernel (sdod_group_norm_nchw: a group is one contiguous slab --
     no transpose, any channel count, fp16 / bf16 / fp32); channels_last fp16 / fp32 inputs with C % 8 == 0 run the NHWC
-    kernels the UNet graph uses, as a view.  Only fp64 and empty tensors take F.group_norm on the device, as the
+    kernels the UNet graph uses, as a view, where one of them takes the shape (else the NCHW kernel, output kept
+    channels_last).  A weight without a bias, or a bias without a weight, is completed with zeros / ones as in F.group_norm.  Only fp64 and empty tensors take F.group_norm on the device, as the
     reference's forward would -- a stated domain limit, not an error fallback.
   * impl='ln'/'bn' reproduce the reference bit for bit by default, INCLUDING its quirk Q1: the affine parameters are not
     applied (:84-85 has that code commented out, so the reference's own tests/gn_to_ln.py prints False for them; pinned by

@@ -3,6 +3,7 @@ host-side pieces (C++ tokenizer, DPM solver tables, libsdod handle/error convent
 golden vectors bit for bit."""
 import ctypes
 import json
+import math
 import os
 import re
 
@@ -350,6 +351,58 @@ def test_group_norm_path_selection_without_a_gpu():
     assert lib.sdod_group_norm_path(1, 100, 64, 0, 32, 1) in (2, 3)     # fp32: LDS / two-pass kernels
     assert lib.sdod_group_norm_path(2, 64, 30, 0, 32, 0) == -1          # channels not divisible by groups
     assert lib.sdod_group_norm_workspace_bytes(2, 32) == (1024 + 2 * 1024 * 32 * 2 + 2 * 32 * 3) * 4
+
+
+def _gn_nhwc_kernel_takes(path, hw, c, groups, dtype):
+    """the shape constraints of each NHWC GroupNorm kernel, restated from csrc/norms.hip (path 0 needs a device)"""
+    cg = c // groups
+    if path == 1:   # (image, group) kernel: fp16, a whole vector of 2 / 4 / 8 halves per channel run, <= 256 vectors per run
+        v = 8 if cg % 8 == 0 else 4 if cg % 4 == 0 else 2 if cg % 2 == 0 else 0
+        return dtype == 0 and v > 0 and cg // v <= 256
+    if path == 2:   # small-map LDS kernel: whole groups per 16-byte aligned channel set, <= 4 groups, slab <= 96 KB
+        sw = cg * 8 // math.gcd(cg, 8)
+        smem = hw * sw * (2 if dtype == 0 else 4) + (2 * sw + 128) * 4 + sw
+        return c % sw == 0 and hw <= 1024 and sw // cg <= 4 and smem <= 96 * 1024
+    if path == 3:   # statistics + apply: <= 2 passes of <= 256 threads over a pixel row, 8 channels each
+        cp = c // 8
+        npass = (cp + 255) // 256
+        return npass <= 2 and cp % npass == 0
+    return False
+
+
+def test_group_norm_dispatch_plan_is_consistent():
+    """sdod_group_norm_path and sdod_group_norm_nhwc share one plan: every shape reported as a path is one that kernel takes,
+    and every shape reported as -1 is refused by the entry point with INVALID_ARGUMENT before any launch (only such shapes
+    are probed with host buffers: nothing reads them)"""
+    import ctypes
+    from sdod.amd import _lib
+    lib = _lib.hip()
+    buf = (ctypes.c_char * 4096)()
+    P = ctypes.c_void_p((ctypes.addressof(buf) + 127) & ~127)
+    holes = {(2, 16, 4104, 8, 1), (1, 64, 2056, 8, 0), (1, 64, 2056, 8, 1), (1, 64, 8192, 2, 0), (1, 2048, 4088, 8, 1)}
+    shapes = set(holes)
+    for hw in (1, 16, 64, 100, 1024, 2048, 16384):
+        for c in (8, 24, 64, 320, 640, 1280, 1920, 2048, 2056, 2560, 4088, 4096, 4104, 4112, 8192):
+            for groups in (1, 2, 3, 8, 32):
+                if c % groups == 0:
+                    for dtype in (0, 1):
+                        shapes.add((1, hw, c, groups, dtype))
+    refused = 0
+    for n, hw, c, groups, dtype in sorted(shapes):
+        path = lib.sdod_group_norm_path(n, hw, c, 0, groups, dtype)
+        assert path in (-1, 0, 1, 2, 3), path
+        if path >= 0:
+            assert path == 0 or _gn_nhwc_kernel_takes(path, hw, c, groups, dtype), (n, hw, c, groups, dtype, path)
+            assert (n, hw, c, groups, dtype) not in holes or path != 3, (n, hw, c, groups, dtype)
+            continue
+        refused += 1
+        rc = lib.sdod_group_norm_nhwc(P, None, P, None, None, n, hw, c, 0, groups, ctypes.c_float(1e-5), 0, dtype, P, None)
+        assert rc == 2, (n, hw, c, groups, dtype, rc)                                   # INVALID_ARGUMENT
+        assert b'unsupported channel count for GroupNorm' in lib.sdod_hip_last_error()
+        assert b'sdod_group_norm_path reports -1' in lib.sdod_hip_last_error()
+    assert refused >= len(holes)
+    for case in holes:
+        assert lib.sdod_group_norm_path(case[0], case[1], case[2], 0, case[3], case[4]) == -1, case
 
 
 def test_argument_checks_answer_before_any_launch():

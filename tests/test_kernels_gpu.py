@@ -763,7 +763,8 @@ def test_group_norm_concat_sources():
 ])
 def test_group_norm_nchw_kernel(shape, groups, dtype, silu, affine):
     """sdod_group_norm_nchw: the operator on torch's default layout (a group = one contiguous slab): no transpose, any
-    channel count, fp16 / bf16 / fp32, in place; against F.group_norm in fp32 on the same rounded inputs"""
+    channel count, fp16 / bf16 / fp32, out of place and launch-to-launch reproducible; against F.group_norm in fp32 on the
+    same rounded inputs (in place: tests/test_group_norm_gpu.py)"""
     from sdod.amd import ops
     g = torch.Generator().manual_seed(hash(shape) % 1000)
     x = (torch.randn(shape, generator=g) * 1.7 + torch.randn((shape[0], shape[1]) + (1,) * (len(shape) - 2), generator=g)).to(dtype)
