@@ -22,6 +22,9 @@
  *                 out0     fp16 [B][77][ctx_dim]         (context.cpp:208 p)
  *   VAE_DECODER   in0 z    fp32 NCHW [B][4][H][W]        (context.cpp:220 y)
  *                 out0 img fp16 NHWC [B][8H][8W][3] in [-1,1]  (context.cpp:221 img)
+ *   VAE_ENCODER   in0 img  uint8 HWC [B][8H][8W][3]      (ldm img2img: x = 2 u / 255 - 1)
+ *                 out0     fp32 NCHW [B][8][H][W]        moments = quant_conv(encoder(x)): mean | logvar (not part of the
+ *                                                        reference, which has no img2img)
  *
  * Parameters are addressed by their CompVis-ldm / HF-CLIP state-dict names (without the
  * `model.diffusion_model.` / `first_stage_model.` / `cond_stage_model.transformer.` prefixes) and are
@@ -43,7 +46,8 @@
 extern "C" {
 #endif
 
-enum sdod_graph_kind { SDOD_GRAPH_UNET = 0, SDOD_GRAPH_VAE_DECODER = 1, SDOD_GRAPH_TEXT_ENCODER = 2, SDOD_GRAPH_TEMB = 3 };
+enum sdod_graph_kind { SDOD_GRAPH_UNET = 0, SDOD_GRAPH_VAE_DECODER = 1, SDOD_GRAPH_TEXT_ENCODER = 2, SDOD_GRAPH_TEMB = 3,
+                       SDOD_GRAPH_VAE_ENCODER = 4 };
 
 typedef struct sdod_model_config {
     int latent_channels; /* 4 */

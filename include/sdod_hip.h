@@ -120,6 +120,11 @@ typedef struct sdod_gemm_desc {
     int w_img_stride;
     int vec_img_stride;
     int softmax_cols;
+    /* conv padding: 0 = symmetric ksize / 2 (zero-initialised descriptors); 1 = ldm's VAE-encoder Downsample, F.pad(x, (0, 1, 0, 1))
+     * then a 3x3 stride-2 pad-0 convolution: nothing above / left of the image, one zero row / column below / right of it, so
+     * h_out = (h_in + 1 - 3) / 2 + 1.  Only the im2col gather kernels honour it: halo-patch tiles decline it (sdod_gemm_halo_ok = 0),
+     * a tail segment or upsampling refuses it, and it needs ksize 3 with stride 2. */
+    int pad_mode;
 } sdod_gemm_desc;
 
 SDOD_API int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream);
@@ -271,6 +276,19 @@ SDOD_API int sdod_latent_im2col_f16(const float* x, void* y, int n_img, int h, i
  * 9 * c <= 64; cout in {64, 128, 256, 320}.  Equals sdod_latent_im2col_f16 followed by the K = 64 sdod_gemm_f16. */
 SDOD_API int sdod_conv_in_f16(const float* x, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout,
                               float scale, void* stream);
+/* The VAE encoder's input convolution in one launch: img uint8 HWC RGB [n][h][wd][3] -> x = fp16(2 * (u / 255) - 1) -> 3x3 pad-1
+ * convolution with w fp16 [cout][64] (k = tap * 3 + channel, zero beyond 27: the PK_CONV3_SMALL packing) + bias fp32 [cout] -> y NHWC
+ * fp16 [n*h*wd][cout].  cout in {64, 128, 256, 320}.  The same core as sdod_conv_in_f16: equals normalising, then
+ * sdod_im2col3x3_small_f16 and the K = 64 sdod_gemm_f16, bit for bit. */
+SDOD_API int sdod_image_conv_in_f16(const uint8_t* img, const void* w, const float* bias, void* y, int n_img, int h, int wd, int cout,
+                                    void* stream);
+/* ldm img2img's latent start in one launch.  moments fp32 NCHW [n][2c][h][w] (mean = channels [0, c), logvar = [c, 2c)):
+ *   std = exp(0.5 * clamp(logvar, -30, 20)); z0 = 0.18215 * (mean + std * n1)      (DiagonalGaussianDistribution.sample,
+ *   x = sqrt_at * z0 + sqrt_one_minus_at * n2                                          get_first_stage_encoding, stochastic_encode)
+ * x, z0, n1, n2: fp32 NCHW [n][c][h][w]; z0 may be NULL.  n1 / n2 NULL: drawn in the kernel, image i's values exactly those of
+ * sdod_randn_f32(count = c*h*w, seed, stream_id = (1 << 32) | (image_index0 + i)) for n1 and (2 << 32) | (image_index0 + i) for n2. */
+SDOD_API int sdod_encode_latent_f32(const float* moments, const float* n1, const float* n2, float* x, float* z0, int n, int c, int hw,
+                                    float sqrt_at, float sqrt_one_minus_at, uint64_t seed, uint64_t image_index0, void* stream);
 SDOD_API int sdod_nchw_f32_to_nhwc_f16(const float* x, void* y, int n, int c, int hw, float scale, void* stream);
 /* y(NHWC fp16)[img][pix][o] = sum_c w[o][c]*(scale*x(NCHW fp32)[img][c][pix]) + b[o]; w/b fp32 [c][c]/[c] or NULL
  * (identity).  Folds ldm's z/0.18215 and first_stage_model.post_quant_conv into the layout change. */

@@ -132,9 +132,23 @@ __global__ void latent_im2col_kernel(const float* x, f16* y, int n_img, int h, i
 // v_mfma_f32_16x16x32_f16 pair per 16 x 16 output block, bias, NHWC fp16 out.  A workgroup owns 32 pixels x all Cout columns
 // (wave w: column blocks w, w + 4, ...): until now this was an im2col launch plus a K = 64 GEMM launch that is all prologue and
 // epilogue (7 + 10 us at 64x64).  Same products in the same order as the GEMM (two K steps), bias added in fp32.
-template <int NB> // 16-column blocks per wave: Cout = 64 * NB
-__global__ __launch_bounds__(256) void conv_in_kernel(const float* x, const f16* w, const float* bias, f16* y, int n_img, int h, int wd, int c,
-                                                      float scale) {
+// The source of the im2col values is a template argument: the UNet's latent (NCHW fp32, scaled) or, for the VAE encoder
+// (sdod_image_conv_in_f16), the uint8 HWC RGB image normalised to 2 u / 255 - 1.
+struct LatentSrc { // x NCHW fp32 [n][c][h][w], value x * scale
+    const float* x;
+    float scale;
+    SDOD_DEVICE float at(int img, int ch, int yy, int xx, int c, int h, int wd) const {
+        return 0.f + x[((size_t)img * c + ch) * h * wd + (size_t)yy * wd + xx] * scale;
+    }
+};
+struct ImageU8Src { // img uint8 HWC [n][h][w][c], value 2 (u / 255) - 1 (ldm img2img's load_img; 2 * q is exact, so a contraction is too)
+    const uint8_t* img;
+    SDOD_DEVICE float at(int img_i, int ch, int yy, int xx, int c, int h, int wd) const {
+        return 2.0f * ((float)img[(((size_t)img_i * h + yy) * wd + xx) * c + ch] / 255.0f) - 1.0f;
+    }
+};
+template <int NB, typename Src> // 16-column blocks per wave: Cout = 64 * NB
+__global__ __launch_bounds__(256) void conv_in_kernel(const Src src, const f16* w, const float* bias, f16* y, int n_img, int h, int wd, int c) {
     __shared__ __attribute__((aligned(16))) f16 sa[32][64 + 8];
     __shared__ __attribute__((aligned(16))) f16 sw[64 * NB][64 + 8];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -154,14 +168,13 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const float* x, const f16*
             const int img = (int)(m / hw), rem = (int)(m - (long long)img * hw);
             const int oy = rem / wd, ox = rem - oy * wd;
             int tap = k0 / c, ch = k0 - tap * c; // one division per thread; (tap, channel) then advance by increments
-            const float* xi = x + (size_t)img * c * hw;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float f = 0.f;
                 if (tap < 9) {
                     const int r = (tap * 11) >> 5, s2 = tap - r * 3; // tap / 3 for tap < 9
                     const int yy = oy + r - 1, xx = ox + s2 - 1;
-                    if (yy >= 0 && yy < h && xx >= 0 && xx < wd) f = 0.f + xi[(size_t)ch * hw + yy * wd + xx] * scale;
+                    if (yy >= 0 && yy < h && xx >= 0 && xx < wd) f = src.at(img, ch, yy, xx, c, h, wd);
                 }
                 v[e] = (f16)f;
                 if (++ch == c) { ch = 0; ++tap; }
@@ -512,34 +525,77 @@ SDOD_DEVICE void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
     const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
     c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
 }
+// block j of stream `stream`: the four Philox words c and their two Box-Muller pairs z
+SDOD_DEVICE void philox_normal4(uint64_t j, uint64_t seed, uint64_t stream, uint32_t (&c)[4], float (&z)[4]) {
+    c[0] = (uint32_t)j; c[1] = (uint32_t)(j >> 32); c[2] = (uint32_t)stream; c[3] = (uint32_t)(stream >> 32);
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+#pragma unroll
+    for (int a = 0; a < 4; a += 2) {
+        const float u1 = ((float)(c[a] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float u2 = ((float)(c[a + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float rad = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(6.283185307179586f * u2, &sn, &cs);
+        z[a] = rad * cs;
+        z[a + 1] = rad * sn;
+    }
+}
 __global__ void randn_kernel(float* out, uint32_t* words, size_t count, uint64_t seed, uint64_t stream) {
     const size_t nblk = (count + 3) / 4;
     GRID_STRIDE(j, nblk) {
-        uint32_t c[4] = {(uint32_t)j, (uint32_t)((uint64_t)j >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
-        uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            philox_round(c, k0, k1);
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
+        uint32_t c[4];
         float z[4];
-#pragma unroll
-        for (int a = 0; a < 4; a += 2) {
-            const float u1 = ((float)(c[a] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float u2 = ((float)(c[a + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float rad = sqrtf(-2.0f * logf(u1));
-            float sn, cs;
-            sincosf(6.283185307179586f * u2, &sn, &cs);
-            z[a] = rad * cs;
-            z[a + 1] = rad * sn;
-        }
+        philox_normal4(j, seed, stream, c, z);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             if (4 * j + q < count) {
                 out[4 * j + q] = z[q];
                 if (words) words[4 * j + q] = c[q];
             }
+    }
+}
+
+// ldm img2img's start latent (include/sdod_hip.h: sdod_encode_latent_f32): posterior sample, 0.18215 scale and stochastic_encode in
+// fp32, torch's operation order (no contraction).  Thread = four consecutive elements of one image = one Philox block of its streams.
+__global__ void encode_latent_kernel(const float* mom, const float* n1, const float* n2, float* x, float* z0, int n, int c, int hw,
+                                     float sqrt_at, float sqrt_1m_at, uint64_t seed, uint64_t index0) {
+    const size_t per = (size_t)c * hw, nblk = per / 4; // per % 4 == 0 (checked by the host)
+    GRID_STRIDE(t, (size_t)n * nblk) {
+        const int img = (int)(t / nblk);
+        const size_t j = t - (size_t)img * nblk;
+        float r1[4], r2[4];
+        if (n1) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) r1[q] = n1[(size_t)img * per + 4 * j + q];
+        } else {
+            uint32_t w[4];
+            philox_normal4(j, seed, (1ull << 32) | (index0 + img), w, r1);
+        }
+        if (n2) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) r2[q] = n2[(size_t)img * per + 4 * j + q];
+        } else {
+            uint32_t w[4];
+            philox_normal4(j, seed, (2ull << 32) | (index0 + img), w, r2);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const size_t e = 4 * j + q;
+            const size_t ch = e / hw, pix = e - ch * hw;
+            const float mean = mom[((size_t)img * 2 * c + ch) * hw + pix];
+            const float logvar = fminf(fmaxf(mom[((size_t)img * 2 * c + c + ch) * hw + pix], -30.0f), 20.0f);
+            const float sd = expf(__fmul_rn(0.5f, logvar));
+            const float z = __fmul_rn(0.18215f, __fadd_rn(mean, __fmul_rn(sd, r1[q])));
+            const size_t o = (size_t)img * per + e;
+            if (z0) z0[o] = z;
+            x[o] = __fadd_rn(__fmul_rn(sqrt_at, z), __fmul_rn(sqrt_1m_at, r2[q]));
+        }
     }
 }
 
@@ -597,22 +653,47 @@ extern "C" int sdod_latent_im2col_f16(const float* x, void* y, int n_img, int h,
     SDOD_CATCH
 }
 
+template <typename Src>
+void launch_conv_in(const Src src, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout, hipStream_t st) {
+    const long long M = (long long)n_img * h * wd;
+    const dim3 grid((unsigned)((M + 31) / 32));
+    switch (cout / 64) {
+    case 1: SDOD_LAUNCH((conv_in_kernel<1, Src>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
+    case 2: SDOD_LAUNCH((conv_in_kernel<2, Src>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
+    case 4: SDOD_LAUNCH((conv_in_kernel<4, Src>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
+    default: SDOD_LAUNCH((conv_in_kernel<5, Src>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
+    }
+    SDOD_HIP_CHECK(hipGetLastError());
+}
+
 extern "C" int sdod_conv_in_f16(const float* x, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout,
                                 float scale, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(x && w && y && n_img > 0 && h > 0 && wd > 0 && c > 0 && 9 * c <= 64, "bad argument (9 * Cin must fit the 64-deep K slab)");
     SDOD_REQUIRE(cout == 320 || cout == 256 || cout == 128 || cout == 64, "Cout must be 64, 128, 256 or 320");
     SDOD_REQUIRE((((uintptr_t)w | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y & 7) == 0, "misaligned pointer");
-    const long long M = (long long)n_img * h * wd;
-    const dim3 grid((unsigned)((M + 31) / 32));
-    hipStream_t st = (hipStream_t)stream;
-    switch (cout / 64) {
-    case 1: SDOD_LAUNCH(conv_in_kernel<1>, grid, dim3(256), 0, st, x, (const f16*)w, bias, (f16*)y, n_img, h, wd, c, scale); break;
-    case 2: SDOD_LAUNCH(conv_in_kernel<2>, grid, dim3(256), 0, st, x, (const f16*)w, bias, (f16*)y, n_img, h, wd, c, scale); break;
-    case 4: SDOD_LAUNCH(conv_in_kernel<4>, grid, dim3(256), 0, st, x, (const f16*)w, bias, (f16*)y, n_img, h, wd, c, scale); break;
-    default: SDOD_LAUNCH(conv_in_kernel<5>, grid, dim3(256), 0, st, x, (const f16*)w, bias, (f16*)y, n_img, h, wd, c, scale); break;
-    }
-    SDOD_HIP_CHECK(hipGetLastError());
+    launch_conv_in(LatentSrc{x, scale}, w, bias, y, n_img, h, wd, c, cout, (hipStream_t)stream);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_image_conv_in_f16(const uint8_t* img, const void* w, const float* bias, void* y, int n_img, int h, int wd, int cout,
+                                      void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(img && w && y && n_img > 0 && h > 0 && wd > 0, "bad argument");
+    SDOD_REQUIRE(cout == 320 || cout == 256 || cout == 128 || cout == 64, "Cout must be 64, 128, 256 or 320");
+    SDOD_REQUIRE((((uintptr_t)w | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y & 7) == 0, "misaligned pointer");
+    launch_conv_in(ImageU8Src{img}, w, bias, y, n_img, h, wd, 3, cout, (hipStream_t)stream);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_encode_latent_f32(const float* moments, const float* n1, const float* n2, float* x, float* z0, int n, int c, int hw,
+                                      float sqrt_at, float sqrt_one_minus_at, uint64_t seed, uint64_t image_index0, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(moments && x && n > 0 && c > 0 && hw > 0 && ((size_t)c * hw) % 4 == 0, "bad argument (c * hw must be a multiple of 4)");
+    LAUNCH(encode_latent_kernel, (size_t)n * c * hw / 4, stream, moments, n1, n2, x, z0, n, c, hw, sqrt_at, sqrt_one_minus_at, seed,
+           image_index0);
     return 0;
     SDOD_CATCH
 }

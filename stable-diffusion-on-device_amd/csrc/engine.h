@@ -166,6 +166,7 @@ private:
     void build();       // dispatches on kind_
     void build_unet();
     void build_vae();
+    void build_vae_encoder();
     void build_clip();
     void build_temb();
 
@@ -192,6 +193,7 @@ private:
         const float* ln_s_raw = nullptr; // LayerNorm fold with vectors the caller owns: ln_s (bias_raw carries the matching t)
         int w_img_stride = 0, vec_img_stride = 0; // per-image weights / vectors (sdod_gemm_desc), with rows_per_img
         int softmax_cols = 0;
+        int pad_mode = 0;          // conv(): sdod_gemm_desc::pad_mode
     };
     // registers the LayerNorm fold of Linear `w_param` ([N][K], row stride ldw): gamma is multiplied into W in place at finalize,
     // the returned device vectors (owned by the graph) are s[n] = sum_k W'[n][k] and t[n] = sum_k beta[k] W[n][k] + bias[n]

@@ -42,7 +42,7 @@ static void parallel_for(int64_t n, F&& fn) {
 
 // ------------------------------------------------------------------------------------------ lifecycle
 Graph::Graph(int kind, const sdod_model_config& cfg, int batch) : kind_(kind), cfg_(cfg), batch_(batch) {
-    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_TEMB, "unknown graph kind");
+    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_VAE_ENCODER, "unknown graph kind");
     SDOD_REQUIRE(batch > 0 && batch <= 64, "batch must be in [1, 64]");
     SDOD_REQUIRE(cfg.model_channels > 0 && cfg.model_channels % 64 == 0, "model_channels must be a multiple of 64");
     SDOD_REQUIRE(cfg.context_dim % 64 == 0, "context_dim must be a multiple of 64");
@@ -608,7 +608,8 @@ ShapeKey key_of(const sdod_gemm_desc& d) {
     // w_in and n_img are part of the key: which halo-patch tiles take a convolution depends on both (halo_geometry), so two
     // convolutions with equal M and h_in but different (n_img, w_in) must not share a pick
     return ShapeKey{{d.a_mode, d.M, d.N, d.K, d.c0, d.c1, d.stride, d.upsample, d.ksize, d.h_in,
-                     (d.residual ? 1 : 0) + (d.geglu ? 2 : 0) + 4 * d.tc0 + 16384 * d.tc1 + (d.ln ? (1 << 30) : 0) + (d.wq ? (1 << 29) : 0) + (d.softmax_cols ? (1 << 28) : 0) + (d.w_img_stride ? (1 << 27) : 0), d.lda,
+                     (d.residual ? 1 : 0) + (d.geglu ? 2 : 0) + 4 * d.tc0 + 16384 * d.tc1 + (d.ln ? (1 << 30) : 0) + (d.wq ? (1 << 29) : 0) + (d.softmax_cols ? (1 << 28) : 0) + (d.w_img_stride ? (1 << 27) : 0) +
+                         (d.pad_mode ? (1 << 26) : 0) /* only when set: every older table line keeps its key */, d.lda,
                      d.a_mode == SDOD_A_CONV3X3 ? d.w_in : 0, d.a_mode == SDOD_A_CONV3X3 ? d.n_img : 0}};
 }
 // a table pick the library would refuse at launch (a halo-patch / A-panel tile that does not take this descriptor: a stale or
@@ -853,7 +854,8 @@ void Graph::linear(const f16* x, int rows, int K, int w, int N, f16* out, const 
 Act Graph::conv(const Act& x, const Act* x2, int w, int cout, int ksize, int stride, bool upsample, const GemmOpt& o) {
     const int ups = upsample ? 1 : 0;
     const int hup = x.h << ups, wup = x.w << ups;
-    const int ho = (hup + 2 * (ksize / 2) - ksize) / stride + 1, wo = (wup + 2 * (ksize / 2) - ksize) / stride + 1;
+    const int pad_sum = o.pad_mode ? 1 : 2 * (ksize / 2); // pad_mode 1: ldm's encoder Downsample, F.pad(x, (0, 1, 0, 1)) + pad 0
+    const int ho = (hup + pad_sum - ksize) / stride + 1, wo = (wup + pad_sum - ksize) / stride + 1;
     Act y;
     y.n = x.n; y.h = ho; y.w = wo; y.c = cout;
     y.p = o.out ? o.out : alloc(y.numel());
@@ -872,8 +874,9 @@ Act Graph::conv(const Act& x, const Act* x2, int w, int cout, int ksize, int str
     d.ldw = params_[w].ld > 0 ? params_[w].ld : d.K; d.ldo = cout;
     d.a_mode = SDOD_A_CONV3X3;
     d.n_img = x.n; d.h_in = x.h; d.w_in = x.w; d.c0 = x.c; d.c1 = x2 ? x2->c : 0;
-    d.stride = stride; d.upsample = ups; d.ksize = ksize;
+    d.stride = stride; d.upsample = ups; d.ksize = ksize; d.pad_mode = o.pad_mode;
     if (o.bias >= 0) d.bias = params_[o.bias].dev;
+    else if (o.bias_raw) d.bias = o.bias_raw;
     d.row_bias = o.row_bias; d.ld_row_bias = o.ld_row_bias; d.rows_per_img = o.rows_per_img;
     d.residual = o.residual; d.ldr = cout;
     d.act = o.act; d.alpha = o.alpha;
@@ -956,6 +959,7 @@ void Graph::build() {
     case SDOD_GRAPH_UNET: build_unet(); break;
     case SDOD_GRAPH_VAE_DECODER: build_vae(); break;
     case SDOD_GRAPH_TEXT_ENCODER: build_clip(); break;
+    case SDOD_GRAPH_VAE_ENCODER: build_vae_encoder(); break;
     default: build_temb(); break;
     }
     settle();

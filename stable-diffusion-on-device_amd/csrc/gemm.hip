@@ -45,6 +45,7 @@ struct GemmP {
     int lda, ldw, ldo, ldr;
     int mode;
     int h_in, w_in, h_out, w_out, c0, c1, stride, ups, ksize;
+    int pad;      // conv: zero rows / columns above and left of the image (ksize / 2, or 0 for sdod_gemm_desc::pad_mode 1)
     int sa0, sa1; // pixel strides (elements) of the two A sources: c0/c1 for NHWC images, lda for plain rows
     int geglu;    // epilogue pairs 16-column blocks: out = a * gelu(gate)
     int k_tail;   // K columns >= k_tail come from the 1x1-gathered tail sources t0|t1 (0 = none)
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmP p) {
             const int tap = k0 / cin;
             const int cc = k0 - tap * cin;
             const int r = tap / p.ksize, s = tap - r * p.ksize;
-            const int pad = p.ksize >> 1;
+            const int pad = p.pad;
             const f16* src = p.a0;
             int csrc = p.c0, ccs = cc;
             if (cc >= p.c0) {
@@ -599,7 +600,7 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
     int a_ro0[A_LD], a_ro1[A_LD], a_py[A_LD], a_px[A_LD], a_im[A_LD];
     unsigned a_mask[A_LD];
     const f16* b_row[B_LD];
-    const int pad = p.ksize >> 1;
+    const int pad = p.pad;
     const int hup = p.h_in << p.ups, wup = p.w_in << p.ups;
     auto setup_rows = [&]() {
 #pragma unroll
@@ -2715,7 +2716,7 @@ struct Plan {
 // Can halo tile `tile` run descriptor d?  Fills the geometry fields of *p (may be null) and the LDS bytes of the launch.
 bool halo_geometry(const sdod_gemm_desc* d, int tile, GemmP* p, size_t* smem_bytes) {
     if (!is_halo_tile(tile)) return false;
-    if (d->a_mode != SDOD_A_CONV3X3 || d->ksize == 1 || d->stride != 1 || d->geglu || d->ln || d->bias_on_m) return false;
+    if (d->a_mode != SDOD_A_CONV3X3 || d->ksize == 1 || d->stride != 1 || d->pad_mode || d->geglu || d->ln || d->bias_on_m) return false;
     if (d->wq && d->k_tail) return false;
     if (d->c0 <= 0 || d->c0 % 64 || d->c1 % 64 || d->h_in <= 0 || d->w_in <= 0 || d->n_img <= 0) return false;
     if (d->upsample && d->k_tail) return false;
@@ -3049,7 +3050,7 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
         SDOD_REQUIRE(d->ldo >= d->N / 2, "geglu: ldo must be >= N/2");
     }
     if (d->k_tail) {
-        SDOD_REQUIRE(d->a_mode == SDOD_A_CONV3X3 && d->stride == 1 && !d->upsample, "tail segment needs a stride-1 conv");
+        SDOD_REQUIRE(d->a_mode == SDOD_A_CONV3X3 && d->stride == 1 && !d->upsample && !d->pad_mode, "tail segment needs a stride-1 conv");
         SDOD_REQUIRE(d->t0 && d->tc0 > 0 && d->tc0 % 64 == 0 && d->tc1 % 64 == 0 && (d->t1 || d->tc1 == 0), "bad tail sources");
         SDOD_REQUIRE(d->K == d->k_tail + d->tc0 + d->tc1, "K must equal k_tail + tc0 + tc1");
     }
@@ -3068,13 +3069,22 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
         p.stride = d->stride; p.ups = d->upsample ? 1 : 0;
         p.sa0 = d->c0; p.sa1 = d->c1;
         const int hup = d->h_in << p.ups, wup = d->w_in << p.ups;
-        p.h_out = (hup + 2 * (ks / 2) - ks) / d->stride + 1;
-        p.w_out = (wup + 2 * (ks / 2) - ks) / d->stride + 1;
+        SDOD_REQUIRE(d->pad_mode == 0 || d->pad_mode == 1, "pad_mode must be 0 or 1");
+        SDOD_REQUIRE(!d->pad_mode || (ks == 3 && d->stride == 2 && !d->upsample && d->h_in >= 2 && d->w_in >= 2),
+                     "pad_mode 1 needs a 3x3 stride-2 conv without upsampling on an image of at least 2 x 2");
+        // pad_mode 1: F.pad(x, (0, 1, 0, 1)) then pad 0 -- the gather's low pad is 0 and its per-tap bound masks zero the extra
+        // bottom row / right column
+        p.pad = d->pad_mode ? 0 : ks / 2;
+        const int pad_sum = d->pad_mode ? 1 : 2 * (ks / 2);
+        p.h_out = (hup + pad_sum - ks) / d->stride + 1;
+        p.w_out = (wup + pad_sum - ks) / d->stride + 1;
+        SDOD_REQUIRE(p.h_out > 0 && p.w_out > 0, "conv input smaller than the kernel");
         SDOD_REQUIRE(d->M == d->n_img * p.h_out * p.w_out, "conv M must equal n_img*h_out*w_out");
     } else {
         SDOD_REQUIRE(d->a_mode == SDOD_A_ROWS, "unknown a_mode");
         SDOD_REQUIRE(d->lda >= d->K && d->lda % 8 == 0, "lda must be >= K and a multiple of 8");
-        p.c0 = d->K; p.c1 = 0; p.h_in = p.w_in = p.h_out = p.w_out = 1; p.stride = 1; p.ksize = 1;
+        SDOD_REQUIRE(d->pad_mode == 0, "pad_mode applies to convolutions only");
+        p.c0 = d->K; p.c1 = 0; p.h_in = p.w_in = p.h_out = p.w_out = 1; p.stride = 1; p.ksize = 1; p.pad = 0;
         p.sa0 = d->lda; p.sa1 = 0;
     }
     p.w_img_stride = d->w_img_stride;

@@ -1,5 +1,5 @@
 // graphs.hip -- launch-list builders for the four graphs of the txt2img path: UNet eps-model, VAE decoder,
-// CLIP text encoder, time-embedding MLP.  They stand in for the serialized QNN graphs the reference loads
+// CLIP text encoder, time-embedding MLP -- and the VAE encoder of the img2img path.  They stand in for the serialized QNN graphs the reference loads
 // (context.cpp:105: "unet.serialized", "text_encoder.serialized", "vae_decoder.serialized", "temb"); the
 // block structure follows the op names visible in the reference's own profiler table
 // (analyze_results.py:20-93: in_layers / emb_layers / out_layers / skip_connection, norm / proj_in /
@@ -594,6 +594,84 @@ void Graph::build_vae() {
     release(h);
     { GemmOpt o; o.bias = cb; o.out = img_out; conv(g, nullptr, cw, 3, 3, 1, false, o); }
     release(g);
+}
+
+// The encoder half of first_stage_model (ldm Encoder, ch 128, ch_mult (1, 2, 4, 4), 2 ResBlocks per level, double_z) and its
+// quant_conv: uint8 image -> moments = quant_conv(encoder(2 u / 255 - 1)), what ldm's img2img encodes the init image with.
+//   * conv_in: normalisation, im2col (K = 27 -> 64) and the MFMA product in one launch (sdod_image_conv_in_f16);
+//   * Downsample = F.pad(h, (0, 1, 0, 1)) + 3x3 stride-2 conv: the gather GEMM with pad_mode 1 (no padded copy);
+//   * quant_conv (1x1, 8 -> 8) composed into conv_out at finalize (sdod_compose_linear_f16: one fp16 rounding of P . W, bias
+//     P b + b_q), then one layout change NHWC fp16 -> NCHW fp32 for the moments.
+void Graph::build_vae_encoder() {
+    const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, LC = cfg_.latent_channels, VC = cfg_.vae_channels;
+    const int IH = 8 * H, IW = 8 * Wd, ZC = 2 * LC;
+    SDOD_REQUIRE(VC == 64 || VC == 128 || VC == 256 || VC == 320, "vae_channels must be 64, 128, 256 or 320 (image input convolution)");
+    const int mult[4] = {1, 2, 4, 4};
+    uint8_t* img_in = (uint8_t*)io_alloc(inputs_, (size_t)B * IH * IW * 3);
+    float* mom_out = (float*)io_alloc(outputs_, (size_t)B * ZC * H * Wd * sizeof(float));
+
+    const int ciw = P("encoder.conv_in.weight", {VC, 3, 3, 3}, PK_CONV3_SMALL), cib = P("encoder.conv_in.bias", {VC}, PK_VEC);
+    Act h = act(B, IH, IW, VC);
+    {
+        const f16* wp = mode_ != DECLARE ? W<f16>(ciw) : nullptr;
+        const float* bp = mode_ != DECLARE ? W<float>(cib) : nullptr;
+        f16* hp = h.p;
+        settle();
+        if (mode_ == REAL) {
+            const double fl = 2.0 * B * IH * IW * VC * 64;
+            flops_ += fl;
+            ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_image_conv_in_f16(img_in, wp, bp, hp, B, IH, IW, VC, st)); }, "image_conv_in",
+                              fl, (double)B * IH * IW * (3 + VC * 2) + VC * 64 * 2, "M" + std::to_string(B * IH * IW) + " N" + std::to_string(VC) + " K64"});
+        }
+    }
+    int ch = VC;
+    for (int level = 0; level < 4; ++level) {
+        const int cout = VC * mult[level];
+        for (int i = 0; i < 2; ++i) {
+            Act r = vae_res_block("encoder.down." + std::to_string(level) + ".block." + std::to_string(i), h, cout);
+            release_after_consumer(h);
+            h = r;
+        }
+        ch = cout;
+        if (level != 3) {
+            const std::string dn = "encoder.down." + std::to_string(level) + ".downsample.conv";
+            const int w = P(dn + ".weight", {ch, ch, 3, 3}, PK_CONV3), b = P(dn + ".bias", {ch}, PK_VEC);
+            GemmOpt o; o.bias = b; o.pad_mode = 1;
+            Act d = conv(h, nullptr, w, ch, 3, 2, false, o);
+            release(h);
+            h = d;
+        }
+    }
+    if (mode_ != DECLARE) SDOD_REQUIRE(h.h == H && h.w == Wd, "image size must be 8x the latent size");
+    { Act r = vae_res_block("encoder.mid.block_1", h, ch); release_after_consumer(h); h = r; }
+    { Act r = vae_attn_block("encoder.mid.attn_1", h); release(h); h = r; }
+    { Act r = vae_res_block("encoder.mid.block_2", h, ch); release_after_consumer(h); h = r; }
+    const int nw = P("encoder.norm_out.weight", {ch}, PK_VEC), nb = P("encoder.norm_out.bias", {ch}, PK_VEC);
+    // conv_out [ZC][9 ch] and quant_conv [ZC][ZC] share one [ZC][9 ch + ZC] matrix; the first 9 ch columns become quant_conv . conv_out
+    const int ld = 9 * ch + ZC;
+    const int cw = Pc("encoder.conv_out.weight", {ZC, ch, 3, 3}, PK_CONV3, ld, 0, -1);
+    const int cb = P("encoder.conv_out.bias", {ZC}, PK_VEC);
+    Pc("quant_conv.weight", {ZC, ZC, 1, 1}, PK_CONV1, ld, 9 * ch, cw);
+    const int qb = P("quant_conv.bias", {ZC}, PK_VEC);
+    Act g = group_norm(h, nullptr, nw, nb, 1e-6f, true);
+    release(h);
+    float* bc = nullptr;
+    if (mode_ == REAL) {
+        SDOD_HIP_CHECK(hipMalloc((void**)&bc, (size_t)ZC * sizeof(float)));
+        derived_.push_back(bc);
+        f16* wc = reinterpret_cast<f16*>(params_[cw].dev);
+        compose_jobs_.push_back(ComposeJob{wc, wc + 9 * ch, ld, ZC, ZC, 9 * ch, W<float>(cb), W<float>(qb), bc});
+    }
+    GemmOpt o;
+    if (mode_ == REAL) o.bias_raw = bc; else o.bias = cb; // (the sizing passes only need a bias of the same shape)
+    Act m = conv(g, nullptr, cw, ZC, 3, 1, false, o);
+    release(g);
+    {
+        const f16* mp = m.p;
+        emit([=](hipStream_t st) { check_rc2(sdod_nhwc_f16_to_nchw_f32(mp, mom_out, B, ZC, H * Wd, st)); }, "nhwc_to_nchw", 0,
+             (double)B * ZC * H * Wd * 6);
+    }
+    release(m);
 }
 
 // ------------------------------------------------------------------------------------------------ CLIP

@@ -38,6 +38,11 @@ def read_checkpoint(path):
     return sd
 
 
+# opt-in graphs (convert --vae-encoder): not part of the txt2img containers, so the default tables, splits and files are unchanged
+OPTIONAL_GRAPHS = {
+    'vae_enc': ('first_stage_model.', 'vae_encoder'),    # encoder.* + quant_conv.*: the img2img path (Txt2Img(with_vae_encoder=True))
+}
+
 # SD v2.x (public ldm v2 checkpoints): same UNet / VAE prefixes, the text tower is open_clip's model under `.model.`
 GRAPHS_SD21 = dict(GRAPHS, text=('cond_stage_model.model.', 'text_encoder'))
 
@@ -49,13 +54,18 @@ def parameter_tables(cfg=None):
             'vae': E.VaeDecoder(cfg, 1).param_table(), 'text': E.TextEncoder(cfg, 1).param_table()}
 
 
+def vae_encoder_table(cfg=None):
+    """[(name, shape), ...] of the VAE encoder graph (img2img; opt-in, see OPTIONAL_GRAPHS); no device needed"""
+    return E.VaeEncoder(cfg or E.sd14_config(), 1).param_table()
+
+
 def split_state_dict(sd, tables=None, dtype=torch.float16):
     """Pick every graph's parameters out of a full checkpoint state dict.  Raises KeyError naming what is missing and
     ValueError on a shape mismatch; entries the graphs do not use (EMA copies, the VAE encoder, position_ids,
     loss / scheduler buffers) are ignored.  Returns ({graph: {name: tensor}}, [unused keys])."""
     tables = tables or parameter_tables()
     names = {n for n, _ in tables.get('text', [])}
-    prefixes = GRAPHS_SD21 if 'ln_final.weight' in names else GRAPHS      # open_clip text tower => an SD2.x checkpoint
+    prefixes = dict(GRAPHS_SD21 if 'ln_final.weight' in names else GRAPHS, **OPTIONAL_GRAPHS)  # open_clip text tower => SD2.x
     out, used, missing = {}, set(), []
     for graph, table in tables.items():
         prefix = prefixes[graph][0]
@@ -78,13 +88,17 @@ def split_state_dict(sd, tables=None, dtype=torch.float16):
     return out, sorted(k for k in sd if k not in used)
 
 
-def convert(ckpt_path, out_dir, dtype=torch.float16, cfg=None):
-    """checkpoint file -> out_dir/{unet,temb,vae_decoder,text_encoder}.sdodw; returns the list of files written"""
-    parts, _ = split_state_dict(read_checkpoint(ckpt_path), parameter_tables(cfg), dtype)
+def convert(ckpt_path, out_dir, dtype=torch.float16, cfg=None, vae_encoder=False):
+    """checkpoint file -> out_dir/{unet,temb,vae_decoder,text_encoder}.sdodw (+ vae_encoder.sdodw with vae_encoder=True);
+    returns the list of files written"""
+    tables = parameter_tables(cfg)
+    if vae_encoder:
+        tables = dict(tables, vae_enc=vae_encoder_table(cfg))
+    parts, _ = split_state_dict(read_checkpoint(ckpt_path), tables, dtype)
     os.makedirs(out_dir, exist_ok=True)
     written = []
     for graph, part in parts.items():
-        path = os.path.join(out_dir, GRAPHS[graph][1] + '.sdodw')
+        path = os.path.join(out_dir, dict(GRAPHS, **OPTIONAL_GRAPHS)[graph][1] + '.sdodw')
         weights.save(path, part)
         written.append(path)
     return written
@@ -96,11 +110,13 @@ def main(argv=None):
     ap.add_argument('--out', required=True, help='models_dir to write')
     ap.add_argument('--fp32', action='store_true', help='keep fp32 payloads (the engine converts at load)')
     ap.add_argument('--model', default='sd14', choices=['sd14', 'sd21'], help='sd21: SD v2.x shapes and open_clip text-tower key names')
+    ap.add_argument('--vae-encoder', action='store_true', help='also write vae_encoder.sdodw (first_stage_model.encoder + '
+                                                                'quant_conv), the img2img path')
     ap.add_argument('--tokenizer-vocab', help='bpe_simple_vocab_16e6.txt.gz, or a directory with HF vocab.json + merges.txt: '
                                               'also write ctokenizer.txt')
     a = ap.parse_args(argv)
     cfg = E.sd21_config() if a.model == 'sd21' else None
-    for p in convert(a.ckpt, a.out, torch.float32 if a.fp32 else torch.float16, cfg):
+    for p in convert(a.ckpt, a.out, torch.float32 if a.fp32 else torch.float16, cfg, vae_encoder=a.vae_encoder):
         print('wrote', p)
     if a.tokenizer_vocab:
         from . import tokenizer_file

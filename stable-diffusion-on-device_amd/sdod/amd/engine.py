@@ -9,7 +9,7 @@ import torch
 from . import _lib
 from ._lib import check
 
-UNET, VAE_DECODER, TEXT_ENCODER, TEMB = 0, 1, 2, 3
+UNET, VAE_DECODER, TEXT_ENCODER, TEMB, VAE_ENCODER = 0, 1, 2, 3, 4
 
 
 class ModelConfig(ctypes.Structure):
@@ -254,4 +254,18 @@ class VaeDecoder(Graph):
         c, b = self.cfg, self.batch
         self.z = self.io_tensor(False, 0, (b, c.latent_channels, c.latent_h, c.latent_w), torch.float32)
         self.img = self.io_tensor(True, 0, (b, 8 * c.latent_h, 8 * c.latent_w, 3), torch.float16)
+        return self
+
+
+class VaeEncoder(Graph):
+    """first_stage_model.encoder + quant_conv: uint8 image [B, 8H, 8W, 3] -> fp32 moments [B, 8, H, W] (mean | logvar)"""
+
+    def __init__(self, cfg, batch, device='cuda:0'):
+        super().__init__(VAE_ENCODER, cfg, batch, device)
+
+    def finalize(self):
+        super().finalize()
+        c, b = self.cfg, self.batch
+        self.img = self.io_tensor(False, 0, (b, 8 * c.latent_h, 8 * c.latent_w, 3), torch.uint8)
+        self.moments = self.io_tensor(True, 0, (b, 2 * c.latent_channels, c.latent_h, c.latent_w), torch.float32)
         return self

@@ -62,6 +62,7 @@ def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=N
     """out = act(alpha * A @ W^T + bias + row_bias) + residual.
 
     a: fp16 [M, K] (rows mode) or NHWC [N, H, W, C0] with conv=dict(stride=1|2, upsample=bool) (3x3 pad 1);
+    conv=dict(stride=2, pad_mode=1): ldm's VAE-encoder Downsample, F.pad(a, (0, 1, 0, 1)) then a 3x3 stride-2 pad-0 conv;
     a2: optional second NHWC source concatenated on channels; w: fp16 [Nout, K] (conv: K = 9*(C0+C1), KRSC)."""
     lib = _lib.hip()
     _req(a, torch.float16, 'a')
@@ -96,9 +97,12 @@ def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=N
             c1 = a2.shape[3]
         stride = int(conv.get('stride', 1)); ups = 1 if conv.get('upsample', False) else 0
         ks = int(conv.get('ksize', 3))
+        pad_mode = int(conv.get('pad_mode', 0))
+        pad_sum = 1 if pad_mode else 2 * (ks // 2)
         hup, wup = h << ups, wd << ups
-        ho, wo = (hup + 2 * (ks // 2) - ks) // stride + 1, (wup + 2 * (ks // 2) - ks) // stride + 1
+        ho, wo = (hup + pad_sum - ks) // stride + 1, (wup + pad_sum - ks) // stride + 1
         d.ksize = ks
+        d.pad_mode = pad_mode
         m = n_img * ho * wo
         d.a_mode = 1
         d.n_img, d.h_in, d.w_in, d.c0, d.c1 = n_img, h, wd, c0, c1
@@ -396,6 +400,38 @@ def conv_in(x, w, bias, scale=1.0):
     out = torch.empty((n, h, wd, cout), dtype=torch.float16, device=x.device)
     check(lib.sdod_conv_in_f16(_p(x), _p(w), _p(bias), _p(out), n, h, wd, c, cout, scale, _stream()))
     return out
+
+
+def image_conv_in(img_u8, w, bias):
+    """the VAE encoder's input convolution in one launch (sdod_image_conv_in_f16): uint8 HWC RGB [n, h, w, 3] -> 2 u / 255 - 1 ->
+    3x3 pad-1 conv with w fp16 [cout, 64] (PK_CONV3_SMALL packing) + bias fp32 [cout] -> NHWC fp16 [n, h, w, cout]"""
+    lib = _lib.hip()
+    _req(img_u8, torch.uint8, 'img'); _req(w, torch.float16, 'w'); _req(bias, torch.float32, 'bias')
+    n, h, wd, c = img_u8.shape
+    assert c == 3 and w.shape[1] == 64
+    cout = w.shape[0]
+    out = torch.empty((n, h, wd, cout), dtype=torch.float16, device=img_u8.device)
+    check(lib.sdod_image_conv_in_f16(_p(img_u8), _p(w), _p(bias), _p(out), n, h, wd, cout, _stream()))
+    return out
+
+
+def encode_latent(moments, sqrt_at, sqrt_one_minus_at, seed=0, image_index=0, n1=None, n2=None, z0=None):
+    """ldm img2img's start latent from fp32 NCHW moments [n, 2c, h, w] (sdod_encode_latent_f32): posterior sample with n1,
+    0.18215 scale, stochastic_encode with n2.  n1 / n2 None: Philox on the device, streams (1 << 32) | (image_index + i) and
+    (2 << 32) | (image_index + i).  z0: optional fp32 [n, c, h, w] that receives 0.18215 * sample.  Returns x fp32 [n, c, h, w]."""
+    lib = _lib.hip()
+    _req(moments, torch.float32, 'moments')
+    n, c2, h, w = moments.shape
+    c = c2 // 2
+    shape = (n, c, h, w)
+    for t, name in ((n1, 'n1'), (n2, 'n2'), (z0, 'z0')):
+        if t is not None:
+            _req(t, torch.float32, name)
+            assert tuple(t.shape) == shape, (name, t.shape, shape)
+    x = torch.empty(shape, dtype=torch.float32, device=moments.device)
+    check(lib.sdod_encode_latent_f32(_p(moments), _p(n1), _p(n2), _p(x), _p(z0), n, c, h * w, float(sqrt_at), float(sqrt_one_minus_at),
+                                     int(seed), int(image_index), _stream()))
+    return x
 
 
 def nchw_f32_to_nhwc_f16(x, scale=1.0):

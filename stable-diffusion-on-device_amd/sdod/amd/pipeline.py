@@ -16,11 +16,14 @@ from .samplers import PLMS_ORDERS, PlmsSchedule
 
 class Txt2Img:
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
-                 tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None):
+                 tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
+                 with_vae_encoder=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
-        ViT-H/14 text tower (open_clip key names, penultimate block + ln_final, prompts padded with id 0 after EOT)."""
+        ViT-H/14 text tower (open_clip key names, penultimate block + ln_final, prompts padded with id 0 after EOT).
+        with_vae_encoder=True: also build the VAE encoder (state_dicts['vae_enc'] or models_dir/vae_encoder.sdodw) for img2img();
+        off, nothing of it is constructed or loaded."""
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self.n = images_per_gpu
@@ -55,10 +58,12 @@ class Txt2Img:
         self.unet = E.UNet(self.cfg, self.n if cfg_split else 2 * self.n, device)
         self.vae = E.VaeDecoder(self.cfg, 1, device) if with_vae else None
         self.text = E.TextEncoder(self.cfg, 2, device) if with_text_encoder else None
+        self.encoder = E.VaeEncoder(self.cfg, 1, device) if with_vae_encoder else None
         self._temb_graphs = {}
         self._sd = state_dicts
         self._dir = models_dir
-        for g, key, stem in ((self.unet, 'unet', 'unet'), (self.vae, 'vae', 'vae_decoder'), (self.text, 'text', 'text_encoder')):
+        for g, key, stem in ((self.unet, 'unet', 'unet'), (self.vae, 'vae', 'vae_decoder'), (self.text, 'text', 'text_encoder'),
+                             (self.encoder, 'vae_enc', 'vae_encoder')):
             if g is None:
                 continue
             self._load(g, key, stem)
@@ -252,6 +257,87 @@ class Txt2Img:
         g.replay()
         return out
 
+    # ------------------------------------------------------------------ img2img (ldm scripts/img2img.py, DDIM eta = 0)
+    def encode(self, init_u8, seed=0, image_index=0, strength=0.75, steps=50, noise=None):
+        """uint8 [n, 8H, 8W, 3] -> x fp32 [n, 4, H, W]: the VAE encoder, a posterior sample scaled by 0.18215, and ldm's
+        stochastic_encode to ddim index t_enc = int(strength * steps).  noise = (n1, n2), fp32 [n, 4, H, W] each, or None: drawn
+        on the device (Philox, seed, streams (1 << 32) | index and (2 << 32) | index with index = image_index + i)."""
+        if self.encoder is None:
+            raise RuntimeError('Txt2Img(..., with_vae_encoder=True) is needed for img2img')
+        sch, t_enc = img2img_schedule(strength, steps)
+        init_u8 = init_u8.to(self.device)
+        xs = []
+        for i in range(init_u8.shape[0]):
+            self.encoder.img.copy_(init_u8[i:i + 1])
+            self.encoder.execute(self.use_hip_graph)
+            n1, n2 = (None, None) if noise is None else (noise[0][i:i + 1].to(self.device, torch.float32).contiguous(),
+                                                         noise[1][i:i + 1].to(self.device, torch.float32).contiguous())
+            xs.append(ops.encode_latent(self.encoder.moments, float(sch.sqrt_alphas[t_enc]), float(sch.sqrt_one_minus_alphas[t_enc]),
+                                        seed, image_index + i, n1, n2))
+        return torch.cat(xs, 0)
+
+    def sample_ddim_from(self, ctx2, x, t_enc, steps=50, guidance=7.5, trace=None):
+        """ldm DDIMSampler.decode: t_enc DDIM steps (eta = 0, CFG mode 1) from ddim index t_enc - 1 down to 0"""
+        sch = PlmsSchedule(steps)
+        temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
+        self._set_context(ctx2)
+        x = x.to(self.device, torch.float32).clone()
+        for i in range(t_enc):
+            index = t_enc - i - 1
+            e_t = self._eps(x, temb[index], guidance, mode=1)
+            ops.ddim_step(x, e_t, **sch.coef(index))
+            if trace is not None:
+                trace.append((int(sch.timesteps[index]), index))
+        return x
+
+    def img2img(self, ctx2, init_u8, strength=0.75, steps=50, guidance=7.5, seed=0, noise=None, image_index=0, trace=None):
+        """ldm scripts/img2img.py: encode the init image, noise it to ddim index int(strength * steps), denoise, decode to uint8"""
+        _, t_enc = img2img_schedule(strength, steps)
+        x = self.encode(init_u8, seed, image_index, strength, steps, noise)
+        z = self.sample_ddim_from(ctx2, x, t_enc, steps, guidance, trace)
+        return self.decode(z, mode=1)
+
+    def img2img_graphed(self, ctx2, init_u8, strength=0.75, steps=50, guidance=7.5, seed=0, noise=None, image_index=0):
+        """img2img() as ONE device graph replay (encoder, start latent, every UNet evaluation, DDIM updates, decoder, uint8), captured
+        once per (t_enc, steps, guidance, shape) from the eager path.  The noise is always an input of the graph: without `noise`
+        it is drawn into it first by sdod_randn_f32 on the streams encode() uses, which is what the encoder's in-kernel draw gives
+        bit for bit, so the result equals img2img() with the same arguments."""
+        _, t_enc = img2img_schedule(strength, steps)
+        if self.cfg_split:
+            return self.img2img(ctx2, init_u8, strength, steps, guidance, seed, noise, image_index)
+        n = init_u8.shape[0]
+        lat = (n, self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
+        key = ('img2img', t_enc, int(steps), float(guidance), tuple(init_u8.shape))
+        cache = self.__dict__.setdefault('_traj', {})
+        if key not in cache:
+            s_ctx = torch.empty_like(ctx2, device=self.device)
+            s_img = torch.empty(tuple(init_u8.shape), dtype=torch.uint8, device=self.device)
+            s_n1 = torch.zeros(lat, dtype=torch.float32, device=self.device)
+            s_n2 = torch.zeros(lat, dtype=torch.float32, device=self.device)
+            s_ctx.copy_(ctx2); s_img.copy_(init_u8)
+            keep = self.use_hip_graph
+            self.use_hip_graph = False          # inside a capture the graphs run their launch lists
+            try:
+                self.img2img(s_ctx, s_img, strength, steps, guidance, noise=(s_n1, s_n2))     # warm-up
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                    out = self.img2img(s_ctx, s_img, strength, steps, guidance, noise=(s_n1, s_n2))
+            finally:
+                self.use_hip_graph = keep
+            cache[key] = (g, s_ctx, s_img, s_n1, s_n2, out)
+        g, s_ctx, s_img, s_n1, s_n2, out = cache[key]
+        s_ctx.copy_(ctx2); s_img.copy_(init_u8)
+        if noise is None:
+            per = lat[1:]
+            for i in range(n):
+                s_n1[i:i + 1].copy_(ops.randn((1,) + per, seed, (1 << 32) | (image_index + i), self.device))
+                s_n2[i:i + 1].copy_(ops.randn((1,) + per, seed, (2 << 32) | (image_index + i), self.device))
+        else:
+            s_n1.copy_(noise[0]); s_n2.copy_(noise[1])
+        g.replay()
+        return out
+
     def generate_pipelined(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms'):
         """generate_graphed() as TWO device graphs -- sampling (context upload, every UNet evaluation, CFG, sampler updates) on
         the current stream and decoding (VAE + uint8) on a side stream -- so that the decode of image i runs while image i+1 is
@@ -303,6 +389,20 @@ class Txt2Img:
             c['g_d'].replay()
             c['decoded'] = torch.cuda.Event(); c['decoded'].record(c['side'])
         return c['out'], c['decoded']
+
+
+def img2img_schedule(strength, steps):
+    """(PlmsSchedule(steps), t_enc) of ldm img2img: t_enc = int(strength * steps), noise added at ddim index t_enc, the first
+    denoising step at timesteps[t_enc - 1].  ldm fails at t_enc == steps (index out of range) and does nothing at 0, so the
+    domain is 1 <= t_enc <= steps - 1; anything else raises ValueError before any device work."""
+    strength = float(strength)
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError(f'strength must be in [0, 1], got {strength}')
+    steps = int(steps)
+    t_enc = int(strength * steps)
+    if not 1 <= t_enc <= steps - 1:
+        raise ValueError(f'int(strength * steps) = {t_enc} is outside [1, steps - 1] = [1, {steps - 1}]')
+    return PlmsSchedule(steps), t_enc
 
 
 def broadcast_conditioning(ctx2, src=0):

@@ -25,6 +25,8 @@ only_geglu = '--only-geglu' in sys.argv   # re-time the LayerNorm-folded GEGLU p
 only_softmax = '--only-softmax' in sys.argv # re-time the score GEMMs of the folded cross-attention (key flag bit 28)
 only_tail = '--only-tail' in sys.argv     # re-time the 3x3 convolutions with a fused 1x1 skip (key flags: tc0 in bits 2..13)
 only_new = '--only-new' in sys.argv       # keep EVERY shipped pick, time only the shapes the table does not have yet (a new fusion's GEMMs)
+only_vae_enc = '--only-vae-encoder' in sys.argv  # keep EVERY shipped pick, time the VAE encoder's new shapes (img2img; key flag bit 26 = pad_mode)
+only_new = only_new or only_vae_enc
 if os.path.exists(out):
     os.remove(out)
 os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -71,6 +73,17 @@ def build(cls, cfg, batch, seed, label, quant=False):
     print(f'[{time.time() - T0:6.1f}s] {label}: {g.stats()["launches"]} launches; table now {n} shapes', flush=True)
     del g
 
+
+def vae_encoders():
+    # img2img: 512 px (batch 1 and 2), 768 px, and the reduced size the GPU tests run
+    for hw, b in ((64, 1), (64, 2), (96, 1), (16, 1)):
+        build(E.VaeEncoder, E.sd14_config(hw, hw), b, 1238, f'vae encoder {hw}x{hw} b{b}')
+
+
+if only_vae_enc:
+    vae_encoders()
+    print(f'done: {out}')
+    sys.exit(0)
 
 if only_quant:
     for hw in (96, 24):
@@ -137,4 +150,5 @@ if not quick:
     build(E.VaeDecoder, c16, 1, 1236, 'vae 16x16')
     c24 = E.sd21_config(24, 24)
     build(E.UNet, c24, 2, 2100, 'sd21 unet 24x24 b2')
+    vae_encoders()
 print(f'done: {out}')
