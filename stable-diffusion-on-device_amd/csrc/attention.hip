@@ -20,6 +20,7 @@
 #include "sdod_hip.h"
 #include "host_util.h"
 
+#include <climits>
 #include <cstdlib>
 #include <type_traits>
 
@@ -79,6 +80,15 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
     // d = 40: V is padded to 48 columns; a column of ones there makes the PV product accumulate the softmax row sum
     // (sum of the SAME fp16-rounded probabilities that weight V) -- 16 packed adds per tile and query tile less on the VALU
     constexpr bool SUM_BY_MFMA = DV > D;
+    // d = 40 / 80: the QK^T contraction is padded too (40 -> 64, 80 -> 96); its column D carries the softmax shift into the MFMA.
+    // K holds -1 there and Q (prescaled by scale * log2 e) the running shift m, so the MFMA returns s * scale_log2 - m, the
+    // exponent itself.  m is DEFERRED: it only has to stay within THR of the true running maximum, which every lane checks on its
+    // own scores (a max tree and a wave vote ahead of the exps); only a vote -- and each group's first tile -- takes the exact
+    // four-lane maximum, rescales O and writes the new m into Q's column D.  m is held as an fp16 value (it is an MFMA operand),
+    // and that exact value is the shift of P, of the rescale and of the KVS merge alike.
+    constexpr bool DEFER = DP > D;
+    constexpr int KS_M = D / 32, G_M = (D % 32) / 8; // Q fragment (k-step, lane group) that holds contraction element D
+    constexpr float THR = 8.0f;                      // log2 units: P <= 2^8 on the common path, far inside fp16
     static_assert(D % 8 == 0, "head dim must be a multiple of 8");
 
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -112,7 +122,9 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
             if (KPADC > 0)
                 for (int idx = tid; idx < KT * KPADC; idx += 256) {
                     const int row = idx / (KPADC > 0 ? KPADC : 1), ch = idx - row * KPADC;
-                    *reinterpret_cast<f16x8*>(sK + row * KSTR + D + ch * 8) = zero8();
+                    f16x8 pad = zero8();
+                    if (DEFER && ch == 0) pad[0] = (f16)-1.0f; // column D: minus the shift held in Q's column D
+                    *reinterpret_cast<f16x8*>(sK + row * KSTR + D + ch * 8) = pad;
                 }
             if (VPADC > 0)
                 for (int idx = tid; idx < KT * VPADC; idx += 256) {
@@ -135,6 +147,9 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
         for (int ks = 0; ks < KSTEPS; ++ks) {
             const int d0 = ks * 32 + g * 8;
             qf[t][ks] = (qrow[t] < p.Lq && d0 + 8 <= D) ? ldg8(qp + d0) : zero8();
+            if (DEFER) // the softmax scale (log2 units) folded into Q once: one more fp16 rounding of Q, no per-score multiply
+#pragma unroll
+                for (int e = 0; e < 8; ++e) qf[t][ks][e] = (f16)((float)qf[t][ks][e] * p.scale_log2);
         }
     }
 
@@ -195,7 +210,7 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
     float m_run[QT], l_run[QT];
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
-        m_run[t] = -1e30f;
+        m_run[t] = DEFER ? 0.f : -1e30f; // (DEFER: the zero Q column D holds; the first tile sets m whatever it is)
         l_run[t] = 0.f;
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) o[t][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -217,9 +232,12 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
     };
     // ---- online softmax of query tile A against key tile t (scores in s_a) and O^T += V^T . P^T; lane owns query qrow[A],
     // keys t*64 + c*16 + 4g + r.  VALU budget matters here (at d=40 the MFMAs of a tile take ~450 cycles, a naive softmax 3x
-    // that): the row max is taken on the RAW scores (scale > 0), exp2(s*c - m*c) is one fma + one v_exp, masking code only
-    // runs for tiles that contain masked keys (the last ragged tile / the causal diagonal).
-    auto softmax_pv = [&](auto a_c, int t, f32x4 (&s_a)[4], const f16x8 (&vfr)[HOLD ? 2 : 1][HOLD ? NDT : 1], const f16* sV) {
+    // that): DEFER (d = 40 / 80) the MFMA already returned the exponent, the common path is a lane-local max tree, a vote and
+    // one v_exp per score; otherwise the row max is taken on the RAW scores (scale > 0) and exp2(s*c - m*c) is one fma + one
+    // v_exp.  Masking code only runs for tiles that contain masked keys (the last ragged tile / the causal diagonal).
+    // thr (DEFER only): the vote threshold's bit pattern, INT_MIN on a group's first tile.
+    auto softmax_pv = [&](auto a_c, int t, int thr, f32x4 (&s_a)[4], const f16x8 (&vfr)[HOLD ? 2 : 1][HOLD ? NDT : 1],
+                          const f16* sV) {
         constexpr int a = decltype(a_c)::value;
         const bool need_mask = (t * KT + KT > p.Lk) || (p.causal && (t * KT + KT - 1 > q_block + wave * (16 * QT)));
         if (need_mask) {
@@ -238,8 +256,7 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
         }
         // row maximum of this lane's 16 scores: three-input maxima (v_max3_f32: 8 instructions instead of 15) as a TREE of depth 3,
         // not a chain of 8 -- the maximum heads the tile's dependent chain (max -> exp -> PV)
-        float mx;
-        {
+        auto lane_max = [&]() {
             const float t0 = fmaxf(fmaxf(s_a[0][0], s_a[0][1]), s_a[0][2]);
             const float t1 = fmaxf(fmaxf(s_a[0][3], s_a[1][0]), s_a[1][1]);
             const float t2 = fmaxf(fmaxf(s_a[1][2], s_a[1][3]), s_a[2][0]);
@@ -247,38 +264,89 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
             const float t4 = fmaxf(fmaxf(s_a[3][0], s_a[3][1]), s_a[3][2]);
             const float u0 = fmaxf(fmaxf(t0, t1), t2);
             const float u1 = fmaxf(fmaxf(t3, t4), s_a[3][3]);
-            mx = fmaxf(u0, u1);
-        }
-        // the four lanes that share a query: row swaps in VALU latency instead of two ds_bpermute round trips on the loop's
-        // critical path (common.h: quad_rows_max; profiles/r03_attention_permlane.txt)
-        mx = quad_rows_max(mx);
-        const float m_new = fmaxf(m_run[a], mx * p.scale_log2); // running max in scaled (log2) units
-        // once the running maxima have settled (a few tiles in) no lane of the wave changes its maximum: skip the
-        // rescale of the output accumulators (wave-uniform branch)
-        const bool rescale = __builtin_amdgcn_ballot_w64(m_new != m_run[a]) != 0;
-        const float alpha = rescale ? __builtin_amdgcn_exp2f(m_run[a] - m_new) : 1.0f;
-        m_run[a] = m_new;
-        // plain fp32 fma / add, NOT the packed forms: beside MFMAs a v_pk_add_f32 / v_pk_fma_f32 costs several times the issue
-        // cycles of the two scalar instructions it replaces (MI355X_MICROARCH.md, per-instruction constants: an anti-lever), and
-        // this loop is bound by the SIMD's vector issue (-ffp-contract=off: the fma is spelled out)
+            return fmaxf(u0, u1);
+        };
         float rs[4] = {0.f, 0.f, 0.f, 0.f};
-        const float sc = p.scale_log2, nm = -m_new;
+        if constexpr (DEFER) {
+            // s_a = s * scale_log2 - m already.  Vote: does any score of the wave exceed m by more than THR?  The lane's maximum
+            // is taken on the bit patterns as signed integers (v_max3_i32): exact for the comparison against a positive
+            // threshold (every negative float is a negative integer) and free of the canonicalising moves fmaxf costs on MFMA
+            // results.  On a group's first tile (thr = INT_MIN) every wave takes the branch.
+            auto bi = [](float x) { return __builtin_bit_cast(int, x); };
+            auto mx3 = [](int x, int y, int z) { return max(max(x, y), z); };
+            const int t0 = mx3(bi(s_a[0][0]), bi(s_a[0][1]), bi(s_a[0][2]));
+            const int t1 = mx3(bi(s_a[0][3]), bi(s_a[1][0]), bi(s_a[1][1]));
+            const int t2 = mx3(bi(s_a[1][2]), bi(s_a[1][3]), bi(s_a[2][0]));
+            const int t3 = mx3(bi(s_a[2][1]), bi(s_a[2][2]), bi(s_a[2][3]));
+            const int t4 = mx3(bi(s_a[3][0]), bi(s_a[3][1]), bi(s_a[3][2]));
+            const int mi = max(mx3(t0, t1, t2), mx3(t3, t4, bi(s_a[3][3])));
+            if (__builtin_amdgcn_ballot_w64(mi > thr) != 0) {
+                const bool first = thr == INT_MIN;
+                // rare (and each group's first tile): the exact maximum of the query's 64 scores, a new shift rounded to fp16,
+                // O (and at d = 80 the row sum) rescaled to it, Q's column D updated for the next tiles, and THIS tile's
+                // exponents re-based BEFORE any exp2 of it is taken -- nothing computed at the old shift reaches P . V
+                const float mx = quad_rows_max(lane_max());
+                const float m_old = m_run[a];
+                float m_new = m_old;
+                if (first || mx > 0.f) m_new = (float)(f16)fminf(fmaxf(m_old + mx, -65504.f), 65504.f);
+                const float delta = m_new - m_old;
+                if (!first) { // (O and l are still zero on the first tile)
+                    const float alpha = __builtin_amdgcn_exp2f(-delta);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
+                    for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float v = __builtin_fmaf(s_a[c][r], sc, nm);
-                if (!(abl & 2)) v = __builtin_amdgcn_exp2f(v);
-                if (!SUM_BY_MFMA) rs[r] += v;
-                s_a[c][r] = v;
+                        for (int r = 0; r < 4; ++r) o[a][dt][r] *= alpha;
+                    if (!SUM_BY_MFMA) l_run[a] *= alpha;
+                }
+                m_run[a] = m_new;
+                if (g == G_M) qf[a][KS_M][0] = (f16)m_new;
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s_a[c][r] -= delta;
             }
-        }
-        if (!SUM_BY_MFMA) l_run[a] = __builtin_fmaf(l_run[a], alpha, (rs[0] + rs[1]) + (rs[2] + rs[3]));
-        if (rescale) {
 #pragma unroll
-            for (int dt = 0; dt < NDT; ++dt)
+            for (int c = 0; c < 4; ++c) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o[a][dt][r] *= alpha;
+                for (int r = 0; r < 4; ++r) {
+                    float v = s_a[c][r];
+                    if (!(abl & 2)) v = __builtin_amdgcn_exp2f(v);
+                    if (!SUM_BY_MFMA) rs[r] += v;
+                    s_a[c][r] = v;
+                }
+            }
+            if (!SUM_BY_MFMA) l_run[a] += (rs[0] + rs[1]) + (rs[2] + rs[3]);
+        } else {
+            // the four lanes that share a query: row swaps in VALU latency instead of two ds_bpermute round trips on the loop's
+            // critical path (common.h: quad_rows_max; profiles/r03_attention_permlane.txt)
+            const float mx = quad_rows_max(lane_max());
+            const float m_new = fmaxf(m_run[a], mx * p.scale_log2); // running max in scaled (log2) units
+            // once the running maxima have settled (a few tiles in) no lane of the wave changes its maximum: skip the
+            // rescale of the output accumulators (wave-uniform branch)
+            const bool rescale = __builtin_amdgcn_ballot_w64(m_new != m_run[a]) != 0;
+            const float alpha = rescale ? __builtin_amdgcn_exp2f(m_run[a] - m_new) : 1.0f;
+            m_run[a] = m_new;
+            // plain fp32 fma / add, NOT the packed forms: beside MFMAs a v_pk_add_f32 / v_pk_fma_f32 costs several times the
+            // issue cycles of the two scalar instructions it replaces (MI355X_MICROARCH.md, per-instruction constants: an
+            // anti-lever), and this loop is bound by the SIMD's vector issue (-ffp-contract=off: the fma is spelled out)
+            const float sc = p.scale_log2, nm = -m_new;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float v = __builtin_fmaf(s_a[c][r], sc, nm);
+                    if (!(abl & 2)) v = __builtin_amdgcn_exp2f(v);
+                    if (!SUM_BY_MFMA) rs[r] += v;
+                    s_a[c][r] = v;
+                }
+            }
+            if (!SUM_BY_MFMA) l_run[a] = __builtin_fmaf(l_run[a], alpha, (rs[0] + rs[1]) + (rs[2] + rs[3]));
+            if (rescale) {
+#pragma unroll
+                for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o[a][dt][r] *= alpha;
+            }
         }
         f16x8 pf[2];
 #pragma unroll
@@ -349,6 +417,7 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
     }
     __syncthreads();
     const int NTG = (NT + KVS - 1) / KVS; // every group runs the same number of iterations (the barriers are workgroup-wide)
+    int thr = INT_MIN;                    // DEFER: the vote threshold of softmax_pv (INT_MIN: a group's first tile)
     for (int it = 0; it < NTG; ++it) {
         const int t = it * KVS + grp;
         const int cur = it & 1;
@@ -374,7 +443,11 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
         // iteration, the compiler's wait-count pass (it cannot count loads under divergent predicates) put a vmcnt(0) in front
         // of the first MFMA, i.e. the full global-load latency on the critical path of every tile
         if (has_next && !(abl & 1)) load_tile(t + KVS);
-        static_for<QT>([&](auto a_c) { softmax_pv(a_c, t, s[decltype(a_c)::value], vfr, sV); });
+        static_for<QT>([&](auto a_c) { softmax_pv(a_c, t, thr, s[decltype(a_c)::value], vfr, sV); });
+        // (opaque to the compiler: a threshold it can see change after the first iteration makes it peel that iteration,
+        // and the peeled copy costs d = 80 its register budget -- spills)
+        thr = __builtin_bit_cast(int, THR);
+        asm volatile("" : "+s"(thr));
         if (has_next) store_tile(cur ^ 1);
         __syncthreads();
     }
