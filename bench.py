@@ -7,13 +7,18 @@ guidance 7.5: CLIP text encode (uncond + cond) -> 21 batched (uncond, cond) UNet
 image(s); rank 0 encodes the prompt and the conditioning is sent with ONE RCCL broadcast).  Synthetic seeded weights
 (no checkpoint exists offline), fixed token ids, injected x_T; all inputs are resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0).  Extra blocks:
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set-up (weights, graphs, the
+trajectory-graph capture), --warmup untimed steps, --steps timed steps, the optional dump, the line.  Extra blocks:
+  dump_outputs -- with --dump-outputs DIR: the files written there (the last timed step's images; the inputs -- weights,
+                  token ids, the step's x_T -- depend on the arguments only, so two builds can be compared file for file)
+  rccl         -- with --gpus N > 1: every rank's own time and device, gathered by the collective itself
+With --full, after the timed steps (nothing of it runs in a plain run):
+  unet_step_ms -- one guided UNet evaluation + sampler update, HIP-graph replay, timed with events
   roofline     -- for the dominant kernel family of the UNet launch list: algorithmic FLOPs (or bytes) per launch
                   divided by its average launch duration, measured in this process with HIP events on the launch stream
   cpu_baseline -- the oracle (PyTorch-CPU fp32 restatement, kind "port") timed on the host cores on a bounded sample
+                  (--no-cpu-baseline leaves it and parity out)
   parity       -- GPU fp16 vs CPU fp32 on the first guided UNet evaluation of this very run
-  dump_outputs -- with --dump-outputs DIR: the files written there (the last timed step's images; the inputs -- weights,
-                  token ids, the step's x_T -- depend on the arguments only, so two builds can be compared file for file)
 """
 import argparse
 import json
@@ -85,7 +90,9 @@ def parse():
     ap.add_argument('--steps', type=int, default=3, help='timed images per GPU')
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--images-per-gpu', type=int, default=1)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also measure the per-UNet-step time, the roofline '
+                    'of the dominant kernel family and (rank 0, one GPU, the headline sampler) the CPU baseline + in-run parity')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baseline and parity blocks')
     ap.add_argument('--overlap-decode', action='store_true', help='experiment: decode image i on a side stream while image i+1 is sampled (measured slower)')
     ap.add_argument('--no-hip-graph', action='store_true')
     ap.add_argument('--sampler', default='plms', choices=['plms', 'dpm'], help="plms: the headline workload (config 3); dpm: the reference "
@@ -180,7 +187,7 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    from sdod.amd import engine as E, ops, weights as Wt
+    from sdod.amd import engine as E, weights as Wt
     from sdod.amd.pipeline import Txt2Img, broadcast_conditioning, device_latent, initial_latent
 
     t_setup = time.time()
@@ -194,13 +201,12 @@ def main():
     log('uploading weights / building graphs')
     pipe = Txt2Img(state_dicts=sds, images_per_gpu=n, latent_hw=64, device=f'cuda:{dev_index}',
                    use_hip_graph=not args.no_hip_graph, cfg_split=args.cfg_split)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and (args.sampler, args.sampler_steps) == ('plms', 20)
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and (args.sampler, args.sampler_steps) == ('plms', 20)
     if not want_cpu:
         sds = None
     setup_s = time.time() - t_setup
 
     img_owner = rank // 2 if args.cfg_split else rank       # latency mode: both ranks of a pair work on the same images
-    x_T = torch.cat([initial_latent(42, img_owner * n + i) for i in range(n)]).to(device)
     ids_u, ids_c = np.asarray(IDS_UNCOND), np.asarray(IDS_COND)
 
     n_images_per_step = n * (world // 2 if args.cfg_split else world)
@@ -278,15 +284,59 @@ def main():
     assert img.shape == (n, 512, 512, 3) and img.dtype == torch.uint8
     log(f'timed region: {elapsed:.3f}s for {args.steps} step(s)')
 
-    # ---- per-UNet-step time (batched cond+uncond evaluation + CFG + sampler update), HIP-graph replay, same stream
-    ctx2 = pipe.encode_tokens(ids_u, ids_c) if rank == 0 else torch.zeros(2, 77, 768, dtype=torch.float16, device=device)
-    pipe._set_context(ctx2)
-    temb = pipe.time_embeddings(np.asarray([951.0], np.float32))
+    unet_step_ms = roof = ctx2 = temb = x_T = None
+    if args.full:
+        ctx2 = pipe.encode_tokens(ids_u, ids_c) if rank == 0 else torch.zeros(2, 77, 768, dtype=torch.float16, device=device)
+        pipe._set_context(ctx2)
+        temb = pipe.time_embeddings(np.asarray([951.0], np.float32))
+        x_T = torch.cat([initial_latent(42, img_owner * n + i) for i in range(n)]).to(device)
+        unet_step_ms = unet_step_time(pipe, temb, x_T)
+        if rank == 0:
+            log(f'per-UNet-step {unet_step_ms:.3f} ms; profiling the launch list')
+            roof = roofline(pipe, unet_step_ms)
+
+    out = None
+    if rank == 0:
+        value = args.steps * n * (world // 2 if args.cfg_split else world) / elapsed
+        out = {
+            'metric': METRIC, 'value': round(value, 4), 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': round(1e3 * elapsed / args.steps, 3), 'higher_is_better': True,
+            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f16', 'data': 'synthetic',
+            'config': {'workload': ('SD v1.4 txt2img 512x512, 20-step PLMS (21 UNet evals, batch 2 = cond+uncond per image), '
+                                    'CLIP encode + VAE decode + uint8, guidance 7.5') if (args.sampler, args.sampler_steps) == ('plms', 20) else
+                                   f'SD v1.4 txt2img 512x512, {args.sampler_steps}-step {args.sampler.upper()}, CLIP encode + VAE decode + uint8, guidance 7.5',
+                       'images_per_gpu': n, 'global_batch': n * (world // 2 if args.cfg_split else world), 'parallelism': (f'dp{world // 2} x cfg-split pairs (1 broadcast + 1 all-gather per UNet evaluation)' if args.cfg_split
+                                       else f'dp{world} (image shards, 1 RCCL broadcast)'),
+                       'hip_graph': not args.no_hip_graph,
+                       'trajectory_graph': not (args.per_step_launches or args.no_hip_graph),
+                       'decode_overlaps_next_sampling': bool(args.overlap_decode) and not (args.per_step_launches or args.no_hip_graph)},
+        }
+        if args.full:
+            out.update(unet_step_ms=round(unet_step_ms, 3), roofline=roof)
+        out['setup_s'] = round(setup_s, 1)
+        if rccl is not None:
+            out['rccl'] = rccl
+
+        if want_cpu:
+            z_gpu = pipe.sample_plms(ctx2, x_T, steps=20, guidance=7.5)
+            out.update(cpu_baseline_and_parity(pipe, sds, x_T, ctx2, e_gpu=pipe._eps(x_T, temb[0], 7.5, 1),
+                                               img_gpu=pipe.decode(z_gpu, mode=1), z_gpu=z_gpu))
+        if last_images is not None:
+            out['dump_outputs'] = {'dir': args.dump_outputs, 'files': dump_outputs(args.dump_outputs, 'images', last_images)}
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def unet_step_time(pipe, temb, x_T):
+    """--full: ms of one step of the sampler loop as sample_plms runs it from its second step on (batched cond+uncond UNet
+    evaluation as a HIP-graph replay, then ONE launch for guidance + multistep combination + DDIM update + staging of the
+    next evaluation's inputs: ops.plms_update), averaged over 10 steps between two events on the launch stream"""
+    from sdod.amd import ops
+    from sdod.amd.samplers import PlmsSchedule, PLMS_ORDERS
     x = x_T.clone()
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    # one step of the sampler loop as sample_plms runs it from its second step on: UNet replay, then ONE launch for guidance +
-    # multistep combination + DDIM update + staging of the next evaluation's inputs (ops.plms_update)
-    from sdod.amd.samplers import PlmsSchedule, PLMS_ORDERS
     sch = PlmsSchedule(20)
     coefs, div = PLMS_ORDERS[1]
     old1 = torch.zeros_like(x)
@@ -306,109 +356,79 @@ def main():
         one_step()
     ev1.record()
     torch.cuda.synchronize()
-    unet_step_ms = ev0.elapsed_time(ev1) / reps
+    return ev0.elapsed_time(ev1) / reps
 
-    out = None
-    if rank == 0:
-        # ---- roofline of the dominant kernel family: per-launch HIP events over the UNet launch list (eager, same stream)
-        log(f'per-UNet-step {unet_step_ms:.3f} ms; profiling the launch list')
-        table = pipe.unet.op_table()
-        ms = pipe.unet.profile(iters=5)
-        # Durations are the kernels' own begin-to-end times (Graph::profile launches every entry through
-        # hipExtLaunchKernelGGL with a start / stop event pair: what a profiler reports per dispatch).  One family per KERNEL
-        # SYMBOL over everything ONE IMAGE launches -- 21 UNet evaluations + the VAE decode + the text encoder -- i.e. the
-        # population behind rocprofv3's per-symbol average for this very command (profiles/*_kernel_stats.csv).
-        fam = {}
-        per_image = [(pipe.unet, table, ms, 21)]
-        for g in (pipe.vae, pipe.text):
-            if g is not None:
-                per_image.append((g, g.op_table(), g.profile(iters=3), 1))
-        for _, tab, tms, reps in per_image:
-            for (label, fl, by), t in zip(tab, tms):
-                f = fam.setdefault(label, dict(ms=0.0, flops=0.0, bytes=0.0, launches=0))
-                f['ms'] += t * reps; f['flops'] += fl * reps; f['bytes'] += by * reps; f['launches'] += reps
-        # per-shape table (label, shape, launches per evaluation, us each, TF/s, GB/s): printed on stderr and carried in
-        # the JSON line, so BENCH, the rocprofv3 CSV and the PMC passes can be compared shape by shape
-        details = pipe.unet.op_details()
-        shapes = {}
-        for (label, fl, by), det, t in zip(table, details, ms):
-            r = shapes.setdefault((label, det), [0, 0.0, 0.0, 0.0])
-            r[0] += 1; r[1] += t; r[2] += fl; r[3] += by
-        shape_rows = [[lab, det, r[0], round(1e3 * r[1] / r[0], 2), round(r[2] / (r[1] * 1e-3) / 1e12, 1) if r[2] else None,
-                       round(r[3] / (r[1] * 1e-3) / 1e9, 1) if r[3] else None]
-                      for (lab, det), r in sorted(shapes.items(), key=lambda kv: -kv[1][1])]
-        log('UNet launch list by shape (kernel begin-to-end, per evaluation):\n' + '\n'.join(
-            f'  {lab:16s} {det:44s} x{n:<3d} {us:8.2f} us  {str(tf):>7s} TF/s  {str(gb):>8s} GB/s' for lab, det, n, us, tf, gb in shape_rows))
-        dom = max(fam, key=lambda k: fam[k]['ms'])
-        d = fam[dom]
-        total_ms = sum(ms)
-        image_kernel_ms = sum(f['ms'] for f in fam.values())
-        if d['flops'] > 0:
-            ach = d['flops'] / (d['ms'] * 1e-3) / 1e12
-            roof = dict(bound='mfma', achieved=round(ach, 2), peak=PEAK_TFLOPS_F16, unit='TFLOP/s', frac=round(ach / PEAK_TFLOPS_F16, 4),
-                        traffic=None)
-        else:
-            ach = d['bytes'] / (d['ms'] * 1e-3) / 1e9
-            roof = dict(bound='hbm', achieved=round(ach, 1), peak=PEAK_HBM_GBS, unit='GB/s', frac=round(ach / PEAK_HBM_GBS, 4), traffic=None)
-        # HBM bytes per launch of that kernel: rocprofv3 PMC passes cannot run inside this process, so the figure comes from
-        # the committed summary of separate `--pmc` passes over the SAME launch list (the shipped tune table fixes the tile
-        # picks, tools/run_profile.sh + tools/pmc_summary.py apply the guide's gfx950 corrections); `traffic_source` says so,
-        # and the fields stay null when no committed measurement matches the dominant symbol
-        try:
-            sym, mangled = kernel_symbol(dom)
-            pmc_file = os.path.join('profiles', PMC_SUMMARY)
-            for k in json.load(open(os.path.join(ROOT, pmc_file)))['kernels']:
-                name = k['kernel']
-                if (mangled and mangled in name) or (not mangled and sym in name):
-                    roof['traffic'] = k['hbm_fetch_bytes_per_launch'] + k['hbm_write_bytes_per_launch']
-                    roof['mfma_util_pmc'] = k['mfma_util']
-                    roof['traffic_source'] = f'offline: {pmc_file} (separate rocprofv3 --pmc passes, not measured in this run)'
-                    break
-        except (OSError, ValueError, KeyError, TypeError):
-            pass
-        roof.update(kernel=dom, kernel_symbol=kernel_symbol(dom)[0],
-                    flops_per_launch=round(d['flops'] / d['launches']), algorithmic_bytes_per_launch=round(d['bytes'] / d['launches']),
-                    launches_per_image=d['launches'], avg_launch_us=round(1e3 * d['ms'] / d['launches'], 2),
-                    share_of_image_kernel_time=round(d['ms'] / image_kernel_ms, 3), image_kernel_ms=round(image_kernel_ms, 2),
-                    unet_eval_kernel_ms=round(total_ms, 3), timing='kernel begin-to-end (hipExtLaunchKernelGGL start/stop events), per image: 21 UNet evaluations + VAE decode + text encoder',
-                    launches_per_unet_eval_total=len(table), tune_table=pipe.unet.tune_source(),
-                    unet_eval_tflops=round(pipe.unet.stats()['flops'] / (unet_step_ms * 1e-3) / 1e12, 1),
-                    families={k: dict(ms=round(v['ms'], 3), launches=v['launches'],
-                                      tflops=round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 1) if v['flops'] else None,
-                                      gbs=round(v['bytes'] / (v['ms'] * 1e-3) / 1e9, 1) if v['bytes'] else None)
-                              for k, v in sorted(fam.items(), key=lambda kv: -kv[1]['ms'])},
-                    shapes=shape_rows)
 
-        value = args.steps * n * (world // 2 if args.cfg_split else world) / elapsed
-        out = {
-            'metric': METRIC, 'value': round(value, 4), 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(1e3 * elapsed / args.steps, 3), 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f16', 'data': 'synthetic',
-            'config': {'workload': ('SD v1.4 txt2img 512x512, 20-step PLMS (21 UNet evals, batch 2 = cond+uncond per image), '
-                                    'CLIP encode + VAE decode + uint8, guidance 7.5') if (args.sampler, args.sampler_steps) == ('plms', 20) else
-                                   f'SD v1.4 txt2img 512x512, {args.sampler_steps}-step {args.sampler.upper()}, CLIP encode + VAE decode + uint8, guidance 7.5',
-                       'images_per_gpu': n, 'global_batch': n * (world // 2 if args.cfg_split else world), 'parallelism': (f'dp{world // 2} x cfg-split pairs (1 broadcast + 1 all-gather per UNet evaluation)' if args.cfg_split
-                                       else f'dp{world} (image shards, 1 RCCL broadcast)'),
-                       'hip_graph': not args.no_hip_graph,
-                       'trajectory_graph': not (args.per_step_launches or args.no_hip_graph),
-                       'decode_overlaps_next_sampling': bool(args.overlap_decode) and not (args.per_step_launches or args.no_hip_graph)},
-            'unet_step_ms': round(unet_step_ms, 3),
-            'roofline': roof,
-            'setup_s': round(setup_s, 1),
-        }
-        if rccl is not None:
-            out['rccl'] = rccl
-
-        if want_cpu:
-            z_gpu = pipe.sample_plms(ctx2, x_T, steps=20, guidance=7.5)
-            out.update(cpu_baseline_and_parity(pipe, sds, x_T, ctx2, e_gpu=pipe._eps(x_T, temb[0], 7.5, 1),
-                                               img_gpu=pipe.decode(z_gpu, mode=1), z_gpu=z_gpu))
-        if last_images is not None:
-            out['dump_outputs'] = {'dir': args.dump_outputs, 'files': dump_outputs(args.dump_outputs, 'images', last_images)}
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+def roofline(pipe, unet_step_ms):
+    """--full, rank 0: roofline of the dominant kernel family, from per-launch HIP events over the launch lists (eager,
+    same stream)"""
+    table = pipe.unet.op_table()
+    ms = pipe.unet.profile(iters=5)
+    # Durations are the kernels' own begin-to-end times (Graph::profile launches every entry through
+    # hipExtLaunchKernelGGL with a start / stop event pair: what a profiler reports per dispatch).  One family per KERNEL
+    # SYMBOL over everything ONE IMAGE launches -- 21 UNet evaluations + the VAE decode + the text encoder -- i.e. the
+    # population behind rocprofv3's per-symbol average for this very command (profiles/*_kernel_stats.csv).
+    fam = {}
+    per_image = [(pipe.unet, table, ms, 21)]
+    for g in (pipe.vae, pipe.text):
+        if g is not None:
+            per_image.append((g, g.op_table(), g.profile(iters=3), 1))
+    for _, tab, tms, reps in per_image:
+        for (label, fl, by), t in zip(tab, tms):
+            f = fam.setdefault(label, dict(ms=0.0, flops=0.0, bytes=0.0, launches=0))
+            f['ms'] += t * reps; f['flops'] += fl * reps; f['bytes'] += by * reps; f['launches'] += reps
+    # per-shape table (label, shape, launches per evaluation, us each, TF/s, GB/s): printed on stderr and carried in
+    # the JSON line, so BENCH, the rocprofv3 CSV and the PMC passes can be compared shape by shape
+    details = pipe.unet.op_details()
+    shapes = {}
+    for (label, fl, by), det, t in zip(table, details, ms):
+        r = shapes.setdefault((label, det), [0, 0.0, 0.0, 0.0])
+        r[0] += 1; r[1] += t; r[2] += fl; r[3] += by
+    shape_rows = [[lab, det, r[0], round(1e3 * r[1] / r[0], 2), round(r[2] / (r[1] * 1e-3) / 1e12, 1) if r[2] else None,
+                   round(r[3] / (r[1] * 1e-3) / 1e9, 1) if r[3] else None]
+                  for (lab, det), r in sorted(shapes.items(), key=lambda kv: -kv[1][1])]
+    log('UNet launch list by shape (kernel begin-to-end, per evaluation):\n' + '\n'.join(
+        f'  {lab:16s} {det:44s} x{n:<3d} {us:8.2f} us  {str(tf):>7s} TF/s  {str(gb):>8s} GB/s' for lab, det, n, us, tf, gb in shape_rows))
+    dom = max(fam, key=lambda k: fam[k]['ms'])
+    d = fam[dom]
+    total_ms = sum(ms)
+    image_kernel_ms = sum(f['ms'] for f in fam.values())
+    if d['flops'] > 0:
+        ach = d['flops'] / (d['ms'] * 1e-3) / 1e12
+        roof = dict(bound='mfma', achieved=round(ach, 2), peak=PEAK_TFLOPS_F16, unit='TFLOP/s', frac=round(ach / PEAK_TFLOPS_F16, 4),
+                    traffic=None)
+    else:
+        ach = d['bytes'] / (d['ms'] * 1e-3) / 1e9
+        roof = dict(bound='hbm', achieved=round(ach, 1), peak=PEAK_HBM_GBS, unit='GB/s', frac=round(ach / PEAK_HBM_GBS, 4), traffic=None)
+    # HBM bytes per launch of that kernel: rocprofv3 PMC passes cannot run inside this process, so the figure comes from
+    # the committed summary of separate `--pmc` passes over the SAME launch list (the shipped tune table fixes the tile
+    # picks, tools/run_profile.sh + tools/pmc_summary.py apply the guide's gfx950 corrections); `traffic_source` says so,
+    # and the fields stay null when no committed measurement matches the dominant symbol
+    try:
+        sym, mangled = kernel_symbol(dom)
+        pmc_file = os.path.join('profiles', PMC_SUMMARY)
+        for k in json.load(open(os.path.join(ROOT, pmc_file)))['kernels']:
+            name = k['kernel']
+            if (mangled and mangled in name) or (not mangled and sym in name):
+                roof['traffic'] = k['hbm_fetch_bytes_per_launch'] + k['hbm_write_bytes_per_launch']
+                roof['mfma_util_pmc'] = k['mfma_util']
+                roof['traffic_source'] = f'offline: {pmc_file} (separate rocprofv3 --pmc passes, not measured in this run)'
+                break
+    except (OSError, ValueError, KeyError, TypeError):
+        pass
+    roof.update(kernel=dom, kernel_symbol=kernel_symbol(dom)[0],
+                flops_per_launch=round(d['flops'] / d['launches']), algorithmic_bytes_per_launch=round(d['bytes'] / d['launches']),
+                launches_per_image=d['launches'], avg_launch_us=round(1e3 * d['ms'] / d['launches'], 2),
+                share_of_image_kernel_time=round(d['ms'] / image_kernel_ms, 3), image_kernel_ms=round(image_kernel_ms, 2),
+                unet_eval_kernel_ms=round(total_ms, 3), timing='kernel begin-to-end (hipExtLaunchKernelGGL start/stop events), per image: 21 UNet evaluations + VAE decode + text encoder',
+                launches_per_unet_eval_total=len(table), tune_table=pipe.unet.tune_source(),
+                unet_eval_tflops=round(pipe.unet.stats()['flops'] / (unet_step_ms * 1e-3) / 1e12, 1),
+                families={k: dict(ms=round(v['ms'], 3), launches=v['launches'],
+                                  tflops=round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 1) if v['flops'] else None,
+                                  gbs=round(v['bytes'] / (v['ms'] * 1e-3) / 1e9, 1) if v['bytes'] else None)
+                          for k, v in sorted(fam.items(), key=lambda kv: -kv[1]['ms'])},
+                shapes=shape_rows)
+    return roof
 
 
 def cpu_baseline_and_parity(pipe, sds, x_T, ctx2, e_gpu, img_gpu, z_gpu):
