@@ -363,6 +363,43 @@ typedef struct sdod_dpm_step_args {
     float guidance, sigma_s, alpha_s, sigma_ratio, c_prev, c_cur;
 } sdod_dpm_step_args;
 SDOD_API int sdod_dpm_step(const sdod_dpm_step_args* a, void* stream);
+
+/* One DDIM step (eta = 0) behind a UNet evaluation in one launch, with inpainting's latent blend (ldm DDIMSampler.ddim_sampling
+ * (mask=, x0=); Python host loop: sdod/amd/pipeline.py, sample_ddim_inpaint):
+ *   e  = CFG(eps) [sdod_cfg_combine; optional v -> eps conversion e = vc0 * e + vc1 * x, sdod_lincomb4_f32]
+ *   x' = DDIM step of x with e [sdod_ddim_step_f32]
+ *   known = known_sa * z0 + known_s1a * nu  (ldm q_sample of the clean latent z0 to the level x' has reached), or z0 when last != 0
+ *   x  = keep * known + (1 - keep) * x'     (ldm: img_orig * mask + (1. - mask) * img; keep broadcast over the c channels)
+ * then the next evaluation's inputs [sdod_stage_unet_inputs: x into x_stage[stage_reps][..], temb_row into temb_dst[temb_reps][..]].
+ * Every product, sum and difference is rounded on its own in fp32 (no FMA contraction): the bits of the separate launches
+ * followed by an elementwise fp32 blend.  nu: `noise` fp32 [n][c][hw], or when NULL drawn in the kernel, image i's values exactly
+ * those of sdod_randn_f32(count = c * hw, seed, stream_id = ((3 + noise_level) << 32) | (image_index0 + i)) (streams 1 and 2 belong
+ * to sdod_encode_latent_f32); with last != 0 no noise is drawn or read.  keep == NULL: a plain fused DDIM step, x = x' (z0, noise,
+ * known_* and last are ignored).  c * hw must be a multiple of 4; x, z0, noise and x_stage 16-byte aligned (they move as 16-byte
+ * lanes).  x_stage, temb_row may be NULL. */
+typedef struct sdod_ddim_inpaint_step_args {
+    const void* eps_nhwc;   /* fp16 [2n][hw][c] */
+    float* x;               /* fp32 [n][c][hw], updated in place */
+    const float* z0;        /* fp32 [n][c][hw]: the clean latent of the init image (needed when keep is given) */
+    const float* keep;      /* fp32 [n][hw]: 1 = keep the init image, 0 = repaint; NULL = no blend */
+    const float* noise;     /* fp32 [n][c][hw] or NULL (drawn in the kernel) */
+    float* x_stage;         /* fp32 [stage_reps][n][c][hw] or NULL */
+    const void* temb_row;   /* fp16 [temb_width] or NULL */
+    void* temb_dst;         /* fp16 [temb_reps][temb_width] */
+    uint64_t seed, image_index0;
+    int n, c, hw, uncond_first, mode, v_pred, last, noise_level, stage_reps, temb_width, temb_reps;
+    float guidance, vc0, vc1, sqrt_one_minus_at, sqrt_at, sqrt_a_prev, dir_coef, known_sa, known_s1a;
+} sdod_ddim_inpaint_step_args;
+SDOD_API int sdod_ddim_inpaint_step(const sdod_ddim_inpaint_step_args* a, void* stream);
+/* Inpainting's latent keep-mask: mask_u8 uint8 [n][factor * h_lat][factor * w_lat] (255 = repaint, 0 = keep) -> keep fp32
+ * [n][h_lat][w_lat] = float(16320 - S) / 16320.0f with S the integer sum of the latent pixel's 8 x 8 block (16320 = 64 * 255; one
+ * correctly rounded fp32 division).  factor must be 8 (the VAE's scale); mask_u8 8-byte aligned. */
+SDOD_API int sdod_mask_to_latent_f32(const uint8_t* mask_u8, float* keep, int n, int h_lat, int w_lat, int factor, void* stream);
+/* Inpainting's pixel composite: img fp16 NHWC [n][hw][3], init_u8 / out_u8 uint8 [n][hw][3], mask_u8 uint8 [n][hw].  Per byte, with
+ * d = the value sdod_image_to_u8(a, b, mode) gives (the same device function), u the init byte, k the pixel's mask byte:
+ * out = (d * k + u * (255 - k) + 127) / 255 in integer arithmetic; k = 0 returns u, k = 255 returns d. */
+SDOD_API int sdod_image_composite_u8(const void* img, const uint8_t* init_u8, const uint8_t* mask_u8, uint8_t* out_u8, int n, size_t hw,
+                                     float a, float b, int mode, void* stream);
 /* img: fp16 NHWC [n][hw][3] -> uint8 HWC per image, f = a*v+b, truncating cast:
  *   mode 0: clamp(255*f, 0, 255)   (context.cpp:392-395; a=1,b=0 is the reference's already-[0,1] convention)
  *   mode 1: 255*clamp(f, 0, 1)     (ldm txt2img with a=0.5, b=0.5) */

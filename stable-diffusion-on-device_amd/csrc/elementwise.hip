@@ -5,7 +5,8 @@
 //   dpm_update          dpm_solver.cpp:136-181
 //   timestep_features   context.cpp:257-274
 //   image_to_u8         context.cpp:392-395
-// and the PLMS/DDIM arithmetic of config 1's CPU reference (ldm PLMSSampler; not in /root/reference).
+// and the PLMS/DDIM arithmetic of config 1's CPU reference (ldm PLMSSampler; not in /root/reference), with ldm's masked DDIM
+// blend for inpainting (ddim_inpaint_step, mask_to_latent, image_composite).
 #include "common.h"
 #include <atomic>
 #include "sdod_hip.h"
@@ -402,17 +403,54 @@ __global__ void lincomb4_kernel(float* out, const float* e0, const float* e1, co
     }
 }
 
+// f = a * v + b -> uint8 (include/sdod_hip.h: sdod_image_to_u8); shared by to_u8_kernel and image_composite_kernel, so that both give
+// the same bits
+SDOD_DEVICE uint8_t to_u8_value(float v, float a, float b, int mode) {
+    float f = add_rn(mul_rn(a, v), b);
+    if (mode == 0) { // context.cpp:392-395: clamp(255*f, 0, 255), truncating cast
+        f = mul_rn(255.0f, f);
+        f = fminf(fmaxf(f, 0.0f), 255.0f);
+    } else {         // ldm txt2img: 255 * clamp(f, 0, 1), truncating cast
+        f = fminf(fmaxf(f, 0.0f), 1.0f);
+        f = mul_rn(255.0f, f);
+    }
+    return (uint8_t)f;
+}
+
 __global__ void to_u8_kernel(const f16* img, uint8_t* out, size_t count, float a, float b, int mode) {
+    GRID_STRIDE(i, count) out[i] = to_u8_value((float)img[i], a, b, mode);
+}
+
+// inpainting's pixel composite: out = (d k + u (255 - k) + 127) / 255 per byte, d = the decoded byte, u = the init byte, k = the mask
+// byte of the pixel (one per 3 channel bytes); at most 255 * 255 + 127, integer arithmetic
+__global__ void image_composite_kernel(const f16* img, const uint8_t* init, const uint8_t* mask, uint8_t* out, size_t count, float a,
+                                       float b, int mode) {
     GRID_STRIDE(i, count) {
-        float f = add_rn(mul_rn(a, (float)img[i]), b);
-        if (mode == 0) { // context.cpp:392-395: clamp(255*f, 0, 255), truncating cast
-            f = mul_rn(255.0f, f);
-            f = fminf(fmaxf(f, 0.0f), 255.0f);
-        } else {         // ldm txt2img: 255 * clamp(f, 0, 1), truncating cast
-            f = fminf(fmaxf(f, 0.0f), 1.0f);
-            f = mul_rn(255.0f, f);
+        const unsigned d = to_u8_value((float)img[i], a, b, mode);
+        const unsigned k = mask[i / 3], u = init[i];
+        out[i] = (uint8_t)((d * k + u * (255u - k) + 127u) / 255u);
+    }
+}
+
+// inpainting's latent keep-mask: S = sum of the factor x factor (8 x 8) block of mask bytes behind a latent pixel, keep = (16320 - S) /
+// 16320 (one IEEE division); a row of the block is one 8-byte load (the image width is 8 w_lat, the base 8-byte aligned)
+__global__ void mask_to_latent_kernel(const uint8_t* mask, float* keep, int n, int h_lat, int w_lat) {
+    const size_t total = (size_t)n * h_lat * w_lat;
+    GRID_STRIDE(i, total) {
+        const int ox = (int)(i % w_lat);
+        const size_t t = i / w_lat;
+        const int oy = (int)(t % h_lat);
+        const size_t img = t / h_lat;
+        const uint8_t* p = mask + ((img * h_lat + oy) * 8) * ((size_t)w_lat * 8) + (size_t)ox * 8;
+        unsigned sum = 0;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const uint64_t v = *reinterpret_cast<const uint64_t*>(p + (size_t)r * w_lat * 8);
+            // bytes 0, 2, 4, 6 and 1, 3, 5, 7 as 16-bit lanes (each <= 510), then the four lanes (<= 2040) by a multiply
+            const uint64_t pair = (v & 0x00FF00FF00FF00FFull) + ((v >> 8) & 0x00FF00FF00FF00FFull);
+            sum += (unsigned)((pair * 0x0001000100010001ull) >> 48);
         }
-        out[i] = (uint8_t)f;
+        keep[i] = div_rn((float)(16320 - (int)sum), 16320.0f);
     }
 }
 
@@ -599,6 +637,74 @@ __global__ void encode_latent_kernel(const float* mom, const float* n1, const fl
     }
 }
 
+// One DDIM step (eta = 0) behind a UNet evaluation in ONE launch, with inpainting's latent blend (include/sdod_hip.h:
+// sdod_ddim_inpaint_step): cfg_kernel's guidance, the optional v -> eps conversion (lincomb4_kernel), ddim_step_kernel's update, then
+// x = keep * known + (1 - keep) * x' with known = sa * z0 + s1a * nu (or z0 at the last step), and the staging of the next
+// evaluation's inputs (stage_unet_inputs_kernel) -- the same fp32 operations in the same order as those launches, every product, sum
+// and difference rounded on its own.  Thread = four consecutive elements of one image = one Philox block of its noise stream (as
+// encode_latent_kernel); x, z0, the noise and x_stage move as 16-byte lanes.
+__global__ void ddim_inpaint_step_kernel(const sdod_ddim_inpaint_step_args a) {
+    const size_t per = (size_t)a.c * a.hw, nblk = per / 4; // per % 4 == 0, pointers 16-byte aligned (checked by the host)
+    const size_t lat = (size_t)a.n * per, nlat = (size_t)a.n * nblk;
+    const size_t nt = a.temb_row ? (size_t)a.temb_width * a.temb_reps : 0;
+    const f16* eps = (const f16*)a.eps_nhwc;
+    GRID_STRIDE(t, nlat + nt) {
+        if (t >= nlat) {
+            ((f16*)a.temb_dst)[t - nlat] = ((const f16*)a.temb_row)[(t - nlat) % a.temb_width];
+            continue;
+        }
+        const int img = (int)(t / nblk);
+        const size_t j = t - (size_t)img * nblk;
+        const size_t o = (size_t)img * per + 4 * j;
+        const int iu = a.uncond_first ? img : img + a.n;
+        const int ic = a.uncond_first ? img + a.n : img;
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + o);
+        const bool blend = a.keep != nullptr;
+        f32x4 zv = f32x4{0.f, 0.f, 0.f, 0.f};
+        float nu[4] = {0.f, 0.f, 0.f, 0.f};
+        if (blend) {
+            zv = *reinterpret_cast<const f32x4*>(a.z0 + o);
+            if (!a.last) {
+                if (a.noise) {
+                    const f32x4 nv = *reinterpret_cast<const f32x4*>(a.noise + o);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) nu[q] = nv[q];
+                } else {
+                    uint32_t w[4];
+                    philox_normal4(j, a.seed, ((uint64_t)(3 + a.noise_level) << 32) | (a.image_index0 + img), w, nu);
+                }
+            }
+        }
+        f32x4 out;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const size_t e_i = 4 * j + q;
+            const size_t ch = e_i / a.hw, pix = e_i - ch * a.hw;
+            const float eu = (float)eps[((size_t)iu * a.hw + pix) * a.c + ch];
+            const float ec = (float)eps[((size_t)ic * a.hw + pix) * a.c + ch];
+            float e;
+            if (a.mode == 0) {
+                e = mul_rn(ec, a.guidance);
+                e = add_rn(e, mul_rn(eu, sub_rn(1.0f, a.guidance)));
+            } else {
+                e = add_rn(eu, mul_rn(a.guidance, sub_rn(ec, eu)));
+            }
+            if (a.v_pred) e = div_rn(add_rn(mul_rn(a.vc0, e), mul_rn(a.vc1, xv[q])), 1.0f); // lincomb4([e, x], [vc0, vc1], 1)
+            const float x0 = div_rn(sub_rn(xv[q], mul_rn(a.sqrt_one_minus_at, e)), a.sqrt_at);
+            float xn = add_rn(mul_rn(a.sqrt_a_prev, x0), mul_rn(a.dir_coef, e));
+            if (blend) {
+                const float k = a.keep[(size_t)img * a.hw + pix];
+                const float known = a.last ? zv[q] : add_rn(mul_rn(a.known_sa, zv[q]), mul_rn(a.known_s1a, nu[q]));
+                xn = add_rn(mul_rn(k, known), mul_rn(sub_rn(1.0f, k), xn));
+            }
+            out[q] = xn;
+        }
+        *reinterpret_cast<f32x4*>(a.x + o) = out;
+        if (a.x_stage)
+            for (int r = 0; r < a.stage_reps; ++r) *reinterpret_cast<f32x4*>(a.x_stage + (size_t)r * lat + o) = out;
+    }
+}
+
 #define LAUNCH(kernel, work, st, ...)                                                            \
     do {                                                                                         \
         SDOD_LAUNCH(kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)(st), __VA_ARGS__); \
@@ -781,6 +887,43 @@ extern "C" int sdod_dpm_step(const sdod_dpm_step_args* a, void* stream) {
     SDOD_REQUIRE(!a->temb_row || (a->temb_dst && a->temb_width > 0 && a->temb_reps > 0), "bad time-conditioning argument");
     const size_t work = (size_t)a->n * a->c * a->hw + (a->temb_row ? (size_t)a->temb_width * a->temb_reps : 0);
     LAUNCH(dpm_step_kernel, work, stream, *a);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_ddim_inpaint_step(const sdod_ddim_inpaint_step_args* a, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(a && a->eps_nhwc && a->x && a->n > 0 && a->c > 0 && a->hw > 0 && (a->mode == 0 || a->mode == 1) && a->sqrt_at != 0.0f,
+                 "bad argument");
+    SDOD_REQUIRE(((size_t)a->c * a->hw) % 4 == 0, "c * hw must be a multiple of 4");
+    SDOD_REQUIRE(!a->keep || a->z0, "keep needs z0");
+    SDOD_REQUIRE(!a->keep || a->last || a->noise || a->noise_level >= 0, "negative noise level");
+    SDOD_REQUIRE(!a->x_stage || a->stage_reps > 0, "x_stage needs stage_reps");
+    SDOD_REQUIRE(!a->temb_row || (a->temb_dst && a->temb_width > 0 && a->temb_reps > 0), "bad time-conditioning argument");
+    SDOD_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->z0 | (uintptr_t)a->noise | (uintptr_t)a->x_stage) & 15) == 0 &&
+                     ((uintptr_t)a->keep & 3) == 0 && ((uintptr_t)a->eps_nhwc & 1) == 0, "misaligned pointer (x, z0, noise, x_stage: 16 bytes)");
+    const size_t work = (size_t)a->n * a->c * a->hw / 4 + (a->temb_row ? (size_t)a->temb_width * a->temb_reps : 0);
+    LAUNCH(ddim_inpaint_step_kernel, work, stream, *a);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_mask_to_latent_f32(const uint8_t* mask_u8, float* keep, int n, int h_lat, int w_lat, int factor, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(mask_u8 && keep && n > 0 && h_lat > 0 && w_lat > 0, "bad argument");
+    SDOD_REQUIRE(factor == 8, "the latent is 8 x smaller than the image: factor must be 8");
+    SDOD_REQUIRE(((uintptr_t)mask_u8 & 7) == 0, "misaligned mask (8 bytes)");
+    LAUNCH(mask_to_latent_kernel, (size_t)n * h_lat * w_lat, stream, mask_u8, keep, n, h_lat, w_lat);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_image_composite_u8(const void* img, const uint8_t* init_u8, const uint8_t* mask_u8, uint8_t* out_u8, int n, size_t hw,
+                                       float a, float b, int mode, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(img && init_u8 && mask_u8 && out_u8 && n > 0 && hw > 0 && (mode == 0 || mode == 1), "bad argument");
+    const size_t count = (size_t)n * hw * 3;
+    LAUNCH(image_composite_kernel, count, stream, (const f16*)img, init_u8, mask_u8, out_u8, count, a, b, mode);
     return 0;
     SDOD_CATCH
 }

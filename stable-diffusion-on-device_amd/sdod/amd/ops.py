@@ -538,6 +538,76 @@ def dpm_step(eps_nhwc, x, y_prev, coef, guidance, mode=0, uncond_first=True, sta
     check(lib.sdod_dpm_step(ctypes.byref(a), _stream()))
 
 
+def ddim_inpaint_step(eps_nhwc, x, ddim, guidance, z0=None, keep=None, known=None, noise=None, seed=0, noise_level=0, image_index=0,
+                      mode=1, v_coef=None, stage=None):
+    """one DDIM step in one launch, with inpainting's latent blend (include/sdod_hip.h: sdod_ddim_inpaint_step): CFG of eps (+ v -> eps
+    with v_coef = (c_e, c_x)), DDIM update of x in place with ddim = schedule.coef(index), then x = keep * known + (1 - keep) * x'
+    with known = sa * z0 + s1a * nu for known = (sa, s1a), or z0 for known = None (the last step: no noise drawn or read), and -- with
+    stage = (x_dst, temb_row, temb_dst) -- the next evaluation's inputs.  nu = noise (fp32, x's shape) or, when None, Philox on the
+    device: stream ((3 + noise_level) << 32) | (image_index + i) of `seed` for image i.  keep (fp32 [n, H, W]) None: a plain fused
+    DDIM step."""
+    lib = _lib.hip()
+    _req(eps_nhwc, torch.float16, 'eps'); _req(x, torch.float32, 'x')
+    n2, c = eps_nhwc.shape[0], eps_nhwc.shape[-1]
+    n = n2 // 2
+    hw = eps_nhwc.numel() // (n2 * c)
+    assert x.numel() == n * c * hw
+    a = _lib.DdimInpaintStepArgs()
+    a.eps_nhwc, a.x = _p(eps_nhwc), _p(x)
+    if keep is not None:
+        _req(keep, torch.float32, 'keep')
+        assert keep.numel() == n * hw, (keep.shape, n, hw)
+        if z0 is not None:
+            _req(z0, torch.float32, 'z0')
+            assert z0.numel() == x.numel()
+        a.keep, a.z0 = _p(keep), _p(z0)
+        if noise is not None:
+            _req(noise, torch.float32, 'noise')
+            assert noise.numel() == x.numel()
+            a.noise = _p(noise)
+        if known is None:
+            a.last = 1                    # the kernel neither draws nor reads noise, whatever the pointer
+        else:
+            a.known_sa, a.known_s1a = known
+            a.seed, a.noise_level, a.image_index0 = int(seed) & (2 ** 64 - 1), int(noise_level), int(image_index) & (2 ** 64 - 1)
+    a.n, a.c, a.hw, a.uncond_first, a.mode = n, c, hw, 1, mode
+    a.guidance = guidance
+    if v_coef is not None:
+        a.v_pred, a.vc0, a.vc1 = 1, v_coef[0], v_coef[1]
+    a.sqrt_one_minus_at, a.sqrt_at, a.sqrt_a_prev, a.dir_coef = ddim['sqrt_one_minus_at'], ddim['sqrt_at'], ddim['sqrt_a_prev'], ddim['dir_coef']
+    if stage is not None:
+        x_dst, temb_row, temb_dst = stage
+        _req(x_dst, torch.float32, 'x_dst'); _req(temb_row, torch.float16, 'temb_row'); _req(temb_dst, torch.float16, 'temb_dst')
+        a.x_stage, a.stage_reps = _p(x_dst), x_dst.numel() // x.numel()
+        assert a.stage_reps * x.numel() == x_dst.numel() and temb_dst.numel() % temb_row.numel() == 0
+        a.temb_row, a.temb_dst, a.temb_width, a.temb_reps = _p(temb_row), _p(temb_dst), temb_row.numel(), temb_dst.numel() // temb_row.numel()
+    check(lib.sdod_ddim_inpaint_step(ctypes.byref(a), _stream()))
+
+
+def mask_to_latent(mask_u8, factor=8):
+    """inpainting's latent keep-mask (sdod_mask_to_latent_f32): uint8 [n, 8H, 8W] (255 = repaint, 0 = keep) -> fp32 [n, H, W],
+    keep = (16320 - sum of the 8 x 8 block) / 16320"""
+    lib = _lib.hip()
+    _req(mask_u8, torch.uint8, 'mask')
+    n, h, w = mask_u8.shape
+    assert h % factor == 0 and w % factor == 0, (h, w, factor)
+    out = torch.empty((n, h // factor, w // factor), dtype=torch.float32, device=mask_u8.device)
+    check(lib.sdod_mask_to_latent_f32(_p(mask_u8), _p(out), n, h // factor, w // factor, factor, _stream()))
+    return out
+
+
+def image_composite(img_nhwc, init_u8, mask_u8, a=0.5, b=0.5, mode=1):
+    """inpainting's pixel composite (sdod_image_composite_u8): img fp16 [n, h, w, 3], init uint8 [n, h, w, 3], mask uint8 [n, h, w] ->
+    uint8 (d k + u (255 - k) + 127) / 255 with d = image_to_u8(img, a, b, mode)"""
+    lib = _lib.hip()
+    _req(img_nhwc, torch.float16, 'img'); _req(init_u8, torch.uint8, 'init'); _req(mask_u8, torch.uint8, 'mask')
+    assert img_nhwc.shape[-1] == 3 and init_u8.numel() == img_nhwc.numel() and mask_u8.numel() * 3 == img_nhwc.numel()
+    n = img_nhwc.shape[0]
+    out = torch.empty(img_nhwc.shape, dtype=torch.uint8, device=img_nhwc.device)
+    check(lib.sdod_image_composite_u8(_p(img_nhwc), _p(init_u8), _p(mask_u8), _p(out), n, mask_u8.numel() // n, a, b, mode, _stream()))
+    return out
+
+
 def stage_unet_inputs(x, x_dst, temb_row, temb_dst):
     """x fp32 [n,...] -> x_dst [reps*n,...] (repeated back to back); temb_row fp16 [w] -> every row of temb_dst [b, w]"""
     lib = _lib.hip()
@@ -548,10 +618,15 @@ def stage_unet_inputs(x, x_dst, temb_row, temb_dst):
                                      temb_dst.numel() // temb_row.numel(), _stream()))
 
 
-def randn(shape, seed, stream_id, device, return_words=False):
-    """N(0,1) fp32 tensor from the in-tree Philox4x32-10 generator: a pure function of (seed, stream_id, element index)"""
+def randn(shape, seed, stream_id, device, return_words=False, out=None):
+    """N(0,1) fp32 tensor from the in-tree Philox4x32-10 generator: a pure function of (seed, stream_id, element index).
+    out: an existing contiguous fp32 tensor of `shape` to fill (a row of a graph's static noise input) instead of a new one"""
     lib = _lib.hip()
-    out = torch.empty(shape, dtype=torch.float32, device=device)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+    else:
+        _req(out, torch.float32, 'out')
+        assert tuple(out.shape) == tuple(shape), (out.shape, shape)
     words = torch.empty(out.numel(), dtype=torch.int32, device=device) if return_words else None
     with torch.cuda.device(out.device):
         check(lib.sdod_randn_f32(_p(out), _p(words), out.numel(), int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 64 - 1), _stream()))

@@ -258,23 +258,29 @@ class Txt2Img:
         return out
 
     # ------------------------------------------------------------------ img2img (ldm scripts/img2img.py, DDIM eta = 0)
-    def encode(self, init_u8, seed=0, image_index=0, strength=0.75, steps=50, noise=None):
+    def encode(self, init_u8, seed=0, image_index=0, strength=0.75, steps=50, noise=None, return_z0=False):
         """uint8 [n, 8H, 8W, 3] -> x fp32 [n, 4, H, W]: the VAE encoder, a posterior sample scaled by 0.18215, and ldm's
         stochastic_encode to ddim index t_enc = int(strength * steps).  noise = (n1, n2), fp32 [n, 4, H, W] each, or None: drawn
-        on the device (Philox, seed, streams (1 << 32) | index and (2 << 32) | index with index = image_index + i)."""
+        on the device (Philox, seed, streams (1 << 32) | index and (2 << 32) | index with index = image_index + i).
+        return_z0=True: returns (x, z0) with z0 fp32 [n, 4, H, W] the clean latent (the scaled posterior sample) from the same launch."""
         if self.encoder is None:
             raise RuntimeError('Txt2Img(..., with_vae_encoder=True) is needed for img2img')
         sch, t_enc = img2img_schedule(strength, steps)
         init_u8 = init_u8.to(self.device)
         xs = []
+        z0 = None
+        if return_z0:
+            z0 = torch.empty((init_u8.shape[0], self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w), dtype=torch.float32,
+                             device=self.device)
         for i in range(init_u8.shape[0]):
             self.encoder.img.copy_(init_u8[i:i + 1])
             self.encoder.execute(self.use_hip_graph)
             n1, n2 = (None, None) if noise is None else (noise[0][i:i + 1].to(self.device, torch.float32).contiguous(),
                                                          noise[1][i:i + 1].to(self.device, torch.float32).contiguous())
             xs.append(ops.encode_latent(self.encoder.moments, float(sch.sqrt_alphas[t_enc]), float(sch.sqrt_one_minus_alphas[t_enc]),
-                                        seed, image_index + i, n1, n2))
-        return torch.cat(xs, 0)
+                                        seed, image_index + i, n1, n2, z0=None if z0 is None else z0[i:i + 1]))
+        x = torch.cat(xs, 0)
+        return (x, z0) if return_z0 else x
 
     def sample_ddim_from(self, ctx2, x, t_enc, steps=50, guidance=7.5, trace=None):
         """ldm DDIMSampler.decode: t_enc DDIM steps (eta = 0, CFG mode 1) from ddim index t_enc - 1 down to 0"""
@@ -335,6 +341,124 @@ class Txt2Img:
                 s_n2[i:i + 1].copy_(ops.randn((1,) + per, seed, (2 << 32) | (image_index + i), self.device))
         else:
             s_n1.copy_(noise[0]); s_n2.copy_(noise[1])
+        g.replay()
+        return out
+
+    # ------------------------------------------------------------------ inpainting (ldm DDIMSampler.ddim_sampling(mask=, x0=) on img2img's start)
+    def sample_ddim_inpaint(self, ctx2, x, z0, keep, t_enc, steps=50, guidance=7.5, seed=0, image_index=0, step_noise=None, trace=None):
+        """t_enc DDIM steps (eta = 0, CFG mode 1) from ddim index t_enc - 1 down to 0 with ldm's latent blend after every step:
+        x' = DDIM step(x, e) has reached the level of ddim index j = index - 1, and x = keep * known + (1 - keep) * x' with
+        known = sqrt_alphas[j] * z0 + sqrt_one_minus_alphas[j] * nu_j (ldm q_sample of the clean latent z0 at timesteps[j]), or
+        known = z0 after the last step (index 0: nothing is drawn).  keep: fp32 [n, H, W], 1 = keep the init image, or None (a plain
+        DDIM decode on the fused step).  nu_j: step_noise[j] (fp32 [t_enc - 1, n, 4, H, W]) or Philox on the device, stream
+        ((3 + j) << 32) | (image_index + i) of `seed` for image i.
+        Against ldm's masked ddim_sampling, which blends BEFORE each evaluation, this blends AFTER each step for the next
+        evaluation: the same sequence, except that the start latent is not blended (it is the noised init image everywhere
+        already) and that there is a final noise-free blend, so the kept region of the result is z0 itself.
+        One staging launch in front of the loop, then per step the UNet replay and ONE launch (ops.ddim_inpaint_step = cfg_combine
+        + ddim_step + the blend + stage_unet_inputs, bit for bit)."""
+        sch = PlmsSchedule(steps)
+        temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
+        self._set_context(ctx2)
+        x = x.to(self.device, torch.float32).clone()
+        ops.stage_unet_inputs(x, self.unet.x, temb[t_enc - 1], self.unet.temb)
+        for index, j, sa, s1a in inpaint_levels(sch, t_enc):
+            self.unet.execute(self.use_hip_graph, static_unchanged=not self._ctx_fresh)
+            self._ctx_fresh = False
+            eps = self._exchange_halves(self.unet.eps) if self.cfg_split else self.unet.eps
+            ops.ddim_inpaint_step(eps, x, sch.coef(index), guidance, z0=z0, keep=keep, known=None if j is None else (sa, s1a),
+                                  noise=None if j is None or step_noise is None else step_noise[j],
+                                  seed=seed, noise_level=j or 0, image_index=image_index, mode=1,
+                                  v_coef=sch.v_to_eps_coef(index) if self.v_prediction else None,
+                                  stage=None if j is None else (self.unet.x, temb[j], self.unet.temb))
+            if trace is not None:
+                trace.append((int(sch.timesteps[index]), index))
+        return x
+
+    def _decode_composite(self, latents, init_u8, mask_u8):
+        """decode(mode 1) with inpainting's pixel composite in the place of image_to_u8: (d k + u (255 - k) + 127) / 255 per byte"""
+        outs = []
+        for i in range(latents.shape[0]):
+            self.vae.z.copy_(latents[i:i + 1])
+            self.vae.execute(self.use_hip_graph)
+            outs.append(ops.image_composite(self.vae.img, init_u8[i:i + 1], mask_u8[i:i + 1], 0.5, 0.5, 1))
+        return torch.cat(outs, 0)
+
+    def _inpaint_args(self, init_u8, mask_u8, strength, steps, step_noise):
+        """the host-side checks of inpaint() / inpaint_graphed(), in one order for both: argument errors (ValueError), then the
+        missing encoder; returns t_enc"""
+        lat = (self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
+        _, t_enc = inpaint_check_args(init_u8, mask_u8, strength, steps, step_noise, lat, self.n)
+        if self.encoder is None:
+            raise RuntimeError('Txt2Img(..., with_vae_encoder=True) is needed for inpainting')
+        return t_enc
+
+    def inpaint(self, ctx2, init_u8, mask_u8, strength=0.75, steps=50, guidance=7.5, seed=0, noise=None, step_noise=None,
+                image_index=0, composite=True, trace=None):
+        """Inpainting with the 4-channel UNet (latent blending): init_u8 uint8 [n, 8H, 8W, 3], mask_u8 uint8 [n, 8H, 8W] (255 =
+        repaint, 0 = keep, values between blend).  keep = (16320 - 8 x 8 block sum of the mask) / 16320 per latent pixel; img2img's
+        start latent at ddim index int(strength * steps) and the clean latent z0 from one launch; sample_ddim_inpaint; VAE decode;
+        then per byte out = (d k + u (255 - k) + 127) / 255 (d decoded, u init, k mask byte), so the pixels with k = 0 are the init
+        image's bit for bit.  composite=False returns the plain decode.  noise = (n1, n2) as encode(); step_noise fp32
+        [t_enc - 1, n, 4, H, W] or None (device Philox, see sample_ddim_inpaint).  Argument errors raise ValueError before any
+        device work."""
+        t_enc = self._inpaint_args(init_u8, mask_u8, strength, steps, step_noise)
+        init_u8 = init_u8.to(self.device).contiguous()
+        mask_u8 = mask_u8.to(self.device).contiguous()
+        if step_noise is not None:
+            step_noise = step_noise.to(self.device, torch.float32).contiguous()
+        keep = ops.mask_to_latent(mask_u8)
+        x, z0 = self.encode(init_u8, seed, image_index, strength, steps, noise, return_z0=True)
+        z = self.sample_ddim_inpaint(ctx2, x, z0, keep, t_enc, steps, guidance, seed, image_index, step_noise, trace)
+        return self._decode_composite(z, init_u8, mask_u8) if composite else self.decode(z, mode=1)
+
+    def inpaint_graphed(self, ctx2, init_u8, mask_u8, strength=0.75, steps=50, guidance=7.5, seed=0, noise=None, step_noise=None,
+                        image_index=0, composite=True):
+        """inpaint() as ONE device graph replay (mask reduction, encoder, start latent, every UNet evaluation and fused step, decoder,
+        composite), captured once per (t_enc, steps, guidance, composite, shape) from the eager path.  Image, mask and all noise are
+        inputs of the graph: without `noise` / `step_noise` they are drawn into it first by sdod_randn_f32 on the streams the eager
+        path draws in its kernels, bit for bit, so the result equals inpaint() with the same arguments.  Eager under cfg_split."""
+        t_enc = self._inpaint_args(init_u8, mask_u8, strength, steps, step_noise)
+        lat = (self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
+        if self.cfg_split:
+            return self.inpaint(ctx2, init_u8, mask_u8, strength, steps, guidance, seed, noise, step_noise, image_index, composite)
+        n = init_u8.shape[0]
+        key = ('inpaint', t_enc, int(steps), float(guidance), bool(composite), tuple(init_u8.shape))
+        cache = self.__dict__.setdefault('_traj', {})
+        if key not in cache:
+            s_ctx = torch.empty_like(ctx2, device=self.device)
+            s_img = torch.empty(tuple(init_u8.shape), dtype=torch.uint8, device=self.device)
+            s_mask = torch.empty(tuple(mask_u8.shape), dtype=torch.uint8, device=self.device)
+            s_n1 = torch.zeros((n,) + lat, dtype=torch.float32, device=self.device)
+            s_n2 = torch.zeros((n,) + lat, dtype=torch.float32, device=self.device)
+            s_sn = torch.zeros((t_enc - 1, n) + lat, dtype=torch.float32, device=self.device)
+            s_ctx.copy_(ctx2); s_img.copy_(init_u8); s_mask.copy_(mask_u8)
+            keep = self.use_hip_graph
+            self.use_hip_graph = False          # inside a capture the graphs run their launch lists
+            try:
+                self.inpaint(s_ctx, s_img, s_mask, strength, steps, guidance, noise=(s_n1, s_n2), step_noise=s_sn, composite=composite)  # warm-up
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                    out = self.inpaint(s_ctx, s_img, s_mask, strength, steps, guidance, noise=(s_n1, s_n2), step_noise=s_sn,
+                                       composite=composite)
+            finally:
+                self.use_hip_graph = keep
+            cache[key] = (g, s_ctx, s_img, s_mask, s_n1, s_n2, s_sn, out)
+        g, s_ctx, s_img, s_mask, s_n1, s_n2, s_sn, out = cache[key]
+        s_ctx.copy_(ctx2); s_img.copy_(init_u8); s_mask.copy_(mask_u8)
+        if noise is None:
+            for i in range(n):
+                ops.randn((1,) + lat, seed, (1 << 32) | (image_index + i), self.device, out=s_n1[i:i + 1])
+                ops.randn((1,) + lat, seed, (2 << 32) | (image_index + i), self.device, out=s_n2[i:i + 1])
+        else:
+            s_n1.copy_(noise[0]); s_n2.copy_(noise[1])
+        if step_noise is None:
+            for j in range(t_enc - 1):
+                for i in range(n):
+                    ops.randn((1,) + lat, seed, ((3 + j) << 32) | (image_index + i), self.device, out=s_sn[j, i:i + 1])
+        else:
+            s_sn.copy_(step_noise)
         g.replay()
         return out
 
@@ -403,6 +527,43 @@ def img2img_schedule(strength, steps):
     if not 1 <= t_enc <= steps - 1:
         raise ValueError(f'int(strength * steps) = {t_enc} is outside [1, steps - 1] = [1, {steps - 1}]')
     return PlmsSchedule(steps), t_enc
+
+
+def inpaint_levels(sch, t_enc):
+    """the steps of sample_ddim_inpaint: [(index, j, sa, s1a)] for ddim index t_enc - 1 .. 0, with j = index - 1 the ddim index of the
+    level the step reaches and (sa, s1a) = (sqrt_alphas[j], sqrt_one_minus_alphas[j]) the q_sample coefficients of the known region
+    there (ldm q_sample at timesteps[j]); the last step (index 0) reaches the clean level: j, sa, s1a are None, no noise is drawn"""
+    out = []
+    for index in range(t_enc - 1, -1, -1):
+        j = index - 1
+        out.append((index, j, float(sch.sqrt_alphas[j]), float(sch.sqrt_one_minus_alphas[j])) if index >= 1 else (0, None, None, None))
+    return out
+
+
+def inpaint_check_args(init_u8, mask_u8, strength, steps, step_noise, latent, n_images):
+    """the argument contract of Txt2Img.inpaint, checked on the host before any device work: init_u8 uint8 [n, 8H, 8W, 3] with n =
+    n_images and (4, H, W) = latent, the pipeline's batch and latent shape; mask_u8 uint8 [n, 8H, 8W]; strength in img2img_schedule's
+    domain; step_noise None or [t_enc - 1, n, 4, H, W].  Returns (schedule, t_enc); raises ValueError."""
+    for t, name in ((init_u8, 'init_u8'), (mask_u8, 'mask_u8')):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise ValueError(f'{name} must be a uint8 tensor, got {getattr(t, "dtype", type(t))}')
+    if init_u8.dim() != 4 or init_u8.shape[-1] != 3:
+        raise ValueError(f'init_u8 must be [n, 8H, 8W, 3], got {tuple(init_u8.shape)}')
+    n, h, w = (int(v) for v in init_u8.shape[:3])
+    if n < 1 or h % 8 or w % 8 or h == 0 or w == 0:
+        raise ValueError(f'init_u8 height and width must be positive multiples of 8, got {tuple(init_u8.shape)}')
+    if tuple(mask_u8.shape) != (n, h, w):
+        raise ValueError(f'mask_u8 must be {(n, h, w)} (the image without its channel axis), got {tuple(mask_u8.shape)}')
+    if n != n_images:
+        raise ValueError(f'the pipeline was built for {n_images} image(s) per call, got {n}')
+    if (h // 8, w // 8) != tuple(latent[1:]):
+        raise ValueError(f'the pipeline was built for {8 * latent[1]} x {8 * latent[2]} images, got {h} x {w}')
+    sch, t_enc = img2img_schedule(strength, steps)
+    if step_noise is not None:
+        want = (t_enc - 1, n) + tuple(latent)
+        if not isinstance(step_noise, torch.Tensor) or tuple(step_noise.shape) != want:
+            raise ValueError(f'step_noise must be {want} (t_enc - 1 = {t_enc - 1} noise levels), got {tuple(getattr(step_noise, "shape", ()))}')
+    return sch, t_enc
 
 
 def broadcast_conditioning(ctx2, src=0):
