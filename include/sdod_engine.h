@@ -15,6 +15,9 @@
  *                                                        ResBlock's emb_layers projection (all of it depends on t only,
  *                                                        so it is computed once per step and cached like context.cpp:276-278)
  *                 in2 ctx  fp16 [B][77][ctx_dim]         (context.cpp:216  p_cond / p_uncond = input(2))
+ *                 in3 cond fp32 NCHW [B][concat_channels][H][W]  only with sdod_model_config.concat_channels > 0 (an inpainting
+ *                                                        checkpoint, ldm `c_concat`): mask (1) | latent of the masked image (4),
+ *                                                        read by the input convolution next to in0; constant over a sampler run
  *                 out0 e   fp16 NHWC [B][H][W][4]        (context.cpp:218  e = unet.allocate_output(0))
  *   TEMB          in0 t    fp32 [B]                      (model time, dpm_solver.cpp:115)
  *                 out0     fp16 [B][E]                   (context.cpp:257-278: sinusoid + temb graph, + emb_layers)
@@ -25,6 +28,8 @@
  *   VAE_ENCODER   in0 img  uint8 HWC [B][8H][8W][3]      (ldm img2img: x = 2 u / 255 - 1)
  *                 out0     fp32 NCHW [B][8][H][W]        moments = quant_conv(encoder(x)): mean | logvar (not part of the
  *                                                        reference, which has no img2img)
+ *   VAE_ENCODER_MASKED  in0 img uint8 HWC [B][8H][8W][3], in1 mask uint8 [B][8H][8W]: the same graph and parameters on the masked
+ *                 image of inpainting, x = mask >= 128 ? 0 : 2 u / 255 - 1 (only the first launch differs); out0 as VAE_ENCODER
  *
  * Parameters are addressed by their CompVis-ldm / HF-CLIP state-dict names (without the
  * `model.diffusion_model.` / `first_stage_model.` / `cond_stage_model.transformer.` prefixes) and are
@@ -47,7 +52,7 @@ extern "C" {
 #endif
 
 enum sdod_graph_kind { SDOD_GRAPH_UNET = 0, SDOD_GRAPH_VAE_DECODER = 1, SDOD_GRAPH_TEXT_ENCODER = 2, SDOD_GRAPH_TEMB = 3,
-                       SDOD_GRAPH_VAE_ENCODER = 4 };
+                       SDOD_GRAPH_VAE_ENCODER = 4, SDOD_GRAPH_VAE_ENCODER_MASKED = 5 };
 
 typedef struct sdod_model_config {
     int latent_channels; /* 4 */
@@ -79,6 +84,11 @@ typedef struct sdod_model_config {
                           * exactly as with weight_quant = 0.  On MI355X no GEMM of the UNet is weight-bandwidth bound at batch 2,
                           * so the uint8 kernels lose wherever there are >= 288 rows and tie at 72
                           * (profiles/r03_config5_op_tables.txt): this is the setting that is never slower than fp16. */
+    int concat_channels; /* 0; 5 for an inpainting checkpoint (sd-v1-5-inpainting, 512-inpainting-ema): the UNet's input convolution
+                          * takes latent_channels + concat_channels channels (`input_blocks.0.0.weight` [320][9][3][3]), the extra ones
+                          * from the UNET graph's in3; its output keeps latent_channels.  9 * (latent_channels + concat_channels) <= 96,
+                          * and with concat_channels > 0 model_channels must be 64, 128, 256 or 320 (the one-launch input convolution;
+                          * the im2col + GEMM form of other widths has no second source). */
 } sdod_model_config;
 
 SDOD_API void sdod_model_config_sd14(sdod_model_config* cfg);
@@ -94,6 +104,10 @@ SDOD_API int sdod_graph_num_params(void* graph);
 SDOD_API int sdod_graph_param_info(void* graph, int index, const char** name, int* ndim, int64_t shape[4]);
 /* data: host pointer in canonical layout, dtype SDOD_F32 or SDOD_F16 (include/sdod_hip.h), numel from shape */
 SDOD_API int sdod_graph_set_param(void* graph, const char* name, const void* data, int dtype, const int64_t* shape, int ndim);
+/* where a set parameter lives in the weight arena, in its PACKED form (conv [Cout][tap * Cin + c] fp16, a tiny-Cin 3x3 convolution
+ * zero-padded to rows of 64 halves while 9 Cin <= 64 and of 128 up to 9 Cin <= 96; vectors fp32), and its size there: for tests and tools
+ * that check the packing or run a kernel on a graph's own weights.  A parameter that aliases columns of a wider matrix reports 0 bytes. */
+SDOD_API int sdod_graph_param_device(void* graph, const char* name, void** device_ptr, size_t* bytes);
 /* load every parameter from a .sdodw container (see DESIGN.md "weight file"); prefix is prepended to graph names */
 SDOD_API int sdod_graph_load_file(void* graph, const char* path, const char* prefix);
 /* checks that every parameter is set, sizes and allocates the activation arena, builds the launch list */

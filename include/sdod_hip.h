@@ -282,6 +282,28 @@ SDOD_API int sdod_conv_in_f16(const float* x, const void* w, const float* bias, 
  * sdod_im2col3x3_small_f16 and the K = 64 sdod_gemm_f16, bit for bit. */
 SDOD_API int sdod_image_conv_in_f16(const uint8_t* img, const void* w, const float* bias, void* y, int n_img, int h, int wd, int cout,
                                     void* stream);
+/* The input convolution of a 9-channel inpainting UNet (ldm `conditioning_key: hybrid`) in one launch: sdod_conv_in_f16 on the channel
+ * concatenation of x NCHW fp32 [n][c][h][w] and cond NCHW fp32 [n][c_cond][h][w], which is never written.  64 < 9 (c + c_cond) <= 96;
+ * w fp16 [cout][128] (k = tap * (c + c_cond) + channel, zero from 9 (c + c_cond): the PK_CONV3_SMALL packing of such a Cin), of which
+ * only the first 96 columns of a row are read (three K steps of 32); cout in {64, 128, 256, 320}.  The same products as
+ * sdod_latent_im2col_f16 (kpad = 128) of the concatenated tensor followed by the K = 128 sdod_gemm_f16 on the same w. */
+SDOD_API int sdod_conv_in_cat_f16(const float* x, const float* cond, const void* w, const float* bias, void* y, int n_img, int h, int wd,
+                                  int c, int c_cond, int cout, void* stream);
+/* sdod_image_conv_in_f16 on the masked image of inpainting, in the encoder's normalised space: a pixel is 0.0 where
+ * mask uint8 [n][h][wd] >= 128 and fp16(2 * (u / 255) - 1) elsewhere (0.0 is not the image of any uint8 value, so the masked image
+ * cannot be prepared as bytes).  With an all-zero mask the result is sdod_image_conv_in_f16's, bit for bit. */
+SDOD_API int sdod_masked_image_conv_in_f16(const uint8_t* img, const uint8_t* mask, const void* w, const float* bias, void* y, int n_img,
+                                           int h, int wd, int cout, void* stream);
+/* The conditioning input of a 9-channel inpainting UNet in one launch: cond fp32 [reps][n][1 + c][h_lat][w_lat] with
+ *   channel 0      = mask_u8[i][8 y][8 x] >= 128 ? 1 : 0   (F.interpolate(mask, size=(h_lat, w_lat)), nearest, of the binarised mask;
+ *                                                           mask_u8 uint8 [n][8 h_lat][8 w_lat])
+ *   channels 1..c  = 0.18215 * (mean + exp(0.5 * clamp(logvar, -30, 20)) * n1) from moments fp32 NCHW [n][2c][h_lat][w_lat] (the VAE
+ *                    encoder's output for the masked image): sdod_encode_latent_f32's z0, bit for bit.
+ * n1 fp32 [n][c][h_lat][w_lat], or NULL: drawn in the kernel, image i's values those of sdod_randn_f32(c * h_lat * w_lat, seed,
+ * (1 << 32) | (image_index0 + i)).  `reps` identical copies back to back (the two classifier-free-guidance halves).
+ * Errors (nothing written): NULL moments / mask / cond, factor != 8, h_lat * w_lat % 4 != 0, cond or n1 not 16-byte aligned. */
+SDOD_API int sdod_inpaint_cond_f32(const float* moments, const uint8_t* mask_u8, const float* n1, float* cond, int n, int c, int h_lat,
+                                   int w_lat, int factor, int reps, uint64_t seed, uint64_t image_index0, void* stream);
 /* ldm img2img's latent start in one launch.  moments fp32 NCHW [n][2c][h][w] (mean = channels [0, c), logvar = [c, 2c)):
  *   std = exp(0.5 * clamp(logvar, -30, 20)); z0 = 0.18215 * (mean + std * n1)      (DiagonalGaussianDistribution.sample,
  *   x = sqrt_at * z0 + sqrt_one_minus_at * n2                                          get_first_stage_encoding, stochastic_encode)

@@ -148,27 +148,58 @@ struct ImageU8Src { // img uint8 HWC [n][h][w][c], value 2 (u / 255) - 1 (ldm im
         return 2.0f * ((float)img[(((size_t)img_i * h + yy) * wd + xx) * c + ch] / 255.0f) - 1.0f;
     }
 };
-template <int NB, typename Src> // 16-column blocks per wave: Cout = 64 * NB
+// The two sources of the 9-channel inpainting UNet's input (ldm `c_concat`): channels [0, c0) from x, the rest from cond, both NCHW
+// fp32 -- the concatenated tensor is never written
+struct CatSrc {
+    const float* x;    // [n][c0][h][w]
+    const float* cond; // [n][c - c0][h][w]
+    int c0;
+    SDOD_DEVICE float at(int img, int ch, int yy, int xx, int c, int h, int wd) const {
+        const size_t pix = (size_t)yy * wd + xx;
+        return ch < c0 ? x[((size_t)img * c0 + ch) * h * wd + pix] : cond[((size_t)img * (c - c0) + (ch - c0)) * h * wd + pix];
+    }
+};
+// ImageU8Src with the inpainting mask applied in the encoder's normalised space: 0.0 where mask >= 128 (a value no uint8 pixel maps to)
+struct MaskedImageU8Src {
+    const uint8_t* img;  // [n][h][w][c]
+    const uint8_t* mask; // [n][h][w]
+    SDOD_DEVICE float at(int img_i, int ch, int yy, int xx, int c, int h, int wd) const {
+        const size_t pix = ((size_t)img_i * h + yy) * wd + xx;
+        if (mask[pix] >= 128) return 0.0f;
+        return 2.0f * ((float)img[pix * c + ch] / 255.0f) - 1.0f;
+    }
+};
+// NB: 16-column blocks per wave, Cout = 64 * NB.  KS: K steps of 32, the im2col row is K = 32 KS long (2: weight rows of 64 halves; 3:
+// K = 96, the first 96 columns of weight rows of 128 halves).
+template <int NB, typename Src, int KS = 2>
 __global__ __launch_bounds__(256) void conv_in_kernel(const Src src, const f16* w, const float* bias, f16* y, int n_img, int h, int wd, int c) {
-    __shared__ __attribute__((aligned(16))) f16 sa[32][64 + 8];
-    __shared__ __attribute__((aligned(16))) f16 sw[64 * NB][64 + 8];
+    constexpr int K = 32 * KS, KP = K / 8, LDW = KS == 2 ? 64 : 128, NW = NB * KP / 4;
+    __shared__ __attribute__((aligned(16))) f16 sa[32][K + 8];
+    __shared__ __attribute__((aligned(16))) f16 sw[64 * NB][K + 8];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cout = 64 * NB, hw = h * wd;
     const long long m0 = (long long)blockIdx.x * 32, M = (long long)n_img * hw;
-    // weights: 8 pieces of 16 bytes per row, 2 NB pieces per thread -- all requested before the first is stored (one memory round
-    // trip, not 2 NB of them)
-    f16x8 wv[2 * NB];
+    // weights: KP pieces of 16 bytes per row, NW pieces per thread -- all requested before the first is stored (one memory round
+    // trip, not NW of them)
+    f16x8 wv[NW];
 #pragma unroll
-    for (int i = 0; i < 2 * NB; ++i) wv[i] = ldg8(w + (size_t)(tid + 256 * i) * 8);
-    // im2col rows: thread = (pixel, 8 consecutive k)
-    {
-        const int pl = tid >> 3, k0 = (tid & 7) * 8;
+    for (int i = 0; i < NW; ++i) {
+        const int idx = tid + 256 * i;
+        if constexpr (K == LDW) wv[i] = ldg8(w + (size_t)idx * 8); // dense rows
+        else wv[i] = ldg8(w + (size_t)(idx / KP) * LDW + (idx % KP) * 8);
+    }
+    // im2col rows: task = (pixel, 8 consecutive k)
+#pragma unroll
+    for (int it = 0; it < (32 * KP + 255) / 256; ++it) {
+        const int task = tid + 256 * it;
+        if ((32 * KP) % 256 != 0 && task >= 32 * KP) break;
+        const int pl = task / KP, k0 = (task % KP) * 8;
         const long long m = m0 + pl;
         f16x8 v = zero8();
         if (m < M) {
             const int img = (int)(m / hw), rem = (int)(m - (long long)img * hw);
             const int oy = rem / wd, ox = rem - oy * wd;
-            int tap = k0 / c, ch = k0 - tap * c; // one division per thread; (tap, channel) then advance by increments
+            int tap = k0 / c, ch = k0 - tap * c; // one division per task; (tap, channel) then advance by increments
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float f = 0.f;
@@ -184,9 +215,9 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const Src src, const f16* 
         *reinterpret_cast<f16x8*>(&sa[pl][k0]) = v;
     }
 #pragma unroll
-    for (int i = 0; i < 2 * NB; ++i) {
+    for (int i = 0; i < NW; ++i) {
         const int idx = tid + 256 * i;
-        *reinterpret_cast<f16x8*>(&sw[idx >> 3][(idx & 7) * 8]) = wv[i];
+        *reinterpret_cast<f16x8*>(&sw[idx / KP][(idx % KP) * 8]) = wv[i];
     }
     __syncthreads();
     const int fr = lane & 15, fg = lane >> 4;
@@ -196,7 +227,7 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const Src src, const f16* 
 #pragma unroll
         for (int j = 0; j < NB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {
         f16x8 fa[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) fa[i] = *reinterpret_cast<const f16x8*>(&sa[i * 16 + fr][ks * 32 + fg * 8]);
@@ -637,6 +668,48 @@ __global__ void encode_latent_kernel(const float* mom, const float* n1, const fl
     }
 }
 
+// The conditioning input of the 9-channel inpainting UNet in ONE launch (include/sdod_hip.h: sdod_inpaint_cond_f32): channel 0 = the
+// binarised mask at latent resolution (nearest: the top-left byte of each 8 x 8 block), channels 1..c = encode_latent_kernel's z0 of
+// the masked image's moments (the same fp32 operations, the same Philox stream), written `reps` times back to back.  Threads
+// [0, n * c * hw / 4): four consecutive latent elements of one image = one Philox block; the rest: one mask element each.
+__global__ void inpaint_cond_kernel(const float* mom, const uint8_t* mask, const float* n1, float* cond, int n, int c, int h_lat, int w_lat,
+                                    int reps, uint64_t seed, uint64_t index0) {
+    const size_t hw = (size_t)h_lat * w_lat, per = (size_t)c * hw, nblk = per / 4; // hw % 4 == 0 (checked by the host)
+    const size_t nlat = (size_t)n * nblk, nmask = (size_t)n * hw, rep_stride = (size_t)n * (c + 1) * hw;
+    GRID_STRIDE(t, nlat + nmask) {
+        if (t >= nlat) {
+            const size_t i = t - nlat;
+            const size_t img = i / hw, pix = i - img * hw;
+            const size_t oy = pix / w_lat, ox = pix - oy * w_lat;
+            const float v = mask[(img * h_lat + oy) * 8 * ((size_t)w_lat * 8) + ox * 8] >= 128 ? 1.0f : 0.0f;
+            for (int r = 0; r < reps; ++r) cond[(size_t)r * rep_stride + img * (c + 1) * hw + pix] = v;
+            continue;
+        }
+        const int img = (int)(t / nblk);
+        const size_t j = t - (size_t)img * nblk;
+        float r1[4];
+        if (n1) {
+            const f32x4 nv = *reinterpret_cast<const f32x4*>(n1 + (size_t)img * per + 4 * j);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) r1[q] = nv[q];
+        } else {
+            uint32_t w[4];
+            philox_normal4(j, seed, (1ull << 32) | (index0 + img), w, r1);
+        }
+        const size_t e0 = 4 * j, ch = e0 / hw, pix = e0 - ch * hw; // the four elements share a channel (hw % 4 == 0)
+        f32x4 out;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float mean = mom[((size_t)img * 2 * c + ch) * hw + pix + q];
+            const float logvar = fminf(fmaxf(mom[((size_t)img * 2 * c + c + ch) * hw + pix + q], -30.0f), 20.0f);
+            const float sd = expf(__fmul_rn(0.5f, logvar));
+            out[q] = __fmul_rn(0.18215f, __fadd_rn(mean, __fmul_rn(sd, r1[q])));
+        }
+        for (int r = 0; r < reps; ++r)
+            *reinterpret_cast<f32x4*>(cond + (size_t)r * rep_stride + ((size_t)img * (c + 1) + 1 + ch) * hw + pix) = out;
+    }
+}
+
 // One DDIM step (eta = 0) behind a UNet evaluation in ONE launch, with inpainting's latent blend (include/sdod_hip.h:
 // sdod_ddim_inpaint_step): cfg_kernel's guidance, the optional v -> eps conversion (lincomb4_kernel), ddim_step_kernel's update, then
 // x = keep * known + (1 - keep) * x' with known = sa * z0 + s1a * nu (or z0 at the last step), and the staging of the next
@@ -759,15 +832,15 @@ extern "C" int sdod_latent_im2col_f16(const float* x, void* y, int n_img, int h,
     SDOD_CATCH
 }
 
-template <typename Src>
+template <typename Src, int KS = 2>
 void launch_conv_in(const Src src, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout, hipStream_t st) {
     const long long M = (long long)n_img * h * wd;
     const dim3 grid((unsigned)((M + 31) / 32));
     switch (cout / 64) {
-    case 1: SDOD_LAUNCH((conv_in_kernel<1, Src>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
-    case 2: SDOD_LAUNCH((conv_in_kernel<2, Src>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
-    case 4: SDOD_LAUNCH((conv_in_kernel<4, Src>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
-    default: SDOD_LAUNCH((conv_in_kernel<5, Src>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
+    case 1: SDOD_LAUNCH((conv_in_kernel<1, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
+    case 2: SDOD_LAUNCH((conv_in_kernel<2, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
+    case 4: SDOD_LAUNCH((conv_in_kernel<4, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
+    default: SDOD_LAUNCH((conv_in_kernel<5, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
     }
     SDOD_HIP_CHECK(hipGetLastError());
 }
@@ -790,6 +863,47 @@ extern "C" int sdod_image_conv_in_f16(const uint8_t* img, const void* w, const f
     SDOD_REQUIRE(cout == 320 || cout == 256 || cout == 128 || cout == 64, "Cout must be 64, 128, 256 or 320");
     SDOD_REQUIRE((((uintptr_t)w | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y & 7) == 0, "misaligned pointer");
     launch_conv_in(ImageU8Src{img}, w, bias, y, n_img, h, wd, 3, cout, (hipStream_t)stream);
+    return 0;
+    SDOD_CATCH
+}
+
+// The K = 96 kernel at Cout = 320 holds 73 KB of LDS per workgroup (two workgroups per CU where three of the K = 64 kernel's fit); it keeps
+// the 32 pixels per workgroup of the K = 64 kernel: 64 pixels were measured and lost, see DESIGN.md "Inpainting checkpoints".
+extern "C" int sdod_conv_in_cat_f16(const float* x, const float* cond, const void* w, const float* bias, void* y, int n_img, int h, int wd,
+                                    int c, int c_cond, int cout, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(x && cond && w && y && n_img > 0 && h > 0 && wd > 0 && c > 0 && c_cond > 0, "bad argument");
+    SDOD_REQUIRE(9 * (c + c_cond) > 64 && 9 * (c + c_cond) <= 96, "9 * (c + c_cond) must be in (64, 96]: the 96-deep K slab (weight rows of 128)");
+    SDOD_REQUIRE(cout == 320 || cout == 256 || cout == 128 || cout == 64, "Cout must be 64, 128, 256 or 320");
+    SDOD_REQUIRE((((uintptr_t)w | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y & 7) == 0 && (((uintptr_t)x | (uintptr_t)cond) & 3) == 0,
+                 "misaligned pointer");
+    const CatSrc src{x, cond, c};
+    launch_conv_in<CatSrc, 3>(src, w, bias, y, n_img, h, wd, c + c_cond, cout, (hipStream_t)stream);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_masked_image_conv_in_f16(const uint8_t* img, const uint8_t* mask, const void* w, const float* bias, void* y, int n_img,
+                                             int h, int wd, int cout, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(img && mask && w && y && n_img > 0 && h > 0 && wd > 0, "bad argument");
+    SDOD_REQUIRE(cout == 320 || cout == 256 || cout == 128 || cout == 64, "Cout must be 64, 128, 256 or 320");
+    SDOD_REQUIRE((((uintptr_t)w | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y & 7) == 0, "misaligned pointer");
+    launch_conv_in(MaskedImageU8Src{img, mask}, w, bias, y, n_img, h, wd, 3, cout, (hipStream_t)stream);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_inpaint_cond_f32(const float* moments, const uint8_t* mask_u8, const float* n1, float* cond, int n, int c, int h_lat,
+                                     int w_lat, int factor, int reps, uint64_t seed, uint64_t image_index0, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(moments && mask_u8 && cond && n > 0 && c > 0 && h_lat > 0 && w_lat > 0 && reps > 0, "bad argument");
+    SDOD_REQUIRE(factor == 8, "the latent is 8 x smaller than the image: factor must be 8");
+    SDOD_REQUIRE(((size_t)h_lat * w_lat) % 4 == 0, "h_lat * w_lat must be a multiple of 4");
+    SDOD_REQUIRE((((uintptr_t)cond | (uintptr_t)n1) & 15) == 0 && ((uintptr_t)moments & 3) == 0, "misaligned pointer (cond, n1: 16 bytes)");
+    const size_t hw = (size_t)h_lat * w_lat;
+    LAUNCH(inpaint_cond_kernel, (size_t)n * c * hw / 4 + (size_t)n * hw, stream, moments, mask_u8, n1, cond, n, c, h_lat, w_lat, reps, seed,
+           image_index0);
     return 0;
     SDOD_CATCH
 }

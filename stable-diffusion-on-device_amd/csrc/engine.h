@@ -21,7 +21,7 @@ typedef _Float16 f16;
 
 enum ParamKind {
     PK_CONV3,       // [Cout][Cin][3][3] -> fp16 [Cout][(r*3+s)*Cin + c]
-    PK_CONV3_SMALL, // Cin < 64: same order, K zero-padded to 64
+    PK_CONV3_SMALL, // tiny Cin: same order, K zero-padded to small_k(Cin) = 64 (9 Cin <= 64) or 128 (9 Cin <= 96)
     PK_CONV1,       // [Cout][Cin][1][1] -> fp16 [Cout][Cin]
     PK_LINEAR,      // [out][in] -> fp16
     PK_EMBED,       // [rows][dim] -> fp16
@@ -30,6 +30,10 @@ enum ParamKind {
     PK_LINEAR_GEGLU, // [2H][in] -> fp16, rows interleaved in 16-row blocks [value | gate] for the fused GEGLU epilogue
     PK_VEC_GEGLU,    // [2H] -> fp32, same interleave
 };
+
+// row length of a PK_CONV3_SMALL matrix: 128 and not 96 beyond 64 because the GEMM needs K % 64 == 0 and the two-launch form (im2col +
+// GEMM) must stay possible on the same bytes; the one-launch kernel reads the first 96 columns only
+inline int small_k(int64_t cin) { return 9 * cin <= 64 ? 64 : 128; }
 
 struct Param {
     std::string name;
@@ -166,7 +170,7 @@ private:
     void build();       // dispatches on kind_
     void build_unet();
     void build_vae();
-    void build_vae_encoder();
+    void build_vae_encoder(bool masked);
     void build_clip();
     void build_temb();
 

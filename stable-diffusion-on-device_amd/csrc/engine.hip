@@ -42,10 +42,11 @@ static void parallel_for(int64_t n, F&& fn) {
 
 // ------------------------------------------------------------------------------------------ lifecycle
 Graph::Graph(int kind, const sdod_model_config& cfg, int batch) : kind_(kind), cfg_(cfg), batch_(batch) {
-    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_VAE_ENCODER, "unknown graph kind");
+    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_VAE_ENCODER_MASKED, "unknown graph kind");
     SDOD_REQUIRE(batch > 0 && batch <= 64, "batch must be in [1, 64]");
     SDOD_REQUIRE(cfg.model_channels > 0 && cfg.model_channels % 64 == 0, "model_channels must be a multiple of 64");
     SDOD_REQUIRE(cfg.context_dim % 64 == 0, "context_dim must be a multiple of 64");
+    SDOD_REQUIRE(cfg.concat_channels >= 0, "concat_channels must not be negative");
     mode_ = DECLARE;
     arena_reset();
     build();
@@ -78,7 +79,7 @@ static size_t param_dev_bytes(const Param& p) {
     if (p.quant) return (size_t)s[0] * s[1] * (p.kind == PK_CONV3 ? 9 : 1); // one byte per code
     switch (p.kind) {
     case PK_CONV3: return (size_t)s[0] * s[1] * 9 * sizeof(f16);
-    case PK_CONV3_SMALL: return (size_t)s[0] * 64 * sizeof(f16);
+    case PK_CONV3_SMALL: return (size_t)s[0] * small_k(s[1]) * sizeof(f16);
     case PK_CONV1:
     case PK_LINEAR:
     case PK_LINEAR_GEGLU:
@@ -184,7 +185,7 @@ static void pack_param_host(const Param& p, const S* src, char* dst_raw) {
     case PK_CONV3:
     case PK_CONV3_SMALL: {
         const int64_t co = s[0], ci = s[1];
-        const int64_t kd = p.kind == PK_CONV3 ? 9 * ci : 64;
+        const int64_t kd = p.kind == PK_CONV3 ? 9 * ci : small_k(ci);
         f16* dst = reinterpret_cast<f16*>(dst_raw);
         parallel_for(co, [&](int64_t b, int64_t e) {
             for (int64_t o = b; o < e; ++o) {
@@ -840,7 +841,7 @@ Graph::LnVecs Graph::ln_fold_vectors(f16* w, int N, int K, int ldw, int ln_w, in
 
 void Graph::linear(const f16* x, int rows, int K, int w, int N, f16* out, const GemmOpt& o) {
     const Param& p = params_[w];
-    const int ldw = p.ld > 0 ? p.ld : p.kind == PK_CONV3_SMALL ? 64 : (int)(p.kind == PK_CONV3 ? p.shape[1] * 9 : p.shape[1]);
+    const int ldw = p.ld > 0 ? p.ld : p.kind == PK_CONV3_SMALL ? small_k(p.shape[1]) : (int)(p.kind == PK_CONV3 ? p.shape[1] * 9 : p.shape[1]);
     if (p.quant) { // (ldw counts elements, i.e. bytes for the uint8 codes)
         GemmOpt oq = o;
         oq.wq_scale = qscale_of(w);
@@ -959,7 +960,8 @@ void Graph::build() {
     case SDOD_GRAPH_UNET: build_unet(); break;
     case SDOD_GRAPH_VAE_DECODER: build_vae(); break;
     case SDOD_GRAPH_TEXT_ENCODER: build_clip(); break;
-    case SDOD_GRAPH_VAE_ENCODER: build_vae_encoder(); break;
+    case SDOD_GRAPH_VAE_ENCODER: build_vae_encoder(false); break;
+    case SDOD_GRAPH_VAE_ENCODER_MASKED: build_vae_encoder(true); break;
     default: build_temb(); break;
     }
     settle();
@@ -1189,6 +1191,7 @@ extern "C" void sdod_model_config_sd14(sdod_model_config* cfg) {
     cfg->vae_channels = 128;
     cfg->linear_proj = 0;
     cfg->text_arch = 0;
+    cfg->concat_channels = 0;
 }
 
 extern "C" void sdod_model_config_sd21(sdod_model_config* cfg) {
@@ -1266,6 +1269,23 @@ extern "C" int sdod_graph_io(void* graph, int is_output, int index, void** devic
     const sdod::IoSlot s = static_cast<Graph*>(graph)->io(is_output != 0, index);
     if (device_ptr) *device_ptr = s.ptr;
     if (bytes) *bytes = s.bytes;
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_param_device(void* graph, const char* name, void** device_ptr, size_t* bytes) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr && name != nullptr, "null argument");
+    Graph* g = static_cast<Graph*>(graph);
+    for (int i = 0; i < g->num_params(); ++i) {
+        const sdod::Param& p = g->param(i);
+        if (p.name != name) continue;
+        SDOD_REQUIRE(p.dev != nullptr && p.set, "parameter '" + p.name + "' has not been set");
+        if (device_ptr) *device_ptr = p.dev;
+        if (bytes) *bytes = p.dev_bytes;
+        return 0;
+    }
+    SDOD_REQUIRE(false, std::string("unknown parameter '") + name + "'");
     return 0;
     SDOD_CATCH
 }

@@ -301,7 +301,12 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
 void Graph::build_unet() {
     const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, LC = cfg_.latent_channels;
     const int MC = cfg_.model_channels, EC = 4 * MC, cd = cfg_.context_dim, CL = cfg_.context_len;
+    const int CC = cfg_.concat_channels, CI = LC + CC; // inpainting checkpoint: the input convolution also reads CC channels of in3
     SDOD_REQUIRE(LC * 9 <= 64, "latent_channels too large for the small-Cin path");
+    SDOD_REQUIRE(CI * 9 <= 96, "latent_channels + concat_channels too large for the small-Cin path (9 Cin <= 96)");
+    SDOD_REQUIRE(CC == 0 || CI * 9 > 64, "concat_channels > 0 needs 9 (latent_channels + concat_channels) > 64 (the K = 96 input convolution)");
+    SDOD_REQUIRE(CC == 0 || MC == 320 || MC == 256 || MC == 128 || MC == 64,
+                 "concat_channels > 0 needs model_channels 64, 128, 256 or 320 (the one-launch input convolution)");
     const int mult[4] = {1, 2, 4, 4};
 
     if (mode_ != DECLARE) { // widths fixed by the DECLARE pass
@@ -312,6 +317,7 @@ void Graph::build_unet() {
     float* x_in = (float*)io_alloc(inputs_, (size_t)B * LC * H * Wd * sizeof(float));
     f16* temb_in = (f16*)io_alloc(inputs_, (size_t)B * std::max(emb_total_, 1) * sizeof(f16));
     f16* ctx_in = (f16*)io_alloc(inputs_, (size_t)B * CL * cd * sizeof(f16));
+    const float* cond_in = CC > 0 ? (const float*)io_alloc(inputs_, (size_t)B * CC * H * Wd * sizeof(float)) : nullptr;
     f16* e_out = (f16*)io_alloc(outputs_, (size_t)B * H * Wd * LC * sizeof(f16));
     Act ctx;
     ctx.p = ctx_in; ctx.n = B; ctx.h = 1; ctx.w = CL; ctx.c = cd;
@@ -332,9 +338,21 @@ void Graph::build_unet() {
     }
 
     // input conv (Cin = 4): im2col to K = 64, then the GEMM
-    const int ciw = P("input_blocks.0.0.weight", {MC, LC, 3, 3}, PK_CONV3_SMALL), cib = P("input_blocks.0.0.bias", {MC}, PK_VEC);
+    const int ciw = P("input_blocks.0.0.weight", {MC, CI, 3, 3}, PK_CONV3_SMALL), cib = P("input_blocks.0.0.bias", {MC}, PK_VEC);
     Act h = act(B, H, Wd, MC);
-    if (MC == 320 || MC == 256 || MC == 128 || MC == 64) {
+    if (CC > 0) {
+        // Cin = 9 from two sources (x | cond), K = 81 -> 96 of the 128-wide packed rows, ONE launch (elementwise.hip: CatSrc)
+        const f16* wp = mode_ != DECLARE ? W<f16>(ciw) : nullptr;
+        const float* bp = mode_ != DECLARE ? W<float>(cib) : nullptr;
+        f16* hp = h.p;
+        settle();
+        if (mode_ == REAL) {
+            flops_ += 2.0 * B * H * Wd * MC * 96;
+            ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_conv_in_cat_f16(x_in, cond_in, wp, bp, hp, B, H, Wd, LC, CC, MC, st)); },
+                              "conv_in_cat", 2.0 * B * H * Wd * MC * 96, (double)B * H * Wd * (CI * 4 + MC * 2) + MC * 96 * 2,
+                              "M" + std::to_string(B * H * Wd) + " N" + std::to_string(MC) + " K96"});
+        }
+    } else if (MC == 320 || MC == 256 || MC == 128 || MC == 64) {
         // ONE launch: im2col rows built in LDS, the whole [MC][64] weight matrix next to them (elementwise.hip: conv_in_kernel)
         const f16* wp = mode_ != DECLARE ? W<f16>(ciw) : nullptr;
         const float* bp = mode_ != DECLARE ? W<float>(cib) : nullptr;
@@ -602,12 +620,15 @@ void Graph::build_vae() {
 //   * Downsample = F.pad(h, (0, 1, 0, 1)) + 3x3 stride-2 conv: the gather GEMM with pad_mode 1 (no padded copy);
 //   * quant_conv (1x1, 8 -> 8) composed into conv_out at finalize (sdod_compose_linear_f16: one fp16 rounding of P . W, bias
 //     P b + b_q), then one layout change NHWC fp16 -> NCHW fp32 for the moments.
-void Graph::build_vae_encoder() {
+// masked (SDOD_GRAPH_VAE_ENCODER_MASKED): a second input, the inpainting mask, applied by the input convolution in the normalised space
+// (sdod_masked_image_conv_in_f16); every other launch and every parameter is the plain encoder's.
+void Graph::build_vae_encoder(bool masked) {
     const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, LC = cfg_.latent_channels, VC = cfg_.vae_channels;
     const int IH = 8 * H, IW = 8 * Wd, ZC = 2 * LC;
     SDOD_REQUIRE(VC == 64 || VC == 128 || VC == 256 || VC == 320, "vae_channels must be 64, 128, 256 or 320 (image input convolution)");
     const int mult[4] = {1, 2, 4, 4};
     uint8_t* img_in = (uint8_t*)io_alloc(inputs_, (size_t)B * IH * IW * 3);
+    const uint8_t* mask_in = masked ? (const uint8_t*)io_alloc(inputs_, (size_t)B * IH * IW) : nullptr;
     float* mom_out = (float*)io_alloc(outputs_, (size_t)B * ZC * H * Wd * sizeof(float));
 
     const int ciw = P("encoder.conv_in.weight", {VC, 3, 3, 3}, PK_CONV3_SMALL), cib = P("encoder.conv_in.bias", {VC}, PK_VEC);
@@ -620,8 +641,14 @@ void Graph::build_vae_encoder() {
         if (mode_ == REAL) {
             const double fl = 2.0 * B * IH * IW * VC * 64;
             flops_ += fl;
-            ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_image_conv_in_f16(img_in, wp, bp, hp, B, IH, IW, VC, st)); }, "image_conv_in",
-                              fl, (double)B * IH * IW * (3 + VC * 2) + VC * 64 * 2, "M" + std::to_string(B * IH * IW) + " N" + std::to_string(VC) + " K64"});
+            if (masked)
+                ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_masked_image_conv_in_f16(img_in, mask_in, wp, bp, hp, B, IH, IW, VC, st)); },
+                                  "masked_image_conv_in", fl, (double)B * IH * IW * (4 + VC * 2) + VC * 64 * 2,
+                                  "M" + std::to_string(B * IH * IW) + " N" + std::to_string(VC) + " K64"});
+            else
+                ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_image_conv_in_f16(img_in, wp, bp, hp, B, IH, IW, VC, st)); }, "image_conv_in",
+                                  fl, (double)B * IH * IW * (3 + VC * 2) + VC * 64 * 2,
+                                  "M" + std::to_string(B * IH * IW) + " N" + std::to_string(VC) + " K64"});
         }
     }
     int ch = VC;

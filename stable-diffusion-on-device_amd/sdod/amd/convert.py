@@ -112,11 +112,16 @@ def main(argv=None):
     ap.add_argument('--model', default='sd14', choices=['sd14', 'sd21'], help='sd21: SD v2.x shapes and open_clip text-tower key names')
     ap.add_argument('--vae-encoder', action='store_true', help='also write vae_encoder.sdodw (first_stage_model.encoder + '
                                                                 'quant_conv), the img2img path')
+    ap.add_argument('--inpaint', action='store_true', help='an inpainting checkpoint (sd-v1-5-inpainting, 512-inpainting-ema): the UNet input '
+                                                            'convolution is [320, 9, 3, 3]; implies --vae-encoder (Txt2Img(inpaint_unet=True))')
     ap.add_argument('--tokenizer-vocab', help='bpe_simple_vocab_16e6.txt.gz, or a directory with HF vocab.json + merges.txt: '
                                               'also write ctokenizer.txt')
     a = ap.parse_args(argv)
     cfg = E.sd21_config() if a.model == 'sd21' else None
-    for p in convert(a.ckpt, a.out, torch.float32 if a.fp32 else torch.float16, cfg, vae_encoder=a.vae_encoder):
+    if a.inpaint:
+        cfg = cfg or E.sd14_config()
+        cfg.concat_channels = 5
+    for p in convert(a.ckpt, a.out, torch.float32 if a.fp32 else torch.float16, cfg, vae_encoder=a.vae_encoder or a.inpaint):
         print('wrote', p)
     if a.tokenizer_vocab:
         from . import tokenizer_file

@@ -9,19 +9,20 @@ import torch
 from . import _lib
 from ._lib import check
 
-UNET, VAE_DECODER, TEXT_ENCODER, TEMB, VAE_ENCODER = 0, 1, 2, 3, 4
+UNET, VAE_DECODER, TEXT_ENCODER, TEMB, VAE_ENCODER, VAE_ENCODER_MASKED = 0, 1, 2, 3, 4, 5
 
 
 class ModelConfig(ctypes.Structure):
     """mirror of `struct sdod_model_config`"""
     _fields_ = [(n, ctypes.c_int) for n in (
         'latent_channels', 'latent_h', 'latent_w', 'model_channels', 'context_dim', 'context_len', 'num_heads',
-        'head_dim', 'vocab_size', 'text_layers', 'text_heads', 'vae_channels', 'linear_proj', 'text_arch', 'weight_quant')]
+        'head_dim', 'vocab_size', 'text_layers', 'text_heads', 'vae_channels', 'linear_proj', 'text_arch', 'weight_quant',
+        'concat_channels')]
 
 
 ENGINE_SYMBOLS = [
     'sdod_model_config_sd14', 'sdod_model_config_sd21', 'sdod_graph_create', 'sdod_graph_destroy', 'sdod_graph_num_params', 'sdod_graph_param_info',
-    'sdod_graph_set_param', 'sdod_graph_load_file', 'sdod_graph_finalize', 'sdod_graph_io', 'sdod_graph_execute', 'sdod_graph_check',
+    'sdod_graph_set_param', 'sdod_graph_param_device', 'sdod_graph_load_file', 'sdod_graph_finalize', 'sdod_graph_io', 'sdod_graph_execute', 'sdod_graph_check',
     'sdod_graph_stats', 'sdod_graph_tune_info', 'sdod_graph_num_ops', 'sdod_graph_op_info', 'sdod_graph_op_detail', 'sdod_graph_profile',
 ]
 
@@ -40,6 +41,7 @@ def _engine():
         lib.sdod_graph_param_info.argtypes = [P, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I), ctypes.POINTER(ctypes.c_int64)]
         lib.sdod_graph_set_param.argtypes = [P, ctypes.c_char_p, P, I, ctypes.POINTER(ctypes.c_int64), I]
         lib.sdod_graph_load_file.argtypes = [P, ctypes.c_char_p, ctypes.c_char_p]
+        lib.sdod_graph_param_device.argtypes = [P, ctypes.c_char_p, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]
         lib.sdod_graph_finalize.argtypes = [P]
         lib.sdod_graph_io.argtypes = [P, I, I, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]
         lib.sdod_graph_execute.argtypes = [P, P, I]
@@ -55,18 +57,20 @@ def _engine():
     return lib
 
 
-def sd14_config(latent_h=64, latent_w=64):
+def sd14_config(latent_h=64, latent_w=64, concat_channels=0):
+    """concat_channels=5: an inpainting checkpoint (sd-v1-5-inpainting), whose UNet input convolution takes 4 + 5 channels"""
     cfg = ModelConfig()
     _engine().sdod_model_config_sd14(ctypes.byref(cfg))
-    cfg.latent_h, cfg.latent_w = latent_h, latent_w
+    cfg.latent_h, cfg.latent_w, cfg.concat_channels = latent_h, latent_w, concat_channels
     return cfg
 
 
-def sd21_config(latent_h=96, latent_w=96):
-    """SD v2.1-768 shapes (BASELINE config 5): UNet with 64-wide heads / context 1024, OpenCLIP ViT-H/14 text tower"""
+def sd21_config(latent_h=96, latent_w=96, concat_channels=0):
+    """SD v2.1-768 shapes (BASELINE config 5): UNet with 64-wide heads / context 1024, OpenCLIP ViT-H/14 text tower;
+    concat_channels=5: an SD 2 inpainting checkpoint (512-inpainting-ema)"""
     cfg = ModelConfig()
     _engine().sdod_model_config_sd21(ctypes.byref(cfg))
-    cfg.latent_h, cfg.latent_w = latent_h, latent_w
+    cfg.latent_h, cfg.latent_w, cfg.concat_channels = latent_h, latent_w, concat_channels
     return cfg
 
 
@@ -127,6 +131,12 @@ class Graph:
         shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
         check(self._lib.sdod_graph_set_param(self._h, name.encode(), ctypes.c_void_p(t.data_ptr()),
                                              1 if t.dtype == torch.float32 else 0, shape, t.dim()))
+
+    def packed_param(self, name, dtype=torch.float16):
+        """a set parameter as it lives in the weight arena (its packed form), as a flat torch view of `dtype`"""
+        p = ctypes.c_void_p(); n = ctypes.c_size_t()
+        check(self._lib.sdod_graph_param_device(self._h, name.encode(), ctypes.byref(p), ctypes.byref(n)))
+        return device_view(p.value, (n.value // torch.empty((), dtype=dtype).element_size(),), dtype, self.device)
 
     def load_state_dict(self, sd, prefix=''):
         """sd: mapping of (prefix+)ldm/HF names to tensors in canonical layout; every graph parameter must be present."""
@@ -218,6 +228,8 @@ class UNet(Graph):
         self.temb = self.io_tensor(False, 1, (b, self.temb_width), torch.float16)
         self.ctx = self.io_tensor(False, 2, (b, c.context_len, c.context_dim), torch.float16)
         self.eps = self.io_tensor(True, 0, (b, c.latent_h, c.latent_w, c.latent_channels), torch.float16)
+        if c.concat_channels > 0:   # inpainting checkpoint: mask | latent of the masked image, read by the input convolution next to x
+            self.cond = self.io_tensor(False, 3, (b, c.concat_channels, c.latent_h, c.latent_w), torch.float32)
         return self
 
 
@@ -267,5 +279,21 @@ class VaeEncoder(Graph):
         super().finalize()
         c, b = self.cfg, self.batch
         self.img = self.io_tensor(False, 0, (b, 8 * c.latent_h, 8 * c.latent_w, 3), torch.uint8)
+        self.moments = self.io_tensor(True, 0, (b, 2 * c.latent_channels, c.latent_h, c.latent_w), torch.float32)
+        return self
+
+
+class MaskedVaeEncoder(Graph):
+    """VaeEncoder on inpainting's masked image: uint8 image [B, 8H, 8W, 3] and uint8 mask [B, 8H, 8W] -> fp32 moments [B, 8, H, W] of
+    x = 0 where mask >= 128, 2 u / 255 - 1 elsewhere.  Same parameters (and weight files) as VaeEncoder."""
+
+    def __init__(self, cfg, batch, device='cuda:0'):
+        super().__init__(VAE_ENCODER_MASKED, cfg, batch, device)
+
+    def finalize(self):
+        super().finalize()
+        c, b = self.cfg, self.batch
+        self.img = self.io_tensor(False, 0, (b, 8 * c.latent_h, 8 * c.latent_w, 3), torch.uint8)
+        self.mask = self.io_tensor(False, 1, (b, 8 * c.latent_h, 8 * c.latent_w), torch.uint8)
         self.moments = self.io_tensor(True, 0, (b, 2 * c.latent_channels, c.latent_h, c.latent_w), torch.float32)
         return self

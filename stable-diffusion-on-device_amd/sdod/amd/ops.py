@@ -379,7 +379,7 @@ def im2col3x3_small(x, kpad=64):
     return out
 
 
-def latent_im2col(x, kpad=64, scale=1.0):
+def latent_im2col(x, kpad=64, scale=1.0):  # kpad=128: the 9-channel inpainting input (9 * 9 = 81 columns, zero beyond)
     """NCHW fp32 latent -> im2col matrix [n*h*w, kpad] fp16 of a 3x3 pad-1 convolution (the UNet's input conv as a K = 64 GEMM)"""
     lib = _lib.hip()
     _req(x, torch.float32, 'x')
@@ -412,6 +412,55 @@ def image_conv_in(img_u8, w, bias):
     cout = w.shape[0]
     out = torch.empty((n, h, wd, cout), dtype=torch.float16, device=img_u8.device)
     check(lib.sdod_image_conv_in_f16(_p(img_u8), _p(w), _p(bias), _p(out), n, h, wd, cout, _stream()))
+    return out
+
+
+def conv_in_cat(x, cond, w, bias):
+    """the 9-channel inpainting UNet's input convolution in one launch (sdod_conv_in_cat_f16): x NCHW fp32 [n, c, h, w] and cond NCHW
+    fp32 [n, c_cond, h, w] read as their channel concatenation, w fp16 [cout, 128] (k = tap * (c + c_cond) + channel, zero from
+    9 (c + c_cond); columns 96.. are not read), bias fp32 [cout] -> NHWC fp16 [n, h, w, cout]"""
+    lib = _lib.hip()
+    _req(x, torch.float32, 'x'); _req(cond, torch.float32, 'cond'); _req(w, torch.float16, 'w'); _req(bias, torch.float32, 'bias')
+    n, c, h, wd = x.shape
+    assert cond.shape[0] == n and tuple(cond.shape[2:]) == (h, wd) and w.shape[1] == 128, (x.shape, cond.shape, w.shape)
+    cout = w.shape[0]
+    out = torch.empty((n, h, wd, cout), dtype=torch.float16, device=x.device)
+    check(lib.sdod_conv_in_cat_f16(_p(x), _p(cond), _p(w), _p(bias), _p(out), n, h, wd, c, cond.shape[1], cout, _stream()))
+    return out
+
+
+def masked_image_conv_in(img_u8, mask_u8, w, bias):
+    """image_conv_in on inpainting's masked image (sdod_masked_image_conv_in_f16): a pixel is 0.0 where mask uint8 [n, h, w] >= 128 and
+    2 u / 255 - 1 elsewhere"""
+    lib = _lib.hip()
+    _req(img_u8, torch.uint8, 'img'); _req(mask_u8, torch.uint8, 'mask'); _req(w, torch.float16, 'w'); _req(bias, torch.float32, 'bias')
+    n, h, wd, c = img_u8.shape
+    assert c == 3 and w.shape[1] == 64 and tuple(mask_u8.shape) == (n, h, wd)
+    cout = w.shape[0]
+    out = torch.empty((n, h, wd, cout), dtype=torch.float16, device=img_u8.device)
+    check(lib.sdod_masked_image_conv_in_f16(_p(img_u8), _p(mask_u8), _p(w), _p(bias), _p(out), n, h, wd, cout, _stream()))
+    return out
+
+
+def inpaint_cond(moments, mask_u8, seed=0, image_index=0, n1=None, out=None, reps=1, factor=8):
+    """the conditioning input of a 9-channel inpainting UNet in one launch (sdod_inpaint_cond_f32): moments fp32 [n, 2c, h, w] of the
+    masked image and mask uint8 [n, 8h, 8w] -> fp32 [reps * n, 1 + c, h, w]: channel 0 = (mask[:, ::8, ::8] >= 128), channels 1.. =
+    encode_latent's z0.  n1 None: Philox on the device, stream (1 << 32) | (image_index + i).  out: the destination (UNet.cond)."""
+    lib = _lib.hip()
+    _req(moments, torch.float32, 'moments'); _req(mask_u8, torch.uint8, 'mask')
+    n, c2, h, w = moments.shape
+    c = c2 // 2
+    assert tuple(mask_u8.shape) == (n, factor * h, factor * w), (mask_u8.shape, moments.shape)
+    if n1 is not None:
+        _req(n1, torch.float32, 'n1')
+        assert tuple(n1.shape) == (n, c, h, w), n1.shape
+    if out is None:
+        out = torch.empty((reps * n, 1 + c, h, w), dtype=torch.float32, device=moments.device)
+    else:
+        _req(out, torch.float32, 'out')
+        assert out.numel() == reps * n * (1 + c) * h * w, (out.shape, reps, n, c, h, w)
+    check(lib.sdod_inpaint_cond_f32(_p(moments), _p(mask_u8), _p(n1), _p(out), n, c, h, w, factor, reps, int(seed) & (2 ** 64 - 1),
+                                    int(image_index) & (2 ** 64 - 1), _stream()))
     return out
 
 

@@ -17,13 +17,16 @@ from .samplers import PLMS_ORDERS, PlmsSchedule
 class Txt2Img:
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
-                 with_vae_encoder=False):
+                 with_vae_encoder=False, inpaint_unet=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
         ViT-H/14 text tower (open_clip key names, penultimate block + ln_final, prompts padded with id 0 after EOT).
         with_vae_encoder=True: also build the VAE encoder (state_dicts['vae_enc'] or models_dir/vae_encoder.sdodw) for img2img();
-        off, nothing of it is constructed or loaded."""
+        off, nothing of it is constructed or loaded.
+        inpaint_unet=True: the UNet checkpoint is an inpainting one (`input_blocks.0.0.weight` [320, 9, 3, 3]): the UNet graph gets its
+        conditioning input (unet.cond) and the masked VAE encoder is built (state_dicts['vae_enc'] or models_dir/vae_encoder.sdodw) for
+        inpaint_concat(); off, nothing of either exists."""
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self.n = images_per_gpu
@@ -33,6 +36,10 @@ class Txt2Img:
         # int8 weight streaming (BASELINE config 5): when the UNet checkpoint holds affine-uint8 tensors (weights.QuantU8, the
         # reference's QNN encoding) they stay uint8 in HBM and the GEMMs expand them on the fly; weight_quant=False keeps the
         # round-1 behaviour (dequantise once at load, fp16 in HBM)
+        self.inpaint_unet = bool(inpaint_unet)
+        if self.inpaint_unet:
+            self.cfg.concat_channels = 5         # mask (1) | latent of the masked image (4), ldm's c_concat
+        self._cond_staged = False
         if weight_quant is None:
             weight_quant = state_dicts is not None and any(hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts['unet'].values())
         # weight_quant='auto' (or 2): stream the codes only where that is not slower than fp16 (sdod_model_config.weight_quant = 2)
@@ -59,11 +66,12 @@ class Txt2Img:
         self.vae = E.VaeDecoder(self.cfg, 1, device) if with_vae else None
         self.text = E.TextEncoder(self.cfg, 2, device) if with_text_encoder else None
         self.encoder = E.VaeEncoder(self.cfg, 1, device) if with_vae_encoder else None
+        self.masked_encoder = E.MaskedVaeEncoder(self.cfg, 1, device) if self.inpaint_unet else None
         self._temb_graphs = {}
         self._sd = state_dicts
         self._dir = models_dir
         for g, key, stem in ((self.unet, 'unet', 'unet'), (self.vae, 'vae', 'vae_decoder'), (self.text, 'text', 'text_encoder'),
-                             (self.encoder, 'vae_enc', 'vae_encoder')):
+                             (self.encoder, 'vae_enc', 'vae_encoder'), (self.masked_encoder, 'vae_enc', 'vae_encoder')):
             if g is None:
                 continue
             self._load(g, key, stem)
@@ -115,7 +123,14 @@ class Txt2Img:
         return self._temb_cache[key]
 
     # ------------------------------------------------------------------ one guided eps evaluation
+    def _require_cond(self):
+        """an inpainting UNet reads unet.cond in every evaluation: refuse to sample before inpaint_concat() has staged it"""
+        if getattr(self, 'inpaint_unet', False) and not self._cond_staged:
+            raise RuntimeError('this pipeline was built with inpaint_unet=True: its UNet needs the conditioning channels that '
+                               'inpaint_concat() stages; nothing has been staged yet')
+
     def _set_context(self, ctx2):
+        self._require_cond()
         n = self.n
         if self.cfg_split:
             self.unet.ctx.copy_(ctx2[self._half:self._half + 1].expand(n, -1, -1))
@@ -223,6 +238,7 @@ class Txt2Img:
         return torch.cat(outs, 0)
 
     def generate(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms'):
+        self._require_cond()
         z = self.sample_plms(ctx2, x_T, steps, guidance) if sampler == 'plms' else self.sample_dpm(ctx2, x_T, steps, guidance)
         return self.decode(z, mode=1 if sampler == 'plms' else 0)
 
@@ -232,6 +248,7 @@ class Txt2Img:
         step, so the GPU never waits for Python between steps (2-3 ms per image at 20 steps).  The sequence is static for a
         given (sampler, steps, guidance, batch): it is captured once from the ordinary eager code path (so it is the same
         kernels on the same buffers, bit for bit) and cached; ctx2 / x_T are copied into the graph's static inputs."""
+        self._require_cond()
         if self.cfg_split:                 # a collective per evaluation cannot live inside one captured graph
             return self.generate(ctx2, x_T, steps, guidance, sampler)
         key = (sampler, int(steps), float(guidance), tuple(x_T.shape))
@@ -462,6 +479,88 @@ class Txt2Img:
         g.replay()
         return out
 
+    # ------------------------------------------------------------------ inpainting with a 9-channel UNet (runwayml inpaint_st.py, ldm `hybrid`)
+    def _inpaint_concat_args(self, init_u8, mask_u8, x_T, steps, sampler, noise):
+        """the host-side checks of inpaint_concat() / inpaint_concat_graphed(), in one order for both: argument errors (ValueError),
+        then the missing 9-channel UNet (RuntimeError)"""
+        lat = (self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
+        inpaint_concat_check_args(init_u8, mask_u8, x_T, steps, sampler, noise, lat, self.n)
+        if getattr(self, 'masked_encoder', None) is None:
+            raise RuntimeError('Txt2Img(..., inpaint_unet=True) and a 9-channel inpainting checkpoint are needed for inpaint_concat')
+
+    def stage_inpaint_cond(self, init_u8, mask_u8, seed=0, image_index=0, noise=None):
+        """the UNet's conditioning input from the image and the mask: the masked encoder per image, then ONE launch into unet.cond
+        (ops.inpaint_cond: nearest-downsampled binarised mask | 0.18215 * posterior sample of the masked image, for both guidance
+        halves).  It is written once per image, no sampler launch touches it."""
+        moments = []
+        for i in range(init_u8.shape[0]):
+            self.masked_encoder.img.copy_(init_u8[i:i + 1])
+            self.masked_encoder.mask.copy_(mask_u8[i:i + 1])
+            self.masked_encoder.execute(self.use_hip_graph)
+            moments.append(self.masked_encoder.moments if init_u8.shape[0] == 1 else self.masked_encoder.moments.clone())
+        mom = moments[0] if len(moments) == 1 else torch.cat(moments, 0)
+        n1 = None if noise is None else noise.to(self.device, torch.float32).contiguous()
+        ops.inpaint_cond(mom, mask_u8, seed, image_index, n1, out=self.unet.cond, reps=self.unet.batch // self.n)
+        self._cond_staged = True
+
+    def inpaint_concat(self, ctx2, init_u8, mask_u8, x_T, steps=20, guidance=7.5, sampler='plms', seed=0, noise=None, image_index=0,
+                       composite=True):
+        """Inpainting with a 9-channel UNet: init_u8 uint8 [n, 8H, 8W, 3], mask_u8 uint8 [n, 8H, 8W] (255 = repaint).  m = mask >= 128;
+        the VAE encoder runs on (2 u / 255 - 1) * (1 - m); c_lat = 0.18215 * posterior sample with noise n1 (`noise`, fp32 [n, 4, H, W], or
+        None: Philox on the device, stream (1 << 32) | (image_index + i) of `seed`); c_mask = m[:, ::8, ::8]; the UNet sees
+        cat(x, c_mask, c_lat) in both guidance halves.  From pure noise x_T the ordinary sampler ('plms' or 'dpm', all steps), decode, and
+        with composite=True the integer pixel composite of inpaint() with the unbinarised mask bytes (pixels with mask byte 0 are
+        the init image's).  Argument errors raise ValueError before any device work."""
+        self._inpaint_concat_args(init_u8, mask_u8, x_T, steps, sampler, noise)
+        init_u8 = init_u8.to(self.device).contiguous()
+        mask_u8 = mask_u8.to(self.device).contiguous()
+        self.stage_inpaint_cond(init_u8, mask_u8, seed, image_index, noise)
+        z = self.sample_plms(ctx2, x_T, steps, guidance) if sampler == 'plms' else self.sample_dpm(ctx2, x_T, steps, guidance)
+        if composite:
+            return self._decode_composite(z, init_u8, mask_u8)
+        return self.decode(z, mode=1)
+
+    def inpaint_concat_graphed(self, ctx2, init_u8, mask_u8, x_T, steps=20, guidance=7.5, sampler='plms', seed=0, noise=None,
+                               image_index=0, composite=True):
+        """inpaint_concat() as ONE device graph replay (masked encoder, conditioning, every UNet evaluation and sampler update, decoder,
+        composite), captured once per (sampler, steps, guidance, composite, shape) from the eager path.  Image, mask, x_T and the noise
+        are inputs of the graph: without `noise` it is drawn into it first by sdod_randn_f32 on the stream the eager path draws in
+        its kernel, bit for bit, so the result equals inpaint_concat() with the same arguments.  Eager under cfg_split."""
+        self._inpaint_concat_args(init_u8, mask_u8, x_T, steps, sampler, noise)
+        if self.cfg_split:
+            return self.inpaint_concat(ctx2, init_u8, mask_u8, x_T, steps, guidance, sampler, seed, noise, image_index, composite)
+        n = init_u8.shape[0]
+        lat = (self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
+        key = ('inpaint_concat', sampler, int(steps), float(guidance), bool(composite), tuple(init_u8.shape))
+        cache = self.__dict__.setdefault('_traj', {})
+        if key not in cache:
+            s_ctx = torch.empty_like(ctx2, device=self.device)
+            s_img = torch.empty(tuple(init_u8.shape), dtype=torch.uint8, device=self.device)
+            s_mask = torch.empty(tuple(mask_u8.shape), dtype=torch.uint8, device=self.device)
+            s_x = torch.empty((n,) + lat, dtype=torch.float32, device=self.device)
+            s_n1 = torch.zeros((n,) + lat, dtype=torch.float32, device=self.device)
+            s_ctx.copy_(ctx2); s_img.copy_(init_u8); s_mask.copy_(mask_u8); s_x.copy_(x_T)
+            keep = self.use_hip_graph
+            self.use_hip_graph = False          # inside a capture the graphs run their launch lists
+            try:
+                self.inpaint_concat(s_ctx, s_img, s_mask, s_x, steps, guidance, sampler, noise=s_n1, composite=composite)  # warm-up
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                    out = self.inpaint_concat(s_ctx, s_img, s_mask, s_x, steps, guidance, sampler, noise=s_n1, composite=composite)
+            finally:
+                self.use_hip_graph = keep
+            cache[key] = (g, s_ctx, s_img, s_mask, s_x, s_n1, out)
+        g, s_ctx, s_img, s_mask, s_x, s_n1, out = cache[key]
+        s_ctx.copy_(ctx2); s_img.copy_(init_u8); s_mask.copy_(mask_u8); s_x.copy_(x_T)
+        if noise is None:
+            for i in range(n):
+                ops.randn((1,) + lat, seed, (1 << 32) | (image_index + i), self.device, out=s_n1[i:i + 1])
+        else:
+            s_n1.copy_(noise)
+        g.replay()
+        return out
+
     def generate_pipelined(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms'):
         """generate_graphed() as TWO device graphs -- sampling (context upload, every UNet evaluation, CFG, sampler updates) on
         the current stream and decoding (VAE + uint8) on a side stream -- so that the decode of image i runs while image i+1 is
@@ -540,10 +639,9 @@ def inpaint_levels(sch, t_enc):
     return out
 
 
-def inpaint_check_args(init_u8, mask_u8, strength, steps, step_noise, latent, n_images):
-    """the argument contract of Txt2Img.inpaint, checked on the host before any device work: init_u8 uint8 [n, 8H, 8W, 3] with n =
-    n_images and (4, H, W) = latent, the pipeline's batch and latent shape; mask_u8 uint8 [n, 8H, 8W]; strength in img2img_schedule's
-    domain; step_noise None or [t_enc - 1, n, 4, H, W].  Returns (schedule, t_enc); raises ValueError."""
+def inpaint_check_images(init_u8, mask_u8, latent, n_images):
+    """the image half of inpainting's argument contract: init_u8 uint8 [n, 8H, 8W, 3] with n = n_images and (4, H, W) = latent, the
+    pipeline's batch and latent shape; mask_u8 uint8 [n, 8H, 8W].  Returns n; raises ValueError."""
     for t, name in ((init_u8, 'init_u8'), (mask_u8, 'mask_u8')):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
             raise ValueError(f'{name} must be a uint8 tensor, got {getattr(t, "dtype", type(t))}')
@@ -558,12 +656,36 @@ def inpaint_check_args(init_u8, mask_u8, strength, steps, step_noise, latent, n_
         raise ValueError(f'the pipeline was built for {n_images} image(s) per call, got {n}')
     if (h // 8, w // 8) != tuple(latent[1:]):
         raise ValueError(f'the pipeline was built for {8 * latent[1]} x {8 * latent[2]} images, got {h} x {w}')
+    return n
+
+
+def inpaint_check_args(init_u8, mask_u8, strength, steps, step_noise, latent, n_images):
+    """the argument contract of Txt2Img.inpaint, checked on the host before any device work: init_u8 uint8 [n, 8H, 8W, 3] with n =
+    n_images and (4, H, W) = latent, the pipeline's batch and latent shape; mask_u8 uint8 [n, 8H, 8W]; strength in img2img_schedule's
+    domain; step_noise None or [t_enc - 1, n, 4, H, W].  Returns (schedule, t_enc); raises ValueError."""
+    n = inpaint_check_images(init_u8, mask_u8, latent, n_images)
     sch, t_enc = img2img_schedule(strength, steps)
     if step_noise is not None:
         want = (t_enc - 1, n) + tuple(latent)
         if not isinstance(step_noise, torch.Tensor) or tuple(step_noise.shape) != want:
             raise ValueError(f'step_noise must be {want} (t_enc - 1 = {t_enc - 1} noise levels), got {tuple(getattr(step_noise, "shape", ()))}')
     return sch, t_enc
+
+
+def inpaint_concat_check_args(init_u8, mask_u8, x_T, steps, sampler, noise, latent, n_images):
+    """the argument contract of Txt2Img.inpaint_concat, checked on the host before any device work: image and mask as
+    inpaint_check_images; x_T a floating-point tensor [n, 4, H, W]; steps >= 1; sampler 'plms' or 'dpm'; noise None or a tensor
+    [n, 4, H, W].  Raises ValueError."""
+    n = inpaint_check_images(init_u8, mask_u8, latent, n_images)
+    want = (n,) + tuple(latent)
+    if not isinstance(x_T, torch.Tensor) or not x_T.is_floating_point() or tuple(x_T.shape) != want:
+        raise ValueError(f'x_T must be a floating-point tensor {want}, got {tuple(getattr(x_T, "shape", ()))} {getattr(x_T, "dtype", type(x_T))}')
+    if sampler not in ('plms', 'dpm'):
+        raise ValueError(f"sampler must be 'plms' or 'dpm', got {sampler!r}")
+    if int(steps) != steps or int(steps) < 1:
+        raise ValueError(f'steps must be a positive integer, got {steps!r}')
+    if noise is not None and (not isinstance(noise, torch.Tensor) or tuple(noise.shape) != want):
+        raise ValueError(f'noise must be {want} (the posterior sample\'s normal draw), got {tuple(getattr(noise, "shape", ()))}')
 
 
 def broadcast_conditioning(ctx2, src=0):
