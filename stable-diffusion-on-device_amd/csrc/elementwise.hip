@@ -376,8 +376,69 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const f16* x, f16* y,
     }
 }
 
-// e = g*e_cond + (1-g)*e_uncond   (mode 0, the reference driver: scale, then accumulate)
+// ---- the sampler-step arithmetic, each piece once: the stand-alone kernels and the fused step kernels call the same
+// force-inlined functions, so a fused launch gives the bits of the launches it replaces by construction
+
+// classifier-free guidance of NCHW element (img, ch, pix) from its (uncond, cond) pair in the NHWC fp16 prediction [2n][hw][c]:
+// e = g*e_cond + (1-g)*e_uncond   (mode 0, the reference driver: scale, then accumulate; context.cpp:359-373)
 // e = e_uncond + g*(e_cond-e_uncond)  (mode 1, ldm's PLMS/DDIM samplers)
+// (I: int or size_t, the index type of the calling kernel, so that each kernel keeps the address arithmetic it had)
+template <typename I>
+SDOD_DEVICE float guided_eps(const f16* eps, int img, I ch, I pix, int n, int c, int hw, int uncond_first, float g, int mode) {
+    const int iu = uncond_first ? img : img + n;
+    const int ic = uncond_first ? img + n : img;
+    const float eu = (float)eps[((size_t)iu * hw + pix) * c + ch];
+    const float ec = (float)eps[((size_t)ic * hw + pix) * c + ch];
+    if (mode == 0) return add_rn(mul_rn(ec, g), mul_rn(eu, sub_rn(1.0f, g)));
+    return add_rn(eu, mul_rn(g, sub_rn(ec, eu)));
+}
+
+// (c0 v0 + c1 e1[i] + c2 e2[i] + c3 e3[i]) / div, a term with a null pointer left out (sdod_lincomb4_f32)
+SDOD_DEVICE float lincomb4(float c0, float v0, float c1, const float* e1, float c2, const float* e2, float c3, const float* e3, size_t i,
+                           float div) {
+    float v = mul_rn(c0, v0);
+    if (e1) v = add_rn(v, mul_rn(c1, e1[i]));
+    if (e2) v = add_rn(v, mul_rn(c2, e2[i]));
+    if (e3) v = add_rn(v, mul_rn(c3, e3[i]));
+    return div_rn(v, div);
+}
+
+// v-prediction: eps = lincomb4([v, x], [vc0, vc1], 1), as the host loop composes it (its division by 1 included)
+SDOD_DEVICE float v_to_eps(float v, float x, float vc0, float vc1) { return lincomb4(vc0, v, vc1, &x, 0.f, nullptr, 0.f, nullptr, 0, 1.0f); }
+
+// ldm DDIM/PLMS step (eta = 0): pred_x0 = (x - s1m_at*e)/s_at ; x = s_aprev*pred_x0 + dir*e
+SDOD_DEVICE float ddim_update(float x, float e, float s1m_at, float s_at, float s_aprev, float dir) {
+    const float x0 = div_rn(sub_rn(x, mul_rn(s1m_at, e)), s_at);
+    return add_rn(mul_rn(s_aprev, x0), mul_rn(dir, e));
+}
+
+// DPM-Solver++(2M) update of x[i] / y_prev[i] in place, dpm_solver.cpp:136-181 in its operation order; returns the new x[i]
+SDOD_DEVICE float dpm_update(float* x, float* y_prev, size_t i, float e, int order, float sigma_s, float alpha_s, float sigma_ratio,
+                             float c_prev, float c_cur) {
+    const float xv = x[i];
+    const float y = div_rn(add_rn(xv, mul_rn(-sigma_s, e)), alpha_s); // :139
+    float xn = mul_rn(xv, sigma_ratio);                               // :153 / :168
+    if (order == 2) xn = add_rn(xn, mul_rn(c_prev, y_prev[i]));       // :169
+    xn = add_rn(xn, mul_rn(c_cur, y));                                // :154 / :170
+    x[i] = xn;
+    y_prev[i] = y;                                                    // :177-180
+    return xn;
+}
+
+// element k of the grid's tail: the projected time-conditioning row broadcast to every batch row, dst [reps][width]
+SDOD_DEVICE void broadcast_row(f16* dst, const f16* row, size_t width, size_t k) { dst[k] = row[k % width]; }
+
+// v (one float, or a 16-byte lane of four) at offset o of each of the `reps` back-to-back copies of the latent in x_stage
+template <typename T>
+SDOD_DEVICE void stage_latent(float* x_stage, int reps, size_t lat, size_t o, T v) {
+    if (x_stage)
+        for (int r = 0; r < reps; ++r) *reinterpret_cast<T*>(x_stage + (size_t)r * lat + o) = v;
+}
+
+// threads of a step kernel's tail (the time-row broadcast), for the kernel and for its launch; A: one of the three step structs
+template <typename A>
+__host__ __device__ inline size_t temb_work(const A& a) { return a.temb_row ? (size_t)a.temb_width * a.temb_reps : 0; }
+
 __global__ void cfg_kernel(const f16* eps, float* out, int n, int c, int hw, float g, int uncond_first, int mode) {
     const size_t total = (size_t)n * c * hw;
     GRID_STRIDE(i, total) { // NCHW output index
@@ -385,53 +446,22 @@ __global__ void cfg_kernel(const f16* eps, float* out, int n, int c, int hw, flo
         const size_t t = i / hw;
         const int ch = (int)(t % c);
         const int img = (int)(t / c);
-        const int iu = uncond_first ? img : img + n;
-        const int ic = uncond_first ? img + n : img;
-        const float eu = (float)eps[((size_t)iu * hw + pix) * c + ch];
-        const float ec = (float)eps[((size_t)ic * hw + pix) * c + ch];
-        float e;
-        if (mode == 0) {
-            e = mul_rn(ec, g);
-            e = add_rn(e, mul_rn(eu, sub_rn(1.0f, g)));
-        } else {
-            e = add_rn(eu, mul_rn(g, sub_rn(ec, eu)));
-        }
-        out[i] = e;
+        out[i] = guided_eps(eps, img, ch, pix, n, c, hw, uncond_first, g, mode);
     }
 }
 
-// dpm_solver.cpp:136-181, same operation order, no FMA contraction
 __global__ void dpm_update_kernel(float* x, const float* eps, float* y_prev, size_t count, int order, float sigma_s,
                                   float alpha_s, float sigma_ratio, float c_prev, float c_cur) {
-    GRID_STRIDE(i, count) {
-        const float xv = x[i];
-        const float y = div_rn(add_rn(xv, mul_rn(-sigma_s, eps[i])), alpha_s); // :139
-        float xn = mul_rn(xv, sigma_ratio);                                            // :153 / :168
-        if (order == 2) xn = add_rn(xn, mul_rn(c_prev, y_prev[i]));                 // :169
-        xn = add_rn(xn, mul_rn(c_cur, y));                                          // :154 / :170
-        x[i] = xn;
-        y_prev[i] = y;                                                                    // :177-180
-    }
+    GRID_STRIDE(i, count) dpm_update(x, y_prev, i, eps[i], order, sigma_s, alpha_s, sigma_ratio, c_prev, c_cur);
 }
 
-// ldm DDIM/PLMS step (eta = 0): pred_x0 = (x - s1m_at*e)/s_at ; x = s_aprev*pred_x0 + dir*e
 __global__ void ddim_step_kernel(float* x, const float* e, size_t count, float s1m_at, float s_at, float s_aprev, float dir) {
-    GRID_STRIDE(i, count) {
-        const float ev = e[i];
-        const float x0 = div_rn(sub_rn(x[i], mul_rn(s1m_at, ev)), s_at);
-        x[i] = add_rn(mul_rn(s_aprev, x0), mul_rn(dir, ev));
-    }
+    GRID_STRIDE(i, count) x[i] = ddim_update(x[i], e[i], s1m_at, s_at, s_aprev, dir);
 }
 
 __global__ void lincomb4_kernel(float* out, const float* e0, const float* e1, const float* e2, const float* e3, float c0,
                                 float c1, float c2, float c3, float div, size_t count) {
-    GRID_STRIDE(i, count) {
-        float v = mul_rn(c0, e0[i]);
-        if (e1) v = add_rn(v, mul_rn(c1, e1[i]));
-        if (e2) v = add_rn(v, mul_rn(c2, e2[i]));
-        if (e3) v = add_rn(v, mul_rn(c3, e3[i]));
-        out[i] = div_rn(v, div);
-    }
+    GRID_STRIDE(i, count) out[i] = lincomb4(c0, e0[i], c1, e1, c2, e2, c3, e3, i, div);
 }
 
 // f = a * v + b -> uint8 (include/sdod_hip.h: sdod_image_to_u8); shared by to_u8_kernel and image_composite_kernel, so that both give
@@ -488,99 +518,61 @@ __global__ void mask_to_latent_kernel(const uint8_t* mask, float* keep, int n, i
 } // namespace
 
 
-// ---- sampler-loop staging: the UNet graph's inputs for one guided evaluation in ONE launch.  The latent x (fp32 NCHW, n
-// images) is written `reps` times back to back (uncond rows, then cond rows) and the projected time-conditioning row is
-// broadcast to every batch row -- the three strided copies the host loop used to issue per evaluation.
-// One PLMS step behind a UNet evaluation in ONE launch: classifier-free guidance (cfg_kernel's arithmetic), the optional
-// v -> eps conversion, the multistep combination (lincomb4_kernel), the DDIM update (ddim_step_kernel) and the staging of the
-// next evaluation's inputs (stage_unet_inputs_kernel) -- the same fp32 operations in the same order, so the results are the
-// bits the four launches produce (tests/test_kernels_gpu.py::test_plms_update_equals_the_four_launches).
+// One PLMS step behind a UNet evaluation in ONE launch: classifier-free guidance (cfg_kernel), the optional v -> eps conversion,
+// the multistep combination (lincomb4_kernel), the DDIM update (ddim_step_kernel) and the staging of the next evaluation's inputs
+// (stage_unet_inputs_kernel), in that order (tests/test_kernels_gpu.py::test_plms_update_equals_the_four_launches).
 __global__ void plms_update_kernel(const sdod_plms_update_args a) {
-    const size_t lat = (size_t)a.n * a.c * a.hw;
-    const size_t nt = a.temb_row ? (size_t)a.temb_width * a.temb_reps : 0;
-    const f16* eps = (const f16*)a.eps_nhwc;
+    const size_t lat = (size_t)a.n * a.c * a.hw, nt = temb_work(a);
     GRID_STRIDE(i, lat + nt) {
         if (i >= lat) {
-            ((f16*)a.temb_dst)[i - lat] = ((const f16*)a.temb_row)[(i - lat) % a.temb_width];
+            broadcast_row((f16*)a.temb_dst, (const f16*)a.temb_row, a.temb_width, i - lat);
             continue;
         }
         const int pix = (int)(i % a.hw);
         const size_t t = i / a.hw;
         const int ch = (int)(t % a.c);
         const int img = (int)(t / a.c);
-        const int iu = a.uncond_first ? img : img + a.n;
-        const int ic = a.uncond_first ? img + a.n : img;
-        const float eu = (float)eps[((size_t)iu * a.hw + pix) * a.c + ch];
-        const float ec = (float)eps[((size_t)ic * a.hw + pix) * a.c + ch];
-        float e;
-        if (a.mode == 0) {
-            e = mul_rn(ec, a.guidance);
-            e = add_rn(e, mul_rn(eu, sub_rn(1.0f, a.guidance)));
-        } else {
-            e = add_rn(eu, mul_rn(a.guidance, sub_rn(ec, eu)));
-        }
+        float e = guided_eps((const f16*)a.eps_nhwc, img, ch, pix, a.n, a.c, a.hw, a.uncond_first, a.guidance, a.mode);
         const float xv = a.x[i];
-        if (a.v_pred) e = div_rn(add_rn(mul_rn(a.vc0, e), mul_rn(a.vc1, xv)), 1.0f); // lincomb4([e, x], [vc0, vc1], 1)
+        if (a.v_pred) e = v_to_eps(e, xv, a.vc0, a.vc1);
         a.e_out[i] = e;
-        float v = mul_rn(a.c0, e);
-        if (a.old1) v = add_rn(v, mul_rn(a.c1, a.old1[i]));
-        if (a.old2) v = add_rn(v, mul_rn(a.c2, a.old2[i]));
-        if (a.old3) v = add_rn(v, mul_rn(a.c3, a.old3[i]));
-        const float ep = div_rn(v, a.div);
-        const float x0 = div_rn(sub_rn(xv, mul_rn(a.sqrt_one_minus_at, ep)), a.sqrt_at);
-        const float xn = add_rn(mul_rn(a.sqrt_a_prev, x0), mul_rn(a.dir_coef, ep));
+        const float ep = lincomb4(a.c0, e, a.c1, a.old1, a.c2, a.old2, a.c3, a.old3, i, a.div);
+        const float xn = ddim_update(xv, ep, a.sqrt_one_minus_at, a.sqrt_at, a.sqrt_a_prev, a.dir_coef);
         a.x[i] = xn;
-        if (a.x_stage)
-            for (int r = 0; r < a.stage_reps; ++r) a.x_stage[(size_t)r * lat + i] = xn;
+        stage_latent(a.x_stage, a.stage_reps, lat, i, xn);
     }
 }
 
 // The reference driver's per-step arithmetic behind a UNet evaluation in ONE launch (context.cpp:359-373 + dpm_solver.cpp:139-180 +
-// the next step's input staging, :348-352): cfg_kernel (either mode), dpm_update_kernel and stage_unet_inputs_kernel, the same
-// fp32 operations in the same order -- bit-identical to the three launches (test_dpm_step_equals_the_three_launches).
+// the next step's input staging, :348-352): cfg_kernel (either mode), dpm_update_kernel and stage_unet_inputs_kernel, in that order
+// (test_dpm_step_equals_the_three_launches).
 __global__ void dpm_step_kernel(const sdod_dpm_step_args a) {
-    const size_t lat = (size_t)a.n * a.c * a.hw;
-    const size_t nt = a.temb_row ? (size_t)a.temb_width * a.temb_reps : 0;
-    const f16* eps = (const f16*)a.eps_nhwc;
+    const size_t lat = (size_t)a.n * a.c * a.hw, nt = temb_work(a);
     GRID_STRIDE(i, lat + nt) {
         if (i >= lat) {
-            ((f16*)a.temb_dst)[i - lat] = ((const f16*)a.temb_row)[(i - lat) % a.temb_width];
+            broadcast_row((f16*)a.temb_dst, (const f16*)a.temb_row, a.temb_width, i - lat);
             continue;
         }
         const int pix = (int)(i % a.hw);
         const size_t t = i / a.hw;
         const int ch = (int)(t % a.c);
         const int img = (int)(t / a.c);
-        const int iu = a.uncond_first ? img : img + a.n;
-        const int ic = a.uncond_first ? img + a.n : img;
-        const float eu = (float)eps[((size_t)iu * a.hw + pix) * a.c + ch];
-        const float ec = (float)eps[((size_t)ic * a.hw + pix) * a.c + ch];
-        float e;
-        if (a.mode == 0) {
-            e = mul_rn(ec, a.guidance);
-            e = add_rn(e, mul_rn(eu, sub_rn(1.0f, a.guidance)));
-        } else {
-            e = add_rn(eu, mul_rn(a.guidance, sub_rn(ec, eu)));
-        }
+        const float e = guided_eps((const f16*)a.eps_nhwc, img, ch, pix, a.n, a.c, a.hw, a.uncond_first, a.guidance, a.mode);
         if (a.e_out) a.e_out[i] = e;
-        const float xv = a.x[i];
-        const float y = div_rn(add_rn(xv, mul_rn(-a.sigma_s, e)), a.alpha_s);
-        float xn = mul_rn(xv, a.sigma_ratio);
-        if (a.order == 2) xn = add_rn(xn, mul_rn(a.c_prev, a.y_prev[i]));
-        xn = add_rn(xn, mul_rn(a.c_cur, y));
-        a.x[i] = xn;
-        a.y_prev[i] = y;
-        if (a.x_stage)
-            for (int r = 0; r < a.stage_reps; ++r) a.x_stage[(size_t)r * lat + i] = xn;
+        const float xn = dpm_update(a.x, a.y_prev, i, e, a.order, a.sigma_s, a.alpha_s, a.sigma_ratio, a.c_prev, a.c_cur);
+        stage_latent(a.x_stage, a.stage_reps, lat, i, xn);
     }
 }
 
+// ---- sampler-loop staging: the UNet graph's inputs for one guided evaluation in ONE launch.  The latent x (fp32 NCHW, n
+// images) is written `reps` times back to back (uncond rows, then cond rows) and the projected time-conditioning row is
+// broadcast to every batch row -- the three strided copies the host loop used to issue per evaluation.
 __global__ void stage_unet_inputs_kernel(const float* x, float* x_dst, size_t lat, int reps, const f16* temb_row, f16* temb_dst,
                                          size_t temb_w, int temb_reps) {
     const size_t nx = lat * (size_t)reps, nt = temb_w * (size_t)temb_reps;
     GRID_STRIDE(i, nx + nt) {
         if (i < nx) x_dst[i] = x[i % lat];
-        else temb_dst[i - nx] = temb_row[(i - nx) % temb_w];
+        else broadcast_row(temb_dst, temb_row, temb_w, i - nx);
     }
 }
 
@@ -630,6 +622,28 @@ __global__ void randn_kernel(float* out, uint32_t* words, size_t count, uint64_t
     }
 }
 
+// the four normals of Philox block j of an image: noise[o .. o + 3] where the caller injects noise, else drawn from `stream` of `seed`
+SDOD_DEVICE f32x4 noise4(const float* noise, size_t o, uint64_t j, uint64_t seed, uint64_t stream) {
+    float z[4];
+    if (noise) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) z[q] = noise[o + q];
+    } else {
+        uint32_t w[4];
+        philox_normal4(j, seed, stream, w, z);
+    }
+    return f32x4{z[0], z[1], z[2], z[3]};
+}
+
+// ldm's posterior sample times the latent scale, 0.18215 * (mean + exp(0.5 * clamp(logvar, -30, 20)) * nrm), in torch's operation
+// order.  On HIP's __fmul_rn / __fadd_rn, not mul_rn / add_rn: they leave the compiler free to contract mean + sd * nrm (see the top
+// of the file), it does, and those are the bits the start latent has always had.
+SDOD_DEVICE float posterior_sample(float mean, float logvar, float nrm) {
+    logvar = fminf(fmaxf(logvar, -30.0f), 20.0f);
+    const float sd = expf(__fmul_rn(0.5f, logvar));
+    return __fmul_rn(0.18215f, __fadd_rn(mean, __fmul_rn(sd, nrm)));
+}
+
 // ldm img2img's start latent (include/sdod_hip.h: sdod_encode_latent_f32): posterior sample, 0.18215 scale and stochastic_encode in
 // fp32, torch's operation order (no contraction).  Thread = four consecutive elements of one image = one Philox block of its streams.
 __global__ void encode_latent_kernel(const float* mom, const float* n1, const float* n2, float* x, float* z0, int n, int c, int hw,
@@ -638,29 +652,13 @@ __global__ void encode_latent_kernel(const float* mom, const float* n1, const fl
     GRID_STRIDE(t, (size_t)n * nblk) {
         const int img = (int)(t / nblk);
         const size_t j = t - (size_t)img * nblk;
-        float r1[4], r2[4];
-        if (n1) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) r1[q] = n1[(size_t)img * per + 4 * j + q];
-        } else {
-            uint32_t w[4];
-            philox_normal4(j, seed, (1ull << 32) | (index0 + img), w, r1);
-        }
-        if (n2) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) r2[q] = n2[(size_t)img * per + 4 * j + q];
-        } else {
-            uint32_t w[4];
-            philox_normal4(j, seed, (2ull << 32) | (index0 + img), w, r2);
-        }
+        const f32x4 r1 = noise4(n1, (size_t)img * per + 4 * j, j, seed, (1ull << 32) | (index0 + img));
+        const f32x4 r2 = noise4(n2, (size_t)img * per + 4 * j, j, seed, (2ull << 32) | (index0 + img));
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const size_t e = 4 * j + q;
             const size_t ch = e / hw, pix = e - ch * hw;
-            const float mean = mom[((size_t)img * 2 * c + ch) * hw + pix];
-            const float logvar = fminf(fmaxf(mom[((size_t)img * 2 * c + c + ch) * hw + pix], -30.0f), 20.0f);
-            const float sd = expf(__fmul_rn(0.5f, logvar));
-            const float z = __fmul_rn(0.18215f, __fadd_rn(mean, __fmul_rn(sd, r1[q])));
+            const float z = posterior_sample(mom[((size_t)img * 2 * c + ch) * hw + pix], mom[((size_t)img * 2 * c + c + ch) * hw + pix], r1[q]);
             const size_t o = (size_t)img * per + e;
             if (z0) z0[o] = z;
             x[o] = __fadd_rn(__fmul_rn(sqrt_at, z), __fmul_rn(sqrt_1m_at, r2[q]));
@@ -670,7 +668,7 @@ __global__ void encode_latent_kernel(const float* mom, const float* n1, const fl
 
 // The conditioning input of the 9-channel inpainting UNet in ONE launch (include/sdod_hip.h: sdod_inpaint_cond_f32): channel 0 = the
 // binarised mask at latent resolution (nearest: the top-left byte of each 8 x 8 block), channels 1..c = encode_latent_kernel's z0 of
-// the masked image's moments (the same fp32 operations, the same Philox stream), written `reps` times back to back.  Threads
+// the masked image's moments (posterior_sample on the same Philox stream), written `reps` times back to back.  Threads
 // [0, n * c * hw / 4): four consecutive latent elements of one image = one Philox block; the rest: one mask element each.
 __global__ void inpaint_cond_kernel(const float* mom, const uint8_t* mask, const float* n1, float* cond, int n, int c, int h_lat, int w_lat,
                                     int reps, uint64_t seed, uint64_t index0) {
@@ -687,84 +685,49 @@ __global__ void inpaint_cond_kernel(const float* mom, const uint8_t* mask, const
         }
         const int img = (int)(t / nblk);
         const size_t j = t - (size_t)img * nblk;
-        float r1[4];
-        if (n1) {
-            const f32x4 nv = *reinterpret_cast<const f32x4*>(n1 + (size_t)img * per + 4 * j);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) r1[q] = nv[q];
-        } else {
-            uint32_t w[4];
-            philox_normal4(j, seed, (1ull << 32) | (index0 + img), w, r1);
-        }
+        const f32x4 r1 = noise4(n1, (size_t)img * per + 4 * j, j, seed, (1ull << 32) | (index0 + img));
         const size_t e0 = 4 * j, ch = e0 / hw, pix = e0 - ch * hw; // the four elements share a channel (hw % 4 == 0)
+        const float* mean = mom + ((size_t)img * 2 * c + ch) * hw + pix; // the logvar plane lies c channels behind
         f32x4 out;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float mean = mom[((size_t)img * 2 * c + ch) * hw + pix + q];
-            const float logvar = fminf(fmaxf(mom[((size_t)img * 2 * c + c + ch) * hw + pix + q], -30.0f), 20.0f);
-            const float sd = expf(__fmul_rn(0.5f, logvar));
-            out[q] = __fmul_rn(0.18215f, __fadd_rn(mean, __fmul_rn(sd, r1[q])));
-        }
+        for (int q = 0; q < 4; ++q) out[q] = posterior_sample(mean[q], mean[(size_t)c * hw + q], r1[q]);
         for (int r = 0; r < reps; ++r)
             *reinterpret_cast<f32x4*>(cond + (size_t)r * rep_stride + ((size_t)img * (c + 1) + 1 + ch) * hw + pix) = out;
     }
 }
 
 // One DDIM step (eta = 0) behind a UNet evaluation in ONE launch, with inpainting's latent blend (include/sdod_hip.h:
-// sdod_ddim_inpaint_step): cfg_kernel's guidance, the optional v -> eps conversion (lincomb4_kernel), ddim_step_kernel's update, then
-// x = keep * known + (1 - keep) * x' with known = sa * z0 + s1a * nu (or z0 at the last step), and the staging of the next
-// evaluation's inputs (stage_unet_inputs_kernel) -- the same fp32 operations in the same order as those launches, every product, sum
-// and difference rounded on its own.  Thread = four consecutive elements of one image = one Philox block of its noise stream (as
-// encode_latent_kernel); x, z0, the noise and x_stage move as 16-byte lanes.
+// sdod_ddim_inpaint_step): cfg_kernel's guidance, the optional v -> eps conversion, ddim_step_kernel's update, then
+// x = keep * known + (1 - keep) * x' with known = sa * z0 + s1a * nu (or z0 at the last step), every product, sum and difference
+// rounded on its own, and the staging of the next evaluation's inputs (stage_unet_inputs_kernel).  Thread = four consecutive elements
+// of one image = one Philox block of its noise stream (as encode_latent_kernel); x, z0 and x_stage move as 16-byte lanes.
 __global__ void ddim_inpaint_step_kernel(const sdod_ddim_inpaint_step_args a) {
     const size_t per = (size_t)a.c * a.hw, nblk = per / 4; // per % 4 == 0, pointers 16-byte aligned (checked by the host)
-    const size_t lat = (size_t)a.n * per, nlat = (size_t)a.n * nblk;
-    const size_t nt = a.temb_row ? (size_t)a.temb_width * a.temb_reps : 0;
-    const f16* eps = (const f16*)a.eps_nhwc;
+    const size_t lat = (size_t)a.n * per, nlat = (size_t)a.n * nblk, nt = temb_work(a);
     GRID_STRIDE(t, nlat + nt) {
         if (t >= nlat) {
-            ((f16*)a.temb_dst)[t - nlat] = ((const f16*)a.temb_row)[(t - nlat) % a.temb_width];
+            broadcast_row((f16*)a.temb_dst, (const f16*)a.temb_row, a.temb_width, t - nlat);
             continue;
         }
         const int img = (int)(t / nblk);
         const size_t j = t - (size_t)img * nblk;
         const size_t o = (size_t)img * per + 4 * j;
-        const int iu = a.uncond_first ? img : img + a.n;
-        const int ic = a.uncond_first ? img + a.n : img;
         const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + o);
         const bool blend = a.keep != nullptr;
         f32x4 zv = f32x4{0.f, 0.f, 0.f, 0.f};
-        float nu[4] = {0.f, 0.f, 0.f, 0.f};
+        f32x4 nu = f32x4{0.f, 0.f, 0.f, 0.f};
         if (blend) {
             zv = *reinterpret_cast<const f32x4*>(a.z0 + o);
-            if (!a.last) {
-                if (a.noise) {
-                    const f32x4 nv = *reinterpret_cast<const f32x4*>(a.noise + o);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) nu[q] = nv[q];
-                } else {
-                    uint32_t w[4];
-                    philox_normal4(j, a.seed, ((uint64_t)(3 + a.noise_level) << 32) | (a.image_index0 + img), w, nu);
-                }
-            }
+            if (!a.last) nu = noise4(a.noise, o, j, a.seed, ((uint64_t)(3 + a.noise_level) << 32) | (a.image_index0 + img));
         }
         f32x4 out;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const size_t e_i = 4 * j + q;
             const size_t ch = e_i / a.hw, pix = e_i - ch * a.hw;
-            const float eu = (float)eps[((size_t)iu * a.hw + pix) * a.c + ch];
-            const float ec = (float)eps[((size_t)ic * a.hw + pix) * a.c + ch];
-            float e;
-            if (a.mode == 0) {
-                e = mul_rn(ec, a.guidance);
-                e = add_rn(e, mul_rn(eu, sub_rn(1.0f, a.guidance)));
-            } else {
-                e = add_rn(eu, mul_rn(a.guidance, sub_rn(ec, eu)));
-            }
-            if (a.v_pred) e = div_rn(add_rn(mul_rn(a.vc0, e), mul_rn(a.vc1, xv[q])), 1.0f); // lincomb4([e, x], [vc0, vc1], 1)
-            const float x0 = div_rn(sub_rn(xv[q], mul_rn(a.sqrt_one_minus_at, e)), a.sqrt_at);
-            float xn = add_rn(mul_rn(a.sqrt_a_prev, x0), mul_rn(a.dir_coef, e));
+            float e = guided_eps((const f16*)a.eps_nhwc, img, ch, pix, a.n, a.c, a.hw, a.uncond_first, a.guidance, a.mode);
+            if (a.v_pred) e = v_to_eps(e, xv[q], a.vc0, a.vc1);
+            float xn = ddim_update(xv[q], e, a.sqrt_one_minus_at, a.sqrt_at, a.sqrt_a_prev, a.dir_coef);
             if (blend) {
                 const float k = a.keep[(size_t)img * a.hw + pix];
                 const float known = a.last ? zv[q] : add_rn(mul_rn(a.known_sa, zv[q]), mul_rn(a.known_s1a, nu[q]));
@@ -773,8 +736,7 @@ __global__ void ddim_inpaint_step_kernel(const sdod_ddim_inpaint_step_args a) {
             out[q] = xn;
         }
         *reinterpret_cast<f32x4*>(a.x + o) = out;
-        if (a.x_stage)
-            for (int r = 0; r < a.stage_reps; ++r) *reinterpret_cast<f32x4*>(a.x_stage + (size_t)r * lat + o) = out;
+        stage_latent(a.x_stage, a.stage_reps, lat, o, out);
     }
 }
 
@@ -981,14 +943,19 @@ extern "C" int sdod_stage_unet_inputs(const float* x, float* x_dst, size_t lat_c
     SDOD_CATCH
 }
 
+// the staging fields the three step structs share: their checks, and the launch's work = `latent_work` threads + the time-row tail
+template <typename A>
+size_t step_work(const A* a, size_t latent_work) {
+    SDOD_REQUIRE(!a->x_stage || a->stage_reps > 0, "x_stage needs stage_reps");
+    SDOD_REQUIRE(!a->temb_row || (a->temb_dst && a->temb_width > 0 && a->temb_reps > 0), "bad time-conditioning argument");
+    return latent_work + temb_work(*a);
+}
+
 extern "C" int sdod_plms_update(const sdod_plms_update_args* a, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(a && a->eps_nhwc && a->e_out && a->x && a->n > 0 && a->c > 0 && a->hw > 0 && (a->mode == 0 || a->mode == 1) && a->div != 0.0f,
                  "bad argument");
-    SDOD_REQUIRE(!a->x_stage || a->stage_reps > 0, "x_stage needs stage_reps");
-    SDOD_REQUIRE(!a->temb_row || (a->temb_dst && a->temb_width > 0 && a->temb_reps > 0), "bad time-conditioning argument");
-    const size_t work = (size_t)a->n * a->c * a->hw + (a->temb_row ? (size_t)a->temb_width * a->temb_reps : 0);
-    LAUNCH(plms_update_kernel, work, stream, *a);
+    LAUNCH(plms_update_kernel, step_work(a, (size_t)a->n * a->c * a->hw), stream, *a);
     return 0;
     SDOD_CATCH
 }
@@ -997,10 +964,7 @@ extern "C" int sdod_dpm_step(const sdod_dpm_step_args* a, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(a && a->eps_nhwc && a->x && a->y_prev && a->n > 0 && a->c > 0 && a->hw > 0 && (a->mode == 0 || a->mode == 1) &&
                      (a->order == 1 || a->order == 2), "bad argument");
-    SDOD_REQUIRE(!a->x_stage || a->stage_reps > 0, "x_stage needs stage_reps");
-    SDOD_REQUIRE(!a->temb_row || (a->temb_dst && a->temb_width > 0 && a->temb_reps > 0), "bad time-conditioning argument");
-    const size_t work = (size_t)a->n * a->c * a->hw + (a->temb_row ? (size_t)a->temb_width * a->temb_reps : 0);
-    LAUNCH(dpm_step_kernel, work, stream, *a);
+    LAUNCH(dpm_step_kernel, step_work(a, (size_t)a->n * a->c * a->hw), stream, *a);
     return 0;
     SDOD_CATCH
 }
@@ -1012,11 +976,9 @@ extern "C" int sdod_ddim_inpaint_step(const sdod_ddim_inpaint_step_args* a, void
     SDOD_REQUIRE(((size_t)a->c * a->hw) % 4 == 0, "c * hw must be a multiple of 4");
     SDOD_REQUIRE(!a->keep || a->z0, "keep needs z0");
     SDOD_REQUIRE(!a->keep || a->last || a->noise || a->noise_level >= 0, "negative noise level");
-    SDOD_REQUIRE(!a->x_stage || a->stage_reps > 0, "x_stage needs stage_reps");
-    SDOD_REQUIRE(!a->temb_row || (a->temb_dst && a->temb_width > 0 && a->temb_reps > 0), "bad time-conditioning argument");
+    const size_t work = step_work(a, (size_t)a->n * a->c * a->hw / 4);
     SDOD_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->z0 | (uintptr_t)a->noise | (uintptr_t)a->x_stage) & 15) == 0 &&
                      ((uintptr_t)a->keep & 3) == 0 && ((uintptr_t)a->eps_nhwc & 1) == 0, "misaligned pointer (x, z0, noise, x_stage: 16 bytes)");
-    const size_t work = (size_t)a->n * a->c * a->hw / 4 + (a->temb_row ? (size_t)a->temb_width * a->temb_reps : 0);
     LAUNCH(ddim_inpaint_step_kernel, work, stream, *a);
     return 0;
     SDOD_CATCH

@@ -532,16 +532,43 @@ def cfg_combine(eps_nhwc, guidance, uncond_first=True, mode=1):
     return out
 
 
+def _guided_dims(eps_nhwc, x):
+    """(n, c, hw) of the fp32 latent x [n, c, ...] behind the fp16 NHWC prediction [2n, ..., c] of its (uncond, cond) batch"""
+    _req(eps_nhwc, torch.float16, 'eps'); _req(x, torch.float32, 'x')
+    n2, c = eps_nhwc.shape[0], eps_nhwc.shape[-1]
+    n = n2 // 2
+    hw = eps_nhwc.numel() // (n2 * c)
+    assert x.numel() == n * c * hw
+    return n, c, hw
+
+
+def _fill_ddim(a, ddim):
+    a.sqrt_one_minus_at, a.sqrt_at, a.sqrt_a_prev, a.dir_coef = ddim['sqrt_one_minus_at'], ddim['sqrt_at'], ddim['sqrt_a_prev'], ddim['dir_coef']
+
+
+def _fill_v_pred(a, v_coef):
+    if v_coef is not None:
+        a.v_pred, a.vc0, a.vc1 = 1, v_coef[0], v_coef[1]
+
+
+def _fill_stage(a, x, stage):
+    """stage = (x_dst, temb_row, temb_dst) or None: the next evaluation's inputs, x repeated into x_dst and temb_row into every row of temb_dst"""
+    if stage is None:
+        return
+    x_dst, temb_row, temb_dst = stage
+    _req(x_dst, torch.float32, 'x_dst'); _req(temb_row, torch.float16, 'temb_row'); _req(temb_dst, torch.float16, 'temb_dst')
+    a.x_stage, a.stage_reps = _p(x_dst), x_dst.numel() // x.numel()
+    assert a.stage_reps * x.numel() == x_dst.numel() and temb_dst.numel() % temb_row.numel() == 0
+    a.temb_row, a.temb_dst, a.temb_width, a.temb_reps = _p(temb_row), _p(temb_dst), temb_row.numel(), temb_dst.numel() // temb_row.numel()
+
+
 def plms_update(eps_nhwc, x, old, coefs, div, ddim, guidance, mode=1, v_coef=None, stage=None):
     """one PLMS step in one launch (include/sdod_hip.h: sdod_plms_update): CFG of eps (+ v -> eps with v_coef = (c_e, c_x)),
     e' = (coefs[0] e_t + coefs[1:] . old) / div, DDIM update of x in place with ddim = schedule.coef(index), and -- with
     stage = (x_dst, temb_row, temb_dst) -- the next evaluation's inputs.  Returns e_t (fp32 [n, c, ...])."""
     lib = _lib.hip()
-    _req(eps_nhwc, torch.float16, 'eps'); _req(x, torch.float32, 'x')
-    n2, c = eps_nhwc.shape[0], eps_nhwc.shape[-1]
-    n = n2 // 2
-    hw = eps_nhwc.numel() // (n2 * c)
-    assert x.numel() == n * c * hw and len(old) <= 3 and len(coefs) == len(old) + 1
+    n, c, hw = _guided_dims(eps_nhwc, x)
+    assert len(old) <= 3 and len(coefs) == len(old) + 1
     e_out = torch.empty_like(x)
     a = _lib.PlmsUpdateArgs()
     a.eps_nhwc, a.e_out, a.x = _p(eps_nhwc), _p(e_out), _p(x)
@@ -551,15 +578,9 @@ def plms_update(eps_nhwc, x, old, coefs, div, ddim, guidance, mode=1, v_coef=Non
     a.old1, a.old2, a.old3 = _p(olds[0]), _p(olds[1]), _p(olds[2])
     a.n, a.c, a.hw, a.uncond_first, a.mode = n, c, hw, 1, mode
     a.guidance, a.c0, a.c1, a.c2, a.c3, a.div = guidance, cs[0], cs[1], cs[2], cs[3], div
-    if v_coef is not None:
-        a.v_pred, a.vc0, a.vc1 = 1, v_coef[0], v_coef[1]
-    a.sqrt_one_minus_at, a.sqrt_at, a.sqrt_a_prev, a.dir_coef = ddim['sqrt_one_minus_at'], ddim['sqrt_at'], ddim['sqrt_a_prev'], ddim['dir_coef']
-    if stage is not None:
-        x_dst, temb_row, temb_dst = stage
-        _req(x_dst, torch.float32, 'x_dst'); _req(temb_row, torch.float16, 'temb_row'); _req(temb_dst, torch.float16, 'temb_dst')
-        a.x_stage, a.stage_reps = _p(x_dst), x_dst.numel() // x.numel()
-        assert a.stage_reps * x.numel() == x_dst.numel() and temb_dst.numel() % temb_row.numel() == 0
-        a.temb_row, a.temb_dst, a.temb_width, a.temb_reps = _p(temb_row), _p(temb_dst), temb_row.numel(), temb_dst.numel() // temb_row.numel()
+    _fill_v_pred(a, v_coef)
+    _fill_ddim(a, ddim)
+    _fill_stage(a, x, stage)
     check(lib.sdod_plms_update(ctypes.byref(a), _stream()))
     return e_out
 
@@ -569,21 +590,15 @@ def dpm_step(eps_nhwc, x, y_prev, coef, guidance, mode=0, uncond_first=True, sta
     DPM-Solver++(2M) update of x / y_prev in place with coef = DpmSolver.coef(step), and -- with stage = (x_dst, temb_row,
     temb_dst) -- the next evaluation's inputs"""
     lib = _lib.hip()
-    _req(eps_nhwc, torch.float16, 'eps'); _req(x, torch.float32, 'x'); _req(y_prev, torch.float32, 'y_prev')
-    n2, c = eps_nhwc.shape[0], eps_nhwc.shape[-1]
-    n = n2 // 2
-    hw = eps_nhwc.numel() // (n2 * c)
-    assert x.numel() == n * c * hw == y_prev.numel()
+    n, c, hw = _guided_dims(eps_nhwc, x)
+    _req(y_prev, torch.float32, 'y_prev')
+    assert x.numel() == y_prev.numel()
     a = _lib.DpmStepArgs()
     a.eps_nhwc, a.x, a.y_prev = _p(eps_nhwc), _p(x), _p(y_prev)
     a.n, a.c, a.hw, a.uncond_first, a.mode, a.order = n, c, hw, 1 if uncond_first else 0, mode, coef['order']
     a.guidance = guidance
     a.sigma_s, a.alpha_s, a.sigma_ratio, a.c_prev, a.c_cur = coef['sigma_s'], coef['alpha_s'], coef['sigma_ratio'], coef['c_prev'], coef['c_cur']
-    if stage is not None:
-        x_dst, temb_row, temb_dst = stage
-        _req(x_dst, torch.float32, 'x_dst'); _req(temb_row, torch.float16, 'temb_row'); _req(temb_dst, torch.float16, 'temb_dst')
-        a.x_stage, a.stage_reps = _p(x_dst), x_dst.numel() // x.numel()
-        a.temb_row, a.temb_dst, a.temb_width, a.temb_reps = _p(temb_row), _p(temb_dst), temb_row.numel(), temb_dst.numel() // temb_row.numel()
+    _fill_stage(a, x, stage)
     check(lib.sdod_dpm_step(ctypes.byref(a), _stream()))
 
 
@@ -596,11 +611,7 @@ def ddim_inpaint_step(eps_nhwc, x, ddim, guidance, z0=None, keep=None, known=Non
     device: stream ((3 + noise_level) << 32) | (image_index + i) of `seed` for image i.  keep (fp32 [n, H, W]) None: a plain fused
     DDIM step."""
     lib = _lib.hip()
-    _req(eps_nhwc, torch.float16, 'eps'); _req(x, torch.float32, 'x')
-    n2, c = eps_nhwc.shape[0], eps_nhwc.shape[-1]
-    n = n2 // 2
-    hw = eps_nhwc.numel() // (n2 * c)
-    assert x.numel() == n * c * hw
+    n, c, hw = _guided_dims(eps_nhwc, x)
     a = _lib.DdimInpaintStepArgs()
     a.eps_nhwc, a.x = _p(eps_nhwc), _p(x)
     if keep is not None:
@@ -621,15 +632,9 @@ def ddim_inpaint_step(eps_nhwc, x, ddim, guidance, z0=None, keep=None, known=Non
             a.seed, a.noise_level, a.image_index0 = int(seed) & (2 ** 64 - 1), int(noise_level), int(image_index) & (2 ** 64 - 1)
     a.n, a.c, a.hw, a.uncond_first, a.mode = n, c, hw, 1, mode
     a.guidance = guidance
-    if v_coef is not None:
-        a.v_pred, a.vc0, a.vc1 = 1, v_coef[0], v_coef[1]
-    a.sqrt_one_minus_at, a.sqrt_at, a.sqrt_a_prev, a.dir_coef = ddim['sqrt_one_minus_at'], ddim['sqrt_at'], ddim['sqrt_a_prev'], ddim['dir_coef']
-    if stage is not None:
-        x_dst, temb_row, temb_dst = stage
-        _req(x_dst, torch.float32, 'x_dst'); _req(temb_row, torch.float16, 'temb_row'); _req(temb_dst, torch.float16, 'temb_dst')
-        a.x_stage, a.stage_reps = _p(x_dst), x_dst.numel() // x.numel()
-        assert a.stage_reps * x.numel() == x_dst.numel() and temb_dst.numel() % temb_row.numel() == 0
-        a.temb_row, a.temb_dst, a.temb_width, a.temb_reps = _p(temb_row), _p(temb_dst), temb_row.numel(), temb_dst.numel() // temb_row.numel()
+    _fill_v_pred(a, v_coef)
+    _fill_ddim(a, ddim)
+    _fill_stage(a, x, stage)
     check(lib.sdod_ddim_inpaint_step(ctypes.byref(a), _stream()))
 
 

@@ -15,6 +15,13 @@ from .samplers import PLMS_ORDERS, PlmsSchedule
 
 
 class Txt2Img:
+    # what an object made by Txt2Img.__new__ (no constructor: the argument checks run without a device) has of these
+    inpaint_unet = False
+    _cond_staged = False
+    encoder = None
+    masked_encoder = None
+    _traj = None        # {key: (graph, static inputs, output)} of _graphed, created with its first entry
+
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False):
@@ -125,7 +132,7 @@ class Txt2Img:
     # ------------------------------------------------------------------ one guided eps evaluation
     def _require_cond(self):
         """an inpainting UNet reads unet.cond in every evaluation: refuse to sample before inpaint_concat() has staged it"""
-        if getattr(self, 'inpaint_unet', False) and not self._cond_staged:
+        if self.inpaint_unet and not self._cond_staged:
             raise RuntimeError('this pipeline was built with inpaint_unet=True: its UNet needs the conditioning channels that '
                                'inpaint_concat() stages; nothing has been staged yet')
 
@@ -151,15 +158,18 @@ class Txt2Img:
             dist.all_gather_into_tensor(both, mine.contiguous(), group=self._pair)
         return both
 
+    def _unet_eps(self):
+        """one UNet evaluation of the staged inputs: the fp16 prediction [2n, H, W, 4] = (uncond rows ; cond rows)"""
+        self.unet.execute(self.use_hip_graph, static_unchanged=not self._ctx_fresh)
+        self._ctx_fresh = False
+        return self._exchange_halves(self.unet.eps) if self.cfg_split else self.unet.eps
+
     def _eps(self, x, temb_row, guidance, mode, v_coef=None):
         """x: fp32 [n,4,H,W]; returns guided eps fp32 [n,4,H,W].  Batch rows: [uncond x n ; cond x n] (ldm order).
         v_coef = (sqrt(abar_t), sqrt(1 - abar_t)) for a v-prediction model: the guided output is v, eps follows from it."""
         # one in-tree launch stages the graph inputs: x repeated for the (uncond, cond) halves, the time row for every batch row
         ops.stage_unet_inputs(x, self.unet.x, temb_row, self.unet.temb)
-        self.unet.execute(self.use_hip_graph, static_unchanged=not self._ctx_fresh)
-        self._ctx_fresh = False
-        eps = self._exchange_halves(self.unet.eps) if self.cfg_split else self.unet.eps
-        out = ops.cfg_combine(eps, guidance, uncond_first=True, mode=mode)
+        out = ops.cfg_combine(self._unet_eps(), guidance, uncond_first=True, mode=mode)
         if v_coef is not None:
             out = ops.lincomb4([out, x], [v_coef[0], v_coef[1]], 1.0)
         return out
@@ -181,9 +191,7 @@ class Txt2Img:
                 # and the staging of the next evaluation's inputs (ops.plms_update = the four separate launches, bit for bit)
                 if not staged:
                     ops.stage_unet_inputs(x, self.unet.x, temb[index], self.unet.temb)
-                self.unet.execute(self.use_hip_graph, static_unchanged=not self._ctx_fresh)
-                self._ctx_fresh = False
-                eps = self._exchange_halves(self.unet.eps) if self.cfg_split else self.unet.eps
+                eps = self._unet_eps()
                 k = min(len(old), 3)
                 coefs, div = PLMS_ORDERS[k]
                 nxt_stage = (self.unet.x, temb[index - 1], self.unet.temb) if i + 1 < n_steps else None
@@ -220,27 +228,65 @@ class Txt2Img:
         # staging of the next step's inputs: ops.dpm_step = cfg_combine + dpm_update + stage_unet_inputs, bit for bit)
         ops.stage_unet_inputs(x, self.unet.x, temb[0], self.unet.temb)
         for s in range(steps):
-            self.unet.execute(self.use_hip_graph, static_unchanged=not self._ctx_fresh)
-            self._ctx_fresh = False
-            eps = self._exchange_halves(self.unet.eps) if self.cfg_split else self.unet.eps
-            ops.dpm_step(eps, x, y_prev, solver.coef(s), guidance, mode=0,
+            ops.dpm_step(self._unet_eps(), x, y_prev, solver.coef(s), guidance, mode=0,
                          stage=(self.unet.x, temb[s + 1], self.unet.temb) if s + 1 < steps else None)
         return x
 
+    def _sample(self, sampler, ctx2, x_T, steps, guidance):
+        return self.sample_plms(ctx2, x_T, steps, guidance) if sampler == 'plms' else self.sample_dpm(ctx2, x_T, steps, guidance)
+
+    @property
+    def _latent_shape(self):
+        return (self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
+
     # ------------------------------------------------------------------ decode
-    def decode(self, latents, mode=1):
-        """latents fp32 [n,4,H,W] -> uint8 [n, 8H, 8W, 3] (mode 1 = ldm's 255*clamp((x+1)/2,0,1); mode 0 = reference driver)"""
+    def decode(self, latents, mode=1, composite=None):
+        """latents fp32 [n,4,H,W] -> uint8 [n, 8H, 8W, 3] (mode 1 = ldm's 255*clamp((x+1)/2,0,1); mode 0 = reference driver).
+        composite = (init_u8, mask_u8): inpainting's pixel composite in the place of image_to_u8, (d k + u (255 - k) + 127) / 255 per
+        byte (d decoded, u init, k mask byte)"""
         outs = []
         for i in range(latents.shape[0]):
             self.vae.z.copy_(latents[i:i + 1])
             self.vae.execute(self.use_hip_graph)
-            outs.append(ops.image_to_u8(self.vae.img, 0.5, 0.5, mode))
+            if composite is None:
+                outs.append(ops.image_to_u8(self.vae.img, 0.5, 0.5, mode))
+            else:
+                outs.append(ops.image_composite(self.vae.img, composite[0][i:i + 1], composite[1][i:i + 1], 0.5, 0.5, mode))
         return torch.cat(outs, 0)
 
     def generate(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms'):
         self._require_cond()
-        z = self.sample_plms(ctx2, x_T, steps, guidance) if sampler == 'plms' else self.sample_dpm(ctx2, x_T, steps, guidance)
-        return self.decode(z, mode=1 if sampler == 'plms' else 0)
+        return self.decode(self._sample(sampler, ctx2, x_T, steps, guidance), mode=1 if sampler == 'plms' else 0)
+
+    # ------------------------------------------------------------------ whole trajectories as one device graph
+    def _graphed(self, key, inputs, run):
+        """The capture behind every *_graphed method.  On the first use of `key`: allocates the graph's static inputs (`inputs`:
+        [(shape, dtype)], zeroed), calls run(*statics) -- the eager method -- once as warm-up (kernel attributes, time embeddings,
+        tuning) and captures a second call as ONE device graph, so a replay is the same kernels on the same buffers, bit for bit.
+        Returns the cached (graph, statics, out); the caller copies its inputs into the statics, then replays."""
+        if self._traj is None:
+            self._traj = {}
+        if key not in self._traj:
+            statics = [torch.zeros(tuple(shape), dtype=dtype, device=self.device) for shape, dtype in inputs]
+            keep = self.use_hip_graph
+            self.use_hip_graph = False          # inside a capture the engine graphs run their launch lists, not graphs of their own
+            try:
+                run(*statics)
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                # thread_local: another thread of the process (a collective backend's watchdog) may touch the runtime meanwhile
+                with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                    out = run(*statics)
+            finally:
+                self.use_hip_graph = keep
+            self._traj[key] = (g, statics, out)
+        return self._traj[key]
+
+    def _fill_noise(self, dst, seed, family, image_index):
+        """dst fp32 [n, 4, H, W] (a static noise input of a graph): image i from Philox stream (family << 32) | (image_index + i) of
+        `seed` by sdod_randn_f32, which is what the eager path's kernels draw for it, bit for bit"""
+        for i in range(dst.shape[0]):
+            ops.randn(tuple(dst[i:i + 1].shape), seed, (family << 32) | (image_index + i), self.device, out=dst[i:i + 1])
 
     def generate_graphed(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms'):
         """generate() with the WHOLE trajectory -- context upload, every UNet evaluation, CFG, sampler updates, VAE decode,
@@ -252,24 +298,8 @@ class Txt2Img:
         if self.cfg_split:                 # a collective per evaluation cannot live inside one captured graph
             return self.generate(ctx2, x_T, steps, guidance, sampler)
         key = (sampler, int(steps), float(guidance), tuple(x_T.shape))
-        cache = self.__dict__.setdefault('_traj', {})
-        if key not in cache:
-            s_ctx = torch.empty_like(ctx2, device=self.device)
-            s_x = torch.empty(tuple(x_T.shape), dtype=torch.float32, device=self.device)
-            s_ctx.copy_(ctx2); s_x.copy_(x_T)
-            keep = self.use_hip_graph
-            self.use_hip_graph = False          # inside a capture the UNet runs its launch list, not its own graph
-            try:
-                self.generate(s_ctx, s_x, steps, guidance, sampler)          # warm-up: kernel attributes, time embeddings, tuning
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                # thread_local: another thread of the process (a collective backend's watchdog) may touch the runtime meanwhile
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                    out = self.generate(s_ctx, s_x, steps, guidance, sampler)
-            finally:
-                self.use_hip_graph = keep
-            cache[key] = (g, s_ctx, s_x, out)
-        g, s_ctx, s_x, out = cache[key]
+        g, (s_ctx, s_x), out = self._graphed(key, [(ctx2.shape, ctx2.dtype), (x_T.shape, torch.float32)],
+                                             lambda c, x: self.generate(c, x, steps, guidance, sampler))
         s_ctx.copy_(ctx2); s_x.copy_(x_T)
         g.replay()
         return out
@@ -287,8 +317,7 @@ class Txt2Img:
         xs = []
         z0 = None
         if return_z0:
-            z0 = torch.empty((init_u8.shape[0], self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w), dtype=torch.float32,
-                             device=self.device)
+            z0 = torch.empty((init_u8.shape[0],) + self._latent_shape, dtype=torch.float32, device=self.device)
         for i in range(init_u8.shape[0]):
             self.encoder.img.copy_(init_u8[i:i + 1])
             self.encoder.execute(self.use_hip_graph)
@@ -328,34 +357,15 @@ class Txt2Img:
         _, t_enc = img2img_schedule(strength, steps)
         if self.cfg_split:
             return self.img2img(ctx2, init_u8, strength, steps, guidance, seed, noise, image_index)
-        n = init_u8.shape[0]
-        lat = (n, self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
+        lat = (init_u8.shape[0],) + self._latent_shape
         key = ('img2img', t_enc, int(steps), float(guidance), tuple(init_u8.shape))
-        cache = self.__dict__.setdefault('_traj', {})
-        if key not in cache:
-            s_ctx = torch.empty_like(ctx2, device=self.device)
-            s_img = torch.empty(tuple(init_u8.shape), dtype=torch.uint8, device=self.device)
-            s_n1 = torch.zeros(lat, dtype=torch.float32, device=self.device)
-            s_n2 = torch.zeros(lat, dtype=torch.float32, device=self.device)
-            s_ctx.copy_(ctx2); s_img.copy_(init_u8)
-            keep = self.use_hip_graph
-            self.use_hip_graph = False          # inside a capture the graphs run their launch lists
-            try:
-                self.img2img(s_ctx, s_img, strength, steps, guidance, noise=(s_n1, s_n2))     # warm-up
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                    out = self.img2img(s_ctx, s_img, strength, steps, guidance, noise=(s_n1, s_n2))
-            finally:
-                self.use_hip_graph = keep
-            cache[key] = (g, s_ctx, s_img, s_n1, s_n2, out)
-        g, s_ctx, s_img, s_n1, s_n2, out = cache[key]
+        g, (s_ctx, s_img, s_n1, s_n2), out = self._graphed(
+            key, [(ctx2.shape, ctx2.dtype), (init_u8.shape, torch.uint8), (lat, torch.float32), (lat, torch.float32)],
+            lambda c, img, n1, n2: self.img2img(c, img, strength, steps, guidance, noise=(n1, n2)))
         s_ctx.copy_(ctx2); s_img.copy_(init_u8)
         if noise is None:
-            per = lat[1:]
-            for i in range(n):
-                s_n1[i:i + 1].copy_(ops.randn((1,) + per, seed, (1 << 32) | (image_index + i), self.device))
-                s_n2[i:i + 1].copy_(ops.randn((1,) + per, seed, (2 << 32) | (image_index + i), self.device))
+            self._fill_noise(s_n1, seed, 1, image_index)
+            self._fill_noise(s_n2, seed, 2, image_index)
         else:
             s_n1.copy_(noise[0]); s_n2.copy_(noise[1])
         g.replay()
@@ -380,10 +390,7 @@ class Txt2Img:
         x = x.to(self.device, torch.float32).clone()
         ops.stage_unet_inputs(x, self.unet.x, temb[t_enc - 1], self.unet.temb)
         for index, j, sa, s1a in inpaint_levels(sch, t_enc):
-            self.unet.execute(self.use_hip_graph, static_unchanged=not self._ctx_fresh)
-            self._ctx_fresh = False
-            eps = self._exchange_halves(self.unet.eps) if self.cfg_split else self.unet.eps
-            ops.ddim_inpaint_step(eps, x, sch.coef(index), guidance, z0=z0, keep=keep, known=None if j is None else (sa, s1a),
+            ops.ddim_inpaint_step(self._unet_eps(), x, sch.coef(index), guidance, z0=z0, keep=keep, known=None if j is None else (sa, s1a),
                                   noise=None if j is None or step_noise is None else step_noise[j],
                                   seed=seed, noise_level=j or 0, image_index=image_index, mode=1,
                                   v_coef=sch.v_to_eps_coef(index) if self.v_prediction else None,
@@ -392,20 +399,10 @@ class Txt2Img:
                 trace.append((int(sch.timesteps[index]), index))
         return x
 
-    def _decode_composite(self, latents, init_u8, mask_u8):
-        """decode(mode 1) with inpainting's pixel composite in the place of image_to_u8: (d k + u (255 - k) + 127) / 255 per byte"""
-        outs = []
-        for i in range(latents.shape[0]):
-            self.vae.z.copy_(latents[i:i + 1])
-            self.vae.execute(self.use_hip_graph)
-            outs.append(ops.image_composite(self.vae.img, init_u8[i:i + 1], mask_u8[i:i + 1], 0.5, 0.5, 1))
-        return torch.cat(outs, 0)
-
     def _inpaint_args(self, init_u8, mask_u8, strength, steps, step_noise):
         """the host-side checks of inpaint() / inpaint_graphed(), in one order for both: argument errors (ValueError), then the
         missing encoder; returns t_enc"""
-        lat = (self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
-        _, t_enc = inpaint_check_args(init_u8, mask_u8, strength, steps, step_noise, lat, self.n)
+        _, t_enc = inpaint_check_args(init_u8, mask_u8, strength, steps, step_noise, self._latent_shape, self.n)
         if self.encoder is None:
             raise RuntimeError('Txt2Img(..., with_vae_encoder=True) is needed for inpainting')
         return t_enc
@@ -427,7 +424,7 @@ class Txt2Img:
         keep = ops.mask_to_latent(mask_u8)
         x, z0 = self.encode(init_u8, seed, image_index, strength, steps, noise, return_z0=True)
         z = self.sample_ddim_inpaint(ctx2, x, z0, keep, t_enc, steps, guidance, seed, image_index, step_noise, trace)
-        return self._decode_composite(z, init_u8, mask_u8) if composite else self.decode(z, mode=1)
+        return self.decode(z, mode=1, composite=(init_u8, mask_u8) if composite else None)
 
     def inpaint_graphed(self, ctx2, init_u8, mask_u8, strength=0.75, steps=50, guidance=7.5, seed=0, noise=None, step_noise=None,
                         image_index=0, composite=True):
@@ -436,44 +433,24 @@ class Txt2Img:
         inputs of the graph: without `noise` / `step_noise` they are drawn into it first by sdod_randn_f32 on the streams the eager
         path draws in its kernels, bit for bit, so the result equals inpaint() with the same arguments.  Eager under cfg_split."""
         t_enc = self._inpaint_args(init_u8, mask_u8, strength, steps, step_noise)
-        lat = (self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
         if self.cfg_split:
             return self.inpaint(ctx2, init_u8, mask_u8, strength, steps, guidance, seed, noise, step_noise, image_index, composite)
-        n = init_u8.shape[0]
+        lat = (init_u8.shape[0],) + self._latent_shape
         key = ('inpaint', t_enc, int(steps), float(guidance), bool(composite), tuple(init_u8.shape))
-        cache = self.__dict__.setdefault('_traj', {})
-        if key not in cache:
-            s_ctx = torch.empty_like(ctx2, device=self.device)
-            s_img = torch.empty(tuple(init_u8.shape), dtype=torch.uint8, device=self.device)
-            s_mask = torch.empty(tuple(mask_u8.shape), dtype=torch.uint8, device=self.device)
-            s_n1 = torch.zeros((n,) + lat, dtype=torch.float32, device=self.device)
-            s_n2 = torch.zeros((n,) + lat, dtype=torch.float32, device=self.device)
-            s_sn = torch.zeros((t_enc - 1, n) + lat, dtype=torch.float32, device=self.device)
-            s_ctx.copy_(ctx2); s_img.copy_(init_u8); s_mask.copy_(mask_u8)
-            keep = self.use_hip_graph
-            self.use_hip_graph = False          # inside a capture the graphs run their launch lists
-            try:
-                self.inpaint(s_ctx, s_img, s_mask, strength, steps, guidance, noise=(s_n1, s_n2), step_noise=s_sn, composite=composite)  # warm-up
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                    out = self.inpaint(s_ctx, s_img, s_mask, strength, steps, guidance, noise=(s_n1, s_n2), step_noise=s_sn,
-                                       composite=composite)
-            finally:
-                self.use_hip_graph = keep
-            cache[key] = (g, s_ctx, s_img, s_mask, s_n1, s_n2, s_sn, out)
-        g, s_ctx, s_img, s_mask, s_n1, s_n2, s_sn, out = cache[key]
+        g, (s_ctx, s_img, s_mask, s_n1, s_n2, s_sn), out = self._graphed(
+            key, [(ctx2.shape, ctx2.dtype), (init_u8.shape, torch.uint8), (mask_u8.shape, torch.uint8), (lat, torch.float32),
+                  (lat, torch.float32), ((t_enc - 1,) + lat, torch.float32)],
+            lambda c, img, mask, n1, n2, sn: self.inpaint(c, img, mask, strength, steps, guidance, noise=(n1, n2), step_noise=sn,
+                                                          composite=composite))
         s_ctx.copy_(ctx2); s_img.copy_(init_u8); s_mask.copy_(mask_u8)
         if noise is None:
-            for i in range(n):
-                ops.randn((1,) + lat, seed, (1 << 32) | (image_index + i), self.device, out=s_n1[i:i + 1])
-                ops.randn((1,) + lat, seed, (2 << 32) | (image_index + i), self.device, out=s_n2[i:i + 1])
+            self._fill_noise(s_n1, seed, 1, image_index)
+            self._fill_noise(s_n2, seed, 2, image_index)
         else:
             s_n1.copy_(noise[0]); s_n2.copy_(noise[1])
         if step_noise is None:
             for j in range(t_enc - 1):
-                for i in range(n):
-                    ops.randn((1,) + lat, seed, ((3 + j) << 32) | (image_index + i), self.device, out=s_sn[j, i:i + 1])
+                self._fill_noise(s_sn[j], seed, 3 + j, image_index)
         else:
             s_sn.copy_(step_noise)
         g.replay()
@@ -483,9 +460,8 @@ class Txt2Img:
     def _inpaint_concat_args(self, init_u8, mask_u8, x_T, steps, sampler, noise):
         """the host-side checks of inpaint_concat() / inpaint_concat_graphed(), in one order for both: argument errors (ValueError),
         then the missing 9-channel UNet (RuntimeError)"""
-        lat = (self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
-        inpaint_concat_check_args(init_u8, mask_u8, x_T, steps, sampler, noise, lat, self.n)
-        if getattr(self, 'masked_encoder', None) is None:
+        inpaint_concat_check_args(init_u8, mask_u8, x_T, steps, sampler, noise, self._latent_shape, self.n)
+        if self.masked_encoder is None:
             raise RuntimeError('Txt2Img(..., inpaint_unet=True) and a 9-channel inpainting checkpoint are needed for inpaint_concat')
 
     def stage_inpaint_cond(self, init_u8, mask_u8, seed=0, image_index=0, noise=None):
@@ -515,10 +491,8 @@ class Txt2Img:
         init_u8 = init_u8.to(self.device).contiguous()
         mask_u8 = mask_u8.to(self.device).contiguous()
         self.stage_inpaint_cond(init_u8, mask_u8, seed, image_index, noise)
-        z = self.sample_plms(ctx2, x_T, steps, guidance) if sampler == 'plms' else self.sample_dpm(ctx2, x_T, steps, guidance)
-        if composite:
-            return self._decode_composite(z, init_u8, mask_u8)
-        return self.decode(z, mode=1)
+        z = self._sample(sampler, ctx2, x_T, steps, guidance)
+        return self.decode(z, mode=1, composite=(init_u8, mask_u8) if composite else None)
 
     def inpaint_concat_graphed(self, ctx2, init_u8, mask_u8, x_T, steps=20, guidance=7.5, sampler='plms', seed=0, noise=None,
                                image_index=0, composite=True):
@@ -529,33 +503,14 @@ class Txt2Img:
         self._inpaint_concat_args(init_u8, mask_u8, x_T, steps, sampler, noise)
         if self.cfg_split:
             return self.inpaint_concat(ctx2, init_u8, mask_u8, x_T, steps, guidance, sampler, seed, noise, image_index, composite)
-        n = init_u8.shape[0]
-        lat = (self.cfg.latent_channels, self.cfg.latent_h, self.cfg.latent_w)
+        lat = (init_u8.shape[0],) + self._latent_shape
         key = ('inpaint_concat', sampler, int(steps), float(guidance), bool(composite), tuple(init_u8.shape))
-        cache = self.__dict__.setdefault('_traj', {})
-        if key not in cache:
-            s_ctx = torch.empty_like(ctx2, device=self.device)
-            s_img = torch.empty(tuple(init_u8.shape), dtype=torch.uint8, device=self.device)
-            s_mask = torch.empty(tuple(mask_u8.shape), dtype=torch.uint8, device=self.device)
-            s_x = torch.empty((n,) + lat, dtype=torch.float32, device=self.device)
-            s_n1 = torch.zeros((n,) + lat, dtype=torch.float32, device=self.device)
-            s_ctx.copy_(ctx2); s_img.copy_(init_u8); s_mask.copy_(mask_u8); s_x.copy_(x_T)
-            keep = self.use_hip_graph
-            self.use_hip_graph = False          # inside a capture the graphs run their launch lists
-            try:
-                self.inpaint_concat(s_ctx, s_img, s_mask, s_x, steps, guidance, sampler, noise=s_n1, composite=composite)  # warm-up
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                    out = self.inpaint_concat(s_ctx, s_img, s_mask, s_x, steps, guidance, sampler, noise=s_n1, composite=composite)
-            finally:
-                self.use_hip_graph = keep
-            cache[key] = (g, s_ctx, s_img, s_mask, s_x, s_n1, out)
-        g, s_ctx, s_img, s_mask, s_x, s_n1, out = cache[key]
+        g, (s_ctx, s_img, s_mask, s_x, s_n1), out = self._graphed(
+            key, [(ctx2.shape, ctx2.dtype), (init_u8.shape, torch.uint8), (mask_u8.shape, torch.uint8), (lat, torch.float32), (lat, torch.float32)],
+            lambda c, img, mask, x, n1: self.inpaint_concat(c, img, mask, x, steps, guidance, sampler, noise=n1, composite=composite))
         s_ctx.copy_(ctx2); s_img.copy_(init_u8); s_mask.copy_(mask_u8); s_x.copy_(x_T)
         if noise is None:
-            for i in range(n):
-                ops.randn((1,) + lat, seed, (1 << 32) | (image_index + i), self.device, out=s_n1[i:i + 1])
+            self._fill_noise(s_n1, seed, 1, image_index)
         else:
             s_n1.copy_(noise)
         g.replay()
@@ -573,45 +528,26 @@ class Txt2Img:
             ev = torch.cuda.Event(); ev.record()
             return out, ev
         key = ('pipelined', sampler, int(steps), float(guidance), tuple(x_T.shape))
-        cache = self.__dict__.setdefault('_traj', {})
         mode = 1 if sampler == 'plms' else 0
-        if key not in cache:
-            s_ctx = torch.empty_like(ctx2, device=self.device)
-            s_x = torch.empty(tuple(x_T.shape), dtype=torch.float32, device=self.device)
-            s_ctx.copy_(ctx2); s_x.copy_(x_T)
-            sample = self.sample_plms if sampler == 'plms' else self.sample_dpm
-            side = torch.cuda.Stream(device=self.device)
-            keep = self.use_hip_graph
-            self.use_hip_graph = False          # inside a capture the graphs run their launch lists
-            try:
-                z = sample(s_ctx, s_x, steps, guidance)                       # warm-up: kernel attributes, time embeddings, tuning
-                self.decode(z, mode=mode)
-                torch.cuda.synchronize(self.device)
-                g_s = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_s, capture_error_mode='thread_local'):
-                    z_s = sample(s_ctx, s_x, steps, guidance)
-                z_in = torch.empty_like(z_s)
-                g_d = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_d, capture_error_mode='thread_local'):
-                    out = self.decode(z_in, mode=mode)
-            finally:
-                self.use_hip_graph = keep
-            cache[key] = dict(g_s=g_s, g_d=g_d, s_ctx=s_ctx, s_x=s_x, z_s=z_s, z_in=z_in, out=out, side=side,
-                              copied=None, decoded=None)
-        c = cache[key]
+        g_s, (s_ctx, s_x), z_s = self._graphed(key + ('sample',), [(ctx2.shape, ctx2.dtype), (x_T.shape, torch.float32)],
+                                               lambda c, x: self._sample(sampler, c, x, steps, guidance))
+        g_d, (z_in,), out = self._graphed(key + ('decode',), [(z_s.shape, z_s.dtype)], lambda z: self.decode(z, mode=mode))
+        if key not in self._traj:
+            self._traj[key] = dict(side=torch.cuda.Stream(device=self.device), copied=None, decoded=None)
+        c = self._traj[key]
         main = torch.cuda.current_stream(self.device)
         if c['copied'] is not None:
             main.wait_event(c['copied'])        # the previous latent has left z_s
-        c['s_ctx'].copy_(ctx2); c['s_x'].copy_(x_T)
-        c['g_s'].replay()
+        s_ctx.copy_(ctx2); s_x.copy_(x_T)
+        g_s.replay()
         sampled = torch.cuda.Event(); sampled.record(main)
         with torch.cuda.stream(c['side']):
             c['side'].wait_event(sampled)
-            c['z_in'].copy_(c['z_s'])
+            z_in.copy_(z_s)
             c['copied'] = torch.cuda.Event(); c['copied'].record(c['side'])
-            c['g_d'].replay()
+            g_d.replay()
             c['decoded'] = torch.cuda.Event(); c['decoded'].record(c['side'])
-        return c['out'], c['decoded']
+        return out, c['decoded']
 
 
 def img2img_schedule(strength, steps):

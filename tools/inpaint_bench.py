@@ -53,22 +53,7 @@ def composed_inpaint(pipe, ctx2, u8, mask, strength, steps, guidance, noise, ste
         ops.ddim_step(x, e_t, **sch.coef(index))
         known = z0 if j is None else sa * z0 + s1a * step_noise[j]
         x = keep * known + (1 - keep) * x
-    return pipe._decode_composite(x, u8, mask)
-
-
-def capture(pipe, fn):
-    """fn() captured as one device graph the way Txt2Img.*_graphed do it: warm-up, then capture with the engine graphs as launch lists"""
-    keep = pipe.use_hip_graph
-    pipe.use_hip_graph = False
-    try:
-        fn()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode='thread_local'):
-            out = fn()
-    finally:
-        pipe.use_hip_graph = keep
-    return g, out
+    return pipe.decode(x, mode=1, composite=(u8, mask))
 
 
 def _summary(v):
@@ -213,7 +198,8 @@ def main():
     eager = pipe.inpaint(ctx2, u8, mask, s, st, gd, noise=(n1, n2), step_noise=sn)
     assert torch.equal(pipe.inpaint_graphed(ctx2, u8, mask, s, st, gd, noise=(n1, n2), step_noise=sn), eager)
     g_fused = pipe._traj[('inpaint', t_enc, int(st), float(gd), True, tuple(u8.shape))][0]
-    g_comp, out_comp = capture(pipe, lambda: composed_inpaint(pipe, ctx2, u8, mask, s, st, gd, (n1, n2), sn))
+    # captured the way Txt2Img.*_graphed do it (warm-up, then capture with the engine graphs as launch lists), on the same inputs
+    g_comp, _, out_comp = pipe._graphed(('composed', t_enc, int(st), float(gd)), [], lambda: composed_inpaint(pipe, ctx2, u8, mask, s, st, gd, (n1, n2), sn))
     g_comp.replay()
     torch.cuda.synchronize()
     composed_equal = bool(torch.equal(out_comp, eager))
