@@ -488,12 +488,12 @@ IoSlot Graph::io(bool output, int index) const {
 // tuner (gemm.hip's static heuristic decides), SDOD_AUTOTUNE=hot ranks with back-to-back launches instead.
 namespace {
 constexpr size_t kPrefetchMinBytes = (size_t)12 << 20; // weight matrices at least this big are prefetched (Graph::run_ops)
-const int kCandidates[] = {1, 2, 3, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, // (25, 26 spill in their epilogue only; the tuner decides)
-                           37, 38, 39, 40, 41, 42, 43, 44, 45, // halo-patch convolution tiles: rejected by every other descriptor
-                           46, 47, 48,
-                           49, 50, 51, 52, // halo-patch tiles of 96 / 192 rows (image rows that are multiples of 3: config 5)
-                           53, 54, 55,     // A-panel tiles (short-K wide-N Linears): rejected by every other descriptor
-                           56, 57, 58, 59, 60, 61}; // ring tiles whose waves own a head's 80 columns: the softmax-epilogue GEMM of the folded cross-attention
+// the candidate tiles: the rows of gemm.hip's tile table that are marked for the tuner (today all but 4, 15 and 16)
+const std::vector<int> kCandidates = [] {
+    std::vector<int> v((size_t)gemm_tuner_tiles(nullptr, 0));
+    gemm_tuner_tiles(v.data(), (int)v.size());
+    return v;
+}();
 
 struct ShapeKey {
     static constexpr int kFields = 14;

@@ -4,23 +4,34 @@
 //
 // This is the arithmetic behind every Linear / 1x1 conv / 3x3 conv of the UNet, VAE decoder and CLIP
 // graphs that the reference executes as opaque QNN blobs (qnn_context.cpp:711-713; op inventory in
-// analyze_results.py:20-93).  Design (MI355X-first, not a CUDA tiling):
-//   * one workgroup = 256 threads = 4 wave64; each wave owns a (BM/WM)x(BN/WN) output tile built from
-//     v_mfma_f32_16x16x32_f16 (fp32 accumulate in the unified VGPR/AGPR file);
+// analyze_results.py:20-93).  Common to every kernel of this file (MI355X-first, not a CUDA tiling):
+//   * a wave owns a (BM/WM)x(BN/WN) part of the workgroup's output tile, built from v_mfma_f32_16x16x32_f16 (fp32 accumulate
+//     in the unified VGPR/AGPR file);
 //   * K is walked in BK=64 slabs; both operands are K-contiguous, so a slab row is one 128-byte line.
 //     For the 3x3 conv the slab of row m=(img,oy,ox) is the 128-byte channel run of ONE input pixel
 //     (tap (r,s), channels c..c+63) -- im2col never exists in HBM; nearest-2x upsampling, stride 2, a
 //     two-tensor channel concat and the 1x1 case (ksize 1) are folded into the same address computation;
-//   * slabs are staged global -> registers -> LDS (double-buffered, one barrier per slab; the loads for
-//     slab t+1 are issued before the MFMAs of slab t), LDS rows are XOR-swizzled in 16-byte chunks so
-//     the ds_read_b128 fragment reads are bank-conflict free;
+//   * LDS rows are XOR-swizzled in 16-byte chunks so the ds_read_b128 fragment reads are bank-conflict free;
 //   * W is the MFMA "A" operand and the activations the "B" operand, so each lane ends up holding four
 //     CONSECUTIVE output columns of one row: the epilogue packs them to fp16, stages the tile through
 //     LDS and stores full 16-byte row segments (coalesced), with bias / per-image bias (time embedding)
 //     / activation / residual fused;
-//   * workgroup ids are remapped so that the n-tiles of one m-tile share an XCD (its L2 holds the A rows);
+//   * workgroup ids are remapped so that consecutive logical tiles share an XCD, and the ORDER of the logical ids (tile_of)
+//     decides which operand each of the eight L2s keeps;
 //   * small-M layers (8x8 / 16x16 feature maps) are weight-bandwidth bound: split-K spreads the weight
 //     stream over all 256 CUs, partial slabs are reduced (with the fused epilogue) by a second kernel.
+// Four kernels differ in how the slabs reach LDS and who multiplies them; which one a tile id means is one row of kTile[]:
+//   * gemm_kernel (tiles 1..5): 256 threads = 4 wave64, slabs staged global -> registers -> LDS, double-buffered, one barrier
+//     per slab (the loads for slab t+1 are issued before the MFMAs of slab t).  Plain epilogue only.
+//   * gemm_glds_kernel (the ring tiles): LDS-DMA into a ring of STAGES slab groups behind counted vmcnt waits; 4 or 8 waves that
+//     each load and multiply, or wave-specialised (SPEC: as many loader waves as consumer waves, software-pipelined consumers).
+//     Carries every fusion: GEGLU, LayerNorm fold, fused 1x1 tail, uint8 weights, per-image weights, the row softmax.
+//   * conv_halo_kernel (the halo tiles): 3x3 stride-1 convolutions with the input patch of the tile resident in LDS -- 4 loader
+//     + 4 consumer waves, split-K with an in-kernel fixup or a chained 1x1 tail.
+//   * gemm_apanel_kernel (the A-panel tiles): short-K wide-N Linears -- a row panel x whole K resident in LDS, 4 loader waves
+//     and two consumer groups that alternate between multiplying a tile and running the epilogue of the previous one.
+// The epilogue steps that do not depend on the kernel (partial-slab store, alpha and the column biases, the uint8 scale, staging
+// and storing the output tile) and the pieces of the pipelined consumer loops are written once, above the kernels.
 #include "common.h"
 #include "sdod_hip.h"
 #include "host_util.h"
@@ -29,6 +40,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -134,6 +146,160 @@ SDOD_DEVICE void tile_of(const GemmP& p, int lid, int& tile_m, int& tile_n) {
 }
 
 SDOD_DEVICE int lds_off(int row, int chunk) { return row * 64 + ((chunk ^ (row & 7)) << 3); }
+
+// compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
+template <int N, int I = 0, class F>
+SDOD_DEVICE void static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<N, I + 1>(f);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Epilogue pieces the kernels share.  After the K loop a lane of every kernel holds the same thing: accumulator quads
+// acc[i][j] = out[m][n .. n + 3] with m = m_wave + 16 i + e_m and n = n_wave + 16 j + e_n -- (m_wave, n_wave) the first row /
+// column of the wave's part of the tile (tile-local: wm_off, wn_off), e_m = lane & 15, e_n = 4 * (lane >> 4) -- so each step
+// that does not depend on how the operands got into LDS is written once here.  All force-inlined, the accumulators by
+// reference: nothing leaves registers.  RULE of the rounding point: a value is rounded to fp16 once, after the activation; the
+// residual is added to that fp16 value in fp32 and the sum rounded again -- stage_ctile + store_ctile on the un-split paths,
+// reduce_quad_epilogue on the split ones.
+// What is NOT here, because the compiler answers the shared form with other registers or another MFMA schedule in some
+// instantiation (compare the device assembly with tools/gemm_isa_diff.py before moving any of it): the per-image row-bias add
+// of the ring and halo kernels, the halo kernel's partial-slab store and store loop, the ring kernel's mfma_half.  The lane's
+// position is passed as plain integers for the same reason: handed over as one struct, these helpers cost most kernels a
+// register or two and a few of them a spill.
+
+// split-K: the lane's fp32 quads -> the partial slab of slice `split` ([M][N] floats, reduced by splitk_reduce_*_kernel)
+template <int TM, int TN>
+SDOD_DEVICE void store_partial_slab(const f32x4 (&acc)[TM][TN], const GemmP& p, int split, int m_wave, int n_wave, int e_m, int e_n) {
+    float* slab = p.partial + (size_t)split * p.M * p.N;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int m = m_wave + i * 16 + e_m;
+        if (m >= p.M) continue;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int n = n_wave + j * 16 + e_n;
+            if (n + 3 < p.N) {
+                *reinterpret_cast<f32x4*>(slab + (size_t)m * p.N + n) = acc[i][j];
+            } else {
+                for (int r = 0; r < 4; ++r)
+                    if (n + r < p.N) slab[(size_t)m * p.N + n + r] = acc[i][j][r];
+            }
+        }
+    }
+}
+
+// uint8 weights: acc holds sum_k A (q + offset_n), the integer codes exactly; out = scale_n * acc.  scale = the tile's scale
+// vector in LDS (fp32, one per tile column)
+template <int TM, int TN>
+SDOD_DEVICE void scale_columns(f32x4 (&acc)[TM][TN], const float* scale, int wn_off, int e_n) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + wn_off + j * 16 + e_n);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] *= sc[r];
+    }
+}
+
+template <int TM, int TN>
+SDOD_DEVICE void scale_alpha(f32x4 (&acc)[TM][TN], float alpha) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] *= alpha;
+}
+
+// (acc + bias) + bias2 from the tile's column vectors in LDS: colv = [bias[BN] | bias2[BN] | ...] fp32, zeros where absent
+template <int BN, int TM, int TN>
+SDOD_DEVICE void add_column_biases(f32x4 (&acc)[TM][TN], const float* colv, int wn_off, int e_n) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int nl = wn_off + j * 16 + e_n;
+        const f32x4 b1 = *reinterpret_cast<const f32x4*>(colv + nl), b2 = *reinterpret_cast<const f32x4*>(colv + BN + nl);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = (acc[i][j][r] + b1[r]) + b2[r];
+    }
+}
+
+// the finished accumulators, rounded to fp16, -> the output tile in LDS (sC: [BM][SC] halves)
+template <int SC, int TM, int TN>
+SDOD_DEVICE void stage_ctile(const f32x4 (&acc)[TM][TN], f16* sC, int wm_off, int wn_off, int e_m, int e_n) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int ml = wm_off + i * 16 + e_m;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int nl = wn_off + j * 16 + e_n;
+            f16x4 h;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) h[r] = (f16)acc[i][j][r];
+            *reinterpret_cast<f16x4*>(sC + ml * SC + nl) = h;
+        }
+    }
+}
+
+// the output tile in LDS -> global memory, + residual: 16-byte row pieces dealt over `nthr` threads, `cpr` of them per tile row;
+// the tile's columns start at n0_out of n_out output columns (GEGLU halves the width).  Unaligned shapes go element by element.
+template <int BM, int SC>
+SDOD_DEVICE void store_ctile(const GemmP& p, const f16* sC, int tid, int nthr, int cpr, int m0, int n0_out, int n_out) {
+    const bool vec_ok = (n_out % 8 == 0) && (p.ldo % 8 == 0) && (p.residual == nullptr || p.ldr % 8 == 0);
+    for (int idx = tid; idx < BM * cpr; idx += nthr) {
+        const int row = idx / cpr;
+        const int ch = idx - row * cpr;
+        const int m = m0 + row, n = n0_out + ch * 8;
+        if (m >= p.M || n >= n_out) continue;
+        f16x8 v = *reinterpret_cast<const f16x8*>(sC + row * SC + ch * 8);
+        if (vec_ok) {
+            if (p.residual != nullptr) {
+                const f16x8 rr = ldg8(p.residual + (size_t)m * p.ldr + n);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = (f16)((float)v[e] + (float)rr[e]);
+            }
+            stg8(p.out + (size_t)m * p.ldo + n, v);
+        } else {
+            for (int e = 0; e < 8; ++e) {
+                if (n + e < n_out) {
+                    float f = (float)v[e];
+                    if (p.residual != nullptr) f += (float)p.residual[(size_t)m * p.ldr + n + e];
+                    p.out[(size_t)m * p.ldo + n + e] = (f16)f;
+                }
+            }
+        }
+    }
+}
+
+// ---- pieces of the software-pipelined consumer loops (wave-specialised ring kernel, A-panel kernel, halo kernel): the K halves
+// of a slab alternate between two fragment register sets; each kernel has its own read_half (the addressing is what differs)
+SDOD_DEVICE f16x8 lds16(unsigned addr) { return *reinterpret_cast<const __attribute__((address_space(3))) f16x8*>((uintptr_t)addr); }
+template <int TM, int TN>
+SDOD_DEVICE void mfma_half(f32x4 (&acc)[TM][TN], const f16x8 (&fa)[TM], const f16x8 (&fb)[TN]) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) acc[i][j] = mfma16(fb[j], fa[i], acc[i][j]);
+}
+// Scheduling directive for the region since the last sched_barrier (one read_half + one mfma_half): ADDR VALU instructions (the
+// address arithmetic of the reads) first, then MFMAs and LDS reads alternating.  A wave issues in order and an MFMA holds its
+// issue port for 8 of its 16 cycles, so a read placed between two MFMAs is free.
+template <int TM, int TN, int ADDR>
+SDOD_DEVICE void interleave_reads_with_mfmas() {
+    constexpr int NRD = TM + TN, NMF = TM * TN, PAIRS = NRD < NMF ? NRD : NMF;
+    __builtin_amdgcn_sched_group_barrier(0x002, ADDR, 0);
+    static_for<PAIRS>([](auto) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); // one MFMA
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); // one LDS read
+    });
+    if constexpr (NMF > PAIRS) __builtin_amdgcn_sched_group_barrier(0x008, NMF - PAIRS, 0);
+    if constexpr (NRD > PAIRS) __builtin_amdgcn_sched_group_barrier(0x100, NRD - PAIRS, 0);
+}
 
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256) void gemm_kernel(const GemmP p) {
@@ -299,22 +465,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmP p) {
     const int e_n = (lane >> 4) * 4;
 
     if (p.splits > 1) {
-        float* slab = p.partial + (size_t)split * p.M * p.N;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int m = m0 + wm * WTM + i * 16 + e_m;
-            if (m >= p.M) continue;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0 + wn * WTN + j * 16 + e_n;
-                if (n + 3 < p.N) {
-                    *reinterpret_cast<f32x4*>(slab + (size_t)m * p.N + n) = acc[i][j];
-                } else {
-                    for (int r = 0; r < 4; ++r)
-                        if (n + r < p.N) slab[(size_t)m * p.N + n + r] = acc[i][j][r];
-                }
-            }
-        }
+        store_partial_slab(acc, p, split, m0 + wm * WTM, n0 + wn * WTN, e_m, e_n);
         return;
     }
 
@@ -349,31 +500,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmP p) {
     }
     __syncthreads();
 
-    constexpr int CPR = BN / 8; // 16-byte chunks per tile row
-    const bool vec_ok = (p.N % 8 == 0) && (p.ldo % 8 == 0) && (p.residual == nullptr || p.ldr % 8 == 0);
-    for (int idx = tid; idx < BM * CPR; idx += 256) {
-        const int row = idx / CPR;
-        const int ch = idx - row * CPR;
-        const int m = m0 + row, n = n0 + ch * 8;
-        if (m >= p.M || n >= p.N) continue;
-        f16x8 v = *reinterpret_cast<const f16x8*>(sC + row * SC + ch * 8);
-        if (vec_ok) {
-            if (p.residual != nullptr) {
-                const f16x8 rr = ldg8(p.residual + (size_t)m * p.ldr + n);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = (f16)((float)v[e] + (float)rr[e]);
-            }
-            stg8(p.out + (size_t)m * p.ldo + n, v);
-        } else {
-            for (int e = 0; e < 8; ++e) {
-                if (n + e < p.N) {
-                    float f = (float)v[e];
-                    if (p.residual != nullptr) f += (float)p.residual[(size_t)m * p.ldr + n + e];
-                    p.out[(size_t)m * p.ldo + n + e] = (f16)f;
-                }
-            }
-        }
-    }
+    store_ctile<BM, SC>(p, sC, tid, 256, BN / 8, m0, n0, p.N);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -443,15 +570,6 @@ SDOD_DEVICE void lds_dma16_saddr(const void* base, unsigned off, f16* lds_dst) {
 // The same with the LDS destination given as a byte address (running pointers of the lean loader loop).
 SDOD_DEVICE void lds_dma16_saddr_raw(const void* base, unsigned off, unsigned lds_byte_addr) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds_byte_addr) : "memory", "m0");
-}
-
-// compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
-template <int N, int I = 0, class F>
-SDOD_DEVICE void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
 }
 
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate): n >= 32 waits for everything
@@ -826,7 +944,6 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
     const int CPR = p.geglu ? BN / 16 : BN / 8; // 16-byte chunks per output tile row
         const int n_out = p.geglu ? p.N / 2 : p.N;
         const int n0_out = p.geglu ? n0 / 2 : n0;
-        const bool vec_ok = (n_out % 8 == 0) && (p.ldo % 8 == 0) && (p.residual == nullptr || p.ldr % 8 == 0);
         if constexpr (RES_PF) {
             if (res_ready) { // same pieces, same order as the loop below; the residual is already in registers
 #pragma unroll
@@ -843,29 +960,7 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
                 return;
             }
         }
-        for (int idx = tid; idx < BM * CPR; idx += NT) {
-            const int row = idx / CPR;
-            const int ch = idx - row * CPR;
-            const int m = m0 + row, n = n0_out + ch * 8;
-            if (m >= p.M || n >= n_out) continue;
-            f16x8 v = *reinterpret_cast<const f16x8*>(sC + row * SC + ch * 8);
-            if (vec_ok) {
-                if (p.residual != nullptr) {
-                    const f16x8 rr = ldg8(p.residual + (size_t)m * p.ldr + n);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (f16)((float)v[e] + (float)rr[e]);
-                }
-                stg8(p.out + (size_t)m * p.ldo + n, v);
-            } else {
-                for (int e = 0; e < 8; ++e) {
-                    if (n + e < n_out) {
-                        float f = (float)v[e];
-                        if (p.residual != nullptr) f += (float)p.residual[(size_t)m * p.ldr + n + e];
-                        p.out[(size_t)m * p.ldo + n + e] = (f16)f;
-                    }
-                }
-            }
-        }
+        store_ctile<BM, SC>(p, sC, tid, NT, CPR, m0, n0_out, n_out);
     };
 
     if constexpr (SPEC) {
@@ -995,7 +1090,6 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
 #pragma unroll
         for (int i = 0; i < TM; ++i) a_addr[i] = smem_base + (unsigned)lds_off(wm * WTM + i * 16 + frag_row, frag_chunk) * 2u;
         const unsigned b_addr0 = smem_base + (unsigned)(BM * 64 + lds_off(wn * WTN + frag_row, frag_chunk)) * 2u;
-        auto lds16 = [](unsigned addr) { return *reinterpret_cast<const __attribute__((address_space(3))) f16x8*>((uintptr_t)addr); };
         auto read_half = [&](auto b_c, auto ks_c, int slot) {
             constexpr int b = decltype(b_c)::value, ks = decltype(ks_c)::value;
             const unsigned base = (unsigned)slot * (unsigned)(STAGE * 2);
@@ -1005,22 +1099,13 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
 #pragma unroll
             for (int j = 0; j < TN; ++j) fb[b][j] = lds16(sb + j * 16 * 128);
         };
-        auto mfma_half = [&](auto b_c) {
+        // (this kernel's own copy of mfma_half(): through the shared function the 32-row tiles triple their registers and spill)
+        auto mfma_half_here = [&](auto b_c) {
             constexpr int b = decltype(b_c)::value;
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int i = 0; i < TM; ++i) acc[i][j] = mfma16(fb[b][j], fa[b][i], acc[i][j]);
-        };
-        auto interleave_reads_with_mfmas = [] { // scheduling directive for the region since the last sched_barrier
-            constexpr int NRD = TM + TN, NMF = TM * TN, PAIRS = NRD < NMF ? NRD : NMF;
-            __builtin_amdgcn_sched_group_barrier(0x002, TM + 3, 0); // the address arithmetic of the reads first
-            static_for<PAIRS>([](auto) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); // one MFMA
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); // one LDS read
-            });
-            if constexpr (NMF > PAIRS) __builtin_amdgcn_sched_group_barrier(0x008, NMF - PAIRS, 0);
-            if constexpr (NRD > PAIRS) __builtin_amdgcn_sched_group_barrier(0x100, NRD - PAIRS, 0);
         };
         __builtin_amdgcn_s_waitcnt(0); // (every counter: also retires the epilogue vectors' LDS-DMA, a "pending flat" to the compiler)
         __builtin_amdgcn_s_barrier();  // the first slab group is in LDS (the loaders waited for it)
@@ -1028,8 +1113,8 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
         read_half(I0{}, I0{}, 0);
         for (int it = 0; it < nkt; ++it) {
             read_half(I1{}, I1{}, slot);
-            mfma_half(I0{});
-            interleave_reads_with_mfmas();
+            mfma_half_here(I0{});
+            interleave_reads_with_mfmas<TM, TN, TM + 3>();
             __builtin_amdgcn_sched_barrier(0);
             if (it + 1 < nkt) {
                 if ((it + 1) % KSUB == 0) {
@@ -1040,8 +1125,8 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
                 __builtin_amdgcn_sched_barrier(0);
                 read_half(I0{}, I0{}, slot);
             }
-            mfma_half(I1{});
-            interleave_reads_with_mfmas();
+            mfma_half_here(I1{});
+            interleave_reads_with_mfmas<TM, TN, TM + 3>();
             __builtin_amdgcn_sched_barrier(0);
         }
     } else {
@@ -1137,32 +1222,10 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
     }
     if (WQ) {
         // affine-uint8 weights: acc holds sum_k A (q + offset_n), exactly the integer codes; out = scale_n * acc
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(colv + 3 * BN + wn * WTN + j * 16 + e_n);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[i][j][r] *= sc[r];
-        }
+        scale_columns(acc, colv + 3 * BN, wn * WTN, e_n);
     }
     if (p.splits > 1) {
-        float* slab = p.partial + (size_t)split * p.M * p.N;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int m = m0 + wm * WTM + i * 16 + e_m;
-            if (m >= p.M) continue;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0 + wn * WTN + j * 16 + e_n;
-                if (n + 3 < p.N) {
-                    *reinterpret_cast<f32x4*>(slab + (size_t)m * p.N + n) = acc[i][j];
-                } else {
-                    for (int r = 0; r < 4; ++r)
-                        if (n + r < p.N) slab[(size_t)m * p.N + n + r] = acc[i][j][r];
-                }
-            }
-        }
+        store_partial_slab(acc, p, split, m0 + wm * WTM, n0 + wn * WTN, e_m, e_n);
         return;
     }
 
@@ -1211,22 +1274,9 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
                 }
             }
         } else if (alpha != 1.0f) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[i][j][r] *= alpha;
+            scale_alpha(acc, alpha);
         }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int nl = wn * WTN + j * 16 + e_n;
-            const f32x4 b1 = *reinterpret_cast<const f32x4*>(colv + nl), b2 = *reinterpret_cast<const f32x4*>(colv + BN + nl);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[i][j][r] = (acc[i][j][r] + b1[r]) + b2[r];
-        }
+        add_column_biases<BN>(acc, colv, wn * WTN, e_n);
         if (p.bias != nullptr && p.bias_on_m) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
@@ -1319,18 +1369,7 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
                 }
             }
         }
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int ml = wm * WTM + i * 16 + e_m;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int nl = wn * WTN + j * 16 + e_n;
-                f16x4 h;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) h[r] = (f16)acc[i][j][r];
-                *reinterpret_cast<f16x4*>(sC + ml * SC + nl) = h;
-            }
-        }
+        stage_ctile<SC>(acc, sC, wm * WTM, wn * WTN, e_m, e_n);
     }
     __syncthreads();
     STAMP(3);
@@ -1510,7 +1549,6 @@ __global__ __launch_bounds__(768) void gemm_apanel_kernel(const GemmP p, const f
 #pragma unroll
     for (int i = 0; i < TM; ++i) a_addr[i] = a_base + (unsigned)lds_off(wm * WTM + i * 16 + frag_row, frag_chunk) * 2u;
     const unsigned b_addr0 = w_base + (unsigned)lds_off(wn * WTN + frag_row, frag_chunk) * 2u;
-    auto lds16 = [](unsigned addr) { return *reinterpret_cast<const __attribute__((address_space(3))) f16x8*>((uintptr_t)addr); };
     f32x4 acc[TM][TN];
     auto read_half = [&](auto b_c, auto ks_c, int it, int slot) {
         constexpr int b = decltype(b_c)::value, ks = decltype(ks_c)::value;
@@ -1520,23 +1558,6 @@ __global__ __launch_bounds__(768) void gemm_apanel_kernel(const GemmP p, const f
         for (int i = 0; i < TM; ++i) fa[b][i] = lds16((a_addr[i] + abase) ^ (ks << 6));
 #pragma unroll
         for (int j = 0; j < TN; ++j) fb[b][j] = lds16(sb + j * 16 * 128);
-    };
-    auto mfma_half = [&](auto b_c) {
-        constexpr int b = decltype(b_c)::value;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i][j] = mfma16(fb[b][j], fa[b][i], acc[i][j]);
-    };
-    auto interleave_reads_with_mfmas = [] {
-        constexpr int NRD = TM + TN, NMF = TM * TN, PAIRS = NRD < NMF ? NRD : NMF;
-        __builtin_amdgcn_sched_group_barrier(0x002, TM + 3, 0);
-        static_for<PAIRS>([](auto) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        });
-        if constexpr (NMF > PAIRS) __builtin_amdgcn_sched_group_barrier(0x008, NMF - PAIRS, 0);
-        if constexpr (NRD > PAIRS) __builtin_amdgcn_sched_group_barrier(0x100, NRD - PAIRS, 0);
     };
     const float alpha = p.alpha;
     const int n_out = p.geglu ? p.N / 2 : p.N;
@@ -1649,8 +1670,8 @@ __global__ __launch_bounds__(768) void gemm_apanel_kernel(const GemmP p, const f
             read_half(I0{}, I0{}, 0, slot);
             for (int it = 0; it < KT; ++it) {
                 read_half(I1{}, I1{}, it, slot);
-                mfma_half(I0{});
-                interleave_reads_with_mfmas();
+                mfma_half(acc, fa[0], fb[0]);
+                interleave_reads_with_mfmas<TM, TN, TM + 3>();
                 __builtin_amdgcn_sched_barrier(0);
                 if (it + 1 < KT) {
                     __builtin_amdgcn_s_waitcnt(0xC07F); // lgkmcnt(0): my reads of this slab are done, its slot may be refilled
@@ -1659,8 +1680,8 @@ __global__ __launch_bounds__(768) void gemm_apanel_kernel(const GemmP p, const f
                     __builtin_amdgcn_sched_barrier(0);
                     read_half(I0{}, I0{}, it + 1, slot);
                 }
-                mfma_half(I1{});
-                interleave_reads_with_mfmas();
+                mfma_half(acc, fa[1], fb[1]);
+                interleave_reads_with_mfmas<TM, TN, TM + 3>();
                 __builtin_amdgcn_sched_barrier(0);
             }
             slot = slot + 1 == STAGES ? 0 : slot + 1;
@@ -2112,7 +2133,6 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
         using I1 = std::integral_constant<int, 1>;
         f16x8 fa[2][TM], fb[2][WQ ? 1 : TN];
         u32x2 fq[2][WQ ? TN : 1]; // uint8 weights: the fragment's 8 codes as read, expanded right before their MFMAs
-        auto lds16 = [](unsigned addr) { return *reinterpret_cast<const __attribute__((address_space(3))) f16x8*>((uintptr_t)addr); };
         auto lds8 = [](unsigned addr) { return *reinterpret_cast<const __attribute__((address_space(3))) u32x2*>((uintptr_t)addr); };
         // fragments of (tap t, K half ks) of the slab in ring slot `slot` -> register set b
         auto read_half = [&](auto b_c, auto t_c, auto ks_c, int slot) {
@@ -2129,7 +2149,9 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
                 for (int j = 0; j < TN; ++j) fb[b][j] = lds16(sb + j * 16 * 128);
             }
         };
-        auto mfma_half = [&](auto b_c) {
+        // the MFMAs of register set b; uint8 weights are expanded right in front of theirs (the scheduler is left to place that
+        // VALU work: no interleave directive behind it)
+        auto multiply_half = [&](auto b_c) {
             constexpr int b = decltype(b_c)::value;
             if constexpr (WQ) {
 #pragma unroll
@@ -2138,31 +2160,14 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
 #pragma unroll
                     for (int i = 0; i < TM; ++i) acc[i][j] = mfma16(w, fa[b][i], acc[i][j]);
                 }
-                return;
-            }
-            if (dbg & 64) { // keep the fragment reads alive without the matrix pipe
+            } else if (dbg & 64) { // keep the fragment reads alive without the matrix pipe
 #pragma unroll
                 for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(fb[b][j]));
 #pragma unroll
                 for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(fa[b][i]));
-                return;
+            } else {
+                mfma_half(acc, fa[b], fb[b]);
             }
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int i = 0; i < TM; ++i) acc[i][j] = mfma16(fb[b][j], fa[b][i], acc[i][j]);
-        };
-
-        auto interleave_reads_with_mfmas = [] { // scheduling directive for the region since the last sched_barrier
-            if constexpr (WQ) return; // (the expansion's VALU work is left to the scheduler)
-            constexpr int NRD = TM + TN, NMF = TM * TN, PAIRS = NRD < NMF ? NRD : NMF;
-            __builtin_amdgcn_sched_group_barrier(0x002, TM + 2, 0); // the address arithmetic of the reads first
-            static_for<PAIRS>([](auto) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); // one MFMA
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); // one LDS read
-            });
-            if constexpr (NMF > PAIRS) __builtin_amdgcn_sched_group_barrier(0x008, NMF - PAIRS, 0);
-            if constexpr (NRD > PAIRS) __builtin_amdgcn_sched_group_barrier(0x100, NRD - PAIRS, 0);
         };
 
         wait_vmcnt<0>(); // the epilogue vectors this wave requested have landed
@@ -2185,8 +2190,8 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
                 // in order, an MFMA holds its issue port for 8 of its 16 cycles, so a fragment read placed between two MFMAs is
                 // free while a block of reads in front of the MFMA block leaves the matrix pipe idle for its whole issue time
                 read_half(I1{}, t_c, I1{}, slot);
-                mfma_half(I0{});
-                interleave_reads_with_mfmas();
+                multiply_half(I0{});
+                if constexpr (!WQ) interleave_reads_with_mfmas<TM, TN, TM + 2>();
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_waitcnt(0xC07F); // lgkmcnt(0): my reads of this slab are done, the ring slot may be refilled
                 if (!(t == 8 && last_chunk)) {
@@ -2202,8 +2207,8 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
                     __builtin_amdgcn_sched_barrier(0);
                     read_half(I0{}, TNEXT{}, I0{}, slot);
                 }
-                mfma_half(I1{});
-                interleave_reads_with_mfmas();
+                multiply_half(I1{});
+                if constexpr (!WQ) interleave_reads_with_mfmas<TM, TN, TM + 2>();
                 __builtin_amdgcn_sched_barrier(0);
             });
         }
@@ -2244,15 +2249,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
     STAMP(2);
 
     if constexpr (WQ) { // acc holds sum_k A (q + offset_n), the integer codes exactly; the column's scale first
-        const float* scv = colv + 2 * BN + BN / 2 + 64;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(scv + wn * WTN + j * 16 + e_n);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[i][j][r] *= sc[r];
-        }
+        scale_columns(acc, colv + 2 * BN + BN / 2 + 64, wn * WTN, e_n);
     }
     int n_store = NT; // threads that take part in the store phase
     if (p.splits > 1 && p.fixup) {
@@ -2351,23 +2348,8 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
     }
 
     const float alpha = p.alpha;
-    if (alpha != 1.0f) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[i][j][r] *= alpha;
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int nl = wn * WTN + j * 16 + e_n;
-        const f32x4 b1 = *reinterpret_cast<const f32x4*>(colv + nl), b2 = *reinterpret_cast<const f32x4*>(colv + BN + nl);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = (acc[i][j][r] + b1[r]) + b2[r];
-    }
+    if (alpha != 1.0f) scale_alpha(acc, alpha);
+    add_column_biases<BN>(acc, colv, wn * WTN, e_n);
     if (rb_lds) {
         const f16* rbl = reinterpret_cast<const f16*>(colv + 2 * BN);
 #pragma unroll
@@ -2409,18 +2391,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[i][j][r] = apply_act(acc[i][j][r], p.act);
     }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int ml = wm * WTM + i * 16 + e_m;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int nl = wn * WTN + j * 16 + e_n;
-            f16x4 h;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h[r] = (f16)acc[i][j][r];
-            *reinterpret_cast<f16x4*>(sC + ml * SC + nl) = h;
-        }
-    }
+    stage_ctile<SC>(acc, sC, wm * WTM, wn * WTN, e_m, e_n);
     __syncthreads();
     STAMP(3);
     store_phase(n_store);
@@ -2428,6 +2399,31 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
     wait_vmcnt<0>();
     STAMP(4);
 #endif
+}
+
+// Can a split-K reduce work on whole quads (four consecutive columns of a row: one aligned vector load per operand, one
+// 8-byte store)?  The host picks the reduce kernel by it, the general kernel its fast path.
+__host__ __device__ inline bool reduce_quads_ok(const GemmP& p) {
+    return (p.N % 4 == 0) && (p.ldo % 4 == 0) && !p.bias_on_m && (p.residual == nullptr || p.ldr % 4 == 0) &&
+           (p.row_bias == nullptr || p.ldrb % 4 == 0) && (((uintptr_t)p.out | (uintptr_t)p.residual | (uintptr_t)p.row_bias) & 7) == 0 &&
+           (((uintptr_t)p.bias | (uintptr_t)p.bias2) & 15) == 0;
+}
+// The fused epilogue on one reduced quad v (the slices already summed): b1 / b2 = its bias / bias2 columns, rb = its row-bias
+// columns, rs = its residual (each read only where the operand exists)
+SDOD_DEVICE f16x4 reduce_quad_epilogue(const GemmP& p, f32x4 v, f32x4 b1, f32x4 b2, f16x4 rb, f16x4 rs) {
+    f16x4 h;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float f = v[r] * p.alpha;
+        if (p.bias) f += b1[r];
+        if (p.bias2) f += b2[r];
+        if (p.row_bias) f += (float)rb[r];
+        f = apply_act(f, p.act);
+        f = (float)(f16)f; // same rounding point as the un-split path
+        if (p.residual) f += (float)rs[r];
+        h[r] = (f16)f;
+    }
+    return h;
 }
 
 // The reduce of every split-K plan in the graphs (whole quads, aligned vectors, bias per column): a workgroup is 64 quads x 4 rows
@@ -2459,19 +2455,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(const GemmP p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += t[r];
     }
-    f16x4 h;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float f = v[r] * p.alpha;
-        if (p.bias) f += b1[r];
-        if (p.bias2) f += b2[r];
-        if (p.row_bias) f += (float)rb[r];
-        f = apply_act(f, p.act);
-        f = (float)(f16)f; // same rounding point as the un-split path
-        if (p.residual) f += (float)rs[r];
-        h[r] = (f16)f;
-    }
-    *reinterpret_cast<f16x4*>(p.out + (size_t)m * p.ldo + n) = h;
+    *reinterpret_cast<f16x4*>(p.out + (size_t)m * p.ldo + n) = reduce_quad_epilogue(p, v, b1, b2, rb, rs);
 }
 
 // Reduce split-K slabs and apply the fused epilogue.  One thread per 4 consecutive columns.
@@ -2480,9 +2464,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmP p) {
     const size_t total = (size_t)p.M * n4;
     // fast path (every use in the graphs): whole quads, 16-byte aligned vectors -> one load per operand and one 8-byte store
     // per thread, all issued before the first use (the per-element scalar form was a chain of dependent L2 round trips)
-    const bool vec = (p.N % 4 == 0) && (p.ldo % 4 == 0) && !p.bias_on_m && (p.residual == nullptr || p.ldr % 4 == 0) &&
-                     (p.row_bias == nullptr || p.ldrb % 4 == 0) && (((uintptr_t)p.out | (uintptr_t)p.residual | (uintptr_t)p.row_bias) & 7) == 0 &&
-                     (((uintptr_t)p.bias | (uintptr_t)p.bias2) & 15) == 0;
+    const bool vec = reduce_quads_ok(p);
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int m = (int)(idx / n4);
         const int n = (int)(idx - (size_t)m * n4) * 4;
@@ -2498,19 +2480,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmP p) {
                 const f32x4 t = *reinterpret_cast<const f32x4*>(p.partial + ((size_t)s * p.M + m) * p.N + n);
                 v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; v[3] += t[3];
             }
-            f16x4 h;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float f = v[r] * p.alpha;
-                if (p.bias) f += b1[r];
-                if (p.bias2) f += b2[r];
-                if (p.row_bias) f += (float)rb[r];
-                f = apply_act(f, p.act);
-                f = (float)(f16)f; // same rounding point as the un-split path
-                if (p.residual) f += (float)rs[r];
-                h[r] = (f16)f;
-            }
-            *reinterpret_cast<f16x4*>(p.out + (size_t)m * p.ldo + n) = h;
+            *reinterpret_cast<f16x4*>(p.out + (size_t)m * p.ldo + n) = reduce_quad_epilogue(p, v, b1, b2, rb, rs);
             continue;
         }
         float v[4] = {0.f, 0.f, 0.f, 0.f};
@@ -2540,53 +2510,115 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmP p) {
     }
 }
 
-struct TileCfg {
-    int bm, bn;
+// ---- THE tile table: one row per tile id, and nothing else in this file (or in the tuner) lists tiles.  A tile id is a persisted
+// format (tune/gfx950.tune stores tile + 1000 * split_k), so rows never move: row i is tile i.  The launch (launch_tile), the
+// plan, sdod_gemm_tile_info / _shape and the tuner's candidate list are all read off these rows; a new tile is one new row.
+enum Family { NONE = -1, REG = 0, RING = 1, HALO = 2, PANEL = 3 }; // gemm_kernel, gemm_glds_kernel, conv_halo_kernel, gemm_apanel_kernel
+struct Tile {
+    Family family;
+    int bm, bn, wm, wn;
+    int stages; // ring depth (0: the register-staged kernel has none)
+    int spec;   // ring kernel: 1 = wave-specialised (consumer + loader waves)
+    int ksub;   // ring kernel: slabs per barrier
+    bool u8;    // an affine-uint8-weight instantiation exists
+    bool tuned; // the engine's tuner tries the tile
 };
-// id 1..5: register-staged kernel; 6..8: LDS-DMA ring kernel (v2), 4 waves; 9..16: v2 with 8 waves (2 per SIMD);
-// 17..20: deep rings for the weight-streaming layers (small M, weights from HBM: bytes in flight per CU is what counts)
-// 21..22: 160-column tiles: N = 320 / 640 / 1280 divide without the 17 % padding a 128-wide tile pays at N = 320, and
-//         M = 8192 x N = 320 becomes exactly 256 workgroups (one per CU)
-const TileCfg kTiles[] = {{0, 0},     {128, 128}, {128, 64}, {64, 64},   {256, 16}, {64, 128}, {128, 128},
-                          {128, 64},  {64, 64},   {128, 128}, {256, 128}, {128, 64}, {256, 64},
-                          {128, 128}, {128, 128}, {256, 128}, {256, 256}, {64, 64},  {128, 64}, {64, 128}, {128, 256},
-                          {64, 160},  {32, 160},
-                          // 23..31: wave-specialised LDS-DMA kernel (4 consumer + 4 loader waves)
-                          {128, 128}, {128, 128}, {128, 256}, {256, 128}, {64, 64}, {64, 64}, {128, 64}, {64, 128}, {64, 160},
-                          // 32..36: wave-specialised, two slabs per barrier
-                          {64, 64}, {128, 64}, {64, 128}, {64, 160}, {128, 128},
-                          // 37..45: halo-patch 3x3 convolution (conv_halo_kernel)
-                          {64, 160}, {128, 80}, {128, 160}, {64, 80}, {256, 32}, {128, 32}, {256, 64}, {128, 64}, {64, 64},
-                          // 46..48: wave-specialised 32-row tiles for the small-M Linear layers (M = 512 at the 16x16 level: twice the
-                          // workgroups of a 64-row tile at three quarters of its bytes per slab)
-                          {32, 64}, {32, 128}, {32, 160},
-                          // 49..52: halo-patch tiles of 96 / 192 rows, for images whose rows are multiples of 3 (config 5: 96 / 48 / 24 / 12)
-                          {96, 160}, {96, 64}, {192, 80}, {192, 64},
-                          // 53..55: A-panel kernel (gemm_apanel_kernel): row panel x whole K resident in LDS, n-tiles streamed past it --
-                          // K = 320 / 640 / 1280 at 128 / 64 / 32 rows (80 KB panels)
-                          {128, 128}, {64, 128}, {32, 128},
-                          // 56..58: 160-wide wave-specialised ring tiles for the score GEMM of the folded cross-attention (the row softmax
-                          // of its epilogue needs a wave that owns a head's 80 columns): a deep ring for the row-starved levels (M = 512 /
-                          // 128: 64 / 16 workgroups, one per CU -- the bytes in flight set the pace), a 128-row tile (M = 8192 x N = 640
-                          // is exactly 256 workgroups) and a two-stage 64-row one that leaves room for two workgroups per CU
-                          {32, 160}, {128, 160}, {64, 160},
-                          // 59..60: ONE head (80 columns) per workgroup, 2 consumer + 2 loader waves: twice the workgroups of the 160-wide
-                          // tiles for the row-starved score GEMMs (M = 512: 128 instead of 64) at 58 % of their bytes each
-                          {32, 80}, {64, 80},
-                          // 61: 128 x 160 with the four consumer waves stacked on the rows (32 x 160 each: an EVEN number of 16-column blocks,
-                          // so the GEGLU epilogue can pair value / gate): M = 512 x N = 10240 is exactly 256 workgroups
-                          {128, 160}};
-constexpr int kNumTiles = 61;
-constexpr bool is_ring_tile(int t) { return (t >= 6 && t <= 36) || (t >= 46 && t <= 48) || (t >= 56 && t <= 61); } // gemm_glds_kernel
-constexpr bool is_wave80_tile(int t) { return t == 21 || t == 22 || t == 31 || t == 35 || t == 48 || (t >= 56 && t <= 60); } // 80 columns per wave
-constexpr int kFirstPanelTile = 53, kLastPanelTile = 55;
-constexpr bool is_panel_tile(int t) { return t >= kFirstPanelTile && t <= kLastPanelTile; }
 constexpr int kPanelStages = 4;
-constexpr int kFirstHaloTile = 37, kLastHaloTile = 45, kFirstHaloTile3 = 49, kLastHaloTile3 = 52;
-constexpr bool is_halo_tile(int t) { return (t >= kFirstHaloTile && t <= kLastHaloTile) || (t >= kFirstHaloTile3 && t <= kLastHaloTile3); }
-// {STAGES} of the halo tiles (WM x WN is 2x2 for the 160- and 64-wide square-ish ones, 4x1 for the tall ones: launch switch)
-const int kHaloStages[] = {4, 4, 3, 4, 6, 6, 4, 4, 4, /* 49.. */ 3, 4, 4, 4};
-constexpr int halo_index(int t) { return t <= kLastHaloTile ? t - kFirstHaloTile : t - kFirstHaloTile3 + (kLastHaloTile - kFirstHaloTile + 1); }
+constexpr Tile kTile[] = {
+    {NONE, 0, 0, 0, 0, 0, 0, 0, false, false},
+    // 1..5: register-staged kernel (4: the skinny default for N <= 16, picked by the plan, never by the tuner)
+    {REG, 128, 128, 2, 2, 0, 0, 1, false, true},
+    {REG, 128, 64, 2, 2, 0, 0, 1, false, true},
+    {REG, 64, 64, 2, 2, 0, 0, 1, false, true},
+    {REG, 256, 16, 4, 1, 0, 0, 1, false, false},
+    {REG, 64, 128, 2, 2, 0, 0, 1, false, true},
+    // 6..8: LDS-DMA ring kernel, 4 waves; 9..16: 8 waves (2 per SIMD)
+    {RING, 128, 128, 2, 2, 3, 0, 1, false, true},
+    {RING, 128, 64, 2, 2, 4, 0, 1, false, true},
+    {RING, 64, 64, 2, 2, 4, 0, 1, true, true},
+    {RING, 128, 128, 2, 4, 3, 0, 1, false, true},
+    {RING, 256, 128, 4, 2, 2, 0, 1, false, true},
+    {RING, 128, 64, 4, 2, 4, 0, 1, false, true},
+    {RING, 256, 64, 4, 2, 3, 0, 1, false, true},
+    {RING, 128, 128, 2, 4, 4, 0, 1, true, true},
+    {RING, 128, 128, 2, 4, 2, 0, 1, false, true},
+    {RING, 256, 128, 4, 2, 3, 0, 1, false, false},
+    {RING, 256, 256, 2, 4, 2, 0, 1, false, false},
+    // 17..20: deep rings for the weight-streaming layers (small M, weights from HBM: bytes in flight per CU is what counts)
+    {RING, 64, 64, 2, 2, 8, 0, 1, false, true},
+    {RING, 128, 64, 2, 2, 6, 0, 1, false, true},
+    {RING, 64, 128, 2, 2, 6, 0, 1, false, true},
+    {RING, 128, 256, 2, 4, 3, 0, 1, false, true},
+    // 21..22: 160-column tiles: N = 320 / 640 / 1280 divide without the 17 % padding a 128-wide tile pays at N = 320, and
+    //         M = 8192 x N = 320 becomes exactly 256 workgroups (one per CU)
+    {RING, 64, 160, 2, 2, 4, 0, 1, false, true},
+    {RING, 32, 160, 2, 2, 6, 0, 1, false, true},
+    // 23..31: wave-specialised ring kernel (4 consumer + 4 loader waves); 25, 26 spill in their epilogue only: the tuner decides
+    {RING, 128, 128, 2, 2, 4, 1, 1, true, true},
+    {RING, 128, 128, 2, 2, 3, 1, 1, true, true},
+    {RING, 128, 256, 2, 2, 3, 1, 1, false, true},
+    {RING, 256, 128, 2, 2, 3, 1, 1, false, true},
+    {RING, 64, 64, 2, 2, 8, 1, 1, true, true},
+    {RING, 64, 64, 2, 2, 4, 1, 1, true, true},
+    {RING, 128, 64, 2, 2, 6, 1, 1, true, true},
+    {RING, 64, 128, 2, 2, 6, 1, 1, true, true},
+    {RING, 64, 160, 2, 2, 4, 1, 1, true, true},
+    // 32..36: wave-specialised, two slabs per barrier
+    {RING, 64, 64, 2, 2, 4, 1, 2, false, true},
+    {RING, 128, 64, 2, 2, 3, 1, 2, false, true},
+    {RING, 64, 128, 2, 2, 3, 1, 2, false, true},
+    {RING, 64, 160, 2, 2, 2, 1, 2, false, true},
+    {RING, 128, 128, 2, 2, 2, 1, 2, false, true},
+    // 37..45: halo-patch 3x3 convolution (conv_halo_kernel; every halo tile has its uint8 form): rejected by every other descriptor.
+    // WM x WN is 2x2 for the 160- and 64-wide square-ish ones, 4x1 for the tall ones
+    {HALO, 64, 160, 2, 2, 4, 0, 1, true, true},
+    {HALO, 128, 80, 4, 1, 4, 0, 1, true, true},
+    {HALO, 128, 160, 2, 2, 3, 0, 1, true, true},
+    {HALO, 64, 80, 4, 1, 4, 0, 1, true, true},
+    {HALO, 256, 32, 4, 1, 6, 0, 1, true, true},
+    {HALO, 128, 32, 4, 1, 6, 0, 1, true, true},
+    {HALO, 256, 64, 4, 1, 4, 0, 1, true, true},
+    {HALO, 128, 64, 2, 2, 4, 0, 1, true, true},
+    {HALO, 64, 64, 2, 2, 4, 0, 1, true, true},
+    // 46..48: wave-specialised 32-row tiles for the small-M Linear layers (M = 512 at the 16x16 level: twice the
+    // workgroups of a 64-row tile at three quarters of its bytes per slab)
+    {RING, 32, 64, 2, 2, 6, 1, 1, false, true},
+    {RING, 32, 128, 1, 4, 6, 1, 1, false, true},
+    {RING, 32, 160, 2, 2, 4, 1, 1, false, true},
+    // 49..52: halo-patch tiles of 96 / 192 rows, for images whose rows are multiples of 3 (config 5: 96 / 48 / 24 / 12)
+    {HALO, 96, 160, 2, 2, 3, 0, 1, true, true},
+    {HALO, 96, 64, 2, 2, 4, 0, 1, true, true},
+    {HALO, 192, 80, 4, 1, 4, 0, 1, true, true},
+    {HALO, 192, 64, 4, 1, 4, 0, 1, true, true},
+    // 53..55: A-panel kernel (gemm_apanel_kernel): row panel x whole K resident in LDS, n-tiles streamed past it --
+    // K = 320 / 640 / 1280 at 128 / 64 / 32 rows (80 KB panels); rejected by every other descriptor
+    {PANEL, 128, 128, 2, 2, kPanelStages, 0, 1, false, true},
+    {PANEL, 64, 128, 2, 2, kPanelStages, 0, 1, false, true},
+    {PANEL, 32, 128, 2, 2, kPanelStages, 0, 1, false, true},
+    // 56..58: 160-wide wave-specialised ring tiles for the score GEMM of the folded cross-attention (the row softmax
+    // of its epilogue needs a wave that owns a head's 80 columns): a deep ring for the row-starved levels (M = 512 /
+    // 128: 64 / 16 workgroups, one per CU -- the bytes in flight set the pace), a 128-row tile (M = 8192 x N = 640
+    // is exactly 256 workgroups) and a two-stage 64-row one that leaves room for two workgroups per CU
+    {RING, 32, 160, 2, 2, 6, 1, 1, false, true},
+    {RING, 128, 160, 2, 2, 3, 1, 1, false, true},
+    {RING, 64, 160, 2, 2, 2, 1, 1, false, true},
+    // 59..60: ONE head (80 columns) per workgroup, 2 consumer + 2 loader waves: twice the workgroups of the 160-wide
+    // tiles for the row-starved score GEMMs (M = 512: 128 instead of 64) at 58 % of their bytes each
+    {RING, 32, 80, 2, 1, 5, 1, 1, false, true},
+    {RING, 64, 80, 2, 1, 5, 1, 1, false, true},
+    // 61: 128 x 160 with the four consumer waves stacked on the rows (32 x 160 each: an EVEN number of 16-column blocks,
+    // so the GEGLU epilogue can pair value / gate): M = 512 x N = 10240 is exactly 256 workgroups
+    {RING, 128, 160, 4, 1, 3, 1, 1, false, true},
+};
+constexpr int kNumTiles = (int)(sizeof(kTile) / sizeof(kTile[0])) - 1;
+constexpr int kU8FallbackTile = 23; // a uint8-weight GEMM planned on a tile without a uint8 form runs on this one
+constexpr Family tile_family(int t) { return t >= 1 && t <= kNumTiles ? kTile[t].family : NONE; }
+constexpr bool is_ring_tile(int t) { return tile_family(t) == RING; }
+constexpr bool is_halo_tile(int t) { return tile_family(t) == HALO; }
+constexpr bool is_panel_tile(int t) { return tile_family(t) == PANEL; }
+constexpr bool is_wave80_tile(int t) { return is_ring_tile(t) && kTile[t].bn / kTile[t].wn == 80; } // a wave owns 80 columns (one head)
+constexpr bool has_u8_form(int t) { return t >= 1 && t <= kNumTiles && kTile[t].u8; }
+static_assert(kTile[kU8FallbackTile].family == RING && kTile[kU8FallbackTile].u8, "the uint8 fallback tile needs a uint8 form");
 
 const f16* zero_line() { // one per device (the pointer is only valid on the device that allocated it)
     static std::atomic<f16*> z[64];
@@ -2603,40 +2635,23 @@ const f16* zero_line() { // one per device (the pointer is only valid on the dev
     return cur;
 }
 
-template <int BM, int BN, int WM, int WN, int STAGES, bool SPEC = false, bool WQ = false, int KSUB = 1>
-hipError_t launch_glds(const GemmP& p, dim3 grid, hipStream_t st) {
-    constexpr size_t ring = (size_t)STAGES * KSUB * (BM + BN) * 64 * sizeof(f16);
-    static_assert(ring + 4 * BN * sizeof(float) <= 160 * 1024, "ring exceeds the 160 KiB of LDS");
-    constexpr size_t ctile = (size_t)BM * (BN + 8) * sizeof(f16) + (size_t)BM * 2 * sizeof(float); // + LayerNorm row stats
-    constexpr size_t smem = (ring > ctile ? ring : ctile) + (size_t)4 * BN * sizeof(float); // + per-column epilogue vectors
+// The one launch path of the four GEMM kernels: the first use on a device raises the kernel's dynamic-LDS limit to `lds_attr`,
+// every kernel but the register-staged one is handed the device's zero line.
+template <auto KERNEL>
+hipError_t launch_kernel(const GemmP& p, dim3 grid, int block, size_t smem, int lds_attr, hipStream_t st) {
     static std::atomic<unsigned long long> attr_devs{0};
     if (sdod::first_use_on_device(attr_devs)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<BM, BN, WM, WN, STAGES, SPEC, WQ, KSUB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr);
         if (e != hipSuccess) return e;
     }
-    const f16* z = zero_line();
-    if (!z) return hipErrorOutOfMemory;
-    SDOD_LAUNCH((gemm_glds_kernel<BM, BN, WM, WN, STAGES, SPEC, WQ, KSUB>), grid, dim3(64 * WM * WN * (SPEC ? 2 : 1)), smem, st, p, z);
-    return hipGetLastError();
-}
-
-template <int BM, int BN, int WM, int WN, int STAGES, bool WQ = false>
-hipError_t launch_halo_q(const GemmP& p, dim3 grid, size_t smem, hipStream_t st) {
-    static std::atomic<unsigned long long> attr_devs{0};
-    if (sdod::first_use_on_device(attr_devs)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<BM, BN, WM, WN, STAGES, WQ>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
+    if constexpr (std::is_same_v<decltype(KERNEL), void (*)(GemmP)>) {
+        SDOD_LAUNCH(KERNEL, grid, dim3(block), smem, st, p);
+    } else {
+        const f16* z = zero_line();
+        if (!z) return hipErrorOutOfMemory;
+        SDOD_LAUNCH(KERNEL, grid, dim3(block), smem, st, p, z);
     }
-    const f16* z = zero_line();
-    if (!z) return hipErrorOutOfMemory;
-    SDOD_LAUNCH((conv_halo_kernel<BM, BN, WM, WN, STAGES, WQ>), grid, dim3(512), smem, st, p, z);
     return hipGetLastError();
-}
-template <int BM, int BN, int WM, int WN, int STAGES>
-hipError_t launch_halo(const GemmP& p, dim3 grid, size_t smem, hipStream_t st) {
-    return p.wq ? launch_halo_q<BM, BN, WM, WN, STAGES, true>(p, grid, smem, st) : launch_halo_q<BM, BN, WM, WN, STAGES, false>(p, grid, smem, st);
 }
 
 size_t panel_smem(int bm, int bn, int K) {
@@ -2650,7 +2665,7 @@ bool panel_ok(const sdod_gemm_desc* d, int tile) {
     if (d->K % BK || d->K / BK < 3 || d->N % 8 || d->ldo % 8 || ((uintptr_t)d->out & 15) || (d->geglu && d->N % 32)) return false;
     if (d->residual && (d->geglu || d->ldr % 4 || ((uintptr_t)d->residual & 7))) return false;
     if ((unsigned long long)d->M * d->lda * 2 >= (1ull << 32) || (unsigned long long)d->N * d->ldw * 2 >= (1ull << 32)) return false;
-    return panel_smem(kTiles[tile].bm, kTiles[tile].bn, d->K) <= 160 * 1024;
+    return panel_smem(kTile[tile].bm, kTile[tile].bn, d->K) <= 160 * 1024;
 }
 
 // n-tiles per workgroup (and groups per panel) of the A-panel kernel: whole waves of 256 workgroups (one per CU) where the
@@ -2673,31 +2688,39 @@ void panel_grid(int panels, int tiles_n, int* tpg_out, int* groups_out) {
     *groups_out = (tiles_n + best_tpg - 1) / best_tpg;
 }
 
-template <int BM, int BN, int WM, int WN>
-hipError_t launch_panel(const GemmP& p, dim3 grid, size_t smem, hipStream_t st) {
-    static std::atomic<unsigned long long> attr_devs{0};
-    if (sdod::first_use_on_device(attr_devs)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_apanel_kernel<BM, BN, WM, WN, kPanelStages>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
+// Launch of tile T, as its table row describes it.  `smem` is the LDS size of the halo and A-panel families (it depends on the
+// descriptor: halo_geometry, panel_smem); the other two derive theirs from the tile shape alone.
+template <int T>
+hipError_t launch_tile(const GemmP& p, dim3 grid, size_t smem, hipStream_t st) {
+    constexpr Tile c = kTile[T];
+    if constexpr (c.family == REG) {
+        constexpr size_t lds = (size_t)2 * (c.bm + c.bn) * 64 * sizeof(f16);
+        return launch_kernel<&gemm_kernel<c.bm, c.bn, c.wm, c.wn>>(p, grid, 256, lds, (int)lds, st);
+    } else if constexpr (c.family == RING) {
+        constexpr size_t ring = (size_t)c.stages * c.ksub * (c.bm + c.bn) * 64 * sizeof(f16);
+        static_assert(ring + 4 * c.bn * sizeof(float) <= 160 * 1024, "ring exceeds the 160 KiB of LDS");
+        constexpr size_t ctile = (size_t)c.bm * (c.bn + 8) * sizeof(f16) + (size_t)c.bm * 2 * sizeof(float); // + LayerNorm row stats
+        constexpr size_t lds = (ring > ctile ? ring : ctile) + (size_t)4 * c.bn * sizeof(float); // + per-column epilogue vectors
+        constexpr int block = 64 * c.wm * c.wn * (c.spec ? 2 : 1);
+        if constexpr (c.u8) {
+            if (p.wq) return launch_kernel<&gemm_glds_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, c.spec != 0, true, c.ksub>>(p, grid, block, lds, (int)lds, st);
+        }
+        if (p.wq) return hipErrorInvalidValue; // (make_plan never leaves a uint8 GEMM on such a tile)
+        return launch_kernel<&gemm_glds_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, c.spec != 0, false, c.ksub>>(p, grid, block, lds, (int)lds, st);
+    } else if constexpr (c.family == HALO) {
+        static_assert(c.u8, "every halo tile carries its uint8 form");
+        return p.wq ? launch_kernel<&conv_halo_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, true>>(p, grid, 512, smem, 160 * 1024, st)
+                    : launch_kernel<&conv_halo_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, false>>(p, grid, 512, smem, 160 * 1024, st);
+    } else {
+        static_assert(c.family == PANEL && c.stages == kPanelStages, "panel_smem() counts kPanelStages ring slots");
+        return launch_kernel<&gemm_apanel_kernel<c.bm, c.bn, c.wm, c.wn, c.stages>>(p, grid, 768, smem, 160 * 1024, st);
     }
-    const f16* z = zero_line();
-    if (!z) return hipErrorOutOfMemory;
-    SDOD_LAUNCH((gemm_apanel_kernel<BM, BN, WM, WN, kPanelStages>), grid, dim3(768), smem, st, p, z);
-    return hipGetLastError();
 }
-
-template <int BM, int BN, int WM, int WN>
-hipError_t launch_cfg(const GemmP& p, dim3 grid, hipStream_t st) {
-    constexpr size_t smem = (size_t)2 * (BM + BN) * 64 * sizeof(f16);
-    static std::atomic<unsigned long long> attr_devs{0};
-    if (sdod::first_use_on_device(attr_devs)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<BM, BN, WM, WN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-    }
-    SDOD_LAUNCH((gemm_kernel<BM, BN, WM, WN>), grid, dim3(256), smem, st, p);
-    return hipGetLastError();
+template <int... I>
+hipError_t launch_tile_id(int tile, std::integer_sequence<int, I...>, const GemmP& p, dim3 grid, size_t smem, hipStream_t st) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((tile == I + 1 && ((e = launch_tile<I + 1>(p, grid, smem, st)), true)) || ...);
+    return e;
 }
 
 bool lean_disabled() { // SDOD_GEMM_LEAN_OFF=1: developer switch (A/B timing of the short issue path)
@@ -2720,7 +2743,7 @@ bool halo_geometry(const sdod_gemm_desc* d, int tile, GemmP* p, size_t* smem_byt
     if (d->wq && d->k_tail) return false;
     if (d->c0 <= 0 || d->c0 % 64 || d->c1 % 64 || d->h_in <= 0 || d->w_in <= 0 || d->n_img <= 0) return false;
     if (d->upsample && d->k_tail) return false;
-    const int BMt = kTiles[tile].bm, BNt = kTiles[tile].bn, stages = kHaloStages[halo_index(tile)];
+    const int BMt = kTile[tile].bm, BNt = kTile[tile].bn, stages = kTile[tile].stages;
     const int ups = d->upsample ? 1 : 0;
     const int H = d->h_in << ups, W = d->w_in << ups; // OUTPUT size: the tile lives there, the patch in the (smaller) source
     int tw, th, parts;
@@ -2811,19 +2834,18 @@ int xcd_panels(const sdod_gemm_desc* d, int tiles_m, int tiles_n) {
 Plan make_plan(const sdod_gemm_desc* d) {
     Plan pl;
     const int KT = d->K / BK;
-    auto ntiles = [&](int t) { return ((d->M + kTiles[t].bm - 1) / kTiles[t].bm) * ((d->N + kTiles[t].bn - 1) / kTiles[t].bn); };
+    auto ntiles = [&](int t) { return ((d->M + kTile[t].bm - 1) / kTile[t].bm) * ((d->N + kTile[t].bn - 1) / kTile[t].bn); };
     int tile = d->tile;
     const bool fused = d->geglu || d->k_tail || d->ln || d->wq;
-    if (fused && (tile < 6 || tile > kNumTiles)) tile = 14; // fusions live in the LDS-DMA kernel family only
+    if (fused && (tile_family(tile) == NONE || tile_family(tile) == REG)) tile = 14; // fusions live in the LDS-DMA kernel families only
     if (d->geglu && is_wave80_tile(tile)) tile = 14;
-    if (d->wq && !(tile == 8 || tile == 13 || tile == 23 || tile == 24 || (tile >= 27 && tile <= 31) || is_halo_tile(tile)))
-        tile = 23; // uint8-weight variants
+    if (d->wq && !has_u8_form(tile)) tile = kU8FallbackTile;
     if (d->wq && d->geglu && tile == 31) tile = 23;  // value/gate pairing needs an even number of 16-column blocks per wave
     // the row softmax of the epilogue lives in one wave: tiles whose waves own 80 columns (the 160-wide ones)
     if (d->softmax_cols && !is_wave80_tile(tile)) tile = 31;
     // per-image weights: an LDS-DMA ring tile whose rows divide the image (a tile must not straddle two weight matrices)
     if (d->w_img_stride && d->rows_per_img > 0 &&
-        (!is_ring_tile(tile) || d->rows_per_img % kTiles[tile].bm != 0))
+        (!is_ring_tile(tile) || d->rows_per_img % kTile[tile].bm != 0))
         tile = d->softmax_cols ? (d->rows_per_img % 64 == 0 ? 31 : 48) : (d->rows_per_img % 64 == 0 ? 27 : 46);
     if (tile <= 0 || tile > kNumTiles) {
         if (d->N <= 16) {
@@ -2893,7 +2915,7 @@ namespace {
 constexpr size_t kFixupCounters = (size_t)64 << 10;
 bool fixup_applies(const sdod_gemm_desc* d, const Plan& pl) {
     if (!d->fix_counters || d->phase != 0 || pl.splits <= 1 || !is_halo_tile(pl.tile) || d->N % 4 != 0) return false;
-    const size_t tiles = (size_t)((d->M + kTiles[pl.tile].bm - 1) / kTiles[pl.tile].bm) * ((d->N + kTiles[pl.tile].bn - 1) / kTiles[pl.tile].bn);
+    const size_t tiles = (size_t)((d->M + kTile[pl.tile].bm - 1) / kTile[pl.tile].bm) * ((d->N + kTile[pl.tile].bn - 1) / kTile[pl.tile].bn);
     return tiles <= kFixupCounters && halo_geometry(d, pl.tile, nullptr, nullptr);
 }
 } // namespace
@@ -2948,39 +2970,34 @@ extern "C" __attribute__((visibility("default"))) int sdod_gemm_stamps(unsigned 
 
 extern "C" int sdod_gemm_num_tiles(void) { return kNumTiles; }
 
-// template arguments of tile `tile` as the launch switch in sdod_gemm_f16 instantiates it: {BM, BN, WM, WN, STAGES (0 = the
-// register-staged gemm_kernel), SPEC, KSUB}; tools and bench.py build the kernel symbol a profiler prints from these
+// template arguments of tile `tile` as launch_tile instantiates it: {BM, BN, WM, WN, STAGES (0 = the register-staged
+// gemm_kernel), SPEC (ring kernel: 0 / 1; 2 = conv_halo_kernel, 3 = gemm_apanel_kernel, both <BM, BN, WM, WN, STAGES>), KSUB};
+// tools and bench.py build the kernel symbol a profiler prints from these
 extern "C" int sdod_gemm_tile_info(int tile, int out[7]) {
-    static const int kInfo[][7] = {
-        {0, 0, 0, 0, 0, 0, 0},
-        {128, 128, 2, 2, 0, 0, 1}, {128, 64, 2, 2, 0, 0, 1}, {64, 64, 2, 2, 0, 0, 1}, {256, 16, 4, 1, 0, 0, 1}, {64, 128, 2, 2, 0, 0, 1},
-        {128, 128, 2, 2, 3, 0, 1}, {128, 64, 2, 2, 4, 0, 1}, {64, 64, 2, 2, 4, 0, 1}, {128, 128, 2, 4, 3, 0, 1}, {256, 128, 4, 2, 2, 0, 1},
-        {128, 64, 4, 2, 4, 0, 1}, {256, 64, 4, 2, 3, 0, 1}, {128, 128, 2, 4, 4, 0, 1}, {128, 128, 2, 4, 2, 0, 1}, {256, 128, 4, 2, 3, 0, 1},
-        {256, 256, 2, 4, 2, 0, 1}, {64, 64, 2, 2, 8, 0, 1}, {128, 64, 2, 2, 6, 0, 1}, {64, 128, 2, 2, 6, 0, 1}, {128, 256, 2, 4, 3, 0, 1},
-        {64, 160, 2, 2, 4, 0, 1}, {32, 160, 2, 2, 6, 0, 1},
-        {128, 128, 2, 2, 4, 1, 1}, {128, 128, 2, 2, 3, 1, 1}, {128, 256, 2, 2, 3, 1, 1}, {256, 128, 2, 2, 3, 1, 1}, {64, 64, 2, 2, 8, 1, 1},
-        {64, 64, 2, 2, 4, 1, 1}, {128, 64, 2, 2, 6, 1, 1}, {64, 128, 2, 2, 6, 1, 1}, {64, 160, 2, 2, 4, 1, 1},
-        {64, 64, 2, 2, 4, 1, 2}, {128, 64, 2, 2, 3, 1, 2}, {64, 128, 2, 2, 3, 1, 2}, {64, 160, 2, 2, 2, 1, 2}, {128, 128, 2, 2, 2, 1, 2},
-        // SPEC column 2 = conv_halo_kernel<BM, BN, WM, WN, STAGES>
-        {64, 160, 2, 2, 4, 2, 1}, {128, 80, 4, 1, 4, 2, 1}, {128, 160, 2, 2, 3, 2, 1}, {64, 80, 4, 1, 4, 2, 1}, {256, 32, 4, 1, 6, 2, 1},
-        {128, 32, 4, 1, 6, 2, 1}, {256, 64, 4, 1, 4, 2, 1}, {128, 64, 2, 2, 4, 2, 1}, {64, 64, 2, 2, 4, 2, 1},
-        {32, 64, 2, 2, 6, 1, 1}, {32, 128, 1, 4, 6, 1, 1}, {32, 160, 2, 2, 4, 1, 1},
-        {96, 160, 2, 2, 3, 2, 1}, {96, 64, 2, 2, 4, 2, 1}, {192, 80, 4, 1, 4, 2, 1}, {192, 64, 4, 1, 4, 2, 1},
-        // SPEC column 3 = gemm_apanel_kernel<BM, BN, WM, WN, STAGES>
-        {128, 128, 2, 2, kPanelStages, 3, 1}, {64, 128, 2, 2, kPanelStages, 3, 1}, {32, 128, 2, 2, kPanelStages, 3, 1},
-        {32, 160, 2, 2, 6, 1, 1}, {128, 160, 2, 2, 3, 1, 1}, {64, 160, 2, 2, 2, 1, 1}, {32, 80, 2, 1, 5, 1, 1}, {64, 80, 2, 1, 5, 1, 1}, {128, 160, 4, 1, 3, 1, 1}};
-    static_assert(sizeof(kInfo) / sizeof(kInfo[0]) == kNumTiles + 1, "one row per tile");
     if (tile < 1 || tile > kNumTiles || !out) return sdod::INVALID_ARGUMENT;
-    for (int i = 0; i < 7; ++i) out[i] = kInfo[tile][i];
+    const Tile& c = kTile[tile];
+    const int v[7] = {c.bm, c.bn, c.wm, c.wn, c.stages, c.family == RING ? c.spec : (int)c.family, c.ksub};
+    for (int i = 0; i < 7; ++i) out[i] = v[i];
     return 0;
 }
 
 extern "C" int sdod_gemm_tile_shape(int tile, int* bm, int* bn, int* lds_dma) {
     if (tile < 1 || tile > kNumTiles) return sdod::INVALID_ARGUMENT;
-    if (bm) *bm = kTiles[tile].bm;
-    if (bn) *bn = kTiles[tile].bn;
-    if (lds_dma) *lds_dma = tile >= 6 ? 1 : 0;
+    if (bm) *bm = kTile[tile].bm;
+    if (bn) *bn = kTile[tile].bn;
+    if (lds_dma) *lds_dma = kTile[tile].family != REG ? 1 : 0;
     return 0;
+}
+
+// the tiles the engine's tuner tries (engine.hip; declared in host_util.h)
+int sdod::gemm_tuner_tiles(int* out, int cap) {
+    int n = 0;
+    for (int t = 1; t <= kNumTiles; ++t)
+        if (kTile[t].tuned) {
+            if (out && n < cap) out[n] = t;
+            ++n;
+        }
+    return n;
 }
 
 extern "C" int sdod_gemm_panel_ok(const sdod_gemm_desc* d, int tile) {
@@ -2996,7 +3013,7 @@ extern "C" int sdod_gemm_halo_ok(const sdod_gemm_desc* d, int tile) {
 extern "C" int sdod_gemm_xcd_panels(const sdod_gemm_desc* d) {
     if (!d || d->K <= 0 || d->K % BK || d->M <= 0 || d->N <= 0) return 0;
     const Plan pl = make_plan(d);
-    const TileCfg tc = kTiles[pl.tile];
+    const Tile& tc = kTile[pl.tile];
     return xcd_panels(d, (d->M + tc.bm - 1) / tc.bm, (d->N + tc.bn - 1) / tc.bn);
 }
 
@@ -3107,7 +3124,7 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
     const Plan pl = make_plan(d);
     SDOD_REQUIRE(!(d->geglu && is_wave80_tile(pl.tile)), "geglu needs a tile with an even number of 16-column blocks per wave");
     SDOD_REQUIRE(!(d->softmax_cols || d->w_img_stride) || is_ring_tile(pl.tile), "softmax_cols / per-image weights need an LDS-DMA ring tile");
-    SDOD_REQUIRE(!(d->geglu || d->k_tail || d->bias2 || d->ln || d->wq) || pl.tile >= 6, "geglu / tail segment / bias2 / ln / uint8 weights need an LDS-DMA tile (6..48)");
+    SDOD_REQUIRE(!(d->geglu || d->k_tail || d->bias2 || d->ln || d->wq) || tile_family(pl.tile) != REG, "geglu / tail segment / bias2 / ln / uint8 weights need an LDS-DMA tile (6..48)");
     p.splits = pl.splits;
     p.kt_per_split = pl.kt_per_split;
     size_t halo_smem = 0;
@@ -3125,7 +3142,7 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
                      "split-K workspace missing or too small");
         p.partial = (float*)d->workspace;
     }
-    const TileCfg tc = kTiles[pl.tile];
+    const Tile& tc = kTile[pl.tile];
     p.tiles_m = (d->M + tc.bm - 1) / tc.bm;
     p.tiles_n = (d->N + tc.bn - 1) / tc.bn;
     make_magic((unsigned)(p.h_out * p.w_out), &p.mg_hw, &p.sh_hw);
@@ -3148,102 +3165,22 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
     dim3 grid(p.tiles_m * p.tiles_n, 1, pl.splits);
     hipStream_t st = (hipStream_t)stream;
     SDOD_REQUIRE(d->phase >= 0 && d->phase <= 2 && (d->phase == 0 || pl.splits > 1), "phase 1/2 only apply to a split-K plan");
-    hipError_t e = hipSuccess;
+    size_t smem = halo_smem; // (the halo and A-panel kernels: the other two know theirs from the tile shape)
     if (is_panel_tile(pl.tile)) {
         SDOD_REQUIRE(panel_ok(d, pl.tile), "this A-panel tile does not take the GEMM (plain rows x fp16 weights, K >= 192, the row panel must fit LDS)");
         // grid: one workgroup per (row panel, group of consecutive n-tiles), about one per CU
         p.ap_panels = p.tiles_m;
         panel_grid(p.ap_panels, p.tiles_n, &p.ap_tpg, &p.ap_groups);
         p.ap_nmajor = (double)d->N * d->K > (double)d->M * d->K ? 1 : 0; // W the bigger operand: an XCD keeps a group's W, not a panel's A
-        const size_t smem = panel_smem(tc.bm, tc.bn, d->K);
-        const dim3 pgrid(p.ap_panels * p.ap_groups);
-        switch (pl.tile) {
-        case 53: e = launch_panel<128, 128, 2, 2>(p, pgrid, smem, st); break;
-        case 54: e = launch_panel<64, 128, 2, 2>(p, pgrid, smem, st); break;
-        default: e = launch_panel<32, 128, 2, 2>(p, pgrid, smem, st); break;
-        }
-        SDOD_HIP_CHECK(e);
-        return 0;
+        smem = panel_smem(tc.bm, tc.bn, d->K);
+        grid = dim3(p.ap_panels * p.ap_groups);
     }
-    const bool halo_tile = is_halo_tile(pl.tile); // (takes uint8 weights itself: launch_halo)
-    if (d->phase != 2 && d->wq && !halo_tile)
-    switch (pl.tile) { // the uint8-weight variants (make_plan maps every other tile onto one of these)
-    case 8: e = launch_glds<64, 64, 2, 2, 4, false, true>(p, grid, st); break;
-    case 13: e = launch_glds<128, 128, 2, 4, 4, false, true>(p, grid, st); break;
-    case 24: e = launch_glds<128, 128, 2, 2, 3, true, true>(p, grid, st); break;
-    case 27: e = launch_glds<64, 64, 2, 2, 8, true, true>(p, grid, st); break;
-    case 28: e = launch_glds<64, 64, 2, 2, 4, true, true>(p, grid, st); break;
-    case 29: e = launch_glds<128, 64, 2, 2, 6, true, true>(p, grid, st); break;
-    case 30: e = launch_glds<64, 128, 2, 2, 6, true, true>(p, grid, st); break;
-    case 31: e = launch_glds<64, 160, 2, 2, 4, true, true>(p, grid, st); break;
-    default: e = launch_glds<128, 128, 2, 2, 4, true, true>(p, grid, st); break; // 23
-    }
-    else if (d->phase != 2)
-    switch (pl.tile) {
-    case 37: e = launch_halo<64, 160, 2, 2, 4>(p, grid, halo_smem, st); break;
-    case 38: e = launch_halo<128, 80, 4, 1, 4>(p, grid, halo_smem, st); break;
-    case 39: e = launch_halo<128, 160, 2, 2, 3>(p, grid, halo_smem, st); break;
-    case 40: e = launch_halo<64, 80, 4, 1, 4>(p, grid, halo_smem, st); break;
-    case 41: e = launch_halo<256, 32, 4, 1, 6>(p, grid, halo_smem, st); break;
-    case 42: e = launch_halo<128, 32, 4, 1, 6>(p, grid, halo_smem, st); break;
-    case 43: e = launch_halo<256, 64, 4, 1, 4>(p, grid, halo_smem, st); break;
-    case 44: e = launch_halo<128, 64, 2, 2, 4>(p, grid, halo_smem, st); break;
-    case 45: e = launch_halo<64, 64, 2, 2, 4>(p, grid, halo_smem, st); break;
-    case 49: e = launch_halo<96, 160, 2, 2, 3>(p, grid, halo_smem, st); break;
-    case 50: e = launch_halo<96, 64, 2, 2, 4>(p, grid, halo_smem, st); break;
-    case 51: e = launch_halo<192, 80, 4, 1, 4>(p, grid, halo_smem, st); break;
-    case 52: e = launch_halo<192, 64, 4, 1, 4>(p, grid, halo_smem, st); break;
-    case 1: e = launch_cfg<128, 128, 2, 2>(p, grid, st); break;
-    case 2: e = launch_cfg<128, 64, 2, 2>(p, grid, st); break;
-    case 3: e = launch_cfg<64, 64, 2, 2>(p, grid, st); break;
-    case 4: e = launch_cfg<256, 16, 4, 1>(p, grid, st); break;
-    case 5: e = launch_cfg<64, 128, 2, 2>(p, grid, st); break;
-    case 6: e = launch_glds<128, 128, 2, 2, 3>(p, grid, st); break;
-    case 7: e = launch_glds<128, 64, 2, 2, 4>(p, grid, st); break;
-    case 8: e = launch_glds<64, 64, 2, 2, 4>(p, grid, st); break;
-    case 9: e = launch_glds<128, 128, 2, 4, 3>(p, grid, st); break;
-    case 10: e = launch_glds<256, 128, 4, 2, 2>(p, grid, st); break;
-    case 11: e = launch_glds<128, 64, 4, 2, 4>(p, grid, st); break;
-    case 12: e = launch_glds<256, 64, 4, 2, 3>(p, grid, st); break;
-    case 13: e = launch_glds<128, 128, 2, 4, 4>(p, grid, st); break;
-    case 14: e = launch_glds<128, 128, 2, 4, 2>(p, grid, st); break;
-    case 15: e = launch_glds<256, 128, 4, 2, 3>(p, grid, st); break;
-    case 16: e = launch_glds<256, 256, 2, 4, 2>(p, grid, st); break;
-    case 17: e = launch_glds<64, 64, 2, 2, 8>(p, grid, st); break;
-    case 18: e = launch_glds<128, 64, 2, 2, 6>(p, grid, st); break;
-    case 19: e = launch_glds<64, 128, 2, 2, 6>(p, grid, st); break;
-    case 20: e = launch_glds<128, 256, 2, 4, 3>(p, grid, st); break;
-    case 21: e = launch_glds<64, 160, 2, 2, 4>(p, grid, st); break;
-    case 22: e = launch_glds<32, 160, 2, 2, 6>(p, grid, st); break;
-    case 23: e = launch_glds<128, 128, 2, 2, 4, true>(p, grid, st); break;
-    case 24: e = launch_glds<128, 128, 2, 2, 3, true>(p, grid, st); break;
-    case 25: e = launch_glds<128, 256, 2, 2, 3, true>(p, grid, st); break;
-    case 26: e = launch_glds<256, 128, 2, 2, 3, true>(p, grid, st); break;
-    case 27: e = launch_glds<64, 64, 2, 2, 8, true>(p, grid, st); break;
-    case 28: e = launch_glds<64, 64, 2, 2, 4, true>(p, grid, st); break;
-    case 29: e = launch_glds<128, 64, 2, 2, 6, true>(p, grid, st); break;
-    case 30: e = launch_glds<64, 128, 2, 2, 6, true>(p, grid, st); break;
-    case 31: e = launch_glds<64, 160, 2, 2, 4, true>(p, grid, st); break;
-    case 32: e = launch_glds<64, 64, 2, 2, 4, true, false, 2>(p, grid, st); break;
-    case 33: e = launch_glds<128, 64, 2, 2, 3, true, false, 2>(p, grid, st); break;
-    case 34: e = launch_glds<64, 128, 2, 2, 3, true, false, 2>(p, grid, st); break;
-    case 35: e = launch_glds<64, 160, 2, 2, 2, true, false, 2>(p, grid, st); break;
-    case 46: e = launch_glds<32, 64, 2, 2, 6, true>(p, grid, st); break;
-    case 47: e = launch_glds<32, 128, 1, 4, 6, true>(p, grid, st); break;
-    case 48: e = launch_glds<32, 160, 2, 2, 4, true>(p, grid, st); break;
-    case 56: e = launch_glds<32, 160, 2, 2, 6, true>(p, grid, st); break;
-    case 57: e = launch_glds<128, 160, 2, 2, 3, true>(p, grid, st); break;
-    case 58: e = launch_glds<64, 160, 2, 2, 2, true>(p, grid, st); break;
-    case 59: e = launch_glds<32, 80, 2, 1, 5, true>(p, grid, st); break;
-    case 60: e = launch_glds<64, 80, 2, 1, 5, true>(p, grid, st); break;
-    case 61: e = launch_glds<128, 160, 4, 1, 3, true>(p, grid, st); break;
-    default: e = launch_glds<128, 128, 2, 2, 2, true, false, 2>(p, grid, st); break;
-    }
+    hipError_t e = hipSuccess;
+    if (d->phase != 2) e = launch_tile_id(pl.tile, std::make_integer_sequence<int, kNumTiles>{}, p, grid, smem, st);
     SDOD_HIP_CHECK(e);
     if (pl.splits > 1 && d->phase != 1 && !p.fixup) {
-        const bool vec = (p.N % 4 == 0) && (p.ldo % 4 == 0) && !p.bias_on_m && (p.residual == nullptr || p.ldr % 4 == 0) &&
-                         (p.row_bias == nullptr || p.ldrb % 4 == 0) && (((uintptr_t)p.out | (uintptr_t)p.residual | (uintptr_t)p.row_bias) & 7) == 0 &&
-                         (((uintptr_t)p.bias | (uintptr_t)p.bias2 | (uintptr_t)p.partial) & 15) == 0 && (d->M + 3) / 4 <= 65535;
+        // splitk_reduce_vec_kernel also reads the slabs as aligned quads and has one grid row per four output rows
+        const bool vec = reduce_quads_ok(p) && ((uintptr_t)p.partial & 15) == 0 && (d->M + 3) / 4 <= 65535;
         if (vec) {
             SDOD_LAUNCH(splitk_reduce_vec_kernel, dim3((d->N / 4 + 63) / 64, (d->M + 3) / 4), dim3(64, 4), 0, st, p);
         } else {

@@ -48,6 +48,9 @@ inline bool first_use_on_device(std::atomic<unsigned long long>& mask) {
     return (mask.fetch_or(bit, std::memory_order_relaxed) & bit) == 0;
 }
 
+// The GEMM tiles the engine's tuner tries, ascending, read off gemm.hip's tile table: writes up to `cap` ids, returns how many there are.
+int gemm_tuner_tiles(int* out, int cap);
+
 } // namespace sdod
 
 #define SDOD_LAUNCH(kernel, grid, block, smem, stream, ...)                                                          \

@@ -419,6 +419,27 @@ def test_argument_checks_answer_before_any_launch():
     assert b'null pointer' in lib.sdod_hip_last_error()
 
 
+def _desc_from_tune_key(key):
+    """the GEMM descriptor a line of tune/gfx950.tune stands for, rebuilt from its 14 key fields (operand pointers are dummies)"""
+    from sdod.amd._lib import GemmDesc
+    a_mode, M, N, K, c0, c1, stride, ups, ksize, h_in, flags, lda, w_in, n_img = key
+    d = GemmDesc()
+    d.a = d.w = d.out = 0x1000
+    d.a2 = 0x1000 if c1 else None
+    d.a_mode, d.M, d.N, d.K, d.c0, d.c1, d.stride, d.upsample, d.ksize = a_mode, M, N, K, c0, c1, stride, ups, ksize
+    d.h_in, d.w_in, d.n_img, d.lda, d.ldw = h_in, w_in, n_img, lda, K
+    d.geglu = 1 if flags & 2 else 0
+    d.ldo = N // 2 if d.geglu else N
+    d.ln = 1 if flags & (1 << 30) else 0
+    d.wq = 1 if flags & (1 << 29) else 0
+    d.tc0, d.tc1 = (flags >> 2) & 4095, (flags >> 14) & 4095
+    if d.tc0:
+        d.k_tail = K - d.tc0 - d.tc1; d.t0 = 0x1000; d.t1 = 0x1000 if d.tc1 else None
+    if flags & 1:
+        d.residual = 0x1000; d.ldr = d.ldo
+    return d
+
+
 def test_shipped_tile_table_is_well_formed():
     """tune/gfx950.tune (the table every process builds its launch lists from): 14 key fields + pick per line, no duplicate
     keys, tile ids the library knows, split factors in range; halo-patch picks only on 3x3 stride-1 convolutions whose
@@ -427,7 +448,6 @@ def test_shipped_tile_table_is_well_formed():
     import ctypes
     import os
     from sdod.amd import _lib
-    from sdod.amd._lib import GemmDesc
     lib = _lib.hip()
     path = os.path.join(os.path.dirname(_lib.LIB_DIR), 'tune', 'gfx950.tune')
     assert os.path.exists(path), path
@@ -447,20 +467,7 @@ def test_shipped_tile_table_is_well_formed():
         assert lib.sdod_gemm_tile_info(tile, info) == 0
         a_mode, M, N, K, c0, c1, stride, ups, ksize, h_in, flags, lda, w_in, n_img = key
         if info[5] in (2, 3):
-            d = GemmDesc()
-            d.a = d.w = d.out = 0x1000
-            d.a2 = 0x1000 if c1 else None
-            d.a_mode, d.M, d.N, d.K, d.c0, d.c1, d.stride, d.upsample, d.ksize = a_mode, M, N, K, c0, c1, stride, ups, ksize
-            d.h_in, d.w_in, d.n_img, d.lda, d.ldw = h_in, w_in, n_img, lda, K
-            d.geglu = 1 if flags & 2 else 0
-            d.ldo = N // 2 if d.geglu else N
-            d.ln = 1 if flags & (1 << 30) else 0
-            d.wq = 1 if flags & (1 << 29) else 0
-            d.tc0, d.tc1 = (flags >> 2) & 4095, (flags >> 14) & 4095
-            if d.tc0:
-                d.k_tail = K - d.tc0 - d.tc1; d.t0 = 0x1000; d.t1 = 0x1000 if d.tc1 else None
-            if flags & 1:
-                d.residual = 0x1000; d.ldr = d.ldo
+            d = _desc_from_tune_key(key)
             d.tile, d.split_k = tile, split
         if info[5] == 2:   # conv_halo_kernel: the key must be a 3x3 stride-1 convolution (a_mode 1, stride 1, ksize 3) the tile holds
             assert a_mode == 1 and stride == 1 and ksize == 3 and w_in > 0 and n_img > 0, (ln, line)
@@ -471,3 +478,51 @@ def test_shipped_tile_table_is_well_formed():
             assert a_mode == 0 and split == 1 and lib.sdod_gemm_panel_ok(ctypes.byref(d), tile) == 1, (ln, line)
             n_panel += 1
     assert len(seen) >= 600 and n_halo >= 100, (len(seen), n_halo, n_panel)
+
+
+def _gemm_tile_answers():
+    """what the library's tile table answers through the host-only C ABI: the seven integers of sdod_gemm_tile_info and the
+    three of sdod_gemm_tile_shape for every tile, and for every distinct descriptor of tune/gfx950.tune (split_k left to the
+    plan) with `tile` forced to each of 0..61: [plan tile, plan splits, halo_ok, panel_ok, workspace bytes, xcd panels]"""
+    import ctypes
+    from sdod.amd import _lib
+    lib = _lib.hip()
+    info, a, b, c = (ctypes.c_int * 7)(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    tiles = []
+    for t in range(1, 62):
+        assert lib.sdod_gemm_tile_info(t, info) == 0 and lib.sdod_gemm_tile_shape(t, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)) == 0
+        tiles.append(list(info) + [a.value, b.value, c.value])
+    keys = sorted({tuple(int(x) for x in line.split()[:14]) for line in open(os.path.join(os.path.dirname(_lib.LIB_DIR), 'tune', 'gfx950.tune'))})
+    plans = {}
+    for key in keys:
+        d = _desc_from_tune_key(key)
+        rows = []
+        for t in range(62):
+            d.tile = t
+            assert lib.sdod_gemm_plan(ctypes.byref(d), ctypes.byref(a), ctypes.byref(b)) == 0
+            rows.append([a.value, b.value, lib.sdod_gemm_halo_ok(ctypes.byref(d), t), lib.sdod_gemm_panel_ok(ctypes.byref(d), t),
+                         lib.sdod_gemm_workspace_bytes(ctypes.byref(d)), lib.sdod_gemm_xcd_panels(ctypes.byref(d))])
+        plans[' '.join(map(str, key))] = rows
+    return {'num_tiles': lib.sdod_gemm_num_tiles(), 'tiles': tiles, 'plans': plans}
+
+
+def test_tile_table_answers_what_it_answered_before_it_was_one_table(golden_dir):
+    """tests/golden/gemm_tiles.json.gz (gzip: 0.9 MB of integers as text) holds _gemm_tile_answers() of the library as it was when every tile was still written down
+    in six places (kTiles, kInfo, kHaloStages, the range predicates, the uint8 list, the launch switches); the one table
+    that replaced them has to answer the same for every tile id 1..61 and plan every shipped descriptor the same on every
+    tile.  (Regenerate only when a tile is ADDED: `python tests/test_host_cabi.py | gzip -9n > tests/golden/gemm_tiles.json.gz`; the rows
+    of the tiles that existed must not change in the diff.)"""
+    import gzip
+    want = json.load(gzip.open(os.path.join(golden_dir, 'gemm_tiles.json.gz'), 'rt'))
+    got = _gemm_tile_answers()
+    assert got['num_tiles'] == want['num_tiles'] == 61
+    assert got['tiles'] == want['tiles']
+    assert len(want['plans']) >= 600 and got['plans'].keys() == want['plans'].keys()
+    for key, rows in want['plans'].items():
+        assert got['plans'][key] == rows, key
+
+
+if __name__ == '__main__':
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'stable-diffusion-on-device_amd'))
+    json.dump(_gemm_tile_answers(), sys.stdout, separators=(',', ':'))
