@@ -413,6 +413,34 @@ typedef struct sdod_ddim_inpaint_step_args {
     float guidance, vc0, vc1, sqrt_one_minus_at, sqrt_at, sqrt_a_prev, dir_coef, known_sa, known_s1a;
 } sdod_ddim_inpaint_step_args;
 SDOD_API int sdod_ddim_inpaint_step(const sdod_ddim_inpaint_step_args* a, void* stream);
+
+/* One step of a k-diffusion sampler (Euler, Euler ancestral, DPM++ 2M; host tables: sdod/amd/samplers.py, KSchedule.coef) behind a
+ * UNet evaluation in one launch.  The three published algorithms reduce to one linear form in the unscaled latent x:
+ *   e   = CFG(eps)                                              [sdod_cfg_combine]
+ *   den = d0 * x + d1 * e                                       [sdod_lincomb4_f32([x, e], [d0, d1], 1)]
+ *   x'  = a * x + b * den (+ cprev * den_prev) (+ u * nu)       [sdod_lincomb4_f32, left to right; the den_prev term only when
+ *                                                                cprev != 0, the nu term only when u != 0]
+ *   den_prev <- den (when den_prev is given);  x <- x'
+ * then the next evaluation's inputs: x_stage[r] = stage_scale * x' (one fp32 multiply: the model sees c_in * x) and temb_row into
+ * temb_dst[temb_reps][..] as sdod_stage_unet_inputs does.  Every product and sum is rounded on its own in fp32 (no FMA contraction):
+ * the bits of those separate launches.  nu: `noise` fp32 [n][c][hw], or when NULL drawn in the kernel, image i's values exactly those
+ * of sdod_randn_f32(count = c * hw, seed, stream_id = ((3 + noise_level) << 32) | (image_index0 + i)); with u == 0 no noise is drawn or
+ * read.  eps_nhwc == NULL is the start form in front of the loop: x <- a * x, then the staging (b, cprev and u must be 0).
+ * c * hw must be a multiple of 4; x, den_prev, noise and x_stage 16-byte aligned (they move as 16-byte lanes); every scalar finite.
+ * den_prev, noise, x_stage, temb_row may be NULL. */
+typedef struct sdod_k_step_args {
+    const void* eps_nhwc;   /* fp16 [2n][hw][c], or NULL: the start form */
+    float* x;               /* fp32 [n][c][hw], updated in place */
+    float* den_prev;        /* fp32 [n][c][hw] or NULL: read when cprev != 0, then replaced by this step's den */
+    const float* noise;     /* fp32 [n][c][hw] or NULL (drawn in the kernel); touched only when u != 0 */
+    float* x_stage;         /* fp32 [stage_reps][n][c][hw] or NULL */
+    const void* temb_row;   /* fp16 [temb_width] or NULL */
+    void* temb_dst;         /* fp16 [temb_reps][temb_width] */
+    uint64_t seed, image_index0;
+    int n, c, hw, uncond_first, mode, noise_level, stage_reps, temb_width, temb_reps;
+    float guidance, d0, d1, a, b, cprev, u, stage_scale;
+} sdod_k_step_args;
+SDOD_API int sdod_k_step(const sdod_k_step_args* a, void* stream);
 /* Inpainting's latent keep-mask: mask_u8 uint8 [n][factor * h_lat][factor * w_lat] (255 = repaint, 0 = keep) -> keep fp32
  * [n][h_lat][w_lat] = float(16320 - S) / 16320.0f with S the integer sum of the latent pixel's 8 x 8 block (16320 = 64 * 255; one
  * correctly rounded fp32 division).  factor must be 8 (the VAE's scale); mask_u8 8-byte aligned. */

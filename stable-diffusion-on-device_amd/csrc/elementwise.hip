@@ -6,9 +6,11 @@
 //   timestep_features   context.cpp:257-274
 //   image_to_u8         context.cpp:392-395
 // and the PLMS/DDIM arithmetic of config 1's CPU reference (ldm PLMSSampler; not in /root/reference), with ldm's masked DDIM
-// blend for inpainting (ddim_inpaint_step, mask_to_latent, image_composite).
+// blend for inpainting (ddim_inpaint_step, mask_to_latent, image_composite), and the k-diffusion samplers' step in its linear form
+// (k_step: Euler, Euler ancestral, DPM++ 2M).
 #include "common.h"
 #include <atomic>
+#include <cmath>
 #include "sdod_hip.h"
 #include "host_util.h"
 
@@ -403,6 +405,15 @@ SDOD_DEVICE float lincomb4(float c0, float v0, float c1, const float* e1, float 
     return div_rn(v, div);
 }
 
+// lincomb4 on values (a step kernel's registers): the e2 / e3 terms are left out where their flag is false, as lincomb4 leaves out a
+// null pointer; the same products, sums and division in the same order
+SDOD_DEVICE float lincomb4v(float c0, float v0, float c1, float v1, bool has2, float c2, float v2, bool has3, float c3, float v3, float div) {
+    float v = add_rn(mul_rn(c0, v0), mul_rn(c1, v1));
+    if (has2) v = add_rn(v, mul_rn(c2, v2));
+    if (has3) v = add_rn(v, mul_rn(c3, v3));
+    return div_rn(v, div);
+}
+
 // v-prediction: eps = lincomb4([v, x], [vc0, vc1], 1), as the host loop composes it (its division by 1 included)
 SDOD_DEVICE float v_to_eps(float v, float x, float vc0, float vc1) { return lincomb4(vc0, v, vc1, &x, 0.f, nullptr, 0.f, nullptr, 0, 1.0f); }
 
@@ -740,6 +751,53 @@ __global__ void ddim_inpaint_step_kernel(const sdod_ddim_inpaint_step_args a) {
     }
 }
 
+// One step of a k-diffusion sampler behind a UNet evaluation in ONE launch (include/sdod_hip.h: sdod_k_step): cfg_kernel's guidance,
+// den = lincomb4([x, e], [d0, d1], 1), x' = lincomb4([x, den, den_prev, nu], [a, b, cprev, u], 1) with the den_prev / nu terms left out
+// when their coefficient is 0 (as lincomb4_kernel leaves out a NULL term; lincomb4v), den_prev <- den, x <- x', x_stage <- stage_scale * x' and
+// the time row (stage_unet_inputs_kernel).  eps NULL: the start form, x' = lincomb4([x], [a], 1).  Thread = four consecutive elements
+// of one image = one Philox block of its noise stream (as ddim_inpaint_step_kernel); x, den_prev, noise, x_stage move as 16-byte lanes.
+__global__ void k_step_kernel(const sdod_k_step_args a) {
+    const size_t per = (size_t)a.c * a.hw, nblk = per / 4; // per % 4 == 0, pointers 16-byte aligned (checked by the host)
+    const size_t lat = (size_t)a.n * per, nlat = (size_t)a.n * nblk, nt = temb_work(a);
+    GRID_STRIDE(t, nlat + nt) {
+        if (t >= nlat) {
+            broadcast_row((f16*)a.temb_dst, (const f16*)a.temb_row, a.temb_width, t - nlat);
+            continue;
+        }
+        const int img = (int)(t / nblk);
+        const size_t j = t - (size_t)img * nblk;
+        const size_t o = (size_t)img * per + 4 * j;
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + o);
+        f32x4 out, den = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (a.eps_nhwc) {
+            f32x4 dp = f32x4{0.f, 0.f, 0.f, 0.f};
+            f32x4 nu = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (a.cprev != 0.0f) dp = *reinterpret_cast<const f32x4*>(a.den_prev + o);
+            if (a.u != 0.0f) nu = noise4(a.noise, o, j, a.seed, ((uint64_t)(3 + a.noise_level) << 32) | (a.image_index0 + img));
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const size_t e_i = 4 * j + q;
+                const size_t ch = e_i / a.hw, pix = e_i - ch * a.hw;
+                const float e = guided_eps((const f16*)a.eps_nhwc, img, ch, pix, a.n, a.c, a.hw, a.uncond_first, a.guidance, a.mode);
+                const float d = lincomb4v(a.d0, xv[q], a.d1, e, false, 0.f, 0.f, false, 0.f, 0.f, 1.0f);
+                den[q] = d;
+                out[q] = lincomb4v(a.a, xv[q], a.b, d, a.cprev != 0.0f, a.cprev, dp[q], a.u != 0.0f, a.u, nu[q], 1.0f);
+            }
+            if (a.den_prev) *reinterpret_cast<f32x4*>(a.den_prev + o) = den;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) out[q] = div_rn(mul_rn(a.a, xv[q]), 1.0f); // lincomb4([x], [a], 1)
+        }
+        *reinterpret_cast<f32x4*>(a.x + o) = out;
+        if (a.x_stage) {
+            f32x4 st;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) st[q] = mul_rn(a.stage_scale, out[q]);
+            stage_latent(a.x_stage, a.stage_reps, lat, o, st);
+        }
+    }
+}
+
 #define LAUNCH(kernel, work, st, ...)                                                            \
     do {                                                                                         \
         SDOD_LAUNCH(kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)(st), __VA_ARGS__); \
@@ -980,6 +1038,23 @@ extern "C" int sdod_ddim_inpaint_step(const sdod_ddim_inpaint_step_args* a, void
     SDOD_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->z0 | (uintptr_t)a->noise | (uintptr_t)a->x_stage) & 15) == 0 &&
                      ((uintptr_t)a->keep & 3) == 0 && ((uintptr_t)a->eps_nhwc & 1) == 0, "misaligned pointer (x, z0, noise, x_stage: 16 bytes)");
     LAUNCH(ddim_inpaint_step_kernel, work, stream, *a);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_k_step(const sdod_k_step_args* a, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(a && a->x && a->n > 0 && a->c > 0 && a->hw > 0 && (a->mode == 0 || a->mode == 1), "bad argument");
+    SDOD_REQUIRE(((size_t)a->c * a->hw) % 4 == 0, "c * hw must be a multiple of 4");
+    SDOD_REQUIRE(std::isfinite(a->guidance) && std::isfinite(a->d0) && std::isfinite(a->d1) && std::isfinite(a->a) && std::isfinite(a->b) &&
+                     std::isfinite(a->cprev) && std::isfinite(a->u) && std::isfinite(a->stage_scale), "non-finite scalar");
+    SDOD_REQUIRE(a->cprev == 0.0f || a->den_prev, "cprev needs den_prev");
+    SDOD_REQUIRE(a->eps_nhwc || (a->b == 0.0f && a->cprev == 0.0f && a->u == 0.0f), "the start form (eps NULL) takes a alone: b, cprev, u must be 0");
+    SDOD_REQUIRE(a->u == 0.0f || a->noise || a->noise_level >= 0, "negative noise level");
+    const size_t work = step_work(a, (size_t)a->n * a->c * a->hw / 4);
+    SDOD_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->den_prev | (uintptr_t)a->noise | (uintptr_t)a->x_stage) & 15) == 0 &&
+                     ((uintptr_t)a->eps_nhwc & 1) == 0, "misaligned pointer (x, den_prev, noise, x_stage: 16 bytes)");
+    LAUNCH(k_step_kernel, work, stream, *a);
     return 0;
     SDOD_CATCH
 }

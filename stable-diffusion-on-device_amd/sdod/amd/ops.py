@@ -638,6 +638,37 @@ def ddim_inpaint_step(eps_nhwc, x, ddim, guidance, z0=None, keep=None, known=Non
     check(lib.sdod_ddim_inpaint_step(ctypes.byref(a), _stream()))
 
 
+def k_step(eps_nhwc, x, coef, guidance=1.0, den_prev=None, noise=None, seed=0, noise_level=0, image_index=0, mode=1, uncond_first=True,
+           stage=None):
+    """one k-diffusion sampler step in one launch (include/sdod_hip.h: sdod_k_step): CFG of eps, den = d0 x + d1 e, x <- a x + b den
+    (+ cprev den_prev) (+ u nu) in place, den_prev <- den, and -- with stage = (x_dst, temb_row, temb_dst) -- the next evaluation's
+    inputs, x_dst = stage_scale * x.  coef = KSchedule.coef(...): d0, d1, a, b, cprev, u, stage_scale (missing keys: d0 = 1, the rest 0).
+    nu = noise (fp32, x's shape) or, when None, Philox on the device: stream ((3 + noise_level) << 32) | (image_index + i) of `seed`
+    for image i; nothing is drawn or read when u == 0.  eps_nhwc None: the start form, x <- a x and the staging."""
+    lib = _lib.hip()
+    _req(x, torch.float32, 'x')
+    a = _lib.KStepArgs()
+    if eps_nhwc is None:
+        n, c = x.shape[0], x.shape[1]
+        hw = x.numel() // (n * c)
+    else:
+        n, c, hw = _guided_dims(eps_nhwc, x)
+        a.eps_nhwc = _p(eps_nhwc)
+    a.x = _p(x)
+    for t, name in ((den_prev, 'den_prev'), (noise, 'noise')):
+        if t is not None:
+            _req(t, torch.float32, name)
+            assert t.numel() == x.numel(), (name, t.shape, x.shape)
+    a.den_prev, a.noise = _p(den_prev), _p(noise)
+    a.seed, a.noise_level, a.image_index0 = int(seed) & (2 ** 64 - 1), int(noise_level), int(image_index) & (2 ** 64 - 1)
+    a.n, a.c, a.hw, a.uncond_first, a.mode = n, c, hw, 1 if uncond_first else 0, mode
+    a.guidance = guidance
+    a.d0, a.d1, a.a, a.b = coef.get('d0', 1.0), coef.get('d1', 0.0), coef.get('a', 0.0), coef.get('b', 0.0)
+    a.cprev, a.u, a.stage_scale = coef.get('cprev', 0.0), coef.get('u', 0.0), coef.get('stage_scale', 0.0)
+    _fill_stage(a, x, stage)
+    check(lib.sdod_k_step(ctypes.byref(a), _stream()))
+
+
 def mask_to_latent(mask_u8, factor=8):
     """inpainting's latent keep-mask (sdod_mask_to_latent_f32): uint8 [n, 8H, 8W] (255 = repaint, 0 = keep) -> fp32 [n, H, W],
     keep = (16320 - sum of the 8 x 8 block) / 16320"""

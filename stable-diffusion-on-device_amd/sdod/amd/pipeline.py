@@ -11,7 +11,7 @@ import torch
 from . import engine as E
 from . import ops
 from .host import DpmSolver
-from .samplers import PLMS_ORDERS, PlmsSchedule
+from .samplers import K_SAMPLERS, K_SCHEDULES, PLMS_ORDERS, KSchedule, PlmsSchedule
 
 
 class Txt2Img:
@@ -232,6 +232,34 @@ class Txt2Img:
                          stage=(self.unet.x, temb[s + 1], self.unet.temb) if s + 1 < steps else None)
         return x
 
+    def sample_k(self, ctx2, x, sampler, steps=20, guidance=7.5, schedule='discrete', eta=1.0, first=0, seed=0, image_index=0,
+                 step_noise=None):
+        """k-diffusion's sample_euler / sample_euler_ancestral / sample_dpmpp_2m ('euler', 'euler_a', 'dpmpp_2m') over KSchedule(steps,
+        schedule), steps first .. steps - 1, CFG mode 1, eps or v models.  first = 0: x is unit-variance noise x_T and the trajectory
+        starts from sigmas[0] * x_T; first > 0 (img2img): x already lies at level sigmas[first] (z0 + sigmas[first] * noise) and the
+        first executed step has no history.  One start launch in front of the loop (the scaling and the first staging), then per step
+        the UNet replay and ONE launch (ops.k_step = cfg_combine + lincomb4 + lincomb4 + the c_in multiply + stage_unet_inputs, bit
+        for bit): the model sees c_in(i) * x at the fractional time times[i].  euler_a's fresh noise of step i: step_noise[i - first]
+        (fp32 [steps - first - 1, n, 4, H, W]; the last step draws none) or Philox on the device, stream ((3 + i) << 32) |
+        (image_index + k) of `seed` for image k.  Under cfg_split the step runs redundantly on both ranks behind the exchange."""
+        k_check_args(sampler, steps, schedule, eta, step_noise, self._latent_shape, x.shape[0], first)
+        sch = KSchedule(steps, schedule)
+        temb = self.time_embeddings(sch.times)                             # row i <-> step i
+        self._set_context(ctx2)
+        x = x.to(self.device, torch.float32).clone()
+        if step_noise is not None:
+            step_noise = step_noise.to(self.device, torch.float32).contiguous()
+        den_prev = torch.empty_like(x) if sampler == 'dpmpp_2m' else None
+        ops.k_step(None, x, dict(a=float(sch.sigmas[0]) if first == 0 else 1.0, stage_scale=sch.c_in(first)),
+                   stage=(self.unet.x, temb[first], self.unet.temb))
+        for i in range(first, steps):
+            cf = sch.coef(sampler, i, eta, self.v_prediction, first)
+            ops.k_step(self._unet_eps(), x, cf, guidance, den_prev=den_prev,
+                       noise=step_noise[i - first] if step_noise is not None and cf['u'] != 0.0 else None,
+                       seed=seed, noise_level=i, image_index=image_index, mode=1,
+                       stage=(self.unet.x, temb[i + 1], self.unet.temb) if i + 1 < steps else None)
+        return x
+
     def _sample(self, sampler, ctx2, x_T, steps, guidance):
         return self.sample_plms(ctx2, x_T, steps, guidance) if sampler == 'plms' else self.sample_dpm(ctx2, x_T, steps, guidance)
 
@@ -254,8 +282,16 @@ class Txt2Img:
                 outs.append(ops.image_composite(self.vae.img, composite[0][i:i + 1], composite[1][i:i + 1], 0.5, 0.5, mode))
         return torch.cat(outs, 0)
 
-    def generate(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms'):
+    def generate(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms', *, schedule='discrete', eta=1.0, seed=0, image_index=0,
+                 step_noise=None):
+        """sampler 'plms' / 'dpm': as ever (schedule, eta, seed, image_index play no part; a non-default schedule or a step_noise
+        raises).  'euler' / 'euler_a' / 'dpmpp_2m': sample_k from sigmas[0] * x_T (x_T stays unit-variance noise) on schedule
+        'discrete' or 'karras', decode mode 1; eta, seed, image_index, step_noise (fp32 [steps - 1, n, 4, H, W]) are euler_a's noise.
+        Argument errors raise ValueError before any device work."""
+        k_check_args(sampler, steps, schedule, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
         self._require_cond()
+        if sampler in K_SAMPLERS:
+            return self.decode(self.sample_k(ctx2, x_T, sampler, steps, guidance, schedule, eta, 0, seed, image_index, step_noise), mode=1)
         return self.decode(self._sample(sampler, ctx2, x_T, steps, guidance), mode=1 if sampler == 'plms' else 0)
 
     # ------------------------------------------------------------------ whole trajectories as one device graph
@@ -288,31 +324,53 @@ class Txt2Img:
         for i in range(dst.shape[0]):
             ops.randn(tuple(dst[i:i + 1].shape), seed, (family << 32) | (image_index + i), self.device, out=dst[i:i + 1])
 
-    def generate_graphed(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms'):
+    def generate_graphed(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms', *, schedule='discrete', eta=1.0, seed=0, image_index=0,
+                         step_noise=None):
         """generate() with the WHOLE trajectory -- context upload, every UNet evaluation, CFG, sampler updates, VAE decode,
         uint8 -- replayed as ONE device graph: the host enqueues a single launch per image instead of ~9 small launches per
         step, so the GPU never waits for Python between steps (2-3 ms per image at 20 steps).  The sequence is static for a
-        given (sampler, steps, guidance, batch): it is captured once from the ordinary eager code path (so it is the same
-        kernels on the same buffers, bit for bit) and cached; ctx2 / x_T are copied into the graph's static inputs."""
+        given (sampler, steps, guidance, batch, schedule, eta): it is captured once from the ordinary eager code path (so it is the
+        same kernels on the same buffers, bit for bit) and cached; ctx2 / x_T are copied into the graph's static inputs.  euler_a's
+        step noise is a static input too: without `step_noise` it is drawn into it first by sdod_randn_f32 on the streams the eager
+        path draws in its kernels, so the graph bakes no seed and the result equals generate() with the same arguments."""
+        k_check_args(sampler, steps, schedule, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
         self._require_cond()
+        kw = dict(schedule=schedule, eta=eta)
         if self.cfg_split:                 # a collective per evaluation cannot live inside one captured graph
-            return self.generate(ctx2, x_T, steps, guidance, sampler)
-        key = (sampler, int(steps), float(guidance), tuple(x_T.shape))
-        g, (s_ctx, s_x), out = self._graphed(key, [(ctx2.shape, ctx2.dtype), (x_T.shape, torch.float32)],
-                                             lambda c, x: self.generate(c, x, steps, guidance, sampler))
+            return self.generate(ctx2, x_T, steps, guidance, sampler, seed=seed, image_index=image_index, step_noise=step_noise, **kw)
+        key = (sampler, int(steps), float(guidance), tuple(x_T.shape), schedule, float(eta))
+        inputs = [(ctx2.shape, ctx2.dtype), (x_T.shape, torch.float32)]
+        if sampler == 'euler_a':
+            g, (s_ctx, s_x, s_sn), out = self._graphed(key, inputs + [((int(steps) - 1,) + tuple(x_T.shape), torch.float32)],
+                                                       lambda c, x, sn: self.generate(c, x, steps, guidance, sampler, step_noise=sn, **kw))
+            self._fill_step_noise(s_sn, step_noise, seed, 0, image_index)
+        else:
+            g, (s_ctx, s_x), out = self._graphed(key, inputs, lambda c, x: self.generate(c, x, steps, guidance, sampler, **kw))
         s_ctx.copy_(ctx2); s_x.copy_(x_T)
         g.replay()
         return out
 
+    def _fill_step_noise(self, s_sn, step_noise, seed, first, image_index):
+        """a graph's static step-noise input [rows, n, 4, H, W], row r = the noise of k-sampler step first + r: the caller's, or what
+        the eager path's kernels draw for it (noise family 3 + step)"""
+        if step_noise is None:
+            for r in range(s_sn.shape[0]):
+                self._fill_noise(s_sn[r], seed, 3 + first + r, image_index)
+        else:
+            s_sn.copy_(step_noise)
+
     # ------------------------------------------------------------------ img2img (ldm scripts/img2img.py, DDIM eta = 0)
-    def encode(self, init_u8, seed=0, image_index=0, strength=0.75, steps=50, noise=None, return_z0=False):
+    def encode(self, init_u8, seed=0, image_index=0, strength=0.75, steps=50, noise=None, return_z0=False, coef=None):
         """uint8 [n, 8H, 8W, 3] -> x fp32 [n, 4, H, W]: the VAE encoder, a posterior sample scaled by 0.18215, and ldm's
         stochastic_encode to ddim index t_enc = int(strength * steps).  noise = (n1, n2), fp32 [n, 4, H, W] each, or None: drawn
         on the device (Philox, seed, streams (1 << 32) | index and (2 << 32) | index with index = image_index + i).
-        return_z0=True: returns (x, z0) with z0 fp32 [n, 4, H, W] the clean latent (the scaled posterior sample) from the same launch."""
+        return_z0=True: returns (x, z0) with z0 fp32 [n, 4, H, W] the clean latent (the scaled posterior sample) from the same launch.
+        coef = (c_z0, c_noise): x = c_z0 * z0 + c_noise * n2 with these in the place of ldm's (sqrt(abar), sqrt(1 - abar)) at t_enc --
+        (1, sigmas[first]) is the k-samplers' start latent."""
         if self.encoder is None:
             raise RuntimeError('Txt2Img(..., with_vae_encoder=True) is needed for img2img')
         sch, t_enc = img2img_schedule(strength, steps)
+        c_z0, c_noise = (float(sch.sqrt_alphas[t_enc]), float(sch.sqrt_one_minus_alphas[t_enc])) if coef is None else coef
         init_u8 = init_u8.to(self.device)
         xs = []
         z0 = None
@@ -323,7 +381,7 @@ class Txt2Img:
             self.encoder.execute(self.use_hip_graph)
             n1, n2 = (None, None) if noise is None else (noise[0][i:i + 1].to(self.device, torch.float32).contiguous(),
                                                          noise[1][i:i + 1].to(self.device, torch.float32).contiguous())
-            xs.append(ops.encode_latent(self.encoder.moments, float(sch.sqrt_alphas[t_enc]), float(sch.sqrt_one_minus_alphas[t_enc]),
+            xs.append(ops.encode_latent(self.encoder.moments, float(c_z0), float(c_noise),
                                         seed, image_index + i, n1, n2, z0=None if z0 is None else z0[i:i + 1]))
         x = torch.cat(xs, 0)
         return (x, z0) if return_z0 else x
@@ -342,26 +400,46 @@ class Txt2Img:
                 trace.append((int(sch.timesteps[index]), index))
         return x
 
-    def img2img(self, ctx2, init_u8, strength=0.75, steps=50, guidance=7.5, seed=0, noise=None, image_index=0, trace=None):
-        """ldm scripts/img2img.py: encode the init image, noise it to ddim index int(strength * steps), denoise, decode to uint8"""
-        _, t_enc = img2img_schedule(strength, steps)
+    def img2img(self, ctx2, init_u8, strength=0.75, steps=50, guidance=7.5, seed=0, noise=None, image_index=0, trace=None, sampler=None,
+                schedule='discrete', eta=1.0, step_noise=None):
+        """ldm scripts/img2img.py: encode the init image, noise it to ddim index int(strength * steps), denoise, decode to uint8.
+        sampler None: ldm's DDIM, as ever.  'euler' / 'euler_a' / 'dpmpp_2m': with t_enc = int(strength * steps) and first = steps -
+        t_enc the start latent is z0 + sigmas[first] * n2 and sample_k(first=first) makes the t_enc evaluations; step_noise fp32
+        [t_enc - 1, n, 4, H, W], row r = step first + r (euler_a); `trace` is not filled."""
+        t_enc = img2img_k_check_args(strength, steps, sampler, schedule, eta, step_noise, self._latent_shape, init_u8.shape[0])
+        if sampler is not None:
+            first = int(steps) - t_enc
+            x = self.encode(init_u8, seed, image_index, strength, steps, noise, coef=(1.0, float(KSchedule(steps, schedule).sigmas[first])))
+            z = self.sample_k(ctx2, x, sampler, steps, guidance, schedule, eta, first, seed, image_index, step_noise)
+            return self.decode(z, mode=1)
         x = self.encode(init_u8, seed, image_index, strength, steps, noise)
         z = self.sample_ddim_from(ctx2, x, t_enc, steps, guidance, trace)
         return self.decode(z, mode=1)
 
-    def img2img_graphed(self, ctx2, init_u8, strength=0.75, steps=50, guidance=7.5, seed=0, noise=None, image_index=0):
+    def img2img_graphed(self, ctx2, init_u8, strength=0.75, steps=50, guidance=7.5, seed=0, noise=None, image_index=0, sampler=None,
+                        schedule='discrete', eta=1.0, step_noise=None):
         """img2img() as ONE device graph replay (encoder, start latent, every UNet evaluation, DDIM updates, decoder, uint8), captured
         once per (t_enc, steps, guidance, shape) from the eager path.  The noise is always an input of the graph: without `noise`
         it is drawn into it first by sdod_randn_f32 on the streams encode() uses, which is what the encoder's in-kernel draw gives
-        bit for bit, so the result equals img2img() with the same arguments."""
-        _, t_enc = img2img_schedule(strength, steps)
+        bit for bit, so the result equals img2img() with the same arguments.  With a k-sampler the key adds (sampler, schedule, eta),
+        and euler_a's step noise is one more input of the graph, filled the same way."""
+        t_enc = img2img_k_check_args(strength, steps, sampler, schedule, eta, step_noise, self._latent_shape, init_u8.shape[0])
+        kw = dict(sampler=sampler, schedule=schedule, eta=eta)
         if self.cfg_split:
-            return self.img2img(ctx2, init_u8, strength, steps, guidance, seed, noise, image_index)
+            return self.img2img(ctx2, init_u8, strength, steps, guidance, seed, noise, image_index, step_noise=step_noise, **kw)
         lat = (init_u8.shape[0],) + self._latent_shape
         key = ('img2img', t_enc, int(steps), float(guidance), tuple(init_u8.shape))
-        g, (s_ctx, s_img, s_n1, s_n2), out = self._graphed(
-            key, [(ctx2.shape, ctx2.dtype), (init_u8.shape, torch.uint8), (lat, torch.float32), (lat, torch.float32)],
-            lambda c, img, n1, n2: self.img2img(c, img, strength, steps, guidance, noise=(n1, n2)))
+        inputs = [(ctx2.shape, ctx2.dtype), (init_u8.shape, torch.uint8), (lat, torch.float32), (lat, torch.float32)]
+        if sampler is not None:
+            key += (sampler, schedule, float(eta))
+        if sampler == 'euler_a':
+            g, (s_ctx, s_img, s_n1, s_n2, s_sn), out = self._graphed(
+                key, inputs + [((t_enc - 1,) + lat, torch.float32)],
+                lambda c, img, n1, n2, sn: self.img2img(c, img, strength, steps, guidance, noise=(n1, n2), step_noise=sn, **kw))
+            self._fill_step_noise(s_sn, step_noise, seed, int(steps) - t_enc, image_index)
+        else:
+            g, (s_ctx, s_img, s_n1, s_n2), out = self._graphed(
+                key, inputs, lambda c, img, n1, n2: self.img2img(c, img, strength, steps, guidance, noise=(n1, n2), **kw))
         s_ctx.copy_(ctx2); s_img.copy_(init_u8)
         if noise is None:
             self._fill_noise(s_n1, seed, 1, image_index)
@@ -522,7 +600,10 @@ class Txt2Img:
         being sampled.  EXPERIMENT, not the default: the guided UNet chain is latency-bound (batch 1 takes 82 % of the time of
         batch 2, tools/two_chain_probe.py), but on MI355X the decode's big grids take more from that chain than the overlap
         gives back (bench.py --overlap-decode: 8.97 vs 9.29 images/s serial, same box).  Returns (uint8 images, event): the
-        images are valid once the event has completed and until the decode of the NEXT call starts."""
+        images are valid once the event has completed and until the decode of the NEXT call starts.  'plms' and 'dpm' only: its
+        sampling graph has no noise input."""
+        if sampler not in ('plms', 'dpm'):
+            raise ValueError(f"generate_pipelined samples with 'plms' or 'dpm', got {sampler!r}")
         if self.cfg_split:
             out = self.generate(ctx2, x_T, steps, guidance, sampler)
             ev = torch.cuda.Event(); ev.record()
@@ -562,6 +643,49 @@ def img2img_schedule(strength, steps):
     if not 1 <= t_enc <= steps - 1:
         raise ValueError(f'int(strength * steps) = {t_enc} is outside [1, steps - 1] = [1, {steps - 1}]')
     return PlmsSchedule(steps), t_enc
+
+
+def k_check_args(sampler, steps, schedule, eta, step_noise, latent, n_images, first=0, old_samplers=False):
+    """the argument contract of the k-diffusion samplers (Txt2Img.sample_k, generate, generate_graphed), checked on the host before any
+    device work: sampler one of K_SAMPLERS (old_samplers=True: or 'plms' / 'dpm', which take schedule 'discrete' and no step_noise);
+    steps a positive integer; 0 <= first < steps; schedule 'discrete' or 'karras'; eta >= 0; step_noise None or -- euler_a only -- an
+    fp32 tensor [steps - first - 1, n_images, *latent].  Raises ValueError."""
+    old = ('plms', 'dpm') if old_samplers else ()
+    if sampler not in K_SAMPLERS + old:
+        raise ValueError(f'sampler must be one of {old + K_SAMPLERS}, got {sampler!r}')
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+        raise ValueError(f'steps must be a positive integer, got {steps!r}')
+    if int(first) != first or not 0 <= first < steps:
+        raise ValueError(f'first must be an integer in [0, steps - 1] = [0, {int(steps) - 1}], got {first!r}')
+    if schedule not in K_SCHEDULES:
+        raise ValueError(f'schedule must be one of {K_SCHEDULES}, got {schedule!r}')
+    if not float(eta) >= 0.0 or float(eta) == float('inf'):
+        raise ValueError(f'eta must be a finite number >= 0, got {eta!r}')
+    if sampler in old:
+        if schedule != 'discrete' or step_noise is not None:
+            raise ValueError(f"sampler {sampler!r} runs on its own time grid without per-step noise: schedule must be 'discrete' and "
+                             f'step_noise None')
+        return
+    if step_noise is not None:
+        if sampler != 'euler_a':
+            raise ValueError(f"step_noise is euler_a's fresh noise; sampler {sampler!r} draws none")
+        want = (int(steps) - int(first) - 1, n_images) + tuple(latent)
+        if not isinstance(step_noise, torch.Tensor) or step_noise.dtype != torch.float32 or tuple(step_noise.shape) != want:
+            raise ValueError(f'step_noise must be an fp32 tensor {want} (one row per step but the last), got '
+                             f'{tuple(getattr(step_noise, "shape", ()))} {getattr(step_noise, "dtype", type(step_noise))}')
+
+
+def img2img_k_check_args(strength, steps, sampler, schedule, eta, step_noise, latent, n_images):
+    """the argument contract of Txt2Img.img2img / img2img_graphed: strength and steps in img2img_schedule's domain; sampler None (ldm's
+    DDIM: schedule 'discrete', no step_noise) or one of K_SAMPLERS with k_check_args' contract at first = steps - t_enc.  Returns t_enc;
+    raises ValueError."""
+    _, t_enc = img2img_schedule(strength, steps)
+    if sampler is None:
+        if schedule != 'discrete' or step_noise is not None:
+            raise ValueError("sampler None is ldm's DDIM (eta = 0): schedule must be 'discrete' and step_noise None")
+        return t_enc
+    k_check_args(sampler, steps, schedule, eta, step_noise, latent, n_images, first=int(steps) - t_enc)
+    return t_enc
 
 
 def inpaint_levels(sch, t_enc):

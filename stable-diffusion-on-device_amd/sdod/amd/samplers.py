@@ -39,3 +39,104 @@ class PlmsSchedule:
 
 # Adams-Bashforth combinations of the eps history (newest first): (coefficients, divisor)
 PLMS_ORDERS = {1: ((3.0, -1.0), 2.0), 2: ((23.0, -16.0, 5.0), 12.0), 3: ((55.0, -59.0, 37.0, -9.0), 24.0)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# k-diffusion's sigma-space samplers (Karras et al. 2022; the public k-diffusion package's sample_euler, sample_euler_ancestral,
+# sample_dpmpp_2m, DiscreteSchedule and get_sigmas_karras).  The tables are float64 numpy; the per-element arithmetic runs on the
+# device in one launch per step (include/sdod_hip.h: sdod_k_step).
+K_SAMPLERS = ('euler', 'euler_a', 'dpmpp_2m')
+K_SCHEDULES = ('discrete', 'karras')
+
+
+class KSchedule:
+    """Noise levels of a k-diffusion trajectory over the model's 1000 training levels sigma_t = sqrt((1 - abar_t) / abar_t).
+    sigmas: float64 [steps + 1], strictly decreasing, last entry 0.  schedule 'discrete': t_to_sigma(linspace(999, 0, steps))
+    (k-diffusion DiscreteSchedule.get_sigmas); 'karras': (smax^(1/rho) + r (smin^(1/rho) - smax^(1/rho)))^rho, r = linspace(0, 1, steps),
+    between sigma_999 and sigma_0 (get_sigmas_karras).  times[i] = sigma_to_t(sigmas[i]), float64 [steps]: the model time of step i's
+    evaluation, fractional in general."""
+
+    def __init__(self, steps=20, schedule='discrete', rho=7.0, n_train=1000):
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError(f'steps must be a positive integer, got {steps}')
+        if schedule not in K_SCHEDULES:
+            raise ValueError(f'schedule must be one of {K_SCHEDULES}, got {schedule!r}')
+        ac = scaled_linear_alphas_cumprod(n_train).astype(np.float64)
+        self.sigma_table = np.sqrt((1.0 - ac) / ac)                          # sigma_t, t = 0 .. n_train - 1, increasing
+        self.log_sigma_table = np.log(self.sigma_table)
+        self.sigma_min, self.sigma_max = float(self.sigma_table[0]), float(self.sigma_table[-1])
+        self.steps, self.schedule, self.rho = steps, schedule, float(rho)
+        if schedule == 'discrete':
+            body = self.t_to_sigma(np.linspace(n_train - 1, 0, steps))
+        else:
+            r = np.linspace(0.0, 1.0, steps)
+            lo, hi = self.sigma_min ** (1.0 / self.rho), self.sigma_max ** (1.0 / self.rho)
+            body = (hi + r * (lo - hi)) ** self.rho
+        self.sigmas = np.concatenate([np.asarray(body, dtype=np.float64).reshape(-1), [0.0]])
+        self.times = self.sigma_to_t(self.sigmas[:-1])
+
+    def sigma_to_t(self, sigma):
+        """k-diffusion DiscreteSchedule.sigma_to_t: linear interpolation in log sigma between the neighbouring integer t, clamped to
+        [0, n_train - 1]"""
+        ls = self.log_sigma_table
+        log_sigma = np.log(np.asarray(sigma, dtype=np.float64))
+        low = np.clip(np.searchsorted(ls, log_sigma, side='right') - 1, 0, len(ls) - 2)   # the last table entry <= log_sigma
+        w = np.clip((ls[low] - log_sigma) / (ls[low] - ls[low + 1]), 0.0, 1.0)
+        return (1.0 - w) * low + w * (low + 1)
+
+    def t_to_sigma(self, t):
+        """k-diffusion DiscreteSchedule.t_to_sigma: the inverse of sigma_to_t"""
+        t = np.asarray(t, dtype=np.float64)
+        low = np.floor(t).astype(np.int64)
+        high = np.ceil(t).astype(np.int64)
+        w = t - low
+        return np.exp((1.0 - w) * self.log_sigma_table[low] + w * self.log_sigma_table[high])
+
+    def c_in(self, i):
+        """the model-input scale at level i: the UNet sees c_in * x (k-diffusion DiscreteEpsDDPMDenoiser.get_scalings, sigma_data = 1)"""
+        return float(1.0 / np.sqrt(self.sigmas[i] ** 2 + 1.0))
+
+    def coef(self, sampler, i, eta=1.0, v_prediction=False, first=0):
+        """the scalars of step i (sigmas[i] -> sigmas[i + 1]) in the one linear form the three published algorithms reduce to,
+            den = d0 x + d1 e ;  x' = a x + b den + cprev den_prev + u nu
+        (e: the guided model output, x: the unscaled latent, den_prev: the previous step's den, nu: fresh unit noise), and stage_scale =
+        c_in(i + 1) for the next evaluation's input.  den: eps models (1, -s); v models (1 / (s^2 + 1), -s / sqrt(s^2 + 1)).
+          euler     d = (x - den) / s ; x + d (s' - s)                     a = s'/s, b = 1 - s'/s
+          euler_a   up = min(s', eta sqrt(s'^2 (s^2 - s'^2) / s^2)), down = sqrt(s'^2 - up^2) ; x + d (down - s) + up nu
+          dpmpp_2m  h = log s - log s', E = -expm1(-h): (s'/s) x + E den_d, den_d = (1 + 1/(2r)) den - 1/(2r) den_prev with
+                    r = (log s_prev - log s) / h; first order (den_d = den) at the trajectory's first step (i == first) and to s' = 0
+        The step to s' = 0 is (a, b, cprev, u) = (0, 1, 0, 0) for all three: the result is den.  Returns a dict of Python floats."""
+        if sampler not in K_SAMPLERS:
+            raise ValueError(f'sampler must be one of {K_SAMPLERS}, got {sampler!r}')
+        if not 0 <= i < self.steps:
+            raise ValueError(f'step {i} is outside [0, {self.steps - 1}]')
+        if not eta >= 0.0:
+            raise ValueError(f'eta must be >= 0, got {eta}')
+        s, s1 = float(self.sigmas[i]), float(self.sigmas[i + 1])
+        if v_prediction:
+            d0, d1 = 1.0 / (s * s + 1.0), -s / np.sqrt(s * s + 1.0)
+        else:
+            d0, d1 = 1.0, -s
+        a, b, cprev, u = 0.0, 1.0, 0.0, 0.0
+        if s1 > 0.0:
+            if sampler == 'euler':
+                a = s1 / s
+                b = 1.0 - a
+            elif sampler == 'euler_a':
+                up = min(s1, float(eta) * np.sqrt(s1 * s1 * (s * s - s1 * s1) / (s * s)))
+                down = np.sqrt(s1 * s1 - up * up)
+                a = down / s
+                b = 1.0 - a
+                u = up
+            else:
+                h = np.log(s) - np.log(s1)
+                e = -np.expm1(-h)
+                a = s1 / s
+                if i == first:
+                    b = e
+                else:
+                    r = (np.log(float(self.sigmas[i - 1])) - np.log(s)) / h
+                    b = e * (1.0 + 1.0 / (2.0 * r))
+                    cprev = -e / (2.0 * r)
+        return dict(d0=float(d0), d1=float(d1), a=float(a), b=float(b), cprev=float(cprev), u=float(u), stage_scale=self.c_in(i + 1))
