@@ -240,7 +240,9 @@ SDOD_API int sdod_layer_norm_f16(const void* x, void* y, const float* weight, co
                                  float eps, void* stream);
 
 /* Fused attention: out[b][q][h*D..] = softmax(scale * Q K^T (+causal mask)) V, never materialising scores.
- * q: [B][Lq][ldq], k/v: [B][Lk][ldk]/[ldv], head h at column offset h*D.  D in {40, 64, 80, 160}. */
+ * q: [B][Lq][ldq], k/v: [B][Lk][ldk]/[ldv], head h at column offset h*D.  D in {40, 64, 80, 160}.
+ * Row strides in halves: ldq, ldk, ldv multiples of 8, ldo a multiple of 4, all >= heads * D; q, k, v 16-byte and out 8-byte
+ * aligned (q / k / v / out may be column offsets into wider rows).  scale must be finite and > 0: anything else is an error. */
 SDOD_API int sdod_attention_f16(const void* q, const void* k, const void* v, void* out, int batch, int heads,
                                 int lq, int lk, int d, int ldq, int ldk, int ldv, int ldo, float scale, int causal,
                                 void* stream);

@@ -21,6 +21,7 @@
 #include "host_util.h"
 
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 
@@ -653,6 +654,9 @@ extern "C" int sdod_attention_f16(const void* q, const void* k, const void* v, v
     SDOD_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0, "row strides must keep 16-byte alignment");
     SDOD_REQUIRE(ldq >= heads * d && ldk >= heads * d && ldv >= heads * d && ldo >= heads * d, "row stride < heads*d");
     SDOD_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0 && ((uintptr_t)out & 7) == 0, "misaligned pointer");
+    // d = 64 / 160 take the row maximum on the RAW scores and scale it afterwards, which is the maximum of the scaled scores
+    // only for scale > 0; no caller passes anything else
+    SDOD_REQUIRE(std::isfinite(scale) && scale > 0.f, "scale must be finite and > 0");
     AttnP p{};
     p.q = (const f16*)q; p.k = (const f16*)k; p.v = (const f16*)v; p.out = (f16*)out;
     p.B = batch; p.H = heads; p.Lq = lq; p.Lk = lk;
@@ -662,7 +666,9 @@ extern "C" int sdod_attention_f16(const void* q, const void* k, const void* v, v
     const bool no_tr = std::getenv("SDOD_ATTN_NO_TR") != nullptr; // debugging aid: scalar LDS reads instead of ds_read_b64_tr_b16
     const bool tr = !no_tr;
     bool big = lq >= 2048 && d != 160; // two query tiles per wave once there is enough work to fill the chip
-    if (const char* e = std::getenv("SDOD_ATTN_QT")) big = e[0] == '2' && d != 160; // developer override (tools/attn_bench.py)
+    // developer override (tools/attn_bench.py), read on EVERY call: tests/test_attention_paths_gpu.py relies on that to run the
+    // two-query-tile kernels (SDOD_ATTN_QT=2) at small shapes and the one-tile kernels (=1) on the same data
+    if (const char* e = std::getenv("SDOD_ATTN_QT")) big = e[0] == '2' && d != 160;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
     switch (d) {
