@@ -14,7 +14,9 @@
  *                                                        TEMB graph's output: the time-MLP output pushed through every
  *                                                        ResBlock's emb_layers projection (all of it depends on t only,
  *                                                        so it is computed once per step and cached like context.cpp:276-278)
- *                 in2 ctx  fp16 [B][77][ctx_dim]         (context.cpp:216  p_cond / p_uncond = input(2))
+ *                 in2 ctx  fp16 [B][context_len][ctx_dim]  (context.cpp:216  p_cond / p_uncond = input(2)); context_len = 77 k
+ *                                                        for a prompt of k text-encoder chunks concatenated along the key axis
+ *                                                        (sdod_context_assemble_f16)
  *                 in3 cond fp32 NCHW [B][concat_channels][H][W]  only with sdod_model_config.concat_channels > 0 (an inpainting
  *                                                        checkpoint, ldm `c_concat`): mask (1) | latent of the masked image (4),
  *                                                        read by the input convolution next to in0; constant over a sampler run
@@ -60,7 +62,9 @@ typedef struct sdod_model_config {
     int latent_w;
     int model_channels;  /* 320 */
     int context_dim;     /* 768 (SD1.x), 1024 (SD2.x) */
-    int context_len;     /* 77 */
+    int context_len;     /* 77: the text encoder's positions (its position table is [context_len][ctx_dim]) and the UNet's
+                          * cross-attention keys.  A UNET graph takes any length >= 1 (77 k for k prompt chunks); above 80 keys
+                          * its transformer blocks run the three-launch cross-attention instead of the folded form */
     int num_heads;       /* 8 (SD1.x: head dim = C/8); 0 = use head_dim */
     int head_dim;        /* 64 (SD2.x); ignored when num_heads > 0 */
     int vocab_size;      /* 49408 */

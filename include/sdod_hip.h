@@ -321,6 +321,18 @@ SDOD_API int sdod_latent_prep_f16(const float* x, const float* w, const float* b
 SDOD_API int sdod_nhwc_f16_to_nchw_f32(const void* x, float* y, int n, int c, int hw, void* stream);
 SDOD_API int sdod_embedding_f16(const int32_t* ids, const void* table, const void* pos, void* y, int rows, int seq,
                                 int c, void* stream);
+/* Long, weighted prompts: the cross-attention context of P prompts from their K text-encoder chunks, in one launch.
+ * enc fp16 [P][K][T][D] (the text encoder's rows, chunk after chunk) -> out fp16 [P][K*T][D]: the same memory order, so the
+ * concatenation along the key axis is the layout itself and the kernel only applies the per-token emphasis w fp32 [P][K][T].
+ * Per (prompt, chunk), in fp32 on the fp16 values:  s0 = sum x,  s1 = sum fl(x * w[t])  over the chunk's T * D values,
+ * r = s0 / s1,  out = fp16(fl(fl(x * w[t]) * r)) -- scale the token rows, then restore the chunk's mean (the rule of the common
+ * web front ends, applied per chunk).  Guard: r = 1 when s1 == 0 or r is not finite (a chunk whose weights are all zero comes out
+ * as zeros, a weighted sum that cancels leaves the weighted rows unrestored) -- never NaN or inf from finite input.
+ * Deterministic: both sums are taken in one fixed order, so all-ones weights give s0 == s1 and out == enc bit for bit.
+ * w == NULL: a plain copy, no sums.  One workgroup per (prompt, chunk), 16-byte lanes.
+ * Errors, returned before any device call: NULL enc / out; P, K or T < 1; D % 8 != 0; enc or out not 16-byte aligned; out
+ * overlapping enc. */
+SDOD_API int sdod_context_assemble_f16(const void* enc, const float* w, void* out, int P, int K, int T, int D, void* stream);
 /* context.cpp:257-274: out[i][j]=cos(t_i*f_j), out[i][half+j]=sin(t_i*f_j), f_j=exp(-ln(1e4)*j/half); fp16 out */
 SDOD_API int sdod_timestep_features_f16(const float* t, void* y, int n, int dim, void* stream);
 

@@ -313,6 +313,60 @@ __global__ void embedding_kernel(const int32_t* ids, const f16* table, const f16
     }
 }
 
+// Prompt emphasis on the text encoder's output (sdod_context_assemble_f16): one workgroup per (prompt, chunk) of T rows x D
+// columns.  Pass 1 sums the chunk before (s0) and after (s1) the per-row weights, pass 2 re-reads it (118 KB at 77 x 768: L2) and
+// writes fp16(fl(fl(x w) r)) with r = s0 / s1.  The order of every addition is fixed by the shape alone and is the same for both
+// sums -- a thread adds the 16-byte lanes tid, tid + 256, .. into eight accumulators (one per half of the lane), folds those as
+// ((0+1)+(2+3))+((4+5)+(6+7)), then the wave butterfly, then the four wave results left to right -- so all-ones weights give
+// s0 == s1 bit for bit, r == 1 and out == enc.  w == NULL: a copy, no sums.
+__global__ __launch_bounds__(256) void context_assemble_kernel(const f16* enc, const float* w, f16* out, int T, int D) {
+    __shared__ float red[8];
+    const int cp = D / 8;
+    const int lanes = T * cp; // 16-byte lanes of the chunk
+    const f16* x = enc + (size_t)blockIdx.x * T * D;
+    f16* y = out + (size_t)blockIdx.x * T * D;
+    if (w == nullptr) {
+        for (int i = threadIdx.x; i < lanes; i += 256) stg8(y + (size_t)i * 8, ldg8(x + (size_t)i * 8));
+        return;
+    }
+    const float* wr = w + (size_t)blockIdx.x * T;
+    float a0[8], a1[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a0[e] = a1[e] = 0.f;
+    for (int i = threadIdx.x; i < lanes; i += 256) {
+        const f16x8 v = ldg8(x + (size_t)i * 8);
+        const float wt = wr[i / cp];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            a0[e] = add_rn(a0[e], (float)v[e]);
+            a1[e] = add_rn(a1[e], mul_rn((float)v[e], wt));
+        }
+    }
+    float s0 = add_rn(add_rn(add_rn(a0[0], a0[1]), add_rn(a0[2], a0[3])), add_rn(add_rn(a0[4], a0[5]), add_rn(a0[6], a0[7])));
+    float s1 = add_rn(add_rn(add_rn(a1[0], a1[1]), add_rn(a1[2], a1[3])), add_rn(add_rn(a1[4], a1[5]), add_rn(a1[6], a1[7])));
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = s0;
+        red[4 + (threadIdx.x >> 6)] = s1;
+    }
+    __syncthreads();
+    s0 = add_rn(add_rn(add_rn(red[0], red[1]), red[2]), red[3]);
+    s1 = add_rn(add_rn(add_rn(red[4], red[5]), red[6]), red[7]);
+    // the guard: a chunk whose weighted sum is zero (all weights zero, or exact cancellation) or whose ratio overflows keeps its
+    // weighted values as they are instead of becoming NaN / inf
+    float r = div_rn(s0, s1);
+    if (s1 == 0.f || !(fabsf(r) <= 3.4028234664e38f)) r = 1.0f;
+    for (int i = threadIdx.x; i < lanes; i += 256) {
+        const f16x8 v = ldg8(x + (size_t)i * 8);
+        const float wt = wr[i / cp];
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (f16)mul_rn(mul_rn((float)v[e], wt), r);
+        stg8(y + (size_t)i * 8, o);
+    }
+}
+
 __global__ void timestep_features_kernel(const float* t, f16* y, int n, int dim) {
     const int half = dim / 2;
     const size_t total = (size_t)n * half;
@@ -968,6 +1022,22 @@ extern "C" int sdod_embedding_f16(const int32_t* ids, const void* table, const v
     SDOD_TRY
     SDOD_REQUIRE(ids && table && pos && y && rows > 0 && seq > 0 && c % 8 == 0, "bad argument");
     LAUNCH(embedding_kernel, (size_t)rows * (c / 8), stream, ids, (const f16*)table, (const f16*)pos, (f16*)y, rows, seq, c);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_context_assemble_f16(const void* enc, const float* w, void* out, int P, int K, int T, int D, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(enc && out, "null pointer");
+    SDOD_REQUIRE(P >= 1 && K >= 1 && T >= 1, "P, K and T must be at least 1");
+    SDOD_REQUIRE(D >= 8 && D % 8 == 0, "D must be a positive multiple of 8 (16-byte lanes)");
+    SDOD_REQUIRE((long long)P * K <= 0x7fffffffLL && (long long)T * D <= 0x7fffffffLL, "shape too large");
+    SDOD_REQUIRE((((uintptr_t)enc | (uintptr_t)out) & 15) == 0, "enc and out must be 16-byte aligned");
+    const size_t bytes = (size_t)P * K * T * D * sizeof(f16);
+    const uintptr_t a = (uintptr_t)enc, b = (uintptr_t)out;
+    SDOD_REQUIRE(a + bytes <= b || b + bytes <= a, "out must not alias enc (the chunk is read twice)");
+    SDOD_LAUNCH(context_assemble_kernel, dim3(P * K), dim3(256), 0, (hipStream_t)stream, (const f16*)enc, w, (f16*)out, T, D);
+    SDOD_HIP_CHECK(hipGetLastError());
     return 0;
     SDOD_CATCH
 }

@@ -46,6 +46,7 @@ Graph::Graph(int kind, const sdod_model_config& cfg, int batch) : kind_(kind), c
     SDOD_REQUIRE(batch > 0 && batch <= 64, "batch must be in [1, 64]");
     SDOD_REQUIRE(cfg.model_channels > 0 && cfg.model_channels % 64 == 0, "model_channels must be a multiple of 64");
     SDOD_REQUIRE(cfg.context_dim % 64 == 0, "context_dim must be a multiple of 64");
+    SDOD_REQUIRE(cfg.context_len >= 1 && cfg.context_len <= 4096, "context_len must be in [1, 4096]");
     SDOD_REQUIRE(cfg.concat_channels >= 0, "concat_channels must not be negative");
     mode_ = DECLARE;
     arena_reset();

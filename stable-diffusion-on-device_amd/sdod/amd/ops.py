@@ -512,6 +512,29 @@ def embedding(ids, table, pos):
     return out
 
 
+def context_assemble(enc, weights=None, out=None):
+    """enc fp16 [P, K, T, D] (the text encoder's output per prompt and 75-token chunk), weights fp32 [P, K, T] or None -> the
+    cross-attention context fp16 [P, K*T, D]: token rows scaled by their emphasis, each chunk's mean restored (include/sdod_hip.h:
+    sdod_context_assemble_f16).  weights None: a copy."""
+    lib = _lib.hip()
+    _req(enc, torch.float16, 'enc')
+    if enc.dim() != 4:
+        raise ValueError(f'enc must be [P, K, T, D], got {tuple(enc.shape)}')
+    p, k, t, d = enc.shape
+    if weights is not None:
+        _req(weights, torch.float32, 'weights')
+        if tuple(weights.shape) != (p, k, t):
+            raise ValueError(f'weights must be {(p, k, t)}, got {tuple(weights.shape)}')
+    if out is None:
+        out = torch.empty((p, k * t, d), dtype=torch.float16, device=enc.device)
+    else:
+        _req(out, torch.float16, 'out')
+        if tuple(out.shape) != (p, k * t, d):
+            raise ValueError(f'out must be {(p, k * t, d)}, got {tuple(out.shape)}')
+    check(lib.sdod_context_assemble_f16(_p(enc), _p(weights), _p(out), p, k, t, d, _stream()))
+    return out
+
+
 def timestep_features(t, dim=320):
     lib = _lib.hip()
     _req(t, torch.float32, 't')

@@ -10,6 +10,7 @@ import torch
 
 from . import engine as E
 from . import ops
+from . import prompts as PR
 from .host import DpmSolver
 from .samplers import K_SAMPLERS, K_SCHEDULES, PLMS_ORDERS, KSchedule, PlmsSchedule
 
@@ -21,10 +22,14 @@ class Txt2Img:
     encoder = None
     masked_encoder = None
     _traj = None        # {key: (graph, static inputs, output)} of _graphed, created with its first entry
+    prompt_chunks = 1
+    model = 'sd14'
+    tokenizer = None
+    text = None
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
-                 with_vae_encoder=False, inpaint_unet=False):
+                 with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -33,7 +38,13 @@ class Txt2Img:
         off, nothing of it is constructed or loaded.
         inpaint_unet=True: the UNet checkpoint is an inpainting one (`input_blocks.0.0.weight` [320, 9, 3, 3]): the UNet graph gets its
         conditioning input (unet.cond) and the masked VAE encoder is built (state_dicts['vae_enc'] or models_dir/vae_encoder.sdodw) for
-        inpaint_concat(); off, nothing of either exists."""
+        inpaint_concat(); off, nothing of either exists.
+        prompt_chunks=k in [1, 4]: prompts of up to k chunks of 75 tokens (sdod/amd/prompts.py).  The UNet is built on a copy of the
+        config with context_len = 77 k -- its transformer blocks then take the three-launch cross-attention, the folded form stops
+        at 80 keys -- and the text encoder with batch 2 k, so one execute encodes every chunk of both prompts; every ctx2 of this
+        pipeline is [2, 77 k, D].  At 1 nothing is constructed or sized differently.  Anything else raises ValueError before any
+        device work."""
+        self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self.n = images_per_gpu
@@ -69,9 +80,13 @@ class Txt2Img:
             self._pair_staged = dist.get_backend() == 'gloo'         # gloo gathers on the host (rehearsals); RCCL on device
         self.use_hip_graph = use_hip_graph
         self.tokenizer = tokenizer
-        self.unet = E.UNet(self.cfg, self.n if cfg_split else 2 * self.n, device)
+        unet_cfg = self.cfg
+        if self.prompt_chunks > 1:       # the text encoder keeps 77 (its position table); only the UNet sees the longer context
+            unet_cfg = E.ModelConfig.from_buffer_copy(self.cfg)
+            unet_cfg.context_len = PR.CHUNK_LEN * self.prompt_chunks
+        self.unet = E.UNet(unet_cfg, self.n if cfg_split else 2 * self.n, device)
         self.vae = E.VaeDecoder(self.cfg, 1, device) if with_vae else None
-        self.text = E.TextEncoder(self.cfg, 2, device) if with_text_encoder else None
+        self.text = E.TextEncoder(self.cfg, 2 * self.prompt_chunks, device) if with_text_encoder else None
         self.encoder = E.VaeEncoder(self.cfg, 1, device) if with_vae_encoder else None
         self.masked_encoder = E.MaskedVaeEncoder(self.cfg, 1, device) if self.inpaint_unet else None
         self._temb_graphs = {}
@@ -94,14 +109,81 @@ class Txt2Img:
 
     # ------------------------------------------------------------------ conditioning
     def encode_tokens(self, ids_uncond, ids_cond):
-        """ids: int arrays [77]; returns fp16 [2, 77, 768] = (uncond, cond), computed on this GPU"""
+        """ids: int arrays [77]; returns fp16 [2, 77 * prompt_chunks, D] = (uncond, cond), computed on this GPU.  With prompt_chunks
+        > 1 both are padded with empty chunks (SOT, EOT, the model's padding) through encode_chunks."""
+        if self.prompt_chunks > 1:
+            return self.encode_chunks(self._pad_ids(ids_uncond), self._pad_ids(ids_cond))
         ids = torch.from_numpy(np.stack([np.asarray(ids_uncond), np.asarray(ids_cond)]).astype(np.int32))
         self.text.ids.copy_(ids)
         self.text.execute(self.use_hip_graph)
         return self.text.out.clone()
 
     def encode_prompt(self, prompt, negative=''):
+        """the prompt as CLIP's one window: cut at 75 tokens and read literally (no emphasis grammar); encode_prompt_weighted is the
+        long, weighted form"""
         return self.encode_tokens(self._ids(negative), self._ids(prompt))
+
+    @property
+    def _pad(self):
+        """prompts.chunk_prompt's padding rule for this model (see _ids)"""
+        return 'zero' if self.model == 'sd21' else 'eot'
+
+    def _pad_ids(self, ids):
+        """ids [77] -> [prompt_chunks, 77]: the empty chunks are SOT (the ids' first), EOT (their largest: EOT is the largest id of the
+        vocabulary and every window holds one), then the model's padding"""
+        ids = np.asarray(ids).astype(np.int64).reshape(1, -1)
+        if ids.shape[1] != PR.CHUNK_LEN:
+            raise ValueError(f'ids must be [{PR.CHUNK_LEN}], got {ids.shape[1:]}')
+        empty = np.full((1, PR.CHUNK_LEN), 0 if self._pad == 'zero' else ids.max(), np.int64)
+        empty[0, 0], empty[0, 1] = ids[0, 0], ids.max()
+        return np.concatenate([ids] + [empty] * (self.prompt_chunks - 1))
+
+    def encode_chunks(self, ids_uncond, ids_cond, weights=None):
+        """ids_uncond, ids_cond: integer arrays [prompt_chunks, 77] (prompts.chunk_prompt / pad_chunks); weights: fp32
+        [2, prompt_chunks, 77] (numpy or torch), uncond first, or None.  Returns the context fp16 [2, 77 * prompt_chunks, D].  ONE
+        text-encoder execute on the ids laid out as (uncond chunks ; cond chunks): its output [2 k, 77, D] already is the
+        concatenation along the key axis.  With weights one more launch, ops.context_assemble (token rows scaled, each chunk's mean
+        restored); without, none.  Shape or dtype errors raise ValueError before any device work."""
+        k = self.prompt_chunks
+        both = []
+        for name, ids in (('ids_uncond', ids_uncond), ('ids_cond', ids_cond)):
+            ids = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+            if ids.dtype.kind not in 'iu':
+                raise ValueError(f'{name} must be an integer array, got {ids.dtype}')
+            if ids.shape != (k, PR.CHUNK_LEN):
+                raise ValueError(f'{name} must be {(k, PR.CHUNK_LEN)} (this pipeline was built with prompt_chunks={k}), got {ids.shape}')
+            vocab = getattr(getattr(self, 'cfg', None), 'vocab_size', None)
+            if ids.min() < 0 or (vocab is not None and ids.max() >= vocab):
+                raise ValueError(f'{name} holds ids outside the vocabulary [0, {vocab})')
+            both.append(ids.astype(np.int32))
+        if weights is not None:
+            if isinstance(weights, np.ndarray):
+                weights = torch.from_numpy(weights)
+            if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != (2, k, PR.CHUNK_LEN):
+                raise ValueError(f'weights must be fp32 {(2, k, PR.CHUNK_LEN)} (uncond first), got '
+                                 f'{tuple(getattr(weights, "shape", ()))} {getattr(weights, "dtype", type(weights))}')
+            if not bool(torch.isfinite(weights).all()):
+                raise ValueError('weights must be finite')
+        if self.text is None:
+            raise RuntimeError('Txt2Img(..., with_text_encoder=True) is needed to encode prompts')
+        self.text.ids.copy_(torch.from_numpy(np.concatenate(both)))
+        self.text.execute(self.use_hip_graph)
+        d = self.text.out.shape[-1]
+        if weights is None:
+            return self.text.out.reshape(2, k * PR.CHUNK_LEN, d).clone()
+        return ops.context_assemble(self.text.out.view(2, k, PR.CHUNK_LEN, d), weights.to(self.device).contiguous())
+
+    def encode_prompt_weighted(self, prompt, negative='', emphasis=True):
+        """prompt and negative through prompts.chunk_prompt (emphasis grammar, 75-token chunks, this model's padding rule), both padded
+        to prompt_chunks with empty chunks, then encode_chunks with the weights.  emphasis=False: the texts are literal, all weights 1
+        (still chunked).  ValueError when either text needs more chunks than the pipeline was built with."""
+        if self.tokenizer is None:
+            raise ValueError('encode_prompt_weighted needs the pipeline\'s tokenizer (Txt2Img(..., tokenizer=host.Tokenizer(path)))')
+        ids, ws = [], []
+        for text in (negative, prompt):
+            i, w = PR.pad_chunks(*PR.chunk_prompt(self.tokenizer, text, self._pad, emphasis), self.prompt_chunks, self.tokenizer, self._pad)
+            ids.append(i); ws.append(w)
+        return self.encode_chunks(ids[0], ids[1], np.stack(ws))
 
     def _ids(self, text):
         """token ids [77]: SOT, tokens, EOT, padding.  CLIP (SD1.x) pads with EOT, as the reference's tokenizer does
@@ -645,6 +727,13 @@ def img2img_schedule(strength, steps):
     return PlmsSchedule(steps), t_enc
 
 
+def check_prompt_chunks(prompt_chunks):
+    """Txt2Img's prompt_chunks: an integer in [1, 4] (77 to 308 keys in the UNet's cross-attention); returns it, raises ValueError"""
+    if isinstance(prompt_chunks, bool) or not isinstance(prompt_chunks, (int, np.integer)) or not 1 <= prompt_chunks <= 4:
+        raise ValueError(f'prompt_chunks must be an integer in [1, 4], got {prompt_chunks!r}')
+    return int(prompt_chunks)
+
+
 def k_check_args(sampler, steps, schedule, eta, step_noise, latent, n_images, first=0, old_samplers=False):
     """the argument contract of the k-diffusion samplers (Txt2Img.sample_k, generate, generate_graphed), checked on the host before any
     device work: sampler one of K_SAMPLERS (old_samplers=True: or 'plms' / 'dpm', which take schedule 'discrete' and no step_noise);
@@ -749,7 +838,8 @@ def inpaint_concat_check_args(init_u8, mask_u8, x_T, steps, sampler, noise, late
 
 
 def broadcast_conditioning(ctx2, src=0):
-    """the one collective of the path: CLIP output [2,77,768] fp16 (236,544 B) from rank `src` to every rank over RCCL"""
+    """the one collective of the path: the conditioning ctx2 fp16 [2, 77 * prompt_chunks, D] (236,544 B at one chunk of SD 1.x) from
+    rank `src` to every rank over RCCL"""
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():
         dist.broadcast(ctx2, src=src)
