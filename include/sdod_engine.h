@@ -139,6 +139,28 @@ SDOD_API int sdod_graph_stats(void* graph, size_t* weight_bytes, size_t* arena_b
  * processes); table_path receives the path(s) consulted */
 SDOD_API int sdod_graph_tune_info(void* graph, int* from_table, int* tuned_in_process, char* table_path, int cap);
 
+/* ---- LoRA adapters: low-rank updates W + scale * up . down merged into the weight arena in place.
+ * sdod_graph_keep_base (before sdod_graph_finalize): finalize keeps a second device copy of the weight arena as it is after every
+ * parameter is set and BEFORE LayerNorm weights are folded in and Linear pairs composed -- what a delta has to be added to.
+ * sdod_graph_base_bytes reports its size, 0 when the base was not kept (such a graph allocates nothing more than before). */
+SDOD_API int sdod_graph_keep_base(void* graph);
+SDOD_API int sdod_graph_base_bytes(void* graph, size_t* bytes);
+typedef struct {
+    const char* name; /* a conv / Linear weight of the graph (3x3 convolutions, 1x1 convolutions, Linear, the GEGLU projection) */
+    const void* up;   /* host, canonical layout: [out][rank] (a convolution's [out][rank][1][1]) */
+    const void* down; /* host, canonical layout: [rank][in] (a 3x3 convolution's [rank][cin][3][3]) */
+    int dtype;        /* SDOD_F16 or SDOD_F32 (rounded to fp16 on the host) */
+    int rank;         /* 1 .. 128 */
+    float scale;      /* strength * alpha / rank */
+} sdod_lora_entry;
+/* Restores the arena from the kept base, merges every entry on the device (sdod_lora_merge_f16 on the parameter's packed location;
+ * entries naming the same parameter accumulate in the order given), re-runs the folds and compositions of finalize and marks the
+ * static launches stale: the next sdod_graph_execute ignores SDOD_EXEC_STATIC_UNCHANGED once.  No address changes: the launch list
+ * and a captured hipGraph stay valid.  count = 0 restores the base model bit for bit.  Every entry is validated first (finalized
+ * graph with a kept base and weight_quant = 0, known parameter of a supported kind, rank, finite scale): on a failure the arena is
+ * untouched.  Synchronises `stream` before it returns. */
+SDOD_API int sdod_graph_set_loras(void* graph, const sdod_lora_entry* entries, int count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,18 @@ SDOD_API int sdod_ln_fold_f16(void* w, int n, int k, int ldw, const float* gamma
  * p or w.  The UNet uses it for transformer_blocks.0.ff.net.2 -> proj_out (analyze_results.py:69-79 lists them as two ops). */
 SDOD_API int sdod_compose_linear_f16(const void* p, int ldp, const void* w, int ldw, void* c, int ldc, int n_out, int n_mid, int k,
                                      const float* bias_w, const float* bias_p, float* bias_out, void* stream);
+/* Low-rank (LoRA) update of a packed fp16 weight matrix, in place:
+ *   W'[row(o)][col(j)] = fp16(float(W[row(o)][col(j)]) + scale * sum_r up[o][r] * down[r][j])     (fp32 accumulate, one rounding)
+ * w: fp16 [n][ldw], k <= ldw columns of it (a column block of a wider row: nothing outside the k columns is written); up: fp16
+ * [n][rank], down: fp16 [rank][k], both in CANONICAL PyTorch order (a 3x3 convolution: down = [rank][cin][3][3] flattened, up the
+ * [n][rank][1][1] factor).  row() is the identity or, with geglu != 0, the 16-row value / gate interleave of a fused-GEGLU
+ * projection (n % 32 == 0); col() is the identity or, with conv_cin > 0 (k = 9 conv_cin, conv_cin % 8 == 0), the KRSC order
+ * j = c * 9 + t -> t * conv_cin + c: the packings of the graph engine (sdod_graph_param_device).  rank in [1, 128] (any value:
+ * staged zero-padded to the MFMA K step), n >= 1, k % 8 == 0, ldw % 8 == 0, w 16-byte aligned, scale finite (it already holds
+ * strength * alpha / rank); anything else is INVALID_ARGUMENT before any device call.  Deterministic (no atomics, fixed
+ * summation order); scale = 0 leaves W bit-identical. */
+SDOD_API int sdod_lora_merge_f16(void* w, int n, int k, int ldw, const void* up, const void* down, int rank, float scale,
+                                 int conv_cin, int geglu, void* stream);
 /* LayerNorm over the last dim of fp16 [M][C] rows, fp32 weight/bias (either may be NULL); C % 8 == 0, C <= 3072. */
 SDOD_API int sdod_layer_norm_f16(const void* x, void* y, const float* weight, const float* bias, int m, int c,
                                  float eps, void* stream);

@@ -74,6 +74,11 @@ public:
     void set_param(const std::string& name, const void* data, int dtype, const int64_t* shape, int ndim);
     void load_file(const std::string& path, const std::string& prefix);
     void finalize();
+    // LoRA adapters (include/sdod_engine.h): keep_base() before finalize() retains the pre-fold arena, set_loras() rebuilds the
+    // arena from it -- restore, merge each entry into its packed location, fold and compose again -- without moving a pointer
+    void keep_base();
+    size_t base_bytes() const { return base_copy_ ? weight_bytes_ : 0; }
+    void set_loras(const sdod_lora_entry* entries, int count, hipStream_t st);
     // skip_static: the inputs marked "static across a sampler run" (UNet: the text context) are unchanged since the
     // previous execute(), so the launches that depend only on them (all cross-attention K/V projections) are skipped
     void execute(hipStream_t st, bool use_hip_graph, bool skip_static = false);
@@ -217,6 +222,10 @@ private:
         float* bias_out;
     };
     std::vector<ComposeJob> compose_jobs_;
+    void run_folds(hipStream_t st); // fold_jobs_ then compose_jobs_ on the arena as set_param left it (finalize, set_loras)
+    bool keep_base_ = false;
+    char* base_copy_ = nullptr;     // the arena before run_folds(), weight_bytes_ long (keep_base())
+    bool static_stale_ = false;     // weights changed under static_ops_' results: execute() runs them whatever skip_static says
     std::vector<void*> derived_; // device buffers created at build time (folded LayerNorm vectors)
     void emit_gemm(sdod_gemm_desc d);
     // out[rows][N] = x[rows][K] . W^T ; W is params_[w] (or a raw fp16 [N][K] pointer through *_raw)

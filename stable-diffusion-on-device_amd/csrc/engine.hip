@@ -65,6 +65,7 @@ Graph::~Graph() {
     for (auto& s : inputs_) (void)hipFree(s.ptr);
     for (auto& s : outputs_) (void)hipFree(s.ptr);
     (void)hipFree(weight_base_);
+    (void)hipFree(base_copy_);
     (void)hipFree(qscale_);
     (void)hipFree(qoff_);
     (void)hipFree(arena_base_);
@@ -1002,25 +1003,125 @@ void Graph::finalize() {
     compose_jobs_.clear();
     flops_ = 0;
     build();
-    for (const FoldJob& j : fold_jobs_)
-        check_rc(sdod_ln_fold_f16(j.w, j.n, j.k, j.ldw, j.gamma, j.beta, j.bias_in, j.s, j.t, nullptr));
-    for (const ComposeJob& j : compose_jobs_) {
-        // P . W needs every row of W for every output row: compose from a copy of the W block
-        f16* tmp = nullptr;
-        SDOD_HIP_CHECK(hipMalloc((void**)&tmp, (size_t)j.n_mid * j.k * sizeof(f16)));
-        SDOD_HIP_CHECK(hipMemcpy2D(tmp, (size_t)j.k * sizeof(f16), j.c, (size_t)j.ld * sizeof(f16), (size_t)j.k * sizeof(f16), (size_t)j.n_mid,
-                                   hipMemcpyDeviceToDevice));
-        const int rc = sdod_compose_linear_f16(j.p, j.ld, tmp, j.k, j.c, j.ld, j.n_out, j.n_mid, j.k, j.bias_w, j.bias_p, j.bias_out, nullptr);
-        SDOD_HIP_CHECK(hipDeviceSynchronize());
-        (void)hipFree(tmp);
-        check_rc(rc);
+    if (keep_base_) { // every parameter is set and none is folded yet: the image a LoRA delta is added to (set_loras)
+        SDOD_HIP_CHECK(hipMalloc((void**)&base_copy_, weight_bytes_));
+        SDOD_HIP_CHECK(hipMemcpy(base_copy_, weight_base_, weight_bytes_, hipMemcpyDeviceToDevice));
     }
+    run_folds(nullptr);
     SDOD_HIP_CHECK(hipDeviceSynchronize());
     if (tune_scratch()) {
         (void)hipFree(tune_scratch());
         tune_scratch() = nullptr;
     }
     finalized_ = true;
+}
+
+void Graph::run_folds(hipStream_t st) {
+    for (const FoldJob& j : fold_jobs_)
+        check_rc(sdod_ln_fold_f16(j.w, j.n, j.k, j.ldw, j.gamma, j.beta, j.bias_in, j.s, j.t, st));
+    for (const ComposeJob& j : compose_jobs_) {
+        // P . W needs every row of W for every output row: compose from a copy of the W block
+        f16* tmp = nullptr;
+        SDOD_HIP_CHECK(hipMalloc((void**)&tmp, (size_t)j.n_mid * j.k * sizeof(f16)));
+        int rc = 0;
+        hipError_t e = hipMemcpy2DAsync(tmp, (size_t)j.k * sizeof(f16), j.c, (size_t)j.ld * sizeof(f16), (size_t)j.k * sizeof(f16), (size_t)j.n_mid,
+                                        hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) rc = sdod_compose_linear_f16(j.p, j.ld, tmp, j.k, j.c, j.ld, j.n_out, j.n_mid, j.k, j.bias_w, j.bias_p, j.bias_out, st);
+        const hipError_t e2 = hipStreamSynchronize(st);
+        (void)hipFree(tmp);
+        SDOD_HIP_CHECK(e);
+        SDOD_HIP_CHECK(e2);
+        check_rc(rc);
+    }
+}
+
+// ------------------------------------------------------------------------------------------ LoRA adapters
+// What a graph derives from its weights, and therefore what set_loras() has to redo after the arena changed:
+//   * in the arena itself, by finalize(): LayerNorm gamma multiplied into the consuming Linear (fold_jobs_) and
+//     ff.net.2 -> proj_out / conv_out -> quant_conv composed into one matrix (compose_jobs_), each with derived fp32 vectors
+//     (s, t, composed bias) in buffers of their own -- run_folds() rewrites all of them from the pre-fold arena;
+//   * once per prompt, by static_ops_: the cross-attention K / V projections (kv_all_) and the folded cross-attention's
+//     W1 / W2 / s1 / t1 (sdod_xattn_fold_f16 reads to_q and to_out) -- static_stale_ makes the next execute() run them.
+// Nothing else reads weights outside the launches themselves: the tuner's picks depend on shapes only, and the uint8 scale /
+// offset rows belong to graphs that are refused here.
+void Graph::keep_base() {
+    SDOD_REQUIRE(!finalized_, "keep_base() must be called before finalize()");
+    keep_base_ = true;
+}
+
+void Graph::set_loras(const sdod_lora_entry* entries, int count, hipStream_t st) {
+    SDOD_REQUIRE(count >= 0 && (count == 0 || entries != nullptr), "bad entry list");
+    SDOD_REQUIRE(finalized_, "graph not finalized");
+    SDOD_REQUIRE(base_copy_ != nullptr, "the graph was finalized without keep_base(): merge on the host and rebuild it");
+    SDOD_REQUIRE(cfg_.weight_quant == 0, "LoRA adapters need fp16 weights (weight_quant = 0): integer codes cannot take a delta");
+    struct Merge {
+        f16* w;
+        int n, k, ldw, cin, geglu, rank;
+        size_t up_off, down_off; // halves into the staging buffer
+        float scale;
+    };
+    std::vector<Merge> merges;
+    size_t halves = 0;
+    for (int i = 0; i < count; ++i) {
+        const sdod_lora_entry& e = entries[i];
+        SDOD_REQUIRE(e.name != nullptr, "entry " + std::to_string(i) + ": null name");
+        const std::string name = e.name;
+        auto it = pindex_.find(name);
+        SDOD_REQUIRE(it != pindex_.end(), "unknown parameter '" + name + "'");
+        const Param& p = params_[it->second];
+        SDOD_REQUIRE(p.kind == PK_LINEAR || p.kind == PK_CONV1 || p.kind == PK_LINEAR_GEGLU || p.kind == PK_CONV3,
+                     "'" + name + "' is not a LoRA target (3x3 / 1x1 convolution, Linear or GEGLU projection weights only)");
+        SDOD_REQUIRE(!p.quant, "'" + name + "' is kept as uint8 codes");
+        SDOD_REQUIRE(e.dtype == SDOD_F16 || e.dtype == SDOD_F32, "'" + name + "': dtype must be SDOD_F16 or SDOD_F32");
+        SDOD_REQUIRE(e.up != nullptr && e.down != nullptr, "'" + name + "': null factor");
+        SDOD_REQUIRE(e.rank >= 1 && e.rank <= 128, "'" + name + "': rank must be in [1, 128]");
+        Merge m{};
+        m.w = reinterpret_cast<f16*>(p.dev);
+        m.n = (int)p.shape[0];
+        m.cin = p.kind == PK_CONV3 ? (int)p.shape[1] : 0;
+        m.k = p.kind == PK_CONV3 ? 9 * (int)p.shape[1] : (int)p.shape[1];
+        m.ldw = p.ld > 0 ? p.ld : m.k;
+        m.geglu = p.kind == PK_LINEAR_GEGLU ? 1 : 0;
+        m.rank = e.rank;
+        m.scale = e.scale;
+        m.up_off = halves;
+        halves += align_up((size_t)m.n * m.rank, 8); // every factor starts on a 16-byte boundary
+        m.down_off = halves;
+        halves += align_up((size_t)m.rank * m.k, 8);
+        try {
+            lora_merge_require(m.w, m.n, m.k, m.ldw, e.up, e.down, m.rank, m.scale, m.cin, m.geglu);
+        } catch (const Error& err) {
+            throw Error(err.code, "'" + name + "': " + err.what());
+        }
+        merges.push_back(m);
+    }
+    // fp16 image of every factor, one upload
+    std::vector<f16> host(halves, (f16)0.0f);
+    for (int i = 0; i < count; ++i) {
+        const Merge& m = merges[i];
+        auto put = [&](const void* src, size_t off, size_t cnt) {
+            f16* dst = host.data() + off;
+            if (entries[i].dtype == SDOD_F16) std::memcpy(dst, src, cnt * sizeof(f16));
+            else
+                for (size_t j = 0; j < cnt; ++j) dst[j] = (f16) static_cast<const float*>(src)[j];
+        };
+        put(entries[i].up, m.up_off, (size_t)m.n * m.rank);
+        put(entries[i].down, m.down_off, (size_t)m.rank * m.k);
+    }
+    struct Staging { // freed on every exit path
+        f16* p = nullptr;
+        ~Staging() { (void)hipFree(p); }
+    } dev;
+    if (halves) {
+        SDOD_HIP_CHECK(hipMalloc((void**)&dev.p, halves * sizeof(f16)));
+        SDOD_HIP_CHECK(hipMemcpy(dev.p, host.data(), halves * sizeof(f16), hipMemcpyHostToDevice));
+    }
+    SDOD_HIP_CHECK(hipMemcpyAsync(weight_base_, base_copy_, weight_bytes_, hipMemcpyDeviceToDevice, st));
+    static_stale_ = true; // from here on the arena no longer matches what the static launches last saw
+    for (const Merge& m : merges)
+        check_rc(sdod_lora_merge_f16(m.w, m.n, m.k, m.ldw, dev.p + m.up_off, dev.p + m.down_off, m.rank, m.scale, m.cin, m.geglu, st));
+    run_folds(st);
+    SDOD_HIP_CHECK(hipStreamSynchronize(st));
 }
 
 // ---- weight prefetch.  Inside a replay every weight matrix comes from HBM (1.7 GB of weights sweep the 256 MiB Infinity Cache
@@ -1084,8 +1185,10 @@ void Graph::check_health() const {
 void Graph::execute(hipStream_t st, bool use_hip_graph, bool skip_static) {
     SDOD_REQUIRE(finalized_, "graph not finalized");
     check_health();
-    if (!skip_static || eager_runs_ == 0)
+    if (!skip_static || eager_runs_ == 0 || static_stale_) {
         for (auto& op : static_ops_) op.fn(st);
+        static_stale_ = false;
+    }
     if (!use_hip_graph || eager_runs_ == 0) {
         // the first run is always eager: it sets kernel attributes (dynamic LDS sizes), which must not happen in capture
         run_ops(st);
@@ -1351,6 +1454,30 @@ extern "C" int sdod_graph_tune_info(void* graph, int* from_table, int* tuned_in_
         if (const char* extra = sdod::tune_cache_path()) s += (s.empty() ? "" : " + ") + std::string(extra);
         std::snprintf(table_path, (size_t)cap, "%s", s.c_str());
     }
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_keep_base(void* graph) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr, "null graph");
+    static_cast<Graph*>(graph)->keep_base();
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_base_bytes(void* graph, size_t* bytes) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr && bytes != nullptr, "null argument");
+    *bytes = static_cast<Graph*>(graph)->base_bytes();
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_set_loras(void* graph, const sdod_lora_entry* entries, int count, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr, "null graph");
+    static_cast<Graph*>(graph)->set_loras(entries, count, (hipStream_t)stream);
     return 0;
     SDOD_CATCH
 }

@@ -51,6 +51,11 @@ inline bool first_use_on_device(std::atomic<unsigned long long>& mask) {
 // The GEMM tiles the engine's tuner tries, ascending, read off gemm.hip's tile table: writes up to `cap` ids, returns how many there are.
 int gemm_tuner_tiles(int* out, int cap);
 
+// The argument checks of sdod_lora_merge_f16 (lora.hip), throwing INVALID_ARGUMENT: Graph::set_loras makes them for every entry
+// before it touches the weight arena.
+void lora_merge_require(const void* w, int n, int k, int ldw, const void* up, const void* down, int rank, float scale, int conv_cin,
+                        int geglu);
+
 } // namespace sdod
 
 #define SDOD_LAUNCH(kernel, grid, block, smem, stream, ...)                                                          \

@@ -20,10 +20,17 @@ class ModelConfig(ctypes.Structure):
         'concat_channels')]
 
 
+class LoraEntry(ctypes.Structure):
+    """mirror of `sdod_lora_entry`"""
+    _fields_ = [('name', ctypes.c_char_p), ('up', ctypes.c_void_p), ('down', ctypes.c_void_p), ('dtype', ctypes.c_int),
+                ('rank', ctypes.c_int), ('scale', ctypes.c_float)]
+
+
 ENGINE_SYMBOLS = [
     'sdod_model_config_sd14', 'sdod_model_config_sd21', 'sdod_graph_create', 'sdod_graph_destroy', 'sdod_graph_num_params', 'sdod_graph_param_info',
     'sdod_graph_set_param', 'sdod_graph_param_device', 'sdod_graph_load_file', 'sdod_graph_finalize', 'sdod_graph_io', 'sdod_graph_execute', 'sdod_graph_check',
     'sdod_graph_stats', 'sdod_graph_tune_info', 'sdod_graph_num_ops', 'sdod_graph_op_info', 'sdod_graph_op_detail', 'sdod_graph_profile',
+    'sdod_graph_keep_base', 'sdod_graph_base_bytes', 'sdod_graph_set_loras',
 ]
 
 
@@ -53,6 +60,9 @@ def _engine():
         lib.sdod_graph_op_info.argtypes = [P, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         lib.sdod_graph_profile.argtypes = [P, P, I, P, I]
         lib.sdod_graph_op_detail.argtypes = [P, I, ctypes.POINTER(ctypes.c_char_p)]
+        lib.sdod_graph_keep_base.argtypes = [P]
+        lib.sdod_graph_base_bytes.argtypes = [P, ctypes.POINTER(ctypes.c_size_t)]
+        lib.sdod_graph_set_loras.argtypes = [P, ctypes.POINTER(LoraEntry), I, P]
         lib._sdod_engine_typed = True
     return lib
 
@@ -156,6 +166,43 @@ class Graph:
             check(self._lib.sdod_graph_finalize(self._h))
         self.finalized = True
         return self
+
+    def keep_base(self):
+        """before finalize(): keep a second device copy of the weights as set, so that set_loras() can re-weight the graph in place
+        (costs base_bytes() of device memory)"""
+        check(self._lib.sdod_graph_keep_base(self._h))
+        return self
+
+    def base_bytes(self):
+        n = ctypes.c_size_t()
+        check(self._lib.sdod_graph_base_bytes(self._h, ctypes.byref(n)))
+        return n.value
+
+    def set_loras(self, entries):
+        """entries: [(param_name, up, down, scale)] with torch CPU tensors in canonical layout (up [out, rank] or [out, rank, 1, 1];
+        down [rank, in] or [rank, cin, kh, kw]).  The graph then computes with W + sum scale * up @ down for every named weight;
+        [] restores the base weights.  Pointers do not move: views, launch list and captured replays stay valid."""
+        shapes = None
+        keep, arr = [], (LoraEntry * max(len(entries), 1))()
+        for i, (name, up, down, scale) in enumerate(entries):
+            if not (torch.is_tensor(up) and torch.is_tensor(down)) or up.dim() < 2 or down.dim() < 2:
+                raise ValueError(f'{name}: up and down must be tensors of at least two dimensions')
+            if shapes is None:
+                shapes = dict(self.param_table())
+            dt = torch.float16 if up.dtype == torch.float16 and down.dtype == torch.float16 else torch.float32
+            up = up.detach().cpu().to(dt).contiguous()
+            down = down.detach().cpu().to(dt).contiguous()
+            rank = down.shape[0]
+            if len(shapes.get(name, ())) >= 2:   # (an unknown name or a vector is the library's to refuse)
+                shape = shapes[name]
+                fan_in = int(np.prod(shape[1:]))
+                if up.numel() != shape[0] * rank or up.shape[0] != shape[0] or down.numel() != rank * fan_in:
+                    raise ValueError(f'{name}: factors {tuple(up.shape)} x {tuple(down.shape)} do not give a {tuple(shape)} weight')
+            keep += [up, down]
+            arr[i] = LoraEntry(name.encode(), up.data_ptr(), down.data_ptr(), 1 if dt == torch.float32 else 0, rank, float(scale))
+        with self._on_device():
+            check(self._lib.sdod_graph_set_loras(self._h, arr, len(entries),
+                                                 ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if torch.cuda.is_available() else None)))
 
     def _io(self, is_out, idx):
         p = ctypes.c_void_p(); n = ctypes.c_size_t()

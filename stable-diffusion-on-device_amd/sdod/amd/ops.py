@@ -270,6 +270,27 @@ def ln_fold(w, gamma, beta, bias=None):
     return w, s, t
 
 
+def lora_merge(w, up, down, scale, *, ld=None, conv_cin=None, geglu=False):
+    """w += scale * up @ down in place on a PACKED fp16 weight matrix (sdod_lora_merge_f16): w is [n][ld] fp16 on the device, of
+    which k columns are updated (a 2-D view of a wider matrix brings its own row stride; ld overrides it); up [n, rank] and down
+    [rank, k] (a 3x3 convolution: [rank, cin, 3, 3]) are fp16 device tensors in canonical order.  conv_cin: w's columns are in
+    KRSC order (t * cin + c); geglu: w's rows carry the 16-row value / gate interleave.  Returns w."""
+    lib = _lib.hip()
+    for t, nme in ((w, 'w'), (up, 'up'), (down, 'down')):
+        if not t.is_cuda or t.dtype != torch.float16:
+            raise ValueError(f'{nme} must be an fp16 tensor on the GPU')
+    _req(up, torch.float16, 'up'); _req(down, torch.float16, 'down')
+    if up.dim() != 2 or w.stride(-1) != 1:
+        raise ValueError('up must be [n, rank] and the columns of w contiguous')
+    n, rank = up.shape
+    k = down.numel() // rank if rank else (down.shape[-1] if down.dim() > 1 else 0)
+    if ld is None:
+        ld = w.stride(0) if w.dim() == 2 and w.shape[0] > 1 else k
+    check(lib.sdod_lora_merge_f16(_p(w), n, k, int(ld), _p(up), _p(down), rank, float(scale), int(conv_cin or 0), 1 if geglu else 0,
+                                  _stream()))
+    return w
+
+
 def layer_norm(x, weight, bias, eps=1e-5, out=None):
     lib = _lib.hip()
     _req(x, torch.float16, 'x')

@@ -26,10 +26,11 @@ class Txt2Img:
     model = 'sd14'
     tokenizer = None
     text = None
+    _loras = False
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
-                 with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1):
+                 with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -43,7 +44,10 @@ class Txt2Img:
         config with context_len = 77 k -- its transformer blocks then take the three-launch cross-attention, the folded form stops
         at 80 keys -- and the text encoder with batch 2 k, so one execute encodes every chunk of both prompts; every ctx2 of this
         pipeline is [2, 77 k, D].  At 1 nothing is constructed or sized differently.  Anything else raises ValueError before any
-        device work."""
+        device work.
+        loras=True: the UNet and the text encoder keep a second device copy of their weights (Graph.keep_base: unet.base_bytes() +
+        text.base_bytes() more device memory) so that set_loras() can re-weight them in place; off, nothing is constructed or sized
+        differently."""
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
@@ -97,7 +101,10 @@ class Txt2Img:
             if g is None:
                 continue
             self._load(g, key, stem)
+            if loras and (g is self.unet or g is self.text):
+                g.keep_base()
             g.finalize()
+        self._loras = bool(loras)
         self._temb_cache = {}
         self._ctx_fresh = True
 
@@ -106,6 +113,48 @@ class Txt2Img:
             g.load_state_dict(self._sd[key])
         else:
             g.load_file(f'{self._dir}/{stem}.sdodw')
+
+    # ------------------------------------------------------------------ LoRA adapters
+    def set_loras(self, adapters, strict=True):
+        """adapters: [(path_or_dict, strength)] or [(path_or_dict, strength_unet, strength_text)] -- kohya-style LoRA files
+        (sdod/amd/lora.py: read_lora, map_key).  All of them are applied together, summed, to the base weights of the UNet and the text
+        encoder, in place on the device: every address, the launch lists and every captured graph (generate_graphed's trajectories
+        included: their first evaluation re-derives the cross-attention operands inside the capture) stay valid.  [] restores the base
+        model.  A context encoded BEFORE a text-encoder adapter was set or cleared is stale: encode the prompt again.
+        strict=False skips the modules the engine cannot adapt; their keys are returned.  RuntimeError when the pipeline was built
+        without loras=True; ValueError, before any device work, for a bad strength, uint8 weights, or text-encoder modules on a
+        pipeline without a text encoder (a cfg_split rank built with with_text_encoder=False)."""
+        from . import lora as L
+        if not self._loras:
+            raise RuntimeError('this pipeline was built without loras=True: merge on the host (lora.merged_state_dict) and build a new one')
+        parsed = []
+        for a in adapters:
+            if not isinstance(a, (tuple, list)) or len(a) not in (2, 3):
+                raise ValueError('an adapter is (path_or_dict, strength) or (path_or_dict, strength_unet, strength_text)')
+            strengths = [a[1], a[1] if len(a) == 2 else a[2]]
+            for v in strengths:
+                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
+                    raise ValueError(f'LoRA strength must be a finite number, got {v!r}')
+            parsed.append((a[0], float(strengths[0]), float(strengths[1])))
+        if self.cfg.weight_quant != 0:
+            raise ValueError('LoRA adapters need fp16 weights: this pipeline keeps uint8 codes (weight_quant); merge on the host instead')
+        lists, skipped = {'unet': [], 'text': []}, []
+        for src, s_unet, s_text in parsed:
+            ent, skip = L.entries_for(src, self.model, s_unet, s_text, strict=strict)
+            lists['unet'] += ent['unet']
+            lists['text'] += ent['text']
+            skipped += skip
+        if lists['text'] and self.text is None:
+            raise ValueError('the adapters hold text-encoder modules and this pipeline has no text encoder')
+        self.unet.set_loras(lists['unet'])
+        if self.text is not None:
+            self.text.set_loras(lists['text'])
+        self._ctx_fresh = True
+        return skipped
+
+    def clear_loras(self):
+        """back to the base weights, bit for bit: set_loras([])"""
+        return self.set_loras([])
 
     # ------------------------------------------------------------------ conditioning
     def encode_tokens(self, ids_uncond, ids_cond):
