@@ -52,7 +52,7 @@ typedef struct sdod_gemm_desc {
     const void* bias;     /* fp32 [N] (or [M] if bias_on_m), may be NULL */
     const void* row_bias; /* fp16 [M / rows_per_img][ld_row_bias] added per image (time embedding), may be NULL */
     const void* residual; /* fp16 [M][ldr], may be NULL */
-    void* out;            /* fp16 [M][ldo] */
+    void* out;            /* fp16 [M][ldo]; out and residual 16-byte aligned when the output width, ldo and ldr are multiples of 8 */
     void* workspace;      /* fp32 split-K slabs, >= split_k*M*N*4 bytes when split_k > 1 */
     size_t workspace_bytes;
     int M, N, K;

@@ -31,6 +31,22 @@ def _req(t, dtype=None, name='tensor'):
     return t
 
 
+def _ld(t, dtype, name, width, mult=8):
+    """Row stride (elements) of a GEMM matrix operand of `width` columns: a contiguous tensor is dense (the width, whatever its
+    shape); a 2-D view with unit column stride (a column range of wider rows) gives its row stride, which must be a multiple
+    of `mult` elements."""
+    if t.is_contiguous():   # (also a ONE-row view into wider rows: torch calls it contiguous, and one row has no stride to honour)
+        _req(t, dtype, name)
+        return width
+    if not t.is_cuda:
+        raise ValueError(f'{name} must live on the GPU')
+    if t.dtype != dtype:
+        raise ValueError(f'{name} must be {dtype}, got {t.dtype}')
+    if t.dim() != 2 or t.shape[1] != width or t.stride(1) != 1 or t.stride(0) < width or t.stride(0) % mult:
+        raise ValueError(f'{name} must be contiguous or a 2-D view with unit column stride and a row stride that is a multiple of {mult}')
+    return t.stride(0)
+
+
 def _affine(weight, bias, c, device):
     """fp32 weight and bias for the kernels, which take both or neither: a missing one of the two becomes ones / zeros on the
     device (F.group_norm accepts either alone)."""
@@ -61,17 +77,19 @@ def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=N
          xcd=0, softmax_cols=0):
     """out = act(alpha * A @ W^T + bias + row_bias) + residual.
 
+    The matrix operands (a in rows mode, w, out, residual, row_bias) are contiguous or 2-D views with unit column stride into
+    wider rows (row stride a multiple of 8 elements, 16 for uint8 w): lda / ldw / ldo / ldr / ld_row_bias are their row strides.
     a: fp16 [M, K] (rows mode) or NHWC [N, H, W, C0] with conv=dict(stride=1|2, upsample=bool) (3x3 pad 1);
     conv=dict(stride=2, pad_mode=1): ldm's VAE-encoder Downsample, F.pad(a, (0, 1, 0, 1)) then a 3x3 stride-2 pad-0 conv;
     a2: optional second NHWC source concatenated on channels; w: fp16 [Nout, K] (conv: K = 9*(C0+C1), KRSC)."""
     lib = _lib.hip()
-    _req(a, torch.float16, 'a')
+    lda = _ld(a, torch.float16, 'a', a.shape[-1]) if conv is None else _req(a, torch.float16, 'a').shape[-1]
     d = GemmDesc()
     if w_scale is not None:   # affine-uint8 weight codes: real = (q + offset) * scale, w_off = offset + 128 per output column
-        _req(w, torch.uint8, 'w'); _req(w_scale, torch.float32, 'w_scale'); _req(w_off, torch.float32, 'w_off')
+        ldw = _ld(w, torch.uint8, 'w', w.shape[-1], 16); _req(w_scale, torch.float32, 'w_scale'); _req(w_off, torch.float32, 'w_off')
         d.wq = 1; d.w_scale = _p(w_scale); d.w_off = _p(w_off)
     else:
-        _req(w, torch.float16, 'w')
+        ldw = _ld(w, torch.float16, 'w', w.shape[-1])
     per_image = w.dim() == 3   # [n_img, Nout, K]: the rows of image i (rows_per_img each) multiply w[i]; bias / ln_s may be [n_img, Nout]
     nout, k = w.shape[-2:]
     if per_image:
@@ -86,7 +104,7 @@ def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=N
         m = a.shape[0]
         assert a.shape[1] == k, (a.shape, w.shape)
         d.a_mode = 0
-        d.lda = k
+        d.lda = lda
         out_shape = (m, nout)
     else:
         n_img, h, wd, c0 = a.shape
@@ -115,11 +133,10 @@ def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=N
     if out is None:
         out = torch.empty(out_shape, dtype=torch.float16, device=a.device)
     else:
-        _req(out, torch.float16, 'out')
         assert out.numel() == m * nvis
     d.a, d.w, d.out = _p(a), _p(w), _p(out)
     d.M, d.N, d.K = m, nout, k
-    d.ldw, d.ldo = k, nvis
+    d.ldw, d.ldo = ldw, _ld(out, torch.float16, 'out', nvis)
     d.geglu = 1 if geglu else 0
     if tail is not None:      # (t0, t1 or None): NHWC tensors read by the 1x1 tail segment; w holds [main K | tail K] columns
         t0, t1 = tail
@@ -133,11 +150,10 @@ def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=N
     if bias is not None:
         _req(bias, torch.float32, 'bias'); d.bias = _p(bias)
     if row_bias is not None:
-        _req(row_bias, torch.float16, 'row_bias'); d.row_bias = _p(row_bias); d.rows_per_img = rows_per_img
-        d.ld_row_bias = row_bias.shape[-1]
+        d.ld_row_bias = _ld(row_bias, torch.float16, 'row_bias', row_bias.shape[-1]); d.row_bias = _p(row_bias); d.rows_per_img = rows_per_img
     if residual is not None:
-        _req(residual, torch.float16, 'residual'); assert residual.numel() == m * nout
-        d.residual = _p(residual); d.ldr = nout
+        assert residual.numel() == m * nout
+        d.residual = _p(residual); d.ldr = _ld(residual, torch.float16, 'residual', nout)
     d.act = ACT[act]
     d.alpha = alpha
     d.bias_on_m = 1 if bias_on_m else 0
