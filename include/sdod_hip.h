@@ -325,6 +325,30 @@ SDOD_API int sdod_inpaint_cond_f32(const float* moments, const uint8_t* mask_u8,
  * sdod_randn_f32(count = c*h*w, seed, stream_id = (1 << 32) | (image_index0 + i)) for n1 and (2 << 32) | (image_index0 + i) for n2. */
 SDOD_API int sdod_encode_latent_f32(const float* moments, const float* n1, const float* n2, float* x, float* z0, int n, int c, int hw,
                                     float sqrt_at, float sqrt_one_minus_at, uint64_t seed, uint64_t image_index0, void* stream);
+/* The latent resize between the two sampler trajectories of the hires pass, with img2img's start-latent formula, in one launch:
+ *   dst = a * R(src) + b * nu          src fp32 NCHW [n][c][h_in][w_in], dst fp32 NCHW [n][c][h_out][w_out]
+ * R = torch.nn.functional.interpolate(size=(h_out, w_out), align_corners=False, antialias=False).  Per axis, output coordinate d:
+ *   mode 0 nearest-exact: index min(floor((2 d + 1) n_in / (2 n_out)), n_in - 1), integer arithmetic
+ *   mode 1 bilinear:      s = max(((2 d + 1) n_in - n_out) / (2 n_out), 0), i0 = floor(s), i1 = min(i0 + 1, n_in - 1), t = s - i0,
+ *                         weights 1 - t, t
+ *   mode 2 bicubic:       s without the clamp, i = floor(s), t = s - i, taps i - 1 .. i + 2 clamped to [0, n_in - 1], weights
+ *                         c2(t + 1), c1(t), c1(1 - t), c2(2 - t) with c1(x) = ((A + 2) x - (A + 3)) x^2 + 1,
+ *                         c2(x) = ((A x - 5 A) x + 8 A) x - 4 A, A = -0.75
+ * floor(s) and the remainder come from an integer division, so t is an exact rational rounded once; the weights are evaluated in
+ * fp64 and rounded once to fp32 (one function for host and device), the sums run in fp32, x first, then y.  The error does not grow
+ * with the coordinate.  n_in == n_out copies the source bit for bit in every mode.
+ * Taps of weight 0 are neither read nor added (that is what makes the copy exact), so a non-finite source value does not propagate
+ * through a zero-weight tap: where torch gives NaN from 0 * inf or 0 * NaN (bilinear with t == 0, the integer ratios), this gives the
+ * finite sum of the other taps.
+ * nu: none is read or drawn when b == 0; else `noise` fp32 [n][c][h_out][w_out], or when NULL drawn in the kernel, image i's values
+ * exactly those of sdod_randn_f32(c * h_out * w_out, seed, (2 << 32) | (image_index0 + i)) (sdod_encode_latent_f32's n2 family).
+ * No alignment or divisibility assumption on any size.  Errors, returned before any device call (dst untouched): NULL src or dst, a
+ * size below 1, an unknown mode, a non-finite a or b, dst overlapping src. */
+SDOD_API int sdod_latent_resize_f32(const float* src, float* dst, int n, int c, int h_in, int w_in, int h_out, int w_out, int mode, float a,
+                                    float b, const float* noise, uint64_t seed, uint64_t image_index0, void* stream);
+/* Host only: the per-axis table sdod_latent_resize_f32 uses, idx int32 [n_out][4] and w fp32 [n_out][4]; unused slots hold index 0
+ * and weight 0. */
+SDOD_API int sdod_latent_resize_taps(int mode, int n_in, int n_out, int32_t* idx, float* w);
 SDOD_API int sdod_nchw_f32_to_nhwc_f16(const float* x, void* y, int n, int c, int hw, float scale, void* stream);
 /* y(NHWC fp16)[img][pix][o] = sum_c w[o][c]*(scale*x(NCHW fp32)[img][c][pix]) + b[o]; w/b fp32 [c][c]/[c] or NULL
  * (identity).  Folds ldm's z/0.18215 and first_stage_model.post_quant_conv into the layout change. */

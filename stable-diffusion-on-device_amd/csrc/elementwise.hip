@@ -731,6 +731,96 @@ __global__ void encode_latent_kernel(const float* mom, const float* n1, const fl
     }
 }
 
+// One axis of torch's interpolate(align_corners=False, antialias=False) for output coordinate d (include/sdod_hip.h:
+// sdod_latent_resize_f32): up to four source indices and their weights; unused slots are index 0, weight 0.  The source coordinate
+// s = ((2 d + 1) n_in - n_out) / (2 n_out) is split into integer part and remainder by integer division, so t is an exact rational
+// rounded once, whatever the coordinate; the weights are evaluated in fp64 and rounded once to fp32.  The same function fills the
+// host's table (sdod_latent_resize_taps) and the kernel's registers.
+__host__ __device__ inline void resize_taps(int mode, int n_in, int n_out, int d, int (&idx)[4], float (&w)[4]) {
+    for (int k = 0; k < 4; ++k) { idx[k] = 0; w[k] = 0.0f; }
+    const long long den = 2ll * n_out, last = n_in - 1;
+    if (mode == 0) { // nearest-exact
+        const long long i = ((2ll * d + 1) * n_in) / den;
+        idx[0] = (int)(i < last ? i : last);
+        w[0] = 1.0f;
+        return;
+    }
+    long long num = (2ll * d + 1) * n_in - n_out;
+    if (mode == 1 && num < 0) num = 0; // bilinear clamps the coordinate at 0
+    long long i = num / den, rem = num - i * den;
+    if (rem < 0) { rem += den; --i; } // floor, not truncation
+    const double t = (double)rem / (double)den;
+    if (mode == 1) {
+        idx[0] = (int)i;
+        idx[1] = (int)(i + 1 < last ? i + 1 : last);
+        w[0] = (float)(1.0 - t);
+        w[1] = (float)t;
+        return;
+    }
+    const double A = -0.75; // bicubic, torch's convolution coefficients
+    const auto c1 = [A](double x) { return ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0; };
+    const auto c2 = [A](double x) { return ((A * x - 5.0 * A) * x + 8.0 * A) * x - 4.0 * A; };
+    for (int k = 0; k < 4; ++k) {
+        const long long j = i - 1 + k;
+        idx[k] = (int)(j < 0 ? 0 : j > last ? last : j);
+    }
+    w[0] = (float)c2(t + 1.0); w[1] = (float)c1(t); w[2] = (float)c1(1.0 - t); w[3] = (float)c2(2.0 - t);
+}
+
+// dst = a * R(src) + b * nu in ONE launch (include/sdod_hip.h: sdod_latent_resize_f32): the latent resize between the two sampler
+// trajectories of the hires pass with img2img's start-latent formula behind it.  Separable: four taps along x for each of up to four
+// source rows, then four taps along y, every product and sum rounded on its own in fp32; taps of weight 0 are neither read nor
+// added, so n -> n copies the source bit for bit.  Thread = four consecutive elements of one image = one Philox block of its
+// stream (as encode_latent_kernel), the last block of an image cut at its end: no size needs to be a multiple of anything.
+__global__ void latent_resize_kernel(const float* src, float* dst, int n, int c, int h_in, int w_in, int h_out, int w_out, int mode, float a,
+                                     float b, const float* noise, uint64_t seed, uint64_t index0) {
+    const size_t hw_out = (size_t)h_out * w_out, per = (size_t)c * hw_out, nblk = (per + 3) / 4;
+    GRID_STRIDE(t, (size_t)n * nblk) {
+        const size_t img = t / nblk, j = t - img * nblk;
+        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (b != 0.0f) {
+            if (noise) {
+                for (int q = 0; q < 4; ++q)
+                    if (4 * j + q < per) z[q] = noise[img * per + 4 * j + q];
+            } else {
+                uint32_t words[4];
+                philox_normal4(j, seed, (2ull << 32) | (index0 + img), words, z);
+            }
+        }
+        for (int q = 0; q < 4; ++q) {
+            const size_t e = 4 * j + q;
+            if (e >= per) break;
+            const size_t ch = e / hw_out, pix = e - ch * hw_out;
+            const int oy = (int)(pix / w_out), ox = (int)(pix - (size_t)oy * w_out);
+            int iy[4], ix[4];
+            float wy[4], wx[4];
+            resize_taps(mode, h_in, h_out, oy, iy, wy);
+            resize_taps(mode, w_in, w_out, ox, ix, wx);
+            const float* plane = src + (img * c + ch) * ((size_t)h_in * w_in);
+            float r = 0.0f;
+            bool any_y = false;
+            for (int ky = 0; ky < 4; ++ky) {
+                if (wy[ky] == 0.0f) continue;
+                const float* row = plane + (size_t)iy[ky] * w_in;
+                float rx = 0.0f;
+                bool any_x = false;
+                for (int kx = 0; kx < 4; ++kx) {
+                    if (wx[kx] == 0.0f) continue;
+                    const float p = mul_rn(wx[kx], row[ix[kx]]);
+                    rx = any_x ? add_rn(rx, p) : p;
+                    any_x = true;
+                }
+                const float p = mul_rn(wy[ky], rx);
+                r = any_y ? add_rn(r, p) : p;
+                any_y = true;
+            }
+            float v = mul_rn(a, r);
+            if (b != 0.0f) v = add_rn(v, mul_rn(b, z[q]));
+            dst[img * per + e] = v;
+        }
+    }
+}
+
 // The conditioning input of the 9-channel inpainting UNet in ONE launch (include/sdod_hip.h: sdod_inpaint_cond_f32): channel 0 = the
 // binarised mask at latent resolution (nearest: the top-left byte of each 8 x 8 block), channels 1..c = encode_latent_kernel's z0 of
 // the masked image's moments (posterior_sample on the same Philox stream), written `reps` times back to back.  Threads
@@ -988,6 +1078,40 @@ extern "C" int sdod_encode_latent_f32(const float* moments, const float* n1, con
     SDOD_REQUIRE(moments && x && n > 0 && c > 0 && hw > 0 && ((size_t)c * hw) % 4 == 0, "bad argument (c * hw must be a multiple of 4)");
     LAUNCH(encode_latent_kernel, (size_t)n * c * hw / 4, stream, moments, n1, n2, x, z0, n, c, hw, sqrt_at, sqrt_one_minus_at, seed,
            image_index0);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_latent_resize_f32(const float* src, float* dst, int n, int c, int h_in, int w_in, int h_out, int w_out, int mode, float a,
+                                      float b, const float* noise, uint64_t seed, uint64_t image_index0, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(src && dst, "NULL src or dst");
+    SDOD_REQUIRE(n > 0 && c > 0 && h_in > 0 && w_in > 0 && h_out > 0 && w_out > 0, "every size must be at least 1");
+    SDOD_REQUIRE(mode >= 0 && mode <= 2, "mode must be 0 (nearest-exact), 1 (bilinear) or 2 (bicubic)");
+    SDOD_REQUIRE(std::isfinite(a) && std::isfinite(b), "non-finite scalar");
+    const size_t planes = (size_t)n * c, count_in = planes * h_in * w_in, count_out = planes * h_out * w_out;
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    SDOD_REQUIRE(d0 + count_out * sizeof(float) <= s0 || s0 + count_in * sizeof(float) <= d0, "dst overlaps src");
+    LAUNCH(latent_resize_kernel, (count_out / n + 3) / 4 * n, stream, src, dst, n, c, h_in, w_in, h_out, w_out, mode, a, b, noise, seed,
+           image_index0);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_latent_resize_taps(int mode, int n_in, int n_out, int32_t* idx, float* w) {
+    SDOD_TRY
+    SDOD_REQUIRE(idx && w, "NULL idx or w");
+    SDOD_REQUIRE(n_in > 0 && n_out > 0, "every size must be at least 1");
+    SDOD_REQUIRE(mode >= 0 && mode <= 2, "mode must be 0 (nearest-exact), 1 (bilinear) or 2 (bicubic)");
+    for (int d = 0; d < n_out; ++d) {
+        int i4[4];
+        float w4[4];
+        resize_taps(mode, n_in, n_out, d, i4, w4);
+        for (int k = 0; k < 4; ++k) {
+            idx[4 * (size_t)d + k] = i4[k];
+            w[4 * (size_t)d + k] = w4[k];
+        }
+    }
     return 0;
     SDOD_CATCH
 }

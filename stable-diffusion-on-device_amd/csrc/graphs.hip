@@ -303,6 +303,8 @@ void Graph::build_unet() {
     const int MC = cfg_.model_channels, EC = 4 * MC, cd = cfg_.context_dim, CL = cfg_.context_len;
     const int CC = cfg_.concat_channels, CI = LC + CC; // inpainting checkpoint: the input convolution also reads CC channels of in3
     SDOD_REQUIRE(LC * 9 <= 64, "latent_channels too large for the small-Cin path");
+    // three stride-2 levels down and nearest-2x back up must land on the skip tensors' sizes
+    SDOD_REQUIRE(H >= 8 && Wd >= 8 && H % 8 == 0 && Wd % 8 == 0, "the UNet needs latent_h and latent_w to be multiples of 8, at least 8");
     SDOD_REQUIRE(CI * 9 <= 96, "latent_channels + concat_channels too large for the small-Cin path (9 Cin <= 96)");
     SDOD_REQUIRE(CC == 0 || CI * 9 > 64, "concat_channels > 0 needs 9 (latent_channels + concat_channels) > 64 (the K = 96 input convolution)");
     SDOD_REQUIRE(CC == 0 || MC == 320 || MC == 256 || MC == 128 || MC == 64,

@@ -520,6 +520,47 @@ def encode_latent(moments, sqrt_at, sqrt_one_minus_at, seed=0, image_index=0, n1
     return x
 
 
+RESIZE_MODES = {'nearest-exact': 0, 'bilinear': 1, 'bicubic': 2}
+
+
+def latent_resize(z, size, mode='bilinear', a=1.0, b=0.0, noise=None, seed=0, image_index=0, out=None):
+    """a * R(z) + b * nu in one launch (sdod_latent_resize_f32): z fp32 [n, c, h, w] -> fp32 [n, c, h_out, w_out] with R =
+    F.interpolate(size=size, mode=mode, align_corners=False, antialias=False), mode 'nearest-exact', 'bilinear' or 'bicubic'.  nu
+    (b != 0 only): `noise` fp32 [n, c, h_out, w_out], or Philox on the device, stream (2 << 32) | (image_index + i) of `seed` for
+    image i.  out: an existing fp32 destination that does not overlap z."""
+    lib = _lib.hip()
+    if mode not in RESIZE_MODES:
+        raise ValueError(f'mode must be one of {tuple(RESIZE_MODES)}, got {mode!r}')
+    _req(z, torch.float32, 'z')
+    if z.dim() != 4:
+        raise ValueError(f'z must be [n, c, h, w], got {tuple(z.shape)}')
+    n, c, h, w = z.shape
+    shape = (n, c, int(size[0]), int(size[1]))
+    if noise is not None:
+        _req(noise, torch.float32, 'noise')
+        if tuple(noise.shape) != shape:
+            raise ValueError(f'noise must be {shape}, got {tuple(noise.shape)}')
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=z.device)
+    else:
+        _req(out, torch.float32, 'out')
+        if tuple(out.shape) != shape:
+            raise ValueError(f'out must be {shape}, got {tuple(out.shape)}')
+    check(lib.sdod_latent_resize_f32(_p(z), _p(out), n, c, h, w, shape[2], shape[3], RESIZE_MODES[mode], float(a), float(b), _p(noise),
+                                     int(seed) & (2 ** 64 - 1), int(image_index) & (2 ** 64 - 1), _stream()))
+    return out
+
+
+def latent_resize_taps(mode, n_in, n_out):
+    """the per-axis table of latent_resize, computed on the host by the function the kernel uses (sdod_latent_resize_taps): (idx int32
+    [n_out, 4], w fp32 [n_out, 4]) as CPU tensors; unused slots hold index 0 and weight 0"""
+    lib = _lib.hip()
+    idx = torch.zeros((max(int(n_out), 0), 4), dtype=torch.int32)
+    w = torch.zeros((max(int(n_out), 0), 4), dtype=torch.float32)
+    check(lib.sdod_latent_resize_taps(RESIZE_MODES.get(mode, mode), int(n_in), int(n_out), _p(idx), _p(w)))
+    return idx, w
+
+
 def nchw_f32_to_nhwc_f16(x, scale=1.0):
     lib = _lib.hip()
     _req(x, torch.float32, 'x')

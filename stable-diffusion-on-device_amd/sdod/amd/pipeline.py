@@ -27,10 +27,11 @@ class Txt2Img:
     tokenizer = None
     text = None
     _loras = False
+    hires = None        # the second pipeline of the hires pass (Txt2Img(..., hires_hw=)), or None
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
-                 with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False):
+                 with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -47,14 +48,27 @@ class Txt2Img:
         device work.
         loras=True: the UNet and the text encoder keep a second device copy of their weights (Graph.keep_base: unet.base_bytes() +
         text.base_bytes() more device memory) so that set_loras() can re-weight them in place; off, nothing is constructed or sized
-        differently."""
+        differently.
+        latent_hw: an integer (a square latent, as ever) or (h, w), each a multiple of 8 and at least 8 (64 px of image): latents are
+        [n, 4, h, w], images [n, 8h, 8w, 3], inpainting masks [n, 8h, 8w] in every entry point.  Anything else raises ValueError
+        before any device work (check_latent_hw).
+        hires_hw=(H2, W2), the same size rule: also build self.hires, a second Txt2Img of the same model arguments at that size with a
+        UNet and a VAE decoder (no text encoder, no VAE encoder), for generate_hires() / generate_hires_graphed() /
+        hires_from_latent().  It loads the same state dicts or containers and owns its own weights: hires.unet.stats() +
+        hires.vae.stats() more device memory ('weight_bytes' + 'arena_bytes' of each; with loras=True hires.unet.base_bytes() on top).
+        Without it nothing is constructed or sized differently.  With cfg_split or inpaint_unet it raises ValueError."""
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
+        latent_h, latent_w = check_latent_hw(latent_hw)
+        if hires_hw is not None:
+            check_latent_hw(hires_hw, 'hires_hw')
+            if cfg_split or inpaint_unet:
+                raise ValueError('hires_hw cannot be combined with cfg_split or inpaint_unet')
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self.n = images_per_gpu
         self.model = model
         self.v_prediction = model == 'sd21'
-        self.cfg = E.sd21_config(latent_hw, latent_hw) if model == 'sd21' else E.sd14_config(latent_hw, latent_hw)
+        self.cfg = E.sd21_config(latent_h, latent_w) if model == 'sd21' else E.sd14_config(latent_h, latent_w)
         # int8 weight streaming (BASELINE config 5): when the UNet checkpoint holds affine-uint8 tensors (weights.QuantU8, the
         # reference's QNN encoding) they stay uint8 in HBM and the GEMMs expand them on the fly; weight_quant=False keeps the
         # round-1 behaviour (dequantise once at load, fp16 in HBM)
@@ -107,6 +121,9 @@ class Txt2Img:
         self._loras = bool(loras)
         self._temb_cache = {}
         self._ctx_fresh = True
+        if hires_hw is not None:
+            self.hires = Txt2Img(state_dicts, models_dir, images_per_gpu, hires_hw, device, use_hip_graph, None, False, model, with_vae,
+                                 False, weight_quant, False, False, prompt_chunks, loras=loras)
 
     def _load(self, g, key, stem):
         if self._sd is not None:
@@ -123,7 +140,8 @@ class Txt2Img:
         model.  A context encoded BEFORE a text-encoder adapter was set or cleared is stale: encode the prompt again.
         strict=False skips the modules the engine cannot adapt; their keys are returned.  RuntimeError when the pipeline was built
         without loras=True; ValueError, before any device work, for a bad strength, uint8 weights, or text-encoder modules on a
-        pipeline without a text encoder (a cfg_split rank built with with_text_encoder=False)."""
+        pipeline without a text encoder (a cfg_split rank built with with_text_encoder=False).  With hires_hw the UNet modules are
+        applied to both UNets, the text-encoder modules to the base pipeline's alone (the hires pipeline has no text encoder)."""
         from . import lora as L
         if not self._loras:
             raise RuntimeError('this pipeline was built without loras=True: merge on the host (lora.merged_state_dict) and build a new one')
@@ -147,6 +165,9 @@ class Txt2Img:
         if lists['text'] and self.text is None:
             raise ValueError('the adapters hold text-encoder modules and this pipeline has no text encoder')
         self.unet.set_loras(lists['unet'])
+        if self.hires is not None:       # the second pass runs the same model: its UNet takes the same adapters
+            self.hires.unet.set_loras(lists['unet'])
+            self.hires._ctx_fresh = True
         if self.text is not None:
             self.text.set_loras(lists['text'])
         self._ctx_fresh = True
@@ -435,8 +456,10 @@ class Txt2Img:
             self._traj = {}
         if key not in self._traj:
             statics = [torch.zeros(tuple(shape), dtype=dtype, device=self.device) for shape, dtype in inputs]
-            keep = self.use_hip_graph
-            self.use_hip_graph = False          # inside a capture the engine graphs run their launch lists, not graphs of their own
+            pipes = [self] if self.hires is None else [self, self.hires]
+            keep = [p.use_hip_graph for p in pipes]
+            for p in pipes:                     # inside a capture the engine graphs run their launch lists, not graphs of their own
+                p.use_hip_graph = False
             try:
                 run(*statics)
                 torch.cuda.synchronize(self.device)
@@ -445,7 +468,8 @@ class Txt2Img:
                 with torch.cuda.graph(g, capture_error_mode='thread_local'):
                     out = run(*statics)
             finally:
-                self.use_hip_graph = keep
+                for p, k in zip(pipes, keep):
+                    p.use_hip_graph = k
             self._traj[key] = (g, statics, out)
         return self._traj[key]
 
@@ -725,6 +749,98 @@ class Txt2Img:
         g.replay()
         return out
 
+    # ------------------------------------------------------------------ hires: sample small, resize the latent, img2img at the target size
+    def hires_from_latent(self, ctx2, z_lo, sampler='dpmpp_2m', guidance=7.5, *, hires_steps, hires_seed, denoise=0.7, upscaler='bilinear',
+                          schedule='karras', eta=1.0, image_index=0, hires_noise=None, hires_step_noise=None):
+        """The second pass alone: z_lo fp32 [n, 4, h, w] (a clean latent of the base size) -> uint8 [n, 8 H2, 8 W2, 3].  The hires
+        pipeline's img2img loop with strength = denoise and steps = hires_steps, started from the resized latent instead of an encoded
+        image: t_enc = int(denoise * hires_steps) (img2img_schedule's domain).
+        sampler 'plms' / 'dpm' (schedule plays no part): x = sqrt_alphas[t_enc] * R(z_lo) + sqrt_one_minus_alphas[t_enc] * nu from ONE
+        ops.latent_resize launch, then hires.sample_ddim_from(ctx2, x, t_enc, hires_steps, guidance); ValueError with model='sd21' (the
+        DDIM img2img loop has no v-conversion).  A k-sampler: first = hires_steps - t_enc, x = R(z_lo) + sigmas[first] * nu, then
+        hires.sample_k(..., first=first) with the same sampler, schedule and eta.  Then hires.decode(z, mode=1).
+        R: upscaler 'nearest-exact', 'bilinear' or 'bicubic' (F.interpolate, align_corners=False, no antialiasing).  nu: hires_noise
+        (fp32 [n, 4, H2, W2]) or Philox family 2 of hires_seed; euler_a's step noise: hires_step_noise (fp32 [t_enc - 1, n, 4, H2, W2],
+        row r = step first + r) or families 3 + step of hires_seed.  hires_steps and hires_seed have no defaults here: generate_hires
+        owns them (steps and seed + 1).  Argument errors raise ValueError before any device work."""
+        if not isinstance(z_lo, torch.Tensor) or z_lo.dim() != 4 or tuple(z_lo.shape[1:]) != self._latent_shape:
+            raise ValueError(f'z_lo must be a tensor [n, {", ".join(str(v) for v in self._latent_shape)}], got {tuple(getattr(z_lo, "shape", ()))}')
+        t_enc = hires_check_args(self, z_lo.shape[0], sampler, hires_steps, denoise, upscaler, schedule, eta, hires_noise, hires_step_noise)
+        hires_steps = int(hires_steps)
+        hi = self.hires
+        z_lo = z_lo.to(self.device, torch.float32).contiguous()
+        if hires_noise is not None:
+            hires_noise = hires_noise.to(self.device, torch.float32).contiguous()
+        if sampler in K_SAMPLERS:
+            first = hires_steps - t_enc
+            a, b = 1.0, float(KSchedule(hires_steps, schedule).sigmas[first])
+        else:
+            sch = PlmsSchedule(hires_steps)
+            a, b = float(sch.sqrt_alphas[t_enc]), float(sch.sqrt_one_minus_alphas[t_enc])
+        x = ops.latent_resize(z_lo, hi._latent_shape[1:], upscaler, a, b, hires_noise, hires_seed, image_index)
+        if sampler in K_SAMPLERS:
+            z = hi.sample_k(ctx2, x, sampler, hires_steps, guidance, schedule, eta, first, hires_seed, image_index, hires_step_noise)
+        else:
+            z = hi.sample_ddim_from(ctx2, x, t_enc, hires_steps, guidance)
+        return hi.decode(z, mode=1)
+
+    def generate_hires(self, ctx2, x_T, steps=20, guidance=7.5, sampler='dpmpp_2m', *, hires_steps=None, denoise=0.7, upscaler='bilinear',
+                       schedule='karras', eta=1.0, seed=0, image_index=0, step_noise=None, hires_seed=None, hires_noise=None,
+                       hires_step_noise=None):
+        """The two-pass hires fix: pass 1 is generate()'s sampling at the base size without the decode (sampler 'plms' / 'dpm', which
+        take no schedule, or a k-sampler on `schedule`; seed, step_noise are euler_a's first-pass noise), pass 2 is hires_from_latent()
+        on its result with hires_steps (default: steps) and denoise.  hires_seed defaults to seed + 1: with the same seed pass 2's
+        step-noise streams would coincide with pass 1's.  Returns uint8 [n, 8 H2, 8 W2, 3].  Argument errors raise ValueError before
+        any device work."""
+        sched1 = schedule if sampler in K_SAMPLERS else 'discrete'
+        hires_steps = steps if hires_steps is None else hires_steps
+        k_check_args(sampler, steps, sched1, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
+        hires_check_args(self, x_T.shape[0], sampler, hires_steps, denoise, upscaler, schedule, eta, hires_noise, hires_step_noise)
+        hires_seed = int(seed) + 1 if hires_seed is None else hires_seed
+        if sampler in K_SAMPLERS:
+            z_lo = self.sample_k(ctx2, x_T, sampler, steps, guidance, schedule, eta, 0, seed, image_index, step_noise)
+        else:
+            z_lo = self._sample(sampler, ctx2, x_T, steps, guidance)
+        return self.hires_from_latent(ctx2, z_lo, sampler, guidance, hires_steps=hires_steps, denoise=denoise, upscaler=upscaler,
+                                      schedule=schedule, eta=eta, hires_seed=hires_seed, image_index=image_index, hires_noise=hires_noise,
+                                      hires_step_noise=hires_step_noise)
+
+    def generate_hires_graphed(self, ctx2, x_T, steps=20, guidance=7.5, sampler='dpmpp_2m', *, hires_steps=None, denoise=0.7,
+                               upscaler='bilinear', schedule='karras', eta=1.0, seed=0, image_index=0, step_noise=None, hires_seed=None,
+                               hires_noise=None, hires_step_noise=None):
+        """generate_hires() as ONE device graph replay (both trajectories, the resize, the decode), captured once per (sampler, steps,
+        hires_steps, t_enc, guidance, upscaler, schedule, eta, shape) from the eager path.  ctx2, x_T and all noise are inputs of the
+        graph: what the caller does not pass is drawn into them first by sdod_randn_f32 on the streams the eager path draws in its
+        kernels, bit for bit, so the graph bakes no seed and the result equals generate_hires() with the same arguments."""
+        sched1 = schedule if sampler in K_SAMPLERS else 'discrete'
+        hires_steps = steps if hires_steps is None else hires_steps
+        k_check_args(sampler, steps, sched1, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
+        t_enc = hires_check_args(self, x_T.shape[0], sampler, hires_steps, denoise, upscaler, schedule, eta, hires_noise, hires_step_noise)
+        hires_steps = int(hires_steps)
+        hires_seed = int(seed) + 1 if hires_seed is None else hires_seed
+        kw = dict(hires_steps=hires_steps, denoise=denoise, upscaler=upscaler, schedule=schedule, eta=eta)
+        n = x_T.shape[0]
+        lat_hi = (n,) + self.hires._latent_shape
+        key = ('hires', sampler, int(steps), hires_steps, t_enc, float(guidance), upscaler, schedule, float(eta), tuple(x_T.shape))
+        inputs = [(ctx2.shape, ctx2.dtype), (x_T.shape, torch.float32), (lat_hi, torch.float32)]
+        if sampler == 'euler_a':
+            g, (s_ctx, s_x, s_hn, s_sn, s_hsn), out = self._graphed(
+                key, inputs + [((int(steps) - 1,) + tuple(x_T.shape), torch.float32), ((t_enc - 1,) + lat_hi, torch.float32)],
+                lambda c, x, hn, sn, hsn: self.generate_hires(c, x, steps, guidance, sampler, step_noise=sn, hires_noise=hn,
+                                                              hires_step_noise=hsn, **kw))
+            self._fill_step_noise(s_sn, step_noise, seed, 0, image_index)
+            self._fill_step_noise(s_hsn, hires_step_noise, hires_seed, hires_steps - t_enc, image_index)
+        else:
+            g, (s_ctx, s_x, s_hn), out = self._graphed(
+                key, inputs, lambda c, x, hn: self.generate_hires(c, x, steps, guidance, sampler, hires_noise=hn, **kw))
+        s_ctx.copy_(ctx2); s_x.copy_(x_T)
+        if hires_noise is None:
+            self._fill_noise(s_hn, hires_seed, 2, image_index)
+        else:
+            s_hn.copy_(hires_noise)
+        g.replay()
+        return out
+
     def generate_pipelined(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms'):
         """generate_graphed() as TWO device graphs -- sampling (context upload, every UNet evaluation, CFG, sampler updates) on
         the current stream and decoding (VAE + uint8) on a side stream -- so that the decode of image i runs while image i+1 is
@@ -781,6 +897,53 @@ def check_prompt_chunks(prompt_chunks):
     if isinstance(prompt_chunks, bool) or not isinstance(prompt_chunks, (int, np.integer)) or not 1 <= prompt_chunks <= 4:
         raise ValueError(f'prompt_chunks must be an integer in [1, 4], got {prompt_chunks!r}')
     return int(prompt_chunks)
+
+
+def check_latent_hw(latent_hw, name='latent_hw'):
+    """Txt2Img's latent_hw / hires_hw: an integer (square) or (h, w), each a multiple of 8 and at least 8 -- 64 px of image: the UNet's
+    three stride-2 levels and the nearest-2x upsampling back must land on the skip tensors' sizes.  Returns (h, w); raises ValueError."""
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    hw = (latent_hw, latent_hw) if is_int(latent_hw) else latent_hw
+    if not isinstance(hw, (tuple, list)) or len(hw) != 2 or not all(is_int(v) for v in hw):
+        raise ValueError(f'{name} must be an integer or (h, w), got {latent_hw!r}')
+    if any(v < 8 or v % 8 for v in hw):
+        raise ValueError(f'{name}: height and width must be multiples of 8, at least 8 (64 px of image), got {latent_hw!r}')
+    return int(hw[0]), int(hw[1])
+
+
+HIRES_UPSCALERS = ('nearest-exact', 'bilinear', 'bicubic')
+
+
+def hires_check_args(pipe, n_images, sampler, hires_steps, denoise, upscaler, schedule, eta, hires_noise, hires_step_noise):
+    """the argument contract of the second pass (Txt2Img.hires_from_latent, generate_hires, generate_hires_graphed), checked on the host
+    before any device work: a pipeline built with hires_hw; sampler 'plms' / 'dpm' (not with model='sd21') or one of K_SAMPLERS;
+    upscaler one of HIRES_UPSCALERS; denoise and hires_steps in img2img_schedule's domain; hires_noise None or an fp32 tensor
+    [n_images, 4, H2, W2]; hires_step_noise None or -- euler_a only -- an fp32 tensor [t_enc - 1, n_images, 4, H2, W2].  Returns t_enc;
+    raises ValueError."""
+    if pipe.hires is None:
+        raise ValueError('this pipeline was built without hires_hw: Txt2Img(..., hires_hw=(H2, W2)) is needed for the hires pass')
+    if upscaler not in HIRES_UPSCALERS:
+        raise ValueError(f'upscaler must be one of {HIRES_UPSCALERS}, got {upscaler!r}')
+    if sampler not in ('plms', 'dpm') + K_SAMPLERS:
+        raise ValueError(f"sampler must be one of {('plms', 'dpm') + K_SAMPLERS}, got {sampler!r}")
+    if isinstance(hires_steps, bool) or int(hires_steps) != hires_steps or int(hires_steps) < 1:
+        raise ValueError(f'hires_steps must be a positive integer, got {hires_steps!r}')
+    _, t_enc = img2img_schedule(denoise, hires_steps)
+    latent = pipe.hires._latent_shape
+    if sampler in K_SAMPLERS:
+        k_check_args(sampler, hires_steps, schedule, eta, hires_step_noise, latent, n_images, first=int(hires_steps) - t_enc)
+    else:
+        if pipe.model == 'sd21':
+            raise ValueError(f"sampler {sampler!r}'s second pass is ldm's DDIM img2img loop, which has no v-conversion: use a k-sampler with model='sd21'")
+        if hires_step_noise is not None:
+            raise ValueError(f"hires_step_noise is euler_a's fresh noise; the DDIM second pass of sampler {sampler!r} draws none")
+    want = (n_images,) + tuple(latent)
+    if hires_noise is not None and (not isinstance(hires_noise, torch.Tensor) or hires_noise.dtype != torch.float32 or
+                                    tuple(hires_noise.shape) != want):
+        raise ValueError(f'hires_noise must be an fp32 tensor {want}, got {tuple(getattr(hires_noise, "shape", ()))} '
+                         f'{getattr(hires_noise, "dtype", type(hires_noise))}')
+    return t_enc
 
 
 def k_check_args(sampler, steps, schedule, eta, step_noise, latent, n_images, first=0, old_samplers=False):

@@ -26,7 +26,8 @@ only_softmax = '--only-softmax' in sys.argv # re-time the score GEMMs of the fol
 only_tail = '--only-tail' in sys.argv     # re-time the 3x3 convolutions with a fused 1x1 skip (key flags: tc0 in bits 2..13)
 only_new = '--only-new' in sys.argv       # keep EVERY shipped pick, time only the shapes the table does not have yet (a new fusion's GEMMs)
 only_vae_enc = '--only-vae-encoder' in sys.argv  # keep EVERY shipped pick, time the VAE encoder's new shapes (img2img; key flag bit 26 = pad_mode)
-only_new = only_new or only_vae_enc
+only_rect = '--only-rect' in sys.argv      # keep EVERY shipped pick, time the sd14 shapes at 64 x 96, 96 x 64 and 96 x 96 (rectangular sizes, the hires pass)
+only_new = only_new or only_vae_enc or only_rect
 if os.path.exists(out):
     os.remove(out)
 os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -82,6 +83,14 @@ def vae_encoders():
 
 if only_vae_enc:
     vae_encoders()
+    print(f'done: {out}')
+    sys.exit(0)
+
+if only_rect:
+    for h, w in ((64, 96), (96, 64), (96, 96)):
+        c = E.sd14_config(h, w)
+        build(E.UNet, c, 2, 1234, f'sd14 unet {h}x{w} b2')
+        build(E.VaeDecoder, c, 1, 1236, f'sd14 vae {h}x{w}')
     print(f'done: {out}')
     sys.exit(0)
 
