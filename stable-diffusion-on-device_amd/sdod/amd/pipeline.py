@@ -122,8 +122,10 @@ class Txt2Img:
         self._temb_cache = {}
         self._ctx_fresh = True
         if hires_hw is not None:
-            self.hires = Txt2Img(state_dicts, models_dir, images_per_gpu, hires_hw, device, use_hip_graph, None, False, model, with_vae,
-                                 False, weight_quant, False, False, prompt_chunks, loras=loras)
+            self.hires = Txt2Img(state_dicts=state_dicts, models_dir=models_dir, images_per_gpu=images_per_gpu, latent_hw=hires_hw,
+                                 device=device, use_hip_graph=use_hip_graph, tokenizer=None, with_text_encoder=False, model=model,
+                                 with_vae=with_vae, cfg_split=False, weight_quant=weight_quant, with_vae_encoder=False, inpaint_unet=False,
+                                 prompt_chunks=prompt_chunks, loras=loras)
 
     def _load(self, g, key, stem):
         if self._sd is not None:
@@ -229,9 +231,7 @@ class Txt2Img:
         if weights is not None:
             if isinstance(weights, np.ndarray):
                 weights = torch.from_numpy(weights)
-            if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != (2, k, PR.CHUNK_LEN):
-                raise ValueError(f'weights must be fp32 {(2, k, PR.CHUNK_LEN)} (uncond first), got '
-                                 f'{tuple(getattr(weights, "shape", ()))} {getattr(weights, "dtype", type(weights))}')
+            _want_tensor('weights', weights, (2, k, PR.CHUNK_LEN), torch.float32, ' (uncond first)')
             if not bool(torch.isfinite(weights).all()):
                 raise ValueError('weights must be finite')
         if self.text is None:
@@ -412,8 +412,25 @@ class Txt2Img:
                        stage=(self.unet.x, temb[i + 1], self.unet.temb) if i + 1 < steps else None)
         return x
 
-    def _sample(self, sampler, ctx2, x_T, steps, guidance):
+    def _sample(self, sampler, ctx2, x_T, steps, guidance, *, schedule='discrete', eta=1.0, seed=0, image_index=0, step_noise=None):
+        """a whole trajectory from unit-variance noise x_T: 'plms', 'dpm' (the keyword arguments play no part) or a k-sampler from its
+        first step"""
+        if sampler in K_SAMPLERS:
+            return self.sample_k(ctx2, x_T, sampler, steps, guidance, schedule, eta, 0, seed, image_index, step_noise)
         return self.sample_plms(ctx2, x_T, steps, guidance) if sampler == 'plms' else self.sample_dpm(ctx2, x_T, steps, guidance)
+
+    def _sample_from(self, k_sampler, ctx2, start, t_enc, steps, guidance, schedule, eta, seed, image_index, step_noise, trace=None):
+        """start at a noise level and finish (img2img, the hires pass): the last t_enc of `steps` evaluations.  start(a, b) makes the
+        start latent a * z0 + b * noise from the clean latent.  k_sampler None: ldm's DDIM, (a, b) = (sqrt_alphas[t_enc],
+        sqrt_one_minus_alphas[t_enc]), then sample_ddim_from(t_enc).  A k-sampler: first = steps - t_enc, (a, b) = (1, sigmas[first]),
+        then sample_k(first=first)."""
+        if k_sampler is None:
+            sch = PlmsSchedule(steps)
+            x = start(float(sch.sqrt_alphas[t_enc]), float(sch.sqrt_one_minus_alphas[t_enc]))
+            return self.sample_ddim_from(ctx2, x, t_enc, steps, guidance, trace)
+        first = int(steps) - t_enc
+        x = start(1.0, float(KSchedule(steps, schedule).sigmas[first]))
+        return self.sample_k(ctx2, x, k_sampler, steps, guidance, schedule, eta, first, seed, image_index, step_noise)
 
     @property
     def _latent_shape(self):
@@ -442,16 +459,16 @@ class Txt2Img:
         Argument errors raise ValueError before any device work."""
         k_check_args(sampler, steps, schedule, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
         self._require_cond()
-        if sampler in K_SAMPLERS:
-            return self.decode(self.sample_k(ctx2, x_T, sampler, steps, guidance, schedule, eta, 0, seed, image_index, step_noise), mode=1)
-        return self.decode(self._sample(sampler, ctx2, x_T, steps, guidance), mode=1 if sampler == 'plms' else 0)
+        z = self._sample(sampler, ctx2, x_T, steps, guidance, schedule=schedule, eta=eta, seed=seed, image_index=image_index,
+                         step_noise=step_noise)
+        return self.decode(z, mode=0 if sampler == 'dpm' else 1)
 
     # ------------------------------------------------------------------ whole trajectories as one device graph
     def _graphed(self, key, inputs, run):
         """The capture behind every *_graphed method.  On the first use of `key`: allocates the graph's static inputs (`inputs`:
         [(shape, dtype)], zeroed), calls run(*statics) -- the eager method -- once as warm-up (kernel attributes, time embeddings,
         tuning) and captures a second call as ONE device graph, so a replay is the same kernels on the same buffers, bit for bit.
-        Returns the cached (graph, statics, out); the caller copies its inputs into the statics, then replays."""
+        Returns the cached (graph, statics, out); the caller (_replay) fills the statics, then replays."""
         if self._traj is None:
             self._traj = {}
         if key not in self._traj:
@@ -479,6 +496,32 @@ class Txt2Img:
         for i in range(dst.shape[0]):
             ops.randn(tuple(dst[i:i + 1].shape), seed, (family << 32) | (image_index + i), self.device, out=dst[i:i + 1])
 
+    def _fill(self, static, desc):
+        """one static input of a graph from its description (_copied, _noise, _step_noise): the caller's tensor copied into it, or --
+        a noise input the caller did not pass -- drawn into it, row r of step noise [rows, n, 4, H, W] from family `family + r`"""
+        _, _, value, draw = desc
+        if value is not None:
+            static.copy_(value)
+            return
+        seed, family, image_index = draw
+        rows = static[None] if static.dim() == 4 else static
+        for r in range(rows.shape[0]):
+            self._fill_noise(rows[r], seed, family + r, image_index)
+
+    def _replay(self, key, run, inputs):
+        """Everything a *_graphed method does after its checks.  inputs: {keyword argument of `run`: description}, in the order the
+        static inputs are allocated; run(**statics) is the eager method on them.  Captures on the first use of `key` (_graphed), fills
+        every static from its description (_fill), replays, returns the graph's output buffer.  The noise descriptions name the Philox
+        streams the eager path's kernels draw from -- (family << 32) | (image_index + i) for image i: family 1 = n1, 2 = n2 (of
+        hires_seed: hires_noise), 3 + step = a k-sampler's or inpaint's step noise -- so graphed equals eager bit for bit and the graph
+        bakes no seed."""
+        names = list(inputs)
+        g, statics, out = self._graphed(key, [d[:2] for d in inputs.values()], lambda *s: run(**dict(zip(names, s))))
+        for static, desc in zip(statics, inputs.values()):
+            self._fill(static, desc)
+        g.replay()
+        return out
+
     def generate_graphed(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms', *, schedule='discrete', eta=1.0, seed=0, image_index=0,
                          step_noise=None):
         """generate() with the WHOLE trajectory -- context upload, every UNet evaluation, CFG, sampler updates, VAE decode,
@@ -486,33 +529,18 @@ class Txt2Img:
         step, so the GPU never waits for Python between steps (2-3 ms per image at 20 steps).  The sequence is static for a
         given (sampler, steps, guidance, batch, schedule, eta): it is captured once from the ordinary eager code path (so it is the
         same kernels on the same buffers, bit for bit) and cached; ctx2 / x_T are copied into the graph's static inputs.  euler_a's
-        step noise is a static input too: without `step_noise` it is drawn into it first by sdod_randn_f32 on the streams the eager
-        path draws in its kernels, so the graph bakes no seed and the result equals generate() with the same arguments."""
+        step noise is a static input too, the caller's or drawn on the eager path's streams (_replay): the result equals generate() with
+        the same arguments."""
         k_check_args(sampler, steps, schedule, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
         self._require_cond()
-        kw = dict(schedule=schedule, eta=eta)
+        kw = dict(steps=steps, guidance=guidance, sampler=sampler, schedule=schedule, eta=eta)
         if self.cfg_split:                 # a collective per evaluation cannot live inside one captured graph
-            return self.generate(ctx2, x_T, steps, guidance, sampler, seed=seed, image_index=image_index, step_noise=step_noise, **kw)
+            return self.generate(ctx2, x_T, seed=seed, image_index=image_index, step_noise=step_noise, **kw)
         key = (sampler, int(steps), float(guidance), tuple(x_T.shape), schedule, float(eta))
-        inputs = [(ctx2.shape, ctx2.dtype), (x_T.shape, torch.float32)]
+        inputs = dict(ctx2=_copied(ctx2), x_T=_copied(x_T, torch.float32))
         if sampler == 'euler_a':
-            g, (s_ctx, s_x, s_sn), out = self._graphed(key, inputs + [((int(steps) - 1,) + tuple(x_T.shape), torch.float32)],
-                                                       lambda c, x, sn: self.generate(c, x, steps, guidance, sampler, step_noise=sn, **kw))
-            self._fill_step_noise(s_sn, step_noise, seed, 0, image_index)
-        else:
-            g, (s_ctx, s_x), out = self._graphed(key, inputs, lambda c, x: self.generate(c, x, steps, guidance, sampler, **kw))
-        s_ctx.copy_(ctx2); s_x.copy_(x_T)
-        g.replay()
-        return out
-
-    def _fill_step_noise(self, s_sn, step_noise, seed, first, image_index):
-        """a graph's static step-noise input [rows, n, 4, H, W], row r = the noise of k-sampler step first + r: the caller's, or what
-        the eager path's kernels draw for it (noise family 3 + step)"""
-        if step_noise is None:
-            for r in range(s_sn.shape[0]):
-                self._fill_noise(s_sn[r], seed, 3 + first + r, image_index)
-        else:
-            s_sn.copy_(step_noise)
+            inputs['step_noise'] = _step_noise(step_noise, (int(steps) - 1,) + tuple(x_T.shape), seed, 0, image_index)
+        return self._replay(key, lambda **s: self.generate(**s, **kw), inputs)
 
     # ------------------------------------------------------------------ img2img (ldm scripts/img2img.py, DDIM eta = 0)
     def encode(self, init_u8, seed=0, image_index=0, strength=0.75, steps=50, noise=None, return_z0=False, coef=None):
@@ -562,47 +590,28 @@ class Txt2Img:
         t_enc the start latent is z0 + sigmas[first] * n2 and sample_k(first=first) makes the t_enc evaluations; step_noise fp32
         [t_enc - 1, n, 4, H, W], row r = step first + r (euler_a); `trace` is not filled."""
         t_enc = img2img_k_check_args(strength, steps, sampler, schedule, eta, step_noise, self._latent_shape, init_u8.shape[0])
-        if sampler is not None:
-            first = int(steps) - t_enc
-            x = self.encode(init_u8, seed, image_index, strength, steps, noise, coef=(1.0, float(KSchedule(steps, schedule).sigmas[first])))
-            z = self.sample_k(ctx2, x, sampler, steps, guidance, schedule, eta, first, seed, image_index, step_noise)
-            return self.decode(z, mode=1)
-        x = self.encode(init_u8, seed, image_index, strength, steps, noise)
-        z = self.sample_ddim_from(ctx2, x, t_enc, steps, guidance, trace)
+        z = self._sample_from(sampler, ctx2, lambda a, b: self.encode(init_u8, seed, image_index, strength, steps, noise, coef=(a, b)),
+                              t_enc, steps, guidance, schedule, eta, seed, image_index, step_noise, trace)
         return self.decode(z, mode=1)
 
     def img2img_graphed(self, ctx2, init_u8, strength=0.75, steps=50, guidance=7.5, seed=0, noise=None, image_index=0, sampler=None,
                         schedule='discrete', eta=1.0, step_noise=None):
         """img2img() as ONE device graph replay (encoder, start latent, every UNet evaluation, DDIM updates, decoder, uint8), captured
-        once per (t_enc, steps, guidance, shape) from the eager path.  The noise is always an input of the graph: without `noise`
-        it is drawn into it first by sdod_randn_f32 on the streams encode() uses, which is what the encoder's in-kernel draw gives
-        bit for bit, so the result equals img2img() with the same arguments.  With a k-sampler the key adds (sampler, schedule, eta),
-        and euler_a's step noise is one more input of the graph, filled the same way."""
+        once per (t_enc, steps, guidance, shape) from the eager path.  The noise is always an input of the graph, the caller's or drawn
+        on the streams encode() uses (_replay), so the result equals img2img() with the same arguments.  With a k-sampler the key adds
+        (sampler, schedule, eta), and euler_a's step noise is one more input of the graph."""
         t_enc = img2img_k_check_args(strength, steps, sampler, schedule, eta, step_noise, self._latent_shape, init_u8.shape[0])
-        kw = dict(sampler=sampler, schedule=schedule, eta=eta)
+        kw = dict(strength=strength, steps=steps, guidance=guidance, sampler=sampler, schedule=schedule, eta=eta)
         if self.cfg_split:
-            return self.img2img(ctx2, init_u8, strength, steps, guidance, seed, noise, image_index, step_noise=step_noise, **kw)
+            return self.img2img(ctx2, init_u8, seed=seed, noise=noise, image_index=image_index, step_noise=step_noise, **kw)
         lat = (init_u8.shape[0],) + self._latent_shape
         key = ('img2img', t_enc, int(steps), float(guidance), tuple(init_u8.shape))
-        inputs = [(ctx2.shape, ctx2.dtype), (init_u8.shape, torch.uint8), (lat, torch.float32), (lat, torch.float32)]
         if sampler is not None:
             key += (sampler, schedule, float(eta))
+        inputs = dict(ctx2=_copied(ctx2), init_u8=_copied(init_u8, torch.uint8), **_noise_pair(noise, lat, seed, image_index))
         if sampler == 'euler_a':
-            g, (s_ctx, s_img, s_n1, s_n2, s_sn), out = self._graphed(
-                key, inputs + [((t_enc - 1,) + lat, torch.float32)],
-                lambda c, img, n1, n2, sn: self.img2img(c, img, strength, steps, guidance, noise=(n1, n2), step_noise=sn, **kw))
-            self._fill_step_noise(s_sn, step_noise, seed, int(steps) - t_enc, image_index)
-        else:
-            g, (s_ctx, s_img, s_n1, s_n2), out = self._graphed(
-                key, inputs, lambda c, img, n1, n2: self.img2img(c, img, strength, steps, guidance, noise=(n1, n2), **kw))
-        s_ctx.copy_(ctx2); s_img.copy_(init_u8)
-        if noise is None:
-            self._fill_noise(s_n1, seed, 1, image_index)
-            self._fill_noise(s_n2, seed, 2, image_index)
-        else:
-            s_n1.copy_(noise[0]); s_n2.copy_(noise[1])
-        g.replay()
-        return out
+            inputs['step_noise'] = _step_noise(step_noise, (t_enc - 1,) + lat, seed, int(steps) - t_enc, image_index)
+        return self._replay(key, lambda n1, n2, **s: self.img2img(noise=(n1, n2), **s, **kw), inputs)
 
     # ------------------------------------------------------------------ inpainting (ldm DDIMSampler.ddim_sampling(mask=, x0=) on img2img's start)
     def sample_ddim_inpaint(self, ctx2, x, z0, keep, t_enc, steps=50, guidance=7.5, seed=0, image_index=0, step_noise=None, trace=None):
@@ -663,31 +672,17 @@ class Txt2Img:
                         image_index=0, composite=True):
         """inpaint() as ONE device graph replay (mask reduction, encoder, start latent, every UNet evaluation and fused step, decoder,
         composite), captured once per (t_enc, steps, guidance, composite, shape) from the eager path.  Image, mask and all noise are
-        inputs of the graph: without `noise` / `step_noise` they are drawn into it first by sdod_randn_f32 on the streams the eager
-        path draws in its kernels, bit for bit, so the result equals inpaint() with the same arguments.  Eager under cfg_split."""
+        inputs of the graph, the caller's or drawn on the eager path's streams (_replay), so the result equals inpaint() with the same
+        arguments.  Eager under cfg_split."""
         t_enc = self._inpaint_args(init_u8, mask_u8, strength, steps, step_noise)
+        kw = dict(strength=strength, steps=steps, guidance=guidance, composite=composite)
         if self.cfg_split:
-            return self.inpaint(ctx2, init_u8, mask_u8, strength, steps, guidance, seed, noise, step_noise, image_index, composite)
+            return self.inpaint(ctx2, init_u8, mask_u8, seed=seed, noise=noise, step_noise=step_noise, image_index=image_index, **kw)
         lat = (init_u8.shape[0],) + self._latent_shape
         key = ('inpaint', t_enc, int(steps), float(guidance), bool(composite), tuple(init_u8.shape))
-        g, (s_ctx, s_img, s_mask, s_n1, s_n2, s_sn), out = self._graphed(
-            key, [(ctx2.shape, ctx2.dtype), (init_u8.shape, torch.uint8), (mask_u8.shape, torch.uint8), (lat, torch.float32),
-                  (lat, torch.float32), ((t_enc - 1,) + lat, torch.float32)],
-            lambda c, img, mask, n1, n2, sn: self.inpaint(c, img, mask, strength, steps, guidance, noise=(n1, n2), step_noise=sn,
-                                                          composite=composite))
-        s_ctx.copy_(ctx2); s_img.copy_(init_u8); s_mask.copy_(mask_u8)
-        if noise is None:
-            self._fill_noise(s_n1, seed, 1, image_index)
-            self._fill_noise(s_n2, seed, 2, image_index)
-        else:
-            s_n1.copy_(noise[0]); s_n2.copy_(noise[1])
-        if step_noise is None:
-            for j in range(t_enc - 1):
-                self._fill_noise(s_sn[j], seed, 3 + j, image_index)
-        else:
-            s_sn.copy_(step_noise)
-        g.replay()
-        return out
+        inputs = dict(ctx2=_copied(ctx2), init_u8=_copied(init_u8), mask_u8=_copied(mask_u8), **_noise_pair(noise, lat, seed, image_index),
+                      step_noise=_step_noise(step_noise, (t_enc - 1,) + lat, seed, 0, image_index))
+        return self._replay(key, lambda n1, n2, **s: self.inpaint(noise=(n1, n2), **s, **kw), inputs)
 
     # ------------------------------------------------------------------ inpainting with a 9-channel UNet (runwayml inpaint_st.py, ldm `hybrid`)
     def _inpaint_concat_args(self, init_u8, mask_u8, x_T, steps, sampler, noise):
@@ -731,23 +726,17 @@ class Txt2Img:
                                image_index=0, composite=True):
         """inpaint_concat() as ONE device graph replay (masked encoder, conditioning, every UNet evaluation and sampler update, decoder,
         composite), captured once per (sampler, steps, guidance, composite, shape) from the eager path.  Image, mask, x_T and the noise
-        are inputs of the graph: without `noise` it is drawn into it first by sdod_randn_f32 on the stream the eager path draws in
-        its kernel, bit for bit, so the result equals inpaint_concat() with the same arguments.  Eager under cfg_split."""
+        are inputs of the graph, the noise the caller's or drawn on the eager path's stream (_replay), so the result equals
+        inpaint_concat() with the same arguments.  Eager under cfg_split."""
         self._inpaint_concat_args(init_u8, mask_u8, x_T, steps, sampler, noise)
+        kw = dict(steps=steps, guidance=guidance, sampler=sampler, composite=composite)
         if self.cfg_split:
-            return self.inpaint_concat(ctx2, init_u8, mask_u8, x_T, steps, guidance, sampler, seed, noise, image_index, composite)
+            return self.inpaint_concat(ctx2, init_u8, mask_u8, x_T, seed=seed, noise=noise, image_index=image_index, **kw)
         lat = (init_u8.shape[0],) + self._latent_shape
         key = ('inpaint_concat', sampler, int(steps), float(guidance), bool(composite), tuple(init_u8.shape))
-        g, (s_ctx, s_img, s_mask, s_x, s_n1), out = self._graphed(
-            key, [(ctx2.shape, ctx2.dtype), (init_u8.shape, torch.uint8), (mask_u8.shape, torch.uint8), (lat, torch.float32), (lat, torch.float32)],
-            lambda c, img, mask, x, n1: self.inpaint_concat(c, img, mask, x, steps, guidance, sampler, noise=n1, composite=composite))
-        s_ctx.copy_(ctx2); s_img.copy_(init_u8); s_mask.copy_(mask_u8); s_x.copy_(x_T)
-        if noise is None:
-            self._fill_noise(s_n1, seed, 1, image_index)
-        else:
-            s_n1.copy_(noise)
-        g.replay()
-        return out
+        inputs = dict(ctx2=_copied(ctx2), init_u8=_copied(init_u8), mask_u8=_copied(mask_u8), x_T=_copied(x_T, torch.float32),
+                      noise=_noise(noise, lat, seed, 1, image_index))
+        return self._replay(key, lambda **s: self.inpaint_concat(**s, **kw), inputs)
 
     # ------------------------------------------------------------------ hires: sample small, resize the latent, img2img at the target size
     def hires_from_latent(self, ctx2, z_lo, sampler='dpmpp_2m', guidance=7.5, *, hires_steps, hires_seed, denoise=0.7, upscaler='bilinear',
@@ -771,17 +760,9 @@ class Txt2Img:
         z_lo = z_lo.to(self.device, torch.float32).contiguous()
         if hires_noise is not None:
             hires_noise = hires_noise.to(self.device, torch.float32).contiguous()
-        if sampler in K_SAMPLERS:
-            first = hires_steps - t_enc
-            a, b = 1.0, float(KSchedule(hires_steps, schedule).sigmas[first])
-        else:
-            sch = PlmsSchedule(hires_steps)
-            a, b = float(sch.sqrt_alphas[t_enc]), float(sch.sqrt_one_minus_alphas[t_enc])
-        x = ops.latent_resize(z_lo, hi._latent_shape[1:], upscaler, a, b, hires_noise, hires_seed, image_index)
-        if sampler in K_SAMPLERS:
-            z = hi.sample_k(ctx2, x, sampler, hires_steps, guidance, schedule, eta, first, hires_seed, image_index, hires_step_noise)
-        else:
-            z = hi.sample_ddim_from(ctx2, x, t_enc, hires_steps, guidance)
+        z = hi._sample_from(sampler if sampler in K_SAMPLERS else None, ctx2,
+                            lambda a, b: ops.latent_resize(z_lo, hi._latent_shape[1:], upscaler, a, b, hires_noise, hires_seed, image_index),
+                            t_enc, hires_steps, guidance, schedule, eta, hires_seed, image_index, hires_step_noise)
         return hi.decode(z, mode=1)
 
     def generate_hires(self, ctx2, x_T, steps=20, guidance=7.5, sampler='dpmpp_2m', *, hires_steps=None, denoise=0.7, upscaler='bilinear',
@@ -797,10 +778,8 @@ class Txt2Img:
         k_check_args(sampler, steps, sched1, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
         hires_check_args(self, x_T.shape[0], sampler, hires_steps, denoise, upscaler, schedule, eta, hires_noise, hires_step_noise)
         hires_seed = int(seed) + 1 if hires_seed is None else hires_seed
-        if sampler in K_SAMPLERS:
-            z_lo = self.sample_k(ctx2, x_T, sampler, steps, guidance, schedule, eta, 0, seed, image_index, step_noise)
-        else:
-            z_lo = self._sample(sampler, ctx2, x_T, steps, guidance)
+        z_lo = self._sample(sampler, ctx2, x_T, steps, guidance, schedule=schedule, eta=eta, seed=seed, image_index=image_index,
+                            step_noise=step_noise)
         return self.hires_from_latent(ctx2, z_lo, sampler, guidance, hires_steps=hires_steps, denoise=denoise, upscaler=upscaler,
                                       schedule=schedule, eta=eta, hires_seed=hires_seed, image_index=image_index, hires_noise=hires_noise,
                                       hires_step_noise=hires_step_noise)
@@ -810,36 +789,23 @@ class Txt2Img:
                                hires_noise=None, hires_step_noise=None):
         """generate_hires() as ONE device graph replay (both trajectories, the resize, the decode), captured once per (sampler, steps,
         hires_steps, t_enc, guidance, upscaler, schedule, eta, shape) from the eager path.  ctx2, x_T and all noise are inputs of the
-        graph: what the caller does not pass is drawn into them first by sdod_randn_f32 on the streams the eager path draws in its
-        kernels, bit for bit, so the graph bakes no seed and the result equals generate_hires() with the same arguments."""
+        graph, the caller's or drawn on the eager path's streams (_replay), so the result equals generate_hires() with the same
+        arguments."""
         sched1 = schedule if sampler in K_SAMPLERS else 'discrete'
         hires_steps = steps if hires_steps is None else hires_steps
         k_check_args(sampler, steps, sched1, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
         t_enc = hires_check_args(self, x_T.shape[0], sampler, hires_steps, denoise, upscaler, schedule, eta, hires_noise, hires_step_noise)
         hires_steps = int(hires_steps)
         hires_seed = int(seed) + 1 if hires_seed is None else hires_seed
-        kw = dict(hires_steps=hires_steps, denoise=denoise, upscaler=upscaler, schedule=schedule, eta=eta)
-        n = x_T.shape[0]
-        lat_hi = (n,) + self.hires._latent_shape
+        kw = dict(steps=steps, guidance=guidance, sampler=sampler, hires_steps=hires_steps, denoise=denoise, upscaler=upscaler,
+                  schedule=schedule, eta=eta)
+        lat_hi = (x_T.shape[0],) + self.hires._latent_shape
         key = ('hires', sampler, int(steps), hires_steps, t_enc, float(guidance), upscaler, schedule, float(eta), tuple(x_T.shape))
-        inputs = [(ctx2.shape, ctx2.dtype), (x_T.shape, torch.float32), (lat_hi, torch.float32)]
+        inputs = dict(ctx2=_copied(ctx2), x_T=_copied(x_T, torch.float32), hires_noise=_noise(hires_noise, lat_hi, hires_seed, 2, image_index))
         if sampler == 'euler_a':
-            g, (s_ctx, s_x, s_hn, s_sn, s_hsn), out = self._graphed(
-                key, inputs + [((int(steps) - 1,) + tuple(x_T.shape), torch.float32), ((t_enc - 1,) + lat_hi, torch.float32)],
-                lambda c, x, hn, sn, hsn: self.generate_hires(c, x, steps, guidance, sampler, step_noise=sn, hires_noise=hn,
-                                                              hires_step_noise=hsn, **kw))
-            self._fill_step_noise(s_sn, step_noise, seed, 0, image_index)
-            self._fill_step_noise(s_hsn, hires_step_noise, hires_seed, hires_steps - t_enc, image_index)
-        else:
-            g, (s_ctx, s_x, s_hn), out = self._graphed(
-                key, inputs, lambda c, x, hn: self.generate_hires(c, x, steps, guidance, sampler, hires_noise=hn, **kw))
-        s_ctx.copy_(ctx2); s_x.copy_(x_T)
-        if hires_noise is None:
-            self._fill_noise(s_hn, hires_seed, 2, image_index)
-        else:
-            s_hn.copy_(hires_noise)
-        g.replay()
-        return out
+            inputs['step_noise'] = _step_noise(step_noise, (int(steps) - 1,) + tuple(x_T.shape), seed, 0, image_index)
+            inputs['hires_step_noise'] = _step_noise(hires_step_noise, (t_enc - 1,) + lat_hi, hires_seed, hires_steps - t_enc, image_index)
+        return self._replay(key, lambda **s: self.generate_hires(**s, **kw), inputs)
 
     def generate_pipelined(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms'):
         """generate_graphed() as TWO device graphs -- sampling (context upload, every UNet evaluation, CFG, sampler updates) on
@@ -876,6 +842,42 @@ class Txt2Img:
             g_d.replay()
             c['decoded'] = torch.cuda.Event(); c['decoded'].record(c['side'])
         return out, c['decoded']
+
+
+# the descriptions of a graph's static inputs (Txt2Img._replay): (shape, dtype, value, draw) -- `value` the caller's tensor to copy, or
+# None for noise to be drawn as draw = (seed, family, image_index) says (Txt2Img._fill)
+def _copied(value, dtype=None):
+    """a tensor the caller always passes; the static takes its shape and `dtype` (default: its own)"""
+    return (tuple(value.shape), value.dtype if dtype is None else dtype, value, None)
+
+
+def _noise(value, shape, seed, family, image_index):
+    """one fp32 noise tensor [n, 4, H, W]: the caller's, or None = Philox family `family` of `seed`"""
+    return (tuple(shape), torch.float32, value, (seed, family, image_index))
+
+
+def _step_noise(value, shape, seed, first, image_index):
+    """fp32 step-noise rows [rows, n, 4, H, W], row r = the noise of step first + r: the caller's, or None = family 3 + first + r"""
+    return _noise(value, shape, seed, 3 + first, image_index)
+
+
+def _noise_pair(noise, lat, seed, image_index):
+    """encode()'s noise=(n1, n2) as the two statics n1, n2 (families 1 and 2); `run` puts the pair together again"""
+    n1, n2 = (None, None) if noise is None else noise
+    return dict(n1=_noise(n1, lat, seed, 1, image_index), n2=_noise(n2, lat, seed, 2, image_index))
+
+
+def _want_tensor(name, t, shape, dtype=None, note=''):
+    """ValueError unless t is a tensor of exactly `shape` (and of `dtype`, when one is given); the message names both"""
+    if not isinstance(t, torch.Tensor) or (dtype is not None and t.dtype != dtype) or tuple(t.shape) != tuple(shape):
+        kind = 'a tensor' if dtype is None else f'a {str(dtype).replace("torch.", "")} tensor'
+        raise ValueError(f'{name} must be {kind} {tuple(shape)}{note}, got {tuple(getattr(t, "shape", ()))} {getattr(t, "dtype", type(t))}')
+
+
+def _want_steps(name, steps):
+    """ValueError unless steps is a positive integer (an integral float passes, a bool does not)"""
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+        raise ValueError(f'{name} must be a positive integer, got {steps!r}')
 
 
 def img2img_schedule(strength, steps):
@@ -927,8 +929,7 @@ def hires_check_args(pipe, n_images, sampler, hires_steps, denoise, upscaler, sc
         raise ValueError(f'upscaler must be one of {HIRES_UPSCALERS}, got {upscaler!r}')
     if sampler not in ('plms', 'dpm') + K_SAMPLERS:
         raise ValueError(f"sampler must be one of {('plms', 'dpm') + K_SAMPLERS}, got {sampler!r}")
-    if isinstance(hires_steps, bool) or int(hires_steps) != hires_steps or int(hires_steps) < 1:
-        raise ValueError(f'hires_steps must be a positive integer, got {hires_steps!r}')
+    _want_steps('hires_steps', hires_steps)
     _, t_enc = img2img_schedule(denoise, hires_steps)
     latent = pipe.hires._latent_shape
     if sampler in K_SAMPLERS:
@@ -938,11 +939,8 @@ def hires_check_args(pipe, n_images, sampler, hires_steps, denoise, upscaler, sc
             raise ValueError(f"sampler {sampler!r}'s second pass is ldm's DDIM img2img loop, which has no v-conversion: use a k-sampler with model='sd21'")
         if hires_step_noise is not None:
             raise ValueError(f"hires_step_noise is euler_a's fresh noise; the DDIM second pass of sampler {sampler!r} draws none")
-    want = (n_images,) + tuple(latent)
-    if hires_noise is not None and (not isinstance(hires_noise, torch.Tensor) or hires_noise.dtype != torch.float32 or
-                                    tuple(hires_noise.shape) != want):
-        raise ValueError(f'hires_noise must be an fp32 tensor {want}, got {tuple(getattr(hires_noise, "shape", ()))} '
-                         f'{getattr(hires_noise, "dtype", type(hires_noise))}')
+    if hires_noise is not None:
+        _want_tensor('hires_noise', hires_noise, (n_images,) + tuple(latent), torch.float32)
     return t_enc
 
 
@@ -954,8 +952,7 @@ def k_check_args(sampler, steps, schedule, eta, step_noise, latent, n_images, fi
     old = ('plms', 'dpm') if old_samplers else ()
     if sampler not in K_SAMPLERS + old:
         raise ValueError(f'sampler must be one of {old + K_SAMPLERS}, got {sampler!r}')
-    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
-        raise ValueError(f'steps must be a positive integer, got {steps!r}')
+    _want_steps('steps', steps)
     if int(first) != first or not 0 <= first < steps:
         raise ValueError(f'first must be an integer in [0, steps - 1] = [0, {int(steps) - 1}], got {first!r}')
     if schedule not in K_SCHEDULES:
@@ -970,10 +967,8 @@ def k_check_args(sampler, steps, schedule, eta, step_noise, latent, n_images, fi
     if step_noise is not None:
         if sampler != 'euler_a':
             raise ValueError(f"step_noise is euler_a's fresh noise; sampler {sampler!r} draws none")
-        want = (int(steps) - int(first) - 1, n_images) + tuple(latent)
-        if not isinstance(step_noise, torch.Tensor) or step_noise.dtype != torch.float32 or tuple(step_noise.shape) != want:
-            raise ValueError(f'step_noise must be an fp32 tensor {want} (one row per step but the last), got '
-                             f'{tuple(getattr(step_noise, "shape", ()))} {getattr(step_noise, "dtype", type(step_noise))}')
+        _want_tensor('step_noise', step_noise, (int(steps) - int(first) - 1, n_images) + tuple(latent), torch.float32,
+                     ' (one row per step but the last)')
 
 
 def img2img_k_check_args(strength, steps, sampler, schedule, eta, step_noise, latent, n_images):
@@ -1027,9 +1022,7 @@ def inpaint_check_args(init_u8, mask_u8, strength, steps, step_noise, latent, n_
     n = inpaint_check_images(init_u8, mask_u8, latent, n_images)
     sch, t_enc = img2img_schedule(strength, steps)
     if step_noise is not None:
-        want = (t_enc - 1, n) + tuple(latent)
-        if not isinstance(step_noise, torch.Tensor) or tuple(step_noise.shape) != want:
-            raise ValueError(f'step_noise must be {want} (t_enc - 1 = {t_enc - 1} noise levels), got {tuple(getattr(step_noise, "shape", ()))}')
+        _want_tensor('step_noise', step_noise, (t_enc - 1, n) + tuple(latent), note=f' (t_enc - 1 = {t_enc - 1} noise levels)')
     return sch, t_enc
 
 
@@ -1045,8 +1038,8 @@ def inpaint_concat_check_args(init_u8, mask_u8, x_T, steps, sampler, noise, late
         raise ValueError(f"sampler must be 'plms' or 'dpm', got {sampler!r}")
     if int(steps) != steps or int(steps) < 1:
         raise ValueError(f'steps must be a positive integer, got {steps!r}')
-    if noise is not None and (not isinstance(noise, torch.Tensor) or tuple(noise.shape) != want):
-        raise ValueError(f'noise must be {want} (the posterior sample\'s normal draw), got {tuple(getattr(noise, "shape", ()))}')
+    if noise is not None:
+        _want_tensor('noise', noise, want, note=" (the posterior sample's normal draw)")
 
 
 def broadcast_conditioning(ctx2, src=0):

@@ -335,3 +335,118 @@ def test_entry_points_refuse_before_any_device_work():
     for name in K_SAMPLERS:
         with pytest.raises(ValueError):
             pipe.generate_pipelined(None, x_T, 20, 7.5, name)
+
+
+# ------------------------------------------------------------------ the graphed entry points' static inputs, without a device
+def test_graphed_entry_points_fill_their_static_inputs(monkeypatch):
+    """Each *_graphed method describes its graph's static inputs to Txt2Img._replay; here _graphed hands out CPU statics and a graph that
+    counts its replays, and ops.randn records what would be drawn.  The draws are compared with the rule written out by hand: image i of
+    a noise input comes from Philox stream (family << 32) | (image_index + i) of the seed, family 1 = n1, 2 = n2 (of hires_seed = seed + 1:
+    hires_noise), 3 + first + r = row r of the step noise, first = 0 for a whole trajectory and steps - t_enc for one that starts at a
+    level.  One image per call here, image_index 3, so every stream ends in 3."""
+    import inspect
+    from sdod.amd import engine as E, ops
+    from sdod.amd.pipeline import Txt2Img
+
+    def bare(h, w):
+        p = Txt2Img.__new__(Txt2Img)
+        p.cfg, p.n, p.device, p.cfg_split = E.sd14_config(h, w), 1, torch.device('cpu'), False
+        return p
+    pipe = bare(16, 24)
+    pipe.hires = bare(24, 32)
+    pipe.encoder = pipe.masked_encoder = object()                       # the entry points only ask whether they exist
+    calls, draws = [], []
+
+    class Graph:
+        replays = 0
+
+        def replay(self):
+            self.replays += 1
+
+    def graphed(key, inputs, run):
+        statics = [torch.zeros(tuple(shape), dtype=dtype) for shape, dtype in inputs]
+        run(*statics)                                                   # the eager twin below: the statics arrive under its argument names
+        calls.append((Graph(), [(tuple(shape), dtype) for shape, dtype in inputs], statics))
+        return calls[-1][0], statics, 'out'
+
+    def randn(shape, seed, stream_id, device, out=None):
+        assert tuple(out.shape) == tuple(shape) and out.dtype == torch.float32
+        draws.append((tuple(shape), seed, stream_id))
+        return out
+    monkeypatch.setattr(pipe, '_graphed', graphed)
+    monkeypatch.setattr(ops, 'randn', randn)
+    for name in ('generate', 'img2img', 'inpaint', 'inpaint_concat', 'generate_hires'):
+        sig = inspect.signature(getattr(Txt2Img, name))
+        monkeypatch.setattr(pipe, name, lambda *a, _sig=sig, **kw: _sig.bind(pipe, *a, **kw))      # TypeError for a name the eager method lacks
+
+    def call(fn, *a, **kw):
+        del draws[:]
+        n = len(calls)
+        assert fn(*a, **kw) == 'out' and len(calls) == n + 1 and calls[-1][0].replays == 1
+        return calls[-1][1], calls[-1][2], sorted(draws)
+
+    lo, hi = (1, 4, 16, 24), (1, 4, 24, 32)
+    f16, f32, u8 = torch.float16, torch.float32, torch.uint8
+    ctx = torch.full((2, 77, 768), 0.5, dtype=f16)
+    img, mask = torch.full((1, 128, 192, 3), 7, dtype=u8), torch.full((1, 128, 192), 255, dtype=u8)
+    x_T = torch.full(lo, 2.0)
+    c_, i_, m_ = (tuple(ctx.shape), f16), (tuple(img.shape), u8), (tuple(mask.shape), u8)
+
+    def stream(family):
+        return (family << 32) | 3
+    at = dict(seed=31, image_index=3)
+
+    # no noise passed: everything is drawn
+    req, _, got = call(pipe.generate_graphed, ctx, x_T, 4, 7.5, 'euler_a', **at)
+    assert req == [c_, (lo, f32), ((3,) + lo, f32)]
+    assert got == sorted((lo, 31, stream(f)) for f in (3, 4, 5))
+    req, _, got = call(pipe.img2img_graphed, ctx, img, 0.5, 6, 7.5, sampler='euler_a', **at)            # t_enc = 3, first = 3
+    assert req == [c_, i_, (lo, f32), (lo, f32), ((2,) + lo, f32)]
+    assert got == sorted((lo, 31, stream(f)) for f in (1, 2, 6, 7))
+    req, _, got = call(pipe.inpaint_graphed, ctx, img, mask, 0.5, 6, 7.5, **at)                         # t_enc = 3
+    assert req == [c_, i_, m_, (lo, f32), (lo, f32), ((2,) + lo, f32)]
+    assert got == sorted((lo, 31, stream(f)) for f in (1, 2, 3, 4))
+    req, _, got = call(pipe.inpaint_concat_graphed, ctx, img, mask, x_T, 4, 7.5, 'plms', **at)
+    assert req == [c_, i_, m_, (lo, f32), (lo, f32)]
+    assert got == [(lo, 31, stream(1))]
+    req, _, got = call(pipe.generate_hires_graphed, ctx, x_T, 4, 7.5, 'euler_a', hires_steps=6, denoise=0.5, **at)   # t_enc = 3, first = 3
+    assert req == [c_, (lo, f32), (hi, f32), ((3,) + lo, f32), ((2,) + hi, f32)]
+    assert got == sorted([(lo, 31, stream(f)) for f in (3, 4, 5)] + [(hi, 32, stream(f)) for f in (2, 6, 7)])
+    _, _, got = call(pipe.generate_hires_graphed, ctx, x_T, 4, 7.5, 'euler_a', hires_steps=6, denoise=0.5, hires_seed=90, **at)
+    assert got == sorted([(lo, 31, stream(f)) for f in (3, 4, 5)] + [(hi, 90, stream(f)) for f in (2, 6, 7)])
+
+    # every noise passed: nothing is drawn, the statics hold the caller's values
+    n1, n2, sn2, sn3 = torch.full(lo, 1.0), torch.full(lo, -2.0), torch.full((2,) + lo, 3.0), torch.full((3,) + lo, 4.0)
+    hn, hsn = torch.full(hi, 5.0), torch.full((2,) + hi, 6.0)
+    for fn, a, kw, want in (
+            (pipe.generate_graphed, (ctx, x_T, 4, 7.5, 'euler_a'), dict(step_noise=sn3), [ctx, x_T, sn3]),
+            (pipe.img2img_graphed, (ctx, img, 0.5, 6, 7.5), dict(sampler='euler_a', noise=(n1, n2), step_noise=sn2), [ctx, img, n1, n2, sn2]),
+            (pipe.inpaint_graphed, (ctx, img, mask, 0.5, 6, 7.5), dict(noise=(n1, n2), step_noise=sn2), [ctx, img, mask, n1, n2, sn2]),
+            (pipe.inpaint_concat_graphed, (ctx, img, mask, x_T, 4, 7.5, 'plms'), dict(noise=n1), [ctx, img, mask, x_T, n1]),
+            (pipe.generate_hires_graphed, (ctx, x_T, 4, 7.5, 'euler_a'),
+             dict(hires_steps=6, denoise=0.5, step_noise=sn3, hires_noise=hn, hires_step_noise=hsn), [ctx, x_T, hn, sn3, hsn])):
+        _, statics, got = call(fn, *a, **kw, **at)
+        assert got == [] and len(statics) == len(want)
+        assert all(torch.equal(s, w) for s, w in zip(statics, want))
+
+    # a sampler that draws no step noise gets no step-noise input
+    for sampler in ('dpmpp_2m', 'euler', 'plms', 'dpm'):
+        req, _, got = call(pipe.generate_graphed, ctx, x_T, 4, 7.5, sampler, **at)
+        assert req == [c_, (lo, f32)] and got == []
+    req, _, got = call(pipe.img2img_graphed, ctx, img, 0.5, 6, 7.5, **at)
+    assert req == [c_, i_, (lo, f32), (lo, f32)] and got == sorted((lo, 31, stream(f)) for f in (1, 2))
+    req, _, got = call(pipe.generate_hires_graphed, ctx, x_T, 4, 7.5, 'dpmpp_2m', hires_steps=6, denoise=0.5, **at)
+    assert req == [c_, (lo, f32), (hi, f32)] and got == [(hi, 32, stream(2))]
+
+    # under cfg_split the four entry points with an eager fallback hand every argument to their eager twin and capture nothing
+    pipe.cfg_split, n = True, len(calls)
+    for fn, a, kw in ((pipe.generate_graphed, (ctx, x_T, 4, 7.5, 'euler_a'), dict(schedule='karras', eta=0.5, step_noise=sn3)),
+                      (pipe.img2img_graphed, (ctx, img, 0.5, 6, 7.5),
+                       dict(sampler='euler_a', schedule='karras', eta=0.5, noise=(n1, n2), step_noise=sn2)),
+                      (pipe.inpaint_graphed, (ctx, img, mask, 0.5, 6, 7.5), dict(noise=(n1, n2), step_noise=sn2, composite=False)),
+                      (pipe.inpaint_concat_graphed, (ctx, img, mask, x_T, 4, 7.5, 'dpm'), dict(noise=n1, composite=False))):
+        twin = getattr(Txt2Img, fn.__name__[:-len('_graphed')])
+        want = inspect.signature(twin).bind(pipe, *a, **kw, **at).arguments
+        got = fn(*a, **kw, **at).arguments
+        assert got.keys() == want.keys() and all(got[k] is want[k] or got[k] == want[k] for k in want), fn.__name__
+    assert len(calls) == n
