@@ -20,6 +20,11 @@
  *                 in3 cond fp32 NCHW [B][concat_channels][H][W]  only with sdod_model_config.concat_channels > 0 (an inpainting
  *                                                        checkpoint, ldm `c_concat`): mask (1) | latent of the masked image (4),
  *                                                        read by the input convolution next to in0; constant over a sampler run
+ *                 in3..6 (in4..7 with concat_channels) feat fp16 NHWC [B / r][H / s][W / s][C], (s, C) = (1, MC), (2, 2 MC), (4, 4 MC),
+ *                                                        (8, 4 MC): only with sdod_adapter_config.adapter_reps = r > 0 (T2I-Adapter
+ *                                                        features): added in place behind ldm's input_blocks.2, .5,
+ *                                                        .8 and .11, before the tensor becomes a skip, to each of the r guidance
+ *                                                        copies of the batch.  Zero after finalize; constant over a sampler run
  *                 out0 e   fp16 NHWC [B][H][W][4]        (context.cpp:218  e = unet.allocate_output(0))
  *   TEMB          in0 t    fp32 [B]                      (model time, dpm_solver.cpp:115)
  *                 out0     fp16 [B][E]                   (context.cpp:257-278: sinusoid + temb graph, + emb_layers)
@@ -32,6 +37,11 @@
  *                                                        reference, which has no img2img)
  *   VAE_ENCODER_MASKED  in0 img uint8 HWC [B][8H][8W][3], in1 mask uint8 [B][8H][8W]: the same graph and parameters on the masked
  *                 image of inpainting, x = mask >= 128 ? 0 : 2 u / 255 - 1 (only the first launch differs); out0 as VAE_ENCODER
+ *   ADAPTER       in0 hint uint8 HWC [B][8H][8W][adapter_hint_channels]   (an edge map, depth map, sketch or pose skeleton)
+ *                 out0..3  fp16 NHWC [B][H / s][W / s][C], the four feature maps above: TencentARC's "full" T2I-Adapter,
+ *                 Adapter(channels=[MC, 2 MC, 4 MC, 4 MC], nums_rb=adapter_res_blocks, ksize=1, sk=True, use_conv=False) on
+ *                 pixel_unshuffle8(hint / 255), parameters by the checkpoint's names (conv_in.*, body.K.{in_conv,block1,block2}.*);
+ *                 always fp16 weights.  Runs once per hint, not once per step (not part of the reference)
  *
  * Parameters are addressed by their CompVis-ldm / HF-CLIP state-dict names (without the
  * `model.diffusion_model.` / `first_stage_model.` / `cond_stage_model.transformer.` prefixes) and are
@@ -54,7 +64,7 @@ extern "C" {
 #endif
 
 enum sdod_graph_kind { SDOD_GRAPH_UNET = 0, SDOD_GRAPH_VAE_DECODER = 1, SDOD_GRAPH_TEXT_ENCODER = 2, SDOD_GRAPH_TEMB = 3,
-                       SDOD_GRAPH_VAE_ENCODER = 4, SDOD_GRAPH_VAE_ENCODER_MASKED = 5 };
+                       SDOD_GRAPH_VAE_ENCODER = 4, SDOD_GRAPH_VAE_ENCODER_MASKED = 5, SDOD_GRAPH_ADAPTER = 6 };
 
 typedef struct sdod_model_config {
     int latent_channels; /* 4 */
@@ -101,6 +111,18 @@ SDOD_API void sdod_model_config_sd14(sdod_model_config* cfg);
 SDOD_API void sdod_model_config_sd21(sdod_model_config* cfg);
 
 SDOD_API int sdod_graph_create(void** graph, int kind, const sdod_model_config* cfg, int batch);
+/* T2I-Adapter structural control.  The three values travel next to sdod_model_config, not inside it: the struct's size and field
+ * list are part of the ABI that existing callers (and their checks) were built against, and all-zero means "no adapter anywhere". */
+typedef struct sdod_adapter_config {
+    int adapter_reps;          /* UNET graph: 0 = no adapter inputs (the graph is exactly the one sdod_graph_create builds: launch list,
+                                * arena and op table); 1 or 2 = it has the four feature inputs, each shared by that many guidance
+                                * copies of the batch; must divide the batch */
+    int adapter_hint_channels; /* ADAPTER graph: 1 or 3 (conv_in takes 64 * adapter_hint_channels channels) */
+    int adapter_res_blocks;    /* ADAPTER graph: residual blocks per stage (nums_rb), 1 .. 8; 0 = 2 */
+} sdod_adapter_config;
+/* sdod_graph_create with an adapter configuration (NULL = all zero).  SDOD_GRAPH_ADAPTER can only be created here; latent_h and
+ * latent_w follow the UNet's rule (multiples of 8, at least 8).  Anything else is INVALID_ARGUMENT. */
+SDOD_API int sdod_graph_create_ex(void** graph, int kind, const sdod_model_config* cfg, const sdod_adapter_config* adapter, int batch);
 SDOD_API int sdod_graph_destroy(void* graph);
 
 /* parameter table (fixed by kind + config) */

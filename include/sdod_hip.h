@@ -35,7 +35,9 @@
 extern "C" {
 #endif
 
-enum sdod_act { SDOD_ACT_NONE = 0, SDOD_ACT_SILU = 1, SDOD_ACT_GELU = 2, SDOD_ACT_QUICK_GELU = 3 };
+/* SDOD_ACT_RELU: sdod_act_f16 only.  The GEMM epilogue's `act` is compiled into shared device code (apply_act), which stays as it
+ * is: sdod_gemm_f16 refuses it. */
+enum sdod_act { SDOD_ACT_NONE = 0, SDOD_ACT_SILU = 1, SDOD_ACT_GELU = 2, SDOD_ACT_QUICK_GELU = 3, SDOD_ACT_RELU = 4 };
 /* SDOD_U8Q (graph parameters only): per-tensor affine uint8, the reference's QNN weight format (`quantize=8`, todlc.py:108;
  * qnn_context.cpp:1018-1033): payload = {float scale; int32 offset (<= 0); uint8 q[numel]}, real = (q + offset) * scale */
 enum sdod_dtype { SDOD_F16 = 0, SDOD_F32 = 1, SDOD_U8Q = 2, SDOD_BF16 = 3 /* sdod_group_norm_nchw only */ };
@@ -279,6 +281,23 @@ SDOD_API int sdod_geglu_f16(const void* x, void* y, int m, int c, void* stream);
 SDOD_API int sdod_act_f16(const void* x, void* y, size_t n, int act, void* stream);
 SDOD_API int sdod_add_f16(const void* a, const void* b, void* y, size_t n, void* stream);
 SDOD_API int sdod_concat_channels_f16(const void* a, const void* b, void* y, size_t rows, int c0, int c1, void* stream);
+/* ---- T2I-Adapter structural control (graph kind SDOD_GRAPH_ADAPTER of include/sdod_engine.h).  Each of the four
+ * checks its arguments and returns INVALID_ARGUMENT before any launch, the destination untouched; fp32 arithmetic, every operation
+ * rounded on its own, one fp16 rounding of the result.
+ * Input of the adapter: img uint8 HWC [n][h * factor][w * factor][ch] -> y fp16 NHWC [n][h][w][ch * factor * factor],
+ *   y[b][i][j][c * factor * factor + dy * factor + dx] = fp16((float)img[b][i * factor + dy][j * factor + dx][c] / 255.0f)
+ * (torch.nn.PixelUnshuffle's channel order).  factor must be 8, ch 1 or 3, y 16-byte aligned. */
+SDOD_API int sdod_pixel_unshuffle_u8_f16(const uint8_t* img, void* y, int n, int h, int w, int ch, int factor, void* stream);
+/* AvgPool2d(2) on NHWC fp16 [n][h][w][c] -> [n][h / 2][w / 2][c]: y = fp16(((a + b) + (c + d)) * 0.25f) with a = (2i, 2j),
+ * b = (2i, 2j + 1), c = (2i + 1, 2j), d = (2i + 1, 2j + 1).  h and w even, c % 8 == 0, 16-byte aligned pointers. */
+SDOD_API int sdod_avg_pool2_f16(const void* x, void* y, int n, int h, int w, int c, void* stream);
+/* dst[i] = fp16(weight * (float)src[i]): an adapter output copied into a feature slot of the UNET graph with the conditioning weight
+ * folded in.  count % 8 == 0, weight finite, 16-byte aligned pointers. */
+SDOD_API int sdod_adapter_stage_f16(const void* src, void* dst, size_t count, float weight, void* stream);
+/* The per-step launch: h fp16 [reps][per_copy] += f fp16 [per_copy] in place, h[r][i] = fp16((float)h[r][i] + (float)f[i]); one
+ * thread loads its 16 bytes of f once and updates every copy.  reps 1 or 2 (the guidance copies, laid out as sdod_stage_unet_inputs
+ * writes them), per_copy % 8 == 0, 16-byte aligned pointers. */
+SDOD_API int sdod_add_feature_f16(void* h, const void* f, size_t per_copy, int reps, void* stream);
 SDOD_API int sdod_im2col3x3_small_f16(const void* x, void* y, int n_img, int h, int w, int c, int kpad, void* stream);
 /* sdod_latent_prep_f16 (w = NULL) followed by sdod_im2col3x3_small_f16 in one launch: x NCHW fp32 [n][c][h][w] -> the im2col matrix
  * [n*h*w][kpad] fp16 of a 3x3 pad-1 convolution (k = tap * c + channel, zero beyond 9c), values (fp16)(x * scale); kpad % 8 == 0 */

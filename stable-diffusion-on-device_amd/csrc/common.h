@@ -129,7 +129,7 @@ SDOD_DEVICE float gelu_erf_f(float x) {
 }
 SDOD_DEVICE float quick_gelu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x)); }
 
-enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_QUICK_GELU = 3 };
+enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_QUICK_GELU = 3, ACT_RELU = 4 /* sdod_act_f16 only: not in apply_act() */ };
 
 SDOD_DEVICE float apply_act(float x, int act) {
     switch (act) {

@@ -71,6 +71,78 @@ __global__ void add_kernel(const f16* a, const f16* b, f16* y, size_t n8) {
     }
 }
 
+// ---- T2I-Adapter (include/sdod_hip.h).  ReLU has a kernel of its own: apply_act() is shared with the GEMM epilogues,
+// whose instantiations stay as they are.  x < 0 ? 0 : x keeps NaN and +inf, as torch.relu does.
+__global__ void relu_kernel(const f16* x, f16* y, size_t n8) {
+    GRID_STRIDE(i, n8) {
+        const f16x8 a = ldg8(x + i * 8);
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = a[e] < (f16)0.0f ? (f16)0.0f : a[e];
+        stg8(y + i * 8, o);
+    }
+}
+
+// torch.nn.PixelUnshuffle(8) of a uint8 HWC image scaled to [0, 1]: thread = the 8 halves (dx = 0..7) of one (pixel, channel, dy), so
+// output element 8 t is the thread's first: one 16-byte store, 8 byte loads `ch` apart
+__global__ void pixel_unshuffle_kernel(const uint8_t* img, f16* y, size_t total, int h, int w, int ch) {
+    GRID_STRIDE(t, total) {
+        const int dy = (int)(t & 7);
+        const size_t q = t >> 3;
+        const int c = (int)(q % ch);
+        const size_t pix = q / ch;
+        const size_t j = pix % w, bi = pix / w; // bi = b * h + i: image rows are 8 (b * h + i) + dy in the [n][8 h] stack
+        const uint8_t* src = img + ((bi * 8 + dy) * ((size_t)w * 8) + j * 8) * ch + c;
+        f16x8 o;
+#pragma unroll
+        for (int dx = 0; dx < 8; ++dx) o[dx] = (f16)div_rn((float)src[(size_t)dx * ch], 255.0f);
+        stg8(y + t * 8, o);
+    }
+}
+
+// 2 x 2 mean, NHWC: thread = 8 channels of one output pixel; ((a + b) + (c + d)) * 0.25f in fp32, every sum rounded on its own
+__global__ void avg_pool2_kernel(const f16* x, f16* y, size_t total, int ho, int wo, int c) {
+    const int cp = c / 8;
+    GRID_STRIDE(t, total) {
+        const int c8 = (int)(t % cp) * 8;
+        const size_t pix = t / cp;
+        const size_t j = pix % wo, bi = pix / wo; // bi = b * ho + i
+        const f16* r0 = x + ((bi * 2) * ((size_t)wo * 2) + j * 2) * c + c8;
+        const f16* r1 = r0 + (size_t)wo * 2 * c;
+        const f16x8 a = ldg8(r0), b = ldg8(r0 + c), cc = ldg8(r1), d = ldg8(r1 + c);
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            o[e] = (f16)mul_rn(add_rn(add_rn((float)a[e], (float)b[e]), add_rn((float)cc[e], (float)d[e])), 0.25f);
+        stg8(y + pix * c + c8, o);
+    }
+}
+
+__global__ void adapter_stage_kernel(const f16* src, f16* dst, size_t n8, float weight) {
+    GRID_STRIDE(i, n8) {
+        const f16x8 a = ldg8(src + i * 8);
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (f16)mul_rn(weight, (float)a[e]);
+        stg8(dst + i * 8, o);
+    }
+}
+
+// the per-step kernel: one thread loads its 16 bytes of the feature once and adds them to every guidance copy of the activation
+__global__ void add_feature_kernel(f16* h, const f16* f, size_t n8, size_t per_copy, int reps) {
+    GRID_STRIDE(i, n8) {
+        const f16x8 v = ldg8(f + i * 8);
+        for (int r = 0; r < reps; ++r) {
+            f16* p = h + (size_t)r * per_copy + i * 8;
+            const f16x8 u = ldg8(p);
+            f16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (f16)add_rn((float)u[e], (float)v[e]);
+            stg8(p, o);
+        }
+    }
+}
+
 __global__ void concat_kernel(const f16* a, const f16* b, f16* y, size_t rows, int c0, int c1) {
     const int cp = (c0 + c1) / 8, cp0 = c0 / 8;
     const size_t total = rows * cp;
@@ -959,7 +1031,52 @@ extern "C" int sdod_geglu_f16(const void* x, void* y, int m, int c, void* stream
 extern "C" int sdod_act_f16(const void* x, void* y, size_t n, int act, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(x && y && n > 0 && n % 8 == 0, "bad argument (count must be a multiple of 8)");
-    LAUNCH(act_kernel, n / 8, stream, (const f16*)x, (f16*)y, n / 8, act);
+    if (act == ACT_RELU) LAUNCH(relu_kernel, n / 8, stream, (const f16*)x, (f16*)y, n / 8);
+    else LAUNCH(act_kernel, n / 8, stream, (const f16*)x, (f16*)y, n / 8, act);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_pixel_unshuffle_u8_f16(const uint8_t* img, void* y, int n, int h, int w, int ch, int factor, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(img && y && n > 0 && h > 0 && w > 0, "bad argument");
+    SDOD_REQUIRE(factor == 8, "the adapter's input is unshuffled by 8: factor must be 8");
+    SDOD_REQUIRE(ch == 1 || ch == 3, "ch must be 1 or 3");
+    SDOD_REQUIRE(((uintptr_t)y & 15) == 0, "misaligned pointer (y: 16 bytes)");
+    const size_t total = (size_t)n * h * w * ch * 8; // 16-byte lanes of y
+    LAUNCH(pixel_unshuffle_kernel, total, stream, img, (f16*)y, total, h, w, ch);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_avg_pool2_f16(const void* x, void* y, int n, int h, int w, int c, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(x && y && n > 0 && h > 0 && w > 0 && c > 0, "bad argument");
+    SDOD_REQUIRE(h % 2 == 0 && w % 2 == 0, "h and w must be even");
+    SDOD_REQUIRE(c % 8 == 0, "c must be a multiple of 8");
+    SDOD_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "misaligned pointer (16 bytes)");
+    const size_t total = (size_t)n * (h / 2) * (w / 2) * (c / 8);
+    LAUNCH(avg_pool2_kernel, total, stream, (const f16*)x, (f16*)y, total, h / 2, w / 2, c);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_adapter_stage_f16(const void* src, void* dst, size_t count, float weight, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(src && dst && count > 0 && count % 8 == 0, "bad argument (count must be a multiple of 8)");
+    SDOD_REQUIRE(std::isfinite(weight), "weight must be finite");
+    SDOD_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "misaligned pointer (16 bytes)");
+    LAUNCH(adapter_stage_kernel, count / 8, stream, (const f16*)src, (f16*)dst, count / 8, weight);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_add_feature_f16(void* h, const void* f, size_t per_copy, int reps, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(h && f && per_copy > 0 && per_copy % 8 == 0, "bad argument (per_copy must be a multiple of 8)");
+    SDOD_REQUIRE(reps == 1 || reps == 2, "reps must be 1 or 2 (the guidance copies)");
+    SDOD_REQUIRE((((uintptr_t)h | (uintptr_t)f) & 15) == 0, "misaligned pointer (16 bytes)");
+    LAUNCH(add_feature_kernel, per_copy / 8, stream, (f16*)h, (const f16*)f, per_copy / 8, per_copy, reps);
     return 0;
     SDOD_CATCH
 }

@@ -65,7 +65,7 @@ struct IoSlot {
 
 class Graph {
 public:
-    Graph(int kind, const sdod_model_config& cfg, int batch);
+    Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg = sdod_adapter_config{0, 0, 0});
     ~Graph();
     Graph(const Graph&) = delete;
 
@@ -90,6 +90,7 @@ private:
     enum Mode { DECLARE, DRY, REAL };
     int kind_;
     sdod_model_config cfg_;
+    sdod_adapter_config acfg_; // T2I-Adapter: all zero = no adapter inputs (UNET), required for kind ADAPTER
     int batch_;
     Mode mode_ = DECLARE;
     bool finalized_ = false;
@@ -178,6 +179,7 @@ private:
     void build_vae_encoder(bool masked);
     void build_clip();
     void build_temb();
+    void build_adapter();
 
     // ---- op emitters (record in REAL mode, account in DRY mode, nothing in DECLARE mode)
     struct GemmOpt {

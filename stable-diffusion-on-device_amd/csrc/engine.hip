@@ -41,13 +41,22 @@ static void parallel_for(int64_t n, F&& fn) {
 }
 
 // ------------------------------------------------------------------------------------------ lifecycle
-Graph::Graph(int kind, const sdod_model_config& cfg, int batch) : kind_(kind), cfg_(cfg), batch_(batch) {
-    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_VAE_ENCODER_MASKED, "unknown graph kind");
+Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg)
+    : kind_(kind), cfg_(cfg), acfg_(acfg), batch_(batch) {
+    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_ADAPTER, "unknown graph kind");
     SDOD_REQUIRE(batch > 0 && batch <= 64, "batch must be in [1, 64]");
     SDOD_REQUIRE(cfg.model_channels > 0 && cfg.model_channels % 64 == 0, "model_channels must be a multiple of 64");
     SDOD_REQUIRE(cfg.context_dim % 64 == 0, "context_dim must be a multiple of 64");
     SDOD_REQUIRE(cfg.context_len >= 1 && cfg.context_len <= 4096, "context_len must be in [1, 4096]");
     SDOD_REQUIRE(cfg.concat_channels >= 0, "concat_channels must not be negative");
+    SDOD_REQUIRE(acfg.adapter_reps >= 0 && acfg.adapter_reps <= 2, "adapter_reps must be 0, 1 or 2");
+    if (kind == SDOD_GRAPH_UNET && acfg.adapter_reps > 0)
+        SDOD_REQUIRE(batch % acfg.adapter_reps == 0, "adapter_reps must divide the batch");
+    if (kind == SDOD_GRAPH_ADAPTER) {
+        SDOD_REQUIRE(acfg.adapter_hint_channels == 1 || acfg.adapter_hint_channels == 3, "adapter_hint_channels must be 1 or 3");
+        SDOD_REQUIRE(acfg.adapter_res_blocks >= 0 && acfg.adapter_res_blocks <= 8, "adapter_res_blocks must be in [1, 8] (0 = 2)");
+        cfg_.weight_quant = 0; // the adapter's weights are always fp16
+    }
     mode_ = DECLARE;
     arena_reset();
     build();
@@ -964,6 +973,7 @@ void Graph::build() {
     case SDOD_GRAPH_TEXT_ENCODER: build_clip(); break;
     case SDOD_GRAPH_VAE_ENCODER: build_vae_encoder(false); break;
     case SDOD_GRAPH_VAE_ENCODER_MASKED: build_vae_encoder(true); break;
+    case SDOD_GRAPH_ADAPTER: build_adapter(); break;
     default: build_temb(); break;
     }
     settle();
@@ -1316,6 +1326,15 @@ extern "C" int sdod_graph_create(void** graph, int kind, const sdod_model_config
     SDOD_REQUIRE(graph != nullptr && cfg != nullptr, "null argument");
     *graph = nullptr;
     *graph = new Graph(kind, *cfg, batch);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_create_ex(void** graph, int kind, const sdod_model_config* cfg, const sdod_adapter_config* adapter, int batch) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr && cfg != nullptr, "null argument");
+    *graph = nullptr;
+    *graph = new Graph(kind, *cfg, batch, adapter ? *adapter : sdod_adapter_config{0, 0, 0});
     return 0;
     SDOD_CATCH
 }

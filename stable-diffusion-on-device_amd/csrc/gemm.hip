@@ -3034,6 +3034,7 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
     SDOD_REQUIRE(d->ldw >= d->K && d->ldw % (d->wq ? 16 : 8) == 0, "ldw must be >= K and keep rows 16-byte aligned");
     SDOD_REQUIRE(d->ldo >= (d->geglu ? d->N / 2 : d->N), "ldo must be >= N");
     SDOD_REQUIRE(((uintptr_t)d->a & 15) == 0 && ((uintptr_t)d->w & 15) == 0, "operands must be 16-byte aligned");
+    SDOD_REQUIRE(d->act != SDOD_ACT_RELU, "SDOD_ACT_RELU is not an epilogue activation: run sdod_act_f16 behind the GEMM");
     // the store phases move 16-byte row pieces whenever the widths allow it (vec_ok in store_ctile / the kernels): the pointers
     // must allow it too -- there is no scalar fallback for a misaligned base under aligned strides
     if ((d->geglu ? d->N / 2 : d->N) % 8 == 0 && d->ldo % 8 == 0 && (!d->residual || d->ldr % 8 == 0))

@@ -320,6 +320,11 @@ void Graph::build_unet() {
     f16* temb_in = (f16*)io_alloc(inputs_, (size_t)B * std::max(emb_total_, 1) * sizeof(f16));
     f16* ctx_in = (f16*)io_alloc(inputs_, (size_t)B * CL * cd * sizeof(f16));
     const float* cond_in = CC > 0 ? (const float*)io_alloc(inputs_, (size_t)B * CC * H * Wd * sizeof(float)) : nullptr;
+    // T2I-Adapter features: one slot per level behind the other inputs, shared by the AR guidance copies of the batch
+    const int AR = acfg_.adapter_reps;
+    const f16* feat_in[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int l = 0; AR > 0 && l < 4; ++l)
+        feat_in[l] = (const f16*)io_alloc(inputs_, (size_t)(B / AR) * (H >> l) * (Wd >> l) * mult[l] * MC * sizeof(f16));
     f16* e_out = (f16*)io_alloc(outputs_, (size_t)B * H * Wd * LC * sizeof(f16));
     Act ctx;
     ctx.p = ctx_in; ctx.n = B; ctx.h = 1; ctx.w = CL; ctx.c = cd;
@@ -387,6 +392,15 @@ void Graph::build_unet() {
                 r = t;
             }
             h = r;
+            if (AR > 0 && i == 1) {
+                // ldm input_blocks.2 / .5 / .8 / .11: h = h + features_adapter[level], BEFORE the tensor becomes a skip (TencentARC
+                // openaimodel.py).  An ordinary emit: a split-K reduce still pending on h is flushed in front of it.
+                f16* hp = h.p;
+                const f16* fp = feat_in[level];
+                const size_t per = h.numel() / AR;
+                emit([=](hipStream_t st) { check_rc2(sdod_add_feature_f16(hp, fp, per, AR, st)); }, "add_feature", 0,
+                     (double)h.numel() * 4 + (double)per * 2);
+            }
             hs.push_back(h);
         }
         if (level != 3) {
@@ -701,6 +715,77 @@ void Graph::build_vae_encoder(bool masked) {
              (double)B * ZC * H * Wd * 6);
     }
     release(m);
+}
+
+// ------------------------------------------------------------------------------------------------ T2I-Adapter
+// TencentARC's "full" adapter, Adapter(channels=[MC, 2 MC, 4 MC, 4 MC], nums_rb, ksize=1, sk=True, use_conv=False), on a uint8 hint:
+//   x = conv_in(pixel_unshuffle8(hint / 255));  for stage i, block j (k = i * nums_rb + j):  x = avg_pool2(x) when i > 0 and j == 0,
+//   then x = in_conv(x) where the width changes, then x = block2(relu(block1(x))) + x;  x behind a stage's last block is output i.
+// block2 (1x1) carries the residual in its epilogue and a stage's last one writes the output slot itself; ReLU is one in-place
+// launch (the GEMM epilogue has no such code, see SDOD_ACT_RELU).  The graph runs once per hint, not once per step.
+void Graph::build_adapter() {
+    const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, MC = cfg_.model_channels;
+    const int HC = acfg_.adapter_hint_channels, NRB = acfg_.adapter_res_blocks > 0 ? acfg_.adapter_res_blocks : 2;
+    SDOD_REQUIRE(H >= 8 && Wd >= 8 && H % 8 == 0 && Wd % 8 == 0, "the adapter needs latent_h and latent_w to be multiples of 8, at least 8");
+    const int cin = 64 * HC;
+    const int ch[4] = {MC, 2 * MC, 4 * MC, 4 * MC};
+    const uint8_t* hint = (const uint8_t*)io_alloc(inputs_, (size_t)B * (8 * H) * (8 * Wd) * HC);
+    f16* outs[4];
+    for (int i = 0; i < 4; ++i) outs[i] = (f16*)io_alloc(outputs_, (size_t)B * (H >> i) * (Wd >> i) * ch[i] * sizeof(f16));
+
+    Act u = act(B, H, Wd, cin);
+    {
+        f16* up = u.p;
+        emit([=](hipStream_t st) { check_rc2(sdod_pixel_unshuffle_u8_f16(hint, up, B, H, Wd, HC, 8, st)); }, "pixel_unshuffle", 0,
+             (double)u.numel() * 3);
+    }
+    const int ciw = P("conv_in.weight", {MC, cin, 3, 3}, PK_CONV3), cib = P("conv_in.bias", {MC}, PK_VEC);
+    Act x;
+    { GemmOpt o; o.bias = cib; x = conv(u, nullptr, ciw, MC, 3, 1, false, o); }
+    release(u);
+    bool x_in_arena = true; // a stage's output lives in its output slot, not in the arena
+    auto drop = [&](const Act& a, bool arena) { if (arena) release(a); };
+    for (int i = 0; i < 4; ++i) {
+        const int c = ch[i];
+        for (int j = 0; j < NRB; ++j) {
+            const std::string pfx = "body." + std::to_string(i * NRB + j);
+            if (i > 0 && j == 0) {
+                Act pl = act(B, x.h / 2, x.w / 2, x.c);
+                const f16* xp = x.p;
+                f16* pp = pl.p;
+                const int xh = x.h, xw = x.w, xc = x.c;
+                emit([=](hipStream_t st) { check_rc2(sdod_avg_pool2_f16(xp, pp, B, xh, xw, xc, st)); }, "avg_pool2", 0, (double)x.numel() * 2.5);
+                drop(x, x_in_arena);
+                x = pl;
+                x_in_arena = true;
+                if (ch[i] != ch[i - 1]) {
+                    const int w = P(pfx + ".in_conv.weight", {c, ch[i - 1], 1, 1}, PK_CONV1), b = P(pfx + ".in_conv.bias", {c}, PK_VEC);
+                    Act y = act(B, x.h, x.w, c);
+                    { GemmOpt o; o.bias = b; linear(x.p, x.rows(), x.c, w, c, y.p, o); }
+                    release(x);
+                    x = y;
+                }
+            }
+            const int w1 = P(pfx + ".block1.weight", {c, c, 3, 3}, PK_CONV3), b1 = P(pfx + ".block1.bias", {c}, PK_VEC);
+            const int w2 = P(pfx + ".block2.weight", {c, c, 1, 1}, PK_CONV1), b2 = P(pfx + ".block2.bias", {c}, PK_VEC);
+            Act t;
+            { GemmOpt o; o.bias = b1; t = conv(x, nullptr, w1, c, 3, 1, false, o); }
+            {
+                f16* tp = t.p;
+                const size_t cnt = t.numel();
+                emit([=](hipStream_t st) { check_rc2(sdod_act_f16(tp, tp, cnt, SDOD_ACT_RELU, st)); }, "relu", 0, (double)cnt * 4);
+            }
+            const bool last = j == NRB - 1;
+            Act y;
+            y.n = x.n; y.h = x.h; y.w = x.w; y.c = c;
+            y.p = last ? outs[i] : alloc(y.numel());
+            { GemmOpt o; o.bias = b2; o.residual = x.p; linear(t.p, t.rows(), c, w2, c, y.p, o); }
+            release(t);
+            drop(x, x_in_arena); // (a split-K reduce still pending on this GEMM reads x: release() flushes it first)
+            x = y;
+            x_in_arena = !last;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ CLIP

@@ -7,6 +7,8 @@ step for the MI355X build.  It runs on a host without a GPU: the engine's parame
 
     python -m sdod.amd.convert --ckpt sd-v1-4.ckpt --out models/          # + --tokenizer-vocab bpe_simple_vocab_16e6.txt.gz
 
+    python -m sdod.amd.convert --adapter t2iadapter_canny_sd14v1.pth --out models/     # adapter.sdodw (Txt2Img(adapter=True))
+
 Only loaders that execute nothing from the file are used: safetensors, or torch.load(weights_only=True).
 """
 import argparse
@@ -104,9 +106,66 @@ def convert(ckpt_path, out_dir, dtype=torch.float16, cfg=None, vae_encoder=False
     return written
 
 
+def adapter_config(sd):
+    """(hint_channels, nums_rb) of a TencentARC T2I-Adapter state dict of the kind the engine builds -- the "full" SD 1.x adapters,
+    Adapter(channels=[320, 640, 1280, 1280], nums_rb, ksize=1, sk=True, use_conv=False): hint_channels = conv_in.weight.shape[1] // 64,
+    nums_rb = (highest body.K + 1) // 4.  Every other layout is refused by name with ValueError: diffusers-format keys
+    (adapter.body.N.resnets.*), Adapter_light (body.N.body.M.*: the color adapter), sk=False (body.K.skep), use_conv=True
+    (body.K.down_opt.op) and a block2 that is not 1x1 (ksize=3)."""
+    import re
+    keys = list(sd)
+    if any(re.match(r'(adapter\.)?body\.\d+\.resnets\.', k) or k.startswith('adapter.') for k in keys):
+        raise ValueError('diffusers-format adapter keys (adapter.body.N.resnets.*): convert the original TencentARC .pth checkpoint')
+    if any(re.match(r'body\.\d+\.body\.\d+\.', k) for k in keys):
+        raise ValueError('Adapter_light checkpoint (keys body.N.body.M.*: the color adapter) is not supported')
+    if any(re.match(r'body\.\d+\.skep\.', k) for k in keys):
+        raise ValueError('adapter built with sk=False (keys body.K.skep.*) is not supported')
+    if any(re.match(r'body\.\d+\.down_opt\.op\.', k) for k in keys):
+        raise ValueError('adapter built with use_conv=True (keys body.K.down_opt.op.*) is not supported')
+    if 'conv_in.weight' not in sd:
+        raise ValueError('not a T2I-Adapter state dict: conv_in.weight is missing')
+    cin = int(sd['conv_in.weight'].shape[1])
+    if cin not in (64, 192):
+        raise ValueError(f'conv_in.weight takes {cin} channels: hints of 1 or 3 channels (64 or 192 after the unshuffle) are supported')
+    blocks = sorted({int(m.group(1)) for m in (re.match(r'body\.(\d+)\.', k) for k in keys) if m})
+    if not blocks or blocks != list(range(blocks[-1] + 1)) or (blocks[-1] + 1) % 4:
+        raise ValueError(f'body.K blocks {blocks[:3]}..{blocks[-1:]} are not four stages of equally many blocks')
+    for k in blocks:
+        w = sd.get(f'body.{k}.block2.weight')
+        if w is None or tuple(w.shape[2:]) != (1, 1):
+            raise ValueError(f'body.{k}.block2.weight must be a 1x1 convolution (ksize=1), got {None if w is None else tuple(w.shape)}')
+    return cin // 64, (blocks[-1] + 1) // 4
+
+
+def adapter_table(hint_channels, nums_rb=2, cfg=None):
+    """[(name, shape), ...] of the ADAPTER graph; no device needed"""
+    cfg = E.copy_config(cfg or E.sd14_config())
+    cfg.adapter_hint_channels, cfg.adapter_res_blocks = hint_channels, nums_rb
+    return E.Adapter(cfg, 1).param_table()
+
+
+def convert_adapter(path, out_dir, dtype=torch.float16):
+    """a TencentARC t2iadapter_*_sd14v1 / sd15v2 .pth -> out_dir/adapter.sdodw; returns the file written"""
+    sd = read_checkpoint(path)
+    hint_channels, nums_rb = adapter_config(sd)
+    part = {}
+    for name, shape in adapter_table(hint_channels, nums_rb):
+        if name not in sd:
+            raise KeyError(f'{name} is missing from the adapter checkpoint')
+        if tuple(sd[name].shape) != tuple(shape):
+            raise ValueError(f'{name}: checkpoint shape {tuple(sd[name].shape)} != graph shape {tuple(shape)}')
+        part[name] = sd[name].to(dtype)
+    os.makedirs(out_dir, exist_ok=True)
+    out = os.path.join(out_dir, 'adapter.sdodw')
+    weights.save(out, part)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
-    ap.add_argument('--ckpt', required=True, help='sd-v1-x .ckpt / .safetensors (ldm key names)')
+    ap.add_argument('--ckpt', help='sd-v1-x .ckpt / .safetensors (ldm key names)')
+    ap.add_argument('--adapter', help='a TencentARC T2I-Adapter checkpoint (t2iadapter_{canny,depth,sketch,seg,openpose,keypose}_sd14v1.pth): '
+                                      'write adapter.sdodw (Txt2Img(adapter=True)); with or without --ckpt')
     ap.add_argument('--out', required=True, help='models_dir to write')
     ap.add_argument('--fp32', action='store_true', help='keep fp32 payloads (the engine converts at load)')
     ap.add_argument('--model', default='sd14', choices=['sd14', 'sd21'], help='sd21: SD v2.x shapes and open_clip text-tower key names')
@@ -117,12 +176,17 @@ def main(argv=None):
     ap.add_argument('--tokenizer-vocab', help='bpe_simple_vocab_16e6.txt.gz, or a directory with HF vocab.json + merges.txt: '
                                               'also write ctokenizer.txt')
     a = ap.parse_args(argv)
+    if not a.ckpt and not a.adapter:
+        ap.error('one of --ckpt and --adapter is required')
     cfg = E.sd21_config() if a.model == 'sd21' else None
     if a.inpaint:
         cfg = cfg or E.sd14_config()
         cfg.concat_channels = 5
-    for p in convert(a.ckpt, a.out, torch.float32 if a.fp32 else torch.float16, cfg, vae_encoder=a.vae_encoder or a.inpaint):
-        print('wrote', p)
+    if a.ckpt:
+        for p in convert(a.ckpt, a.out, torch.float32 if a.fp32 else torch.float16, cfg, vae_encoder=a.vae_encoder or a.inpaint):
+            print('wrote', p)
+    if a.adapter:
+        print('wrote', convert_adapter(a.adapter, a.out, torch.float32 if a.fp32 else torch.float16))
     if a.tokenizer_vocab:
         from . import tokenizer_file
         print('wrote', tokenizer_file.generate(a.tokenizer_vocab, os.path.join(a.out, 'ctokenizer.txt')))

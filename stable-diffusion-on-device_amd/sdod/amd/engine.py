@@ -9,7 +9,7 @@ import torch
 from . import _lib
 from ._lib import check
 
-UNET, VAE_DECODER, TEXT_ENCODER, TEMB, VAE_ENCODER, VAE_ENCODER_MASKED = 0, 1, 2, 3, 4, 5
+UNET, VAE_DECODER, TEXT_ENCODER, TEMB, VAE_ENCODER, VAE_ENCODER_MASKED, ADAPTER = 0, 1, 2, 3, 4, 5, 6
 
 
 class ModelConfig(ctypes.Structure):
@@ -18,6 +18,31 @@ class ModelConfig(ctypes.Structure):
         'latent_channels', 'latent_h', 'latent_w', 'model_channels', 'context_dim', 'context_len', 'num_heads',
         'head_dim', 'vocab_size', 'text_layers', 'text_heads', 'vae_channels', 'linear_proj', 'text_arch', 'weight_quant',
         'concat_channels')]
+    # T2I-Adapter (`struct sdod_adapter_config`, which travels NEXT to the model config: the struct above keeps its size): plain
+    # attributes of the instance, 0 = no adapter.  Every copy made from a ModelConfig carries them: from_buffer_copy() and copy_config().
+    adapter_reps = 0
+    adapter_hint_channels = 0
+    adapter_res_blocks = 0
+    _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks')
+
+    @classmethod
+    def from_buffer_copy(cls, source, offset=0):
+        out = type(ctypes.Structure).from_buffer_copy(cls, source, offset)   # (a method of the ctypes metaclass: no super() reaches it)
+        for n in cls._ADAPTER_FIELDS:          # (a raw buffer has none: the class defaults, 0, stay)
+            v = int(getattr(source, n, 0))
+            if v:
+                setattr(out, n, v)
+        return out
+
+
+class AdapterConfig(ctypes.Structure):
+    """mirror of `struct sdod_adapter_config`"""
+    _fields_ = [(n, ctypes.c_int) for n in ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks')]
+
+
+def copy_config(cfg):
+    """an independent copy of a ModelConfig, its adapter attributes included"""
+    return ModelConfig.from_buffer_copy(cfg)
 
 
 class LoraEntry(ctypes.Structure):
@@ -27,7 +52,7 @@ class LoraEntry(ctypes.Structure):
 
 
 ENGINE_SYMBOLS = [
-    'sdod_model_config_sd14', 'sdod_model_config_sd21', 'sdod_graph_create', 'sdod_graph_destroy', 'sdod_graph_num_params', 'sdod_graph_param_info',
+    'sdod_model_config_sd14', 'sdod_model_config_sd21', 'sdod_graph_create', 'sdod_graph_create_ex', 'sdod_graph_destroy', 'sdod_graph_num_params', 'sdod_graph_param_info',
     'sdod_graph_set_param', 'sdod_graph_param_device', 'sdod_graph_load_file', 'sdod_graph_finalize', 'sdod_graph_io', 'sdod_graph_execute', 'sdod_graph_check',
     'sdod_graph_stats', 'sdod_graph_tune_info', 'sdod_graph_num_ops', 'sdod_graph_op_info', 'sdod_graph_op_detail', 'sdod_graph_profile',
     'sdod_graph_keep_base', 'sdod_graph_base_bytes', 'sdod_graph_set_loras',
@@ -43,6 +68,7 @@ def _engine():
         lib.sdod_model_config_sd21.argtypes = [ctypes.POINTER(ModelConfig)]
         lib.sdod_model_config_sd21.restype = None
         lib.sdod_graph_create.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), I]
+        lib.sdod_graph_create_ex.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(AdapterConfig), I]
         lib.sdod_graph_destroy.argtypes = [P]
         lib.sdod_graph_num_params.argtypes = [P]
         lib.sdod_graph_param_info.argtypes = [P, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I), ctypes.POINTER(ctypes.c_int64)]
@@ -67,11 +93,14 @@ def _engine():
     return lib
 
 
-def sd14_config(latent_h=64, latent_w=64, concat_channels=0):
-    """concat_channels=5: an inpainting checkpoint (sd-v1-5-inpainting), whose UNet input convolution takes 4 + 5 channels"""
+def sd14_config(latent_h=64, latent_w=64, concat_channels=0, adapter_reps=0, adapter_hint_channels=0, adapter_res_blocks=0):
+    """concat_channels=5: an inpainting checkpoint (sd-v1-5-inpainting), whose UNet input convolution takes 4 + 5 channels.
+    adapter_reps=1 or 2: a UNet built on this config has the four T2I-Adapter feature inputs (UNet.adapter_feat), each shared by that
+    many guidance copies of its batch; adapter_hint_channels=1 or 3 (and adapter_res_blocks, 0 = 2): what an Adapter graph needs."""
     cfg = ModelConfig()
     _engine().sdod_model_config_sd14(ctypes.byref(cfg))
     cfg.latent_h, cfg.latent_w, cfg.concat_channels = latent_h, latent_w, concat_channels
+    cfg.adapter_reps, cfg.adapter_hint_channels, cfg.adapter_res_blocks = int(adapter_reps), int(adapter_hint_channels), int(adapter_res_blocks)
     return cfg
 
 
@@ -106,8 +135,12 @@ class Graph:
         self._h = ctypes.c_void_p()
         self.kind, self.cfg, self.batch = kind, cfg, batch
         self.device = torch.device(device)
+        acfg = AdapterConfig(*(int(getattr(cfg, n, 0)) for n, _ in AdapterConfig._fields_))
         with self._on_device():
-            check(self._lib.sdod_graph_create(ctypes.byref(self._h), kind, ctypes.byref(cfg), batch))
+            if kind == ADAPTER or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_):
+                check(self._lib.sdod_graph_create_ex(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(acfg), batch))
+            else:       # no adapter anywhere: the entry point, and the graph, of every build before it
+                check(self._lib.sdod_graph_create(ctypes.byref(self._h), kind, ctypes.byref(cfg), batch))
         self.finalized = False
 
     def _on_device(self):
@@ -277,6 +310,31 @@ class UNet(Graph):
         self.eps = self.io_tensor(True, 0, (b, c.latent_h, c.latent_w, c.latent_channels), torch.float16)
         if c.concat_channels > 0:   # inpainting checkpoint: mask | latent of the masked image, read by the input convolution next to x
             self.cond = self.io_tensor(False, 3, (b, c.concat_channels, c.latent_h, c.latent_w), torch.float32)
+        reps = int(getattr(c, 'adapter_reps', 0))
+        if reps > 0:                # T2I-Adapter: four feature slots behind the other inputs, zero until something is staged into them
+            first = 4 if c.concat_channels > 0 else 3
+            self.adapter_feat = [self.io_tensor(False, first + k, shape, torch.float16) for k, shape in enumerate(adapter_feature_shapes(c, b // reps))]
+        return self
+
+
+def adapter_feature_shapes(cfg, n):
+    """the four T2I-Adapter feature maps of n images, NHWC: [n, H / s, W / s, C] for (s, C) = (1, MC), (2, 2 MC), (4, 4 MC), (8, 4 MC)"""
+    mc = cfg.model_channels
+    return [(n, cfg.latent_h // s, cfg.latent_w // s, m * mc) for s, m in ((1, 1), (2, 2), (4, 4), (8, 4))]
+
+
+class Adapter(Graph):
+    """TencentARC's full T2I-Adapter (SD 1.x canny / depth / sketch / seg / openpose / keypose checkpoints): uint8 hint
+    [B, 8H, 8W, cfg.adapter_hint_channels] -> four fp16 NHWC feature maps (adapter_feature_shapes).  One execute per hint image."""
+
+    def __init__(self, cfg, batch, device='cuda:0'):
+        super().__init__(ADAPTER, cfg, batch, device)
+
+    def finalize(self):
+        super().finalize()
+        c, b = self.cfg, self.batch
+        self.hint = self.io_tensor(False, 0, (b, 8 * c.latent_h, 8 * c.latent_w, c.adapter_hint_channels), torch.uint8)
+        self.out = [self.io_tensor(True, k, shape, torch.float16) for k, shape in enumerate(adapter_feature_shapes(c, b))]
         return self
 
 

@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from ._lib import GemmDesc, check
 
-ACT = {None: 0, 'none': 0, 'silu': 1, 'gelu': 2, 'quick_gelu': 3}
+ACT = {None: 0, 'none': 0, 'silu': 1, 'gelu': 2, 'quick_gelu': 3, 'relu': 4}   # 'relu': activation() only, not a GEMM epilogue
 
 
 def _stream():
@@ -395,6 +395,57 @@ def add(a, b, out=None):
         out = torch.empty_like(a)
     check(lib.sdod_add_f16(_p(a), _p(b), _p(out), a.numel(), _stream()))
     return out
+
+
+def pixel_unshuffle_u8(img_u8, factor=8, out=None):
+    """the T2I-Adapter's input (sdod_pixel_unshuffle_u8_f16): uint8 HWC [n, 8h, 8w, ch] -> fp16 NHWC [n, h, w, 64 ch] = img / 255 in
+    torch.nn.PixelUnshuffle(8)'s channel order (c * 64 + dy * 8 + dx); ch 1 or 3"""
+    lib = _lib.hip()
+    _req(img_u8, torch.uint8, 'img')
+    n, ih, iw, ch = img_u8.shape
+    h, w = ih // factor, iw // factor
+    assert ih == h * factor and iw == w * factor, img_u8.shape
+    if out is None:
+        out = torch.empty((n, h, w, ch * factor * factor), dtype=torch.float16, device=img_u8.device)
+    else:
+        _req(out, torch.float16, 'out')
+        assert out.numel() == img_u8.numel(), (out.shape, img_u8.shape)
+    check(lib.sdod_pixel_unshuffle_u8_f16(_p(img_u8), _p(out), n, h, w, ch, factor, _stream()))
+    return out
+
+
+def avg_pool2(x, out=None):
+    """AvgPool2d(2) on NHWC fp16 [n, h, w, c] (sdod_avg_pool2_f16): ((a + b) + (c + d)) * 0.25 in fp32; h, w even, c % 8 == 0"""
+    lib = _lib.hip()
+    _req(x, torch.float16, 'x')
+    n, h, w, c = x.shape
+    if out is None:
+        out = torch.empty((n, h // 2, w // 2, c), dtype=torch.float16, device=x.device)
+    else:
+        _req(out, torch.float16, 'out')
+        assert out.numel() * 4 == x.numel(), (out.shape, x.shape)
+    check(lib.sdod_avg_pool2_f16(_p(x), _p(out), n, h, w, c, _stream()))
+    return out
+
+
+def adapter_stage(src, dst, weight=1.0):
+    """dst = fp16(weight * src) (sdod_adapter_stage_f16): an adapter output into a feature slot of the UNet, the conditioning weight
+    folded in"""
+    lib = _lib.hip()
+    _req(src, torch.float16, 'src'); _req(dst, torch.float16, 'dst')
+    assert dst.numel() == src.numel(), (dst.shape, src.shape)
+    check(lib.sdod_adapter_stage_f16(_p(src), _p(dst), src.numel(), float(weight), _stream()))
+    return dst
+
+
+def add_feature(h, f, reps):
+    """h fp16 [reps * per_copy] += f fp16 [per_copy] for each of the reps (1 or 2) guidance copies, in place (sdod_add_feature_f16:
+    the launch a UNet graph with adapter inputs makes at four places per evaluation)"""
+    lib = _lib.hip()
+    _req(h, torch.float16, 'h'); _req(f, torch.float16, 'f')
+    assert h.numel() == reps * f.numel(), (h.shape, f.shape, reps)
+    check(lib.sdod_add_feature_f16(_p(h), _p(f), f.numel(), reps, _stream()))
+    return h
 
 
 def concat_channels(a, b):

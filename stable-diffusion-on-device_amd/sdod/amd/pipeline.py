@@ -28,10 +28,13 @@ class Txt2Img:
     text = None
     _loras = False
     hires = None        # the second pipeline of the hires pass (Txt2Img(..., hires_hw=)), or None
+    adapter = None      # the T2I-Adapter graph (Txt2Img(..., adapter=True)), or None
+    adapter_channels = 3
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
-                 with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None):
+                 with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
+                 adapter_channels=3):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -56,9 +59,17 @@ class Txt2Img:
         UNet and a VAE decoder (no text encoder, no VAE encoder), for generate_hires() / generate_hires_graphed() /
         hires_from_latent().  It loads the same state dicts or containers and owns its own weights: hires.unet.stats() +
         hires.vae.stats() more device memory ('weight_bytes' + 'arena_bytes' of each; with loras=True hires.unet.base_bytes() on top).
-        Without it nothing is constructed or sized differently.  With cfg_split or inpaint_unet it raises ValueError."""
+        Without it nothing is constructed or sized differently.  With cfg_split or inpaint_unet it raises ValueError.
+        adapter=True: structural control by a T2I-Adapter (TencentARC's full SD 1.x adapters: canny, depth, sketch, seg, openpose,
+        keypose).  The UNet graph gets four feature slots (unet.adapter_feat, zero until a hint is set) that it
+        adds behind input_blocks.2 / .5 / .8 / .11 in both guidance halves, and self.adapter = E.Adapter(cfg, 1) is built from
+        state_dicts['adapter'] or models_dir/adapter.sdodw, for hints of adapter_channels (1 or 3) channels: set_adapter_hint() /
+        clear_adapter_hint().  Off, nothing is constructed or sized differently.  Not with cfg_split, hires_hw, inpaint_unet or
+        model='sd21' (the released adapters are SD 1.x ones; the other three would each need the slots in a second place): ValueError
+        before any device work, as for an adapter_channels other than 1 or 3."""
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         latent_h, latent_w = check_latent_hw(latent_hw)
+        adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_unet, model)
         if hires_hw is not None:
             check_latent_hw(hires_hw, 'hires_hw')
             if cfg_split or inpaint_unet:
@@ -100,18 +111,27 @@ class Txt2Img:
         self.tokenizer = tokenizer
         unet_cfg = self.cfg
         if self.prompt_chunks > 1:       # the text encoder keeps 77 (its position table); only the UNet sees the longer context
-            unet_cfg = E.ModelConfig.from_buffer_copy(self.cfg)
+            unet_cfg = E.copy_config(self.cfg)
             unet_cfg.context_len = PR.CHUNK_LEN * self.prompt_chunks
+        if adapter:                      # only the UNet graph takes the feature slots: one per level, shared by the two guidance halves
+            unet_cfg = E.copy_config(unet_cfg)
+            unet_cfg.adapter_reps = 2
+            self.adapter_channels = int(adapter_channels)
         self.unet = E.UNet(unet_cfg, self.n if cfg_split else 2 * self.n, device)
         self.vae = E.VaeDecoder(self.cfg, 1, device) if with_vae else None
         self.text = E.TextEncoder(self.cfg, 2 * self.prompt_chunks, device) if with_text_encoder else None
         self.encoder = E.VaeEncoder(self.cfg, 1, device) if with_vae_encoder else None
         self.masked_encoder = E.MaskedVaeEncoder(self.cfg, 1, device) if self.inpaint_unet else None
+        if adapter:
+            acfg = E.copy_config(self.cfg)
+            acfg.adapter_hint_channels = self.adapter_channels
+            self.adapter = E.Adapter(acfg, 1, device)
         self._temb_graphs = {}
         self._sd = state_dicts
         self._dir = models_dir
         for g, key, stem in ((self.unet, 'unet', 'unet'), (self.vae, 'vae', 'vae_decoder'), (self.text, 'text', 'text_encoder'),
-                             (self.encoder, 'vae_enc', 'vae_encoder'), (self.masked_encoder, 'vae_enc', 'vae_encoder')):
+                             (self.encoder, 'vae_enc', 'vae_encoder'), (self.masked_encoder, 'vae_enc', 'vae_encoder'),
+                             (self.adapter, 'adapter', 'adapter')):
             if g is None:
                 continue
             self._load(g, key, stem)
@@ -178,6 +198,33 @@ class Txt2Img:
     def clear_loras(self):
         """back to the base weights, bit for bit: set_loras([])"""
         return self.set_loras([])
+
+    # ------------------------------------------------------------------ structural control (T2I-Adapter)
+    def set_adapter_hint(self, hint_u8, weight=1.0):
+        """hint_u8: uint8 [n, 8h, 8w, adapter_channels] ([n, 8h, 8w] is accepted for one channel) -- an edge map, depth map, sketch or
+        pose skeleton, one per image of the pipeline's batch; the caller makes it (no preprocessor here).  The adapter runs once per
+        image, then four launches write weight * feature into the UNet's slots (ops.adapter_stage).  The slots are memory of the UNet
+        graph at fixed addresses that every evaluation reads: from here on EVERY entry point is conditioned -- generate,
+        generate_graphed, img2img*, inpaint*, every sampler -- and a trajectory that was captured already picks up a new hint or
+        weight without a new capture.  weight scales the features (TencentARC's cond_weight); 0.0 is clear_adapter_hint().
+        ValueError for a wrong shape or dtype or a non-finite weight (adapter_check_args), before any device work; RuntimeError on a
+        pipeline built without adapter=True."""
+        if self.adapter is None:
+            raise RuntimeError('this pipeline was built without adapter=True: Txt2Img(..., adapter=True) is needed for structural control')
+        hint_u8 = adapter_check_args(hint_u8, weight, self._latent_shape, self.n, self.adapter_channels)
+        hint_u8 = hint_u8.to(self.device).contiguous()
+        for i in range(self.n):
+            self.adapter.hint.copy_(hint_u8[i:i + 1])
+            self.adapter.execute(self.use_hip_graph)
+            for out, slot in zip(self.adapter.out, self.unet.adapter_feat):
+                ops.adapter_stage(out, slot[i:i + 1], weight)
+
+    def clear_adapter_hint(self):
+        """zero the UNet's feature slots: the unconditioned model again (its additions of zero change no bit)"""
+        if self.adapter is None:
+            raise RuntimeError('this pipeline was built without adapter=True: Txt2Img(..., adapter=True) is needed for structural control')
+        for slot in self.unet.adapter_feat:
+            slot.zero_()
 
     # ------------------------------------------------------------------ conditioning
     def encode_tokens(self, ids_uncond, ids_cond):
@@ -912,6 +959,33 @@ def check_latent_hw(latent_hw, name='latent_hw'):
     if any(v < 8 or v % 8 for v in hw):
         raise ValueError(f'{name}: height and width must be multiples of 8, at least 8 (64 px of image), got {latent_hw!r}')
     return int(hw[0]), int(hw[1])
+
+
+def adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_unet, model):
+    """Txt2Img's adapter=True: adapter_channels 1 or 3, and none of cfg_split, hires_hw, inpaint_unet, model='sd21'.  Raises ValueError."""
+    if not adapter:
+        return
+    if isinstance(adapter_channels, bool) or not isinstance(adapter_channels, (int, np.integer)) or adapter_channels not in (1, 3):
+        raise ValueError(f'adapter_channels must be 1 or 3, got {adapter_channels!r}')
+    for name, on in (('cfg_split', cfg_split), ('hires_hw', hires_hw is not None), ('inpaint_unet', inpaint_unet), ("model='sd21'", model == 'sd21')):
+        if on:
+            raise ValueError(f'adapter=True cannot be combined with {name}')
+
+
+def adapter_check_args(hint_u8, weight, latent, n_images, channels):
+    """the argument contract of Txt2Img.set_adapter_hint, checked on the host before any device work: hint_u8 a uint8 tensor
+    [n_images, 8H, 8W, channels] with (4, H, W) = latent -- [n_images, 8H, 8W] is accepted when channels == 1 -- and weight a finite
+    number.  Returns the hint as [n_images, 8H, 8W, channels]; raises ValueError."""
+    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not np.isfinite(float(weight)):
+        raise ValueError(f'weight must be a finite number, got {weight!r}')
+    if not isinstance(hint_u8, torch.Tensor) or hint_u8.dtype != torch.uint8:
+        raise ValueError(f'hint_u8 must be a uint8 tensor, got {getattr(hint_u8, "dtype", type(hint_u8))}')
+    want = (n_images, 8 * latent[1], 8 * latent[2], channels)
+    if channels == 1 and tuple(hint_u8.shape) == want[:3]:
+        hint_u8 = hint_u8[..., None]
+    if tuple(hint_u8.shape) != want:
+        raise ValueError(f'hint_u8 must be {want}' + (f' or {want[:3]}' if channels == 1 else '') + f', got {tuple(hint_u8.shape)}')
+    return hint_u8
 
 
 HIRES_UPSCALERS = ('nearest-exact', 'bilinear', 'bicubic')
