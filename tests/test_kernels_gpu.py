@@ -351,7 +351,8 @@ def test_conv3x3_with_skip_tail_segment(tile):
     check(out, ref, name=f'conv + skip tail tile{tile}')
 
 
-@pytest.mark.parametrize('case', ['rows_small_m', 'rows_ragged', 'rows_geglu_ln', 'conv', 'conv_split', 'halo', 'halo_split_tail'])
+@pytest.mark.parametrize('case', ['rows_small_m', 'rows_ragged', 'rows_geglu_ln', 'conv', 'conv_split', 'halo', 'halo_split_tail', 'conv_rect',
+                                  'halo_rect'])
 def test_xcd_tile_orders_give_identical_bits(case):
     """sdod_gemm_desc::xcd_panels only permutes which workgroup computes which tile (gemm.hip: tile_of): every order --
     the per-shape choice, m-major, 2 / 4 / 8 panels, ragged panel widths included -- must produce the same bits"""
@@ -381,6 +382,14 @@ def test_xcd_tile_orders_give_identical_bits(case):
     elif case == 'halo':
         x0 = rnd((2, 32, 32, 192), 312).to(d); w = rnd((400, 9 * 192), 313, (9 * 192) ** -0.5).to(d)
         run = lambda x: tgemm(x0, w, conv=dict(stride=1), tile=38, split_k=1, xcd=x)  # 16 x 5 tiles of 128 x 80
+        ref = conv_ref(x0.cpu(), w.cpu(), None)
+    elif case == 'conv_rect':
+        x0 = rnd((2, 24, 16, 128), 319).to(d); w = rnd((200, 9 * 128), 320, (9 * 128) ** -0.5).to(d)
+        run = lambda x: tgemm(x0, w, conv=dict(stride=1), tile=28, split_k=1, xcd=x)  # 768 rows x 200 columns, h != w
+        ref = conv_ref(x0.cpu(), w.cpu(), None)
+    elif case == 'halo_rect':
+        x0 = rnd((2, 32, 48, 64), 321).to(d); w = rnd((200, 9 * 64), 322, (9 * 64) ** -0.5).to(d)
+        run = lambda x: tgemm(x0, w, conv=dict(stride=1), tile=50, split_k=1, xcd=x)  # 32 x 4 tiles of 96 x 64: two image rows of 48 each
         ref = conv_ref(x0.cpu(), w.cpu(), None)
     else:
         hm = rnd((2, 16, 16, 128), 314).to(d); t0 = rnd((2, 16, 16, 192), 315).to(d)
@@ -1021,17 +1030,20 @@ def test_image_to_u8_vs_oracle(oracle_lib):
     assert np.array_equal(got.reshape(-1), ref)
 
 
-@pytest.mark.parametrize('case', ['64x64 C320 d40', '32x32 C640 d80', '16x16 C1280 d160', '8x8 C1280 d160', 'sd21 24x24 C1280 d64'])
+@pytest.mark.parametrize('case', ['64x64 C320 d40', '32x32 C640 d80', '16x16 C1280 d160', '8x8 C1280 d160', 'sd21 24x24 C1280 d64',
+                                  '8x12 C1280 d160', '16x24 C640 d80'])
 def test_folded_cross_attention_matches_linear_attention_linear(case):
     """The cross-attention block as two GEMMs (sdod_xattn_fold_f16 once per prompt; per evaluation a LayerNorm-folded score GEMM
     with per-image weights and the row softmax in its epilogue, then P . (V Wo^T) + bias + residual with per-image weights)
     against the three-op form it replaces -- LayerNorm -> to_q -> softmax(q k^T / sqrt d) v -> to_out + residual in fp32 torch
-    (the reference's /attn2/* ops, analyze_results.py:69-79).  Tolerance as the attention / Linear kernel tests."""
+    (the reference's /attn2/* ops, analyze_results.py:69-79).  Tolerance as the attention / Linear kernel tests.
+    The image is HxW: 8x12 (the deepest level of a 64x96 latent) is 96 rows, which only the 32-row softmax tile divides -- the
+    plan replaces tile 31 by 48 there; 16x24 is 384 rows."""
     from sdod.amd import ops
-    hw = int(case.split('x')[0].split()[-1]); c = int(case.split('C')[1].split()[0]); d = int(case.split(' d')[1])
+    hh, ww = (int(v) for v in case.split(' C')[0].split()[-1].split('x')); c = int(case.split('C')[1].split()[0]); d = int(case.split(' d')[1])
     heads, L, B, cd = c // d, 77, 2, 768
     g = torch.Generator().manual_seed(sum(map(ord, case)))
-    rows = hw * hw
+    rows = hh * ww
     x = (torch.randn(B * rows, c, generator=g) * 1.5 + 0.3).half().cuda()
     ctx = torch.randn(B * L, cd, generator=g).half().cuda()
     wq = (torch.randn(c, c, generator=g) / c ** 0.5).half().cuda(); wo = (torch.randn(c, c, generator=g) / c ** 0.5).half().cuda()
@@ -1061,6 +1073,31 @@ def test_folded_cross_attention_matches_linear_attention_linear(case):
     assert float(pv[..., 77:].abs().max()) == 0 and float((pv.sum(-1) - 1).abs().max()) < 5e-3
     out = ops.gemm(p, w2, bo, residual=x, rows_per_img=rows)
     check(out, ref, tol=4e-3, name=f'folded cross-attention {case}')
+    if rows == 96:
+        assert run_gemm(x, w1, t1, ln_s=s1, rows_per_img=rows, softmax_cols=80, tile=31, runs_on=48, tag='kernels')[1] == 48
+
+
+@pytest.mark.parametrize('rows', [24, 8])
+def test_per_image_weights_refuse_images_no_32_row_tile_divides(rows):
+    """rows_per_img = 24 (4x6) and 8 (2x4) are the deepest levels of a (16, 24) and an (8, 16) latent.  No tile of the per-image
+    GEMMs divides them (the smallest has 32 rows, and a tile must not straddle two weight matrices), so sdod_gemm refuses the
+    descriptor -- with and without the softmax epilogue -- and writes nothing.  The UNet builder never emits the form there:
+    graphs.hip takes the folded cross-attention only where L % 32 == 0 (`xfold`) and otherwise keeps Linear -> attention kernel
+    -> Linear, which sees only the flattened row count."""
+    from sdod.amd import _lib, ops
+    g = torch.Generator().manual_seed(700 + rows)
+    B, c, nk = 2, 320, 640
+    x = torch.randn(B * rows, c, generator=g).half().cuda()
+    w1 = (torch.randn(B, nk, c, generator=g) / c ** 0.5).half().cuda(); w2 = (torch.randn(B, c, nk, generator=g) / nk ** 0.5).half().cuda()
+    s1 = torch.ones(B, nk).cuda(); t1 = torch.zeros(B, nk).cuda()
+    p = torch.full((B * rows, nk), float('nan'), dtype=torch.float16).cuda()
+    with pytest.raises(_lib.SdodError, match='rows_per_img a multiple of 32'):
+        ops.gemm(x, w1, t1, ln_s=s1, rows_per_img=rows, softmax_cols=80, out=p)
+    out = torch.full((B * rows, c), float('nan'), dtype=torch.float16).cuda()
+    with pytest.raises(_lib.SdodError, match='rows_per_img a multiple of 32'):
+        ops.gemm(torch.zeros_like(p), w2, None, residual=x, rows_per_img=rows, out=out)
+    torch.cuda.synchronize()
+    assert torch.isnan(p).all() and torch.isnan(out).all(), 'a refused GEMM wrote to its destination'
 
 
 def test_latent_im2col_equals_latent_prep_then_im2col():
