@@ -123,6 +123,16 @@ typedef struct sdod_adapter_config {
 /* sdod_graph_create with an adapter configuration (NULL = all zero).  SDOD_GRAPH_ADAPTER can only be created here; latent_h and
  * latent_w follow the UNet's rule (multiples of 8, at least 8).  Anything else is INVALID_ARGUMENT. */
 SDOD_API int sdod_graph_create_ex(void** graph, int kind, const sdod_model_config* cfg, const sdod_adapter_config* adapter, int batch);
+/* Seamless tiling.  sdod_graph_create_ex with a graph-wide `wrap`: bit 0 = the x axis wraps (left / right edges join), bit 1 = the
+ * y axis wraps.  Every 3x3 symmetric-pad convolution of the graph -- ResBlocks, downsample and upsample convolutions, input and
+ * output convolutions -- takes a circular border on the wrapped axes (sdod_gemm_desc::pad_mode 2 / 3 / 4, sdod_conv_in_wrap_f16,
+ * sdod_im2col3x3_small_wrap_f16); GroupNorm, attention and nearest-2x upsampling do not know where the border is.  Like the adapter
+ * configuration, the flag travels next to sdod_model_config, whose size is part of the ABI.  wrap = 0 builds exactly the graph of
+ * sdod_graph_create_ex, and a wrapped graph has the plain graph's launch list, tiles and arena.  Honoured by SDOD_GRAPH_UNET (with
+ * concat_channels == 0) and SDOD_GRAPH_VAE_DECODER; a non-zero wrap for any other kind is INVALID_ARGUMENT.  Latent shifts of a
+ * wrapped UNet commute with it for multiples of 8 (three stride-2 levels); the wrapped decoder commutes with any shift. */
+SDOD_API int sdod_graph_create_wrap(void** graph, int kind, const sdod_model_config* cfg, const sdod_adapter_config* adapter, int wrap,
+                                    int batch);
 SDOD_API int sdod_graph_destroy(void* graph);
 
 /* parameter table (fixed by kind + config) */

@@ -125,7 +125,12 @@ typedef struct sdod_gemm_desc {
     /* conv padding: 0 = symmetric ksize / 2 (zero-initialised descriptors); 1 = ldm's VAE-encoder Downsample, F.pad(x, (0, 1, 0, 1))
      * then a 3x3 stride-2 pad-0 convolution: nothing above / left of the image, one zero row / column below / right of it, so
      * h_out = (h_in + 1 - 3) / 2 + 1.  Only the im2col gather kernels honour it: halo-patch tiles decline it (sdod_gemm_halo_ok = 0),
-     * a tail segment or upsampling refuses it, and it needs ksize 3 with stride 2. */
+     * a tail segment or upsampling refuses it, and it needs ksize 3 with stride 2.
+     * 2 / 3 / 4 = seamless tiling: the symmetric pad-1 border of a 3x3 convolution is CIRCULAR on both axes (2), on x only (3:
+     * columns wrap, zero rows above and below) or on y only (4: rows wrap, zero columns left and right).  A wrapped tap reads pixel
+     * (y mod H, x mod W) of the same image, in output coordinates before the >> 1 of upsampling.  Output size, plan, workspace
+     * and every fusion (stride 1 or 2, upsampling, concat, tail segment, row bias, residual, split-K, uint8 weights) are those of
+     * pad_mode 0, and every kernel family honours it (halo-patch tiles take it wherever they take 0); ksize 1 refuses it. */
     int pad_mode;
 } sdod_gemm_desc;
 
@@ -299,6 +304,9 @@ SDOD_API int sdod_adapter_stage_f16(const void* src, void* dst, size_t count, fl
  * writes them), per_copy % 8 == 0, 16-byte aligned pointers. */
 SDOD_API int sdod_add_feature_f16(void* h, const void* f, size_t per_copy, int reps, void* stream);
 SDOD_API int sdod_im2col3x3_small_f16(const void* x, void* y, int n_img, int h, int w, int c, int kpad, void* stream);
+/* the same kernel with a circular border: wrap bit 0 = columns (x) wrap, bit 1 = rows (y) wrap; a wrapped tap reads pixel
+ * (y mod h, x mod w) of its own image.  wrap = 0 is sdod_im2col3x3_small_f16, bit for bit. */
+SDOD_API int sdod_im2col3x3_small_wrap_f16(const void* x, void* y, int n_img, int h, int w, int c, int kpad, int wrap, void* stream);
 /* sdod_latent_prep_f16 (w = NULL) followed by sdod_im2col3x3_small_f16 in one launch: x NCHW fp32 [n][c][h][w] -> the im2col matrix
  * [n*h*w][kpad] fp16 of a 3x3 pad-1 convolution (k = tap * c + channel, zero beyond 9c), values (fp16)(x * scale); kpad % 8 == 0 */
 SDOD_API int sdod_latent_im2col_f16(const float* x, void* y, int n_img, int h, int w, int c, int kpad, float scale, void* stream);
@@ -309,6 +317,10 @@ SDOD_API int sdod_latent_im2col_f16(const float* x, void* y, int n_img, int h, i
  * 9 * c <= 64; cout in {64, 128, 256, 320}.  Equals sdod_latent_im2col_f16 followed by the K = 64 sdod_gemm_f16. */
 SDOD_API int sdod_conv_in_f16(const float* x, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout,
                               float scale, void* stream);
+/* sdod_conv_in_f16 with a circular border (seamless tiling): wrap bit 0 = x, bit 1 = y, as in sdod_im2col3x3_small_wrap_f16.
+ * wrap = 0 is sdod_conv_in_f16, bit for bit (the old entry point forwards here). */
+SDOD_API int sdod_conv_in_wrap_f16(const float* x, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout,
+                                   float scale, int wrap, void* stream);
 /* The VAE encoder's input convolution in one launch: img uint8 HWC RGB [n][h][wd][3] -> x = fp16(2 * (u / 255) - 1) -> 3x3 pad-1
  * convolution with w fp16 [cout][64] (k = tap * 3 + channel, zero beyond 27: the PK_CONV3_SMALL packing) + bias fp32 [cout] -> y NHWC
  * fp16 [n*h*wd][cout].  cout in {64, 128, 256, 320}.  The same core as sdod_conv_in_f16: equals normalising, then

@@ -154,8 +154,14 @@ __global__ void concat_kernel(const f16* a, const f16* b, f16* y, size_t rows, i
     }
 }
 
+// v mod n for v in [-1, n]: a 3x3 tap is at most one pixel outside its image (circular border, `wrap` bit 0 = columns, bit 1 = rows)
+SDOD_DEVICE int wrap1(int v, int n) {
+    v += v < 0 ? n : 0;
+    return v - (v >= n ? n : 0);
+}
+
 // 3x3 pad-1 im2col for tiny Cin (the 4-channel latent): y[row][k], k=(r*3+s)*c+ch, zero-padded to kpad
-__global__ void im2col_small_kernel(const f16* x, f16* y, int n_img, int h, int w, int c, int kpad) {
+__global__ void im2col_small_kernel(const f16* x, f16* y, int n_img, int h, int w, int c, int kpad, int wrap) {
     const size_t total = (size_t)n_img * h * w * kpad;
     GRID_STRIDE(i, total) {
         const size_t row = i / kpad;
@@ -167,7 +173,9 @@ __global__ void im2col_small_kernel(const f16* x, f16* y, int n_img, int h, int 
             const int img = (int)(row / ((size_t)h * w));
             const int rem = (int)(row - (size_t)img * h * w);
             const int oy = rem / w, ox = rem - oy * w;
-            const int yy = oy + r - 1, xx = ox + s - 1;
+            int yy = oy + r - 1, xx = ox + s - 1;
+            if (wrap & 2) yy = wrap1(yy, h);
+            if (wrap & 1) xx = wrap1(xx, w);
             if (yy >= 0 && yy < h && xx >= 0 && xx < w) v = x[(((size_t)img * h + yy) * w + xx) * c + ch];
         }
         y[i] = v;
@@ -246,7 +254,7 @@ struct MaskedImageU8Src {
 // NB: 16-column blocks per wave, Cout = 64 * NB.  KS: K steps of 32, the im2col row is K = 32 KS long (2: weight rows of 64 halves; 3:
 // K = 96, the first 96 columns of weight rows of 128 halves).
 template <int NB, typename Src, int KS = 2>
-__global__ __launch_bounds__(256) void conv_in_kernel(const Src src, const f16* w, const float* bias, f16* y, int n_img, int h, int wd, int c) {
+__global__ __launch_bounds__(256) void conv_in_kernel(const Src src, const f16* w, const float* bias, f16* y, int n_img, int h, int wd, int c, int wrap) {
     constexpr int K = 32 * KS, KP = K / 8, LDW = KS == 2 ? 64 : 128, NW = NB * KP / 4;
     __shared__ __attribute__((aligned(16))) f16 sa[32][K + 8];
     __shared__ __attribute__((aligned(16))) f16 sw[64 * NB][K + 8];
@@ -279,7 +287,9 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const Src src, const f16* 
                 float f = 0.f;
                 if (tap < 9) {
                     const int r = (tap * 11) >> 5, s2 = tap - r * 3; // tap / 3 for tap < 9
-                    const int yy = oy + r - 1, xx = ox + s2 - 1;
+                    int yy = oy + r - 1, xx = ox + s2 - 1;
+                    if (wrap & 2) yy = wrap1(yy, h);
+                    if (wrap & 1) xx = wrap1(xx, wd);
                     if (yy >= 0 && yy < h && xx >= 0 && xx < wd) f = src.at(img, ch, yy, xx, c, h, wd);
                 }
                 v[e] = (f16)f;
@@ -1097,12 +1107,17 @@ extern "C" int sdod_concat_channels_f16(const void* a, const void* b, void* y, s
     SDOD_CATCH
 }
 
-extern "C" int sdod_im2col3x3_small_f16(const void* x, void* y, int n_img, int h, int w, int c, int kpad, void* stream) {
+extern "C" int sdod_im2col3x3_small_wrap_f16(const void* x, void* y, int n_img, int h, int w, int c, int kpad, int wrap, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(x && y && n_img > 0 && h > 0 && w > 0 && c > 0 && kpad >= 9 * c, "bad argument");
-    LAUNCH(im2col_small_kernel, (size_t)n_img * h * w * kpad, stream, (const f16*)x, (f16*)y, n_img, h, w, c, kpad);
+    SDOD_REQUIRE(wrap >= 0 && wrap <= 3, "wrap must be 0 .. 3 (bit 0 = x, bit 1 = y)");
+    LAUNCH(im2col_small_kernel, (size_t)n_img * h * w * kpad, stream, (const f16*)x, (f16*)y, n_img, h, w, c, kpad, wrap);
     return 0;
     SDOD_CATCH
+}
+
+extern "C" int sdod_im2col3x3_small_f16(const void* x, void* y, int n_img, int h, int w, int c, int kpad, void* stream) {
+    return sdod_im2col3x3_small_wrap_f16(x, y, n_img, h, w, c, kpad, 0, stream);
 }
 
 extern "C" int sdod_latent_im2col_f16(const float* x, void* y, int n_img, int h, int w, int c, int kpad, float scale, void* stream) {
@@ -1114,27 +1129,33 @@ extern "C" int sdod_latent_im2col_f16(const float* x, void* y, int n_img, int h,
 }
 
 template <typename Src, int KS = 2>
-void launch_conv_in(const Src src, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout, hipStream_t st) {
+void launch_conv_in(const Src src, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout, hipStream_t st, int wrap = 0) {
     const long long M = (long long)n_img * h * wd;
     const dim3 grid((unsigned)((M + 31) / 32));
     switch (cout / 64) {
-    case 1: SDOD_LAUNCH((conv_in_kernel<1, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
-    case 2: SDOD_LAUNCH((conv_in_kernel<2, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
-    case 4: SDOD_LAUNCH((conv_in_kernel<4, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
-    default: SDOD_LAUNCH((conv_in_kernel<5, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c); break;
+    case 1: SDOD_LAUNCH((conv_in_kernel<1, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c, wrap); break;
+    case 2: SDOD_LAUNCH((conv_in_kernel<2, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c, wrap); break;
+    case 4: SDOD_LAUNCH((conv_in_kernel<4, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c, wrap); break;
+    default: SDOD_LAUNCH((conv_in_kernel<5, Src, KS>), grid, dim3(256), 0, st, src, (const f16*)w, bias, (f16*)y, n_img, h, wd, c, wrap); break;
     }
     SDOD_HIP_CHECK(hipGetLastError());
 }
 
-extern "C" int sdod_conv_in_f16(const float* x, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout,
-                                float scale, void* stream) {
+extern "C" int sdod_conv_in_wrap_f16(const float* x, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout,
+                                     float scale, int wrap, void* stream) {
     SDOD_TRY
+    SDOD_REQUIRE(wrap >= 0 && wrap <= 3, "wrap must be 0 .. 3 (bit 0 = x, bit 1 = y)");
     SDOD_REQUIRE(x && w && y && n_img > 0 && h > 0 && wd > 0 && c > 0 && 9 * c <= 64, "bad argument (9 * Cin must fit the 64-deep K slab)");
     SDOD_REQUIRE(cout == 320 || cout == 256 || cout == 128 || cout == 64, "Cout must be 64, 128, 256 or 320");
     SDOD_REQUIRE((((uintptr_t)w | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y & 7) == 0, "misaligned pointer");
-    launch_conv_in(LatentSrc{x, scale}, w, bias, y, n_img, h, wd, c, cout, (hipStream_t)stream);
+    launch_conv_in(LatentSrc{x, scale}, w, bias, y, n_img, h, wd, c, cout, (hipStream_t)stream, wrap);
     return 0;
     SDOD_CATCH
+}
+
+extern "C" int sdod_conv_in_f16(const float* x, const void* w, const float* bias, void* y, int n_img, int h, int wd, int c, int cout,
+                                float scale, void* stream) {
+    return sdod_conv_in_wrap_f16(x, w, bias, y, n_img, h, wd, c, cout, scale, 0, stream);
 }
 
 extern "C" int sdod_image_conv_in_f16(const uint8_t* img, const void* w, const float* bias, void* y, int n_img, int h, int wd, int cout,

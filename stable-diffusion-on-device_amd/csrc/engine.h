@@ -65,7 +65,7 @@ struct IoSlot {
 
 class Graph {
 public:
-    Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg = sdod_adapter_config{0, 0, 0});
+    Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg = sdod_adapter_config{0, 0, 0}, int wrap = 0);
     ~Graph();
     Graph(const Graph&) = delete;
 
@@ -92,6 +92,7 @@ private:
     sdod_model_config cfg_;
     sdod_adapter_config acfg_; // T2I-Adapter: all zero = no adapter inputs (UNET), required for kind ADAPTER
     int batch_;
+    int wrap_ = 0; // seamless tiling (UNET, VAE_DECODER): bit 0 = x wraps, bit 1 = y wraps; conv() turns it into sdod_gemm_desc::pad_mode
     Mode mode_ = DECLARE;
     bool finalized_ = false;
 

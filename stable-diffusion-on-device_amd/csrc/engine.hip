@@ -41,8 +41,8 @@ static void parallel_for(int64_t n, F&& fn) {
 }
 
 // ------------------------------------------------------------------------------------------ lifecycle
-Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg)
-    : kind_(kind), cfg_(cfg), acfg_(acfg), batch_(batch) {
+Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg, int wrap)
+    : kind_(kind), cfg_(cfg), acfg_(acfg), batch_(batch), wrap_(wrap) {
     SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_ADAPTER, "unknown graph kind");
     SDOD_REQUIRE(batch > 0 && batch <= 64, "batch must be in [1, 64]");
     SDOD_REQUIRE(cfg.model_channels > 0 && cfg.model_channels % 64 == 0, "model_channels must be a multiple of 64");
@@ -50,6 +50,10 @@ Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapt
     SDOD_REQUIRE(cfg.context_len >= 1 && cfg.context_len <= 4096, "context_len must be in [1, 4096]");
     SDOD_REQUIRE(cfg.concat_channels >= 0, "concat_channels must not be negative");
     SDOD_REQUIRE(acfg.adapter_reps >= 0 && acfg.adapter_reps <= 2, "adapter_reps must be 0, 1 or 2");
+    SDOD_REQUIRE(wrap >= 0 && wrap <= 3, "wrap must be 0 .. 3 (bit 0 = x, bit 1 = y)");
+    if (wrap != 0) // the encoder, adapter and inpainting input convolutions keep their zero border
+        SDOD_REQUIRE((kind == SDOD_GRAPH_UNET || kind == SDOD_GRAPH_VAE_DECODER) && cfg.concat_channels == 0,
+                     "wrap applies to the UNET (without concat_channels) and VAE_DECODER graphs only");
     if (kind == SDOD_GRAPH_UNET && acfg.adapter_reps > 0)
         SDOD_REQUIRE(batch % acfg.adapter_reps == 0, "adapter_reps must divide the batch");
     if (kind == SDOD_GRAPH_ADAPTER) {
@@ -621,7 +625,8 @@ ShapeKey key_of(const sdod_gemm_desc& d) {
     // convolutions with equal M and h_in but different (n_img, w_in) must not share a pick
     return ShapeKey{{d.a_mode, d.M, d.N, d.K, d.c0, d.c1, d.stride, d.upsample, d.ksize, d.h_in,
                      (d.residual ? 1 : 0) + (d.geglu ? 2 : 0) + 4 * d.tc0 + 16384 * d.tc1 + (d.ln ? (1 << 30) : 0) + (d.wq ? (1 << 29) : 0) + (d.softmax_cols ? (1 << 28) : 0) + (d.w_img_stride ? (1 << 27) : 0) +
-                         (d.pad_mode ? (1 << 26) : 0) /* only when set: every older table line keeps its key */, d.lda,
+                         (d.pad_mode == 1 ? (1 << 26) : 0) /* only when set: every older table line keeps its key; a circular border (2..4) is the
+                                                                work of pad_mode 0 and shares its picks */, d.lda,
                      d.a_mode == SDOD_A_CONV3X3 ? d.w_in : 0, d.a_mode == SDOD_A_CONV3X3 ? d.n_img : 0}};
 }
 // a table pick the library would refuse at launch (a halo-patch / A-panel tile that does not take this descriptor: a stale or
@@ -866,7 +871,9 @@ void Graph::linear(const f16* x, int rows, int K, int w, int N, f16* out, const 
 Act Graph::conv(const Act& x, const Act* x2, int w, int cout, int ksize, int stride, bool upsample, const GemmOpt& o) {
     const int ups = upsample ? 1 : 0;
     const int hup = x.h << ups, wup = x.w << ups;
-    const int pad_sum = o.pad_mode ? 1 : 2 * (ksize / 2); // pad_mode 1: ldm's encoder Downsample, F.pad(x, (0, 1, 0, 1)) + pad 0
+    // seamless tiling: every 3x3 symmetric-pad convolution of a wrapped graph takes the circular border on the wrapped axes
+    const int pad_mode = o.pad_mode == 0 && ksize == 3 && wrap_ != 0 ? (wrap_ == 3 ? 2 : wrap_ == 1 ? 3 : 4) : o.pad_mode;
+    const int pad_sum = pad_mode == 1 ? 1 : 2 * (ksize / 2); // pad_mode 1: ldm's encoder Downsample, F.pad(x, (0, 1, 0, 1)) + pad 0
     const int ho = (hup + pad_sum - ksize) / stride + 1, wo = (wup + pad_sum - ksize) / stride + 1;
     Act y;
     y.n = x.n; y.h = ho; y.w = wo; y.c = cout;
@@ -886,7 +893,7 @@ Act Graph::conv(const Act& x, const Act* x2, int w, int cout, int ksize, int str
     d.ldw = params_[w].ld > 0 ? params_[w].ld : d.K; d.ldo = cout;
     d.a_mode = SDOD_A_CONV3X3;
     d.n_img = x.n; d.h_in = x.h; d.w_in = x.w; d.c0 = x.c; d.c1 = x2 ? x2->c : 0;
-    d.stride = stride; d.upsample = ups; d.ksize = ksize; d.pad_mode = o.pad_mode;
+    d.stride = stride; d.upsample = ups; d.ksize = ksize; d.pad_mode = pad_mode;
     if (o.bias >= 0) d.bias = params_[o.bias].dev;
     else if (o.bias_raw) d.bias = o.bias_raw;
     d.row_bias = o.row_bias; d.ld_row_bias = o.ld_row_bias; d.rows_per_img = o.rows_per_img;
@@ -1335,6 +1342,16 @@ extern "C" int sdod_graph_create_ex(void** graph, int kind, const sdod_model_con
     SDOD_REQUIRE(graph != nullptr && cfg != nullptr, "null argument");
     *graph = nullptr;
     *graph = new Graph(kind, *cfg, batch, adapter ? *adapter : sdod_adapter_config{0, 0, 0});
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_create_wrap(void** graph, int kind, const sdod_model_config* cfg, const sdod_adapter_config* adapter, int wrap,
+                                      int batch) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr && cfg != nullptr, "null argument");
+    *graph = nullptr;
+    *graph = new Graph(kind, *cfg, batch, adapter ? *adapter : sdod_adapter_config{0, 0, 0}, wrap);
     return 0;
     SDOD_CATCH
 }

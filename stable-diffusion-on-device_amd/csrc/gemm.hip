@@ -109,6 +109,10 @@ struct GemmP {
     int xg_s1, xg_s0;        // tiles per wide / narrow panel (tiles_m * width)
     int xg_nbig;             // n-tiles covered by the wide panels
     unsigned mg_s1, sh_s1, mg_s0, sh_s0, mg_w1, sh_w1, mg_w0, sh_w0;
+    // gather form of a convolution: bit 0 = ups, bits 1..2 = the circular border of sdod_gemm_desc::pad_mode 2..4 (bit 1: columns
+    // wrap, bit 2: rows wrap).  A wrapped tap reads pixel (y mod H, x mod W) of its own image, in output coordinates before the >> 1
+    // of upsampling.  LAST, so that every older field keeps its kernarg offset (and the kernels their scalar loads).
+    int gmode;
 };
 
 constexpr int BK = 64;
@@ -143,6 +147,12 @@ SDOD_DEVICE void tile_of(const GemmP& p, int lid, int& tile_m, int& tile_n) {
         tile_m = fast_div(o, p.mg_w0, p.sh_w0);
         tile_n = p.xg_nbig + j * p.xg_w + (o - tile_m * p.xg_w);
     }
+}
+
+// v mod n for v in [-1, n]: a 3x3 tap is at most one pixel outside its image
+SDOD_DEVICE int wrap1(int v, int n) {
+    v += v < 0 ? n : 0;
+    return v - (v >= n ? n : 0);
 }
 
 SDOD_DEVICE int lds_off(int row, int chunk) { return row * 64 + ((chunk ^ (row & 7)) << 3); }
@@ -383,6 +393,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmP p) {
 #pragma unroll
             for (int i = 0; i < A_IT; ++i) {
                 int yy = a_oy[i] + r - pad, xx = a_ox[i] + s - pad;
+                if (p.gmode & 4) yy = wrap1(yy, hup);
+                if (p.gmode & 2) xx = wrap1(xx, wup);
                 const bool ok = a_ok[i] && yy >= 0 && yy < hup && xx >= 0 && xx < wup;
                 yy >>= p.ups;
                 xx >>= p.ups;
@@ -643,7 +655,11 @@ SDOD_DEVICE f16x8 wq_frag(const f16* sB, int row, int ks, int fc, f16 z) {
 // or registers (several sit exactly at the 128-register step that lets two workgroups share a CU).
 // KSUB = slabs per barrier: the ring holds STAGES groups of KSUB slabs and the workgroup synchronises once per GROUP (the
 // counted wait + barrier + loop bookkeeping of a 64-deep slab cost ~0.15 us, a third of a 64x64 tile's slab time).
-template <int BM, int BN, int WM, int WN, int STAGES, bool SPEC = false, bool WQ = false, int KSUB = 1>
+// WRAP = the convolution has a circular border (GemmP::gmode > 1): a compile-time variant like WQ, launched for such descriptors only.
+// As a run-time branch of the gather it cost the zero-pad instantiations registers -- a scalar or two more alive in the slab loop
+// spills SGPRs into a VGPR, and several tiles sit exactly at a VGPR step (64, 80, 128) that decides how many workgroups share a CU
+// (profiles/tiling_isa.txt); with WRAP = false none of its code exists and every older instantiation compiles to what it was.
+template <int BM, int BN, int WM, int WN, int STAGES, bool SPEC = false, bool WQ = false, int KSUB = 1, bool WRAP = false>
 __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kernel(const GemmP p, const f16* __restrict__ zeros) {
     constexpr int NC = WM * WN;                   // waves that own output tiles
     constexpr int NW = SPEC ? 2 * NC : NC;        // waves per workgroup: 4 (one per SIMD) or 8 (two per SIMD)
@@ -746,6 +762,21 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
                 }
             a_mask[i] = mask;
         }
+        // circular border (3x3): a tap of a wrapped axis always exists; the other axis keeps its bound
+        if constexpr (WRAP) {
+            const bool wrap_y = (p.gmode & 4) != 0, wrap_x = (p.gmode & 2) != 0;
+#pragma unroll
+            for (int i = 0; i < A_LD; ++i) {
+                const bool row_ok = m0 + (i * NL + lw) * 8 + lrow < p.M;
+                unsigned mask = 0;
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const bool ok = row_ok & (wrap_y | ((unsigned)(a_py[i] + t / 3) < (unsigned)hup)) & (wrap_x | ((unsigned)(a_px[i] + t % 3) < (unsigned)wup));
+                    mask |= (ok ? 1u : 0u) << t;
+                }
+                a_mask[i] = mask;
+            }
+        }
     #pragma unroll
         for (int i = 0; i < B_LD; ++i) {
             if (!WQ) {
@@ -835,6 +866,22 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
         const int sa = second ? p.sa1 : p.sa0;
         const int ccs = second ? cc - p.c0 : cc;
         if (dbg & 8) {
+        } else if constexpr (WRAP) {
+            // circular border, with or without upsampling: the tap's pixel is recomputed per row and wrapped on the circular axes in
+            // output coordinates (at most one pixel outside: one conditional add / subtract per side); the other axis stays under a_mask
+            const bool wrap_y = (p.gmode & 4) != 0, wrap_x = (p.gmode & 2) != 0; // wave-uniform
+#pragma unroll
+            for (int i = 0; i < A_LD; ++i) {
+                int yy = a_py[i] + r, xx = a_px[i] + sx;
+                if (wrap_y) yy = wrap1(yy, hup);
+                if (wrap_x) xx = wrap1(xx, wup);
+                yy >>= p.ups;
+                xx >>= p.ups;
+                const int ro = ((a_im[i] + yy) * p.w_in + xx) * sa + ccs + lchunk * 8;
+                const bool ok = (a_mask[i] >> tap) & 1u;
+                const f16* g = ok ? src + ro : zeros;
+                __builtin_amdgcn_global_load_lds((glb_void_ptr)g, (lds_void_ptr)(sA + (i * NL + lw) * 8 * 64), 16, 0, 0);
+            }
         } else if (!p.ups) {
             const int sdelta = (r * p.w_in + sx) * sa + ccs; // wave-uniform
 #pragma unroll
@@ -1934,6 +1981,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
                 const int y0 = fast_div(rem0, p.mg_w, p.sh_w);
                 const int x0 = rem0 - y0 * p.w_out;
                 unsigned boff0[NRMAX], boff1[NRMAX], vmask = 0;
+                const int wrap_h = (p.gmode & 4) ? p.h_in : 0, wrap_w = (p.gmode & 2) ? p.w_in : 0; // circular axes: one image height / width, else 0
 #pragma unroll
                 for (int j = 0; j < NRMAX; ++j) {
                     const int pix = (j * 256 + lw * 64 + lane) >> 3;
@@ -1942,7 +1990,11 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmP p, const f16
                     const int py = fast_div(r2, p.mg_pw, p.sh_pw);
                     const int px = r2 - py * p.h_pw;
                     // patch origin in the source image: one pixel above / left of the tile (upsampling: of its pre-image)
-                    const int gy = (p.ups ? (y0 - 1) >> 1 : y0 - 1) + py, gx = (p.ups ? (x0 - 1) >> 1 : x0 - 1) + px, img = img0 + part;
+                    // (a circular axis: the patch lies at most one pixel outside the image, and that pixel is the opposite border's)
+                    int gy = (p.ups ? (y0 - 1) >> 1 : y0 - 1) + py, gx = (p.ups ? (x0 - 1) >> 1 : x0 - 1) + px;
+                    const int img = img0 + part;
+                    gy += gy < 0 ? wrap_h : 0; gy -= gy >= p.h_in ? wrap_h : 0;
+                    gx += gx < 0 ? wrap_w : 0; gx -= gx >= p.w_in ? wrap_w : 0;
                     const bool ok = pix < p.h_npix && img < p.h_nimg && (unsigned)gy < (unsigned)p.h_in && (unsigned)gx < (unsigned)p.w_in;
                     const unsigned gp = ok ? (unsigned)((img * p.h_in + gy) * p.w_in + gx) : 0u;
                     boff0[j] = (gp * (unsigned)p.sa0 + (unsigned)lchunk * 8u) * 2u;
@@ -2703,9 +2755,11 @@ hipError_t launch_tile(const GemmP& p, dim3 grid, size_t smem, hipStream_t st) {
         constexpr size_t lds = (ring > ctile ? ring : ctile) + (size_t)4 * c.bn * sizeof(float); // + per-column epilogue vectors
         constexpr int block = 64 * c.wm * c.wn * (c.spec ? 2 : 1);
         if constexpr (c.u8) {
+            if (p.wq && p.gmode > 1) return launch_kernel<&gemm_glds_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, c.spec != 0, true, c.ksub, true>>(p, grid, block, lds, (int)lds, st);
             if (p.wq) return launch_kernel<&gemm_glds_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, c.spec != 0, true, c.ksub>>(p, grid, block, lds, (int)lds, st);
         }
         if (p.wq) return hipErrorInvalidValue; // (make_plan never leaves a uint8 GEMM on such a tile)
+        if (p.gmode > 1) return launch_kernel<&gemm_glds_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, c.spec != 0, false, c.ksub, true>>(p, grid, block, lds, (int)lds, st);
         return launch_kernel<&gemm_glds_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, c.spec != 0, false, c.ksub>>(p, grid, block, lds, (int)lds, st);
     } else if constexpr (c.family == HALO) {
         static_assert(c.u8, "every halo tile carries its uint8 form");
@@ -2739,7 +2793,7 @@ struct Plan {
 // Can halo tile `tile` run descriptor d?  Fills the geometry fields of *p (may be null) and the LDS bytes of the launch.
 bool halo_geometry(const sdod_gemm_desc* d, int tile, GemmP* p, size_t* smem_bytes) {
     if (!is_halo_tile(tile)) return false;
-    if (d->a_mode != SDOD_A_CONV3X3 || d->ksize == 1 || d->stride != 1 || d->pad_mode || d->geglu || d->ln || d->bias_on_m) return false;
+    if (d->a_mode != SDOD_A_CONV3X3 || d->ksize == 1 || d->stride != 1 || d->pad_mode == 1 || d->geglu || d->ln || d->bias_on_m) return false;
     if (d->wq && d->k_tail) return false;
     if (d->c0 <= 0 || d->c0 % 64 || d->c1 % 64 || d->h_in <= 0 || d->w_in <= 0 || d->n_img <= 0) return false;
     if (d->upsample && d->k_tail) return false;
@@ -3073,7 +3127,7 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
         SDOD_REQUIRE(d->ldo >= d->N / 2, "geglu: ldo must be >= N/2");
     }
     if (d->k_tail) {
-        SDOD_REQUIRE(d->a_mode == SDOD_A_CONV3X3 && d->stride == 1 && !d->upsample && !d->pad_mode, "tail segment needs a stride-1 conv");
+        SDOD_REQUIRE(d->a_mode == SDOD_A_CONV3X3 && d->stride == 1 && !d->upsample && d->pad_mode != 1, "tail segment needs a stride-1 conv");
         SDOD_REQUIRE(d->t0 && d->tc0 > 0 && d->tc0 % 64 == 0 && d->tc1 % 64 == 0 && (d->t1 || d->tc1 == 0), "bad tail sources");
         SDOD_REQUIRE(d->K == d->k_tail + d->tc0 + d->tc1, "K must equal k_tail + tc0 + tc1");
     }
@@ -3092,13 +3146,15 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
         p.stride = d->stride; p.ups = d->upsample ? 1 : 0;
         p.sa0 = d->c0; p.sa1 = d->c1;
         const int hup = d->h_in << p.ups, wup = d->w_in << p.ups;
-        SDOD_REQUIRE(d->pad_mode == 0 || d->pad_mode == 1, "pad_mode must be 0 or 1");
-        SDOD_REQUIRE(!d->pad_mode || (ks == 3 && d->stride == 2 && !d->upsample && d->h_in >= 2 && d->w_in >= 2),
+        SDOD_REQUIRE(d->pad_mode >= 0 && d->pad_mode <= 4, "pad_mode must be 0 .. 4");
+        SDOD_REQUIRE(d->pad_mode < 2 || ks == 3, "pad_mode 2..4 (circular border) needs a 3x3 conv");
+        p.gmode = p.ups | (d->pad_mode == 2 ? 6 : d->pad_mode == 3 ? 2 : d->pad_mode == 4 ? 4 : 0);
+        SDOD_REQUIRE(d->pad_mode != 1 || (ks == 3 && d->stride == 2 && !d->upsample && d->h_in >= 2 && d->w_in >= 2),
                      "pad_mode 1 needs a 3x3 stride-2 conv without upsampling on an image of at least 2 x 2");
         // pad_mode 1: F.pad(x, (0, 1, 0, 1)) then pad 0 -- the gather's low pad is 0 and its per-tap bound masks zero the extra
         // bottom row / right column
-        p.pad = d->pad_mode ? 0 : ks / 2;
-        const int pad_sum = d->pad_mode ? 1 : 2 * (ks / 2);
+        p.pad = d->pad_mode == 1 ? 0 : ks / 2;
+        const int pad_sum = d->pad_mode == 1 ? 1 : 2 * (ks / 2);
         p.h_out = (hup + pad_sum - ks) / d->stride + 1;
         p.w_out = (wup + pad_sum - ks) / d->stride + 1;
         SDOD_REQUIRE(p.h_out > 0 && p.w_out > 0, "conv input smaller than the kernel");

@@ -367,12 +367,20 @@ void Graph::build_unet() {
         settle();
         if (mode_ == REAL) {
             flops_ += 2.0 * B * H * Wd * MC * 64;
-            ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_conv_in_f16(x_in, wp, bp, hp, B, H, Wd, LC, MC, 1.0f, st)); }, "conv_in",
+            const int wr = wrap_;
+            ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_conv_in_wrap_f16(x_in, wp, bp, hp, B, H, Wd, LC, MC, 1.0f, wr, st)); }, "conv_in",
                               2.0 * B * H * Wd * MC * 64, (double)B * H * Wd * (LC * 4 + MC * 2) + MC * 64 * 2,
                               "M" + std::to_string(B * H * Wd) + " N" + std::to_string(MC) + " K64"});
         }
     } else {
         f16* cols = alloc((size_t)B * H * Wd * 64);
+        if (wrap_ != 0) { // the wrapped im2col reads NHWC fp16: sdod_latent_im2col_f16 as the two launches it fuses
+            Act xl = act(B, H, Wd, LC);
+            const int wr = wrap_;
+            emit([=](hipStream_t st) { check_rc2(sdod_latent_prep_f16(x_in, nullptr, nullptr, xl.p, B, LC, H * Wd, 1.0f, st)); });
+            emit([=](hipStream_t st) { check_rc2(sdod_im2col3x3_small_wrap_f16(xl.p, cols, B, H, Wd, LC, 64, wr, st)); });
+            release(xl);
+        } else
         emit([=](hipStream_t st) { check_rc2(sdod_latent_im2col_f16(x_in, cols, B, H, Wd, LC, 64, 1.0f, st)); });
         { GemmOpt o; o.bias = cib; linear(cols, B * H * Wd, 64, ciw, MC, h.p, o); }
         release(cols);
@@ -597,7 +605,8 @@ void Graph::build_vae() {
     int ch = VC * mult[3];
     const int ciw = P("decoder.conv_in.weight", {ch, LC, 3, 3}, PK_CONV3_SMALL), cib = P("decoder.conv_in.bias", {ch}, PK_VEC);
     f16* cols = alloc((size_t)B * H * Wd * 64);
-    emit([=](hipStream_t st) { check_rc2(sdod_im2col3x3_small_f16(zl.p, cols, B, H, Wd, LC, 64, st)); });
+    const int wr = wrap_;
+    emit([=](hipStream_t st) { check_rc2(sdod_im2col3x3_small_wrap_f16(zl.p, cols, B, H, Wd, LC, 64, wr, st)); });
     Act h = act(B, H, Wd, ch);
     { GemmOpt o; o.bias = cib; linear(cols, B * H * Wd, 64, ciw, ch, h.p, o); }
     release(cols); release(zl);

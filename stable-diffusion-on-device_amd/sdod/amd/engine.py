@@ -23,7 +23,10 @@ class ModelConfig(ctypes.Structure):
     adapter_reps = 0
     adapter_hint_channels = 0
     adapter_res_blocks = 0
-    _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks')
+    # Seamless tiling (the `wrap` argument of sdod_graph_create_wrap, which also travels next to the struct): bit 0 = the x axis wraps,
+    # bit 1 = the y axis wraps; read by UNet and VaeDecoder only, 0 = the plain graphs through the old creation entry points.
+    tiling = 0
+    _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'tiling')
 
     @classmethod
     def from_buffer_copy(cls, source, offset=0):
@@ -40,8 +43,18 @@ class AdapterConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks')]
 
 
+TILING_WRAP = {False: 0, True: 3, 'xy': 3, 'x': 1, 'y': 2}
+
+
+def tiling_wrap(tiling):
+    """Txt2Img's `tiling` argument -> the engine's wrap bits (bit 0 = x, bit 1 = y); anything else is a ValueError"""
+    if isinstance(tiling, (bool, str)) and tiling in TILING_WRAP:
+        return TILING_WRAP[tiling]
+    raise ValueError(f"tiling must be False, True, 'xy', 'x' or 'y', not {tiling!r}")
+
+
 def copy_config(cfg):
-    """an independent copy of a ModelConfig, its adapter attributes included"""
+    """an independent copy of a ModelConfig, its adapter and tiling attributes included"""
     return ModelConfig.from_buffer_copy(cfg)
 
 
@@ -52,7 +65,7 @@ class LoraEntry(ctypes.Structure):
 
 
 ENGINE_SYMBOLS = [
-    'sdod_model_config_sd14', 'sdod_model_config_sd21', 'sdod_graph_create', 'sdod_graph_create_ex', 'sdod_graph_destroy', 'sdod_graph_num_params', 'sdod_graph_param_info',
+    'sdod_model_config_sd14', 'sdod_model_config_sd21', 'sdod_graph_create', 'sdod_graph_create_ex', 'sdod_graph_create_wrap', 'sdod_graph_destroy', 'sdod_graph_num_params', 'sdod_graph_param_info',
     'sdod_graph_set_param', 'sdod_graph_param_device', 'sdod_graph_load_file', 'sdod_graph_finalize', 'sdod_graph_io', 'sdod_graph_execute', 'sdod_graph_check',
     'sdod_graph_stats', 'sdod_graph_tune_info', 'sdod_graph_num_ops', 'sdod_graph_op_info', 'sdod_graph_op_detail', 'sdod_graph_profile',
     'sdod_graph_keep_base', 'sdod_graph_base_bytes', 'sdod_graph_set_loras',
@@ -69,6 +82,7 @@ def _engine():
         lib.sdod_model_config_sd21.restype = None
         lib.sdod_graph_create.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), I]
         lib.sdod_graph_create_ex.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(AdapterConfig), I]
+        lib.sdod_graph_create_wrap.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(AdapterConfig), I, I]
         lib.sdod_graph_destroy.argtypes = [P]
         lib.sdod_graph_num_params.argtypes = [P]
         lib.sdod_graph_param_info.argtypes = [P, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I), ctypes.POINTER(ctypes.c_int64)]
@@ -130,14 +144,18 @@ class Graph:
     Without a GPU only the parameter table can be read (what the checkpoint converter needs); everything that touches
     device memory raises."""
 
-    def __init__(self, kind, cfg, batch, device='cuda:0'):
+    def __init__(self, kind, cfg, batch, device='cuda:0', wrap=None):
+        """wrap: None = the creation entry points of every build before seamless tiling; an int 0..3 goes through
+        sdod_graph_create_wrap (0 builds the plain graph there)"""
         self._lib = _engine()
         self._h = ctypes.c_void_p()
         self.kind, self.cfg, self.batch = kind, cfg, batch
         self.device = torch.device(device)
         acfg = AdapterConfig(*(int(getattr(cfg, n, 0)) for n, _ in AdapterConfig._fields_))
         with self._on_device():
-            if kind == ADAPTER or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_):
+            if wrap is not None:
+                check(self._lib.sdod_graph_create_wrap(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(acfg), int(wrap), batch))
+            elif kind == ADAPTER or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_):
                 check(self._lib.sdod_graph_create_ex(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(acfg), batch))
             else:       # no adapter anywhere: the entry point, and the graph, of every build before it
                 check(self._lib.sdod_graph_create(ctypes.byref(self._h), kind, ctypes.byref(cfg), batch))
@@ -297,8 +315,8 @@ class Graph:
 
 
 class UNet(Graph):
-    def __init__(self, cfg, batch, device='cuda:0'):
-        super().__init__(UNET, cfg, batch, device)
+    def __init__(self, cfg, batch, device='cuda:0', wrap=None):
+        super().__init__(UNET, cfg, batch, device, wrap if wrap is not None else (int(getattr(cfg, 'tiling', 0)) or None))
 
     def finalize(self):
         super().finalize()
@@ -363,8 +381,8 @@ class TextEncoder(Graph):
 
 
 class VaeDecoder(Graph):
-    def __init__(self, cfg, batch, device='cuda:0'):
-        super().__init__(VAE_DECODER, cfg, batch, device)
+    def __init__(self, cfg, batch, device='cuda:0', wrap=None):
+        super().__init__(VAE_DECODER, cfg, batch, device, wrap if wrap is not None else (int(getattr(cfg, 'tiling', 0)) or None))
 
     def finalize(self):
         super().finalize()

@@ -81,6 +81,7 @@ def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=N
     wider rows (row stride a multiple of 8 elements, 16 for uint8 w): lda / ldw / ldo / ldr / ld_row_bias are their row strides.
     a: fp16 [M, K] (rows mode) or NHWC [N, H, W, C0] with conv=dict(stride=1|2, upsample=bool) (3x3 pad 1);
     conv=dict(stride=2, pad_mode=1): ldm's VAE-encoder Downsample, F.pad(a, (0, 1, 0, 1)) then a 3x3 stride-2 pad-0 conv;
+    conv=dict(pad_mode=2 | 3 | 4): seamless tiling, the 3x3 pad-1 border is circular on both axes / x only / y only;
     a2: optional second NHWC source concatenated on channels; w: fp16 [Nout, K] (conv: K = 9*(C0+C1), KRSC)."""
     lib = _lib.hip()
     lda = _ld(a, torch.float16, 'a', a.shape[-1]) if conv is None else _req(a, torch.float16, 'a').shape[-1]
@@ -116,7 +117,7 @@ def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=N
         stride = int(conv.get('stride', 1)); ups = 1 if conv.get('upsample', False) else 0
         ks = int(conv.get('ksize', 3))
         pad_mode = int(conv.get('pad_mode', 0))
-        pad_sum = 1 if pad_mode else 2 * (ks // 2)
+        pad_sum = 1 if pad_mode == 1 else 2 * (ks // 2)   # (2 / 3 / 4: the circular borders, same output size as 0)
         hup, wup = h << ups, wd << ups
         ho, wo = (hup + pad_sum - ks) // stride + 1, (wup + pad_sum - ks) // stride + 1
         d.ksize = ks
@@ -458,12 +459,16 @@ def concat_channels(a, b):
     return out
 
 
-def im2col3x3_small(x, kpad=64):
+def im2col3x3_small(x, kpad=64, wrap=None):
+    """wrap (None = sdod_im2col3x3_small_f16; an int goes through sdod_im2col3x3_small_wrap_f16): circular border, bit 0 = x, bit 1 = y"""
     lib = _lib.hip()
     _req(x, torch.float16, 'x')
     n, h, w, c = x.shape
     out = torch.empty((n * h * w, kpad), dtype=torch.float16, device=x.device)
-    check(lib.sdod_im2col3x3_small_f16(_p(x), _p(out), n, h, w, c, kpad, _stream()))
+    if wrap is None:
+        check(lib.sdod_im2col3x3_small_f16(_p(x), _p(out), n, h, w, c, kpad, _stream()))
+    else:
+        check(lib.sdod_im2col3x3_small_wrap_f16(_p(x), _p(out), n, h, w, c, kpad, int(wrap), _stream()))
     return out
 
 
@@ -477,16 +482,20 @@ def latent_im2col(x, kpad=64, scale=1.0):  # kpad=128: the 9-channel inpainting 
     return out
 
 
-def conv_in(x, w, bias, scale=1.0):
+def conv_in(x, w, bias, scale=1.0, wrap=None):
     """the UNet's input convolution in one launch (include/sdod_hip.h: sdod_conv_in_f16): x NCHW fp32 [n, c, h, w], w fp16
-    [cout, 64] (k = tap * c + channel, zero beyond 9 c), bias fp32 [cout] -> NHWC fp16 [n, h, w, cout]"""
+    [cout, 64] (k = tap * c + channel, zero beyond 9 c), bias fp32 [cout] -> NHWC fp16 [n, h, w, cout].  wrap (None = that entry point;
+    an int goes through sdod_conv_in_wrap_f16): circular border, bit 0 = x, bit 1 = y"""
     lib = _lib.hip()
     _req(x, torch.float32, 'x'); _req(w, torch.float16, 'w'); _req(bias, torch.float32, 'bias')
     n, c, h, wd = x.shape
     cout = w.shape[0]
     assert w.shape[1] == 64
     out = torch.empty((n, h, wd, cout), dtype=torch.float16, device=x.device)
-    check(lib.sdod_conv_in_f16(_p(x), _p(w), _p(bias), _p(out), n, h, wd, c, cout, scale, _stream()))
+    if wrap is None:
+        check(lib.sdod_conv_in_f16(_p(x), _p(w), _p(bias), _p(out), n, h, wd, c, cout, scale, _stream()))
+    else:
+        check(lib.sdod_conv_in_wrap_f16(_p(x), _p(w), _p(bias), _p(out), n, h, wd, c, cout, scale, int(wrap), _stream()))
     return out
 
 

@@ -30,11 +30,12 @@ class Txt2Img:
     hires = None        # the second pipeline of the hires pass (Txt2Img(..., hires_hw=)), or None
     adapter = None      # the T2I-Adapter graph (Txt2Img(..., adapter=True)), or None
     adapter_channels = 3
+    tiling = 0          # seamless tiling: the wrap bits the UNet and the VAE decoder were built with (bit 0 = x, bit 1 = y)
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
-                 adapter_channels=3):
+                 adapter_channels=3, tiling=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -66,10 +67,19 @@ class Txt2Img:
         state_dicts['adapter'] or models_dir/adapter.sdodw, for hints of adapter_channels (1 or 3) channels: set_adapter_hint() /
         clear_adapter_hint().  Off, nothing is constructed or sized differently.  Not with cfg_split, hires_hw, inpaint_unet or
         model='sd21' (the released adapters are SD 1.x ones; the other three would each need the slots in a second place): ValueError
-        before any device work, as for an adapter_channels other than 1 or 3."""
+        before any device work, as for an adapter_channels other than 1 or 3.
+        tiling=True or 'xy': seamless tiling -- the left / right and top / bottom edges of every image join without a seam (textures,
+        backgrounds); 'x' / 'y': that axis only ('x': 360-degree panoramas).  The UNet and the VAE decoder are built with a circular
+        border in every 3x3 convolution (E.UNet / E.VaeDecoder on a config copy with cfg.tiling set: sdod_graph_create_wrap); same
+        launches, tiles and memory as the plain graphs, and every sampler, generate / generate_graphed / generate_pipelined,
+        latent_hw, prompt_chunks, loras, model='sd21', weight_quant and cfg_split work as without it.  False: nothing is constructed
+        or sized differently.  Not with with_vae_encoder, inpaint_unet (the encoder graphs are not wrapped: no img2img or inpainting
+        under tiling), hires_hw (the latent resize clamps at the border) or adapter (the adapter graph is not wrapped), and no other
+        value: ValueError before any device work (tiling_check_build)."""
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         latent_h, latent_w = check_latent_hw(latent_hw)
         adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_unet, model)
+        self.tiling = tiling_check_build(tiling, with_vae_encoder, inpaint_unet, hires_hw, adapter)
         if hires_hw is not None:
             check_latent_hw(hires_hw, 'hires_hw')
             if cfg_split or inpaint_unet:
@@ -117,8 +127,12 @@ class Txt2Img:
             unet_cfg = E.copy_config(unet_cfg)
             unet_cfg.adapter_reps = 2
             self.adapter_channels = int(adapter_channels)
+        vae_cfg = self.cfg
+        if self.tiling:                  # the UNet and the VAE decoder take the circular border; every other graph has no border to wrap
+            unet_cfg, vae_cfg = E.copy_config(unet_cfg), E.copy_config(self.cfg)
+            unet_cfg.tiling = vae_cfg.tiling = self.tiling
         self.unet = E.UNet(unet_cfg, self.n if cfg_split else 2 * self.n, device)
-        self.vae = E.VaeDecoder(self.cfg, 1, device) if with_vae else None
+        self.vae = E.VaeDecoder(vae_cfg, 1, device) if with_vae else None
         self.text = E.TextEncoder(self.cfg, 2 * self.prompt_chunks, device) if with_text_encoder else None
         self.encoder = E.VaeEncoder(self.cfg, 1, device) if with_vae_encoder else None
         self.masked_encoder = E.MaskedVaeEncoder(self.cfg, 1, device) if self.inpaint_unet else None
@@ -970,6 +984,21 @@ def adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_
     for name, on in (('cfg_split', cfg_split), ('hires_hw', hires_hw is not None), ('inpaint_unet', inpaint_unet), ("model='sd21'", model == 'sd21')):
         if on:
             raise ValueError(f'adapter=True cannot be combined with {name}')
+
+
+def tiling_check_build(tiling, with_vae_encoder, inpaint_unet, hires_hw, adapter):
+    """Txt2Img's tiling: False, True / 'xy', 'x' or 'y', and for anything but False none of with_vae_encoder, inpaint_unet, hires_hw,
+    adapter.  Returns the engine's wrap bits (0 = off, bit 0 = x, bit 1 = y); raises ValueError."""
+    wrap = E.tiling_wrap(tiling)
+    if not wrap:
+        return 0
+    for name, on, why in (('with_vae_encoder', with_vae_encoder, 'the VAE encoder graph is not wrapped (no img2img under tiling)'),
+                          ('inpaint_unet', inpaint_unet, 'the encoder graphs and the 9-channel input convolution are not wrapped'),
+                          ('hires_hw', hires_hw is not None, 'the latent resize of the hires pass clamps at the border'),
+                          ('adapter', adapter, 'the adapter graph is not wrapped')):
+        if on:
+            raise ValueError(f'tiling cannot be combined with {name}: {why}')
+    return wrap
 
 
 def adapter_check_args(hint_u8, weight, latent, n_images, channels):
