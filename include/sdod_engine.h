@@ -42,6 +42,11 @@
  *                 Adapter(channels=[MC, 2 MC, 4 MC, 4 MC], nums_rb=adapter_res_blocks, ksize=1, sk=True, use_conv=False) on
  *                 pixel_unshuffle8(hint / 255), parameters by the checkpoint's names (conv_in.*, body.K.{in_conv,block1,block2}.*);
  *                 always fp16 weights.  Runs once per hint, not once per step (not part of the reference)
+ *   UPSCALER      in0 img  uint8 HWC [B][H][W][3]        (the pipeline's uint8 image, or any other)
+ *                 out0     fp16 NHWC [B][4H][4W][3], the network's output, nominally in [0, 1], not clamped: ESRGAN's RRDBNet
+ *                 (64 features, growth 32, scale 4, sdod_upscaler_config.num_blocks blocks) on u / 255, parameters by basicsr's names
+ *                 (conv_first, body.N.rdbK.convJ, conv_body, conv_up1, conv_up2, conv_hr, conv_last); always fp16 weights;
+ *                 15 num_blocks + 6 launches (not part of the reference)
  *
  * Parameters are addressed by their CompVis-ldm / HF-CLIP state-dict names (without the
  * `model.diffusion_model.` / `first_stage_model.` / `cond_stage_model.transformer.` prefixes) and are
@@ -64,7 +69,7 @@ extern "C" {
 #endif
 
 enum sdod_graph_kind { SDOD_GRAPH_UNET = 0, SDOD_GRAPH_VAE_DECODER = 1, SDOD_GRAPH_TEXT_ENCODER = 2, SDOD_GRAPH_TEMB = 3,
-                       SDOD_GRAPH_VAE_ENCODER = 4, SDOD_GRAPH_VAE_ENCODER_MASKED = 5, SDOD_GRAPH_ADAPTER = 6 };
+                       SDOD_GRAPH_VAE_ENCODER = 4, SDOD_GRAPH_VAE_ENCODER_MASKED = 5, SDOD_GRAPH_ADAPTER = 6, SDOD_GRAPH_UPSCALER = 7 };
 
 typedef struct sdod_model_config {
     int latent_channels; /* 4 */
@@ -133,6 +138,16 @@ SDOD_API int sdod_graph_create_ex(void** graph, int kind, const sdod_model_confi
  * wrapped UNet commute with it for multiples of 8 (three stride-2 levels); the wrapped decoder commutes with any shift. */
 SDOD_API int sdod_graph_create_wrap(void** graph, int kind, const sdod_model_config* cfg, const sdod_adapter_config* adapter, int wrap,
                                     int batch);
+/* ESRGAN upscaler (SDOD_GRAPH_UPSCALER).  Its three values travel next to sdod_model_config for the same reason, and the kind has
+ * its own create entry because no field of sdod_model_config applies to it: the existing create functions refuse the kind.  Fixed:
+ * 64 features, growth 32, scale 4.  num_blocks in [1, 23]; in_h and in_w multiples of 8 in [8, 1024] (the largest tensor then stays
+ * below 2^31 elements).  NULL or anything else is INVALID_ARGUMENT. */
+typedef struct sdod_upscaler_config {
+    int num_blocks; /* RRDB blocks: 23 (ESRGAN_4x, R-ESRGAN 4x+), 6 (the anime model) */
+    int in_h;       /* input image height */
+    int in_w;       /* input image width */
+} sdod_upscaler_config;
+SDOD_API int sdod_graph_create_upscaler(void** graph, const sdod_upscaler_config* cfg, int batch);
 SDOD_API int sdod_graph_destroy(void* graph);
 
 /* parameter table (fixed by kind + config) */

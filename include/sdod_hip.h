@@ -339,6 +339,48 @@ SDOD_API int sdod_conv_in_cat_f16(const float* x, const float* cond, const void*
  * cannot be prepared as bytes).  With an all-zero mask the result is sdod_image_conv_in_f16's, bit for bit. */
 SDOD_API int sdod_masked_image_conv_in_f16(const uint8_t* img, const uint8_t* mask, const void* w, const float* bias, void* y, int n_img,
                                            int h, int wd, int cout, void* stream);
+/* sdod_image_conv_in_f16 in the [0, 1] space: x = fp16(u / 255), zero padding in THAT space (RRDBNet's conv_first; graph kind
+ * SDOD_GRAPH_UPSCALER).  Not a re-parametrisation of the encoder's entry point: there the border taps see 0 where this space has
+ * -1 -> 0.5, so folding the affine map into weights and bias is wrong on the border pixels.  Same kernel, arguments and checks.
+ * y2 (may be NULL): a second copy of the result with pixel stride ld2 halves (ld2 % 8 == 0, ld2 >= cout, 16-byte aligned) -- the
+ * upscaler keeps y for the trunk's skip while the first dense block updates the copy inside its wide buffer in place. */
+SDOD_API int sdod_image_conv_in_unit_f16(const uint8_t* img, const void* w, const float* bias, void* y, void* y2, int ld2, int n_img, int h,
+                                         int wd, int cout, void* stream);
+
+/* ---- ESRGAN upscaler: the 3x3, stride 1, zero-pad-1 convolution of RRDBNet's residual dense block, NHWC fp16 with
+ * fp32 accumulation, reading a channel prefix of a wide pixel row and writing a column slice of a (possibly the same) wide row:
+ *   acc[pixel][o] = sum_{tap, c < cin} in[pixel + tap][c] * w[o][tap * cin + c]          (w: the KRSC packing [cout][9 cin])
+ *   y = alpha * (acc + bias[o]);  if slope != 0: y = y < 0 ? slope * y : y;  if res1: y += c1 * res1[pixel][o];
+ *   if res2: y += res2[pixel][o];  out[pixel][out_col + o] = fp16(y)                       (fp32 throughout, one rounding)
+ * in: [n][h][w_in] pixels of ld_in halves, of which channels [0, cin) are read and NOTHING else (K is walked in 32-channel chunks;
+ * the other channels may hold Inf or NaN).  cin in {64, 96, 128, 160, 192}, cout in {32, 64}.  upsample = 1: nearest-2x in front of
+ * the convolution, output [n][2h][2w_in] (conv_up1 / conv_up2).  res1 / res2 point at channel 0 of the residual slice of pixel 0
+ * and are read at the output pixel only, by the thread that writes it: either may be the written slice itself (the last
+ * convolution of an RRDB adds the block input it overwrites).  out may be the input buffer when the written columns are disjoint
+ * from [0, cin) (convolutions 1 to 4 of a dense block: ld_out = ld_in, out_col >= cin).  Any n, h, w_in >= 1 with fewer than 2^31
+ * output pixels: tiles are clipped at the image edge.
+ * Errors (INVALID_ARGUMENT before any launch, destination untouched): a null in / w / out; a pointer that is not 16-byte aligned;
+ * another cin or cout; ld_in < cin, or a stride or out_col that is not a multiple of 8; out_col + cout > ld_out; a geometry outside
+ * the above; a non-finite coefficient; a written slice that overlaps the channels read (with upsample: the input at all); a
+ * residual that overlaps the written slice without being that slice or other columns of the same pixel rows. */
+typedef struct sdod_dense_conv_desc {
+    const void* in;     /* fp16 [n][h][w_in][ld_in] */
+    const void* w;      /* fp16 [cout][9 * cin] */
+    const float* bias;  /* fp32 [cout] or NULL */
+    void* out;          /* fp16 [n][h_out][w_out][ld_out]; columns [out_col, out_col + cout) are written */
+    const void* res1;   /* fp16, pixel stride ld_res1, or NULL */
+    const void* res2;   /* fp16, pixel stride ld_res2, or NULL */
+    int ld_in, ld_out, ld_res1, ld_res2;
+    int out_col;
+    int cin, cout;
+    int n, h, w_in;
+    int upsample;
+    float alpha, slope, c1;
+} sdod_dense_conv_desc;
+SDOD_API int sdod_dense_conv3x3_f16(const sdod_dense_conv_desc* d, void* stream);
+/* 1 when the call above takes the descriptor, 0 when it would refuse it.  Host-only. */
+SDOD_API int sdod_dense_conv3x3_ok(const sdod_dense_conv_desc* d);
+
 /* The conditioning input of a 9-channel inpainting UNet in one launch: cond fp32 [reps][n][1 + c][h_lat][w_lat] with
  *   channel 0      = mask_u8[i][8 y][8 x] >= 128 ? 1 : 0   (F.interpolate(mask, size=(h_lat, w_lat)), nearest, of the binarised mask;
  *                                                           mask_u8 uint8 [n][8 h_lat][8 w_lat])

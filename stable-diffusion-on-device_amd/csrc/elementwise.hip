@@ -230,6 +230,20 @@ struct ImageU8Src { // img uint8 HWC [n][h][w][c], value 2 (u / 255) - 1 (ldm im
         return 2.0f * ((float)img[(((size_t)img_i * h + yy) * wd + xx) * c + ch] / 255.0f) - 1.0f;
     }
 };
+struct ImageU8UnitSrc { // img uint8 HWC [n][h][w][c], value u / 255 (RRDBNet's [0, 1] input; the zero border is zero in this space)
+    const uint8_t* img;
+    f16* y2; // second copy of the output, pixel stride ld2 (or NULL)
+    int ld2;
+    SDOD_DEVICE float at(int img_i, int ch, int yy, int xx, int c, int h, int wd) const {
+        return (float)img[(((size_t)img_i * h + yy) * wd + xx) * c + ch] / 255.0f;
+    }
+};
+// a source may ask for a second copy of the output (four channels of row m from column n); the others have none
+template <typename Src>
+SDOD_DEVICE void conv_in_store2(const Src&, long long, int, f16x4) {}
+SDOD_DEVICE void conv_in_store2(const ImageU8UnitSrc& s, long long m, int n, f16x4 o) {
+    if (s.y2) *reinterpret_cast<f16x4*>(s.y2 + (size_t)m * s.ld2 + n) = o;
+}
 // The two sources of the 9-channel inpainting UNet's input (ldm `c_concat`): channels [0, c0) from x, the rest from cond, both NCHW
 // fp32 -- the concatenated tensor is never written
 struct CatSrc {
@@ -334,6 +348,7 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const Src src, const f16* 
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[r] = (f16)(acc[i][j][r] + b[r]);
                 *reinterpret_cast<f16x4*>(y + (size_t)m * cout + n) = o;
+                conv_in_store2(src, m, n, o);
             }
         }
     }
@@ -1165,6 +1180,18 @@ extern "C" int sdod_image_conv_in_f16(const uint8_t* img, const void* w, const f
     SDOD_REQUIRE(cout == 320 || cout == 256 || cout == 128 || cout == 64, "Cout must be 64, 128, 256 or 320");
     SDOD_REQUIRE((((uintptr_t)w | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y & 7) == 0, "misaligned pointer");
     launch_conv_in(ImageU8Src{img}, w, bias, y, n_img, h, wd, 3, cout, (hipStream_t)stream);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_image_conv_in_unit_f16(const uint8_t* img, const void* w, const float* bias, void* y, void* y2, int ld2, int n_img, int h,
+                                           int wd, int cout, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(img && w && y && n_img > 0 && h > 0 && wd > 0, "bad argument");
+    SDOD_REQUIRE(cout == 320 || cout == 256 || cout == 128 || cout == 64, "Cout must be 64, 128, 256 or 320");
+    SDOD_REQUIRE((((uintptr_t)w | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y & 7) == 0, "misaligned pointer");
+    SDOD_REQUIRE(!y2 || (ld2 >= cout && ld2 % 8 == 0 && ((uintptr_t)y2 & 15) == 0 && y2 != y), "y2 needs ld2 >= cout, ld2 % 8 == 0 and 16-byte alignment");
+    launch_conv_in(ImageU8UnitSrc{img, (f16*)y2, ld2}, w, bias, y, n_img, h, wd, 3, cout, (hipStream_t)stream);
     return 0;
     SDOD_CATCH
 }

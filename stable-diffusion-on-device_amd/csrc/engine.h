@@ -65,7 +65,8 @@ struct IoSlot {
 
 class Graph {
 public:
-    Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg = sdod_adapter_config{0, 0, 0}, int wrap = 0);
+    Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg = sdod_adapter_config{0, 0, 0}, int wrap = 0,
+          const sdod_upscaler_config& ucfg = sdod_upscaler_config{0, 0, 0});
     ~Graph();
     Graph(const Graph&) = delete;
 
@@ -91,6 +92,7 @@ private:
     int kind_;
     sdod_model_config cfg_;
     sdod_adapter_config acfg_; // T2I-Adapter: all zero = no adapter inputs (UNET), required for kind ADAPTER
+    sdod_upscaler_config ucfg_; // kind UPSCALER only (sdod_graph_create_upscaler); all zero for every other kind
     int batch_;
     int wrap_ = 0; // seamless tiling (UNET, VAE_DECODER): bit 0 = x wraps, bit 1 = y wraps; conv() turns it into sdod_gemm_desc::pad_mode
     Mode mode_ = DECLARE;
@@ -181,6 +183,7 @@ private:
     void build_clip();
     void build_temb();
     void build_adapter();
+    void build_upscaler();
 
     // ---- op emitters (record in REAL mode, account in DRY mode, nothing in DECLARE mode)
     struct GemmOpt {
@@ -206,6 +209,7 @@ private:
         int w_img_stride = 0, vec_img_stride = 0; // per-image weights / vectors (sdod_gemm_desc), with rows_per_img
         int softmax_cols = 0;
         int pad_mode = 0;          // conv(): sdod_gemm_desc::pad_mode
+        int split_k = 0;           // conv(): sdod_gemm_desc::split_k (0 = planned; 1 = one launch whatever the shape)
     };
     // registers the LayerNorm fold of Linear `w_param` ([N][K], row stride ldw): gamma is multiplied into W in place at finalize,
     // the returned device vectors (owned by the graph) are s[n] = sum_k W'[n][k] and t[n] = sum_k beta[k] W[n][k] + bias[n]
@@ -238,6 +242,8 @@ private:
     Act conv(const Act& x, const Act* x2, int w, int cout, int ksize, int stride, bool upsample, const GemmOpt& o);
     Act group_norm(const Act& x, const Act* x2, int gw, int gb, float eps, bool silu);
     Act layer_norm(const Act& x, int lw, int lb, float eps);
+    // the upscaler's dense-block convolution (sdod_dense_conv3x3_f16): one launch-list entry; w / bias are parameter indices
+    void dense_conv(sdod_dense_conv_desc d, int w, int bias);
     void attention(const f16* q, const f16* k, const f16* v, f16* out, int B, int heads, int lq, int lk, int d, int ldq,
                    int ldk, int ldv, int ldo, bool causal);
 

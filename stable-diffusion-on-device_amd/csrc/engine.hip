@@ -41,9 +41,18 @@ static void parallel_for(int64_t n, F&& fn) {
 }
 
 // ------------------------------------------------------------------------------------------ lifecycle
-Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg, int wrap)
-    : kind_(kind), cfg_(cfg), acfg_(acfg), batch_(batch), wrap_(wrap) {
-    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_ADAPTER, "unknown graph kind");
+Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg, int wrap, const sdod_upscaler_config& ucfg)
+    : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), batch_(batch), wrap_(wrap) {
+    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_UPSCALER, "unknown graph kind");
+    if (kind == SDOD_GRAPH_UPSCALER) {
+        SDOD_REQUIRE(ucfg.num_blocks != 0 || ucfg.in_h != 0 || ucfg.in_w != 0, "the UPSCALER graph is created by sdod_graph_create_upscaler");
+        SDOD_REQUIRE(ucfg.num_blocks >= 1 && ucfg.num_blocks <= 23, "num_blocks must be in [1, 23]");
+        SDOD_REQUIRE(ucfg.in_h >= 8 && ucfg.in_h <= 1024 && ucfg.in_h % 8 == 0 && ucfg.in_w >= 8 && ucfg.in_w <= 1024 && ucfg.in_w % 8 == 0,
+                     "in_h and in_w must be multiples of 8 in [8, 1024]");
+        cfg_.weight_quant = 0; // the upscaler's weights are always fp16
+    } else {
+        SDOD_REQUIRE(ucfg.num_blocks == 0 && ucfg.in_h == 0 && ucfg.in_w == 0, "an upscaler configuration needs kind SDOD_GRAPH_UPSCALER");
+    }
     SDOD_REQUIRE(batch > 0 && batch <= 64, "batch must be in [1, 64]");
     SDOD_REQUIRE(cfg.model_channels > 0 && cfg.model_channels % 64 == 0, "model_channels must be a multiple of 64");
     SDOD_REQUIRE(cfg.context_dim % 64 == 0, "context_dim must be a multiple of 64");
@@ -899,6 +908,7 @@ Act Graph::conv(const Act& x, const Act* x2, int w, int cout, int ksize, int str
     d.row_bias = o.row_bias; d.ld_row_bias = o.ld_row_bias; d.rows_per_img = o.rows_per_img;
     d.residual = o.residual; d.ldr = cout;
     d.act = o.act; d.alpha = o.alpha;
+    d.split_k = o.split_k;
     if (params_[w].quant) {
         if (o.tail0) throw Error(INTERNAL_ERROR, "tail segment with uint8 weights");
         d.wq = 1;
@@ -981,6 +991,7 @@ void Graph::build() {
     case SDOD_GRAPH_VAE_ENCODER: build_vae_encoder(false); break;
     case SDOD_GRAPH_VAE_ENCODER_MASKED: build_vae_encoder(true); break;
     case SDOD_GRAPH_ADAPTER: build_adapter(); break;
+    case SDOD_GRAPH_UPSCALER: build_upscaler(); break;
     default: build_temb(); break;
     }
     settle();
@@ -1352,6 +1363,18 @@ extern "C" int sdod_graph_create_wrap(void** graph, int kind, const sdod_model_c
     SDOD_REQUIRE(graph != nullptr && cfg != nullptr, "null argument");
     *graph = nullptr;
     *graph = new Graph(kind, *cfg, batch, adapter ? *adapter : sdod_adapter_config{0, 0, 0}, wrap);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_create_upscaler(void** graph, const sdod_upscaler_config* ucfg, int batch) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr, "null argument");
+    *graph = nullptr;
+    SDOD_REQUIRE(ucfg != nullptr, "null upscaler configuration");
+    sdod_model_config cfg{};
+    sdod_model_config_sd14(&cfg); // (no field applies to this kind; the constructor's common checks want a valid one)
+    *graph = new Graph(SDOD_GRAPH_UPSCALER, cfg, batch, sdod_adapter_config{0, 0, 0}, 0, *ucfg);
     return 0;
     SDOD_CATCH
 }

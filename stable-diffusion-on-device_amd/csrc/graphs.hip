@@ -797,6 +797,99 @@ void Graph::build_adapter() {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ ESRGAN upscaler
+void Graph::dense_conv(sdod_dense_conv_desc d, int w, int bias) {
+    settle();
+    if (mode_ == DECLARE) return;
+    d.w = params_[w].dev;
+    d.bias = W<float>(bias);
+    if (mode_ != REAL) return;
+    SDOD_REQUIRE(sdod_dense_conv3x3_ok(&d) == 1, "dense-block convolution refused by its kernel");
+    const double px = (double)d.n * (d.h << d.upsample) * (d.w_in << d.upsample);
+    const double fl = 2.0 * px * d.cout * 9.0 * d.cin;
+    flops_ += fl;
+    const double by = (double)d.n * d.h * d.w_in * d.cin * 2 + 9.0 * d.cin * d.cout * 2 + px * d.cout * 2 * (1 + (d.res1 ? 1 : 0) + (d.res2 ? 1 : 0));
+    ops_.push_back(Op{[d](hipStream_t st) { check_rc2(sdod_dense_conv3x3_f16(&d, st)); }, d.cout == 32 ? "dense_conv_n32" : "dense_conv_n64", fl, by,
+                      std::string("conv3") + (d.upsample ? "u" : "") + " M" + std::to_string((long long)px) + " N" + std::to_string(d.cout) + " K" +
+                          std::to_string(9 * d.cin)});
+}
+
+// ESRGAN's RRDBNet (Wang et al. 2018; basicsr's RRDBNet(3, 3, num_feat=64, num_block, num_grow_ch=32, scale=4)) on u / 255:
+//   f = conv_first(x);  t = f;  per block: t = RRDB(t);  f = f + conv_body(t);
+//   f = lrelu(conv_up1(up2(f)));  f = lrelu(conv_up2(up2(f)));  out = conv_last(lrelu(conv_hr(f)))        (lrelu: slope 0.2)
+//   RDB(x): x1..x4 = lrelu(conv_k(x | x1 | ..)), x5 = conv5(x | x1..x4), 0.2 x5 + x;   RRDB(x) = 0.2 RDB3(RDB2(RDB1(x))) + x
+// Buffer plan: three [B H W][192] buffers, one per RDB of a block.  A buffer's channels [0, 64) are the RDB's input and convolution k
+// writes x_k into channels [64 + 32 (k - 1), 64 + 32 k) of the same buffer, so the concat is the buffer itself; conv5 writes the RDB's
+// output (residual in the epilogue) into channels [0, 64) of the next buffer, and the third RDB's conv5 folds the RRDB residual and
+// writes the block's output over the block's input in the first buffer (y = 0.04 (acc + b) + 0.2 x3 + x0).  No concat, activation or
+// add launch: 15 launches per block.  conv_first keeps a dense copy of its output for conv_body's skip; nearest-2x is folded into
+// conv_up1 / conv_up2 (the dense-block kernel with cin = 64); conv_last (64 -> 3) is the gather GEMM.  15 num_blocks + 6 launches.
+void Graph::build_upscaler() {
+    const int B = batch_, H = ucfg_.in_h, Wd = ucfg_.in_w, NB = ucfg_.num_blocks;
+    constexpr int NF = 64, GC = 32, LD = NF + 4 * GC;
+    const uint8_t* img_in = (const uint8_t*)io_alloc(inputs_, (size_t)B * H * Wd * 3);
+    f16* img_out = (f16*)io_alloc(outputs_, (size_t)B * (4 * H) * (4 * Wd) * 3 * sizeof(f16));
+    const size_t rows = (size_t)B * H * Wd;
+
+    const int cfw = P("conv_first.weight", {NF, 3, 3, 3}, PK_CONV3_SMALL), cfb = P("conv_first.bias", {NF}, PK_VEC);
+    Act feat = act(B, H, Wd, NF);
+    f16* buf[3];
+    for (int i = 0; i < 3; ++i) buf[i] = alloc(rows * LD);
+    {
+        const f16* wp = mode_ != DECLARE ? W<f16>(cfw) : nullptr;
+        const float* bp = mode_ != DECLARE ? W<float>(cfb) : nullptr;
+        f16 *fp = feat.p, *b0 = buf[0];
+        const double fl = 2.0 * rows * NF * 64;
+        if (mode_ == REAL) flops_ += fl;
+        emit([=](hipStream_t st) { check_rc2(sdod_image_conv_in_unit_f16(img_in, wp, bp, fp, b0, LD, B, H, Wd, NF, st)); }, "image_conv_in_unit", fl,
+             (double)rows * (3 + NF * 4) + NF * 64 * 2);
+    }
+    auto dc = [&](const f16* in, int ld_in, int cin, int w, int b, f16* out, int ld_out, int out_col, int cout, int h, int wd, int ups, float alpha,
+                  float slope, const f16* r1, int ld1, float c1, const f16* r2, int ld2) {
+        sdod_dense_conv_desc d{};
+        d.in = in; d.out = out; d.res1 = r1; d.res2 = r2;
+        d.ld_in = ld_in; d.ld_out = ld_out; d.ld_res1 = ld1; d.ld_res2 = ld2;
+        d.out_col = out_col; d.cin = cin; d.cout = cout;
+        d.n = B; d.h = h; d.w_in = wd; d.upsample = ups;
+        d.alpha = alpha; d.slope = slope; d.c1 = c1;
+        dense_conv(d, w, b);
+    };
+    for (int blk = 0; blk < NB; ++blk)
+        for (int r = 0; r < 3; ++r) {
+            const std::string pfx = "body." + std::to_string(blk) + ".rdb" + std::to_string(r + 1) + ".conv";
+            f16* cur = buf[r];
+            for (int k = 1; k <= 5; ++k) {
+                const int cin = NF + GC * (k - 1), cout = k < 5 ? GC : NF;
+                const int w = P(pfx + std::to_string(k) + ".weight", {cout, cin, 3, 3}, PK_CONV3), b = P(pfx + std::to_string(k) + ".bias", {cout}, PK_VEC);
+                if (k < 5) dc(cur, LD, cin, w, b, cur, LD, cin, cout, H, Wd, 0, 1.0f, 0.2f, nullptr, 0, 0.f, nullptr, 0);
+                else if (r < 2) dc(cur, LD, cin, w, b, buf[r + 1], LD, 0, cout, H, Wd, 0, 0.2f, 0.f, cur, LD, 1.0f, nullptr, 0);
+                else dc(cur, LD, cin, w, b, buf[0], LD, 0, cout, H, Wd, 0, 0.04f, 0.f, cur, LD, 0.2f, buf[0], LD);
+            }
+        }
+    const int cbw = P("conv_body.weight", {NF, NF, 3, 3}, PK_CONV3), cbb = P("conv_body.bias", {NF}, PK_VEC);
+    const int u1w = P("conv_up1.weight", {NF, NF, 3, 3}, PK_CONV3), u1b = P("conv_up1.bias", {NF}, PK_VEC);
+    const int u2w = P("conv_up2.weight", {NF, NF, 3, 3}, PK_CONV3), u2b = P("conv_up2.bias", {NF}, PK_VEC);
+    const int hrw = P("conv_hr.weight", {NF, NF, 3, 3}, PK_CONV3), hrb = P("conv_hr.bias", {NF}, PK_VEC);
+    const int lw = P("conv_last.weight", {3, NF, 3, 3}, PK_CONV3), lb = P("conv_last.bias", {3}, PK_VEC);
+    // f = feat + conv_body(trunk): into buffer 1's first rows, dense (buffers 1 and 2 are free once the trunk is done)
+    f16* f0 = buf[1];
+    dc(buf[0], LD, NF, cbw, cbb, f0, NF, 0, NF, H, Wd, 0, 1.0f, 0.f, feat.p, NF, 1.0f, nullptr, 0);
+    release(feat);
+    release(buf[0]);
+    release(buf[2]);
+    Act f1 = act(B, 2 * H, 2 * Wd, NF);
+    dc(f0, NF, NF, u1w, u1b, f1.p, NF, 0, NF, H, Wd, 1, 1.0f, 0.2f, nullptr, 0, 0.f, nullptr, 0);
+    release(buf[1]);
+    Act f2 = act(B, 4 * H, 4 * Wd, NF);
+    dc(f1.p, NF, NF, u2w, u2b, f2.p, NF, 0, NF, 2 * H, 2 * Wd, 1, 1.0f, 0.2f, nullptr, 0, 0.f, nullptr, 0);
+    release(f1);
+    Act f3 = act(B, 4 * H, 4 * Wd, NF);
+    dc(f2.p, NF, NF, hrw, hrb, f3.p, NF, 0, NF, 4 * H, 4 * Wd, 0, 1.0f, 0.2f, nullptr, 0, 0.f, nullptr, 0);
+    release(f2);
+    { GemmOpt o; o.bias = lb; o.out = img_out; o.split_k = 1; conv(f3, nullptr, lw, 3, 3, 1, false, o); }
+    release(f3);
+}
+
 // ------------------------------------------------------------------------------------------------ CLIP
 void Graph::build_clip() {
     const int B = batch_, L = cfg_.context_len, D = cfg_.context_dim, heads = cfg_.text_heads, NL = cfg_.text_layers;

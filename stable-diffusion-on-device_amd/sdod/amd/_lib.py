@@ -95,6 +95,13 @@ class GemmDesc(ctypes.Structure):
     ]
 
 
+class DenseConvDesc(ctypes.Structure):
+    """mirror of `struct sdod_dense_conv_desc` (include/sdod_hip.h)"""
+    _fields_ = [(k, c_void_p) for k in ('inp', 'w', 'bias', 'out', 'res1', 'res2')] + \
+               [(k, c_int) for k in ('ld_in', 'ld_out', 'ld_res1', 'ld_res2', 'out_col', 'cin', 'cout', 'n', 'h', 'w_in', 'upsample')] + \
+               [(k, c_float) for k in ('alpha', 'slope', 'c1')]
+
+
 def _declare(lib):
     P = c_void_p
     sig = {
@@ -144,6 +151,9 @@ def _declare(lib):
         'sdod_conv_in_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
         'sdod_conv_in_wrap_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P]),
         'sdod_image_conv_in_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
+        'sdod_image_conv_in_unit_f16': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+        'sdod_dense_conv3x3_f16': (c_int, [ctypes.POINTER(DenseConvDesc), P]),
+        'sdod_dense_conv3x3_ok': (c_int, [ctypes.POINTER(DenseConvDesc)]),
         'sdod_conv_in_cat_f16': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
         'sdod_masked_image_conv_in_f16': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
         'sdod_inpaint_cond_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint64, ctypes.c_uint64, P]),
@@ -184,7 +194,7 @@ HIP_SYMBOLS = [
     'sdod_add_f16', 'sdod_concat_channels_f16', 'sdod_pixel_unshuffle_u8_f16', 'sdod_avg_pool2_f16', 'sdod_adapter_stage_f16', 'sdod_add_feature_f16', 'sdod_im2col3x3_small_f16', 'sdod_im2col3x3_small_wrap_f16', 'sdod_latent_im2col_f16', 'sdod_conv_in_f16', 'sdod_conv_in_wrap_f16', 'sdod_image_conv_in_f16', 'sdod_conv_in_cat_f16', 'sdod_masked_image_conv_in_f16', 'sdod_inpaint_cond_f32', 'sdod_encode_latent_f32', 'sdod_latent_resize_f32', 'sdod_latent_resize_taps', 'sdod_plms_update', 'sdod_dpm_step', 'sdod_ddim_inpaint_step', 'sdod_k_step', 'sdod_mask_to_latent_f32', 'sdod_image_composite_u8', 'sdod_nchw_f32_to_nhwc_f16',
     'sdod_nhwc_f16_to_nchw_f32', 'sdod_latent_prep_f16', 'sdod_embedding_f16', 'sdod_context_assemble_f16', 'sdod_timestep_features_f16', 'sdod_cfg_combine', 'sdod_stage_unet_inputs', 'sdod_randn_f32',
     'sdod_dpm_update', 'sdod_ddim_step_f32', 'sdod_lincomb4_f32', 'sdod_image_to_u8', 'sdod_hip_last_error',
-    'sdod_hip_device_info',
+    'sdod_hip_device_info', 'sdod_image_conv_in_unit_f16', 'sdod_dense_conv3x3_f16', 'sdod_dense_conv3x3_ok',
 ]
 
 

@@ -9,6 +9,8 @@ step for the MI355X build.  It runs on a host without a GPU: the engine's parame
 
     python -m sdod.amd.convert --adapter t2iadapter_canny_sd14v1.pth --out models/     # adapter.sdodw (Txt2Img(adapter=True))
 
+    python -m sdod.amd.convert --upscaler RealESRGAN_x4plus.pth --out models/          # upscaler.sdodw (Txt2Img(upscaler=True))
+
 Only loaders that execute nothing from the file are used: safetensors, or torch.load(weights_only=True).
 """
 import argparse
@@ -161,11 +163,107 @@ def convert_adapter(path, out_dir, dtype=torch.float16):
     return out
 
 
+UPSCALER_TOP = ('conv_first', 'conv_body', 'conv_up1', 'conv_up2', 'conv_hr', 'conv_last')
+# the same network under the original ESRGAN repository's two namings -> basicsr's (the graph's)
+_ESRGAN_NEW_ARCH = {'trunk_conv': 'conv_body', 'upconv1': 'conv_up1', 'upconv2': 'conv_up2', 'HRconv': 'conv_hr'}
+_ESRGAN_OLD_ARCH = {'model.0': 'conv_first', 'model.3': 'conv_up1', 'model.6': 'conv_up2', 'model.8': 'conv_hr', 'model.10': 'conv_last'}
+
+
+def upscaler_state_dict(sd):
+    """An ESRGAN / Real-ESRGAN x4 RRDBNet state dict under any of its three namings -> (basicsr-named dict, num_blocks).  A
+    `params_ema` or `params` wrapper is unwrapped.  Accepted: basicsr / Real-ESRGAN (conv_first, body.N.rdbK.convJ, conv_body, conv_up1,
+    conv_up2, conv_hr, conv_last), the original ESRGAN "new arch" (RRDB_trunk.N.RDBk.convJ, trunk_conv, upconv1, upconv2, HRconv) and
+    its "old arch" (model.0, model.1.sub.N.RDBk.convJ.0, model.1.sub.<nb> for the trunk convolution, model.3, model.6, model.8,
+    model.10).  Refused by name with ValueError: x2 and x1 models, feature / growth widths other than 64 / 32, SRVGGNetCompact keys,
+    anything without conv_first or model.0."""
+    import re
+    for wrap in ('params_ema', 'params'):
+        if isinstance(sd, dict) and wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+            break
+    keys = list(sd)
+    if any(re.match(r'body\.\d+\.(weight|bias)$', k) for k in keys):
+        raise ValueError('SRVGGNetCompact keys (body.N.weight): the compact Real-ESRGAN networks are not supported, only RRDBNet')
+    out = {}
+    if 'conv_first.weight' in sd and any(k.startswith('body.') for k in keys):
+        out = dict(sd)
+    elif 'conv_first.weight' in sd and any(k.startswith('RRDB_trunk.') for k in keys):
+        for k, v in sd.items():
+            m = re.match(r'RRDB_trunk\.(\d+)\.RDB(\d)\.conv(\d)\.(weight|bias)$', k)
+            if m:
+                out[f'body.{m.group(1)}.rdb{m.group(2)}.conv{m.group(3)}.{m.group(4)}'] = v
+                continue
+            stem, _, leaf = k.rpartition('.')
+            out[_ESRGAN_NEW_ARCH.get(stem, stem) + '.' + leaf] = v
+    elif 'model.0.weight' in sd:
+        subs = sorted({int(m.group(1)) for m in (re.match(r'model\.1\.sub\.(\d+)\.', k) for k in keys) if m})
+        if not subs:
+            raise ValueError('old-arch ESRGAN keys without model.1.sub.N: not an RRDBNet')
+        nb = subs[-1]                                   # model.1.sub.<nb> is the trunk convolution behind blocks 0 .. nb - 1
+        for k, v in sd.items():
+            m = re.match(r'model\.1\.sub\.(\d+)\.RDB(\d)\.conv(\d)\.0\.(weight|bias)$', k)
+            if m:
+                out[f'body.{m.group(1)}.rdb{m.group(2)}.conv{m.group(3)}.{m.group(4)}'] = v
+                continue
+            stem, _, leaf = k.rpartition('.')
+            if stem == f'model.1.sub.{nb}':
+                out['conv_body.' + leaf] = v
+            else:
+                out[_ESRGAN_OLD_ARCH.get(stem, stem) + '.' + leaf] = v
+    else:
+        raise ValueError('not an ESRGAN RRDBNet state dict: neither conv_first.weight nor model.0.weight is present')
+    cf = out['conv_first.weight']
+    if cf.dim() == 4 and int(cf.shape[1]) == 12:
+        raise ValueError('x2 model (conv_first takes 12 channels, the pixel-unshuffled input): only x4 models are supported')
+    if cf.dim() == 4 and int(cf.shape[1]) == 48:
+        raise ValueError('x1 model (conv_first takes 48 channels, the pixel-unshuffled input): only x4 models are supported')
+    if 'conv_up2.weight' not in out:
+        raise ValueError('x1 / x2 model (no conv_up2): only x4 models are supported')
+    if cf.dim() != 4 or tuple(cf.shape[1:]) != (3, 3, 3):
+        raise ValueError(f'conv_first.weight has shape {tuple(cf.shape)}, expected [64, 3, 3, 3]')
+    g = out.get('body.0.rdb1.conv1.weight')
+    if int(cf.shape[0]) != 64 or g is None or int(g.shape[0]) != 32:
+        raise ValueError(f'feature / growth widths {int(cf.shape[0])} / {None if g is None else int(g.shape[0])}: only 64 / 32 is supported')
+    blocks = sorted({int(m.group(1)) for m in (re.match(r'body\.(\d+)\.', k) for k in out) if m})
+    if blocks != list(range(len(blocks))) or not 1 <= len(blocks) <= 23:
+        raise ValueError(f'body.N blocks {blocks[:3]}..{blocks[-1:]}: 1 to 23 consecutive blocks are supported')
+    return out, len(blocks)
+
+
+def upscaler_table(num_blocks):
+    """[(name, shape), ...] of the UPSCALER graph; no device needed"""
+    return E.Upscaler(num_blocks, (8, 8), 1).param_table()
+
+
+def upscaler_parameters(sd, dtype=torch.float16):
+    """a state dict as upscaler_state_dict takes it -> ({graph name: tensor of `dtype`}, num_blocks), every shape checked"""
+    sd, nb = upscaler_state_dict(sd)
+    part = {}
+    for name, shape in upscaler_table(nb):
+        if name not in sd:
+            raise KeyError(f'{name} is missing from the upscaler checkpoint')
+        if tuple(sd[name].shape) != tuple(shape):
+            raise ValueError(f'{name}: checkpoint shape {tuple(sd[name].shape)} != graph shape {tuple(shape)}')
+        part[name] = sd[name].to(dtype)
+    return part, nb
+
+
+def convert_upscaler(path, out_dir, dtype=torch.float16):
+    """an ESRGAN_4x / RealESRGAN_x4plus(.pth, .safetensors) checkpoint -> out_dir/upscaler.sdodw; returns the file written"""
+    part, _ = upscaler_parameters(read_checkpoint(path), dtype)
+    os.makedirs(out_dir, exist_ok=True)
+    out = os.path.join(out_dir, 'upscaler.sdodw')
+    weights.save(out, part)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     ap.add_argument('--ckpt', help='sd-v1-x .ckpt / .safetensors (ldm key names)')
     ap.add_argument('--adapter', help='a TencentARC T2I-Adapter checkpoint (t2iadapter_{canny,depth,sketch,seg,openpose,keypose}_sd14v1.pth): '
                                       'write adapter.sdodw (Txt2Img(adapter=True)); with or without --ckpt')
+    ap.add_argument('--upscaler', help='an ESRGAN x4 RRDBNet checkpoint (ESRGAN_4x, RealESRGAN_x4plus, the 6-block anime model; basicsr or '
+                                       'original ESRGAN key names): write upscaler.sdodw (Txt2Img(upscaler=True)); with or without --ckpt')
     ap.add_argument('--out', required=True, help='models_dir to write')
     ap.add_argument('--fp32', action='store_true', help='keep fp32 payloads (the engine converts at load)')
     ap.add_argument('--model', default='sd14', choices=['sd14', 'sd21'], help='sd21: SD v2.x shapes and open_clip text-tower key names')
@@ -176,8 +274,8 @@ def main(argv=None):
     ap.add_argument('--tokenizer-vocab', help='bpe_simple_vocab_16e6.txt.gz, or a directory with HF vocab.json + merges.txt: '
                                               'also write ctokenizer.txt')
     a = ap.parse_args(argv)
-    if not a.ckpt and not a.adapter:
-        ap.error('one of --ckpt and --adapter is required')
+    if not a.ckpt and not a.adapter and not a.upscaler:
+        ap.error('one of --ckpt, --adapter and --upscaler is required')
     cfg = E.sd21_config() if a.model == 'sd21' else None
     if a.inpaint:
         cfg = cfg or E.sd14_config()
@@ -187,6 +285,8 @@ def main(argv=None):
             print('wrote', p)
     if a.adapter:
         print('wrote', convert_adapter(a.adapter, a.out, torch.float32 if a.fp32 else torch.float16))
+    if a.upscaler:
+        print('wrote', convert_upscaler(a.upscaler, a.out, torch.float32 if a.fp32 else torch.float16))
     if a.tokenizer_vocab:
         from . import tokenizer_file
         print('wrote', tokenizer_file.generate(a.tokenizer_vocab, os.path.join(a.out, 'ctokenizer.txt')))

@@ -9,7 +9,7 @@ import torch
 from . import _lib
 from ._lib import check
 
-UNET, VAE_DECODER, TEXT_ENCODER, TEMB, VAE_ENCODER, VAE_ENCODER_MASKED, ADAPTER = 0, 1, 2, 3, 4, 5, 6
+UNET, VAE_DECODER, TEXT_ENCODER, TEMB, VAE_ENCODER, VAE_ENCODER_MASKED, ADAPTER, UPSCALER = 0, 1, 2, 3, 4, 5, 6, 7
 
 
 class ModelConfig(ctypes.Structure):
@@ -43,6 +43,11 @@ class AdapterConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks')]
 
 
+class UpscalerConfig(ctypes.Structure):
+    """mirror of `struct sdod_upscaler_config`"""
+    _fields_ = [(n, ctypes.c_int) for n in ('num_blocks', 'in_h', 'in_w')]
+
+
 TILING_WRAP = {False: 0, True: 3, 'xy': 3, 'x': 1, 'y': 2}
 
 
@@ -68,7 +73,7 @@ ENGINE_SYMBOLS = [
     'sdod_model_config_sd14', 'sdod_model_config_sd21', 'sdod_graph_create', 'sdod_graph_create_ex', 'sdod_graph_create_wrap', 'sdod_graph_destroy', 'sdod_graph_num_params', 'sdod_graph_param_info',
     'sdod_graph_set_param', 'sdod_graph_param_device', 'sdod_graph_load_file', 'sdod_graph_finalize', 'sdod_graph_io', 'sdod_graph_execute', 'sdod_graph_check',
     'sdod_graph_stats', 'sdod_graph_tune_info', 'sdod_graph_num_ops', 'sdod_graph_op_info', 'sdod_graph_op_detail', 'sdod_graph_profile',
-    'sdod_graph_keep_base', 'sdod_graph_base_bytes', 'sdod_graph_set_loras',
+    'sdod_graph_keep_base', 'sdod_graph_base_bytes', 'sdod_graph_set_loras', 'sdod_graph_create_upscaler',
 ]
 
 
@@ -83,6 +88,7 @@ def _engine():
         lib.sdod_graph_create.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), I]
         lib.sdod_graph_create_ex.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(AdapterConfig), I]
         lib.sdod_graph_create_wrap.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(AdapterConfig), I, I]
+        lib.sdod_graph_create_upscaler.argtypes = [ctypes.POINTER(P), ctypes.POINTER(UpscalerConfig), I]
         lib.sdod_graph_destroy.argtypes = [P]
         lib.sdod_graph_num_params.argtypes = [P]
         lib.sdod_graph_param_info.argtypes = [P, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I), ctypes.POINTER(ctypes.c_int64)]
@@ -153,7 +159,9 @@ class Graph:
         self.device = torch.device(device)
         acfg = AdapterConfig(*(int(getattr(cfg, n, 0)) for n, _ in AdapterConfig._fields_))
         with self._on_device():
-            if wrap is not None:
+            if kind == UPSCALER:    # its configuration is the UpscalerConfig itself; no ModelConfig field applies
+                check(self._lib.sdod_graph_create_upscaler(ctypes.byref(self._h), ctypes.byref(cfg), batch))
+            elif wrap is not None:
                 check(self._lib.sdod_graph_create_wrap(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(acfg), int(wrap), batch))
             elif kind == ADAPTER or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_):
                 check(self._lib.sdod_graph_create_ex(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(acfg), batch))
@@ -353,6 +361,39 @@ class Adapter(Graph):
         c, b = self.cfg, self.batch
         self.hint = self.io_tensor(False, 0, (b, 8 * c.latent_h, 8 * c.latent_w, c.adapter_hint_channels), torch.uint8)
         self.out = [self.io_tensor(True, k, shape, torch.float16) for k, shape in enumerate(adapter_feature_shapes(c, b))]
+        return self
+
+
+def upscaler_check_config(num_blocks, image_hw):
+    """the UPSCALER graph's own limits, as a ValueError before anything is created"""
+    if not isinstance(num_blocks, int) or isinstance(num_blocks, bool) or not 1 <= num_blocks <= 23:
+        raise ValueError(f'upscaler: num_blocks must be an integer in [1, 23], not {num_blocks!r}')
+    try:
+        h, w = (int(v) for v in image_hw)
+    except (TypeError, ValueError):
+        raise ValueError(f'upscaler: image_hw must be a (height, width) pair, not {image_hw!r}') from None
+    for v in (h, w):
+        if v < 8 or v > 1024 or v % 8:
+            raise ValueError(f'upscaler: image height and width must be multiples of 8 in [8, 1024], not {(h, w)}')
+    return h, w
+
+
+class Upscaler(Graph):
+    """ESRGAN's RRDBNet (64 features, growth 32, scale 4; the front ends' "ESRGAN_4x" and "R-ESRGAN 4x+"): uint8 image [B, H, W, 3] ->
+    fp16 NHWC [B, 4H, 4W, 3], the network's output, nominally in [0, 1], not clamped.  Parameters by basicsr's names."""
+
+    SCALE = 4
+
+    def __init__(self, num_blocks=23, image_hw=(512, 512), batch=1, device='cuda:0'):
+        h, w = upscaler_check_config(num_blocks, image_hw)
+        self.num_blocks, self.image_hw = num_blocks, (h, w)
+        super().__init__(UPSCALER, UpscalerConfig(num_blocks, h, w), batch, device)
+
+    def finalize(self):
+        super().finalize()
+        (h, w), b = self.image_hw, self.batch
+        self.img = self.io_tensor(False, 0, (b, h, w, 3), torch.uint8)
+        self.out = self.io_tensor(True, 0, (b, 4 * h, 4 * w, 3), torch.float16)
         return self
 
 

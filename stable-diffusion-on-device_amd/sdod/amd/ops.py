@@ -512,6 +512,47 @@ def image_conv_in(img_u8, w, bias):
     return out
 
 
+def image_conv_in_unit(img_u8, w, bias, out2=None):
+    """RRDBNet's conv_first in one launch (sdod_image_conv_in_unit_f16): image_conv_in on u / 255, zero padding in that space.
+    out2: optional fp16 [n, h, w, ld2] buffer (ld2 >= cout, a multiple of 8) whose first cout channels receive a second copy."""
+    lib = _lib.hip()
+    _req(img_u8, torch.uint8, 'img'); _req(w, torch.float16, 'w'); _req(bias, torch.float32, 'bias')
+    n, h, wd, c = img_u8.shape
+    assert c == 3 and w.shape[1] == 64
+    cout = w.shape[0]
+    out = torch.empty((n, h, wd, cout), dtype=torch.float16, device=img_u8.device)
+    ld2 = 0
+    if out2 is not None:
+        _req(out2, torch.float16, 'out2')
+        assert tuple(out2.shape[:3]) == (n, h, wd), out2.shape
+        ld2 = out2.shape[3]
+    check(lib.sdod_image_conv_in_unit_f16(_p(img_u8), _p(w), _p(bias), _p(out), _p(out2), ld2, n, h, wd, cout, _stream()))
+    return out
+
+
+def dense_conv_desc(inp, w, bias, out, *, n, h, wd, cin, cout, ld_in, ld_out, out_col=0, in_off=0, out_off=0, alpha=1.0, slope=0.0,
+                    res1=None, res1_off=0, ld_res1=0, c1=0.0, res2=None, res2_off=0, ld_res2=0, upsample=0):
+    """a sdod_dense_conv_desc over torch buffers: every operand is (tensor, element offset), so that a test can place an image inside
+    a guarded buffer, alias operands or misalign a pointer; nothing is checked here -- the library's checks are what callers rely on"""
+    def at(t, off):
+        return None if t is None else ctypes.c_void_p(t.data_ptr() + off * t.element_size())
+    return _lib.DenseConvDesc(at(inp, in_off), _p(w), _p(bias), at(out, out_off), at(res1, res1_off), at(res2, res2_off),
+                              ld_in, ld_out, ld_res1, ld_res2, out_col, cin, cout, n, h, wd, upsample, alpha, slope, c1)
+
+
+def dense_conv(inp, w, bias, out, **kw):
+    """the ESRGAN dense-block convolution (sdod_dense_conv3x3_f16) on raw buffers; see dense_conv_desc for the arguments"""
+    d = dense_conv_desc(inp, w, bias, out, **kw)
+    check(_lib.hip().sdod_dense_conv3x3_f16(ctypes.byref(d), _stream()))
+    return out
+
+
+def dense_conv_ok(inp, w, bias, out, **kw):
+    """1 when sdod_dense_conv3x3_f16 takes these arguments (host-only query)"""
+    d = dense_conv_desc(inp, w, bias, out, **kw)
+    return _lib.hip().sdod_dense_conv3x3_ok(ctypes.byref(d))
+
+
 def conv_in_cat(x, cond, w, bias):
     """the 9-channel inpainting UNet's input convolution in one launch (sdod_conv_in_cat_f16): x NCHW fp32 [n, c, h, w] and cond NCHW
     fp32 [n, c_cond, h, w] read as their channel concatenation, w fp16 [cout, 128] (k = tap * (c + c_cond) + channel, zero from

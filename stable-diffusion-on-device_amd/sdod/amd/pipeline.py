@@ -5,12 +5,15 @@ Mirrors the reference's Context (context.cpp:49-403) in structure: setup -> grap
 cached time embeddings; generate -> tokenise, text-encode, sampler loop over the batched (uncond, cond) UNet
 evaluation with CFG, decode, uint8.  Multi-GPU: one process per GPU, images sharded over ranks, the text conditioning
 computed on rank 0 and sent with ONE RCCL broadcast."""
+import os
+
 import numpy as np
 import torch
 
 from . import engine as E
 from . import ops
 from . import prompts as PR
+from . import upscale as UP
 from .host import DpmSolver
 from .samplers import K_SAMPLERS, K_SCHEDULES, PLMS_ORDERS, KSchedule, PlmsSchedule
 
@@ -30,12 +33,13 @@ class Txt2Img:
     hires = None        # the second pipeline of the hires pass (Txt2Img(..., hires_hw=)), or None
     adapter = None      # the T2I-Adapter graph (Txt2Img(..., adapter=True)), or None
     adapter_channels = 3
+    upscaler = None     # the ESRGAN x4 upscaler (Txt2Img(..., upscaler=True): sdod.amd.upscale.Upscaler), or None
     tiling = 0          # seamless tiling: the wrap bits the UNet and the VAE decoder were built with (bit 0 = x, bit 1 = y)
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
-                 adapter_channels=3, tiling=False):
+                 adapter_channels=3, tiling=False, upscaler=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -75,11 +79,17 @@ class Txt2Img:
         latent_hw, prompt_chunks, loras, model='sd21', weight_quant and cfg_split work as without it.  False: nothing is constructed
         or sized differently.  Not with with_vae_encoder, inpaint_unet (the encoder graphs are not wrapped: no img2img or inpainting
         under tiling), hires_hw (the latent resize clamps at the border) or adapter (the adapter graph is not wrapped), and no other
-        value: ValueError before any device work (tiling_check_build)."""
+        value: ValueError before any device work (tiling_check_build).
+        upscaler=True: ESRGAN x4 upscaling of the pipeline's images: self.upscaler, an
+        sdod.amd.upscale.Upscaler built from state_dicts['upscaler'] or models_dir/upscaler.sdodw at this pipeline's image size -- with
+        hires_hw at the hires image size -- for upscale(), generate_upscaled() and generate_upscaled_graphed().  Its memory:
+        upscaler.graph.stats().  Off, nothing is constructed or sized differently.  Not with tiling (the upscaler's border is not
+        circular) or an image side above 1024 px: ValueError before any device work (upscaler_check_build)."""
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         latent_h, latent_w = check_latent_hw(latent_hw)
         adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_unet, model)
         self.tiling = tiling_check_build(tiling, with_vae_encoder, inpaint_unet, hires_hw, adapter)
+        up_args = upscaler_check_build(upscaler, tiling, hires_hw if hires_hw is not None else latent_hw, state_dicts, models_dir)
         if hires_hw is not None:
             check_latent_hw(hires_hw, 'hires_hw')
             if cfg_split or inpaint_unet:
@@ -152,6 +162,8 @@ class Txt2Img:
             if loras and (g is self.unet or g is self.text):
                 g.keep_base()
             g.finalize()
+        if up_args is not None:
+            self.upscaler = UP.Upscaler(device=device, use_hip_graph=use_hip_graph, **up_args)
         self._loras = bool(loras)
         self._temb_cache = {}
         self._ctx_fresh = True
@@ -603,6 +615,50 @@ class Txt2Img:
             inputs['step_noise'] = _step_noise(step_noise, (int(steps) - 1,) + tuple(x_T.shape), seed, 0, image_index)
         return self._replay(key, lambda **s: self.generate(**s, **kw), inputs)
 
+    # ------------------------------------------------------------------ ESRGAN x4 upscaling of the pipeline's images
+    def upscale(self, img_u8):
+        """uint8 [n, 8H, 8W, 3] (this pipeline's images; with hires_hw the hires pipeline's) -> uint8 [n, 32H, 32W, 3] through
+        self.upscaler (Txt2Img(upscaler=True)).  Argument errors raise ValueError before any device work."""
+        upscale_check_args(self, img_u8)
+        return self.upscaler.upscale(img_u8.to(self.device))
+
+    def generate_upscaled(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms', *, schedule='discrete', eta=1.0, seed=0, image_index=0,
+                          step_noise=None):
+        """upscale(generate(...)) -- with hires_hw: upscale(generate_hires(...)) with the hires pass's defaults.  generate()'s arguments."""
+        upscale_check_args(self, None)
+        kw = dict(steps=steps, guidance=guidance, sampler=sampler, schedule=schedule, eta=eta, seed=seed, image_index=image_index,
+                  step_noise=step_noise)
+        k_check_args(sampler, steps, schedule, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
+        img = self.generate(ctx2, x_T, **kw) if self.hires is None else self.generate_hires(ctx2, x_T, **kw)
+        return self.upscaler.upscale(img)
+
+    def generate_upscaled_graphed(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms', *, schedule='discrete', eta=1.0, seed=0,
+                                  image_index=0, step_noise=None):
+        """generate_upscaled() with the trajectory, the decode and the upscale replayed as ONE device graph (captured once per
+        generate_graphed key from the eager path, so it is the same kernels on the same buffers: the result equals
+        generate_upscaled() with the same arguments).  generate_graphed()'s arguments; not with hires_hw (generate_hires_graphed has
+        its own noise inputs) or cfg_split: ValueError."""
+        upscale_check_args(self, None)
+        if self.hires is not None or getattr(self, 'cfg_split', False):
+            raise ValueError('generate_upscaled_graphed cannot be combined with hires_hw or cfg_split: use generate_upscaled')
+        k_check_args(sampler, steps, schedule, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
+        self._require_cond()
+        kw = dict(steps=steps, guidance=guidance, sampler=sampler, schedule=schedule, eta=eta)
+        key = ('upscaled', sampler, int(steps), float(guidance), tuple(x_T.shape), schedule, float(eta))
+        inputs = dict(ctx2=_copied(ctx2), x_T=_copied(x_T, torch.float32))
+        if sampler == 'euler_a':
+            inputs['step_noise'] = _step_noise(step_noise, (int(steps) - 1,) + tuple(x_T.shape), seed, 0, image_index)
+        up = self.upscaler
+        keep = up.use_hip_graph
+
+        def run(**s):
+            up.use_hip_graph = False       # inside the capture the upscaler runs its launch list, like the other engine graphs
+            try:
+                return self.generate_upscaled(**s, **kw)
+            finally:
+                up.use_hip_graph = keep
+        return self._replay(key, run, inputs)
+
     # ------------------------------------------------------------------ img2img (ldm scripts/img2img.py, DDIM eta = 0)
     def encode(self, init_u8, seed=0, image_index=0, strength=0.75, steps=50, noise=None, return_z0=False, coef=None):
         """uint8 [n, 8H, 8W, 3] -> x fp32 [n, 4, H, W]: the VAE encoder, a posterior sample scaled by 0.18215, and ldm's
@@ -984,6 +1040,38 @@ def adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_
     for name, on in (('cfg_split', cfg_split), ('hires_hw', hires_hw is not None), ('inpaint_unet', inpaint_unet), ("model='sd21'", model == 'sd21')):
         if on:
             raise ValueError(f'adapter=True cannot be combined with {name}')
+
+
+def upscaler_check_build(upscaler, tiling, latent_hw, state_dicts, models_dir):
+    """Txt2Img's upscaler=True: not with tiling; the image (8 x the latent, the hires one with hires_hw) at most 1024 px a side; the
+    parameters in state_dicts['upscaler'] or models_dir/upscaler.sdodw.  Returns the keyword arguments of sdod.amd.upscale.Upscaler, or
+    None when off; raises ValueError."""
+    if not upscaler:
+        return None
+    if E.tiling_wrap(tiling):
+        raise ValueError("upscaler=True cannot be combined with tiling: the upscaler's border is not circular")
+    h, w = check_latent_hw(latent_hw)
+    if state_dicts is not None:
+        if 'upscaler' not in state_dicts:
+            raise ValueError("upscaler=True needs state_dicts['upscaler']")
+        src = dict(state_dict=state_dicts['upscaler'])
+    elif models_dir is not None:
+        src = dict(path=os.path.join(models_dir, 'upscaler.sdodw'))
+        if not os.path.exists(src['path']):
+            raise ValueError(f"upscaler=True needs {src['path']} (python -m sdod.amd.convert --upscaler FILE --out DIR)")
+    else:
+        raise ValueError('upscaler=True needs state_dicts or models_dir')
+    UP.upscaler_check_build(src.get('state_dict'), src.get('path'), (8 * h, 8 * w), None)
+    return dict(src, image_hw=(8 * h, 8 * w))
+
+
+def upscale_check_args(pipe, img_u8):
+    """Txt2Img.upscale / generate_upscaled*: a pipeline built with upscaler=True and (when given) a uint8 image [n, H, W, 3] of the size
+    the upscaler was built for; raises ValueError"""
+    if pipe.upscaler is None:
+        raise ValueError('this pipeline was built without upscaler=True')
+    if img_u8 is not None:
+        UP.upscale_check_args(img_u8, pipe.upscaler.image_hw)
 
 
 def tiling_check_build(tiling, with_vae_encoder, inpaint_unet, hires_hw, adapter):

@@ -77,6 +77,20 @@ def save(path, tensors):
             f.write(t.payload() if isinstance(t, QuantU8) else t.numpy().tobytes())
 
 
+def names(path):
+    """the tensor names of a container, from its header alone (no payload is read)"""
+    with open(path, 'rb') as f:
+        head = f.read(16)
+        assert head[:8] == MAGIC, 'bad magic'
+        out = []
+        for _ in range(struct.unpack_from('<Q', head, 8)[0]):
+            nl = struct.unpack('<I', f.read(4))[0]
+            out.append(f.read(nl).decode())
+            nd = struct.unpack('<II', f.read(8))[1]
+            f.read(8 * nd + 16)
+    return out
+
+
 def load(path):
     """Inverse of save(); returns {name: tensor or QuantU8}."""
     out = {}
