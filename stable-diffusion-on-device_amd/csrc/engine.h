@@ -19,6 +19,11 @@ namespace sdod {
 
 typedef _Float16 f16;
 
+// a kernel entry point's return code as an exception carrying the library's message
+inline void check_rc(int rc) {
+    if (rc != 0) throw Error(rc, get_last_error());
+}
+
 enum ParamKind {
     PK_CONV3,       // [Cout][Cin][3][3] -> fp16 [Cout][(r*3+s)*Cin + c]
     PK_CONV3_SMALL, // tiny Cin: same order, K zero-padded to small_k(Cin) = 64 (9 Cin <= 64) or 128 (9 Cin <= 96)
@@ -274,8 +279,11 @@ private:
         drain_parked();
     }
     Act spatial_transformer(const std::string& pfx, const Act& x, const Act& ctx);
+    Act unet_conv_in(const float* x_in, const float* cond_in); // input_blocks.0.0 in its three forms
     Act vae_res_block(const std::string& pfx, const Act& x, int cout);
     Act vae_attn_block(const std::string& pfx, const Act& x);
+    void vae_res_step(const std::string& pfx, Act& h, int cout); // h = vae_res_block(h); the old h, the block's residual, is parked
+    void vae_mid(const std::string& pfx, Act& h, int ch);        // mid.block_1 -> mid.attn_1 -> mid.block_2, in place on h
     int emb_total_ = 0; // sum of ResBlock output channels (set by the DECLARE pass)
     int kv_total_ = 0;  // sum over SpatialTransformers of 2*C: width of the batched cross-attention K/V matrix
     f16* kv_all_ = nullptr; // [B*context_len][kv_total_], persistent (not arena memory)
@@ -283,9 +291,13 @@ private:
     std::vector<std::pair<std::string, int>> unet_res_blocks() const; // (prefix, cout) in declaration order
     const char* group_base(const std::string& group) const;
     int group_first(const std::string& group) const; // index of the first parameter of a fused group
-    void emit(std::function<void(hipStream_t)> fn, const char* label = "elementwise", double flops = 0, double bytes = 0) {
+    // records one launch: flushes what is pending or parked, then in REAL mode accounts `flops` and appends to the current list.
+    // Every launch goes through here except the GEMM's and GroupNorm's, which produce / consume pending_ themselves.
+    void emit(std::function<void(hipStream_t)> fn, std::string label = "elementwise", double flops = 0, double bytes = 0, std::string detail = "") {
         settle();
-        if (mode_ == REAL) sink().push_back(Op{std::move(fn), label, flops, bytes, ""});
+        if (mode_ != REAL) return;
+        flops_ += flops;
+        sink().push_back(Op{std::move(fn), std::move(label), flops, bytes, std::move(detail)});
     }
 
 public:

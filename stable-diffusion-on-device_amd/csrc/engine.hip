@@ -20,10 +20,6 @@ namespace sdod {
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static void check_rc(int rc) {
-    if (rc != 0) throw Error(rc, get_last_error());
-}
-
 template <typename F>
 static void parallel_for(int64_t n, F&& fn) {
     int nt = (int)std::min<int64_t>(n, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
@@ -957,28 +953,21 @@ Act Graph::group_norm(const Act& x, const Act* x2, int gw, int gb, float eps, bo
 
 Act Graph::layer_norm(const Act& x, int lw, int lb, float eps) {
     Act y = act(x.n, x.h, x.w, x.c);
-    settle();
-    if (mode_ != REAL) return y;
     const void* xp = x.p; void* yp = y.p;
     const float* wp = W<float>(lw); const float* bp = W<float>(lb);
     const int m = x.rows(), c = x.c;
-    ops_.push_back(Op{[=](hipStream_t st) { check_rc(sdod_layer_norm_f16(xp, yp, wp, bp, m, c, eps, st)); }, "layer_norm", 0,
-                      2.0 * m * c * 2, "m" + std::to_string(m) + " c" + std::to_string(c)});
+    emit([=](hipStream_t st) { check_rc(sdod_layer_norm_f16(xp, yp, wp, bp, m, c, eps, st)); }, "layer_norm", 0, 2.0 * m * c * 2,
+         "m" + std::to_string(m) + " c" + std::to_string(c));
     return y;
 }
 
 void Graph::attention(const f16* q, const f16* k, const f16* v, f16* out, int B, int heads, int lq, int lk, int d, int ldq,
                       int ldk, int ldv, int ldo, bool causal) {
-    settle();
-    if (mode_ != REAL) return;
-    const double fl = 4.0 * B * heads * (double)lq * lk * d;
-    flops_ += fl;
     const float scale = 1.0f / sqrtf((float)d);
     const int ca = causal ? 1 : 0;
-    ops_.push_back(Op{[=](hipStream_t st) {
-        check_rc(sdod_attention_f16(q, k, v, out, B, heads, lq, lk, d, ldq, ldk, ldv, ldo, scale, ca, st));
-    }, "attn_d" + std::to_string(d), fl, 2.0 * B * heads * d * (2.0 * lq + 2.0 * lk),
-                      "B" + std::to_string(B) + " h" + std::to_string(heads) + " lq" + std::to_string(lq) + " lk" + std::to_string(lk)});
+    emit([=](hipStream_t st) { check_rc(sdod_attention_f16(q, k, v, out, B, heads, lq, lk, d, ldq, ldk, ldv, ldo, scale, ca, st)); },
+         "attn_d" + std::to_string(d), 4.0 * B * heads * (double)lq * lk * d, 2.0 * B * heads * d * (2.0 * lq + 2.0 * lk),
+         "B" + std::to_string(B) + " h" + std::to_string(heads) + " lq" + std::to_string(lq) + " lk" + std::to_string(lk));
 }
 
 // ------------------------------------------------------------------------------------------ finalize / run

@@ -1,5 +1,6 @@
-// graphs.hip -- launch-list builders for the four graphs of the txt2img path: UNet eps-model, VAE decoder,
-// CLIP text encoder, time-embedding MLP -- and the VAE encoder of the img2img path.  They stand in for the serialized QNN graphs the reference loads
+// graphs.hip -- launch-list builders, one per graph kind (include/sdod_engine.h): UNet eps-model (with the inpainting, T2I-Adapter
+// and seamless-tiling variants of its inputs), time-embedding MLP, CLIP text encoder, VAE decoder, VAE encoder and its masked form
+// (img2img, inpainting), T2I-Adapter, ESRGAN upscaler.  The first four stand in for the serialized QNN graphs the reference loads
 // (context.cpp:105: "unet.serialized", "text_encoder.serialized", "vae_decoder.serialized", "temb"); the
 // block structure follows the op names visible in the reference's own profiler table
 // (analyze_results.py:20-93: in_layers / emb_layers / out_layers / skip_connection, norm / proj_in /
@@ -17,9 +18,8 @@
 
 namespace sdod {
 
-static void check_rc2(int rc) {
-    if (rc != 0) throw Error(rc, get_last_error());
-}
+// channel multiplier per resolution level: UNet and T2I-Adapter on model_channels, both VAE halves on vae_channels
+static const int kChMult[4] = {1, 2, 4, 4};
 
 int Graph::group_first(const std::string& group) const {
     auto it = gindex_.find(group);
@@ -146,32 +146,38 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
     const int pob = P(pfx + ".proj_out.bias", {C}, PK_VEC);
     if (mode_ == DECLARE) return act(x.n, x.h, x.w, C);
 
+    // ---- 1. proj_in
     Act g = group_norm(x, nullptr, nw, nb, 1e-6f, false);
     Act t0 = act(B, 1, L, C);
     { GemmOpt o; o.bias = pib; linear(g.p, rows, C, piw, C, t0.p, o); }
     release(g);
-    // self-attention
     // the three LayerNorms of the block are folded into the Linear that consumes them (no LN launch, no LN tensor) -- except
-    // with uint8 weights, whose integer codes cannot absorb gamma: there LayerNorm is a launch and the Linear a plain one
+    // with uint8 weights, whose integer codes cannot absorb gamma: there LayerNorm is a launch and the Linear a plain one.
+    // gemm(a, o) emits that Linear on the rows at `a`; its output is allocated by the caller, BEFORE the normalised tensor.
     const bool fold = !quant_block;
-    auto normed = [&](const Act& src, int lw, int lb) -> Act { return layer_norm(src, lw, lb, 1e-5f); };
+    auto behind_ln = [&](const Act& src, int lw, int lb, GemmOpt o, auto gemm) {
+        if (fold) {
+            o.ln_w = lw; o.ln_b = lb;
+            gemm(src.p, o);
+        } else { // (uint8 weights are never composed: src is a dense [rows][C] tensor)
+            Act nrm = layer_norm(src, lw, lb, 1e-5f);
+            gemm(nrm.p, o);
+            release(nrm);
+        }
+    };
+    // ---- 2. self-attention
     f16* qkv = alloc((size_t)rows * 3 * C);
-    if (fold) {
-        GemmOpt o; o.ln_w = l1w; o.ln_b = l1b;
-        linear_raw(t0.p, rows, C, reinterpret_cast<const f16*>(group_base(gq)), C, 3 * C, qkv, o);
-    } else {
-        Act nrm = normed(t0, l1w, l1b);
-        GemmOpt o; o.wq_scale = qscale_of(group_first(gq)); o.wq_off = qoff_of(group_first(gq));
-        linear_raw(nrm.p, rows, C, reinterpret_cast<const f16*>(group_base(gq)), C, 3 * C, qkv, o);
-        release(nrm);
-    }
+    { GemmOpt o; o.wq_scale = qscale_of(group_first(gq)); o.wq_off = qoff_of(group_first(gq)); // (null unless the block keeps uint8 codes)
+      behind_ln(t0, l1w, l1b, o, [&](const f16* a, const GemmOpt& og) {
+          linear_raw(a, rows, C, reinterpret_cast<const f16*>(group_base(gq)), C, 3 * C, qkv, og); }); }
     f16* a1 = alloc((size_t)rows * C);
     attention(qkv, qkv + C, qkv + 2 * C, a1, B, heads, L, L, d, 3 * C, 3 * C, 3 * C, C, false);
     release(qkv);
     Act t1 = act(B, 1, L, C);
     { GemmOpt o; o.bias = o1b; o.residual = t0.p; linear(a1, rows, C, o1w, C, t1.p, o); }
     release(a1); release(t0);
-    // cross-attention on the text context.  FOLDED form (attention.hip: sdod_xattn_fold_f16): the context, and with it K and V,
+    // ---- 3. cross-attention on the text context, in two forms
+    // FOLDED form (attention.hip: sdod_xattn_fold_f16): the context, and with it K and V,
     // is constant over the sampler run, so to_q is multiplied into K and to_out into V once per prompt (static launch list) and
     // the block is two GEMMs per evaluation -- scores = LN(t1) . (Wq^T K_h^T) with the row softmax over each head's 77 (+3
     // padding) columns in the epilogue, then [P_1 | .. | P_H] . (V_h Wo_h^T) + bias + residual -- instead of Linear + attention
@@ -181,6 +187,9 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
     static const bool xfold_on = [] { const char* e = std::getenv("SDOD_XATTN_FOLD"); return !(e && e[0] == '0'); }();
     const int NK = heads * 80;
     const bool xfold = xfold_on && fold && ctx.w <= 80 && NK % 320 == 0 && L % 32 == 0 && d <= 160 && d % 4 == 0;
+    // either form leaves its last GEMM to be emitted once its destination is known: t2 = a[rows][K] . w^T + o2b + t1
+    struct { f16* a; int K; const f16* w; GemmOpt o; } xo;
+    xo.o.bias = o2b; xo.o.residual = t1.p;
     if (xfold) {
         f16 *w1 = nullptr, *w2 = nullptr;
         float *s1 = nullptr, *t1v = nullptr;
@@ -196,9 +205,9 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
             const f16* kvp = kv_all_;
             const int ldkv = kv_total_, koff = my_kv, Lk = ctx.w, hh = heads, dd = d;
             const float scale = 1.0f / sqrtf((float)d);
-            to_static_ = true;
+            to_static_ = true; // (not emit(): its settle() would put a still pending split-K reduce into the static list)
             sink().push_back(Op{[=](hipStream_t st) {
-                check_rc2(sdod_xattn_fold_f16(kvp, ldkv, koff, koff + C, B, Lk, wq, C, qv.s, qv.t, wo, C, hh, dd, scale, w1, s1, t1v, w2, st));
+                check_rc(sdod_xattn_fold_f16(kvp, ldkv, koff, koff + C, B, Lk, wq, C, qv.s, qv.t, wo, C, hh, dd, scale, w1, s1, t1v, w2, st));
             }, "xattn_fold", 4.0 * B * NK * (double)C * d, 4.0 * B * NK * C * 2, "C" + std::to_string(C) + " d" + std::to_string(d)});
             to_static_ = false;
         }
@@ -208,62 +217,35 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
         { GemmOpt o; o.ln_s_raw = mode_ == REAL ? s1 : reinterpret_cast<const float*>(wq); o.bias_raw = mode_ == REAL ? t1v : reinterpret_cast<const float*>(wq);
           o.w_img_stride = NK * C; o.vec_img_stride = NK; o.softmax_cols = 80; o.rows_per_img = L;
           linear_raw(t1.p, rows, C, w1p, C, NK, pb, o); }
-        GemmOpt o2;
-        o2.bias = o2b; o2.residual = t1.p; o2.w_img_stride = C * NK; o2.rows_per_img = L;
-        if (compose) {
-            f16* cat = alloc((size_t)rows * 5 * C);
-            f16* t2c = cat + 4 * C;
-            o2.ldr = C; o2.ldo = 5 * C;
-            linear_raw(pb, rows, NK, w2p, NK, C, t2c, o2);
-            release(pb); release(t1);
-            { GemmOpt o; o.bias = f1b; o.geglu = true; o.ln_w = l3w; o.ln_b = l3b; o.lda = 5 * C; o.ldo = 5 * C; linear(t2c, rows, C, f1w, 8 * C, cat, o); }
-            float* bc = nullptr;
-            if (mode_ == REAL) {
-                SDOD_HIP_CHECK(hipMalloc((void**)&bc, (size_t)C * sizeof(float)));
-                derived_.push_back(bc);
-                f16* wc = reinterpret_cast<f16*>(params_[f2w].dev);
-                compose_jobs_.push_back(ComposeJob{wc, wc + 4 * C, 5 * C, C, C, 4 * C, W<float>(f2b), W<float>(pob), bc});
-            }
-            Act out = act(x.n, x.h, x.w, C);
-            { GemmOpt o; o.bias_raw = mode_ == REAL ? bc : reinterpret_cast<const float*>(params_[f2w].dev); o.residual = x.p;
-              linear_raw(cat, rows, 5 * C, reinterpret_cast<const f16*>(params_[f2w].dev), 5 * C, C, out.p, o); }
-            release(cat);
-            return out;
-        }
-        Act t2 = act(B, 1, L, C);
-        linear_raw(pb, rows, NK, w2p, NK, C, t2.p, o2);
-        release(pb); release(t1);
-        f16* gg = alloc((size_t)rows * 4 * C);
-        { GemmOpt o; o.bias = f1b; o.geglu = true; o.ln_w = l3w; o.ln_b = l3b; linear(t2.p, rows, C, f1w, 8 * C, gg, o); }
-        Act t3 = act(B, 1, L, C);
-        { GemmOpt o; o.bias = f2b; o.residual = t2.p; linear(gg, rows, 4 * C, f2w, C, t3.p, o); }
-        release(gg); release(t2);
-        Act out = act(x.n, x.h, x.w, C);
-        { GemmOpt o; o.bias = pob; o.residual = x.p; linear(t3.p, rows, C, pow_, C, out.p, o); }
-        release(t3);
-        return out;
-    }
-    f16* q2 = alloc((size_t)rows * C);
-    if (fold) {
-        GemmOpt o; o.ln_w = l2w; o.ln_b = l2b; linear(t1.p, rows, C, q2w, C, q2, o);
+        xo.a = pb; xo.K = NK; xo.w = w2p;
+        xo.o.w_img_stride = C * NK; xo.o.rows_per_img = L;
     } else {
-        Act nrm = normed(t1, l2w, l2b);
-        linear(nrm.p, rows, C, q2w, C, q2, GemmOpt{});
-        release(nrm);
+        f16* q2 = alloc((size_t)rows * C);
+        behind_ln(t1, l2w, l2b, GemmOpt{}, [&](const f16* a, const GemmOpt& og) { linear(a, rows, C, q2w, C, q2, og); });
+        const int Lk = ctx.w;
+        const f16* kv = kv_all_ + my_kv;
+        f16* a2 = alloc((size_t)rows * C);
+        attention(q2, kv, kv + C, a2, B, heads, L, Lk, d, C, kv_total_, kv_total_, C, false);
+        release(q2);
+        xo.a = a2; xo.K = C; xo.w = W<f16>(o2w);
+        xo.o.wq_scale = qscale_of(o2w); xo.o.wq_off = qoff_of(o2w);
     }
-    const int Lk = ctx.w;
-    const f16* kv = kv_all_ + my_kv;
-    f16* a2 = alloc((size_t)rows * C);
-    attention(q2, kv, kv + C, a2, B, heads, L, Lk, d, C, kv_total_, kv_total_, C, false);
-    release(q2);
+    // t2's place.  Composed: [g | t2] rows of 5C -- attn2.to_out writes its C columns (row stride 5C), the GEGLU projection reads
+    // them (LayerNorm folded) and writes the first 4C, the composed Linear reads all 5C.  Otherwise a tensor of its own.
+    f16* cat = compose ? alloc((size_t)rows * 5 * C) : nullptr;
+    const int ld2 = compose ? 5 * C : 0; // (0 = dense)
+    Act t2;
+    if (compose) { t2.p = cat + 4 * C; t2.n = B; t2.h = 1; t2.w = L; t2.c = C; }
+    else t2 = act(B, 1, L, C);
+    xo.o.ldr = compose ? C : 0; xo.o.ldo = ld2;
+    linear_raw(xo.a, rows, xo.K, xo.w, xo.K, C, t2.p, xo.o);
+    release(xo.a); release(t1);
+    // ---- 4. GEGLU feed-forward, fused into the ff.net.0.proj epilogue: the [rows][8C] tensor never exists
+    f16* gg = compose ? cat : alloc((size_t)rows * 4 * C);
+    { GemmOpt o; o.bias = f1b; o.geglu = true; o.lda = ld2; o.ldo = ld2;
+      behind_ln(t2, l3w, l3b, o, [&](const f16* a, const GemmOpt& og) { linear(a, rows, C, f1w, 8 * C, gg, og); }); }
+    Act out;
     if (compose) {
-        // [g | t2] rows of 5C: attn2.to_out writes its C columns (row stride 5C), the GEGLU projection reads them (LayerNorm
-        // folded) and writes the first 4C, the composed Linear reads all 5C
-        f16* cat = alloc((size_t)rows * 5 * C);
-        f16* t2c = cat + 4 * C;
-        { GemmOpt o; o.bias = o2b; o.residual = t1.p; o.ldr = C; o.ldo = 5 * C; linear(a2, rows, C, o2w, C, t2c, o); }
-        release(a2); release(t1);
-        { GemmOpt o; o.bias = f1b; o.geglu = true; o.ln_w = l3w; o.ln_b = l3b; o.lda = 5 * C; o.ldo = 5 * C; linear(t2c, rows, C, f1w, 8 * C, cat, o); }
         float* bc = nullptr;
         if (mode_ == REAL) {
             SDOD_HIP_CHECK(hipMalloc((void**)&bc, (size_t)C * sizeof(float)));
@@ -271,31 +253,54 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
             f16* wc = reinterpret_cast<f16*>(params_[f2w].dev);
             compose_jobs_.push_back(ComposeJob{wc, wc + 4 * C, 5 * C, C, C, 4 * C, W<float>(f2b), W<float>(pob), bc});
         }
-        Act out = act(x.n, x.h, x.w, C);
+        out = act(x.n, x.h, x.w, C);
         { GemmOpt o; o.bias_raw = mode_ == REAL ? bc : reinterpret_cast<const float*>(params_[f2w].dev); o.residual = x.p;
-          linear_raw(cat, rows, 5 * C, reinterpret_cast<const f16*>(params_[f2w].dev), 5 * C, C, out.p, o); }
+          linear_raw(cat, rows, 5 * C, W<f16>(f2w), 5 * C, C, out.p, o); }
         release(cat);
-        return out;
-    }
-    Act t2 = act(B, 1, L, C);
-    { GemmOpt o; o.bias = o2b; o.residual = t1.p; linear(a2, rows, C, o2w, C, t2.p, o); }
-    release(a2); release(t1);
-    // GEGLU feed-forward
-    f16* gg = alloc((size_t)rows * 4 * C); // GEGLU fused into the ff.net.0.proj epilogue: the [rows][8C] tensor never exists
-    if (fold) {
-        GemmOpt o; o.bias = f1b; o.geglu = true; o.ln_w = l3w; o.ln_b = l3b; linear(t2.p, rows, C, f1w, 8 * C, gg, o);
     } else {
-        Act nrm = normed(t2, l3w, l3b);
-        GemmOpt o; o.bias = f1b; o.geglu = true; linear(nrm.p, rows, C, f1w, 8 * C, gg, o);
-        release(nrm);
+        Act t3 = act(B, 1, L, C);
+        { GemmOpt o; o.bias = f2b; o.residual = t2.p; linear(gg, rows, 4 * C, f2w, C, t3.p, o); }
+        release(gg); release(t2);
+        out = act(x.n, x.h, x.w, C);
+        { GemmOpt o; o.bias = pob; o.residual = x.p; linear(t3.p, rows, C, pow_, C, out.p, o); }
+        release(t3);
     }
-    Act t3 = act(B, 1, L, C);
-    { GemmOpt o; o.bias = f2b; o.residual = t2.p; linear(gg, rows, 4 * C, f2w, C, t3.p, o); }
-    release(gg); release(t2);
-    Act out = act(x.n, x.h, x.w, C);
-    { GemmOpt o; o.bias = pob; o.residual = x.p; linear(t3.p, rows, C, pow_, C, out.p, o); }
-    release(t3);
     return out;
+}
+
+// input_blocks.0.0, the 3x3 convolution on the fp32 NCHW latent (build_unet() has checked the sizes)
+Act Graph::unet_conv_in(const float* x_in, const float* cond_in) {
+    const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, LC = cfg_.latent_channels, MC = cfg_.model_channels;
+    const int CC = cfg_.concat_channels, CI = LC + CC, wr = wrap_;
+    const int ciw = P("input_blocks.0.0.weight", {MC, CI, 3, 3}, PK_CONV3_SMALL), cib = P("input_blocks.0.0.bias", {MC}, PK_VEC);
+    Act h = act(B, H, Wd, MC);
+    const f16* wp = W<f16>(ciw);
+    const float* bp = W<float>(cib);
+    f16* hp = h.p;
+    const std::string shape = "M" + std::to_string(B * H * Wd) + " N" + std::to_string(MC);
+    if (CC > 0) {
+        // Cin = 9 from two sources (x | cond), K = 81 -> 96 of the 128-wide packed rows, ONE launch (elementwise.hip: CatSrc)
+        emit([=](hipStream_t st) { check_rc(sdod_conv_in_cat_f16(x_in, cond_in, wp, bp, hp, B, H, Wd, LC, CC, MC, st)); }, "conv_in_cat",
+             2.0 * B * H * Wd * MC * 96, (double)B * H * Wd * (CI * 4 + MC * 2) + MC * 96 * 2, shape + " K96");
+    } else if (MC == 320 || MC == 256 || MC == 128 || MC == 64) {
+        // ONE launch: im2col rows built in LDS, the whole [MC][64] weight matrix next to them (elementwise.hip: conv_in_kernel)
+        emit([=](hipStream_t st) { check_rc(sdod_conv_in_wrap_f16(x_in, wp, bp, hp, B, H, Wd, LC, MC, 1.0f, wr, st)); }, "conv_in",
+             2.0 * B * H * Wd * MC * 64, (double)B * H * Wd * (LC * 4 + MC * 2) + MC * 64 * 2, shape + " K64");
+    } else {
+        // Cin = 4, any width: im2col to K = 64, then the GEMM
+        f16* cols = alloc((size_t)B * H * Wd * 64);
+        if (wr != 0) { // the wrapped im2col reads NHWC fp16: sdod_latent_im2col_f16 as the two launches it fuses
+            Act xl = act(B, H, Wd, LC);
+            emit([=](hipStream_t st) { check_rc(sdod_latent_prep_f16(x_in, nullptr, nullptr, xl.p, B, LC, H * Wd, 1.0f, st)); });
+            emit([=](hipStream_t st) { check_rc(sdod_im2col3x3_small_wrap_f16(xl.p, cols, B, H, Wd, LC, 64, wr, st)); });
+            release(xl);
+        } else {
+            emit([=](hipStream_t st) { check_rc(sdod_latent_im2col_f16(x_in, cols, B, H, Wd, LC, 64, 1.0f, st)); });
+        }
+        { GemmOpt o; o.bias = cib; linear(cols, B * H * Wd, 64, ciw, MC, h.p, o); }
+        release(cols);
+    }
+    return h;
 }
 
 void Graph::build_unet() {
@@ -309,7 +314,6 @@ void Graph::build_unet() {
     SDOD_REQUIRE(CC == 0 || CI * 9 > 64, "concat_channels > 0 needs 9 (latent_channels + concat_channels) > 64 (the K = 96 input convolution)");
     SDOD_REQUIRE(CC == 0 || MC == 320 || MC == 256 || MC == 128 || MC == 64,
                  "concat_channels > 0 needs model_channels 64, 128, 256 or 320 (the one-launch input convolution)");
-    const int mult[4] = {1, 2, 4, 4};
 
     if (mode_ != DECLARE) { // widths fixed by the DECLARE pass
         int tot = 0;
@@ -324,7 +328,7 @@ void Graph::build_unet() {
     const int AR = acfg_.adapter_reps;
     const f16* feat_in[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int l = 0; AR > 0 && l < 4; ++l)
-        feat_in[l] = (const f16*)io_alloc(inputs_, (size_t)(B / AR) * (H >> l) * (Wd >> l) * mult[l] * MC * sizeof(f16));
+        feat_in[l] = (const f16*)io_alloc(inputs_, (size_t)(B / AR) * (H >> l) * (Wd >> l) * kChMult[l] * MC * sizeof(f16));
     f16* e_out = (f16*)io_alloc(outputs_, (size_t)B * H * Wd * LC * sizeof(f16));
     Act ctx;
     ctx.p = ctx_in; ctx.n = B; ctx.h = 1; ctx.w = CL; ctx.c = cd;
@@ -344,56 +348,15 @@ void Graph::build_unet() {
         to_static_ = false;
     }
 
-    // input conv (Cin = 4): im2col to K = 64, then the GEMM
-    const int ciw = P("input_blocks.0.0.weight", {MC, CI, 3, 3}, PK_CONV3_SMALL), cib = P("input_blocks.0.0.bias", {MC}, PK_VEC);
-    Act h = act(B, H, Wd, MC);
-    if (CC > 0) {
-        // Cin = 9 from two sources (x | cond), K = 81 -> 96 of the 128-wide packed rows, ONE launch (elementwise.hip: CatSrc)
-        const f16* wp = mode_ != DECLARE ? W<f16>(ciw) : nullptr;
-        const float* bp = mode_ != DECLARE ? W<float>(cib) : nullptr;
-        f16* hp = h.p;
-        settle();
-        if (mode_ == REAL) {
-            flops_ += 2.0 * B * H * Wd * MC * 96;
-            ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_conv_in_cat_f16(x_in, cond_in, wp, bp, hp, B, H, Wd, LC, CC, MC, st)); },
-                              "conv_in_cat", 2.0 * B * H * Wd * MC * 96, (double)B * H * Wd * (CI * 4 + MC * 2) + MC * 96 * 2,
-                              "M" + std::to_string(B * H * Wd) + " N" + std::to_string(MC) + " K96"});
-        }
-    } else if (MC == 320 || MC == 256 || MC == 128 || MC == 64) {
-        // ONE launch: im2col rows built in LDS, the whole [MC][64] weight matrix next to them (elementwise.hip: conv_in_kernel)
-        const f16* wp = mode_ != DECLARE ? W<f16>(ciw) : nullptr;
-        const float* bp = mode_ != DECLARE ? W<float>(cib) : nullptr;
-        f16* hp = h.p;
-        settle();
-        if (mode_ == REAL) {
-            flops_ += 2.0 * B * H * Wd * MC * 64;
-            const int wr = wrap_;
-            ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_conv_in_wrap_f16(x_in, wp, bp, hp, B, H, Wd, LC, MC, 1.0f, wr, st)); }, "conv_in",
-                              2.0 * B * H * Wd * MC * 64, (double)B * H * Wd * (LC * 4 + MC * 2) + MC * 64 * 2,
-                              "M" + std::to_string(B * H * Wd) + " N" + std::to_string(MC) + " K64"});
-        }
-    } else {
-        f16* cols = alloc((size_t)B * H * Wd * 64);
-        if (wrap_ != 0) { // the wrapped im2col reads NHWC fp16: sdod_latent_im2col_f16 as the two launches it fuses
-            Act xl = act(B, H, Wd, LC);
-            const int wr = wrap_;
-            emit([=](hipStream_t st) { check_rc2(sdod_latent_prep_f16(x_in, nullptr, nullptr, xl.p, B, LC, H * Wd, 1.0f, st)); });
-            emit([=](hipStream_t st) { check_rc2(sdod_im2col3x3_small_wrap_f16(xl.p, cols, B, H, Wd, LC, 64, wr, st)); });
-            release(xl);
-        } else
-        emit([=](hipStream_t st) { check_rc2(sdod_latent_im2col_f16(x_in, cols, B, H, Wd, LC, 64, 1.0f, st)); });
-        { GemmOpt o; o.bias = cib; linear(cols, B * H * Wd, 64, ciw, MC, h.p, o); }
-        release(cols);
-    }
-
+    Act h = unet_conv_in(x_in, cond_in);
     std::vector<Act> hs;
     hs.push_back(h);
     int ch = MC, ds = 1, idx = 1;
     for (int level = 0; level < 4; ++level) {
         for (int i = 0; i < 2; ++i) {
             const std::string pfx = "input_blocks." + std::to_string(idx++);
-            Act r = res_block(pfx + ".0", h, nullptr, mult[level] * MC, emb_all, emb_ld, emb_off);
-            ch = mult[level] * MC;
+            Act r = res_block(pfx + ".0", h, nullptr, kChMult[level] * MC, emb_all, emb_ld, emb_off);
+            ch = kChMult[level] * MC;
             if (ds <= 4) {
                 Act t = spatial_transformer(pfx + ".1", r, ctx);
                 release(r);
@@ -406,7 +369,7 @@ void Graph::build_unet() {
                 f16* hp = h.p;
                 const f16* fp = feat_in[level];
                 const size_t per = h.numel() / AR;
-                emit([=](hipStream_t st) { check_rc2(sdod_add_feature_f16(hp, fp, per, AR, st)); }, "add_feature", 0,
+                emit([=](hipStream_t st) { check_rc(sdod_add_feature_f16(hp, fp, per, AR, st)); }, "add_feature", 0,
                      (double)h.numel() * 4 + (double)per * 2);
             }
             hs.push_back(h);
@@ -436,9 +399,9 @@ void Graph::build_unet() {
             const std::string pfx = "output_blocks." + std::to_string(oidx++);
             Act skip = hs.back();
             hs.pop_back();
-            Act r = res_block(pfx + ".0", h, &skip, mult[level] * MC, emb_all, emb_ld, emb_off);
+            Act r = res_block(pfx + ".0", h, &skip, kChMult[level] * MC, emb_all, emb_ld, emb_off);
             release(h); release(skip);
-            ch = mult[level] * MC;
+            ch = kChMult[level] * MC;
             int sub = 1;
             if (ds <= 4) {
                 Act t = spatial_transformer(pfx + "." + std::to_string(sub++), r, ctx);
@@ -473,17 +436,16 @@ void Graph::build_unet() {
 std::vector<std::pair<std::string, int>> Graph::unet_res_blocks() const {
     std::vector<std::pair<std::string, int>> v;
     const int MC = cfg_.model_channels;
-    const int mult[4] = {1, 2, 4, 4};
     int idx = 1;
     for (int level = 0; level < 4; ++level) {
-        for (int i = 0; i < 2; ++i) v.emplace_back("input_blocks." + std::to_string(idx++) + ".0", mult[level] * MC);
+        for (int i = 0; i < 2; ++i) v.emplace_back("input_blocks." + std::to_string(idx++) + ".0", kChMult[level] * MC);
         if (level != 3) ++idx;
     }
     v.emplace_back("middle_block.0", 4 * MC);
     v.emplace_back("middle_block.2", 4 * MC);
     int oidx = 0;
     for (int level = 3; level >= 0; --level)
-        for (int i = 0; i < 3; ++i) v.emplace_back("output_blocks." + std::to_string(oidx++) + ".0", mult[level] * MC);
+        for (int i = 0; i < 3; ++i) v.emplace_back("output_blocks." + std::to_string(oidx++) + ".0", kChMult[level] * MC);
     return v;
 }
 
@@ -504,7 +466,7 @@ void Graph::build_temb() {
         P(rb.first + ".emb_layers.1.bias", {rb.second}, PK_VEC, "emb_b");
     }
     f16* feat = alloc((size_t)B * MC);
-    emit([=](hipStream_t st) { check_rc2(sdod_timestep_features_f16(t_in, feat, B, MC, st)); });
+    emit([=](hipStream_t st) { check_rc(sdod_timestep_features_f16(t_in, feat, B, MC, st)); });
     f16* hmid = alloc((size_t)B * EC);
     { GemmOpt o; o.bias = b0; o.act = SDOD_ACT_SILU; linear(feat, B, MC, w0, EC, hmid, o); }
     f16* emb = alloc((size_t)B * EC);
@@ -578,7 +540,7 @@ Act Graph::vae_attn_block(const std::string& pfx, const Act& x) {
         f16* sc = alloc((size_t)L * L);  // scores, softmaxed in place
         { GemmOpt o; o.alpha = 1.0f / sqrtf((float)C); o.lda = 2 * C;
           linear_raw(qk + (size_t)b * L * 2 * C, L, C, qk + (size_t)b * L * 2 * C + C, 2 * C, L, sc, o); }
-        emit([=](hipStream_t st) { check_rc2(sdod_softmax_rows_f16(sc, sc, L, L, st)); }, "softmax_rows", 0, 2.0 * L * L * 2);
+        emit([=](hipStream_t st) { check_rc(sdod_softmax_rows_f16(sc, sc, L, L, st)); }, "softmax_rows", 0, 2.0 * L * L * 2);
         linear_raw(sc, L, L, vt, L, C, att + (size_t)b * L * C, GemmOpt{});
         release(sc); release(vt);
     }
@@ -589,10 +551,21 @@ Act Graph::vae_attn_block(const std::string& pfx, const Act& x) {
     return out;
 }
 
+void Graph::vae_res_step(const std::string& pfx, Act& h, int cout) {
+    Act r = vae_res_block(pfx, h, cout);
+    release_after_consumer(h); // residual of r's (possibly still split-K) out conv
+    h = r;
+}
+
+void Graph::vae_mid(const std::string& pfx, Act& h, int ch) {
+    vae_res_step(pfx + ".block_1", h, ch);
+    { Act r = vae_attn_block(pfx + ".attn_1", h); release(h); h = r; }
+    vae_res_step(pfx + ".block_2", h, ch);
+}
+
 void Graph::build_vae() {
     const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, LC = cfg_.latent_channels, VC = cfg_.vae_channels;
     SDOD_REQUIRE(LC * 9 <= 64, "latent_channels too large for the small-Cin path");
-    const int mult[4] = {1, 2, 4, 4};
     float* z_in = (float*)io_alloc(inputs_, (size_t)B * LC * H * Wd * sizeof(float));
     f16* img_out = (f16*)io_alloc(outputs_, (size_t)B * (8 * H) * (8 * Wd) * 3 * sizeof(f16));
 
@@ -600,28 +573,21 @@ void Graph::build_vae() {
     Act zl = act(B, H, Wd, LC);
     {
         const float* wq = W<float>(pqw); const float* bq = W<float>(pqb);
-        emit([=](hipStream_t st) { check_rc2(sdod_latent_prep_f16(z_in, wq, bq, zl.p, B, LC, H * Wd, 1.0f / 0.18215f, st)); });
+        emit([=](hipStream_t st) { check_rc(sdod_latent_prep_f16(z_in, wq, bq, zl.p, B, LC, H * Wd, 1.0f / 0.18215f, st)); });
     }
-    int ch = VC * mult[3];
+    int ch = VC * kChMult[3];
     const int ciw = P("decoder.conv_in.weight", {ch, LC, 3, 3}, PK_CONV3_SMALL), cib = P("decoder.conv_in.bias", {ch}, PK_VEC);
     f16* cols = alloc((size_t)B * H * Wd * 64);
     const int wr = wrap_;
-    emit([=](hipStream_t st) { check_rc2(sdod_im2col3x3_small_wrap_f16(zl.p, cols, B, H, Wd, LC, 64, wr, st)); });
+    emit([=](hipStream_t st) { check_rc(sdod_im2col3x3_small_wrap_f16(zl.p, cols, B, H, Wd, LC, 64, wr, st)); });
     Act h = act(B, H, Wd, ch);
     { GemmOpt o; o.bias = cib; linear(cols, B * H * Wd, 64, ciw, ch, h.p, o); }
     release(cols); release(zl);
 
-    { Act r = vae_res_block("decoder.mid.block_1", h, ch); release_after_consumer(h); h = r; }
-    { Act r = vae_attn_block("decoder.mid.attn_1", h); release(h); h = r; }
-    { Act r = vae_res_block("decoder.mid.block_2", h, ch); release_after_consumer(h); h = r; }
+    vae_mid("decoder.mid", h, ch);
     for (int level = 3; level >= 0; --level) {
-        const int cout = VC * mult[level];
-        for (int i = 0; i < 3; ++i) {
-            Act r = vae_res_block("decoder.up." + std::to_string(level) + ".block." + std::to_string(i), h, cout);
-            release_after_consumer(h);
-            h = r;
-        }
-        ch = cout;
+        ch = VC * kChMult[level];
+        for (int i = 0; i < 3; ++i) vae_res_step("decoder.up." + std::to_string(level) + ".block." + std::to_string(i), h, ch);
         if (level != 0) {
             const std::string up = "decoder.up." + std::to_string(level) + ".upsample.conv";
             const int w = P(up + ".weight", {ch, ch, 3, 3}, PK_CONV3), b = P(up + ".bias", {ch}, PK_VEC);
@@ -651,7 +617,6 @@ void Graph::build_vae_encoder(bool masked) {
     const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, LC = cfg_.latent_channels, VC = cfg_.vae_channels;
     const int IH = 8 * H, IW = 8 * Wd, ZC = 2 * LC;
     SDOD_REQUIRE(VC == 64 || VC == 128 || VC == 256 || VC == 320, "vae_channels must be 64, 128, 256 or 320 (image input convolution)");
-    const int mult[4] = {1, 2, 4, 4};
     uint8_t* img_in = (uint8_t*)io_alloc(inputs_, (size_t)B * IH * IW * 3);
     const uint8_t* mask_in = masked ? (const uint8_t*)io_alloc(inputs_, (size_t)B * IH * IW) : nullptr;
     float* mom_out = (float*)io_alloc(outputs_, (size_t)B * ZC * H * Wd * sizeof(float));
@@ -659,32 +624,22 @@ void Graph::build_vae_encoder(bool masked) {
     const int ciw = P("encoder.conv_in.weight", {VC, 3, 3, 3}, PK_CONV3_SMALL), cib = P("encoder.conv_in.bias", {VC}, PK_VEC);
     Act h = act(B, IH, IW, VC);
     {
-        const f16* wp = mode_ != DECLARE ? W<f16>(ciw) : nullptr;
-        const float* bp = mode_ != DECLARE ? W<float>(cib) : nullptr;
+        const f16* wp = W<f16>(ciw);
+        const float* bp = W<float>(cib);
         f16* hp = h.p;
-        settle();
-        if (mode_ == REAL) {
-            const double fl = 2.0 * B * IH * IW * VC * 64;
-            flops_ += fl;
-            if (masked)
-                ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_masked_image_conv_in_f16(img_in, mask_in, wp, bp, hp, B, IH, IW, VC, st)); },
-                                  "masked_image_conv_in", fl, (double)B * IH * IW * (4 + VC * 2) + VC * 64 * 2,
-                                  "M" + std::to_string(B * IH * IW) + " N" + std::to_string(VC) + " K64"});
-            else
-                ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_image_conv_in_f16(img_in, wp, bp, hp, B, IH, IW, VC, st)); }, "image_conv_in",
-                                  fl, (double)B * IH * IW * (3 + VC * 2) + VC * 64 * 2,
-                                  "M" + std::to_string(B * IH * IW) + " N" + std::to_string(VC) + " K64"});
-        }
+        const double fl = 2.0 * B * IH * IW * VC * 64;
+        const std::string shape = "M" + std::to_string(B * IH * IW) + " N" + std::to_string(VC) + " K64";
+        if (masked)
+            emit([=](hipStream_t st) { check_rc(sdod_masked_image_conv_in_f16(img_in, mask_in, wp, bp, hp, B, IH, IW, VC, st)); },
+                 "masked_image_conv_in", fl, (double)B * IH * IW * (4 + VC * 2) + VC * 64 * 2, shape);
+        else
+            emit([=](hipStream_t st) { check_rc(sdod_image_conv_in_f16(img_in, wp, bp, hp, B, IH, IW, VC, st)); }, "image_conv_in", fl,
+                 (double)B * IH * IW * (3 + VC * 2) + VC * 64 * 2, shape);
     }
     int ch = VC;
     for (int level = 0; level < 4; ++level) {
-        const int cout = VC * mult[level];
-        for (int i = 0; i < 2; ++i) {
-            Act r = vae_res_block("encoder.down." + std::to_string(level) + ".block." + std::to_string(i), h, cout);
-            release_after_consumer(h);
-            h = r;
-        }
-        ch = cout;
+        ch = VC * kChMult[level];
+        for (int i = 0; i < 2; ++i) vae_res_step("encoder.down." + std::to_string(level) + ".block." + std::to_string(i), h, ch);
         if (level != 3) {
             const std::string dn = "encoder.down." + std::to_string(level) + ".downsample.conv";
             const int w = P(dn + ".weight", {ch, ch, 3, 3}, PK_CONV3), b = P(dn + ".bias", {ch}, PK_VEC);
@@ -695,9 +650,7 @@ void Graph::build_vae_encoder(bool masked) {
         }
     }
     if (mode_ != DECLARE) SDOD_REQUIRE(h.h == H && h.w == Wd, "image size must be 8x the latent size");
-    { Act r = vae_res_block("encoder.mid.block_1", h, ch); release_after_consumer(h); h = r; }
-    { Act r = vae_attn_block("encoder.mid.attn_1", h); release(h); h = r; }
-    { Act r = vae_res_block("encoder.mid.block_2", h, ch); release_after_consumer(h); h = r; }
+    vae_mid("encoder.mid", h, ch);
     const int nw = P("encoder.norm_out.weight", {ch}, PK_VEC), nb = P("encoder.norm_out.bias", {ch}, PK_VEC);
     // conv_out [ZC][9 ch] and quant_conv [ZC][ZC] share one [ZC][9 ch + ZC] matrix; the first 9 ch columns become quant_conv . conv_out
     const int ld = 9 * ch + ZC;
@@ -720,7 +673,7 @@ void Graph::build_vae_encoder(bool masked) {
     release(g);
     {
         const f16* mp = m.p;
-        emit([=](hipStream_t st) { check_rc2(sdod_nhwc_f16_to_nchw_f32(mp, mom_out, B, ZC, H * Wd, st)); }, "nhwc_to_nchw", 0,
+        emit([=](hipStream_t st) { check_rc(sdod_nhwc_f16_to_nchw_f32(mp, mom_out, B, ZC, H * Wd, st)); }, "nhwc_to_nchw", 0,
              (double)B * ZC * H * Wd * 6);
     }
     release(m);
@@ -737,7 +690,7 @@ void Graph::build_adapter() {
     const int HC = acfg_.adapter_hint_channels, NRB = acfg_.adapter_res_blocks > 0 ? acfg_.adapter_res_blocks : 2;
     SDOD_REQUIRE(H >= 8 && Wd >= 8 && H % 8 == 0 && Wd % 8 == 0, "the adapter needs latent_h and latent_w to be multiples of 8, at least 8");
     const int cin = 64 * HC;
-    const int ch[4] = {MC, 2 * MC, 4 * MC, 4 * MC};
+    const int ch[4] = {kChMult[0] * MC, kChMult[1] * MC, kChMult[2] * MC, kChMult[3] * MC};
     const uint8_t* hint = (const uint8_t*)io_alloc(inputs_, (size_t)B * (8 * H) * (8 * Wd) * HC);
     f16* outs[4];
     for (int i = 0; i < 4; ++i) outs[i] = (f16*)io_alloc(outputs_, (size_t)B * (H >> i) * (Wd >> i) * ch[i] * sizeof(f16));
@@ -745,7 +698,7 @@ void Graph::build_adapter() {
     Act u = act(B, H, Wd, cin);
     {
         f16* up = u.p;
-        emit([=](hipStream_t st) { check_rc2(sdod_pixel_unshuffle_u8_f16(hint, up, B, H, Wd, HC, 8, st)); }, "pixel_unshuffle", 0,
+        emit([=](hipStream_t st) { check_rc(sdod_pixel_unshuffle_u8_f16(hint, up, B, H, Wd, HC, 8, st)); }, "pixel_unshuffle", 0,
              (double)u.numel() * 3);
     }
     const int ciw = P("conv_in.weight", {MC, cin, 3, 3}, PK_CONV3), cib = P("conv_in.bias", {MC}, PK_VEC);
@@ -763,7 +716,7 @@ void Graph::build_adapter() {
                 const f16* xp = x.p;
                 f16* pp = pl.p;
                 const int xh = x.h, xw = x.w, xc = x.c;
-                emit([=](hipStream_t st) { check_rc2(sdod_avg_pool2_f16(xp, pp, B, xh, xw, xc, st)); }, "avg_pool2", 0, (double)x.numel() * 2.5);
+                emit([=](hipStream_t st) { check_rc(sdod_avg_pool2_f16(xp, pp, B, xh, xw, xc, st)); }, "avg_pool2", 0, (double)x.numel() * 2.5);
                 drop(x, x_in_arena);
                 x = pl;
                 x_in_arena = true;
@@ -782,7 +735,7 @@ void Graph::build_adapter() {
             {
                 f16* tp = t.p;
                 const size_t cnt = t.numel();
-                emit([=](hipStream_t st) { check_rc2(sdod_act_f16(tp, tp, cnt, SDOD_ACT_RELU, st)); }, "relu", 0, (double)cnt * 4);
+                emit([=](hipStream_t st) { check_rc(sdod_act_f16(tp, tp, cnt, SDOD_ACT_RELU, st)); }, "relu", 0, (double)cnt * 4);
             }
             const bool last = j == NRB - 1;
             Act y;
@@ -799,19 +752,15 @@ void Graph::build_adapter() {
 
 // ------------------------------------------------------------------------------------------------ ESRGAN upscaler
 void Graph::dense_conv(sdod_dense_conv_desc d, int w, int bias) {
-    settle();
-    if (mode_ == DECLARE) return;
     d.w = params_[w].dev;
     d.bias = W<float>(bias);
-    if (mode_ != REAL) return;
-    SDOD_REQUIRE(sdod_dense_conv3x3_ok(&d) == 1, "dense-block convolution refused by its kernel");
+    if (mode_ == REAL) SDOD_REQUIRE(sdod_dense_conv3x3_ok(&d) == 1, "dense-block convolution refused by its kernel");
     const double px = (double)d.n * (d.h << d.upsample) * (d.w_in << d.upsample);
-    const double fl = 2.0 * px * d.cout * 9.0 * d.cin;
-    flops_ += fl;
     const double by = (double)d.n * d.h * d.w_in * d.cin * 2 + 9.0 * d.cin * d.cout * 2 + px * d.cout * 2 * (1 + (d.res1 ? 1 : 0) + (d.res2 ? 1 : 0));
-    ops_.push_back(Op{[d](hipStream_t st) { check_rc2(sdod_dense_conv3x3_f16(&d, st)); }, d.cout == 32 ? "dense_conv_n32" : "dense_conv_n64", fl, by,
-                      std::string("conv3") + (d.upsample ? "u" : "") + " M" + std::to_string((long long)px) + " N" + std::to_string(d.cout) + " K" +
-                          std::to_string(9 * d.cin)});
+    emit([d](hipStream_t st) { check_rc(sdod_dense_conv3x3_f16(&d, st)); }, d.cout == 32 ? "dense_conv_n32" : "dense_conv_n64",
+         2.0 * px * d.cout * 9.0 * d.cin, by,
+         std::string("conv3") + (d.upsample ? "u" : "") + " M" + std::to_string((long long)px) + " N" + std::to_string(d.cout) + " K" +
+             std::to_string(9 * d.cin));
 }
 
 // ESRGAN's RRDBNet (Wang et al. 2018; basicsr's RRDBNet(3, 3, num_feat=64, num_block, num_grow_ch=32, scale=4)) on u / 255:
@@ -836,13 +785,11 @@ void Graph::build_upscaler() {
     f16* buf[3];
     for (int i = 0; i < 3; ++i) buf[i] = alloc(rows * LD);
     {
-        const f16* wp = mode_ != DECLARE ? W<f16>(cfw) : nullptr;
-        const float* bp = mode_ != DECLARE ? W<float>(cfb) : nullptr;
+        const f16* wp = W<f16>(cfw);
+        const float* bp = W<float>(cfb);
         f16 *fp = feat.p, *b0 = buf[0];
-        const double fl = 2.0 * rows * NF * 64;
-        if (mode_ == REAL) flops_ += fl;
-        emit([=](hipStream_t st) { check_rc2(sdod_image_conv_in_unit_f16(img_in, wp, bp, fp, b0, LD, B, H, Wd, NF, st)); }, "image_conv_in_unit", fl,
-             (double)rows * (3 + NF * 4) + NF * 64 * 2);
+        emit([=](hipStream_t st) { check_rc(sdod_image_conv_in_unit_f16(img_in, wp, bp, fp, b0, LD, B, H, Wd, NF, st)); }, "image_conv_in_unit",
+             2.0 * rows * NF * 64, (double)rows * (3 + NF * 4) + NF * 64 * 2);
     }
     auto dc = [&](const f16* in, int ld_in, int cin, int w, int b, f16* out, int ld_out, int out_col, int cout, int h, int wd, int ups, float alpha,
                   float slope, const f16* r1, int ld1, float c1, const f16* r2, int ld2) {
@@ -905,7 +852,7 @@ void Graph::build_clip() {
     Act x = act(B, 1, L, D);
     {
         const f16* tp = W<f16>(te); const f16* pp = W<f16>(pe);
-        emit([=](hipStream_t st) { check_rc2(sdod_embedding_f16(ids, tp, pp, x.p, rows, L, D, st)); });
+        emit([=](hipStream_t st) { check_rc(sdod_embedding_f16(ids, tp, pp, x.p, rows, L, D, st)); });
     }
     for (int l = 0; l < NL; ++l) {
         const std::string pfx = (oc ? "transformer.resblocks." : "text_model.encoder.layers.") + std::to_string(l);
@@ -950,11 +897,9 @@ void Graph::build_clip() {
     }
     const int fw = P(oc ? "ln_final.weight" : "text_model.final_layer_norm.weight", {D}, PK_VEC);
     const int fb = P(oc ? "ln_final.bias" : "text_model.final_layer_norm.bias", {D}, PK_VEC);
-    settle();
-    if (mode_ == REAL) {
+    {
         const f16* xp = x.p; const float* wp = W<float>(fw); const float* bp = W<float>(fb);
-        ops_.push_back(Op{[=](hipStream_t st) { check_rc2(sdod_layer_norm_f16(xp, out, wp, bp, rows, D, 1e-5f, st)); }, "layer_norm", 0,
-                          2.0 * rows * D * 2, ""});
+        emit([=](hipStream_t st) { check_rc(sdod_layer_norm_f16(xp, out, wp, bp, rows, D, 1e-5f, st)); }, "layer_norm", 0, 2.0 * rows * D * 2);
     }
     release(x);
 }
