@@ -47,6 +47,25 @@
  *                 (64 features, growth 32, scale 4, sdod_upscaler_config.num_blocks blocks) on u / 255, parameters by basicsr's names
  *                 (conv_first, body.N.rdbK.convJ, conv_body, conv_up1, conv_up2, conv_hr, conv_last); always fp16 weights;
  *                 15 num_blocks + 6 launches (not part of the reference)
+ *   UNET with sdod_control_config.control_inputs (ControlNet): behind every other input, 13 residual inputs
+ *                 fp16 NHWC [B][H / s][W / s][C] in skip order -- (s, C) = (1, MC) x3, (2, MC), (2, 2 MC) x2, (4, 2 MC), (4, 4 MC) x2,
+ *                 (8, 4 MC) x3, and (8, 4 MC) for the middle block's output -- and one input control_scale fp32 [13]; all zero after
+ *                 finalize.  One launch behind the middle block (sdod_add_control_f16) does cldm's ControlledUnetModel additions in
+ *                 place: hs[k] += control_scale[k] * residual[k], h += control_scale[12] * residual[12]
+ *   CONTROLNET    in0 x fp32 NCHW [B][4][H][W], in1 temb fp16 [B][E_c] (the control TEMB graph's output), in2 ctx fp16
+ *                 [B][context_len][ctx_dim], in3 guided hint fp16 NHWC [B / 2][H][W][MC] (the CONTROL_HINT graph's output, shared by
+ *                 the two guidance halves of the batch; zero after finalize); out0..12 the 13 residuals above.  ldm's cldm.ControlNet
+ *                 for SD 1.x: input_blocks.0.0, + guided hint, the UNet's input blocks and middle block on the checkpoint's own
+ *                 weights, then zero_convs.k.0 (k = 0..11) on the twelve skip tensors and middle_block_out.0 on the middle output.
+ *                 Parameters by the checkpoint's names without `control_model.`; always fp16 weights; batch must be even
+ *   CONTROL_HINT  in0 hint uint8 HWC [B][8H][8W][3]; out0 fp16 NHWC [B][H][W][MC]: cldm's input_hint_block on u / 255, eight 3x3
+ *                 convolutions 3 -> 16 -> 16 -> 32 (stride 2) -> 32 -> 96 (stride 2) -> 96 -> 256 (stride 2) -> MC with SiLU behind
+ *                 all but the last (input_hint_block.0, .2, .., .14).  The 16 / 32 / 96 channel widths are built zero-padded to 64 /
+ *                 64 / 128 (the GEMM needs K % 64 == 0), which is exact: zero weights, zero bias and SiLU(0) = 0 keep the padded
+ *                 channels zero.  The parameter table lists the PADDED shapes; whoever sets the parameters pads (sdod.amd.engine's
+ *                 ControlHint does).  Runs once per hint, not once per step
+ *   TEMB with sdod_control_config.control_temb: the time conditioning of a CONTROLNET graph, out0 fp16 [B][E_c]: the checkpoint's own
+ *                 time_embed.* and the emb_layers of its ten ResBlocks (8 input blocks, 2 middle), E_c = 30 MC
  *
  * Parameters are addressed by their CompVis-ldm / HF-CLIP state-dict names (without the
  * `model.diffusion_model.` / `first_stage_model.` / `cond_stage_model.transformer.` prefixes) and are
@@ -69,7 +88,8 @@ extern "C" {
 #endif
 
 enum sdod_graph_kind { SDOD_GRAPH_UNET = 0, SDOD_GRAPH_VAE_DECODER = 1, SDOD_GRAPH_TEXT_ENCODER = 2, SDOD_GRAPH_TEMB = 3,
-                       SDOD_GRAPH_VAE_ENCODER = 4, SDOD_GRAPH_VAE_ENCODER_MASKED = 5, SDOD_GRAPH_ADAPTER = 6, SDOD_GRAPH_UPSCALER = 7 };
+                       SDOD_GRAPH_VAE_ENCODER = 4, SDOD_GRAPH_VAE_ENCODER_MASKED = 5, SDOD_GRAPH_ADAPTER = 6, SDOD_GRAPH_UPSCALER = 7,
+                       SDOD_GRAPH_CONTROLNET = 8, SDOD_GRAPH_CONTROL_HINT = 9 };
 
 typedef struct sdod_model_config {
     int latent_channels; /* 4 */
@@ -148,6 +168,20 @@ typedef struct sdod_upscaler_config {
     int in_w;       /* input image width */
 } sdod_upscaler_config;
 SDOD_API int sdod_graph_create_upscaler(void** graph, const sdod_upscaler_config* cfg, int batch);
+/* ControlNet.  Like the adapter's, its switches travel next to sdod_model_config; all zero = nothing changes.  The
+ * kinds SDOD_GRAPH_CONTROLNET and SDOD_GRAPH_CONTROL_HINT can only be created here (control may then be NULL); the other create
+ * functions refuse them.  For the remaining kinds this is sdod_graph_create plus the two switches; a switch on a kind it does not
+ * apply to, a CONTROLNET graph with an odd batch, concat_channels or weight_quant on a control graph: INVALID_ARGUMENT. */
+typedef struct sdod_control_config {
+    int control_inputs; /* UNET graph: 1 = it has the 13 residual inputs and control_scale, and one more launch; 0 = the plain graph */
+    int control_temb;   /* TEMB graph: 1 = the time conditioning of a CONTROLNET graph ([B][30 MC]); 0 = the UNet's */
+} sdod_control_config;
+SDOD_API int sdod_graph_create_control(void** graph, int kind, const sdod_model_config* cfg, const sdod_control_config* control, int batch);
+/* Before sdod_graph_finalize: output `index` of the graph is written to device_ptr (memory the caller owns, typically an input slot
+ * of another graph, so that nothing is copied between the two per run) instead of a slot the graph allocates.  bytes must equal the
+ * output's size and device_ptr be 256-byte aligned, else INVALID_ARGUMENT.  sdod_graph_io then reports device_ptr.  Unbound outputs
+ * stay owned by the graph.  The last GEMM of the path writes there directly (no extra launch). */
+SDOD_API int sdod_graph_bind_output(void* graph, int index, void* device_ptr, size_t bytes);
 SDOD_API int sdod_graph_destroy(void* graph);
 
 /* parameter table (fixed by kind + config) */

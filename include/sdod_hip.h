@@ -303,6 +303,21 @@ SDOD_API int sdod_adapter_stage_f16(const void* src, void* dst, size_t count, fl
  * thread loads its 16 bytes of f once and updates every copy.  reps 1 or 2 (the guidance copies, laid out as sdod_stage_unet_inputs
  * writes them), per_copy % 8 == 0, 16-byte aligned pointers. */
 SDOD_API int sdod_add_feature_f16(void* h, const void* f, size_t per_copy, int reps, void* stream);
+/* ---- ControlNet: the additions of cldm's ControlledUnetModel, hs[k] + control[k] for the twelve skip tensors and
+ * h + control[12] for the middle output, as ONE launch over a by-value table of up to SDOD_CONTROL_MAX_SEGS segments:
+ *   seg[k].h[i] = fp16((float)seg[k].h[i] + scales[k] * (float)seg[k].r[i]),  i < seg[k].count
+ * in place, the product and the sum each rounded to fp32 on its own (no FMA).  16-byte lanes; every workgroup lies inside one
+ * segment (up to 8192 halves of it).  scales is DEVICE memory, fp32 [count], read by the kernel: a captured launch picks up a new
+ * weight.  A segment whose scale is exactly 0 is neither read nor written (its r may hold anything, its h keeps its bits).
+ * count in [1, SDOD_CONTROL_MAX_SEGS]; every h and r non-null and 16-byte aligned, every seg count > 0 and % 8 == 0, scales 4-byte
+ * aligned; otherwise INVALID_ARGUMENT before any launch, the destinations untouched.  Segments must not overlap (not checked). */
+#define SDOD_CONTROL_MAX_SEGS 16
+typedef struct sdod_control_seg {
+    void* h;       /* fp16, updated in place */
+    const void* r; /* fp16 residual, same length */
+    size_t count;  /* halves */
+} sdod_control_seg;
+SDOD_API int sdod_add_control_f16(const sdod_control_seg* segs, int count, const float* scales, void* stream);
 SDOD_API int sdod_im2col3x3_small_f16(const void* x, void* y, int n_img, int h, int w, int c, int kpad, void* stream);
 /* the same kernel with a circular border: wrap bit 0 = columns (x) wrap, bit 1 = rows (y) wrap; a wrapped tap reads pixel
  * (y mod h, x mod w) of its own image.  wrap = 0 is sdod_im2col3x3_small_f16, bit for bit. */

@@ -143,6 +143,36 @@ __global__ void add_feature_kernel(f16* h, const f16* f, size_t n8, size_t per_c
     }
 }
 
+// ControlNet's thirteen additions in one launch.  The table travels by value (kernel arguments): segment k owns the workgroups
+// [first[k], first[k + 1]), each of which covers kControlChunk halves of it, so a workgroup never straddles two segments and the
+// scale is one scalar load.  A zero scale ends the workgroup before it touches h or r.
+constexpr int kControlChunk = 256 * 8 * 4; // halves per workgroup: four 16-byte lanes per thread
+struct ControlTable {
+    f16* h[SDOD_CONTROL_MAX_SEGS];
+    const f16* r[SDOD_CONTROL_MAX_SEGS];
+    size_t n8[SDOD_CONTROL_MAX_SEGS];          // 16-byte lanes of the segment
+    unsigned first[SDOD_CONTROL_MAX_SEGS + 1]; // first workgroup of the segment; first[count] = grid size
+    int count;
+};
+
+__global__ void add_control_kernel(const ControlTable t, const float* scales) {
+    int k = 0;
+    while (k + 1 < t.count && blockIdx.x >= t.first[k + 1]) ++k; // (uniform: blockIdx only)
+    const float s = scales[k];
+    if (s == 0.f) return;
+    f16* h = t.h[k];
+    const f16* r = t.r[k];
+    const size_t base = (size_t)(blockIdx.x - t.first[k]) * (kControlChunk / 8);
+    const size_t end = base + kControlChunk / 8 < t.n8[k] ? base + kControlChunk / 8 : t.n8[k];
+    for (size_t i = base + threadIdx.x; i < end; i += 256) {
+        const f16x8 u = ldg8(h + i * 8), v = ldg8(r + i * 8);
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (f16)add_rn((float)u[e], mul_rn(s, (float)v[e]));
+        stg8(h + i * 8, o);
+    }
+}
+
 __global__ void concat_kernel(const f16* a, const f16* b, f16* y, size_t rows, int c0, int c1) {
     const int cp = (c0 + c1) / 8, cp0 = c0 / 8;
     const size_t total = rows * cp;
@@ -1102,6 +1132,31 @@ extern "C" int sdod_add_feature_f16(void* h, const void* f, size_t per_copy, int
     SDOD_REQUIRE(reps == 1 || reps == 2, "reps must be 1 or 2 (the guidance copies)");
     SDOD_REQUIRE((((uintptr_t)h | (uintptr_t)f) & 15) == 0, "misaligned pointer (16 bytes)");
     LAUNCH(add_feature_kernel, per_copy / 8, stream, (f16*)h, (const f16*)f, per_copy / 8, per_copy, reps);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_add_control_f16(const sdod_control_seg* segs, int count, const float* scales, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(segs && scales && count >= 1 && count <= SDOD_CONTROL_MAX_SEGS, "bad argument (1 .. 16 segments)");
+    SDOD_REQUIRE(((uintptr_t)scales & 3) == 0, "misaligned pointer (scales: 4 bytes)");
+    ControlTable t{};
+    t.count = count;
+    size_t groups = 0;
+    for (int k = 0; k < count; ++k) {
+        SDOD_REQUIRE(segs[k].h && segs[k].r && segs[k].count > 0 && segs[k].count % 8 == 0,
+                     "bad argument (every segment needs h, r and a count that is a multiple of 8)");
+        SDOD_REQUIRE((((uintptr_t)segs[k].h | (uintptr_t)segs[k].r) & 15) == 0, "misaligned pointer (16 bytes)");
+        t.h[k] = (f16*)segs[k].h;
+        t.r[k] = (const f16*)segs[k].r;
+        t.n8[k] = segs[k].count / 8;
+        t.first[k] = (unsigned)groups;
+        groups += (segs[k].count + kControlChunk - 1) / kControlChunk;
+        SDOD_REQUIRE(groups <= 0x7fffffffu, "too many elements for one launch");
+    }
+    t.first[count] = (unsigned)groups;
+    SDOD_LAUNCH(add_control_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, t, scales);
+    SDOD_HIP_CHECK(hipGetLastError());
     return 0;
     SDOD_CATCH
 }

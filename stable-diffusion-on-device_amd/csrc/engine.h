@@ -66,12 +66,13 @@ struct Act {
 struct IoSlot {
     void* ptr = nullptr;
     size_t bytes = 0;
+    bool owned = true; // false: an output bound to the caller's memory (bind_output)
 };
 
 class Graph {
 public:
     Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg = sdod_adapter_config{0, 0, 0}, int wrap = 0,
-          const sdod_upscaler_config& ucfg = sdod_upscaler_config{0, 0, 0});
+          const sdod_upscaler_config& ucfg = sdod_upscaler_config{0, 0, 0}, const sdod_control_config* ccfg = nullptr);
     ~Graph();
     Graph(const Graph&) = delete;
 
@@ -90,6 +91,8 @@ public:
     void execute(hipStream_t st, bool use_hip_graph, bool skip_static = false);
     void check_health() const; // throws RUNTIME_ERROR once a GroupNorm grid barrier has timed out on this device (sticky)
     IoSlot io(bool output, int index) const;
+    // before finalize(): output `index` is written to `ptr` (the caller's memory) instead of a slot of the graph's own
+    void bind_output(int index, void* ptr, size_t bytes);
     void stats(size_t* wbytes, size_t* abytes, int* launches, double* flops) const;
 
 private:
@@ -98,6 +101,8 @@ private:
     sdod_model_config cfg_;
     sdod_adapter_config acfg_; // T2I-Adapter: all zero = no adapter inputs (UNET), required for kind ADAPTER
     sdod_upscaler_config ucfg_; // kind UPSCALER only (sdod_graph_create_upscaler); all zero for every other kind
+    sdod_control_config ccfg_{0, 0}; // ControlNet switches of the UNET / TEMB graphs (sdod_graph_create_control); all zero = none
+    bool has_kv() const { return kind_ == SDOD_GRAPH_UNET || kind_ == SDOD_GRAPH_CONTROLNET; } // owns kv_all_ and the static K/V GEMM
     int batch_;
     int wrap_ = 0; // seamless tiling (UNET, VAE_DECODER): bit 0 = x wraps, bit 1 = y wraps; conv() turns it into sdod_gemm_desc::pad_mode
     Mode mode_ = DECLARE;
@@ -156,6 +161,8 @@ private:
     // ---- io
     std::vector<IoSlot> inputs_, outputs_;
     void* io_alloc(std::vector<IoSlot>& v, size_t bytes);
+    std::vector<size_t> out_bytes_;   // output sizes as the DECLARE pass saw them (bind_output checks against them)
+    std::map<int, void*> bound_out_;  // output index -> the caller's memory
 
     // ---- launch list
     struct Op {
@@ -189,6 +196,8 @@ private:
     void build_temb();
     void build_adapter();
     void build_upscaler();
+    void build_controlnet();
+    void build_control_hint();
 
     // ---- op emitters (record in REAL mode, account in DRY mode, nothing in DECLARE mode)
     struct GemmOpt {
@@ -280,6 +289,14 @@ private:
     }
     Act spatial_transformer(const std::string& pfx, const Act& x, const Act& ctx);
     Act unet_conv_in(const float* x_in, const float* cond_in); // input_blocks.0.0 in its three forms
+    // input_blocks.1 .. 11 and middle_block.0/1/2 behind input_blocks.0 (h): the half the UNet and the ControlNet share.  hs != null
+    // (UNet): every skip tensor is pushed and kept.  hs == null (ControlNet): on_skip(k, t) sees skip tensor k = 1 .. 11 when it is
+    // complete and the tensor returns to the arena once its next consumer has read it.  Returns the middle block's output.
+    Act unet_encoder(Act h, const Act& ctx, const f16* emb_all, int emb_ld, int& emb_off, const f16* const* feat_in, std::vector<Act>* hs,
+                     const std::function<void(int, const Act&)>& on_skip);
+    size_t control_residual_numel(int k) const; // ControlNet residual k = 0 .. 12 at this graph's batch, in halves
+    void kv_all_gemm(const f16* ctx_in); // the static launch: cross-attention K / V of every transformer of the graph
+    std::vector<std::pair<std::string, int>> temb_blocks() const; // the ResBlocks a TEMB graph projects for (control_temb: the first ten)
     Act vae_res_block(const std::string& pfx, const Act& x, int cout);
     Act vae_attn_block(const std::string& pfx, const Act& x);
     void vae_res_step(const std::string& pfx, Act& h, int cout); // h = vae_res_block(h); the old h, the block's residual, is parked

@@ -37,9 +37,23 @@ static void parallel_for(int64_t n, F&& fn) {
 }
 
 // ------------------------------------------------------------------------------------------ lifecycle
-Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg, int wrap, const sdod_upscaler_config& ucfg)
+Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg, int wrap, const sdod_upscaler_config& ucfg,
+             const sdod_control_config* ccfg)
     : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), batch_(batch), wrap_(wrap) {
-    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_UPSCALER, "unknown graph kind");
+    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_CONTROL_HINT, "unknown graph kind");
+    const bool control_kind = kind == SDOD_GRAPH_CONTROLNET || kind == SDOD_GRAPH_CONTROL_HINT;
+    SDOD_REQUIRE(!control_kind || ccfg, "the CONTROLNET and CONTROL_HINT graphs are created by sdod_graph_create_control");
+    if (ccfg) {
+        ccfg_ = *ccfg;
+        SDOD_REQUIRE((ccfg_.control_inputs == 0 || ccfg_.control_inputs == 1) && (ccfg_.control_temb == 0 || ccfg_.control_temb == 1),
+                     "control_inputs and control_temb must be 0 or 1");
+        SDOD_REQUIRE(ccfg_.control_inputs == 0 || kind == SDOD_GRAPH_UNET, "control_inputs applies to the UNET graph only");
+        SDOD_REQUIRE(ccfg_.control_temb == 0 || kind == SDOD_GRAPH_TEMB, "control_temb applies to the TEMB graph only");
+        if (control_kind || ccfg_.control_temb) {
+            SDOD_REQUIRE(cfg.concat_channels == 0 && cfg.weight_quant == 0, "a control graph takes no concat_channels and no weight_quant");
+            SDOD_REQUIRE(kind != SDOD_GRAPH_CONTROLNET || batch % 2 == 0, "the CONTROLNET graph needs an even batch (the two guidance halves)");
+        }
+    }
     if (kind == SDOD_GRAPH_UPSCALER) {
         SDOD_REQUIRE(ucfg.num_blocks != 0 || ucfg.in_h != 0 || ucfg.in_w != 0, "the UPSCALER graph is created by sdod_graph_create_upscaler");
         SDOD_REQUIRE(ucfg.num_blocks >= 1 && ucfg.num_blocks <= 23, "num_blocks must be in [1, 23]");
@@ -81,7 +95,8 @@ Graph::~Graph() {
     for (hipEvent_t e : pf_events_) (void)hipEventDestroy(e);
     if (hip_graph_) (void)hipGraphDestroy(hip_graph_);
     for (auto& s : inputs_) (void)hipFree(s.ptr);
-    for (auto& s : outputs_) (void)hipFree(s.ptr);
+    for (auto& s : outputs_)
+        if (s.owned) (void)hipFree(s.ptr);
     (void)hipFree(weight_base_);
     (void)hipFree(base_copy_);
     (void)hipFree(qscale_);
@@ -485,12 +500,27 @@ void* Graph::io_alloc(std::vector<IoSlot>& v, size_t bytes) {
     IoSlot s;
     s.bytes = bytes;
     if (mode_ == REAL) {
-        SDOD_HIP_CHECK(hipMalloc(&s.ptr, align_up(bytes, 256)));
-        SDOD_HIP_CHECK(hipMemset(s.ptr, 0, align_up(bytes, 256)));
+        auto bound = &v == &outputs_ ? bound_out_.find((int)v.size()) : bound_out_.end();
+        if (bound != bound_out_.end()) { // bind_output(): the caller's memory, as it is
+            s.ptr = bound->second;
+            s.owned = false;
+        } else {
+            SDOD_HIP_CHECK(hipMalloc(&s.ptr, align_up(bytes, 256)));
+            SDOD_HIP_CHECK(hipMemset(s.ptr, 0, align_up(bytes, 256)));
+        }
         v.push_back(s);
         return s.ptr;
     }
+    if (mode_ == DECLARE && &v == &outputs_) out_bytes_.push_back(bytes);
     return kFakeBase + (size_t(1) << 39) + v.size() * 4096; // never dereferenced
+}
+
+void Graph::bind_output(int index, void* ptr, size_t bytes) {
+    SDOD_REQUIRE(!finalized_, "bind_output() must be called before finalize()");
+    SDOD_REQUIRE(index >= 0 && index < (int)out_bytes_.size(), "output index out of range");
+    SDOD_REQUIRE(ptr && ((uintptr_t)ptr & 255) == 0, "misaligned pointer (a bound output needs 256 bytes)");
+    SDOD_REQUIRE(bytes == out_bytes_[index], "size mismatch: output " + std::to_string(index) + " has " + std::to_string(out_bytes_[index]) + " bytes");
+    bound_out_[index] = ptr;
 }
 
 IoSlot Graph::io(bool output, int index) const {
@@ -526,6 +556,10 @@ struct ShapeKey {
 //     an MI355X by tools/make_tune_cache.py and committed, so that every process -- bench, rocprofv3 passes, the C API, a
 //     service restart -- builds the SAME launch list without timing anything, and images are bit-identical across processes
 //     (SDOD_TUNE_DEFAULT=0 ignores it);
+//   * tune/gfx950_control.tune next to it: the picks for the ControlNet graphs' own shapes (zero convolutions, hint encoder, the
+//     control graph's K/V projection) at the sizes its tests and tools/controlnet_bench.py build.  A file of its own because the
+//     first one's key set is pinned (tests/golden/gemm_tiles.json.gz plans exactly its descriptors); it only ADDS shapes: a key
+//     the first table already holds keeps that pick, so no graph that existed before can change;
 //   * SDOD_TUNE_CACHE=<file>: read after (so it overrides) the shipped table; shapes found in neither are timed once and
 //     appended to it.  Picks depend on the build and the device: regenerate the table when the tiles change.
 const char* tune_cache_path() {
@@ -544,6 +578,10 @@ std::string shipped_tune_path() {
     if (b == std::string::npos) return "";
     return lib.substr(0, b) + "/tune/gfx950.tune";
 }
+std::string control_tune_path() {
+    const std::string first = shipped_tune_path();
+    return first.empty() ? first : first.substr(0, first.size() - 5) + "_control.tune";
+}
 struct TuneEntry {
     int v;          // tile + 1000 * split_k
     bool from_file; // read from a table (as opposed to timed by this process)
@@ -553,7 +591,7 @@ struct TuneCache { // process-wide; graphs may be built from several threads (li
     std::map<ShapeKey, TuneEntry> map;
     bool loaded = false;
 };
-void tune_cache_read(const char* path, std::map<ShapeKey, TuneEntry>& c) {
+void tune_cache_read(const char* path, std::map<ShapeKey, TuneEntry>& c, bool keep_existing = false) {
     FILE* f = std::fopen(path, "r");
     if (!f) return;
     char line[512];
@@ -587,7 +625,9 @@ void tune_cache_read(const char* path, std::map<ShapeKey, TuneEntry>& c) {
             continue;
         }
         const int tile = v % 1000, split = v / 1000;
-        if (tile >= 1 && tile <= sdod_gemm_num_tiles() && split >= 1 && split <= 64) c[k] = TuneEntry{v, true}; // a stale table is re-tuned, not trusted
+        if (!(tile >= 1 && tile <= sdod_gemm_num_tiles() && split >= 1 && split <= 64)) continue; // a stale table is re-tuned, not trusted
+        if (keep_existing) c.emplace(k, TuneEntry{v, true});
+        else c[k] = TuneEntry{v, true};
     }
     std::fclose(f);
 }
@@ -598,6 +638,7 @@ TuneCache& tune_cache() {
         c.loaded = true;
         const std::string shipped = shipped_tune_path();
         if (!shipped.empty()) tune_cache_read(shipped.c_str(), c.map);
+        if (!shipped.empty()) tune_cache_read(control_tune_path().c_str(), c.map, true);
         if (const char* path = tune_cache_path()) tune_cache_read(path, c.map);
     }
     return c;
@@ -981,6 +1022,8 @@ void Graph::build() {
     case SDOD_GRAPH_VAE_ENCODER_MASKED: build_vae_encoder(true); break;
     case SDOD_GRAPH_ADAPTER: build_adapter(); break;
     case SDOD_GRAPH_UPSCALER: build_upscaler(); break;
+    case SDOD_GRAPH_CONTROLNET: build_controlnet(); break;
+    case SDOD_GRAPH_CONTROL_HINT: build_control_hint(); break;
     default: build_temb(); break;
     }
     settle();
@@ -1010,7 +1053,7 @@ void Graph::finalize() {
     SDOD_HIP_CHECK(hipMemset(gn_ws_, 0, gn_ws_bytes_)); // the one-launch GroupNorm keeps its grid-barrier words in here: zero once
     SDOD_HIP_CHECK(hipMalloc((void**)&fix_counters_, sdod_gemm_fixup_counters() * sizeof(unsigned)));
     SDOD_HIP_CHECK(hipMemset(fix_counters_, 0, sdod_gemm_fixup_counters() * sizeof(unsigned)));
-    if (kind_ == SDOD_GRAPH_UNET && kv_total_ > 0)
+    if (has_kv() && kv_total_ > 0)
         SDOD_HIP_CHECK(hipMalloc((void**)&kv_all_, (size_t)batch_ * cfg_.context_len * kv_total_ * sizeof(f16)));
     mode_ = REAL;
     arena_reset();
@@ -1368,6 +1411,24 @@ extern "C" int sdod_graph_create_upscaler(void** graph, const sdod_upscaler_conf
     SDOD_CATCH
 }
 
+extern "C" int sdod_graph_create_control(void** graph, int kind, const sdod_model_config* cfg, const sdod_control_config* control, int batch) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph && cfg, "null argument");
+    SDOD_REQUIRE(kind != SDOD_GRAPH_UPSCALER && kind != SDOD_GRAPH_ADAPTER, "this kind has a create function of its own");
+    const sdod_control_config none{0, 0};
+    *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, control ? control : &none);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_bind_output(void* graph, int index, void* device_ptr, size_t bytes) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph, "null argument");
+    static_cast<Graph*>(graph)->bind_output(index, device_ptr, bytes);
+    return 0;
+    SDOD_CATCH
+}
+
 extern "C" int sdod_graph_destroy(void* graph) {
     SDOD_TRY
     delete static_cast<Graph*>(graph);
@@ -1499,6 +1560,7 @@ extern "C" int sdod_graph_tune_info(void* graph, int* from_table, int* tuned_in_
     if (tuned_in_process) *tuned_in_process = g->tune_misses();
     if (table_path && cap > 0) {
         std::string s = sdod::shipped_tune_path();
+        if (!s.empty()) s += " + " + sdod::control_tune_path();
         if (const char* extra = sdod::tune_cache_path()) s += (s.empty() ? "" : " + ") + std::string(extra);
         std::snprintf(table_path, (size_t)cap, "%s", s.c_str());
     }

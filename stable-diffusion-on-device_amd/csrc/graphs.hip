@@ -1,6 +1,6 @@
 // graphs.hip -- launch-list builders, one per graph kind (include/sdod_engine.h): UNet eps-model (with the inpainting, T2I-Adapter
 // and seamless-tiling variants of its inputs), time-embedding MLP, CLIP text encoder, VAE decoder, VAE encoder and its masked form
-// (img2img, inpainting), T2I-Adapter, ESRGAN upscaler.  The first four stand in for the serialized QNN graphs the reference loads
+// (img2img, inpainting), T2I-Adapter, ESRGAN upscaler, ControlNet and its hint encoder.  The first four stand in for the serialized QNN graphs the reference loads
 // (context.cpp:105: "unet.serialized", "text_encoder.serialized", "vae_decoder.serialized", "temb"); the
 // block structure follows the op names visible in the reference's own profiler table
 // (analyze_results.py:20-93: in_layers / emb_layers / out_layers / skip_connection, norm / proj_in /
@@ -303,6 +303,78 @@ Act Graph::unet_conv_in(const float* x_in, const float* cond_in) {
     return h;
 }
 
+// cross-attention K/V of ALL transformers of the graph: one GEMM on the text context, re-run only when the context changes
+void Graph::kv_all_gemm(const f16* ctx_in) {
+    if (mode_ == DECLARE || kv_total_ <= 0) return;
+    to_static_ = true;
+    GemmOpt okv;
+    if (quant_mode()) { okv.wq_scale = qscale_of(group_first("attn2_kv_all")); okv.wq_off = qoff_of(group_first("attn2_kv_all")); }
+    linear_raw(ctx_in, batch_ * cfg_.context_len, cfg_.context_dim, reinterpret_cast<const f16*>(group_base("attn2_kv_all")), cfg_.context_dim,
+               kv_total_, mode_ == REAL ? kv_all_ : const_cast<f16*>(ctx_in) /* placeholder during the sizing pass */, okv);
+    to_static_ = false;
+}
+
+Act Graph::unet_encoder(Act h, const Act& ctx, const f16* emb_all, int emb_ld, int& emb_off, const f16* const* feat_in, std::vector<Act>* hs,
+                        const std::function<void(int, const Act&)>& on_skip) {
+    const int MC = cfg_.model_channels, AR = acfg_.adapter_reps;
+    int ch = MC, ds = 1, idx = 1, k = 1;
+    auto skip = [&](const Act& t) {
+        if (hs) hs->push_back(t);
+        else on_skip(k, t);
+        ++k;
+    };
+    for (int level = 0; level < 4; ++level) {
+        for (int i = 0; i < 2; ++i) {
+            const std::string pfx = "input_blocks." + std::to_string(idx++);
+            Act r = res_block(pfx + ".0", h, nullptr, kChMult[level] * MC, emb_all, emb_ld, emb_off);
+            if (!hs) release_after_consumer(h); // (the block's input: tail or residual of r's, possibly still split-K, out conv)
+            ch = kChMult[level] * MC;
+            if (ds <= 4) {
+                Act t = spatial_transformer(pfx + ".1", r, ctx);
+                release(r);
+                r = t;
+            }
+            h = r;
+            if (feat_in && i == 1) {
+                // ldm input_blocks.2 / .5 / .8 / .11: h = h + features_adapter[level], BEFORE the tensor becomes a skip (TencentARC
+                // openaimodel.py).  An ordinary emit: a split-K reduce still pending on h is flushed in front of it.
+                f16* hp = h.p;
+                const f16* fp = feat_in[level];
+                const size_t per = h.numel() / AR;
+                emit([=](hipStream_t st) { check_rc(sdod_add_feature_f16(hp, fp, per, AR, st)); }, "add_feature", 0,
+                     (double)h.numel() * 4 + (double)per * 2);
+            }
+            skip(h);
+        }
+        if (level != 3) {
+            const std::string pfx = "input_blocks." + std::to_string(idx++) + ".0.op";
+            quant_rows(h.rows() / 4);
+            const int w = P(pfx + ".weight", {ch, ch, 3, 3}, PK_CONV3), b = P(pfx + ".bias", {ch}, PK_VEC);
+            GemmOpt o; o.bias = b;
+            Act d = conv(h, nullptr, w, ch, 3, 2, false, o);
+            if (!hs) release(h);
+            h = d;
+            skip(h);
+            ds *= 2;
+        }
+    }
+    // middle (UNet: h is the last skip and stays on the stack until popped)
+    Act r1 = res_block("middle_block.0", h, nullptr, ch, emb_all, emb_ld, emb_off);
+    if (!hs) release_after_consumer(h);
+    Act t = spatial_transformer("middle_block.1", r1, ctx);
+    release(r1);
+    Act r2 = res_block("middle_block.2", t, nullptr, ch, emb_all, emb_ld, emb_off);
+    release_after_consumer(t); // residual of r2's (possibly still split-K) out conv
+    return r2;
+}
+
+// numel of ControlNet residual k at this graph's batch: the twelve skip tensors in the order the encoder makes them, then the middle
+static const int kCtrlDown[13] = {1, 1, 1, 2, 2, 2, 4, 4, 4, 8, 8, 8, 8};
+static const int kCtrlMult[13] = {1, 1, 1, 1, 2, 2, 2, 4, 4, 4, 4, 4, 4};
+size_t Graph::control_residual_numel(int k) const {
+    return (size_t)batch_ * (cfg_.latent_h / kCtrlDown[k]) * (cfg_.latent_w / kCtrlDown[k]) * kCtrlMult[k] * cfg_.model_channels;
+}
+
 void Graph::build_unet() {
     const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, LC = cfg_.latent_channels;
     const int MC = cfg_.model_channels, EC = 4 * MC, cd = cfg_.context_dim, CL = cfg_.context_len;
@@ -329,6 +401,13 @@ void Graph::build_unet() {
     const f16* feat_in[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int l = 0; AR > 0 && l < 4; ++l)
         feat_in[l] = (const f16*)io_alloc(inputs_, (size_t)(B / AR) * (H >> l) * (Wd >> l) * kChMult[l] * MC * sizeof(f16));
+    // ControlNet residuals: 13 slots in skip order and their fp32 scales, behind every other input
+    const f16* ctrl_in[13] = {};
+    const float* ctrl_scale = nullptr;
+    if (ccfg_.control_inputs) {
+        for (int k = 0; k < 13; ++k) ctrl_in[k] = (const f16*)io_alloc(inputs_, control_residual_numel(k) * sizeof(f16));
+        ctrl_scale = (const float*)io_alloc(inputs_, 13 * sizeof(float));
+    }
     f16* e_out = (f16*)io_alloc(outputs_, (size_t)B * H * Wd * LC * sizeof(f16));
     Act ctx;
     ctx.p = ctx_in; ctx.n = B; ctx.h = 1; ctx.w = CL; ctx.c = cd;
@@ -338,60 +417,28 @@ void Graph::build_unet() {
     const f16* emb_all = temb_in;
     int emb_off = 0;
     kv_off_ = 0;
-    // cross-attention K/V of ALL transformers: one GEMM on the text context, re-run only when the context changes
-    if (mode_ != DECLARE && kv_total_ > 0) {
-        to_static_ = true;
-        GemmOpt okv;
-        if (quant_mode()) { okv.wq_scale = qscale_of(group_first("attn2_kv_all")); okv.wq_off = qoff_of(group_first("attn2_kv_all")); }
-        linear_raw(ctx_in, B * CL, cd, reinterpret_cast<const f16*>(group_base("attn2_kv_all")), cd, kv_total_,
-                   mode_ == REAL ? kv_all_ : ctx_in /* placeholder during the sizing pass */, okv);
-        to_static_ = false;
-    }
+    kv_all_gemm(ctx_in);
 
     Act h = unet_conv_in(x_in, cond_in);
     std::vector<Act> hs;
     hs.push_back(h);
-    int ch = MC, ds = 1, idx = 1;
-    for (int level = 0; level < 4; ++level) {
-        for (int i = 0; i < 2; ++i) {
-            const std::string pfx = "input_blocks." + std::to_string(idx++);
-            Act r = res_block(pfx + ".0", h, nullptr, kChMult[level] * MC, emb_all, emb_ld, emb_off);
-            ch = kChMult[level] * MC;
-            if (ds <= 4) {
-                Act t = spatial_transformer(pfx + ".1", r, ctx);
-                release(r);
-                r = t;
-            }
-            h = r;
-            if (AR > 0 && i == 1) {
-                // ldm input_blocks.2 / .5 / .8 / .11: h = h + features_adapter[level], BEFORE the tensor becomes a skip (TencentARC
-                // openaimodel.py).  An ordinary emit: a split-K reduce still pending on h is flushed in front of it.
-                f16* hp = h.p;
-                const f16* fp = feat_in[level];
-                const size_t per = h.numel() / AR;
-                emit([=](hipStream_t st) { check_rc(sdod_add_feature_f16(hp, fp, per, AR, st)); }, "add_feature", 0,
-                     (double)h.numel() * 4 + (double)per * 2);
-            }
-            hs.push_back(h);
+    h = unet_encoder(h, ctx, emb_all, emb_ld, emb_off, AR > 0 ? feat_in : nullptr, &hs, nullptr);
+    int ch = h.c, ds = 8;
+    if (ccfg_.control_inputs) {
+        // cldm's ControlledUnetModel: h + control[12] and, where the decoder pops them, hs[k] + control[k].  Every encoder launch has
+        // been recorded by now, so the twelve skips take their residual in place, here, in the one launch that also updates h.
+        // emit() settles first: a split-K reduce still pending on h (or one that reads a skip tensor as its residual) runs in front
+        // of the launch and parked tensors go back to the arena, so nothing reads or writes these tensors behind it but the decoder.
+        if (hs.size() != 12) throw Error(INTERNAL_ERROR, "the UNet encoder must leave twelve skip tensors");
+        std::vector<sdod_control_seg> segs;
+        double by = 0;
+        for (int k = 0; k < 13; ++k) {
+            const Act& a = k < 12 ? hs[k] : h;
+            if (control_residual_numel(k) != a.numel()) throw Error(INTERNAL_ERROR, "control residual shape mismatch");
+            segs.push_back(sdod_control_seg{a.p, ctrl_in[k], a.numel()});
+            by += (double)a.numel() * 6;
         }
-        if (level != 3) {
-            const std::string pfx = "input_blocks." + std::to_string(idx++) + ".0.op";
-            quant_rows(h.rows() / 4);
-            const int w = P(pfx + ".weight", {ch, ch, 3, 3}, PK_CONV3), b = P(pfx + ".bias", {ch}, PK_VEC);
-            GemmOpt o; o.bias = b;
-            h = conv(h, nullptr, w, ch, 3, 2, false, o);
-            hs.push_back(h);
-            ds *= 2;
-        }
-    }
-    // middle (h is the last skip and stays on the stack until popped)
-    {
-        Act r1 = res_block("middle_block.0", h, nullptr, ch, emb_all, emb_ld, emb_off);
-        Act t = spatial_transformer("middle_block.1", r1, ctx);
-        release(r1);
-        Act r2 = res_block("middle_block.2", t, nullptr, ch, emb_all, emb_ld, emb_off);
-        release_after_consumer(t); // residual of r2's (possibly still split-K) out conv
-        h = r2;
+        emit([=](hipStream_t st) { check_rc(sdod_add_control_f16(segs.data(), 13, ctrl_scale, st)); }, "add_control", 0, by);
     }
     int oidx = 0;
     for (int level = 3; level >= 0; --level) {
@@ -449,12 +496,105 @@ std::vector<std::pair<std::string, int>> Graph::unet_res_blocks() const {
     return v;
 }
 
+std::vector<std::pair<std::string, int>> Graph::temb_blocks() const {
+    auto v = unet_res_blocks();
+    if (ccfg_.control_temb || kind_ == SDOD_GRAPH_CONTROLNET) v.resize(10); // a ControlNet has the 8 input and 2 middle ResBlocks only
+    return v;
+}
+
+// ------------------------------------------------------------------------------------------------ ControlNet
+// ldm's cldm.ControlNet for SD 1.x: the UNet's encoder half on weights of its own, the guided hint added behind
+// input_blocks.0, and a 1x1 "zero convolution" on each of the twelve skip tensors and on the middle output.  A zero conv writes its
+// output slot directly (which sdod_graph_bind_output can point at the UNet's residual input).  No skip stack: a skip tensor goes
+// back to the arena once its zero conv and the next block have read it.
+void Graph::build_controlnet() {
+    const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, LC = cfg_.latent_channels;
+    const int MC = cfg_.model_channels, cd = cfg_.context_dim, CL = cfg_.context_len;
+    SDOD_REQUIRE(LC * 9 <= 64, "latent_channels too large for the small-Cin path");
+    SDOD_REQUIRE(H >= 8 && Wd >= 8 && H % 8 == 0 && Wd % 8 == 0, "the ControlNet needs latent_h and latent_w to be multiples of 8, at least 8");
+    if (mode_ != DECLARE) {
+        int tot = 0;
+        for (auto& rb : temb_blocks()) tot += rb.second;
+        emb_total_ = tot;
+    }
+    float* x_in = (float*)io_alloc(inputs_, (size_t)B * LC * H * Wd * sizeof(float));
+    f16* temb_in = (f16*)io_alloc(inputs_, (size_t)B * std::max(emb_total_, 1) * sizeof(f16));
+    f16* ctx_in = (f16*)io_alloc(inputs_, (size_t)B * CL * cd * sizeof(f16));
+    const f16* hint_in = (const f16*)io_alloc(inputs_, (size_t)(B / 2) * H * Wd * MC * sizeof(f16));
+    f16* outs[13];
+    for (int k = 0; k < 13; ++k) outs[k] = (f16*)io_alloc(outputs_, control_residual_numel(k) * sizeof(f16));
+    Act ctx;
+    ctx.p = ctx_in; ctx.n = B; ctx.h = 1; ctx.w = CL; ctx.c = cd;
+    int emb_off = 0;
+    kv_off_ = 0;
+    kv_all_gemm(ctx_in);
+
+    auto zero_conv = [&](int k, const Act& t) {
+        const std::string pfx = k < 12 ? "zero_convs." + std::to_string(k) + ".0" : std::string("middle_block_out.0");
+        const int w = P(pfx + ".weight", {t.c, t.c, 1, 1}, PK_CONV1), b = P(pfx + ".bias", {t.c}, PK_VEC);
+        if (control_residual_numel(k) != t.numel()) throw Error(INTERNAL_ERROR, "control residual shape mismatch");
+        GemmOpt o; o.bias = b;
+        linear(t.p, t.rows(), t.c, w, t.c, outs[k], o);
+    };
+    Act h = unet_conv_in(x_in, nullptr);
+    {
+        f16* hp = h.p;
+        const size_t per = h.numel() / 2;
+        emit([=](hipStream_t st) { check_rc(sdod_add_feature_f16(hp, hint_in, per, 2, st)); }, "add_feature", 0, (double)h.numel() * 4 + (double)per * 2);
+    }
+    zero_conv(0, h);
+    h = unet_encoder(h, ctx, temb_in, emb_total_, emb_off, nullptr, nullptr, zero_conv);
+    zero_conv(12, h);
+    release(h);
+    if (mode_ == DECLARE) kv_total_ = kv_off_;
+    else if (emb_off != emb_total_ || kv_off_ != kv_total_) throw Error(INTERNAL_ERROR, "ControlNet conditioning bookkeeping mismatch");
+}
+
+// cldm's input_hint_block on u / 255: conv 3->16, 16->16, 16->32 /2, 32->32, 32->96 /2, 96->96, 96->256 /2, 256->MC, SiLU behind all but
+// the last.  The narrow widths are declared zero-padded (16, 32 -> 64; 96 -> 128) so that every gather GEMM has K % 64 == 0; the
+// padded channels stay exactly zero (zero weights, zero bias, SiLU(0) = 0).  The first convolution is the one-launch image input
+// convolution in its u / 255 form (its border is zero in the normalised space), SiLU behind it as a launch of its own; the others
+// carry SiLU in the GEMM epilogue and the last one writes the output slot.
+void Graph::build_control_hint() {
+    const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, MC = cfg_.model_channels;
+    SDOD_REQUIRE(H >= 1 && Wd >= 1 && H <= 256 && Wd <= 256, "the hint encoder needs latent_h and latent_w in [1, 256]");
+    const int IH = 8 * H, IW = 8 * Wd;
+    const uint8_t* img_in = (const uint8_t*)io_alloc(inputs_, (size_t)B * IH * IW * 3);
+    f16* out = (f16*)io_alloc(outputs_, (size_t)B * H * Wd * MC * sizeof(f16));
+    static const int cpad[8] = {3, 64, 64, 64, 64, 128, 128, 256}; // input width of convolution j as built
+    static const int stride[8] = {1, 1, 2, 1, 2, 1, 2, 1};
+    const int w0 = P("input_hint_block.0.weight", {cpad[1], 3, 3, 3}, PK_CONV3_SMALL), b0 = P("input_hint_block.0.bias", {cpad[1]}, PK_VEC);
+    Act h = act(B, IH, IW, cpad[1]);
+    {
+        const f16* wp = W<f16>(w0);
+        const float* bp = W<float>(b0);
+        f16* hp = h.p;
+        const size_t cnt = h.numel();
+        const int c1 = cpad[1];
+        emit([=](hipStream_t st) { check_rc(sdod_image_conv_in_unit_f16(img_in, wp, bp, hp, nullptr, 0, B, IH, IW, c1, st)); }, "image_conv_in_unit",
+             2.0 * B * IH * IW * c1 * 64, (double)B * IH * IW * (3 + c1 * 2) + c1 * 64 * 2);
+        emit([=](hipStream_t st) { check_rc(sdod_act_f16(hp, hp, cnt, SDOD_ACT_SILU, st)); }, "silu", 0, (double)cnt * 4);
+    }
+    for (int j = 1; j < 8; ++j) {
+        const std::string pfx = "input_hint_block." + std::to_string(2 * j);
+        const int cout = j < 7 ? cpad[j + 1] : MC;
+        const int w = P(pfx + ".weight", {cout, cpad[j], 3, 3}, PK_CONV3), b = P(pfx + ".bias", {cout}, PK_VEC);
+        GemmOpt o; o.bias = b;
+        if (j < 7) o.act = SDOD_ACT_SILU;
+        else o.out = out;
+        Act y = conv(h, nullptr, w, cout, 3, stride[j], false, o);
+        release(h);
+        h = y;
+    }
+    if (mode_ != DECLARE) SDOD_REQUIRE(h.h == H && h.w == Wd, "hint size must be 8x the latent size");
+}
+
 // ------------------------------------------------------------------------------------------------ temb
 void Graph::build_temb() {
     // context.cpp:257-278 (sinusoid -> time MLP), extended by everything else that depends on t only: SiLU and the
     // emb_layers projection of all 22 ResBlocks, as ONE GEMM.  Output row = what the UNet graph consumes as in1.
     const int B = batch_, MC = cfg_.model_channels, EC = 4 * MC;
-    const auto blocks = unet_res_blocks();
+    const auto blocks = temb_blocks(); // (control_temb: a ControlNet checkpoint's own time_embed and its ten ResBlocks)
     int total = 0;
     for (auto& rb : blocks) total += rb.second;
     float* t_in = (float*)io_alloc(inputs_, (size_t)B * sizeof(float));

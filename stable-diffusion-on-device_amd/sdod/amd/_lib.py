@@ -102,6 +102,11 @@ class DenseConvDesc(ctypes.Structure):
                [(k, c_float) for k in ('alpha', 'slope', 'c1')]
 
 
+class ControlSeg(ctypes.Structure):
+    """mirror of `struct sdod_control_seg` (include/sdod_hip.h)"""
+    _fields_ = [('h', c_void_p), ('r', c_void_p), ('count', c_size_t)]
+
+
 def _declare(lib):
     P = c_void_p
     sig = {
@@ -145,6 +150,7 @@ def _declare(lib):
         'sdod_avg_pool2_f16': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
         'sdod_adapter_stage_f16': (c_int, [P, P, c_size_t, c_float, P]),
         'sdod_add_feature_f16': (c_int, [P, P, c_size_t, c_int, P]),
+        'sdod_add_control_f16': (c_int, [ctypes.POINTER(ControlSeg), c_int, P, P]),
         'sdod_im2col3x3_small_f16': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
         'sdod_im2col3x3_small_wrap_f16': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
         'sdod_latent_im2col_f16': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
@@ -195,6 +201,7 @@ HIP_SYMBOLS = [
     'sdod_nhwc_f16_to_nchw_f32', 'sdod_latent_prep_f16', 'sdod_embedding_f16', 'sdod_context_assemble_f16', 'sdod_timestep_features_f16', 'sdod_cfg_combine', 'sdod_stage_unet_inputs', 'sdod_randn_f32',
     'sdod_dpm_update', 'sdod_ddim_step_f32', 'sdod_lincomb4_f32', 'sdod_image_to_u8', 'sdod_hip_last_error',
     'sdod_hip_device_info', 'sdod_image_conv_in_unit_f16', 'sdod_dense_conv3x3_f16', 'sdod_dense_conv3x3_ok',
+    'sdod_add_control_f16',
 ]
 
 

@@ -11,6 +11,8 @@ step for the MI355X build.  It runs on a host without a GPU: the engine's parame
 
     python -m sdod.amd.convert --upscaler RealESRGAN_x4plus.pth --out models/          # upscaler.sdodw (Txt2Img(upscaler=True))
 
+    python -m sdod.amd.convert --controlnet control_v11p_sd15_canny.pth --out models/  # controlnet.sdodw (Txt2Img(controlnet=True))
+
 Only loaders that execute nothing from the file are used: safetensors, or torch.load(weights_only=True).
 """
 import argparse
@@ -257,6 +259,70 @@ def convert_upscaler(path, out_dir, dtype=torch.float16):
     return out
 
 
+def controlnet_tables(cfg=None):
+    """{'controlnet': ..., 'temb': ..., 'hint': ...}: the parameter tables of the three graphs a ControlNet checkpoint feeds (control
+    graph, control TEMB, hint encoder -- the last with its PADDED shapes); no device needed"""
+    cfg = E.copy_config(cfg or E.sd14_config())
+    tcfg = E.copy_config(cfg)
+    tcfg.control_temb = 1
+    return {'controlnet': E.ControlNet(cfg, 2).param_table(), 'temb': E.Temb(tcfg, 1).param_table(), 'hint': E.ControlHint(cfg, 1).param_table()}
+
+
+def controlnet_state_dict(sd):
+    """A ControlNet 1.0 / 1.1 state dict for SD 1.x in ldm's (cldm's) naming -> the same tensors with `control_model.` stripped;
+    entries outside that prefix (a full control_sd15_*.pth also carries the base model) are dropped.  Refused by name with ValueError:
+    diffusers-format keys (controlnet_cond_embedding.*, down_blocks.*), a context width other than 768 (an SD 2.x ControlNet), a hint
+    convolution that does not take 3 channels, anything without input_hint_block / zero_convs."""
+    keys = list(sd)
+    if any(k.startswith(('controlnet_cond_embedding.', 'down_blocks.', 'controlnet_down_blocks.', 'mid_block.')) for k in keys):
+        raise ValueError('diffusers-format ControlNet keys (controlnet_cond_embedding.*, down_blocks.*): convert the original '
+                         'lllyasviel .pth / .safetensors checkpoint (control_model.* names)')
+    if any(k.startswith('control_model.') for k in keys):
+        sd = {k[len('control_model.'):]: v for k, v in sd.items() if k.startswith('control_model.')}
+    if 'input_hint_block.0.weight' not in sd or 'zero_convs.0.0.weight' not in sd:
+        raise ValueError('not a ControlNet state dict: input_hint_block.0.weight / zero_convs.0.0.weight are missing')
+    kw = sd.get('input_blocks.1.1.transformer_blocks.0.attn2.to_k.weight')
+    if kw is None or int(kw.shape[1]) != 768:
+        raise ValueError(f'cross-attention context width {None if kw is None else int(kw.shape[1])}: only SD 1.x ControlNets (768) are supported')
+    hw = sd['input_hint_block.0.weight']
+    if hw.dim() != 4 or int(hw.shape[1]) != 3:
+        raise ValueError(f'input_hint_block.0.weight has shape {tuple(hw.shape)}: only 3-channel hints are supported')
+    return sd
+
+
+def controlnet_parameters(sd, dtype=torch.float16):
+    """a state dict as controlnet_state_dict takes it -> {name: tensor of `dtype`} for controlnet.sdodw: every tensor the three graphs
+    name, shapes checked against the checkpoint's own, the hint encoder's 16 / 32 / 96 channel widths zero-padded to the graph's
+    64 / 64 / 128"""
+    sd = controlnet_state_dict(sd)
+    tables = controlnet_tables()
+    want = dict(E.control_hint_checkpoint_table())
+    part = {}
+    for graph, table in tables.items():
+        for name, shape in table:
+            if name not in sd:
+                raise KeyError(f'{name} is missing from the ControlNet checkpoint')
+            t = sd[name]
+            ckpt_shape = want[name] if graph == 'hint' else tuple(shape)
+            if tuple(t.shape) != tuple(ckpt_shape):
+                raise ValueError(f'{name}: checkpoint shape {tuple(t.shape)} != expected {tuple(ckpt_shape)}')
+            if tuple(t.shape) != tuple(shape):          # (hint encoder: zero weights and zero bias in the padded channels)
+                padded = torch.zeros(tuple(shape), dtype=t.dtype)
+                padded[tuple(slice(0, n) for n in t.shape)] = t
+                t = padded
+            part[name] = t.to(dtype)
+    return part
+
+
+def convert_controlnet(path, out_dir, dtype=torch.float16):
+    """a ControlNet 1.0 / 1.1 SD 1.x checkpoint (.pth / .safetensors) -> out_dir/controlnet.sdodw; returns the file written"""
+    part = controlnet_parameters(read_checkpoint(path), dtype)
+    os.makedirs(out_dir, exist_ok=True)
+    out = os.path.join(out_dir, 'controlnet.sdodw')
+    weights.save(out, part)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     ap.add_argument('--ckpt', help='sd-v1-x .ckpt / .safetensors (ldm key names)')
@@ -264,6 +330,9 @@ def main(argv=None):
                                       'write adapter.sdodw (Txt2Img(adapter=True)); with or without --ckpt')
     ap.add_argument('--upscaler', help='an ESRGAN x4 RRDBNet checkpoint (ESRGAN_4x, RealESRGAN_x4plus, the 6-block anime model; basicsr or '
                                        'original ESRGAN key names): write upscaler.sdodw (Txt2Img(upscaler=True)); with or without --ckpt')
+    ap.add_argument('--controlnet', help='a ControlNet 1.0 / 1.1 checkpoint for SD 1.x (control_sd15_*.pth, control_v11*_sd15_*.pth / '
+                                         '.safetensors; control_model.* names): write controlnet.sdodw (Txt2Img(controlnet=True)); with or '
+                                         'without --ckpt')
     ap.add_argument('--out', required=True, help='models_dir to write')
     ap.add_argument('--fp32', action='store_true', help='keep fp32 payloads (the engine converts at load)')
     ap.add_argument('--model', default='sd14', choices=['sd14', 'sd21'], help='sd21: SD v2.x shapes and open_clip text-tower key names')
@@ -274,8 +343,8 @@ def main(argv=None):
     ap.add_argument('--tokenizer-vocab', help='bpe_simple_vocab_16e6.txt.gz, or a directory with HF vocab.json + merges.txt: '
                                               'also write ctokenizer.txt')
     a = ap.parse_args(argv)
-    if not a.ckpt and not a.adapter and not a.upscaler:
-        ap.error('one of --ckpt, --adapter and --upscaler is required')
+    if not a.ckpt and not a.adapter and not a.upscaler and not a.controlnet:
+        ap.error('one of --ckpt, --adapter, --upscaler and --controlnet is required')
     cfg = E.sd21_config() if a.model == 'sd21' else None
     if a.inpaint:
         cfg = cfg or E.sd14_config()
@@ -287,6 +356,8 @@ def main(argv=None):
         print('wrote', convert_adapter(a.adapter, a.out, torch.float32 if a.fp32 else torch.float16))
     if a.upscaler:
         print('wrote', convert_upscaler(a.upscaler, a.out, torch.float32 if a.fp32 else torch.float16))
+    if a.controlnet:
+        print('wrote', convert_controlnet(a.controlnet, a.out, torch.float32 if a.fp32 else torch.float16))
     if a.tokenizer_vocab:
         from . import tokenizer_file
         print('wrote', tokenizer_file.generate(a.tokenizer_vocab, os.path.join(a.out, 'ctokenizer.txt')))

@@ -9,7 +9,7 @@ import torch
 from . import _lib
 from ._lib import check
 
-UNET, VAE_DECODER, TEXT_ENCODER, TEMB, VAE_ENCODER, VAE_ENCODER_MASKED, ADAPTER, UPSCALER = 0, 1, 2, 3, 4, 5, 6, 7
+UNET, VAE_DECODER, TEXT_ENCODER, TEMB, VAE_ENCODER, VAE_ENCODER_MASKED, ADAPTER, UPSCALER, CONTROLNET, CONTROL_HINT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 
 
 class ModelConfig(ctypes.Structure):
@@ -26,7 +26,11 @@ class ModelConfig(ctypes.Structure):
     # Seamless tiling (the `wrap` argument of sdod_graph_create_wrap, which also travels next to the struct): bit 0 = the x axis wraps,
     # bit 1 = the y axis wraps; read by UNet and VaeDecoder only, 0 = the plain graphs through the old creation entry points.
     tiling = 0
-    _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'tiling')
+    # ControlNet (`struct sdod_control_config`, next to the struct like the others): control_inputs = 1 gives a UNet the 13 residual
+    # inputs and control_scale, control_temb = 1 makes a Temb the time conditioning of a ControlNet graph; 0 = the plain graphs.
+    control_inputs = 0
+    control_temb = 0
+    _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'tiling', 'control_inputs', 'control_temb')
 
     @classmethod
     def from_buffer_copy(cls, source, offset=0):
@@ -41,6 +45,11 @@ class ModelConfig(ctypes.Structure):
 class AdapterConfig(ctypes.Structure):
     """mirror of `struct sdod_adapter_config`"""
     _fields_ = [(n, ctypes.c_int) for n in ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks')]
+
+
+class ControlConfig(ctypes.Structure):
+    """mirror of `struct sdod_control_config`"""
+    _fields_ = [(n, ctypes.c_int) for n in ('control_inputs', 'control_temb')]
 
 
 class UpscalerConfig(ctypes.Structure):
@@ -74,6 +83,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_set_param', 'sdod_graph_param_device', 'sdod_graph_load_file', 'sdod_graph_finalize', 'sdod_graph_io', 'sdod_graph_execute', 'sdod_graph_check',
     'sdod_graph_stats', 'sdod_graph_tune_info', 'sdod_graph_num_ops', 'sdod_graph_op_info', 'sdod_graph_op_detail', 'sdod_graph_profile',
     'sdod_graph_keep_base', 'sdod_graph_base_bytes', 'sdod_graph_set_loras', 'sdod_graph_create_upscaler',
+    'sdod_graph_create_control', 'sdod_graph_bind_output',
 ]
 
 
@@ -89,6 +99,8 @@ def _engine():
         lib.sdod_graph_create_ex.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(AdapterConfig), I]
         lib.sdod_graph_create_wrap.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(AdapterConfig), I, I]
         lib.sdod_graph_create_upscaler.argtypes = [ctypes.POINTER(P), ctypes.POINTER(UpscalerConfig), I]
+        lib.sdod_graph_create_control.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(ControlConfig), I]
+        lib.sdod_graph_bind_output.argtypes = [P, I, P, ctypes.c_size_t]
         lib.sdod_graph_destroy.argtypes = [P]
         lib.sdod_graph_num_params.argtypes = [P]
         lib.sdod_graph_param_info.argtypes = [P, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I), ctypes.POINTER(ctypes.c_int64)]
@@ -158,8 +170,14 @@ class Graph:
         self.kind, self.cfg, self.batch = kind, cfg, batch
         self.device = torch.device(device)
         acfg = AdapterConfig(*(int(getattr(cfg, n, 0)) for n, _ in AdapterConfig._fields_))
+        ccfg = ControlConfig(int(getattr(cfg, 'control_inputs', 0)) if kind == UNET else 0, int(getattr(cfg, 'control_temb', 0)) if kind == TEMB else 0)
+        control = kind in (CONTROLNET, CONTROL_HINT) or ccfg.control_inputs or ccfg.control_temb
+        if control and (wrap or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_)):
+            raise ValueError('a ControlNet graph, or a UNet with control inputs, takes neither tiling nor a T2I-Adapter configuration')
         with self._on_device():
-            if kind == UPSCALER:    # its configuration is the UpscalerConfig itself; no ModelConfig field applies
+            if control:             # the ControlNet kinds and switches have an entry point of their own; without them nothing changes
+                check(self._lib.sdod_graph_create_control(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(ccfg), batch))
+            elif kind == UPSCALER:    # its configuration is the UpscalerConfig itself; no ModelConfig field applies
                 check(self._lib.sdod_graph_create_upscaler(ctypes.byref(self._h), ctypes.byref(cfg), batch))
             elif wrap is not None:
                 check(self._lib.sdod_graph_create_wrap(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(acfg), int(wrap), batch))
@@ -263,6 +281,14 @@ class Graph:
             check(self._lib.sdod_graph_set_loras(self._h, arr, len(entries),
                                                  ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if torch.cuda.is_available() else None)))
 
+    def bind_output(self, index, tensor):
+        """before finalize(): output `index` is written straight into `tensor` (device memory of the same size that outlives the
+        graph, typically an input slot of another graph) instead of a slot of this graph's own"""
+        if not tensor.is_cuda or not tensor.is_contiguous():
+            raise ValueError('a bound output must be a contiguous device tensor')
+        self._bound = getattr(self, '_bound', []) + [tensor]      # keep it alive as long as the graph
+        check(self._lib.sdod_graph_bind_output(self._h, int(index), ctypes.c_void_p(tensor.data_ptr()), tensor.numel() * tensor.element_size()))
+
     def _io(self, is_out, idx):
         p = ctypes.c_void_p(); n = ctypes.c_size_t()
         check(self._lib.sdod_graph_io(self._h, 1 if is_out else 0, idx, ctypes.byref(p), ctypes.byref(n)))
@@ -340,6 +366,74 @@ class UNet(Graph):
         if reps > 0:                # T2I-Adapter: four feature slots behind the other inputs, zero until something is staged into them
             first = 4 if c.concat_channels > 0 else 3
             self.adapter_feat = [self.io_tensor(False, first + k, shape, torch.float16) for k, shape in enumerate(adapter_feature_shapes(c, b // reps))]
+        if int(getattr(c, 'control_inputs', 0)):   # ControlNet: 13 residual slots and their scales, zero until a ControlNet graph fills them
+            first = 4 if c.concat_channels > 0 else 3
+            self.control_res = [self.io_tensor(False, first + k, shape, torch.float16) for k, shape in enumerate(control_residual_shapes(c, b))]
+            self.control_scale = self.io_tensor(False, first + 13, (13,), torch.float32)
+        return self
+
+
+def control_residual_shapes(cfg, batch):
+    """the 13 ControlNet residuals of `batch` UNet rows, NHWC, in skip order: (H / s, W / s, m MC) for (s, m) = (1, 1) x3, (2, 1),
+    (2, 2) x2, (4, 2), (4, 4) x2, (8, 4) x3, and (8, 4) for the middle block's output"""
+    mc = cfg.model_channels
+    sm = [(1, 1)] * 3 + [(2, 1)] + [(2, 2)] * 2 + [(4, 2)] + [(4, 4)] * 2 + [(8, 4)] * 4
+    return [(batch, cfg.latent_h // s, cfg.latent_w // s, m * mc) for s, m in sm]
+
+
+def control_hint_checkpoint_table(model_channels=320):
+    """(name, shape) of input_hint_block.* as a ControlNet CHECKPOINT holds them (the ControlHint graph's own table lists the padded
+    shapes): eight 3x3 convolutions 3 -> 16 -> 16 -> 32 -> 32 -> 96 -> 96 -> 256 -> model_channels at indices 0, 2, .., 14"""
+    widths = [3, 16, 16, 32, 32, 96, 96, 256, model_channels]
+    out = []
+    for j in range(8):
+        out += [(f'input_hint_block.{2 * j}.weight', (widths[j + 1], widths[j], 3, 3)), (f'input_hint_block.{2 * j}.bias', (widths[j + 1],))]
+    return out
+
+
+class ControlNet(Graph):
+    """ldm's cldm.ControlNet for SD 1.x (ControlNet 1.0 / 1.1 checkpoints, `control_model.` stripped): x, temb (a control Temb's
+    output), ctx and the guided hint (a ControlHint's output, one per image, shared by the two guidance halves of the batch) -> the 13
+    residuals of control_residual_shapes.  bind_output(k, unet.control_res[k]) before finalize() makes it write a UNet's slots."""
+
+    def __init__(self, cfg, batch, device='cuda:0'):
+        super().__init__(CONTROLNET, cfg, batch, device)
+
+    def finalize(self):
+        super().finalize()
+        c, b = self.cfg, self.batch
+        self.x = self.io_tensor(False, 0, (b, c.latent_channels, c.latent_h, c.latent_w), torch.float32)
+        self.temb_width = self._io(False, 1)[1] // (2 * b)
+        self.temb = self.io_tensor(False, 1, (b, self.temb_width), torch.float16)
+        self.ctx = self.io_tensor(False, 2, (b, c.context_len, c.context_dim), torch.float16)
+        self.hint = self.io_tensor(False, 3, (b // 2, c.latent_h, c.latent_w, c.model_channels), torch.float16)
+        self.out = [self.io_tensor(True, k, shape, torch.float16) for k, shape in enumerate(control_residual_shapes(c, b))]
+        return self
+
+
+class ControlHint(Graph):
+    """cldm's input_hint_block: uint8 hint [B, 8H, 8W, 3] -> the guided hint, fp16 NHWC [B, H, W, MC].  The graph is built with the
+    16 / 32 / 96 channel widths zero-padded to 64 / 64 / 128 and its parameter table lists those shapes; set_param pads a checkpoint
+    tensor of the original shape with zeros (exact: the padded channels stay zero).  One execute per hint image."""
+
+    def __init__(self, cfg, batch, device='cuda:0'):
+        super().__init__(CONTROL_HINT, cfg, batch, device)
+        self._shapes = dict(self.param_table())
+
+    def set_param(self, name, tensor):
+        want = self._shapes.get(name)
+        if want is not None and torch.is_tensor(tensor) and tuple(tensor.shape) != want and tensor.dim() == len(want) \
+                and all(a <= b for a, b in zip(tensor.shape, want)):
+            padded = torch.zeros(want, dtype=tensor.dtype)
+            padded[tuple(slice(0, n) for n in tensor.shape)] = tensor.detach().cpu()
+            tensor = padded
+        super().set_param(name, tensor)
+
+    def finalize(self):
+        super().finalize()
+        c, b = self.cfg, self.batch
+        self.hint = self.io_tensor(False, 0, (b, 8 * c.latent_h, 8 * c.latent_w, 3), torch.uint8)
+        self.out = self.io_tensor(True, 0, (b, c.latent_h, c.latent_w, c.model_channels), torch.float16)
         return self
 
 

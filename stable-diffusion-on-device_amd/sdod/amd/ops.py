@@ -449,6 +449,25 @@ def add_feature(h, f, reps):
     return h
 
 
+def add_control(hs, rs, scales):
+    """hs[k] += scales[k] * rs[k] in place for up to 16 fp16 tensor pairs in ONE launch (sdod_add_control_f16: the launch a UNet
+    graph with ControlNet inputs makes behind its middle block).  scales: fp32 device tensor [len(hs)], read by the kernel; a segment
+    whose scale is exactly 0 is neither read nor written.  The pointer and size checks are the library's."""
+    lib = _lib.hip()
+    if len(hs) != len(rs):
+        raise ValueError(f'{len(hs)} destinations but {len(rs)} residuals')
+    for k, (h, r) in enumerate(zip(hs, rs)):
+        _req(h, torch.float16, f'hs[{k}]'); _req(r, torch.float16, f'rs[{k}]')
+        if h.numel() != r.numel():
+            raise ValueError(f'segment {k}: {tuple(h.shape)} and {tuple(r.shape)} differ in size')
+    _req(scales, torch.float32, 'scales')
+    if scales.numel() != len(hs):
+        raise ValueError(f'{len(hs)} segments need {len(hs)} scales, got {scales.numel()}')
+    segs = (_lib.ControlSeg * max(len(hs), 1))(*[_lib.ControlSeg(h.data_ptr(), r.data_ptr(), h.numel()) for h, r in zip(hs, rs)])
+    check(lib.sdod_add_control_f16(segs, len(hs), _p(scales), _stream()))
+    return hs
+
+
 def concat_channels(a, b):
     lib = _lib.hip()
     _req(a, torch.float16, 'a'); _req(b, torch.float16, 'b')

@@ -32,6 +32,10 @@ class Txt2Img:
     _loras = False
     hires = None        # the second pipeline of the hires pass (Txt2Img(..., hires_hw=)), or None
     adapter = None      # the T2I-Adapter graph (Txt2Img(..., adapter=True)), or None
+    controlnet = None   # the ControlNet graph (Txt2Img(..., controlnet=True)), or None; control_hint: its hint encoder
+    control_hint = None
+    _control_on = False         # a hint is set: every evaluation runs the control graph in front of the UNet
+    _control_ctx_fresh = True   # the control graph's own static-unchanged state
     adapter_channels = 3
     upscaler = None     # the ESRGAN x4 upscaler (Txt2Img(..., upscaler=True): sdod.amd.upscale.Upscaler), or None
     tiling = 0          # seamless tiling: the wrap bits the UNet and the VAE decoder were built with (bit 0 = x, bit 1 = y)
@@ -39,7 +43,7 @@ class Txt2Img:
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
-                 adapter_channels=3, tiling=False, upscaler=False):
+                 adapter_channels=3, tiling=False, upscaler=False, controlnet=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -84,10 +88,20 @@ class Txt2Img:
         sdod.amd.upscale.Upscaler built from state_dicts['upscaler'] or models_dir/upscaler.sdodw at this pipeline's image size -- with
         hires_hw at the hires image size -- for upscale(), generate_upscaled() and generate_upscaled_graphed().  Its memory:
         upscaler.graph.stats().  Off, nothing is constructed or sized differently.  Not with tiling (the upscaler's border is not
-        circular) or an image side above 1024 px: ValueError before any device work (upscaler_check_build)."""
+        circular) or an image side above 1024 px: ValueError before any device work (upscaler_check_build).
+
+        controlnet=True: structural control by a ControlNet (the SD 1.x ControlNet 1.0 / 1.1 checkpoints: canny, depth, openpose,
+        scribble, softedge, lineart, seg, normalbae, mlsd; INTEGRATION.md "Structural control (ControlNet)").  The UNet graph gets 13
+        residual inputs and their scales (unet.control_res, unet.control_scale: zero until a hint is set) and one more launch;
+        self.controlnet = E.ControlNet(cfg, 2 n) writes those inputs directly (its outputs are bound to them), self.control_hint =
+        E.ControlHint(cfg, 1) encodes one hint image per run.  All three take their weights from state_dicts['controlnet'] (one dict,
+        `control_model.` stripped) or models_dir/controlnet.sdodw: set_control_hint() / clear_control_hint().  Off, nothing is
+        constructed or sized differently.  Not with cfg_split, hires_hw, inpaint_unet, adapter, tiling or model='sd21': ValueError
+        before any device work (control_check_build).  LoRA adapters re-weight the UNet, not the ControlNet."""
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         latent_h, latent_w = check_latent_hw(latent_hw)
         adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_unet, model)
+        control_check_build(controlnet, cfg_split, hires_hw, inpaint_unet, adapter, tiling, model)
         self.tiling = tiling_check_build(tiling, with_vae_encoder, inpaint_unet, hires_hw, adapter)
         up_args = upscaler_check_build(upscaler, tiling, hires_hw if hires_hw is not None else latent_hw, state_dicts, models_dir)
         if hires_hw is not None:
@@ -137,6 +151,9 @@ class Txt2Img:
             unet_cfg = E.copy_config(unet_cfg)
             unet_cfg.adapter_reps = 2
             self.adapter_channels = int(adapter_channels)
+        if controlnet:                   # 13 residual slots and their scales, filled by the control graph built below
+            unet_cfg = E.copy_config(unet_cfg)
+            unet_cfg.control_inputs = 1
         vae_cfg = self.cfg
         if self.tiling:                  # the UNet and the VAE decoder take the circular border; every other graph has no border to wrap
             unet_cfg, vae_cfg = E.copy_config(unet_cfg), E.copy_config(self.cfg)
@@ -162,6 +179,20 @@ class Txt2Img:
             if loras and (g is self.unet or g is self.text):
                 g.keep_base()
             g.finalize()
+        if controlnet:
+            # the control graph sees the UNet's context length; its 13 outputs ARE the UNet's residual inputs (no copy per step)
+            ccfg = E.copy_config(unet_cfg)
+            ccfg.control_inputs, ccfg.weight_quant = 0, 0       # (a ControlNet's weights are always fp16)
+            self.controlnet = E.ControlNet(ccfg, 2 * self.n, device)
+            self.control_hint = E.ControlHint(ccfg, 1, device)
+            for g in (self.controlnet, self.control_hint):
+                self._load(g, 'controlnet', 'controlnet')
+            for k, slot in enumerate(self.unet.control_res):
+                self.controlnet.bind_output(k, slot)
+            self.controlnet.finalize()
+            self.control_hint.finalize()
+            self._temb_stage = torch.zeros((self.unet.batch, self.unet.temb_width + self.controlnet.temb_width), dtype=torch.float16,
+                                           device=self.device)
         if up_args is not None:
             self.upscaler = UP.Upscaler(device=device, use_hip_graph=use_hip_graph, **up_args)
         self._loras = bool(loras)
@@ -244,6 +275,37 @@ class Txt2Img:
             self.adapter.execute(self.use_hip_graph)
             for out, slot in zip(self.adapter.out, self.unet.adapter_feat):
                 ops.adapter_stage(out, slot[i:i + 1], weight)
+
+    # ------------------------------------------------------------------ ControlNet
+    def _require_controlnet(self):
+        if self.controlnet is None:
+            raise RuntimeError('this pipeline was built without controlnet=True: Txt2Img(..., controlnet=True) is needed for ControlNet')
+
+    def set_control_hint(self, hint_u8, weight=1.0):
+        """hint_u8: uint8 [n, 8h, 8w, 3] ([n, 8h, 8w] is expanded to three equal channels) -- the preprocessed control image (edge
+        map, depth map, pose skeleton, ...), one per image of the pipeline's batch; the caller makes it (no preprocessor here).
+        weight: a finite float, or 13 finite floats, one per residual in skip order with the middle block's last (the front ends'
+        control weight; cldm's control_scales).  Runs the hint encoder once per image into the control graph's guided-hint slot and
+        writes the 13 scales; from then on every evaluation runs the control graph in front of the UNet, on both guidance halves,
+        until clear_control_hint().  Slots and scales are fixed memory read by the launches: a captured trajectory picks up a new
+        hint or weight without a new capture.  All scales 0.0 still runs the control graph and adds nothing.  ValueError for a wrong
+        shape or dtype or a non-finite weight (control_check_args), before any device work; RuntimeError without controlnet=True."""
+        self._require_controlnet()
+        hint_u8, scales = control_check_args(hint_u8, weight, self._latent_shape, self.n)
+        hint_u8 = hint_u8.to(self.device)
+        for i in range(self.n):
+            self.control_hint.hint.copy_(hint_u8[i:i + 1])
+            self.control_hint.execute(self.use_hip_graph)
+            self.controlnet.hint[i:i + 1].copy_(self.control_hint.out)
+        self.unet.control_scale.copy_(torch.tensor(scales, dtype=torch.float32))
+        self._control_on = True
+
+    def clear_control_hint(self):
+        """no control: the scales are zeroed (the UNet's one extra launch then reads and writes nothing) and the control graph is
+        no longer executed, eager or captured -- the plain pipeline's images, bit for bit"""
+        self._require_controlnet()
+        self.unet.control_scale.zero_()
+        self._control_on = False
 
     def clear_adapter_hint(self):
         """zero the UNet's feature slots: the unconditioned model again (its additions of zero change no bit)"""
@@ -351,8 +413,29 @@ class Txt2Img:
                 self._temb_graphs[len(key)] = g
             g.t.copy_(torch.tensor(key, dtype=torch.float32))
             g.execute()
-            self._temb_cache[key] = g.out.clone()
+            if self.controlnet is None:
+                self._temb_cache[key] = g.out.clone()
+            else:
+                # a ControlNet has a time MLP of its own: its columns ride behind the UNet's in the same row, so that every sampler
+                # keeps its indexing and its one staging launch (_temb_dst); _unet_eps hands each graph its part
+                cg = self._temb_graphs.get(('control', len(key)))
+                if cg is None:
+                    ccfg = E.copy_config(self.cfg)
+                    ccfg.control_temb, ccfg.weight_quant = 1, 0
+                    cg = E.Temb(ccfg, len(key), self.device)
+                    self._load(cg, 'controlnet', 'controlnet')
+                    cg.finalize()
+                    self._temb_graphs[('control', len(key))] = cg
+                cg.t.copy_(g.t)
+                cg.execute()
+                self._temb_cache[key] = torch.cat([g.out, cg.out], dim=1)
         return self._temb_cache[key]
+
+    @property
+    def _temb_dst(self):
+        """where the samplers stage an evaluation's time row: the UNet's slot, or -- with a ControlNet, whose columns ride in the same
+        row -- the pipeline's wider buffer that _unet_eps splits between the two graphs"""
+        return self.unet.temb if self.controlnet is None else self._temb_stage
 
     # ------------------------------------------------------------------ one guided eps evaluation
     def _require_cond(self):
@@ -369,6 +452,9 @@ class Txt2Img:
         else:
             self.unet.ctx[:n].copy_(ctx2[0:1].expand(n, -1, -1))
             self.unet.ctx[n:].copy_(ctx2[1:2].expand(n, -1, -1))
+        if self.controlnet is not None:
+            self.controlnet.ctx.copy_(self.unet.ctx)
+            self._control_ctx_fresh = True
         self._ctx_fresh = True     # the next UNet execute must redo the cross-attention K/V projections
 
     def _exchange_halves(self, mine):
@@ -385,6 +471,15 @@ class Txt2Img:
 
     def _unet_eps(self):
         """one UNet evaluation of the staged inputs: the fp16 prediction [2n, H, W, 4] = (uncond rows ; cond rows)"""
+        if self.controlnet is not None:
+            w = self.unet.temb_width
+            self.unet.temb.copy_(self._temb_stage[:, :w])
+            if self._control_on:         # control first: its 13 outputs are the UNet's residual inputs
+                cn = self.controlnet
+                cn.x.copy_(self.unet.x)
+                cn.temb.copy_(self._temb_stage[:, w:])
+                cn.execute(self.use_hip_graph, static_unchanged=not self._control_ctx_fresh)
+                self._control_ctx_fresh = False
         self.unet.execute(self.use_hip_graph, static_unchanged=not self._ctx_fresh)
         self._ctx_fresh = False
         return self._exchange_halves(self.unet.eps) if self.cfg_split else self.unet.eps
@@ -393,7 +488,7 @@ class Txt2Img:
         """x: fp32 [n,4,H,W]; returns guided eps fp32 [n,4,H,W].  Batch rows: [uncond x n ; cond x n] (ldm order).
         v_coef = (sqrt(abar_t), sqrt(1 - abar_t)) for a v-prediction model: the guided output is v, eps follows from it."""
         # one in-tree launch stages the graph inputs: x repeated for the (uncond, cond) halves, the time row for every batch row
-        ops.stage_unet_inputs(x, self.unet.x, temb_row, self.unet.temb)
+        ops.stage_unet_inputs(x, self.unet.x, temb_row, self._temb_dst)
         out = ops.cfg_combine(self._unet_eps(), guidance, uncond_first=True, mode=mode)
         if v_coef is not None:
             out = ops.lincomb4([out, x], [v_coef[0], v_coef[1]], 1.0)
@@ -415,11 +510,11 @@ class Txt2Img:
                 # steps 2..: stage (unless done) -> UNet -> ONE launch for guidance, the multistep combination, the DDIM update
                 # and the staging of the next evaluation's inputs (ops.plms_update = the four separate launches, bit for bit)
                 if not staged:
-                    ops.stage_unet_inputs(x, self.unet.x, temb[index], self.unet.temb)
+                    ops.stage_unet_inputs(x, self.unet.x, temb[index], self._temb_dst)
                 eps = self._unet_eps()
                 k = min(len(old), 3)
                 coefs, div = PLMS_ORDERS[k]
-                nxt_stage = (self.unet.x, temb[index - 1], self.unet.temb) if i + 1 < n_steps else None
+                nxt_stage = (self.unet.x, temb[index - 1], self._temb_dst) if i + 1 < n_steps else None
                 e_t = ops.plms_update(eps, x, old[::-1][:k], coefs, div, sch.coef(index), guidance, mode=1, v_coef=vc, stage=nxt_stage)
                 staged = nxt_stage is not None
                 old.append(e_t)
@@ -451,10 +546,10 @@ class Txt2Img:
         y_prev = torch.zeros_like(x)
         # one staging launch in front of the loop; every step is then the UNet replay + ONE launch (guidance, solver update and the
         # staging of the next step's inputs: ops.dpm_step = cfg_combine + dpm_update + stage_unet_inputs, bit for bit)
-        ops.stage_unet_inputs(x, self.unet.x, temb[0], self.unet.temb)
+        ops.stage_unet_inputs(x, self.unet.x, temb[0], self._temb_dst)
         for s in range(steps):
             ops.dpm_step(self._unet_eps(), x, y_prev, solver.coef(s), guidance, mode=0,
-                         stage=(self.unet.x, temb[s + 1], self.unet.temb) if s + 1 < steps else None)
+                         stage=(self.unet.x, temb[s + 1], self._temb_dst) if s + 1 < steps else None)
         return x
 
     def sample_k(self, ctx2, x, sampler, steps=20, guidance=7.5, schedule='discrete', eta=1.0, first=0, seed=0, image_index=0,
@@ -476,13 +571,13 @@ class Txt2Img:
             step_noise = step_noise.to(self.device, torch.float32).contiguous()
         den_prev = torch.empty_like(x) if sampler == 'dpmpp_2m' else None
         ops.k_step(None, x, dict(a=float(sch.sigmas[0]) if first == 0 else 1.0, stage_scale=sch.c_in(first)),
-                   stage=(self.unet.x, temb[first], self.unet.temb))
+                   stage=(self.unet.x, temb[first], self._temb_dst))
         for i in range(first, steps):
             cf = sch.coef(sampler, i, eta, self.v_prediction, first)
             ops.k_step(self._unet_eps(), x, cf, guidance, den_prev=den_prev,
                        noise=step_noise[i - first] if step_noise is not None and cf['u'] != 0.0 else None,
                        seed=seed, noise_level=i, image_index=image_index, mode=1,
-                       stage=(self.unet.x, temb[i + 1], self.unet.temb) if i + 1 < steps else None)
+                       stage=(self.unet.x, temb[i + 1], self._temb_dst) if i + 1 < steps else None)
         return x
 
     def _sample(self, sampler, ctx2, x_T, steps, guidance, *, schedule='discrete', eta=1.0, seed=0, image_index=0, step_noise=None):
@@ -544,6 +639,8 @@ class Txt2Img:
         Returns the cached (graph, statics, out); the caller (_replay) fills the statics, then replays."""
         if self._traj is None:
             self._traj = {}
+        if self._control_on:                    # a capture made with the control graph in it is another trajectory than one without
+            key = (key, 'control')
         if key not in self._traj:
             statics = [torch.zeros(tuple(shape), dtype=dtype, device=self.device) for shape, dtype in inputs]
             pipes = [self] if self.hires is None else [self, self.hires]
@@ -747,13 +844,13 @@ class Txt2Img:
         temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
         self._set_context(ctx2)
         x = x.to(self.device, torch.float32).clone()
-        ops.stage_unet_inputs(x, self.unet.x, temb[t_enc - 1], self.unet.temb)
+        ops.stage_unet_inputs(x, self.unet.x, temb[t_enc - 1], self._temb_dst)
         for index, j, sa, s1a in inpaint_levels(sch, t_enc):
             ops.ddim_inpaint_step(self._unet_eps(), x, sch.coef(index), guidance, z0=z0, keep=keep, known=None if j is None else (sa, s1a),
                                   noise=None if j is None or step_noise is None else step_noise[j],
                                   seed=seed, noise_level=j or 0, image_index=image_index, mode=1,
                                   v_coef=sch.v_to_eps_coef(index) if self.v_prediction else None,
-                                  stage=None if j is None else (self.unet.x, temb[j], self.unet.temb))
+                                  stage=None if j is None else (self.unet.x, temb[j], self._temb_dst))
             if trace is not None:
                 trace.append((int(sch.timesteps[index]), index))
         return x
@@ -1040,6 +1137,39 @@ def adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_
     for name, on in (('cfg_split', cfg_split), ('hires_hw', hires_hw is not None), ('inpaint_unet', inpaint_unet), ("model='sd21'", model == 'sd21')):
         if on:
             raise ValueError(f'adapter=True cannot be combined with {name}')
+
+
+def control_check_build(controlnet, cfg_split, hires_hw, inpaint_unet, adapter, tiling, model):
+    """Txt2Img's controlnet=True: none of cfg_split, hires_hw, inpaint_unet, adapter, tiling, model='sd21' (each would need the
+    residual slots or the control graph in a second place, or a checkpoint family that does not exist for it).  Raises ValueError;
+    needs no device."""
+    if not controlnet:
+        return
+    for name, on in (('cfg_split', cfg_split), ('hires_hw', hires_hw is not None), ('inpaint_unet', inpaint_unet), ('adapter', adapter),
+                     ('tiling', tiling not in (False, None, 0)), ("model='sd21'", model == 'sd21')):
+        if on:
+            raise ValueError(f'controlnet=True cannot be combined with {name}')
+
+
+def control_check_args(hint_u8, weight, latent, n_images):
+    """the argument contract of Txt2Img.set_control_hint, checked on the host before any device work.  Returns (hint uint8
+    [n, 8h, 8w, 3] contiguous, the 13 scales as floats); raises ValueError."""
+    _, h, w = latent
+    if not torch.is_tensor(hint_u8) or hint_u8.dtype != torch.uint8:
+        raise ValueError('hint_u8 must be a uint8 tensor')
+    if hint_u8.dim() == 3:
+        hint_u8 = hint_u8[..., None].expand(-1, -1, -1, 3)
+    if tuple(hint_u8.shape) != (n_images, 8 * h, 8 * w, 3):
+        raise ValueError(f'hint_u8 must be [{n_images}, {8 * h}, {8 * w}, 3] (or without the channel axis), got {tuple(hint_u8.shape)}')
+    if isinstance(weight, (bool, str)):
+        raise ValueError(f'weight must be a finite number or 13 of them, got {weight!r}')
+    try:
+        scales = [float(weight)] * 13 if np.isscalar(weight) else [float(v) for v in weight]
+    except (TypeError, ValueError):
+        raise ValueError(f'weight must be a finite number or 13 of them, got {weight!r}') from None
+    if len(scales) != 13 or not all(np.isfinite(v) for v in scales):
+        raise ValueError(f'weight must be a finite number or 13 of them (one per residual), got {weight!r}')
+    return hint_u8.contiguous(), scales
 
 
 def upscaler_check_build(upscaler, tiling, latent_hw, state_dicts, models_dir):
