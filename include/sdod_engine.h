@@ -177,6 +177,16 @@ typedef struct sdod_control_config {
     int control_temb;   /* TEMB graph: 1 = the time conditioning of a CONTROLNET graph ([B][30 MC]); 0 = the UNet's */
 } sdod_control_config;
 SDOD_API int sdod_graph_create_control(void** graph, int kind, const sdod_model_config* cfg, const sdod_control_config* control, int batch);
+/* Regional prompts, UNET graph only.  cfg->context_len must be 77 * regions: in2 holds, per image, the encodings of
+ * `regions` prompts one behind the other.  Behind every other input the graph gets four inputs region_w[level], fp32
+ * [H / ds * W / ds][regions] for ds = 1, 2, 4, 8 (what sdod_region_weights_f32 writes), shared by all images of the batch and
+ * "region 0 everywhere" after finalize.  Every cross-attention computes sum_r w_r(pixel) attn(x, ctx[:, 77 r : 77 r + 77]); the
+ * weights are read by the kernels in the launch, so a captured graph picks up new ones.  regions in [2, 4]; no weight_quant and no
+ * concat_channels.  The other create functions build exactly what they built before. */
+typedef struct sdod_region_config {
+    int regions; /* prompts per image */
+} sdod_region_config;
+SDOD_API int sdod_graph_create_regions(void** graph, int kind, const sdod_model_config* cfg, const sdod_region_config* regions, int batch);
 /* Before sdod_graph_finalize: output `index` of the graph is written to device_ptr (memory the caller owns, typically an input slot
  * of another graph, so that nothing is copied between the two per run) instead of a slot the graph allocates.  bytes must equal the
  * output's size and device_ptr be 256-byte aligned, else INVALID_ARGUMENT.  sdod_graph_io then reports device_ptr.  Unbound outputs

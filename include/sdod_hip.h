@@ -135,6 +135,13 @@ typedef struct sdod_gemm_desc {
 } sdod_gemm_desc;
 
 SDOD_API int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream);
+/* Regional prompts: the score GEMM of the folded cross-attention with its 80-column groups laid out as
+ * [region][head][80].  Plans and computes exactly as sdod_gemm_f16; in the softmax epilogue the probabilities of group g of row m are
+ * multiplied by region_w[(m % rows_per_img) * regions + g / (N / 80 / regions)] (fp32 [rows_per_img][regions], read by the kernel in
+ * the launch: a captured graph picks up new values).  The weight goes into the reciprocal of the group's sum, so weight 1.0 leaves
+ * every bit as sdod_gemm_f16 writes it and weight 0 gives exact zeros.  Needs softmax_cols == 80, w_img_stride != 0 (with it
+ * rows_per_img % 32 == 0), N % (80 * regions) == 0 and regions in [1, 4]; anything else is INVALID_ARGUMENT with nothing written. */
+SDOD_API int sdod_gemm_region_f16(const sdod_gemm_desc* d, const void* region_w, int regions, void* stream);
 /* 1 when the call above reduces its split-K slices inside the GEMM launch (see fix_counters), else 0 */
 SDOD_API int sdod_gemm_fixup(const sdod_gemm_desc* d);
 /* counter words a fix_counters buffer must hold for any descriptor (one per output tile; 64 Ki covers M*N up to 2^28 at 64x64) */
@@ -278,6 +285,14 @@ SDOD_API int sdod_xattn_fold_f16(const void* kv, int ld_kv, int k_off, int v_off
                                  const void* sq, const void* tq, const void* wo, int ldwo, int heads, int d, float scale, void* w1,
                                  void* s1, void* t1, void* w2, void* stream);
 
+/* The same for regional prompts: kv holds n_img * regions segments of L rows (image-major), one per (image, region prompt).  w1 /
+ * s1 / t1 are what the call above writes for n_img * regions images, bit for bit: for image b, [regions][heads*80] rows.  w2 for
+ * image b is [C][regions * heads*80] -- region r's columns at r * heads*80, each slice what the call above writes -- so the
+ * second GEMM sums over regions through its K axis.  regions in [1, 4]; 1 is the call above. */
+SDOD_API int sdod_xattn_fold_regions_f16(const void* kv, int ld_kv, int k_off, int v_off, int n_img, int regions, int L, const void* wq,
+                                         int ldq, const void* sq, const void* tq, const void* wo, int ldwo, int heads, int d, float scale,
+                                         void* w1, void* s1, void* t1, void* w2, void* stream);
+
 /* Row softmax on fp16 [M][N] in place semantics allowed (y may equal x); fp32 math. */
 SDOD_API int sdod_softmax_rows_f16(const void* x, void* y, int m, int n, void* stream);
 
@@ -285,6 +300,18 @@ SDOD_API int sdod_softmax_rows_f16(const void* x, void* y, int m, int n, void* s
 SDOD_API int sdod_geglu_f16(const void* x, void* y, int m, int c, void* stream); /* x:[M][2c] -> y = x[:, :c]*gelu(x[:, c:]) */
 SDOD_API int sdod_act_f16(const void* x, void* y, size_t n, int act, void* stream);
 SDOD_API int sdod_add_f16(const void* a, const void* b, void* y, size_t n, void* stream);
+/* ---- Regional prompts.  Region masks -> per-pixel blend weights of the four UNet levels, one launch.
+ * masks: uint8 [regions][8 h][8 w] at image resolution (255 = fully inside; soft and overlapping masks allowed), h x w the latent
+ * size, both multiples of 8.  For ds = 1, 2, 4, 8: s_r = the integer sum of mask r over the (8 ds)^2 image pixels of a level pixel,
+ * w_r = (float)s_r / (float)sum_r s_r (one correctly rounded division); where no region covers the pixel w_0 = 1, the others 0.
+ * w1 / w2 / w4 / w8: fp32 [h / ds * w / ds][regions], row-major in pixels.  regions in [1, 4], masks 16-byte aligned. */
+SDOD_API int sdod_region_weights_f32(const uint8_t* masks, int regions, int h, int w, float* w1, float* w2, float* w4, float* w8, void* stream);
+/* out[m][j] = fp16(sum_r w[m % rows_per_img][r] * (float)a[r * region_stride + m * c + j]) for regions in [1, 4]: acc = w_0 a_0, then
+ * acc = acc + w_r a_r for r = 1 .., every product and every sum rounded on its own in fp32 (no FMA).  a: fp16, `regions` tensors of
+ * [rows][c] region_stride elements apart (>= rows * c, a multiple of 8); w: fp32 [rows_per_img][regions]; c % 8 == 0, rows_per_img
+ * divides rows, a and out 16-byte aligned.  out may be a's first tensor. */
+SDOD_API int sdod_region_blend_f16(const void* a, size_t region_stride, const float* w, void* out, int rows, int rows_per_img, int c, int regions,
+                                   void* stream);
 SDOD_API int sdod_concat_channels_f16(const void* a, const void* b, void* y, size_t rows, int c0, int c1, void* stream);
 /* ---- T2I-Adapter structural control (graph kind SDOD_GRAPH_ADAPTER of include/sdod_engine.h).  Each of the four
  * checks its arguments and returns INVALID_ARGUMENT before any launch, the destination untouched; fp32 arithmetic, every operation

@@ -556,6 +556,8 @@ struct FoldP {
     f16* w1; float* s1; float* t1; f16* w2;
     int tiles_c; // C / 80
     int n_w;     // work items of W1 (and of W2): n_img * heads * tiles_c
+    int regions; // sdod_xattn_fold_regions_f16: n_img counts (image, region) segments; W2 puts a segment's columns behind its image's
+                 // earlier regions, [C][regions * NK].  1 = one segment per image
 };
 constexpr int kFoldKMax = 160;
 // One launch per transformer block: workgroups [0, n_w) build 80 x 80 tiles of W1 (rows = a head's 80 key slots, columns = 80
@@ -629,7 +631,8 @@ __global__ __launch_bounds__(256) void xattn_fold_kernel(const FoldP p) {
             }
         }
         const int m = rb * 16 + fr;
-        f16* row = second ? p.w2 + ((long long)img * p.C + tc * 80 + m) * NK + h * 80
+        const int wimg = img / p.regions, reg = img - wimg * p.regions;
+        f16* row = second ? p.w2 + ((long long)wimg * p.C + tc * 80 + m) * ((long long)p.regions * NK) + reg * NK + h * 80
                           : p.w1 + ((long long)(img * p.heads + h) * 80 + m) * p.C + tc * 80;
         const float al = second ? 1.0f : p.alpha;
 #pragma unroll
@@ -690,10 +693,14 @@ extern "C" int sdod_attention_f16(const void* q, const void* k, const void* v, v
     SDOD_CATCH
 }
 
-extern "C" int sdod_xattn_fold_f16(const void* kv, int ld_kv, int k_off, int v_off, int n_img, int L, const void* wq, int ldq,
-                                   const void* sq, const void* tq, const void* wo, int ldwo, int heads, int d, float scale, void* w1,
-                                   void* s1, void* t1, void* w2, void* stream) {
+namespace {
+int xattn_fold_launch(const void* kv, int ld_kv, int k_off, int v_off, int n_img, int regions, int L, const void* wq, int ldq, const void* sq,
+                      const void* tq, const void* wo, int ldwo, int heads, int d, float scale, void* w1, void* s1, void* t1, void* w2,
+                      void* stream) {
     SDOD_TRY
+    SDOD_REQUIRE(regions >= 1 && regions <= 4, "regions must be in [1, 4]");
+    SDOD_REQUIRE(n_img <= (1 << 20), "bad shape (too many images)");
+    n_img *= regions; // (image, region) segments of L rows
     SDOD_REQUIRE(kv && wq && sq && tq && wo && w1 && s1 && t1 && w2, "null pointer");
     SDOD_REQUIRE(n_img > 0 && heads > 0 && d > 0 && d <= kFoldKMax && d % 8 == 0 && L > 0 && L <= 80, "bad shape (d <= 160, d % 8 == 0, L <= 80)");
     const int C = heads * d, NK = heads * 80;
@@ -710,9 +717,23 @@ extern "C" int sdod_xattn_fold_f16(const void* kv, int ld_kv, int k_off, int v_o
     p.w1 = (f16*)w1; p.s1 = (float*)s1; p.t1 = (float*)t1; p.w2 = (f16*)w2;
     p.tiles_c = C / 80;
     p.n_w = n_img * heads * p.tiles_c;
+    p.regions = regions;
     const int blocks = 2 * p.n_w + (n_img * NK + 255) / 256;
     SDOD_LAUNCH(xattn_fold_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     SDOD_HIP_CHECK(hipGetLastError());
     return 0;
     SDOD_CATCH
+}
+} // namespace
+
+extern "C" int sdod_xattn_fold_f16(const void* kv, int ld_kv, int k_off, int v_off, int n_img, int L, const void* wq, int ldq,
+                                   const void* sq, const void* tq, const void* wo, int ldwo, int heads, int d, float scale, void* w1,
+                                   void* s1, void* t1, void* w2, void* stream) {
+    return xattn_fold_launch(kv, ld_kv, k_off, v_off, n_img, 1, L, wq, ldq, sq, tq, wo, ldwo, heads, d, scale, w1, s1, t1, w2, stream);
+}
+
+extern "C" int sdod_xattn_fold_regions_f16(const void* kv, int ld_kv, int k_off, int v_off, int n_img, int regions, int L, const void* wq,
+                                           int ldq, const void* sq, const void* tq, const void* wo, int ldwo, int heads, int d, float scale,
+                                           void* w1, void* s1, void* t1, void* w2, void* stream) {
+    return xattn_fold_launch(kv, ld_kv, k_off, v_off, n_img, regions, L, wq, ldq, sq, tq, wo, ldwo, heads, d, scale, w1, s1, t1, w2, stream);
 }

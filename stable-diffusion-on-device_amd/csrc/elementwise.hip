@@ -173,6 +173,79 @@ __global__ void add_control_kernel(const ControlTable t, const float* scales) {
     }
 }
 
+// ---- Regional prompts (include/sdod_hip.h).  Masks uint8 [k][8h][8w] -> per-pixel region weights of the four UNet
+// levels in one launch.  A workgroup owns one pixel of the coarsest level (64 x 64 image pixels = 8 x 8 latent pixels): the sums of
+// the finest level come from the image bytes (thread = a quarter of a latent pixel, two 8-byte rows), every coarser level from the
+// four sums below it -- integers throughout, so the order is free -- and each weight is ONE correctly rounded fp32 division.
+struct RegionWeightsP {
+    const uint8_t* masks;
+    float* out[4]; // level ds = 1, 2, 4, 8: [h / ds * w / ds][k]
+    int h, w, k;   // latent size (multiples of 8), regions
+};
+
+__global__ __launch_bounds__(256) void region_weights_kernel(const RegionWeightsP p) {
+    __shared__ int s[4][85]; // per region: 64 + 16 + 4 + 1 sums, level after level
+    const int tid = threadIdx.x;
+    const int cw = p.w >> 3, cy = blockIdx.x / cw, cx = blockIdx.x - cy * cw;
+    const size_t iw = (size_t)p.w * 8, plane = (size_t)p.h * 8 * iw;
+    for (int i = tid; i < 4 * 85; i += 256) s[i / 85][i % 85] = 0;
+    __syncthreads();
+    const int pix = tid >> 2, q = tid & 3, py = pix >> 3, px = pix & 7;
+    for (int r = 0; r < p.k; ++r) {
+        const uint8_t* src = p.masks + r * plane + ((size_t)cy * 64 + py * 8 + q * 2) * iw + (size_t)cx * 64 + px * 8;
+        int acc = 0;
+#pragma unroll
+        for (int row = 0; row < 2; ++row) {
+            const u32x2 v = *reinterpret_cast<const u32x2*>(src + row * iw);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc += (int)((v[0] >> (8 * b)) & 255u) + (int)((v[1] >> (8 * b)) & 255u);
+        }
+        atomicAdd(&s[r][pix], acc);
+    }
+    __syncthreads();
+    // the coarser levels: cell j of a level with n x n cells sums its 2 x 2 children
+    for (int n = 4, src = 0, dst = 64; n >= 1; src = dst, dst += n * n, n >>= 1) {
+        for (int i = tid; i < p.k * n * n; i += 256) {
+            const int r = i / (n * n), j = i - r * n * n, y = j / n, x = j - y * n;
+            const int* c = &s[r][src + (2 * y) * (2 * n) + 2 * x];
+            s[r][dst + j] = (c[0] + c[1]) + (c[2 * n] + c[2 * n + 1]);
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < 85; i += 256) {
+        const int lvl = i < 64 ? 0 : i < 80 ? 1 : i < 84 ? 2 : 3;
+        const int n = 8 >> lvl, j = i - (lvl == 0 ? 0 : lvl == 1 ? 64 : lvl == 2 ? 80 : 84);
+        const int y = j / n, x = j - y * n;
+        int tot = 0;
+        for (int r = 0; r < p.k; ++r) tot += s[r][i];
+        float* o = p.out[lvl] + ((size_t)(cy * n + y) * (cw * n) + cx * n + x) * p.k;
+        for (int r = 0; r < p.k; ++r) // nothing covers the pixel: region 0 is the background
+            o[r] = tot == 0 ? (r == 0 ? 1.0f : 0.0f) : div_rn((float)s[r][i], (float)tot);
+    }
+}
+
+// out[m][c] = fp16(sum_r w[m % rows_per_img][r] * a_r[m][c]): acc = w_0 a_0, then acc + w_r a_r, every product and sum rounded
+__global__ void region_blend_kernel(const f16* a, size_t region_stride, const float* w, f16* out, size_t total, int c, int rows_per_img, int k) {
+    const int cp = c / 8;
+    GRID_STRIDE(i, total) {
+        const size_t m = i / cp;
+        const float* wr = w + (m % rows_per_img) * k;
+        f16x8 v = ldg8(a + i * 8);
+        float acc[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = mul_rn(wr[0], (float)v[e]);
+        for (int r = 1; r < k; ++r) {
+            v = ldg8(a + r * region_stride + i * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = add_rn(acc[e], mul_rn(wr[r], (float)v[e]));
+        }
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (f16)acc[e];
+        stg8(out + i * 8, o);
+    }
+}
+
 __global__ void concat_kernel(const f16* a, const f16* b, f16* y, size_t rows, int c0, int c1) {
     const int cp = (c0 + c1) / 8, cp0 = c0 / 8;
     const size_t total = rows * cp;
@@ -1157,6 +1230,37 @@ extern "C" int sdod_add_control_f16(const sdod_control_seg* segs, int count, con
     t.first[count] = (unsigned)groups;
     SDOD_LAUNCH(add_control_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, t, scales);
     SDOD_HIP_CHECK(hipGetLastError());
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_region_weights_f32(const uint8_t* masks, int regions, int h, int w, float* w1, float* w2, float* w4, float* w8, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(masks && w1 && w2 && w4 && w8, "null pointer");
+    SDOD_REQUIRE(regions >= 1 && regions <= 4, "regions must be in [1, 4]");
+    SDOD_REQUIRE(h >= 8 && w >= 8 && h % 8 == 0 && w % 8 == 0 && h <= 1024 && w <= 1024, "h and w (latent pixels) must be multiples of 8 in [8, 1024]");
+    SDOD_REQUIRE(((uintptr_t)masks & 15) == 0 && (((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)w4 | (uintptr_t)w8) & 3) == 0, "misaligned pointer (masks: 16 bytes)");
+    RegionWeightsP p{};
+    p.masks = masks;
+    p.out[0] = w1; p.out[1] = w2; p.out[2] = w4; p.out[3] = w8;
+    p.h = h; p.w = w; p.k = regions;
+    SDOD_LAUNCH(region_weights_kernel, dim3((unsigned)((h / 8) * (w / 8))), dim3(256), 0, (hipStream_t)stream, p);
+    SDOD_HIP_CHECK(hipGetLastError());
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_region_blend_f16(const void* a, size_t region_stride, const float* w, void* out, int rows, int rows_per_img, int c, int regions,
+                                     void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(a && w && out, "null pointer");
+    SDOD_REQUIRE(regions >= 1 && regions <= 4, "regions must be in [1, 4]");
+    SDOD_REQUIRE(rows > 0 && rows_per_img > 0 && rows % rows_per_img == 0, "rows_per_img must divide rows");
+    SDOD_REQUIRE(c > 0 && c % 8 == 0, "c must be a multiple of 8");
+    SDOD_REQUIRE(region_stride >= (size_t)rows * c && region_stride % 8 == 0, "region_stride must be >= rows * c and a multiple of 8");
+    SDOD_REQUIRE((((uintptr_t)a | (uintptr_t)out) & 15) == 0 && ((uintptr_t)w & 3) == 0, "misaligned pointer (16 bytes)");
+    const size_t total = (size_t)rows * (c / 8);
+    LAUNCH(region_blend_kernel, total, stream, (const f16*)a, region_stride, w, (f16*)out, total, c, rows_per_img, regions);
     return 0;
     SDOD_CATCH
 }

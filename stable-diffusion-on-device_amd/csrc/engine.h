@@ -72,7 +72,7 @@ struct IoSlot {
 class Graph {
 public:
     Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg = sdod_adapter_config{0, 0, 0}, int wrap = 0,
-          const sdod_upscaler_config& ucfg = sdod_upscaler_config{0, 0, 0}, const sdod_control_config* ccfg = nullptr);
+          const sdod_upscaler_config& ucfg = sdod_upscaler_config{0, 0, 0}, const sdod_control_config* ccfg = nullptr, int regions = 0);
     ~Graph();
     Graph(const Graph&) = delete;
 
@@ -102,6 +102,8 @@ private:
     sdod_adapter_config acfg_; // T2I-Adapter: all zero = no adapter inputs (UNET), required for kind ADAPTER
     sdod_upscaler_config ucfg_; // kind UPSCALER only (sdod_graph_create_upscaler); all zero for every other kind
     sdod_control_config ccfg_{0, 0}; // ControlNet switches of the UNET / TEMB graphs (sdod_graph_create_control); all zero = none
+    int regions_ = 0;                    // regional prompts of the UNET graph (sdod_graph_create_regions): prompts per image; 0 = none
+    const float* region_w_[4] = {};      // ... and its four weight inputs, level ds = 1, 2, 4, 8 (set by build_unet())
     bool has_kv() const { return kind_ == SDOD_GRAPH_UNET || kind_ == SDOD_GRAPH_CONTROLNET; } // owns kv_all_ and the static K/V GEMM
     int batch_;
     int wrap_ = 0; // seamless tiling (UNET, VAE_DECODER): bit 0 = x wraps, bit 1 = y wraps; conv() turns it into sdod_gemm_desc::pad_mode
@@ -222,6 +224,8 @@ private:
         const float* ln_s_raw = nullptr; // LayerNorm fold with vectors the caller owns: ln_s (bias_raw carries the matching t)
         int w_img_stride = 0, vec_img_stride = 0; // per-image weights / vectors (sdod_gemm_desc), with rows_per_img
         int softmax_cols = 0;
+        const float* region_w = nullptr; // regional prompts: the softmax GEMM goes through sdod_gemm_region_f16(region_w, regions)
+        int regions = 0;
         int pad_mode = 0;          // conv(): sdod_gemm_desc::pad_mode
         int split_k = 0;           // conv(): sdod_gemm_desc::split_k (0 = planned; 1 = one launch whatever the shape)
     };
@@ -248,7 +252,7 @@ private:
     char* base_copy_ = nullptr;     // the arena before run_folds(), weight_bytes_ long (keep_base())
     bool static_stale_ = false;     // weights changed under static_ops_' results: execute() runs them whatever skip_static says
     std::vector<void*> derived_; // device buffers created at build time (folded LayerNorm vectors)
-    void emit_gemm(sdod_gemm_desc d);
+    void emit_gemm(sdod_gemm_desc d, const float* region_w = nullptr, int regions = 0);
     // out[rows][N] = x[rows][K] . W^T ; W is params_[w] (or a raw fp16 [N][K] pointer through *_raw)
     void linear(const f16* x, int rows, int K, int w, int N, f16* out, const GemmOpt& o);
     void linear_raw(const f16* x, int rows, int K, const f16* w, int ldw, int N, f16* out, const GemmOpt& o);

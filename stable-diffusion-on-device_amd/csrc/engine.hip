@@ -38,8 +38,9 @@ static void parallel_for(int64_t n, F&& fn) {
 
 // ------------------------------------------------------------------------------------------ lifecycle
 Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg, int wrap, const sdod_upscaler_config& ucfg,
-             const sdod_control_config* ccfg)
-    : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), batch_(batch), wrap_(wrap) {
+             const sdod_control_config* ccfg, int regions)
+    : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), regions_(regions), batch_(batch), wrap_(wrap) {
+    SDOD_REQUIRE(regions == 0 || (kind == SDOD_GRAPH_UNET && regions >= 2 && regions <= 4), "regions: the UNET graph only, 2 .. 4");
     SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_CONTROL_HINT, "unknown graph kind");
     const bool control_kind = kind == SDOD_GRAPH_CONTROLNET || kind == SDOD_GRAPH_CONTROL_HINT;
     SDOD_REQUIRE(!control_kind || ccfg, "the CONTROLNET and CONTROL_HINT graphs are created by sdod_graph_create_control");
@@ -560,6 +561,9 @@ struct ShapeKey {
 //     control graph's K/V projection) at the sizes its tests and tools/controlnet_bench.py build.  A file of its own because the
 //     first one's key set is pinned (tests/golden/gemm_tiles.json.gz plans exactly its descriptors); it only ADDS shapes: a key
 //     the first table already holds keeps that pick, so no graph that existed before can change;
+//   * tune/gfx950_regions.tune behind both, on the same terms: the picks for the regional-prompt UNet's own shapes (the score and
+//     output GEMMs of the folded cross-attention at regions x 640 columns, the K/V projection of regions x 77 keys) at the sizes its
+//     tests and tools/regions_bench.py build;
 //   * SDOD_TUNE_CACHE=<file>: read after (so it overrides) the shipped table; shapes found in neither are timed once and
 //     appended to it.  Picks depend on the build and the device: regenerate the table when the tiles change.
 const char* tune_cache_path() {
@@ -581,6 +585,10 @@ std::string shipped_tune_path() {
 std::string control_tune_path() {
     const std::string first = shipped_tune_path();
     return first.empty() ? first : first.substr(0, first.size() - 5) + "_control.tune";
+}
+std::string regions_tune_path() {
+    const std::string first = shipped_tune_path();
+    return first.empty() ? first : first.substr(0, first.size() - 5) + "_regions.tune";
 }
 struct TuneEntry {
     int v;          // tile + 1000 * split_k
@@ -639,6 +647,7 @@ TuneCache& tune_cache() {
         const std::string shipped = shipped_tune_path();
         if (!shipped.empty()) tune_cache_read(shipped.c_str(), c.map);
         if (!shipped.empty()) tune_cache_read(control_tune_path().c_str(), c.map, true);
+        if (!shipped.empty()) tune_cache_read(regions_tune_path().c_str(), c.map, true);
         if (const char* path = tune_cache_path()) tune_cache_read(path, c.map);
     }
     return c;
@@ -696,7 +705,7 @@ void Graph::flush_pending() {
     sink().push_back(Op{[d2](hipStream_t st) { check_rc(sdod_gemm_f16(&d2, st)); }, "splitk_reduce", 0.0, pending_.bytes, pending_.detail});
 }
 
-void Graph::emit_gemm(sdod_gemm_desc d) {
+void Graph::emit_gemm(sdod_gemm_desc d, const float* region_w, int regions) {
     settle();
     if (mode_ == DECLARE) return;
     // (N <= 16: the skinny default tile -- except the UNet's output convolution, 320 -> 4 channels, where a halo-patch tile without
@@ -805,6 +814,11 @@ void Graph::emit_gemm(sdod_gemm_desc d) {
     static const bool fixup_on = [] { const char* e = std::getenv("SDOD_GEMM_FIXUP"); return e && e[0] == '1'; }();
     if (!fixup_on) d.fix_counters = nullptr;
     static const bool fuse_reduce_gn = [] { const char* e = std::getenv("SDOD_GN_REDUCE"); return e && e[0] == '1'; }();
+    if (regions > 0) { // (the softmax epilogue plans no split-K)
+        if (splits > 1) throw Error(INTERNAL_ERROR, "a region-weighted GEMM planned split-K");
+        sink().push_back(Op{[d, region_w, regions](hipStream_t st) { check_rc(sdod_gemm_region_f16(&d, region_w, regions, st)); }, label, fl, by, detail});
+        return;
+    }
     if (splits > 1 && !fuse_reduce_gn && sdod_gemm_fixup(&d)) {
         // the K slices are reduced inside the GEMM launch: ONE entry
         const double part = (double)splits * d.M * d.N * 4;
@@ -888,7 +902,7 @@ void Graph::linear_raw(const f16* x, int rows, int K, const f16* w, int ldw, int
         d.ln_s = o.ln_s_raw;
     }
     d.w_img_stride = o.w_img_stride; d.vec_img_stride = o.vec_img_stride; d.softmax_cols = o.softmax_cols;
-    emit_gemm(d);
+    emit_gemm(d, o.region_w, o.regions);
 }
 
 Graph::LnVecs Graph::ln_fold_vectors(f16* w, int N, int K, int ldw, int ln_w, int ln_b, const float* bias) {
@@ -1421,6 +1435,18 @@ extern "C" int sdod_graph_create_control(void** graph, int kind, const sdod_mode
     SDOD_CATCH
 }
 
+extern "C" int sdod_graph_create_regions(void** graph, int kind, const sdod_model_config* cfg, const sdod_region_config* regions, int batch) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph && cfg, "null argument");
+    *graph = nullptr;
+    SDOD_REQUIRE(regions != nullptr && kind == SDOD_GRAPH_UNET, "regional prompts: a region configuration and kind SDOD_GRAPH_UNET");
+    SDOD_REQUIRE(regions->regions >= 2 && regions->regions <= 4, "regions must be in [2, 4]");
+    SDOD_REQUIRE(cfg->context_len == 77 * regions->regions, "regional prompts: context_len must be 77 * regions");
+    *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, nullptr, regions->regions);
+    return 0;
+    SDOD_CATCH
+}
+
 extern "C" int sdod_graph_bind_output(void* graph, int index, void* device_ptr, size_t bytes) {
     SDOD_TRY
     SDOD_REQUIRE(graph, "null argument");
@@ -1560,7 +1586,7 @@ extern "C" int sdod_graph_tune_info(void* graph, int* from_table, int* tuned_in_
     if (tuned_in_process) *tuned_in_process = g->tune_misses();
     if (table_path && cap > 0) {
         std::string s = sdod::shipped_tune_path();
-        if (!s.empty()) s += " + " + sdod::control_tune_path();
+        if (!s.empty()) s += " + " + sdod::control_tune_path() + " + " + sdod::regions_tune_path();
         if (const char* extra = sdod::tune_cache_path()) s += (s.empty() ? "" : " + ") + std::string(extra);
         std::snprintf(table_path, (size_t)cap, "%s", s.c_str());
     }

@@ -61,9 +61,14 @@ struct GemmP {
     int sa0, sa1; // pixel strides (elements) of the two A sources: c0/c1 for NHWC images, lda for plain rows
     int geglu;    // epilogue pairs 16-column blocks: out = a * gelu(gate)
     int k_tail;   // K columns >= k_tail come from the 1x1-gathered tail sources t0|t1 (0 = none)
-    const f16* t0;
+    // Regional prompts (sdod_gemm_region_f16) share the tail's slots -- the softmax epilogue needs per-image weights, which exclude a
+    // tail, and no kernel reads t0 / tc0 / tc1 unless k_tail != 0 -- so the struct, and with it every kernel's argument offsets, stay
+    // as they were: with softmax_g the epilogue multiplies the probabilities of 80-column group g of row m by
+    // region_w[(m % rows_per_img) * regions + g / groups_per_region]; null = the plain softmax (the host clears the slots without a tail)
+    union { const f16* t0; const float* region_w; };
     const f16* t1;
-    int tc0, tc1;
+    union { int tc0; int regions; };
+    union { int tc1; int groups_per_region; };
     const float* bias2;
     unsigned mg_hw, sh_hw, mg_w, sh_w, mg_tn, sh_tn, mg_cin, sh_cin; // magic multipliers: m/(h_out*w_out), rem/w_out, lid/tiles_n, k0/cin
     int ln;            // LayerNorm of the A rows folded into this GEMM (row statistics gathered from the LDS slabs)
@@ -659,8 +664,18 @@ SDOD_DEVICE f16x8 wq_frag(const f16* sB, int row, int ks, int fc, f16 z) {
 // As a run-time branch of the gather it cost the zero-pad instantiations registers -- a scalar or two more alive in the slab loop
 // spills SGPRs into a VGPR, and several tiles sit exactly at a VGPR step (64, 80, 128) that decides how many workgroups share a CU
 // (profiles/tiling_isa.txt); with WRAP = false none of its code exists and every older instantiation compiles to what it was.
-template <int BM, int BN, int WM, int WN, int STAGES, bool SPEC = false, bool WQ = false, int KSUB = 1, bool WRAP = false>
+// REGION = the softmax epilogue multiplies every 80-column group by its region's weight (regional prompts, GemmP::region_w): a
+// compile-time variant for the same reason -- as a run-time branch it moved the VGPR count of nine of the twenty softmax
+// instantiations.  It travels as bit kRegionFlag of the KSUB argument, not as a tenth template argument, which would rename every
+// instantiation (and a body shared by two kernels, called with the arguments by reference, changed the scalar code of all of them):
+// every older instantiation keeps its name and compiles to what it was (profiles/regions_gemm_isa.txt).  The REGION forms exist for
+// the wave-80 tiles only and are launched by sdod_gemm_region_f16 alone.
+constexpr int kRegionFlag = 16;
+template <int BM, int BN, int WM, int WN, int STAGES, bool SPEC = false, bool WQ = false, int KSUB_R = 1, bool WRAP = false>
 __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kernel(const GemmP p, const f16* __restrict__ zeros) {
+    constexpr int KSUB = KSUB_R & (kRegionFlag - 1);
+    constexpr bool REGION = (KSUB_R & kRegionFlag) != 0;
+    static_assert(!REGION || (BN / WN == 80 && !WQ && !WRAP), "the region weight lives in the softmax epilogue of the wave-80 tiles");
     constexpr int NC = WM * WN;                   // waves that own output tiles
     constexpr int NW = SPEC ? 2 * NC : NC;        // waves per workgroup: 4 (one per SIMD) or 8 (two per SIMD)
     constexpr int NL = SPEC ? NC : NW;            // waves that issue the DMA
@@ -1390,6 +1405,14 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
             // bias is -30000, scores already in log2 units): a row's columns sit in this lane (TN blocks x 4) and in the three
             // lanes 16 / 32 / 48 away -- two row swaps per reduction (quad_rows_max / _sum), nothing leaves the wave.
             if (p.softmax_g) {
+                // regional prompts: this wave's group belongs to ONE region prompt; its weight at the lane's rows (tiles never
+                // straddle images) goes into the reciprocal of the sum -- 1.0 changes no bit, 0 gives exact zeros
+                const float* rw = nullptr;
+                if constexpr (REGION) {
+                    const int g = (n0 + wn * WTN) / 80, gpr = p.groups_per_region; // (regions <= 4; a group past N clamps)
+                    const int reg = min((g >= gpr ? 1 : 0) + (g >= 2 * gpr ? 1 : 0) + (g >= 3 * gpr ? 1 : 0), p.regions - 1);
+                    rw = p.region_w + (size_t)(m0 - fast_div(m0, p.mg_rpi, p.sh_rpi) * p.rows_per_img + wm * WTM + e_m) * p.regions + reg;
+                }
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     float mx = acc[i][0][0];
@@ -1408,7 +1431,8 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1)) void gemm_glds_kerne
                             sum += e;
                         }
                     sum = quad_rows_sum(sum);
-                    const float inv = __builtin_amdgcn_rcpf(sum);
+                    float inv = __builtin_amdgcn_rcpf(sum);
+                    if constexpr (REGION) inv *= rw[i * 16 * p.regions];
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -2759,6 +2783,11 @@ hipError_t launch_tile(const GemmP& p, dim3 grid, size_t smem, hipStream_t st) {
             if (p.wq) return launch_kernel<&gemm_glds_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, c.spec != 0, true, c.ksub>>(p, grid, block, lds, (int)lds, st);
         }
         if (p.wq) return hipErrorInvalidValue; // (make_plan never leaves a uint8 GEMM on such a tile)
+        if (p.softmax_g && p.k_tail == 0 && p.region_w != nullptr) { // sdod_gemm_region_f16 (rows mode: no border to wrap)
+            if constexpr (c.bn / c.wn == 80)
+                return launch_kernel<&gemm_glds_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, c.spec != 0, false, c.ksub | kRegionFlag>>(p, grid, block, lds, (int)lds, st);
+            return hipErrorInvalidValue; // (the plan keeps a softmax epilogue on the wave-80 tiles)
+        }
         if (p.gmode > 1) return launch_kernel<&gemm_glds_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, c.spec != 0, false, c.ksub, true>>(p, grid, block, lds, (int)lds, st);
         return launch_kernel<&gemm_glds_kernel<c.bm, c.bn, c.wm, c.wn, c.stages, c.spec != 0, false, c.ksub>>(p, grid, block, lds, (int)lds, st);
     } else if constexpr (c.family == HALO) {
@@ -3079,7 +3108,9 @@ extern "C" int sdod_gemm_plan(const sdod_gemm_desc* d, int* tile, int* splits) {
     return 0;
 }
 
-extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
+namespace {
+// sdod_gemm_f16, and sdod_gemm_region_f16 with regions >= 1 (region_w checked by the caller)
+int gemm_launch(const sdod_gemm_desc* d, const float* region_w, int regions, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(d != nullptr, "null descriptor");
     SDOD_REQUIRE(d->a && d->w && d->out, "null operand pointer");
@@ -3112,7 +3143,7 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
     p.rows_per_img = d->rows_per_img > 0 ? d->rows_per_img : 1;
     p.geglu = d->geglu ? 1 : 0;
     p.k_tail = d->k_tail;
-    p.t0 = (const f16*)d->t0; p.t1 = (const f16*)d->t1; p.tc0 = d->tc0; p.tc1 = d->tc1;
+    if (d->k_tail) { p.t0 = (const f16*)d->t0; p.t1 = (const f16*)d->t1; p.tc0 = d->tc0; p.tc1 = d->tc1; } // (else null / 0: the slots are region_w's)
     p.bias2 = (const float*)d->bias2;
     p.ln = d->ln ? 1 : 0;
     p.ln_s = (const float*)d->ln_s;
@@ -3169,6 +3200,13 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
     p.w_img_stride = d->w_img_stride;
     p.vec_img_stride = d->vec_img_stride;
     p.softmax_g = d->softmax_cols;
+    if (regions > 0) {
+        SDOD_REQUIRE(regions <= 4 && d->softmax_cols == 80 && d->w_img_stride != 0 && d->N % (80 * regions) == 0,
+                     "region weights: regions in [1, 4], softmax_cols == 80, per-image weights, N a multiple of 80 * regions");
+        p.region_w = region_w;
+        p.regions = regions;
+        p.groups_per_region = d->N / 80 / regions;
+    }
     make_magic((unsigned)p.rows_per_img, &p.mg_rpi, &p.sh_rpi);
     if (d->w_img_stride || d->vec_img_stride)
         SDOD_REQUIRE(d->w_img_stride > 0 && d->vec_img_stride >= 0 && d->a_mode == SDOD_A_ROWS && d->rows_per_img > 0 && d->rows_per_img % 32 == 0 &&
@@ -3255,6 +3293,17 @@ extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) {
     }
     return 0;
     SDOD_CATCH
+}
+} // namespace
+
+extern "C" int sdod_gemm_f16(const sdod_gemm_desc* d, void* stream) { return gemm_launch(d, nullptr, 0, stream); }
+
+extern "C" int sdod_gemm_region_f16(const sdod_gemm_desc* d, const void* region_w, int regions, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(region_w != nullptr && ((uintptr_t)region_w & 3) == 0, "region_w: null or misaligned pointer");
+    SDOD_REQUIRE(regions >= 1, "regions must be in [1, 4]");
+    SDOD_CATCH
+    return gemm_launch(d, (const float*)region_w, regions, stream);
 }
 
 // developer aid: average duration (ms) of `iters` back-to-back launches, timed with HIP events on `stream`

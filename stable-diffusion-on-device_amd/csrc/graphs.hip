@@ -185,8 +185,22 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
     // Needs the LayerNorm fold (fp16 weights), heads * 80 columns tiled by the 160-wide GEMM tiles and the 64-deep K slabs,
     // image rows a multiple of 32.  SDOD_XATTN_FOLD=0 keeps the three-launch form (A/B switch).
     static const bool xfold_on = [] { const char* e = std::getenv("SDOD_XATTN_FOLD"); return !(e && e[0] == '0'); }();
+    // REGIONAL PROMPTS (regions_ > 0): the context holds regions_ prompts of Lk keys per image and the block's output is
+    // sum_r w_r(pixel) attn(x, K_r, V_r).  Folded: the score GEMM's 80-column groups are laid out [region][head][80], its epilogue
+    // multiplies each group by its region's weight at the row's pixel and the second GEMM sums over regions through its K axis --
+    // the same launches as the plain fold, both GEMMs regions_ times as wide.  Otherwise one attention launch per (image, region)
+    // and a blend launch (correct, not fast: only levels of fewer than 32 pixels, or not a multiple of 32, come here).
+    const int RG = regions_, NR = RG > 0 ? RG : 1;
+    const int Lkeys = ctx.w / NR; // keys per prompt
+    const float* rgw = nullptr;   // this level's weights, fp32 [L][RG]
+    if (RG > 0) {
+        int lvl = 0;
+        while (lvl < 4 && (cfg_.latent_h >> lvl) != x.h) ++lvl;
+        if (lvl == 4 || (cfg_.latent_w >> lvl) != x.w) throw Error(INTERNAL_ERROR, "regional prompts: a transformer off the four UNet levels");
+        rgw = region_w_[lvl];
+    }
     const int NK = heads * 80;
-    const bool xfold = xfold_on && fold && ctx.w <= 80 && NK % 320 == 0 && L % 32 == 0 && d <= 160 && d % 4 == 0;
+    const bool xfold = xfold_on && fold && Lkeys <= 80 && NK % 320 == 0 && L % 32 == 0 && d <= 160 && d % 4 == 0;
     // either form leaves its last GEMM to be emitted once its destination is known: t2 = a[rows][K] . w^T + o2b + t1
     struct { f16* a; int K; const f16* w; GemmOpt o; } xo;
     xo.o.bias = o2b; xo.o.residual = t1.p;
@@ -196,16 +210,22 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
         f16* wq = reinterpret_cast<f16*>(params_[q2w].dev);
         const f16* wo = reinterpret_cast<const f16*>(params_[o2w].dev);
         if (mode_ == REAL) {
-            SDOD_HIP_CHECK(hipMalloc((void**)&w1, (size_t)B * NK * C * sizeof(f16)));
-            SDOD_HIP_CHECK(hipMalloc((void**)&w2, (size_t)B * NK * C * sizeof(f16)));
-            SDOD_HIP_CHECK(hipMalloc((void**)&s1, (size_t)B * NK * sizeof(float)));
-            SDOD_HIP_CHECK(hipMalloc((void**)&t1v, (size_t)B * NK * sizeof(float)));
+            SDOD_HIP_CHECK(hipMalloc((void**)&w1, (size_t)B * NR * NK * C * sizeof(f16)));
+            SDOD_HIP_CHECK(hipMalloc((void**)&w2, (size_t)B * NR * NK * C * sizeof(f16)));
+            SDOD_HIP_CHECK(hipMalloc((void**)&s1, (size_t)B * NR * NK * sizeof(float)));
+            SDOD_HIP_CHECK(hipMalloc((void**)&t1v, (size_t)B * NR * NK * sizeof(float)));
             derived_.push_back(w1); derived_.push_back(w2); derived_.push_back(s1); derived_.push_back(t1v);
             const LnVecs qv = ln_fold_vectors(wq, C, C, C, l2w, l2b, nullptr);
             const f16* kvp = kv_all_;
-            const int ldkv = kv_total_, koff = my_kv, Lk = ctx.w, hh = heads, dd = d;
+            const int ldkv = kv_total_, koff = my_kv, Lk = Lkeys, hh = heads, dd = d;
             const float scale = 1.0f / sqrtf((float)d);
             to_static_ = true; // (not emit(): its settle() would put a still pending split-K reduce into the static list)
+            if (RG > 0)
+                sink().push_back(Op{[=](hipStream_t st) {
+                    check_rc(sdod_xattn_fold_regions_f16(kvp, ldkv, koff, koff + C, B, RG, Lk, wq, C, qv.s, qv.t, wo, C, hh, dd, scale, w1, s1, t1v, w2, st));
+                }, "xattn_fold", 4.0 * B * RG * NK * (double)C * d, 4.0 * B * RG * NK * C * 2,
+                   "C" + std::to_string(C) + " d" + std::to_string(d) + " regions" + std::to_string(RG)});
+            else
             sink().push_back(Op{[=](hipStream_t st) {
                 check_rc(sdod_xattn_fold_f16(kvp, ldkv, koff, koff + C, B, Lk, wq, C, qv.s, qv.t, wo, C, hh, dd, scale, w1, s1, t1v, w2, st));
             }, "xattn_fold", 4.0 * B * NK * (double)C * d, 4.0 * B * NK * C * 2, "C" + std::to_string(C) + " d" + std::to_string(d)});
@@ -213,12 +233,29 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
         }
         const f16* w1p = mode_ == REAL ? w1 : wq; // (placeholders during the sizing pass)
         const f16* w2p = mode_ == REAL ? w2 : wq;
-        f16* pb = alloc((size_t)rows * NK);
+        const int NKR = NR * NK; // (regions: [region][head][80] columns)
+        f16* pb = alloc((size_t)rows * NKR);
         { GemmOpt o; o.ln_s_raw = mode_ == REAL ? s1 : reinterpret_cast<const float*>(wq); o.bias_raw = mode_ == REAL ? t1v : reinterpret_cast<const float*>(wq);
-          o.w_img_stride = NK * C; o.vec_img_stride = NK; o.softmax_cols = 80; o.rows_per_img = L;
-          linear_raw(t1.p, rows, C, w1p, C, NK, pb, o); }
-        xo.a = pb; xo.K = NK; xo.w = w2p;
-        xo.o.w_img_stride = C * NK; xo.o.rows_per_img = L;
+          o.w_img_stride = NKR * C; o.vec_img_stride = NKR; o.softmax_cols = 80; o.rows_per_img = L;
+          o.region_w = rgw; o.regions = RG;
+          linear_raw(t1.p, rows, C, w1p, C, NKR, pb, o); }
+        xo.a = pb; xo.K = NKR; xo.w = w2p;
+        xo.o.w_img_stride = C * NKR; xo.o.rows_per_img = L;
+    } else if (RG > 0) {
+        f16* q2 = alloc((size_t)rows * C);
+        behind_ln(t1, l2w, l2b, GemmOpt{}, [&](const f16* a, const GemmOpt& og) { linear(a, rows, C, q2w, C, q2, og); });
+        // sdod_attention_f16 steps from image to image by Lk * ldk rows; an (image, region) segment does not: batch 1 each
+        f16* ar = alloc((size_t)RG * rows * C);
+        for (int b = 0; b < B; ++b)
+            for (int r = 0; r < RG; ++r) {
+                const f16* kv = kv_all_ + (size_t)(b * RG + r) * Lkeys * kv_total_ + my_kv;
+                attention(q2 + (size_t)b * L * C, kv, kv + C, ar + ((size_t)r * rows + (size_t)b * L) * C, 1, heads, L, Lkeys, d, C, kv_total_, kv_total_, C, false);
+            }
+        release(q2);
+        { const int rr = rows, LL = L, CC2 = C;
+          emit([=](hipStream_t st) { check_rc(sdod_region_blend_f16(ar, (size_t)rr * CC2, rgw, ar, rr, LL, CC2, RG, st)); }, "region_blend", 2.0 * RG * rows * C,
+               (double)(RG + 1) * rows * C * 2, "rows" + std::to_string(rows) + " C" + std::to_string(C) + " regions" + std::to_string(RG)); }
+        xo.a = ar; xo.K = C; xo.w = W<f16>(o2w);
     } else {
         f16* q2 = alloc((size_t)rows * C);
         behind_ln(t1, l2w, l2b, GemmOpt{}, [&](const f16* a, const GemmOpt& og) { linear(a, rows, C, q2w, C, q2, og); });
@@ -407,6 +444,24 @@ void Graph::build_unet() {
     if (ccfg_.control_inputs) {
         for (int k = 0; k < 13; ++k) ctrl_in[k] = (const f16*)io_alloc(inputs_, control_residual_numel(k) * sizeof(f16));
         ctrl_scale = (const float*)io_alloc(inputs_, 13 * sizeof(float));
+    }
+    // regional prompts: the blend weights of the four levels, fp32 [H / ds * W / ds][regions], behind every other
+    // input and shared by all images; "region 0 everywhere" until the caller writes them (sdod_region_weights_f32)
+    for (int l = 0; l < 4; ++l) region_w_[l] = nullptr;
+    if (regions_ > 0) {
+        SDOD_REQUIRE(CL == 77 * regions_, "regional prompts: context_len must be 77 * regions");
+        SDOD_REQUIRE(AR == 0 && !ccfg_.control_inputs && CC == 0 && wrap_ == 0 && !quant_mode(),
+                     "regional prompts exclude adapter inputs, control inputs, concat_channels, wrap and weight_quant");
+        for (int l = 0; l < 4; ++l) {
+            const size_t n = (size_t)(H >> l) * (Wd >> l) * regions_;
+            float* wp = (float*)io_alloc(inputs_, n * sizeof(float));
+            if (mode_ == REAL) {
+                std::vector<float> init(n, 0.f);
+                for (size_t i = 0; i < n; i += regions_) init[i] = 1.f;
+                SDOD_HIP_CHECK(hipMemcpy(wp, init.data(), n * sizeof(float), hipMemcpyHostToDevice));
+            }
+            region_w_[l] = wp;
+        }
     }
     f16* e_out = (f16*)io_alloc(outputs_, (size_t)B * H * Wd * LC * sizeof(f16));
     Act ctx;

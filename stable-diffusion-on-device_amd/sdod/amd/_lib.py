@@ -111,6 +111,7 @@ def _declare(lib):
     P = c_void_p
     sig = {
         'sdod_gemm_f16': (c_int, [ctypes.POINTER(GemmDesc), P]),
+        'sdod_gemm_region_f16': (c_int, [ctypes.POINTER(GemmDesc), P, c_int, P]),
         'sdod_gemm_fixup': (c_int, [P]),
         'sdod_gemm_fixup_counters': (c_size_t, []),
         'sdod_gemm_workspace_bytes': (c_size_t, [ctypes.POINTER(GemmDesc)]),
@@ -141,6 +142,9 @@ def _declare(lib):
         'sdod_lora_merge_f16': (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_float, c_int, c_int, P]),
         'sdod_attention_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P]),
         'sdod_xattn_fold_f16': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
+        'sdod_xattn_fold_regions_f16': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
+        'sdod_region_weights_f32': (c_int, [P, c_int, c_int, c_int, P, P, P, P, P]),
+        'sdod_region_blend_f16': (c_int, [P, c_size_t, P, P, c_int, c_int, c_int, c_int, P]),
         'sdod_softmax_rows_f16': (c_int, [P, P, c_int, c_int, P]),
         'sdod_geglu_f16': (c_int, [P, P, c_int, c_int, P]),
         'sdod_act_f16': (c_int, [P, P, c_size_t, c_int, P]),
@@ -202,6 +206,7 @@ HIP_SYMBOLS = [
     'sdod_dpm_update', 'sdod_ddim_step_f32', 'sdod_lincomb4_f32', 'sdod_image_to_u8', 'sdod_hip_last_error',
     'sdod_hip_device_info', 'sdod_image_conv_in_unit_f16', 'sdod_dense_conv3x3_f16', 'sdod_dense_conv3x3_ok',
     'sdod_add_control_f16',
+    'sdod_gemm_region_f16', 'sdod_xattn_fold_regions_f16', 'sdod_region_weights_f32', 'sdod_region_blend_f16',
 ]
 
 

@@ -30,7 +30,10 @@ class ModelConfig(ctypes.Structure):
     # inputs and control_scale, control_temb = 1 makes a Temb the time conditioning of a ControlNet graph; 0 = the plain graphs.
     control_inputs = 0
     control_temb = 0
-    _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'tiling', 'control_inputs', 'control_temb')
+    # Regional prompts (`struct sdod_region_config`, next to the struct like the others): prompts per image of a UNet, whose context_len
+    # is then 77 * regions and which gets the four UNet.region_w inputs; 0 = the plain graph through the old creation entry points.
+    regions = 0
+    _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'tiling', 'control_inputs', 'control_temb', 'regions')
 
     @classmethod
     def from_buffer_copy(cls, source, offset=0):
@@ -50,6 +53,11 @@ class AdapterConfig(ctypes.Structure):
 class ControlConfig(ctypes.Structure):
     """mirror of `struct sdod_control_config`"""
     _fields_ = [(n, ctypes.c_int) for n in ('control_inputs', 'control_temb')]
+
+
+class RegionConfig(ctypes.Structure):
+    """mirror of `struct sdod_region_config`"""
+    _fields_ = [('regions', ctypes.c_int)]
 
 
 class UpscalerConfig(ctypes.Structure):
@@ -83,7 +91,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_set_param', 'sdod_graph_param_device', 'sdod_graph_load_file', 'sdod_graph_finalize', 'sdod_graph_io', 'sdod_graph_execute', 'sdod_graph_check',
     'sdod_graph_stats', 'sdod_graph_tune_info', 'sdod_graph_num_ops', 'sdod_graph_op_info', 'sdod_graph_op_detail', 'sdod_graph_profile',
     'sdod_graph_keep_base', 'sdod_graph_base_bytes', 'sdod_graph_set_loras', 'sdod_graph_create_upscaler',
-    'sdod_graph_create_control', 'sdod_graph_bind_output',
+    'sdod_graph_create_control', 'sdod_graph_bind_output', 'sdod_graph_create_regions',
 ]
 
 
@@ -100,6 +108,7 @@ def _engine():
         lib.sdod_graph_create_wrap.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(AdapterConfig), I, I]
         lib.sdod_graph_create_upscaler.argtypes = [ctypes.POINTER(P), ctypes.POINTER(UpscalerConfig), I]
         lib.sdod_graph_create_control.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(ControlConfig), I]
+        lib.sdod_graph_create_regions.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(RegionConfig), I]
         lib.sdod_graph_bind_output.argtypes = [P, I, P, ctypes.c_size_t]
         lib.sdod_graph_destroy.argtypes = [P]
         lib.sdod_graph_num_params.argtypes = [P]
@@ -174,8 +183,14 @@ class Graph:
         control = kind in (CONTROLNET, CONTROL_HINT) or ccfg.control_inputs or ccfg.control_temb
         if control and (wrap or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_)):
             raise ValueError('a ControlNet graph, or a UNet with control inputs, takes neither tiling nor a T2I-Adapter configuration')
+        regions = int(getattr(cfg, 'regions', 0)) if kind == UNET else 0
+        if regions and (control or wrap or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_)):
+            raise ValueError('a UNet with regions takes no control inputs, no tiling and no T2I-Adapter configuration')
         with self._on_device():
-            if control:             # the ControlNet kinds and switches have an entry point of their own; without them nothing changes
+            if regions:             # regional prompts have an entry point of their own; without them nothing changes
+                rcfg = RegionConfig(regions)
+                check(self._lib.sdod_graph_create_regions(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(rcfg), batch))
+            elif control:             # the ControlNet kinds and switches have an entry point of their own; without them nothing changes
                 check(self._lib.sdod_graph_create_control(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(ccfg), batch))
             elif kind == UPSCALER:    # its configuration is the UpscalerConfig itself; no ModelConfig field applies
                 check(self._lib.sdod_graph_create_upscaler(ctypes.byref(self._h), ctypes.byref(cfg), batch))
@@ -370,6 +385,9 @@ class UNet(Graph):
             first = 4 if c.concat_channels > 0 else 3
             self.control_res = [self.io_tensor(False, first + k, shape, torch.float16) for k, shape in enumerate(control_residual_shapes(c, b))]
             self.control_scale = self.io_tensor(False, first + 13, (13,), torch.float32)
+        k = int(getattr(c, 'regions', 0))
+        if k:                       # regional prompts: the blend weights of the four levels, "region 0 everywhere" until set (ops.region_weights)
+            self.region_w = [self.io_tensor(False, 3 + lvl, ((c.latent_h >> lvl) * (c.latent_w >> lvl), k), torch.float32) for lvl in range(4)]
         return self
 
 

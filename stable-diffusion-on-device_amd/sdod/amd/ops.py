@@ -74,7 +74,7 @@ def workspace(nbytes, device, tag='default'):
 def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=None, alpha=1.0, out=None,
          conv=None, a2=None, bias_on_m=False, split_k=0, tile=0, time_iters=0, geglu=False, tail=None, bias2=None,
          ln_s=None, ln_eps=1e-5, cold_scratch=None, phase=0, return_desc=False, w_scale=None, w_off=None, fixup=False,
-         xcd=0, softmax_cols=0):
+         xcd=0, softmax_cols=0, region_w=None, regions=0):
     """out = act(alpha * A @ W^T + bias + row_bias) + residual.
 
     The matrix operands (a in rows mode, w, out, residual, row_bias) are contiguous or 2-D views with unit column stride into
@@ -82,7 +82,10 @@ def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=N
     a: fp16 [M, K] (rows mode) or NHWC [N, H, W, C0] with conv=dict(stride=1|2, upsample=bool) (3x3 pad 1);
     conv=dict(stride=2, pad_mode=1): ldm's VAE-encoder Downsample, F.pad(a, (0, 1, 0, 1)) then a 3x3 stride-2 pad-0 conv;
     conv=dict(pad_mode=2 | 3 | 4): seamless tiling, the 3x3 pad-1 border is circular on both axes / x only / y only;
-    a2: optional second NHWC source concatenated on channels; w: fp16 [Nout, K] (conv: K = 9*(C0+C1), KRSC)."""
+    a2: optional second NHWC source concatenated on channels; w: fp16 [Nout, K] (conv: K = 9*(C0+C1), KRSC).
+    region_w (fp32 [rows_per_img, regions]) with regions >= 1: sdod_gemm_region_f16, the softmax epilogue's 80-column groups are laid
+    out [region][head][80] and group g's probabilities at row m are multiplied by region_w[m % rows_per_img, g // (Nout / 80 / regions)];
+    the checks are the library's."""
     lib = _lib.hip()
     lda = _ld(a, torch.float16, 'a', a.shape[-1]) if conv is None else _req(a, torch.float16, 'a').shape[-1]
     d = GemmDesc()
@@ -176,7 +179,10 @@ def gemm(a, w, bias=None, *, residual=None, row_bias=None, rows_per_img=0, act=N
             check(lib.sdod_gemm_time(ctypes.byref(d), _stream(), time_iters, ctypes.byref(ms)))
         return ms.value
     d.phase = phase           # split-K only: 1 = partial slabs only (a GroupNorm may finish the job, group_norm_reduce)
-    check(lib.sdod_gemm_f16(ctypes.byref(d), _stream()))
+    if region_w is not None or regions:
+        check(lib.sdod_gemm_region_f16(ctypes.byref(d), _p(region_w), int(regions), _stream()))
+    else:
+        check(lib.sdod_gemm_f16(ctypes.byref(d), _stream()))
     if return_desc:
         d._keep = (a, w, bias, residual, row_bias, out, a2, bias2)   # the descriptor holds raw pointers
         return out, d
@@ -335,19 +341,26 @@ def attention(q, k, v, heads, scale=None, causal=False, out=None):
     return out
 
 
-def xattn_fold(kv, k_off, v_off, n_img, L, wq, sq, tq, wo, heads, scale=None):
+def xattn_fold(kv, k_off, v_off, n_img, L, wq, sq, tq, wo, heads, scale=None, regions=None):
     """once-per-prompt part of the folded cross-attention (include/sdod_hip.h: sdod_xattn_fold_f16).  kv: fp16 [n_img * L, ld]
     holding K at column k_off and V at v_off; wq: LayerNorm-folded to_q weight with its fold vectors sq, tq (ln_fold); wo: to_out
-    weight.  Returns (w1 [n_img, heads*80, C], s1, t1 [n_img, heads*80], w2 [n_img, C, heads*80])."""
+    weight.  Returns (w1 [n_img, heads*80, C], s1, t1 [n_img, heads*80], w2 [n_img, C, heads*80]).
+    regions=k (sdod_xattn_fold_regions_f16): kv is [n_img * k * L, ld], one segment per (image, region prompt); returns
+    (w1 [n_img, k*heads*80, C], s1, t1 [n_img, k*heads*80], w2 [n_img, C, k*heads*80]), region-major."""
     lib = _lib.hip()
     _req(kv, torch.float16, 'kv'); _req(wq, torch.float16, 'wq'); _req(wo, torch.float16, 'wo')
     _req(sq, torch.float32, 'sq'); _req(tq, torch.float32, 'tq')
     c = wq.shape[0]; d = c // heads
     if scale is None:
         scale = d ** -0.5
-    w1 = torch.empty(n_img, heads * 80, c, dtype=torch.float16, device=kv.device)
-    w2 = torch.empty(n_img, c, heads * 80, dtype=torch.float16, device=kv.device)
-    s1 = torch.empty(n_img, heads * 80, dtype=torch.float32, device=kv.device); t1 = torch.empty_like(s1)
+    nk = heads * 80 * (1 if regions is None else int(regions))
+    w1 = torch.empty(n_img, nk, c, dtype=torch.float16, device=kv.device)
+    w2 = torch.empty(n_img, c, nk, dtype=torch.float16, device=kv.device)
+    s1 = torch.empty(n_img, nk, dtype=torch.float32, device=kv.device); t1 = torch.empty_like(s1)
+    if regions is not None:
+        check(lib.sdod_xattn_fold_regions_f16(_p(kv), kv.shape[-1], k_off, v_off, n_img, int(regions), L, _p(wq), wq.shape[1], _p(sq), _p(tq),
+                                              _p(wo), wo.shape[1], heads, d, scale, _p(w1), _p(s1), _p(t1), _p(w2), _stream()))
+        return w1, s1, t1, w2
     check(lib.sdod_xattn_fold_f16(_p(kv), kv.shape[-1], k_off, v_off, n_img, L, _p(wq), wq.shape[1], _p(sq), _p(tq), _p(wo), wo.shape[1],
                                   heads, d, scale, _p(w1), _p(s1), _p(t1), _p(w2), _stream()))
     return w1, s1, t1, w2
@@ -466,6 +479,45 @@ def add_control(hs, rs, scales):
     segs = (_lib.ControlSeg * max(len(hs), 1))(*[_lib.ControlSeg(h.data_ptr(), r.data_ptr(), h.numel()) for h, r in zip(hs, rs)])
     check(lib.sdod_add_control_f16(segs, len(hs), _p(scales), _stream()))
     return hs
+
+
+def region_weights(masks_u8, out=None):
+    """region masks uint8 [k, 8h, 8w] -> the blend weights of the four UNet levels, fp32 [h/ds * w/ds, k] for ds = 1, 2, 4, 8
+    (sdod_region_weights_f32: integer box sums, one division; region 0 where nothing covers a pixel).  out: the four destinations."""
+    lib = _lib.hip()
+    _req(masks_u8, torch.uint8, 'masks')
+    if masks_u8.dim() != 3:
+        raise ValueError(f'masks must be [regions, 8h, 8w], got {tuple(masks_u8.shape)}')
+    k, ih, iw = masks_u8.shape
+    h, w = ih // 8, iw // 8
+    if ih != 8 * h or iw != 8 * w:
+        raise ValueError(f'mask size {ih} x {iw} is not 8 x a latent size')
+    if out is None:
+        out = [torch.empty((h // ds) * (w // ds), k, dtype=torch.float32, device=masks_u8.device) for ds in (1, 2, 4, 8)]
+    for lvl, o in enumerate(out):
+        _req(o, torch.float32, f'out[{lvl}]')
+        if o.numel() != (h >> lvl) * (w >> lvl) * k:
+            raise ValueError(f'out[{lvl}] holds {o.numel()} floats, the level needs {(h >> lvl) * (w >> lvl) * k}')
+    check(lib.sdod_region_weights_f32(_p(masks_u8), k, h, w, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _stream()))
+    return out
+
+
+def region_blend(a, w, out=None):
+    """out[m] = fp16(sum_r w[m % rows_per_img, r] * a[r, m]) (sdod_region_blend_f16): a fp16 [k, rows, C], w fp32 [rows_per_img, k];
+    acc = w_0 a_0, then acc + w_r a_r, each product and sum rounded in fp32"""
+    lib = _lib.hip()
+    _req(a, torch.float16, 'a'); _req(w, torch.float32, 'w')
+    if a.dim() != 3 or w.dim() != 2 or w.shape[1] != a.shape[0]:
+        raise ValueError(f'a must be [k, rows, C] and w [rows_per_img, k], got {tuple(a.shape)} and {tuple(w.shape)}')
+    k, rows, c = a.shape
+    if out is None:
+        out = torch.empty(rows, c, dtype=torch.float16, device=a.device)
+    else:
+        _req(out, torch.float16, 'out')
+        if out.numel() != rows * c:
+            raise ValueError(f'out holds {out.numel()} halves, need {rows * c}')
+    check(lib.sdod_region_blend_f16(_p(a), rows * c, _p(w), _p(out), rows, w.shape[0], c, k, _stream()))
+    return out
 
 
 def concat_channels(a, b):

@@ -13,6 +13,7 @@ import torch
 from . import engine as E
 from . import ops
 from . import prompts as PR
+from . import regions as RG
 from . import upscale as UP
 from .host import DpmSolver
 from .samplers import K_SAMPLERS, K_SCHEDULES, PLMS_ORDERS, KSchedule, PlmsSchedule
@@ -39,11 +40,12 @@ class Txt2Img:
     adapter_channels = 3
     upscaler = None     # the ESRGAN x4 upscaler (Txt2Img(..., upscaler=True): sdod.amd.upscale.Upscaler), or None
     tiling = 0          # seamless tiling: the wrap bits the UNet and the VAE decoder were built with (bit 0 = x, bit 1 = y)
+    regions = 0         # regional prompts: prompts per image the UNet was built for (Txt2Img(..., regions=k)), 0 = none
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
-                 adapter_channels=3, tiling=False, upscaler=False, controlnet=False):
+                 adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -97,12 +99,24 @@ class Txt2Img:
         E.ControlHint(cfg, 1) encodes one hint image per run.  All three take their weights from state_dicts['controlnet'] (one dict,
         `control_model.` stripped) or models_dir/controlnet.sdodw: set_control_hint() / clear_control_hint().  Off, nothing is
         constructed or sized differently.  Not with cfg_split, hires_hw, inpaint_unet, adapter, tiling or model='sd21': ValueError
-        before any device work (control_check_build).  LoRA adapters re-weight the UNet, not the ControlNet."""
+        before any device work (control_check_build).  LoRA adapters re-weight the UNet, not the ControlNet.
+        regions=k in [2, 4]: regional prompts (sdod/amd/regions.py).  The UNet is built on a config copy with context_len =
+        77 k and regions = k, the text encoder with batch 2 k; encode_regions(prompts, negative) gives the context [2, 77 k, D],
+        set_regions(masks_u8) says where each prompt applies (uint8 [k, 8h, 8w]; region 0 everywhere until then, and after
+        clear_regions()).  Every cross-attention computes sum_r w_r(pixel) attn(x, prompt r).  Works with rectangular latent_hw, loras,
+        with_vae_encoder, upscaler, every sampler and the eager, graphed and pipelined entry points; a captured trajectory picks up new
+        masks without a recapture.  With prompt_chunks > 1, cfg_split, hires_hw, controlnet, adapter, tiling, inpaint_unet, model='sd21'
+        or uint8 weights: ValueError before any device work (regions.regions_check_build).  False: nothing is constructed or sized
+        differently."""
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         latent_h, latent_w = check_latent_hw(latent_hw)
         adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_unet, model)
         control_check_build(controlnet, cfg_split, hires_hw, inpaint_unet, adapter, tiling, model)
         self.tiling = tiling_check_build(tiling, with_vae_encoder, inpaint_unet, hires_hw, adapter)
+        quant_asked = bool(regions) and (weight_quant or (weight_quant is None and state_dicts is not None and any(
+            hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts.get('unet', {}).values())))      # (uint8 codes decide it, as below)
+        self.regions = RG.regions_check_build(regions, self.prompt_chunks, cfg_split, hires_hw, controlnet, adapter, tiling, inpaint_unet,
+                                              model, quant_asked)
         up_args = upscaler_check_build(upscaler, tiling, hires_hw if hires_hw is not None else latent_hw, state_dicts, models_dir)
         if hires_hw is not None:
             check_latent_hw(hires_hw, 'hires_hw')
@@ -154,13 +168,17 @@ class Txt2Img:
         if controlnet:                   # 13 residual slots and their scales, filled by the control graph built below
             unet_cfg = E.copy_config(unet_cfg)
             unet_cfg.control_inputs = 1
+        if self.regions:                 # k prompts per image: only the UNet sees the k-fold context and has the weight inputs
+            unet_cfg = E.copy_config(unet_cfg)
+            unet_cfg.context_len = PR.CHUNK_LEN * self.regions
+            unet_cfg.regions = self.regions
         vae_cfg = self.cfg
         if self.tiling:                  # the UNet and the VAE decoder take the circular border; every other graph has no border to wrap
             unet_cfg, vae_cfg = E.copy_config(unet_cfg), E.copy_config(self.cfg)
             unet_cfg.tiling = vae_cfg.tiling = self.tiling
         self.unet = E.UNet(unet_cfg, self.n if cfg_split else 2 * self.n, device)
         self.vae = E.VaeDecoder(vae_cfg, 1, device) if with_vae else None
-        self.text = E.TextEncoder(self.cfg, 2 * self.prompt_chunks, device) if with_text_encoder else None
+        self.text = E.TextEncoder(self.cfg, 2 * (self.regions or self.prompt_chunks), device) if with_text_encoder else None
         self.encoder = E.VaeEncoder(self.cfg, 1, device) if with_vae_encoder else None
         self.masked_encoder = E.MaskedVaeEncoder(self.cfg, 1, device) if self.inpaint_unet else None
         if adapter:
@@ -307,6 +325,36 @@ class Txt2Img:
         self.unet.control_scale.zero_()
         self._control_on = False
 
+    # ------------------------------------------------------------------ regional prompts
+    def set_regions(self, masks_u8):
+        """masks_u8: uint8 [regions, 8h, 8w] at image resolution (torch or numpy; 255 = inside, soft and overlapping masks allowed,
+        regions.column_masks / row_masks / feather make the common ones): where each of encode_regions' prompts applies, for every image
+        of the batch and both guidance halves.  One launch (ops.region_weights) writes the four levels' weights into the UNet's inputs,
+        which its kernels read in every evaluation: captured trajectories pick them up without a recapture.  ValueError for a wrong
+        dtype, shape or region count (regions.regions_check_args), before any device work; RuntimeError without regions."""
+        masks = RG.regions_check_args(self, masks_u8)
+        ops.region_weights(masks.to(self.device), out=self.unet.region_w)
+
+    def clear_regions(self):
+        """region 0 everywhere, the state after construction: every pixel takes the first prompt"""
+        if not self.regions:
+            raise RuntimeError('this pipeline was built without regions: Txt2Img(..., regions=k) is needed for regional prompts')
+        for w in self.unet.region_w:
+            w.zero_()
+            w[:, 0] = 1.0
+
+    def encode_regions(self, prompts, negative=''):
+        """prompts: exactly `regions` literal texts (CLIP's one window each, no emphasis grammar), region 0 first.  Returns the context
+        fp16 [2, 77 regions, D]: the unconditional row holds the negative prompt's encoding once per region, the conditional row the
+        prompts' encodings in order.  ONE text-encoder execute (the encode_chunks path)."""
+        prompts = RG.regions_check_prompts(self, prompts)
+        if not isinstance(negative, str):
+            raise ValueError('negative must be a string: per-region negative prompts are not supported')
+        if self.tokenizer is None:
+            raise ValueError('encode_regions needs the pipeline\'s tokenizer (Txt2Img(..., tokenizer=host.Tokenizer(path)))')
+        neg = np.asarray(self._ids(negative))
+        return self.encode_chunks(np.stack([neg] * self.regions), np.stack([np.asarray(self._ids(p)) for p in prompts]))
+
     def clear_adapter_hint(self):
         """zero the UNet's feature slots: the unconditioned model again (its additions of zero change no bit)"""
         if self.adapter is None:
@@ -351,14 +399,15 @@ class Txt2Img:
         text-encoder execute on the ids laid out as (uncond chunks ; cond chunks): its output [2 k, 77, D] already is the
         concatenation along the key axis.  With weights one more launch, ops.context_assemble (token rows scaled, each chunk's mean
         restored); without, none.  Shape or dtype errors raise ValueError before any device work."""
-        k = self.prompt_chunks
+        k = self.regions or self.prompt_chunks     # (regional prompts: one window per region in the place of the chunks)
         both = []
         for name, ids in (('ids_uncond', ids_uncond), ('ids_cond', ids_cond)):
             ids = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
             if ids.dtype.kind not in 'iu':
                 raise ValueError(f'{name} must be an integer array, got {ids.dtype}')
             if ids.shape != (k, PR.CHUNK_LEN):
-                raise ValueError(f'{name} must be {(k, PR.CHUNK_LEN)} (this pipeline was built with prompt_chunks={k}), got {ids.shape}')
+                built = f'regions={k}' if self.regions else f'prompt_chunks={k}'
+                raise ValueError(f'{name} must be {(k, PR.CHUNK_LEN)} (this pipeline was built with {built}), got {ids.shape}')
             vocab = getattr(getattr(self, 'cfg', None), 'vocab_size', None)
             if ids.min() < 0 or (vocab is not None and ids.max() >= vocab):
                 raise ValueError(f'{name} holds ids outside the vocabulary [0, {vocab})')

@@ -7,6 +7,7 @@ Builds every graph of the configurations the benches and the GPU tests use with 
 every process builds the same launch lists without timing anything.
 
 usage (GPU box):  python tools/make_tune_cache.py gpurun_out/gfx950.tune [--quick | --only-quant | --only-rows3 | --only-ln | --only-new]
+                  python tools/make_tune_cache.py out/gfx950_regions.tune --only-regions    (-> tune/gfx950_regions.tune)
 NEVER run under a profiler (timing noise would be baked into the picks)."""
 import os
 import sys
@@ -27,7 +28,8 @@ only_tail = '--only-tail' in sys.argv     # re-time the 3x3 convolutions with a 
 only_new = '--only-new' in sys.argv       # keep EVERY shipped pick, time only the shapes the table does not have yet (a new fusion's GEMMs)
 only_vae_enc = '--only-vae-encoder' in sys.argv  # keep EVERY shipped pick, time the VAE encoder's new shapes (img2img; key flag bit 26 = pad_mode)
 only_rect = '--only-rect' in sys.argv      # keep EVERY shipped pick, time the sd14 shapes at 64 x 96, 96 x 64 and 96 x 96 (rectangular sizes, the hires pass)
-only_new = only_new or only_vae_enc or only_rect
+only_regions = '--only-regions' in sys.argv  # keep EVERY pick of gfx950.tune and gfx950_control.tune, time the regional-prompt UNets' new shapes, write ONLY those
+only_new = only_new or only_vae_enc or only_rect or only_regions
 if os.path.exists(out):
     os.remove(out)
 os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -55,6 +57,11 @@ if only_quant or only_rows3 or only_ln or only_new or only_n160 or only_geglu or
                 drop = (int(v[10]) & (1 << 29)) if only_quant else (v[0] == '1' and v[6] == '1' and v[8] == '3' and int(v[9]) % 3 == 0)
             if not drop:
                 g.write(line)
+    if only_regions:   # the second table's picks too: the output is what NEITHER table holds
+        with open(shipped.replace('.tune', '_control.tune')) as f, open(out, 'a') as g:
+            g.writelines(line for line in f if len(line.split()) == 15)
+        with open(out) as f:
+            known = set(f.read().splitlines())
 os.environ['SDOD_TUNE_CACHE'] = out
 os.environ['SDOD_TUNE_DEFAULT'] = '0'
 
@@ -84,6 +91,23 @@ def vae_encoders():
 if only_vae_enc:
     vae_encoders()
     print(f'done: {out}')
+    sys.exit(0)
+
+if only_regions:
+    # the sizes tests/test_regions_gpu.py and tools/regions_bench.py build: 16 x 16, 8 x 16 and 64 x 64 at batch 2, 2 and 3 regions; the
+    # text encoder at batch 2 k (Txt2Img(regions=k).encode_regions)
+    for h, w in ((16, 16), (8, 16), (64, 64)):
+        for k in (2, 3):
+            c = E.sd14_config(h, w)
+            c.context_len, c.regions = 77 * k, k
+            build(E.UNet, c, 2, 1234, f'sd14 unet {h}x{w} b2, {k} regions')
+    for k in (2, 3):
+        build(E.TextEncoder, E.sd14_config(16, 16), 2 * k, 1237, f'clip-L b{2 * k}')
+    with open(out) as f:
+        new = [line for line in f.read().splitlines() if line not in known]
+    with open(out, 'w') as f:
+        f.write(''.join(line + '\n' for line in new))
+    print(f'done: {out} ({len(new)} new shapes)')
     sys.exit(0)
 
 if only_rect:
