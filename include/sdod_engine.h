@@ -64,6 +64,17 @@
  *                 64 / 128 (the GEMM needs K % 64 == 0), which is exact: zero weights, zero bias and SiLU(0) = 0 keep the padded
  *                 channels zero.  The parameter table lists the PADDED shapes; whoever sets the parameters pads (sdod.amd.engine's
  *                 ControlHint does).  Runs once per hint, not once per step
+ *   UNET with sdod_ip_config.ip_tokens = T (image prompts): behind every other input, ip_ctx fp16 [B][T][ctx_dim] (static
+ *                 over a sampler run, like in2) and four inputs ip_w fp32 [H / ds * W / ds][2], ds = 1, 2, 4, 8; (1, 0) after finalize
+ *   IMAGE_ENCODER in0 img uint8 HWC [B][S][S][3] (resized and cropped by the caller); out0 fp16 [B][proj_dim]: HF
+ *                 CLIPVisionModelWithProjection's image_embeds -- CLIP's mean / std normalisation, patch embedding, class token and
+ *                 position embedding, pre_layrnorm, the encoder layers, post_layernorm and visual_projection on the class token.
+ *                 Parameters by HF's names (vision_model.embeddings.*, vision_model.pre_layrnorm.*, vision_model.encoder.layers.N.*,
+ *                 vision_model.post_layernorm.*, visual_projection.weight).  The table lists patch_embedding.weight as the matrix
+ *                 [width][Kpad] (the conv weight flattened, zero-padded from 3 p^2 to the next multiple of 64) and class_embedding as
+ *                 [1][width]; whoever sets the parameters reshapes and pads (sdod.amd.engine's ImageEncoder does)
+ *   IMAGE_PROJ    in0 fp16 [B][proj_dim] (image_embeds); out0 fp16 [B][T][ctx_dim] = LayerNorm(Linear(in0).reshape(T, ctx_dim)):
+ *                 IP-Adapter's ImageProjModel, parameters proj.weight / proj.bias / norm.weight / norm.bias
  *   TEMB with sdod_control_config.control_temb: the time conditioning of a CONTROLNET graph, out0 fp16 [B][E_c]: the checkpoint's own
  *                 time_embed.* and the emb_layers of its ten ResBlocks (8 input blocks, 2 middle), E_c = 30 MC
  *
@@ -89,7 +100,7 @@ extern "C" {
 
 enum sdod_graph_kind { SDOD_GRAPH_UNET = 0, SDOD_GRAPH_VAE_DECODER = 1, SDOD_GRAPH_TEXT_ENCODER = 2, SDOD_GRAPH_TEMB = 3,
                        SDOD_GRAPH_VAE_ENCODER = 4, SDOD_GRAPH_VAE_ENCODER_MASKED = 5, SDOD_GRAPH_ADAPTER = 6, SDOD_GRAPH_UPSCALER = 7,
-                       SDOD_GRAPH_CONTROLNET = 8, SDOD_GRAPH_CONTROL_HINT = 9 };
+                       SDOD_GRAPH_CONTROLNET = 8, SDOD_GRAPH_CONTROL_HINT = 9, SDOD_GRAPH_IMAGE_ENCODER = 10, SDOD_GRAPH_IMAGE_PROJ = 11 };
 
 typedef struct sdod_model_config {
     int latent_channels; /* 4 */
@@ -187,6 +198,35 @@ typedef struct sdod_region_config {
     int regions; /* prompts per image */
 } sdod_region_config;
 SDOD_API int sdod_graph_create_regions(void** graph, int kind, const sdod_model_config* cfg, const sdod_region_config* regions, int batch);
+/* Image prompts (IP-Adapter's decoupled cross-attention), UNET graph only.  ip_tokens = T > 0: behind every other
+ * input the graph gets ip_ctx fp16 [B][T][ctx_dim] (the projected image tokens; static over a sampler run like the text context) and
+ * four inputs ip_w[level], fp32 [H / ds * W / ds][2] for ds = 1, 2, 4, 8 (what sdod_ip_weights_f32 writes), shared by all images
+ * of the batch and (1, 0) after finalize.  Every transformer block has two more parameters, `...attn2.to_k_ip.weight` and
+ * `...attn2.to_v_ip.weight` [C][ctx_dim], and every cross-attention computes
+ *   to_out(w_0(pixel) attn(q, K_text, V_text) + w_1(pixel) attn(q, to_k_ip(ip_ctx), to_v_ip(ip_ctx))) + bias.
+ * The weights are read by the kernels in the launch, so a captured graph picks up new ones; with w_1 = 0 the image segment
+ * contributes exact zeros.  T in [1, 16]; context_len <= 80; no weight_quant and no concat_channels.  ip == NULL or all zero builds
+ * exactly what sdod_graph_create builds. */
+typedef struct sdod_ip_config {
+    int ip_tokens; /* image tokens per image: 4 for ip-adapter_sd15 */
+} sdod_ip_config;
+SDOD_API int sdod_graph_create_ip(void** graph, int kind, const sdod_model_config* cfg, const sdod_ip_config* ip, int batch);
+/* The image side of an image prompt: the kinds SDOD_GRAPH_IMAGE_ENCODER and SDOD_GRAPH_IMAGE_PROJ can only be created
+ * here; every other create function refuses them.  IMAGE_ENCODER reads `vision` alone (cfg and ip may be NULL); IMAGE_PROJ reads
+ * vision->proj_dim, cfg->context_dim and ip->ip_tokens.  Both always keep fp16 weights and run once per image prompt, not per step.
+ * ViT-H/14, the encoder of ip-adapter_sd15: {224, 14, 1280, 32, 16, 5120, 1024, 0}. */
+typedef struct sdod_vision_config {
+    int image_size; /* S: the input is [B][S][S][3]; a multiple of patch */
+    int patch;      /* patch size p; the patch-embedding rows are 3 p^2 long, zero-padded to the next multiple of 64 */
+    int width;      /* hidden size, a multiple of 64 */
+    int layers;     /* encoder layers */
+    int heads;      /* width / heads must be 64 or 80 */
+    int mlp_dim;    /* intermediate size, a multiple of 64 */
+    int proj_dim;   /* width of image_embeds, a multiple of 64 */
+    int quick_gelu; /* 1: x sigmoid(1.702 x) (OpenAI CLIP); 0: erf GELU (OpenCLIP ViT-H / bigG) */
+} sdod_vision_config;
+SDOD_API int sdod_graph_create_vision(void** graph, int kind, const sdod_model_config* cfg, const sdod_vision_config* vision, const sdod_ip_config* ip,
+                                      int batch);
 /* Before sdod_graph_finalize: output `index` of the graph is written to device_ptr (memory the caller owns, typically an input slot
  * of another graph, so that nothing is copied between the two per run) instead of a slot the graph allocates.  bytes must equal the
  * output's size and device_ptr be 256-byte aligned, else INVALID_ARGUMENT.  sdod_graph_io then reports device_ptr.  Unbound outputs

@@ -293,6 +293,15 @@ SDOD_API int sdod_xattn_fold_regions_f16(const void* kv, int ld_kv, int k_off, i
                                          int ldq, const void* sq, const void* tq, const void* wo, int ldwo, int heads, int d, float scale,
                                          void* w1, void* s1, void* t1, void* w2, void* stream);
 
+/* The same for an image prompt (IP-Adapter's decoupled cross-attention): two segments per image from two sources.
+ * Segment 0 of image b is rows [b L, b L + L) of kv (the text keys, as in sdod_xattn_fold_f16); segment 1 is rows [b T, b T + T) of
+ * kv_ip (the image tokens), which has a row stride and K / V offsets of its own.  w1 / s1 / t1 / w2 have the layout
+ * sdod_xattn_fold_regions_f16 writes for regions = 2, and each slice is bit for bit what sdod_xattn_fold_f16 writes for that source
+ * alone, padding columns included (s = 0, t = -30000, w2 zero).  1 <= T <= 16; k_off_ip / v_off_ip + heads * d <= ld_ip. */
+SDOD_API int sdod_xattn_fold_ip_f16(const void* kv, int ld_kv, int k_off, int v_off, const void* kv_ip, int ld_ip, int k_off_ip, int v_off_ip,
+                                    int n_img, int L, int T, const void* wq, int ldq, const void* sq, const void* tq, const void* wo, int ldwo,
+                                    int heads, int d, float scale, void* w1, void* s1, void* t1, void* w2, void* stream);
+
 /* Row softmax on fp16 [M][N] in place semantics allowed (y may equal x); fp32 math. */
 SDOD_API int sdod_softmax_rows_f16(const void* x, void* y, int m, int n, void* stream);
 
@@ -312,6 +321,24 @@ SDOD_API int sdod_region_weights_f32(const uint8_t* masks, int regions, int h, i
  * divides rows, a and out 16-byte aligned.  out may be a's first tensor. */
 SDOD_API int sdod_region_blend_f16(const void* a, size_t region_stride, const float* w, void* out, int rows, int rows_per_img, int c, int regions,
                                    void* stream);
+/* ---- Image prompts.  The per-pixel weights of the two cross-attention segments (text, image tokens) at the four
+ * UNet levels, one launch: w1 / w2 / w4 / w8 fp32 [h / ds * w / ds][2] for ds = 1, 2, 4, 8.  Column 0 is 1.0f; column 1 is
+ * scale * ((float)S / (float)(255 * (8 ds)^2)), S the integer sum of mask (uint8 [8 h][8 w], 255 = the image prompt fully applies)
+ * over the level pixel, the division and the multiply each rounded once in fp32.  mask == NULL: scale everywhere.  h, w multiples of
+ * 8 in [8, 1024]; scale finite and >= 0; mask 16-byte aligned. */
+SDOD_API int sdod_ip_weights_f32(const uint8_t* mask, float scale, int h, int w, float* w1, float* w2, float* w4, float* w8, void* stream);
+/* The CLIP vision tower's input side (graph kind SDOD_GRAPH_IMAGE_ENCODER).
+ * sdod_patch_embed_u8_f16: img uint8 HWC [n][S][S][3], S a multiple of patch -> out fp16 [n * (S / patch)^2][kpad], the rows of the
+ * patch-embedding GEMM, patches row-major.  Column c * p * p + dy * p + dx (the conv weight's flattening) is
+ * fp16(((float)u / 255 - mean3[c]) / std3[c]), every operation rounded on its own in fp32; columns from 3 p * p up to kpad, which
+ * must be 3 p * p rounded up to a multiple of 64, are zero.  mean3 / std3 are host pointers (CLIP's constants), std > 0.
+ * sdod_vit_tokens_f16: patches fp16 [n][P][W] (the GEMM's output), class_embedding fp16 [W], position_embedding fp16 [P + 1][W],
+ * LayerNorm weight / bias fp32 [W] -> out fp16 [n][P + 1][W]: row 0 = LN(class + pos_0), row 1 + i = LN(patch_i + pos_{1 + i}); fp32
+ * math, one fp16 rounding. */
+SDOD_API int sdod_patch_embed_u8_f16(const uint8_t* img, void* out, int n, int image_size, int patch, int kpad, const float* mean3, const float* std3,
+                                     void* stream);
+SDOD_API int sdod_vit_tokens_f16(const void* patches, const void* class_embedding, const void* position_embedding, const float* ln_weight,
+                                 const float* ln_bias, void* out, int n, int num_patches, int width, float eps, void* stream);
 SDOD_API int sdod_concat_channels_f16(const void* a, const void* b, void* y, size_t rows, int c0, int c1, void* stream);
 /* ---- T2I-Adapter structural control (graph kind SDOD_GRAPH_ADAPTER of include/sdod_engine.h).  Each of the four
  * checks its arguments and returns INVALID_ARGUMENT before any launch, the destination untouched; fp32 arithmetic, every operation

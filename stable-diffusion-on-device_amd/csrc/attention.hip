@@ -558,12 +558,32 @@ struct FoldP {
     int n_w;     // work items of W1 (and of W2): n_img * heads * tiles_c
     int regions; // sdod_xattn_fold_regions_f16: n_img counts (image, region) segments; W2 puts a segment's columns behind its image's
                  // earlier regions, [C][regions * NK].  1 = one segment per image
+    // sdod_xattn_fold_ip_f16 (regions == 2): the odd segments come from a second K/V source with a length and strides of its own
+    const f16* kv2; int ld_kv2, k_off2, v_off2, L2; // kv2 == nullptr: every segment from kv
 };
 constexpr int kFoldKMax = 160;
+// where segment `seg` of n_img finds its keys and values: rows [0, L) at k / v, row stride ld.  TWO_SRC is a compile-time switch so
+// that the one-source kernel, which every plain graph runs 16 times per prompt, carries no test of kv2 and no pointer selects
+struct FoldSeg { const f16* k; const f16* v; int ld, L; };
+template <bool TWO_SRC>
+__device__ __forceinline__ FoldSeg fold_segment(const FoldP& p, int seg) {
+    if constexpr (!TWO_SRC) {
+        const f16* base = p.kv + (long long)seg * p.L * p.ld_kv;
+        return FoldSeg{base + p.k_off, base + p.v_off, p.ld_kv, p.L};
+    }
+    const int b = seg >> 1; // segment 2 b = image b's text keys, 2 b + 1 = its image tokens
+    if (seg & 1) {
+        const f16* base = p.kv2 + (long long)b * p.L2 * p.ld_kv2;
+        return FoldSeg{base + p.k_off2, base + p.v_off2, p.ld_kv2, p.L2};
+    }
+    const f16* base = p.kv + (long long)b * p.L * p.ld_kv;
+    return FoldSeg{base + p.k_off, base + p.v_off, p.ld_kv, p.L};
+}
 // One launch per transformer block: workgroups [0, n_w) build 80 x 80 tiles of W1 (rows = a head's 80 key slots, columns = 80
 // input channels), [n_w, 2 n_w) tiles of W2 (rows = 80 output channels, columns = a head's key slots), the rest the fold
 // vectors.  Both products contract over the head dimension d (<= 160, zero-padded to the MFMA's 32): operands staged in LDS as
 // [row][k], v_mfma_f32_16x16x32_f16, 5 x 5 blocks of 16 x 16 per tile over 4 waves.
+template <bool TWO_SRC>
 __global__ __launch_bounds__(256) void xattn_fold_kernel(const FoldP p) {
     __shared__ __attribute__((aligned(16))) f16 sa[80][kFoldKMax + 8], sb[80][kFoldKMax + 8];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -575,12 +595,13 @@ __global__ __launch_bounds__(256) void xattn_fold_kernel(const FoldP p) {
         const int idx = (item - 2 * p.n_w) * 256 + tid;
         if (idx >= p.n_img * NK) return;
         const int j = idx % 80, bh = idx / 80, h = bh % p.heads, img = bh / p.heads;
-        if (j >= p.L) {
+        const FoldSeg sg = fold_segment<TWO_SRC>(p, img);
+        if (j >= sg.L) {
             p.s1[idx] = 0.f;
             p.t1[idx] = -30000.f;
             return;
         }
-        const f16* kr = p.kv + ((long long)img * p.L + j) * p.ld_kv + p.k_off + h * d;
+        const f16* kr = sg.k + (long long)j * sg.ld + h * d;
         float a = 0.f, b = 0.f;
         for (int dd = 0; dd < d; ++dd) {
             const float kval = (float)kr[dd];
@@ -595,6 +616,7 @@ __global__ __launch_bounds__(256) void xattn_fold_kernel(const FoldP p) {
     if (second) item -= p.n_w;
     const int tc = item % p.tiles_c, bh = item / p.tiles_c, h = bh % p.heads, img = bh / p.heads;
     const int KP = (d + 31) & ~31, kc = KP / 8;
+    const FoldSeg sg = fold_segment<TWO_SRC>(p, img);
     // rows of K / V (key slots; slots past L and columns past d are zero) and of Wo: contiguous along k, 16-byte pieces
     auto stage_rows = [&](f16 (*dst)[kFoldKMax + 8], const f16* base, long long row_stride, int valid_rows) {
         for (int idx = tid; idx < 80 * kc; idx += 256) {
@@ -604,7 +626,7 @@ __global__ __launch_bounds__(256) void xattn_fold_kernel(const FoldP p) {
         }
     };
     if (!second) {
-        stage_rows(sa, p.kv + (long long)img * p.L * p.ld_kv + p.k_off + h * d, p.ld_kv, p.L);
+        stage_rows(sa, sg.k + h * d, sg.ld, sg.L);
         // Wq'[(h, k)][c]: contiguous along c -> transposed into [c][k]
         for (int idx = tid; idx < KP * 10; idx += 256) {
             const int k = idx / 10, ch = idx - k * 10;
@@ -614,7 +636,7 @@ __global__ __launch_bounds__(256) void xattn_fold_kernel(const FoldP p) {
         }
     } else {
         stage_rows(sa, p.wo + (long long)(tc * 80) * p.ldwo + h * d, p.ldwo, 80);
-        stage_rows(sb, p.kv + (long long)img * p.L * p.ld_kv + p.v_off + h * d, p.ld_kv, p.L);
+        stage_rows(sb, sg.v + h * d, sg.ld, sg.L);
     }
     __syncthreads();
     const int fr = lane & 15, fg = lane >> 4;
@@ -694,11 +716,21 @@ extern "C" int sdod_attention_f16(const void* q, const void* k, const void* v, v
 }
 
 namespace {
+// the image-token source of sdod_xattn_fold_ip_f16; kv == nullptr for the one-source calls
+struct FoldSrc2 { const void* kv; int ld, k_off, v_off, L; };
 int xattn_fold_launch(const void* kv, int ld_kv, int k_off, int v_off, int n_img, int regions, int L, const void* wq, int ldq, const void* sq,
                       const void* tq, const void* wo, int ldwo, int heads, int d, float scale, void* w1, void* s1, void* t1, void* w2,
-                      void* stream) {
+                      void* stream, const FoldSrc2& ip = FoldSrc2{nullptr, 0, 0, 0, 0}) {
     SDOD_TRY
     SDOD_REQUIRE(regions >= 1 && regions <= 4, "regions must be in [1, 4]");
+    if (ip.kv) {
+        SDOD_REQUIRE(regions == 2, "two sources are two segments per image");
+        SDOD_REQUIRE(ip.L >= 1 && ip.L <= 16, "image tokens must be in [1, 16]");
+        SDOD_REQUIRE(ip.ld % 8 == 0 && ip.k_off % 8 == 0 && ip.v_off % 8 == 0 && ip.k_off >= 0 && ip.v_off >= 0 && ((uintptr_t)ip.kv & 15) == 0,
+                     "operands must keep 16-byte alignment");
+        SDOD_REQUIRE(heads > 0 && d > 0 && (long long)ip.k_off + (long long)heads * d <= ip.ld && (long long)ip.v_off + (long long)heads * d <= ip.ld,
+                     "image K / V offsets + heads * d must fit the image row stride");
+    }
     SDOD_REQUIRE(n_img <= (1 << 20), "bad shape (too many images)");
     n_img *= regions; // (image, region) segments of L rows
     SDOD_REQUIRE(kv && wq && sq && tq && wo && w1 && s1 && t1 && w2, "null pointer");
@@ -718,8 +750,10 @@ int xattn_fold_launch(const void* kv, int ld_kv, int k_off, int v_off, int n_img
     p.tiles_c = C / 80;
     p.n_w = n_img * heads * p.tiles_c;
     p.regions = regions;
+    p.kv2 = (const f16*)ip.kv; p.ld_kv2 = ip.ld; p.k_off2 = ip.k_off; p.v_off2 = ip.v_off; p.L2 = ip.L;
     const int blocks = 2 * p.n_w + (n_img * NK + 255) / 256;
-    SDOD_LAUNCH(xattn_fold_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    if (ip.kv) SDOD_LAUNCH(xattn_fold_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    else SDOD_LAUNCH(xattn_fold_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     SDOD_HIP_CHECK(hipGetLastError());
     return 0;
     SDOD_CATCH
@@ -736,4 +770,14 @@ extern "C" int sdod_xattn_fold_regions_f16(const void* kv, int ld_kv, int k_off,
                                            int ldq, const void* sq, const void* tq, const void* wo, int ldwo, int heads, int d, float scale,
                                            void* w1, void* s1, void* t1, void* w2, void* stream) {
     return xattn_fold_launch(kv, ld_kv, k_off, v_off, n_img, regions, L, wq, ldq, sq, tq, wo, ldwo, heads, d, scale, w1, s1, t1, w2, stream);
+}
+
+extern "C" int sdod_xattn_fold_ip_f16(const void* kv, int ld_kv, int k_off, int v_off, const void* kv_ip, int ld_ip, int k_off_ip, int v_off_ip,
+                                      int n_img, int L, int T, const void* wq, int ldq, const void* sq, const void* tq, const void* wo, int ldwo,
+                                      int heads, int d, float scale, void* w1, void* s1, void* t1, void* w2, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(kv_ip, "null pointer");
+    SDOD_CATCH
+    return xattn_fold_launch(kv, ld_kv, k_off, v_off, n_img, 2, L, wq, ldq, sq, tq, wo, ldwo, heads, d, scale, w1, s1, t1, w2, stream,
+                             FoldSrc2{kv_ip, ld_ip, k_off_ip, v_off_ip, T});
 }

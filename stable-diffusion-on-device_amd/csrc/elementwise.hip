@@ -183,16 +183,16 @@ struct RegionWeightsP {
     int h, w, k;   // latent size (multiples of 8), regions
 };
 
-__global__ __launch_bounds__(256) void region_weights_kernel(const RegionWeightsP p) {
-    __shared__ int s[4][85]; // per region: 64 + 16 + 4 + 1 sums, level after level
+// The mask sums of one pixel of the coarsest level (workgroup (cy, cx), 256 threads), shared by the region and the image-prompt
+// weights: s[r] = 64 + 16 + 4 + 1 integer sums of mask r, level after level.  Ends behind a barrier.
+SDOD_DEVICE void mask_level_sums(int (*s)[85], const uint8_t* masks, int k, int h, int w, int cy, int cx) {
     const int tid = threadIdx.x;
-    const int cw = p.w >> 3, cy = blockIdx.x / cw, cx = blockIdx.x - cy * cw;
-    const size_t iw = (size_t)p.w * 8, plane = (size_t)p.h * 8 * iw;
+    const size_t iw = (size_t)w * 8, plane = (size_t)h * 8 * iw;
     for (int i = tid; i < 4 * 85; i += 256) s[i / 85][i % 85] = 0;
     __syncthreads();
     const int pix = tid >> 2, q = tid & 3, py = pix >> 3, px = pix & 7;
-    for (int r = 0; r < p.k; ++r) {
-        const uint8_t* src = p.masks + r * plane + ((size_t)cy * 64 + py * 8 + q * 2) * iw + (size_t)cx * 64 + px * 8;
+    for (int r = 0; r < k; ++r) {
+        const uint8_t* src = masks + r * plane + ((size_t)cy * 64 + py * 8 + q * 2) * iw + (size_t)cx * 64 + px * 8;
         int acc = 0;
 #pragma unroll
         for (int row = 0; row < 2; ++row) {
@@ -205,22 +205,51 @@ __global__ __launch_bounds__(256) void region_weights_kernel(const RegionWeights
     __syncthreads();
     // the coarser levels: cell j of a level with n x n cells sums its 2 x 2 children
     for (int n = 4, src = 0, dst = 64; n >= 1; src = dst, dst += n * n, n >>= 1) {
-        for (int i = tid; i < p.k * n * n; i += 256) {
+        for (int i = tid; i < k * n * n; i += 256) {
             const int r = i / (n * n), j = i - r * n * n, y = j / n, x = j - y * n;
             const int* c = &s[r][src + (2 * y) * (2 * n) + 2 * x];
             s[r][dst + j] = (c[0] + c[1]) + (c[2 * n] + c[2 * n + 1]);
         }
         __syncthreads();
     }
-    for (int i = tid; i < 85; i += 256) {
-        const int lvl = i < 64 ? 0 : i < 80 ? 1 : i < 84 ? 2 : 3;
-        const int n = 8 >> lvl, j = i - (lvl == 0 ? 0 : lvl == 1 ? 64 : lvl == 2 ? 80 : 84);
-        const int y = j / n, x = j - y * n;
+}
+// sum i of the 85 -> its level (ds = 1 << lvl) and its pixel's row in that level's [h / ds * w / ds] output
+SDOD_DEVICE size_t mask_level_pixel(int i, int cy, int cx, int cw, int& lvl) {
+    lvl = i < 64 ? 0 : i < 80 ? 1 : i < 84 ? 2 : 3;
+    const int n = 8 >> lvl, j = i - (lvl == 0 ? 0 : lvl == 1 ? 64 : lvl == 2 ? 80 : 84);
+    const int y = j / n, x = j - y * n;
+    return (size_t)(cy * n + y) * (cw * n) + cx * n + x;
+}
+
+__global__ __launch_bounds__(256) void region_weights_kernel(const RegionWeightsP p) {
+    __shared__ int s[4][85];
+    const int cw = p.w >> 3, cy = blockIdx.x / cw, cx = blockIdx.x - cy * cw;
+    mask_level_sums(s, p.masks, p.k, p.h, p.w, cy, cx);
+    for (int i = threadIdx.x; i < 85; i += 256) {
+        int lvl;
+        const size_t pixel = mask_level_pixel(i, cy, cx, cw, lvl);
         int tot = 0;
         for (int r = 0; r < p.k; ++r) tot += s[r][i];
-        float* o = p.out[lvl] + ((size_t)(cy * n + y) * (cw * n) + cx * n + x) * p.k;
+        float* o = p.out[lvl] + pixel * p.k;
         for (int r = 0; r < p.k; ++r) // nothing covers the pixel: region 0 is the background
             o[r] = tot == 0 ? (r == 0 ? 1.0f : 0.0f) : div_rn((float)s[r][i], (float)tot);
+    }
+}
+
+// ---- Image prompts (include/sdod_hip.h).  The weights of the two cross-attention segments (text, image tokens) at
+// the four levels: (1, scale * S / (255 (8 ds)^2)) with S the mask's integer sum over the level pixel; without a mask the pixel
+// counts as fully covered.  RegionWeightsP with k = 1 (masks may be null).
+__global__ __launch_bounds__(256) void ip_weights_kernel(const RegionWeightsP p, float scale) {
+    __shared__ int s[4][85];
+    const int cw = p.w >> 3, cy = blockIdx.x / cw, cx = blockIdx.x - cy * cw;
+    if (p.masks) mask_level_sums(s, p.masks, 1, p.h, p.w, cy, cx); // (uniform over the grid)
+    for (int i = threadIdx.x; i < 85; i += 256) {
+        int lvl;
+        const size_t pixel = mask_level_pixel(i, cy, cx, cw, lvl);
+        const int full = 255 * (64 << (2 * lvl)); // 255 (8 ds)^2
+        float* o = p.out[lvl] + pixel * 2;
+        o[0] = 1.0f;
+        o[1] = mul_rn(scale, div_rn((float)(p.masks ? s[0][i] : full), (float)full));
     }
 }
 
@@ -1250,6 +1279,22 @@ extern "C" int sdod_region_weights_f32(const uint8_t* masks, int regions, int h,
     SDOD_CATCH
 }
 
+extern "C" int sdod_ip_weights_f32(const uint8_t* mask, float scale, int h, int w, float* w1, float* w2, float* w4, float* w8, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(w1 && w2 && w4 && w8, "null pointer");
+    SDOD_REQUIRE(std::isfinite(scale) && scale >= 0.f, "scale must be finite and >= 0");
+    SDOD_REQUIRE(h >= 8 && w >= 8 && h % 8 == 0 && w % 8 == 0 && h <= 1024 && w <= 1024, "h and w (latent pixels) must be multiples of 8 in [8, 1024]");
+    SDOD_REQUIRE(((uintptr_t)mask & 15) == 0 && (((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)w4 | (uintptr_t)w8) & 7) == 0, "misaligned pointer (mask: 16 bytes)");
+    RegionWeightsP p{};
+    p.masks = mask;
+    p.out[0] = w1; p.out[1] = w2; p.out[2] = w4; p.out[3] = w8;
+    p.h = h; p.w = w; p.k = 1;
+    SDOD_LAUNCH(ip_weights_kernel, dim3((unsigned)((h / 8) * (w / 8))), dim3(256), 0, (hipStream_t)stream, p, scale);
+    SDOD_HIP_CHECK(hipGetLastError());
+    return 0;
+    SDOD_CATCH
+}
+
 extern "C" int sdod_region_blend_f16(const void* a, size_t region_stride, const float* w, void* out, int rows, int rows_per_img, int c, int regions,
                                      void* stream) {
     SDOD_TRY
@@ -1679,6 +1724,57 @@ extern "C" int sdod_l2_prefetch(const void* ptr, size_t bytes, void* stream) {
     const int blocks = (int)std::min<size_t>(48, (lines + 255) / 256);
     SDOD_LAUNCH(l2_prefetch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned*)ptr, lines, cur);
     SDOD_HIP_CHECK(hipGetLastError());
+    return 0;
+    SDOD_CATCH
+}
+
+// ---- CLIP vision tower (include/sdod_hip.h).  uint8 HWC image -> the rows of the patch-embedding GEMM: row = (image,
+// patch), column c * p * p + dy * p + dx (the conv weight's flattening) = fp16(((float)u / 255 - mean_c) / std_c), every operation
+// rounded on its own; columns from 3 p * p up to kpad are zero.  A thread writes 8 columns.
+namespace {
+struct PatchEmbedP {
+    const uint8_t* img; f16* out;
+    int S, p, g, kpad; // image size, patch size, patches per side, padded row length
+    float mean[3], sdev[3];
+};
+__global__ void patch_embed_kernel(const PatchEmbedP q, size_t total) {
+    const int kc = q.kpad / 8, pp = q.p * q.p;
+    GRID_STRIDE(i, total) {
+        const size_t row = i / kc;
+        const int k0 = (int)(i - row * kc) * 8;
+        const size_t n = row / ((size_t)q.g * q.g);
+        const int patch = (int)(row - n * q.g * q.g), py = patch / q.g, px = patch - py * q.g;
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int k = k0 + e;
+            float v = 0.f;
+            if (k < 3 * pp) {
+                const int c = k / pp, r = k - c * pp, dy = r / q.p, dx = r - dy * q.p;
+                const uint8_t u = q.img[((n * q.S + (size_t)(py * q.p + dy)) * q.S + (size_t)(px * q.p + dx)) * 3 + c];
+                v = div_rn(sub_rn(div_rn((float)u, 255.0f), q.mean[c]), q.sdev[c]);
+            }
+            o[e] = (f16)v;
+        }
+        stg8(q.out + i * 8, o);
+    }
+}
+} // namespace
+
+extern "C" int sdod_patch_embed_u8_f16(const uint8_t* img, void* out, int n, int image_size, int patch, int kpad, const float* mean3, const float* std3,
+                                       void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(img && out && mean3 && std3, "null pointer");
+    SDOD_REQUIRE(n > 0 && n <= 4096 && patch >= 1 && patch <= 64 && image_size >= patch && image_size <= 4096 && image_size % patch == 0,
+                 "image_size must be a multiple of patch (patch <= 64, image_size <= 4096, n <= 4096)");
+    SDOD_REQUIRE(kpad == (3 * patch * patch + 63) / 64 * 64, "kpad must be 3 * patch^2 rounded up to a multiple of 64");
+    SDOD_REQUIRE(((uintptr_t)out & 15) == 0, "misaligned pointer (16 bytes)");
+    for (int c = 0; c < 3; ++c) SDOD_REQUIRE(std::isfinite(mean3[c]) && std::isfinite(std3[c]) && std3[c] > 0.f, "mean must be finite, std finite and > 0");
+    PatchEmbedP q{};
+    q.img = img; q.out = (f16*)out; q.S = image_size; q.p = patch; q.g = image_size / patch; q.kpad = kpad;
+    for (int c = 0; c < 3; ++c) { q.mean[c] = mean3[c]; q.sdev[c] = std3[c]; }
+    const size_t total = (size_t)n * q.g * q.g * (kpad / 8);
+    LAUNCH(patch_embed_kernel, total, stream, q, total);
     return 0;
     SDOD_CATCH
 }

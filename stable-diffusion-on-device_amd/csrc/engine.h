@@ -72,7 +72,8 @@ struct IoSlot {
 class Graph {
 public:
     Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg = sdod_adapter_config{0, 0, 0}, int wrap = 0,
-          const sdod_upscaler_config& ucfg = sdod_upscaler_config{0, 0, 0}, const sdod_control_config* ccfg = nullptr, int regions = 0);
+          const sdod_upscaler_config& ucfg = sdod_upscaler_config{0, 0, 0}, const sdod_control_config* ccfg = nullptr, int regions = 0,
+          int ip_tokens = 0, const sdod_vision_config* vcfg = nullptr);
     ~Graph();
     Graph(const Graph&) = delete;
 
@@ -104,6 +105,10 @@ private:
     sdod_control_config ccfg_{0, 0}; // ControlNet switches of the UNET / TEMB graphs (sdod_graph_create_control); all zero = none
     int regions_ = 0;                    // regional prompts of the UNET graph (sdod_graph_create_regions): prompts per image; 0 = none
     const float* region_w_[4] = {};      // ... and its four weight inputs, level ds = 1, 2, 4, 8 (set by build_unet())
+    sdod_vision_config vcfg_{0, 0, 0, 0, 0, 0, 0, 0}; // kinds IMAGE_ENCODER / IMAGE_PROJ (sdod_graph_create_vision); all zero otherwise
+    int ip_tokens_ = 0;                  // image prompt of the UNET graph (sdod_graph_create_ip): image tokens per image; 0 = none
+    const float* ip_w_[4] = {};          // ... its four weight inputs [pixels][2], level ds = 1, 2, 4, 8 (set by build_unet())
+    f16* ip_kv_all_ = nullptr;           // ... and the image tokens' K / V of every transformer, [B * ip_tokens][kv_total_], persistent
     bool has_kv() const { return kind_ == SDOD_GRAPH_UNET || kind_ == SDOD_GRAPH_CONTROLNET; } // owns kv_all_ and the static K/V GEMM
     int batch_;
     int wrap_ = 0; // seamless tiling (UNET, VAE_DECODER): bit 0 = x wraps, bit 1 = y wraps; conv() turns it into sdod_gemm_desc::pad_mode
@@ -195,6 +200,11 @@ private:
     void build_vae();
     void build_vae_encoder(bool masked);
     void build_clip();
+    // one pre-LN block of a CLIP tower (text, causal; vision, not): both LayerNorms folded into the consuming Linear.  oc = open_clip's
+    // parameter names (fused in_proj), else HF's; consumes x.  In the DECLARE pass it only lists the parameters and returns x
+    Act clip_block(const std::string& pfx, bool oc, Act x, int heads, int inter, bool causal, int mlp_act);
+    void build_image_encoder(); // SDOD_GRAPH_IMAGE_ENCODER: HF CLIPVisionModelWithProjection -> image_embeds
+    void build_image_proj();    // SDOD_GRAPH_IMAGE_PROJ: IP-Adapter's ImageProjModel
     void build_temb();
     void build_adapter();
     void build_upscaler();
@@ -300,6 +310,7 @@ private:
                      const std::function<void(int, const Act&)>& on_skip);
     size_t control_residual_numel(int k) const; // ControlNet residual k = 0 .. 12 at this graph's batch, in halves
     void kv_all_gemm(const f16* ctx_in); // the static launch: cross-attention K / V of every transformer of the graph
+    void ip_kv_all_gemm(const f16* ip_ctx_in); // its twin on the image tokens: group attn2_kv_ip_all -> ip_kv_all_
     std::vector<std::pair<std::string, int>> temb_blocks() const; // the ResBlocks a TEMB graph projects for (control_temb: the first ten)
     Act vae_res_block(const std::string& pfx, const Act& x, int cout);
     Act vae_attn_block(const std::string& pfx, const Act& x);

@@ -38,10 +38,31 @@ static void parallel_for(int64_t n, F&& fn) {
 
 // ------------------------------------------------------------------------------------------ lifecycle
 Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg, int wrap, const sdod_upscaler_config& ucfg,
-             const sdod_control_config* ccfg, int regions)
-    : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), regions_(regions), batch_(batch), wrap_(wrap) {
+             const sdod_control_config* ccfg, int regions, int ip_tokens, const sdod_vision_config* vcfg)
+    : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), regions_(regions), ip_tokens_(ip_tokens), batch_(batch), wrap_(wrap) {
+    SDOD_REQUIRE(ip_tokens == 0 || ((kind == SDOD_GRAPH_UNET || kind == SDOD_GRAPH_IMAGE_PROJ) && ip_tokens >= 1 && ip_tokens <= 16 && regions == 0),
+                 "ip_tokens: the UNET and IMAGE_PROJ graphs only, 1 .. 16, not with regions");
+    const bool vision_kind = kind == SDOD_GRAPH_IMAGE_ENCODER || kind == SDOD_GRAPH_IMAGE_PROJ;
+    SDOD_REQUIRE(vision_kind == (vcfg != nullptr), "the IMAGE_ENCODER and IMAGE_PROJ graphs, and only they, are created by sdod_graph_create_vision");
+    if (vcfg) {
+        vcfg_ = *vcfg;
+        cfg_.weight_quant = 0; // always fp16 weights
+        SDOD_REQUIRE(vcfg_.proj_dim >= 64 && vcfg_.proj_dim <= 4096 && vcfg_.proj_dim % 64 == 0, "proj_dim must be a multiple of 64 in [64, 4096]");
+        if (kind == SDOD_GRAPH_IMAGE_ENCODER) {
+            SDOD_REQUIRE(vcfg_.patch >= 1 && vcfg_.patch <= 64 && vcfg_.image_size >= vcfg_.patch && vcfg_.image_size <= 1024 && vcfg_.image_size % vcfg_.patch == 0,
+                         "image_size must be a multiple of patch (patch <= 64, image_size <= 1024)");
+            SDOD_REQUIRE(vcfg_.width >= 64 && vcfg_.width <= 3072 && vcfg_.width % 64 == 0 && vcfg_.mlp_dim >= 64 && vcfg_.mlp_dim % 64 == 0 && vcfg_.mlp_dim <= 16384,
+                         "width and mlp_dim must be multiples of 64 (width <= 3072, mlp_dim <= 16384)");
+            SDOD_REQUIRE(vcfg_.layers >= 1 && vcfg_.layers <= 64 && vcfg_.heads >= 1 && vcfg_.width % vcfg_.heads == 0 &&
+                             (vcfg_.width / vcfg_.heads == 64 || vcfg_.width / vcfg_.heads == 80),
+                         "layers in [1, 64]; the head dim width / heads must be 64 or 80");
+            SDOD_REQUIRE(vcfg_.quick_gelu == 0 || vcfg_.quick_gelu == 1, "quick_gelu must be 0 or 1");
+        } else {
+            SDOD_REQUIRE(ip_tokens >= 1, "the IMAGE_PROJ graph needs ip_tokens");
+        }
+    }
     SDOD_REQUIRE(regions == 0 || (kind == SDOD_GRAPH_UNET && regions >= 2 && regions <= 4), "regions: the UNET graph only, 2 .. 4");
-    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_CONTROL_HINT, "unknown graph kind");
+    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_IMAGE_PROJ, "unknown graph kind");
     const bool control_kind = kind == SDOD_GRAPH_CONTROLNET || kind == SDOD_GRAPH_CONTROL_HINT;
     SDOD_REQUIRE(!control_kind || ccfg, "the CONTROLNET and CONTROL_HINT graphs are created by sdod_graph_create_control");
     if (ccfg) {
@@ -106,6 +127,7 @@ Graph::~Graph() {
     (void)hipFree(ws_);
     (void)hipFree(gn_ws_);
     (void)hipFree(kv_all_);
+    (void)hipFree(ip_kv_all_);
     for (void* d : derived_) (void)hipFree(d);
 }
 
@@ -564,6 +586,9 @@ struct ShapeKey {
 //   * tune/gfx950_regions.tune behind both, on the same terms: the picks for the regional-prompt UNet's own shapes (the score and
 //     output GEMMs of the folded cross-attention at regions x 640 columns, the K/V projection of regions x 77 keys) at the sizes its
 //     tests and tools/regions_bench.py build;
+//   * tune/gfx950_ip.tune behind the three, on the same terms: the picks for the shapes image prompts add (the image tokens' K/V
+//     projection, the image encoder's and the image projection's GEMMs) at the sizes tests/test_ipadapter_gpu.py and
+//     tools/ipadapter_bench.py build; the folded cross-attention's two GEMMs have the shapes of two regions and keep those picks;
 //   * SDOD_TUNE_CACHE=<file>: read after (so it overrides) the shipped table; shapes found in neither are timed once and
 //     appended to it.  Picks depend on the build and the device: regenerate the table when the tiles change.
 const char* tune_cache_path() {
@@ -589,6 +614,10 @@ std::string control_tune_path() {
 std::string regions_tune_path() {
     const std::string first = shipped_tune_path();
     return first.empty() ? first : first.substr(0, first.size() - 5) + "_regions.tune";
+}
+std::string ip_tune_path() {
+    const std::string first = shipped_tune_path();
+    return first.empty() ? first : first.substr(0, first.size() - 5) + "_ip.tune";
 }
 struct TuneEntry {
     int v;          // tile + 1000 * split_k
@@ -648,6 +677,7 @@ TuneCache& tune_cache() {
         if (!shipped.empty()) tune_cache_read(shipped.c_str(), c.map);
         if (!shipped.empty()) tune_cache_read(control_tune_path().c_str(), c.map, true);
         if (!shipped.empty()) tune_cache_read(regions_tune_path().c_str(), c.map, true);
+        if (!shipped.empty()) tune_cache_read(ip_tune_path().c_str(), c.map, true);
         if (const char* path = tune_cache_path()) tune_cache_read(path, c.map);
     }
     return c;
@@ -1036,6 +1066,8 @@ void Graph::build() {
     case SDOD_GRAPH_VAE_ENCODER_MASKED: build_vae_encoder(true); break;
     case SDOD_GRAPH_ADAPTER: build_adapter(); break;
     case SDOD_GRAPH_UPSCALER: build_upscaler(); break;
+    case SDOD_GRAPH_IMAGE_ENCODER: build_image_encoder(); break;
+    case SDOD_GRAPH_IMAGE_PROJ: build_image_proj(); break;
     case SDOD_GRAPH_CONTROLNET: build_controlnet(); break;
     case SDOD_GRAPH_CONTROL_HINT: build_control_hint(); break;
     default: build_temb(); break;
@@ -1069,6 +1101,8 @@ void Graph::finalize() {
     SDOD_HIP_CHECK(hipMemset(fix_counters_, 0, sdod_gemm_fixup_counters() * sizeof(unsigned)));
     if (has_kv() && kv_total_ > 0)
         SDOD_HIP_CHECK(hipMalloc((void**)&kv_all_, (size_t)batch_ * cfg_.context_len * kv_total_ * sizeof(f16)));
+    if (ip_tokens_ > 0 && kv_total_ > 0)
+        SDOD_HIP_CHECK(hipMalloc((void**)&ip_kv_all_, (size_t)batch_ * ip_tokens_ * kv_total_ * sizeof(f16)));
     mode_ = REAL;
     arena_reset();
     ops_.clear();
@@ -1447,6 +1481,41 @@ extern "C" int sdod_graph_create_regions(void** graph, int kind, const sdod_mode
     SDOD_CATCH
 }
 
+extern "C" int sdod_graph_create_ip(void** graph, int kind, const sdod_model_config* cfg, const sdod_ip_config* ip, int batch) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph && cfg, "null argument");
+    *graph = nullptr;
+    SDOD_REQUIRE(kind != SDOD_GRAPH_UPSCALER && kind != SDOD_GRAPH_ADAPTER && kind != SDOD_GRAPH_CONTROLNET && kind != SDOD_GRAPH_CONTROL_HINT,
+                 "this graph kind has a create function of its own");
+    const int T = ip ? ip->ip_tokens : 0;
+    if (T != 0) {
+        SDOD_REQUIRE(kind == SDOD_GRAPH_UNET, "image prompts: kind SDOD_GRAPH_UNET");
+        SDOD_REQUIRE(T >= 1 && T <= 16, "ip_tokens must be in [1, 16]");
+        SDOD_REQUIRE(cfg->weight_quant == 0 && cfg->concat_channels == 0, "image prompts take no weight_quant and no concat_channels");
+        SDOD_REQUIRE(cfg->context_len <= 80, "image prompts: context_len must be <= 80");
+    }
+    *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, nullptr, 0, T);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_create_vision(void** graph, int kind, const sdod_model_config* cfg, const sdod_vision_config* vision, const sdod_ip_config* ip,
+                                        int batch) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph, "null argument");
+    *graph = nullptr;
+    SDOD_REQUIRE(vision && (kind == SDOD_GRAPH_IMAGE_ENCODER || kind == SDOD_GRAPH_IMAGE_PROJ),
+                 "a vision configuration and kind SDOD_GRAPH_IMAGE_ENCODER or SDOD_GRAPH_IMAGE_PROJ");
+    SDOD_REQUIRE(kind == SDOD_GRAPH_IMAGE_ENCODER || (cfg && ip), "the IMAGE_PROJ graph needs the model configuration (context_dim) and ip_tokens");
+    sdod_model_config base;
+    sdod_model_config_sd14(&base);
+    if (cfg) base = *cfg;
+    *graph = new Graph(kind, base, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, nullptr, 0,
+                       kind == SDOD_GRAPH_IMAGE_PROJ ? ip->ip_tokens : 0, vision);
+    return 0;
+    SDOD_CATCH
+}
+
 extern "C" int sdod_graph_bind_output(void* graph, int index, void* device_ptr, size_t bytes) {
     SDOD_TRY
     SDOD_REQUIRE(graph, "null argument");
@@ -1586,7 +1655,7 @@ extern "C" int sdod_graph_tune_info(void* graph, int* from_table, int* tuned_in_
     if (tuned_in_process) *tuned_in_process = g->tune_misses();
     if (table_path && cap > 0) {
         std::string s = sdod::shipped_tune_path();
-        if (!s.empty()) s += " + " + sdod::control_tune_path() + " + " + sdod::regions_tune_path();
+        if (!s.empty()) s += " + " + sdod::control_tune_path() + " + " + sdod::regions_tune_path() + " + " + sdod::ip_tune_path();
         if (const char* extra = sdod::tune_cache_path()) s += (s.empty() ? "" : " + ") + std::string(extra);
         std::snprintf(table_path, (size_t)cap, "%s", s.c_str());
     }

@@ -1,6 +1,7 @@
 // graphs.hip -- launch-list builders, one per graph kind (include/sdod_engine.h): UNet eps-model (with the inpainting, T2I-Adapter
 // and seamless-tiling variants of its inputs), time-embedding MLP, CLIP text encoder, VAE decoder, VAE encoder and its masked form
-// (img2img, inpainting), T2I-Adapter, ESRGAN upscaler, ControlNet and its hint encoder.  The first four stand in for the serialized QNN graphs the reference loads
+// (img2img, inpainting), T2I-Adapter, ESRGAN upscaler, ControlNet and its hint encoder, CLIP image encoder and IP-Adapter image
+// projection.  The first four stand in for the serialized QNN graphs the reference loads
 // (context.cpp:105: "unet.serialized", "text_encoder.serialized", "vae_decoder.serialized", "temb"); the
 // block structure follows the op names visible in the reference's own profiler table
 // (analyze_results.py:20-93: in_layers / emb_layers / out_layers / skip_connection, norm / proj_in /
@@ -118,6 +119,10 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
     quant_global(); // (one encoding policy for the whole group: its GEMM runs on M = 77 rows per prompt)
     P(tb + ".attn2.to_k.weight", {C, cd}, PK_LINEAR, "attn2_kv_all");
     P(tb + ".attn2.to_v.weight", {C, cd}, PK_LINEAR, "attn2_kv_all");
+    if (ip_tokens_ > 0) { // image prompt: the image tokens' projections, one group and one static GEMM like the text's (ip_kv_all_gemm)
+        P(tb + ".attn2.to_k_ip.weight", {C, cd}, PK_LINEAR, "attn2_kv_ip_all");
+        P(tb + ".attn2.to_v_ip.weight", {C, cd}, PK_LINEAR, "attn2_kv_ip_all");
+    }
     quant_decl_ = quant_block;
     const int my_kv = kv_off_;
     kv_off_ += 2 * C;
@@ -190,14 +195,18 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
     // multiplies each group by its region's weight at the row's pixel and the second GEMM sums over regions through its K axis --
     // the same launches as the plain fold, both GEMMs regions_ times as wide.  Otherwise one attention launch per (image, region)
     // and a blend launch (correct, not fast: only levels of fewer than 32 pixels, or not a multiple of 32, come here).
-    const int RG = regions_, NR = RG > 0 ? RG : 1;
-    const int Lkeys = ctx.w / NR; // keys per prompt
+    // IMAGE PROMPT (ip_tokens_ > 0): the same two forms with two segments per image, the text keys of kv_all_ and the
+    // IPT image tokens of ip_kv_all_ (same column layout: this block's K | V at my_kv), weights (1, s(pixel)): to_out sees
+    // attn(q, K_text, V_text) + s attn(q, K_img, V_img).  Only the fold launch differs (two sources of different lengths).
+    const int IPT = ip_tokens_;
+    const int RG = IPT > 0 ? 2 : regions_, NR = RG > 0 ? RG : 1;
+    const int Lkeys = IPT > 0 ? ctx.w : ctx.w / NR; // keys per prompt
     const float* rgw = nullptr;   // this level's weights, fp32 [L][RG]
     if (RG > 0) {
         int lvl = 0;
         while (lvl < 4 && (cfg_.latent_h >> lvl) != x.h) ++lvl;
         if (lvl == 4 || (cfg_.latent_w >> lvl) != x.w) throw Error(INTERNAL_ERROR, "regional prompts: a transformer off the four UNet levels");
-        rgw = region_w_[lvl];
+        rgw = IPT > 0 ? ip_w_[lvl] : region_w_[lvl];
     }
     const int NK = heads * 80;
     const bool xfold = xfold_on && fold && Lkeys <= 80 && NK % 320 == 0 && L % 32 == 0 && d <= 160 && d % 4 == 0;
@@ -220,7 +229,14 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
             const int ldkv = kv_total_, koff = my_kv, Lk = Lkeys, hh = heads, dd = d;
             const float scale = 1.0f / sqrtf((float)d);
             to_static_ = true; // (not emit(): its settle() would put a still pending split-K reduce into the static list)
-            if (RG > 0)
+            const f16* ipkv = ip_kv_all_;
+            if (IPT > 0)
+                sink().push_back(Op{[=](hipStream_t st) {
+                    check_rc(sdod_xattn_fold_ip_f16(kvp, ldkv, koff, koff + C, ipkv, ldkv, koff, koff + C, B, Lk, IPT, wq, C, qv.s, qv.t, wo, C, hh, dd, scale,
+                                                    w1, s1, t1v, w2, st));
+                }, "xattn_fold", 4.0 * B * RG * NK * (double)C * d, 4.0 * B * RG * NK * C * 2,
+                   "C" + std::to_string(C) + " d" + std::to_string(d) + " ip" + std::to_string(IPT)});
+            else if (RG > 0)
                 sink().push_back(Op{[=](hipStream_t st) {
                     check_rc(sdod_xattn_fold_regions_f16(kvp, ldkv, koff, koff + C, B, RG, Lk, wq, C, qv.s, qv.t, wo, C, hh, dd, scale, w1, s1, t1v, w2, st));
                 }, "xattn_fold", 4.0 * B * RG * NK * (double)C * d, 4.0 * B * RG * NK * C * 2,
@@ -248,8 +264,12 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
         f16* ar = alloc((size_t)RG * rows * C);
         for (int b = 0; b < B; ++b)
             for (int r = 0; r < RG; ++r) {
-                const f16* kv = kv_all_ + (size_t)(b * RG + r) * Lkeys * kv_total_ + my_kv;
-                attention(q2 + (size_t)b * L * C, kv, kv + C, ar + ((size_t)r * rows + (size_t)b * L) * C, 1, heads, L, Lkeys, d, C, kv_total_, kv_total_, C, false);
+                const bool img_seg = IPT > 0 && r == 1; // (image prompt: segment 1 is image b's tokens)
+                const f16* kv = img_seg     ? ip_kv_all_ + (size_t)b * IPT * kv_total_ + my_kv
+                                : IPT > 0   ? kv_all_ + (size_t)b * Lkeys * kv_total_ + my_kv
+                                            : kv_all_ + (size_t)(b * RG + r) * Lkeys * kv_total_ + my_kv;
+                attention(q2 + (size_t)b * L * C, kv, kv + C, ar + ((size_t)r * rows + (size_t)b * L) * C, 1, heads, L, img_seg ? IPT : Lkeys, d, C, kv_total_,
+                          kv_total_, C, false);
             }
         release(q2);
         { const int rr = rows, LL = L, CC2 = C;
@@ -348,6 +368,14 @@ void Graph::kv_all_gemm(const f16* ctx_in) {
     if (quant_mode()) { okv.wq_scale = qscale_of(group_first("attn2_kv_all")); okv.wq_off = qoff_of(group_first("attn2_kv_all")); }
     linear_raw(ctx_in, batch_ * cfg_.context_len, cfg_.context_dim, reinterpret_cast<const f16*>(group_base("attn2_kv_all")), cfg_.context_dim,
                kv_total_, mode_ == REAL ? kv_all_ : const_cast<f16*>(ctx_in) /* placeholder during the sizing pass */, okv);
+    to_static_ = false;
+}
+
+void Graph::ip_kv_all_gemm(const f16* ip_ctx_in) {
+    if (mode_ == DECLARE || kv_total_ <= 0) return;
+    to_static_ = true;
+    linear_raw(ip_ctx_in, batch_ * ip_tokens_, cfg_.context_dim, reinterpret_cast<const f16*>(group_base("attn2_kv_ip_all")), cfg_.context_dim,
+               kv_total_, mode_ == REAL ? ip_kv_all_ : const_cast<f16*>(ip_ctx_in) /* placeholder during the sizing pass */, GemmOpt{});
     to_static_ = false;
 }
 
@@ -463,6 +491,26 @@ void Graph::build_unet() {
             region_w_[l] = wp;
         }
     }
+    // image prompt: the projected image tokens, static like the text context, and the weights of the two segments at
+    // the four levels, fp32 [H / ds * W / ds][2], behind every other input; (1, 0) -- no image prompt -- until the caller writes them
+    const f16* ip_ctx_in = nullptr;
+    for (int l = 0; l < 4; ++l) ip_w_[l] = nullptr;
+    if (ip_tokens_ > 0) {
+        SDOD_REQUIRE(CL <= 80, "image prompts: context_len must be <= 80");
+        SDOD_REQUIRE(AR == 0 && !ccfg_.control_inputs && CC == 0 && wrap_ == 0 && !quant_mode() && regions_ == 0,
+                     "image prompts exclude adapter inputs, control inputs, concat_channels, wrap, weight_quant and regions");
+        ip_ctx_in = (const f16*)io_alloc(inputs_, (size_t)B * ip_tokens_ * cd * sizeof(f16));
+        for (int l = 0; l < 4; ++l) {
+            const size_t n = (size_t)(H >> l) * (Wd >> l) * 2;
+            float* wp = (float*)io_alloc(inputs_, n * sizeof(float));
+            if (mode_ == REAL) {
+                std::vector<float> init(n, 0.f);
+                for (size_t i = 0; i < n; i += 2) init[i] = 1.f;
+                SDOD_HIP_CHECK(hipMemcpy(wp, init.data(), n * sizeof(float), hipMemcpyHostToDevice));
+            }
+            ip_w_[l] = wp;
+        }
+    }
     f16* e_out = (f16*)io_alloc(outputs_, (size_t)B * H * Wd * LC * sizeof(f16));
     Act ctx;
     ctx.p = ctx_in; ctx.n = B; ctx.h = 1; ctx.w = CL; ctx.c = cd;
@@ -473,6 +521,7 @@ void Graph::build_unet() {
     int emb_off = 0;
     kv_off_ = 0;
     kv_all_gemm(ctx_in);
+    if (ip_tokens_ > 0) ip_kv_all_gemm(ip_ctx_in);
 
     Act h = unet_conv_in(x_in, cond_in);
     std::vector<Act> hs;
@@ -1033,6 +1082,48 @@ void Graph::build_upscaler() {
 }
 
 // ------------------------------------------------------------------------------------------------ CLIP
+Act Graph::clip_block(const std::string& pfx, bool oc, Act x, int heads, int inter, bool causal, int mlp_act) {
+    const int B = x.n, L = x.w, D = x.c, rows = B * L;
+    const int l1w = P(pfx + (oc ? ".ln_1.weight" : ".layer_norm1.weight"), {D}, PK_VEC), l1b = P(pfx + (oc ? ".ln_1.bias" : ".layer_norm1.bias"), {D}, PK_VEC);
+    const std::string gw = pfx + ".qkv_w", gb = pfx + ".qkv_b";
+    int qkvw = -1, qkvb = -1;
+    if (oc) {
+        qkvw = P(pfx + ".attn.in_proj_weight", {3 * D, D}, PK_LINEAR);
+        qkvb = P(pfx + ".attn.in_proj_bias", {3 * D}, PK_VEC);
+    } else {
+        for (const char* n : {"q_proj", "k_proj", "v_proj"}) P(pfx + ".self_attn." + n + ".weight", {D, D}, PK_LINEAR, gw);
+        for (const char* n : {"q_proj", "k_proj", "v_proj"}) P(pfx + ".self_attn." + n + ".bias", {D}, PK_VEC, gb);
+    }
+    const int ow = P(pfx + (oc ? ".attn.out_proj.weight" : ".self_attn.out_proj.weight"), {D, D}, PK_LINEAR);
+    const int ob = P(pfx + (oc ? ".attn.out_proj.bias" : ".self_attn.out_proj.bias"), {D}, PK_VEC);
+    const int l2w = P(pfx + (oc ? ".ln_2.weight" : ".layer_norm2.weight"), {D}, PK_VEC), l2b = P(pfx + (oc ? ".ln_2.bias" : ".layer_norm2.bias"), {D}, PK_VEC);
+    const int f1w = P(pfx + (oc ? ".mlp.c_fc.weight" : ".mlp.fc1.weight"), {inter, D}, PK_LINEAR), f1b = P(pfx + (oc ? ".mlp.c_fc.bias" : ".mlp.fc1.bias"), {inter}, PK_VEC);
+    const int f2w = P(pfx + (oc ? ".mlp.c_proj.weight" : ".mlp.fc2.weight"), {D, inter}, PK_LINEAR), f2b = P(pfx + (oc ? ".mlp.c_proj.bias" : ".mlp.fc2.bias"), {D}, PK_VEC);
+    if (mode_ == DECLARE) return x;
+    // both LayerNorms of a block are folded into the Linear that consumes them (as in the UNet's transformer blocks): no
+    // LayerNorm launch, no normalised tensor -- 2 x text_layers launches fewer per prompt
+    f16* qkv = alloc((size_t)rows * 3 * D);
+    if (oc) {
+        GemmOpt o; o.bias = qkvb; o.ln_w = l1w; o.ln_b = l1b;
+        linear(x.p, rows, D, qkvw, 3 * D, qkv, o);
+    } else {
+        GemmOpt o; o.bias_raw = reinterpret_cast<const float*>(group_base(gb)); o.ln_w = l1w; o.ln_b = l1b;
+        linear_raw(x.p, rows, D, reinterpret_cast<const f16*>(group_base(gw)), D, 3 * D, qkv, o);
+    }
+    f16* a = alloc((size_t)rows * D);
+    attention(qkv, qkv + D, qkv + 2 * D, a, B, heads, L, L, D / heads, 3 * D, 3 * D, 3 * D, D, causal);
+    release(qkv);
+    Act x1 = act(B, 1, L, D);
+    { GemmOpt o; o.bias = ob; o.residual = x.p; linear(a, rows, D, ow, D, x1.p, o); }
+    release(a); release(x);
+    f16* f = alloc((size_t)rows * inter);
+    { GemmOpt o; o.bias = f1b; o.act = mlp_act; o.ln_w = l2w; o.ln_b = l2b; linear(x1.p, rows, D, f1w, inter, f, o); }
+    Act x2 = act(B, 1, L, D);
+    { GemmOpt o; o.bias = f2b; o.residual = x1.p; linear(f, rows, inter, f2w, D, x2.p, o); }
+    release(f); release(x1);
+    return x2;
+}
+
 void Graph::build_clip() {
     const int B = batch_, L = cfg_.context_len, D = cfg_.context_dim, heads = cfg_.text_heads, NL = cfg_.text_layers;
     const int rows = B * L, inter = 4 * D;
@@ -1049,47 +1140,9 @@ void Graph::build_clip() {
         const f16* tp = W<f16>(te); const f16* pp = W<f16>(pe);
         emit([=](hipStream_t st) { check_rc(sdod_embedding_f16(ids, tp, pp, x.p, rows, L, D, st)); });
     }
-    for (int l = 0; l < NL; ++l) {
-        const std::string pfx = (oc ? "transformer.resblocks." : "text_model.encoder.layers.") + std::to_string(l);
-        const int l1w = P(pfx + (oc ? ".ln_1.weight" : ".layer_norm1.weight"), {D}, PK_VEC), l1b = P(pfx + (oc ? ".ln_1.bias" : ".layer_norm1.bias"), {D}, PK_VEC);
-        const std::string gw = pfx + ".qkv_w", gb = pfx + ".qkv_b";
-        int qkvw = -1, qkvb = -1;
-        if (oc) {
-            qkvw = P(pfx + ".attn.in_proj_weight", {3 * D, D}, PK_LINEAR);
-            qkvb = P(pfx + ".attn.in_proj_bias", {3 * D}, PK_VEC);
-        } else {
-            for (const char* n : {"q_proj", "k_proj", "v_proj"}) P(pfx + ".self_attn." + n + ".weight", {D, D}, PK_LINEAR, gw);
-            for (const char* n : {"q_proj", "k_proj", "v_proj"}) P(pfx + ".self_attn." + n + ".bias", {D}, PK_VEC, gb);
-        }
-        const int ow = P(pfx + (oc ? ".attn.out_proj.weight" : ".self_attn.out_proj.weight"), {D, D}, PK_LINEAR);
-        const int ob = P(pfx + (oc ? ".attn.out_proj.bias" : ".self_attn.out_proj.bias"), {D}, PK_VEC);
-        const int l2w = P(pfx + (oc ? ".ln_2.weight" : ".layer_norm2.weight"), {D}, PK_VEC), l2b = P(pfx + (oc ? ".ln_2.bias" : ".layer_norm2.bias"), {D}, PK_VEC);
-        const int f1w = P(pfx + (oc ? ".mlp.c_fc.weight" : ".mlp.fc1.weight"), {inter, D}, PK_LINEAR), f1b = P(pfx + (oc ? ".mlp.c_fc.bias" : ".mlp.fc1.bias"), {inter}, PK_VEC);
-        const int f2w = P(pfx + (oc ? ".mlp.c_proj.weight" : ".mlp.fc2.weight"), {D, inter}, PK_LINEAR), f2b = P(pfx + (oc ? ".mlp.c_proj.bias" : ".mlp.fc2.bias"), {D}, PK_VEC);
-        if (mode_ == DECLARE) continue;
-        // both LayerNorms of a block are folded into the Linear that consumes them (as in the UNet's transformer blocks): no
-        // LayerNorm launch, no normalised tensor -- 2 x text_layers launches fewer per prompt
-        f16* qkv = alloc((size_t)rows * 3 * D);
-        if (oc) {
-            GemmOpt o; o.bias = qkvb; o.ln_w = l1w; o.ln_b = l1b;
-            linear(x.p, rows, D, qkvw, 3 * D, qkv, o);
-        } else {
-            GemmOpt o; o.bias_raw = reinterpret_cast<const float*>(group_base(gb)); o.ln_w = l1w; o.ln_b = l1b;
-            linear_raw(x.p, rows, D, reinterpret_cast<const f16*>(group_base(gw)), D, 3 * D, qkv, o);
-        }
-        f16* a = alloc((size_t)rows * D);
-        attention(qkv, qkv + D, qkv + 2 * D, a, B, heads, L, L, D / heads, 3 * D, 3 * D, 3 * D, D, true);
-        release(qkv);
-        Act x1 = act(B, 1, L, D);
-        { GemmOpt o; o.bias = ob; o.residual = x.p; linear(a, rows, D, ow, D, x1.p, o); }
-        release(a); release(x);
-        f16* f = alloc((size_t)rows * inter);
-        { GemmOpt o; o.bias = f1b; o.act = oc ? SDOD_ACT_GELU : SDOD_ACT_QUICK_GELU; o.ln_w = l2w; o.ln_b = l2b; linear(x1.p, rows, D, f1w, inter, f, o); }
-        Act x2 = act(B, 1, L, D);
-        { GemmOpt o; o.bias = f2b; o.residual = x1.p; linear(f, rows, inter, f2w, D, x2.p, o); }
-        release(f); release(x1);
-        x = x2;
-    }
+    for (int l = 0; l < NL; ++l)
+        x = clip_block((oc ? "transformer.resblocks." : "text_model.encoder.layers.") + std::to_string(l), oc, x, heads, inter, true,
+                       oc ? SDOD_ACT_GELU : SDOD_ACT_QUICK_GELU);
     const int fw = P(oc ? "ln_final.weight" : "text_model.final_layer_norm.weight", {D}, PK_VEC);
     const int fb = P(oc ? "ln_final.bias" : "text_model.final_layer_norm.bias", {D}, PK_VEC);
     {
@@ -1097,6 +1150,60 @@ void Graph::build_clip() {
         emit([=](hipStream_t st) { check_rc(sdod_layer_norm_f16(xp, out, wp, bp, rows, D, 1e-5f, st)); }, "layer_norm", 0, 2.0 * rows * D * 2);
     }
     release(x);
+}
+
+// ------------------------------------------------------------------------------------------------ image prompt
+// HF CLIPVisionModelWithProjection.  The stride-p patch convolution is a GEMM on rows gathered by sdod_patch_embed_u8_f16 (CLIP's
+// normalisation included; K = 3 p^2 zero-padded to a multiple of 64, the weight listed padded); sdod_vit_tokens_f16 puts the class
+// token in front, adds the positions and applies pre_layrnorm; the blocks are the text tower's, not causal; post_layernorm is folded
+// into visual_projection, which reads the class rows only (row stride (P + 1) W) and writes the output slot.
+void Graph::build_image_encoder() {
+    static const float kMean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, kStd[3] = {0.26862954f, 0.26130258f, 0.27577711f}; // CLIP's
+    const int B = batch_, S = vcfg_.image_size, p = vcfg_.patch, D = vcfg_.width, g = S / p, NP = g * g, L = NP + 1;
+    const int KP = (3 * p * p + 63) / 64 * 64, PD = vcfg_.proj_dim;
+    const uint8_t* img = (const uint8_t*)io_alloc(inputs_, (size_t)B * S * S * 3);
+    f16* out = (f16*)io_alloc(outputs_, (size_t)B * PD * sizeof(f16));
+    const std::string em = "vision_model.embeddings.";
+    const int pw = P(em + "patch_embedding.weight", {D, KP}, PK_LINEAR);
+    const int ce = P(em + "class_embedding", {1, D}, PK_EMBED), pe = P(em + "position_embedding.weight", {L, D}, PK_EMBED);
+    const int plw = P("vision_model.pre_layrnorm.weight", {D}, PK_VEC), plb = P("vision_model.pre_layrnorm.bias", {D}, PK_VEC);
+    f16* cols = alloc((size_t)B * NP * KP);
+    emit([=](hipStream_t st) { check_rc(sdod_patch_embed_u8_f16(img, cols, B, S, p, KP, kMean, kStd, st)); }, "patch_embed", 0,
+         (double)B * S * S * 3 + (double)B * NP * KP * 2);
+    f16* pt = alloc((size_t)B * NP * D);
+    linear(cols, B * NP, KP, pw, D, pt, GemmOpt{});
+    release(cols);
+    Act x = act(B, 1, L, D);
+    {
+        const f16* cp = W<f16>(ce); const f16* pp = W<f16>(pe); const float* wp = W<float>(plw); const float* bp = W<float>(plb);
+        f16* xp = x.p;
+        emit([=](hipStream_t st) { check_rc(sdod_vit_tokens_f16(pt, cp, pp, wp, bp, xp, B, NP, D, 1e-5f, st)); }, "vit_tokens", 0, 4.0 * B * L * D);
+    }
+    release(pt);
+    for (int l = 0; l < vcfg_.layers; ++l)
+        x = clip_block("vision_model.encoder.layers." + std::to_string(l), false, x, vcfg_.heads, vcfg_.mlp_dim, false,
+                       vcfg_.quick_gelu ? SDOD_ACT_QUICK_GELU : SDOD_ACT_GELU);
+    const int fw = P("vision_model.post_layernorm.weight", {D}, PK_VEC), fb = P("vision_model.post_layernorm.bias", {D}, PK_VEC);
+    const int vp = P("visual_projection.weight", {PD, D}, PK_LINEAR);
+    { GemmOpt o; o.ln_w = fw; o.ln_b = fb; o.lda = L * D; linear(x.p, B, D, vp, PD, out, o); }
+    release(x);
+}
+
+// IP-Adapter's ImageProjModel: LayerNorm(Linear(image_embeds).reshape(T, ctx_dim)) -- a GEMM and a LayerNorm launch into the output slot
+void Graph::build_image_proj() {
+    const int B = batch_, PD = vcfg_.proj_dim, T = ip_tokens_, cd = cfg_.context_dim;
+    const f16* in = (const f16*)io_alloc(inputs_, (size_t)B * PD * sizeof(f16));
+    f16* out = (f16*)io_alloc(outputs_, (size_t)B * T * cd * sizeof(f16));
+    const int w = P("proj.weight", {T * cd, PD}, PK_LINEAR), b = P("proj.bias", {T * cd}, PK_VEC);
+    const int nw = P("norm.weight", {cd}, PK_VEC), nb = P("norm.bias", {cd}, PK_VEC);
+    f16* y = alloc((size_t)B * T * cd);
+    { GemmOpt o; o.bias = b; linear(in, B, PD, w, T * cd, y, o); }
+    {
+        const float* wp = W<float>(nw); const float* bp = W<float>(nb);
+        const int rows = B * T;
+        emit([=](hipStream_t st) { check_rc(sdod_layer_norm_f16(y, out, wp, bp, rows, cd, 1e-5f, st)); }, "layer_norm", 0, 2.0 * rows * cd * 2);
+    }
+    release(y);
 }
 
 } // namespace sdod

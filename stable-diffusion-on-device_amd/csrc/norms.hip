@@ -1927,3 +1927,43 @@ extern "C" int sdod_layer_norm_f16(const void* x, void* y, const float* weight, 
     return 0;
     SDOD_CATCH
 }
+
+// ---- CLIP vision tower (include/sdod_hip.h): class token, position embedding and pre_layrnorm in one launch.
+// out[n][0] = LN(class + pos[0]), out[n][1 + i] = LN(patch[n][i] + pos[1 + i]); one wave per row, the sums in fp32 (two-pass
+// statistics on the recomputed fp32 values), one fp16 rounding at the store.
+namespace {
+__global__ __launch_bounds__(256) void vit_tokens_kernel(const f16* patches, const f16* cls, const f16* pos, const float* w, const float* b, f16* out,
+                                                         int rows, int P, int W, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6); // (wave-uniform)
+    if (row >= rows) return;
+    const int n = row / (P + 1), t = row - n * (P + 1);
+    const f16* src = t == 0 ? cls : patches + ((size_t)n * P + (t - 1)) * W;
+    const f16* pr = pos + (size_t)t * W;
+    float sum = 0.f;
+    for (int c = lane; c < W; c += 64) sum += (float)src[c] + (float)pr[c];
+    const float mean = group_sum<64>(sum) / (float)W;
+    float sq = 0.f;
+    for (int c = lane; c < W; c += 64) {
+        const float d = ((float)src[c] + (float)pr[c]) - mean;
+        sq += d * d;
+    }
+    const float rstd = 1.0f / sqrtf(group_sum<64>(sq) / (float)W + eps);
+    f16* o = out + (size_t)row * W;
+    for (int c = lane; c < W; c += 64) o[c] = (f16)((((float)src[c] + (float)pr[c]) - mean) * rstd * w[c] + b[c]);
+}
+} // namespace
+
+extern "C" int sdod_vit_tokens_f16(const void* patches, const void* class_embedding, const void* position_embedding, const float* ln_weight,
+                                   const float* ln_bias, void* out, int n, int num_patches, int width, float eps, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(patches && class_embedding && position_embedding && ln_weight && ln_bias && out, "null pointer");
+    SDOD_REQUIRE(n > 0 && n <= 4096 && num_patches >= 1 && num_patches <= 65536 && width >= 1 && width <= 8192, "bad shape");
+    SDOD_REQUIRE(std::isfinite(eps) && eps > 0.f, "eps must be finite and > 0");
+    const int rows = n * (num_patches + 1);
+    SDOD_LAUNCH(vit_tokens_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const f16*)patches, (const f16*)class_embedding,
+                (const f16*)position_embedding, ln_weight, ln_bias, (f16*)out, rows, num_patches, width, eps);
+    SDOD_HIP_CHECK(hipGetLastError());
+    return 0;
+    SDOD_CATCH
+}

@@ -144,6 +144,11 @@ def _declare(lib):
         'sdod_xattn_fold_f16': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
         'sdod_xattn_fold_regions_f16': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
         'sdod_region_weights_f32': (c_int, [P, c_int, c_int, c_int, P, P, P, P, P]),
+        'sdod_xattn_fold_ip_f16': (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_float,
+                                           P, P, P, P, P]),
+        'sdod_ip_weights_f32': (c_int, [P, c_float, c_int, c_int, P, P, P, P, P]),
+        'sdod_patch_embed_u8_f16': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P]),
+        'sdod_vit_tokens_f16': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, P]),
         'sdod_region_blend_f16': (c_int, [P, c_size_t, P, P, c_int, c_int, c_int, c_int, P]),
         'sdod_softmax_rows_f16': (c_int, [P, P, c_int, c_int, P]),
         'sdod_geglu_f16': (c_int, [P, P, c_int, c_int, P]),
@@ -207,6 +212,7 @@ HIP_SYMBOLS = [
     'sdod_hip_device_info', 'sdod_image_conv_in_unit_f16', 'sdod_dense_conv3x3_f16', 'sdod_dense_conv3x3_ok',
     'sdod_add_control_f16',
     'sdod_gemm_region_f16', 'sdod_xattn_fold_regions_f16', 'sdod_region_weights_f32', 'sdod_region_blend_f16',
+    'sdod_xattn_fold_ip_f16', 'sdod_ip_weights_f32', 'sdod_patch_embed_u8_f16', 'sdod_vit_tokens_f16',
 ]
 
 

@@ -13,6 +13,9 @@ step for the MI355X build.  It runs on a host without a GPU: the engine's parame
 
     python -m sdod.amd.convert --controlnet control_v11p_sd15_canny.pth --out models/  # controlnet.sdodw (Txt2Img(controlnet=True))
 
+    python -m sdod.amd.convert --ip-adapter ip-adapter_sd15.safetensors --out models/  # ip_adapter.sdodw (Txt2Img(ip_adapter=True))
+    python -m sdod.amd.convert --image-encoder image_encoder/ --out models/            # image_encoder.sdodw (CLIP ViT-H/14, optional)
+
 Only loaders that execute nothing from the file are used: safetensors, or torch.load(weights_only=True).
 """
 import argparse
@@ -323,6 +326,41 @@ def convert_controlnet(path, out_dir, dtype=torch.float16):
     return out
 
 
+def read_ip_adapter(path):
+    """an IP-Adapter file -> its state dict: `.safetensors` (flat image_proj.* / ip_adapter.* keys) through safetensors, `.bin` (the
+    nested {'image_proj', 'ip_adapter'} dict) through torch.load(weights_only=True)"""
+    if path.endswith('.safetensors'):
+        from safetensors.torch import load_file
+        return load_file(path, device='cpu')
+    return torch.load(path, map_location='cpu', weights_only=True)
+
+
+def convert_ip_adapter(path, out_dir, dtype=torch.float16):
+    """ip-adapter_sd15.{bin,safetensors} -> out_dir/ip_adapter.sdodw (ip_adapter.adapter_parameters); returns the file written"""
+    from . import ip_adapter as IP
+    part = IP.adapter_parameters(read_ip_adapter(path), dtype)
+    os.makedirs(out_dir, exist_ok=True)
+    out = os.path.join(out_dir, 'ip_adapter.sdodw')
+    weights.save(out, part)
+    return out
+
+
+def convert_image_encoder(path, out_dir, dtype=torch.float16):
+    """an HF CLIPVisionModelWithProjection checkpoint (model.safetensors / pytorch_model.bin, or the directory that holds one) ->
+    out_dir/image_encoder.sdodw (ip_adapter.image_encoder_parameters); returns the file written"""
+    from . import ip_adapter as IP
+    if os.path.isdir(path):
+        found = [os.path.join(path, n) for n in ('model.safetensors', 'pytorch_model.bin') if os.path.exists(os.path.join(path, n))]
+        if not found:
+            raise ValueError(f'{path} holds neither model.safetensors nor pytorch_model.bin')
+        path = found[0]
+    part = IP.image_encoder_parameters(read_checkpoint(path), dtype)
+    os.makedirs(out_dir, exist_ok=True)
+    out = os.path.join(out_dir, 'image_encoder.sdodw')
+    weights.save(out, part)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     ap.add_argument('--ckpt', help='sd-v1-x .ckpt / .safetensors (ldm key names)')
@@ -333,6 +371,10 @@ def main(argv=None):
     ap.add_argument('--controlnet', help='a ControlNet 1.0 / 1.1 checkpoint for SD 1.x (control_sd15_*.pth, control_v11*_sd15_*.pth / '
                                          '.safetensors; control_model.* names): write controlnet.sdodw (Txt2Img(controlnet=True)); with or '
                                          'without --ckpt')
+    ap.add_argument('--ip-adapter', help='ip-adapter_sd15.bin / .safetensors (IP-Adapter for SD 1.x, not the "plus" or FaceID files): write '
+                                         'ip_adapter.sdodw (Txt2Img(ip_adapter=True)); with or without --ckpt')
+    ap.add_argument('--image-encoder', help='the IP-Adapter image encoder, an HF CLIPVisionModelWithProjection model.safetensors or its '
+                                            'directory: write image_encoder.sdodw')
     ap.add_argument('--out', required=True, help='models_dir to write')
     ap.add_argument('--fp32', action='store_true', help='keep fp32 payloads (the engine converts at load)')
     ap.add_argument('--model', default='sd14', choices=['sd14', 'sd21'], help='sd21: SD v2.x shapes and open_clip text-tower key names')
@@ -343,8 +385,8 @@ def main(argv=None):
     ap.add_argument('--tokenizer-vocab', help='bpe_simple_vocab_16e6.txt.gz, or a directory with HF vocab.json + merges.txt: '
                                               'also write ctokenizer.txt')
     a = ap.parse_args(argv)
-    if not a.ckpt and not a.adapter and not a.upscaler and not a.controlnet:
-        ap.error('one of --ckpt, --adapter, --upscaler and --controlnet is required')
+    if not a.ckpt and not a.adapter and not a.upscaler and not a.controlnet and not a.ip_adapter and not a.image_encoder:
+        ap.error('one of --ckpt, --adapter, --upscaler, --controlnet, --ip-adapter and --image-encoder is required')
     cfg = E.sd21_config() if a.model == 'sd21' else None
     if a.inpaint:
         cfg = cfg or E.sd14_config()
@@ -358,6 +400,10 @@ def main(argv=None):
         print('wrote', convert_upscaler(a.upscaler, a.out, torch.float32 if a.fp32 else torch.float16))
     if a.controlnet:
         print('wrote', convert_controlnet(a.controlnet, a.out, torch.float32 if a.fp32 else torch.float16))
+    if a.ip_adapter:
+        print('wrote', convert_ip_adapter(a.ip_adapter, a.out, torch.float32 if a.fp32 else torch.float16))
+    if a.image_encoder:
+        print('wrote', convert_image_encoder(a.image_encoder, a.out, torch.float32 if a.fp32 else torch.float16))
     if a.tokenizer_vocab:
         from . import tokenizer_file
         print('wrote', tokenizer_file.generate(a.tokenizer_vocab, os.path.join(a.out, 'ctokenizer.txt')))

@@ -10,6 +10,7 @@ from . import _lib
 from ._lib import check
 
 UNET, VAE_DECODER, TEXT_ENCODER, TEMB, VAE_ENCODER, VAE_ENCODER_MASKED, ADAPTER, UPSCALER, CONTROLNET, CONTROL_HINT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+IMAGE_ENCODER, IMAGE_PROJ = 10, 11
 
 
 class ModelConfig(ctypes.Structure):
@@ -33,7 +34,11 @@ class ModelConfig(ctypes.Structure):
     # Regional prompts (`struct sdod_region_config`, next to the struct like the others): prompts per image of a UNet, whose context_len
     # is then 77 * regions and which gets the four UNet.region_w inputs; 0 = the plain graph through the old creation entry points.
     regions = 0
-    _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'tiling', 'control_inputs', 'control_temb', 'regions')
+    # Image prompts (`struct sdod_ip_config`, next to the struct like the others): image tokens per image of a UNet, which then has the
+    # to_k_ip / to_v_ip parameters and the UNet.ip_ctx / UNet.ip_w inputs; 0 = the plain graph through the old creation entry points.
+    ip_tokens = 0
+    _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'tiling', 'control_inputs', 'control_temb', 'regions',
+                       'ip_tokens')
 
     @classmethod
     def from_buffer_copy(cls, source, offset=0):
@@ -58,6 +63,21 @@ class ControlConfig(ctypes.Structure):
 class RegionConfig(ctypes.Structure):
     """mirror of `struct sdod_region_config`"""
     _fields_ = [('regions', ctypes.c_int)]
+
+
+class IpConfig(ctypes.Structure):
+    """mirror of `struct sdod_ip_config`"""
+    _fields_ = [('ip_tokens', ctypes.c_int)]
+
+
+class VisionConfig(ctypes.Structure):
+    """mirror of `struct sdod_vision_config`"""
+    _fields_ = [(n, ctypes.c_int) for n in ('image_size', 'patch', 'width', 'layers', 'heads', 'mlp_dim', 'proj_dim', 'quick_gelu')]
+
+
+def vit_h14_config():
+    """OpenCLIP ViT-H/14 as HF CLIPVisionModelWithProjection holds it: the image encoder of ip-adapter_sd15"""
+    return VisionConfig(224, 14, 1280, 32, 16, 5120, 1024, 0)
 
 
 class UpscalerConfig(ctypes.Structure):
@@ -92,6 +112,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_stats', 'sdod_graph_tune_info', 'sdod_graph_num_ops', 'sdod_graph_op_info', 'sdod_graph_op_detail', 'sdod_graph_profile',
     'sdod_graph_keep_base', 'sdod_graph_base_bytes', 'sdod_graph_set_loras', 'sdod_graph_create_upscaler',
     'sdod_graph_create_control', 'sdod_graph_bind_output', 'sdod_graph_create_regions',
+    'sdod_graph_create_ip', 'sdod_graph_create_vision',
 ]
 
 
@@ -109,6 +130,8 @@ def _engine():
         lib.sdod_graph_create_upscaler.argtypes = [ctypes.POINTER(P), ctypes.POINTER(UpscalerConfig), I]
         lib.sdod_graph_create_control.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(ControlConfig), I]
         lib.sdod_graph_create_regions.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(RegionConfig), I]
+        lib.sdod_graph_create_ip.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(IpConfig), I]
+        lib.sdod_graph_create_vision.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(VisionConfig), ctypes.POINTER(IpConfig), I]
         lib.sdod_graph_bind_output.argtypes = [P, I, P, ctypes.c_size_t]
         lib.sdod_graph_destroy.argtypes = [P]
         lib.sdod_graph_num_params.argtypes = [P]
@@ -186,8 +209,17 @@ class Graph:
         regions = int(getattr(cfg, 'regions', 0)) if kind == UNET else 0
         if regions and (control or wrap or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_)):
             raise ValueError('a UNet with regions takes no control inputs, no tiling and no T2I-Adapter configuration')
+        ip_tokens = int(getattr(cfg, 'ip_tokens', 0)) if kind == UNET else 0
+        if ip_tokens and (regions or control or wrap or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_)):
+            raise ValueError('a UNet with an image prompt takes no regions, no control inputs, no tiling and no T2I-Adapter configuration')
         with self._on_device():
-            if regions:             # regional prompts have an entry point of their own; without them nothing changes
+            if kind in (IMAGE_ENCODER, IMAGE_PROJ):   # the image side of an image prompt: cfg.vision, and cfg.ip_tokens for the projection
+                icfg = IpConfig(int(getattr(cfg, 'ip_tokens', 0)))
+                check(self._lib.sdod_graph_create_vision(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(cfg.vision), ctypes.byref(icfg), batch))
+            elif ip_tokens:         # image prompts have an entry point of their own; without them nothing changes
+                icfg = IpConfig(ip_tokens)
+                check(self._lib.sdod_graph_create_ip(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(icfg), batch))
+            elif regions:           # regional prompts have an entry point of their own; without them nothing changes
                 rcfg = RegionConfig(regions)
                 check(self._lib.sdod_graph_create_regions(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(rcfg), batch))
             elif control:             # the ControlNet kinds and switches have an entry point of their own; without them nothing changes
@@ -388,6 +420,10 @@ class UNet(Graph):
         k = int(getattr(c, 'regions', 0))
         if k:                       # regional prompts: the blend weights of the four levels, "region 0 everywhere" until set (ops.region_weights)
             self.region_w = [self.io_tensor(False, 3 + lvl, ((c.latent_h >> lvl) * (c.latent_w >> lvl), k), torch.float32) for lvl in range(4)]
+        t = int(getattr(c, 'ip_tokens', 0))
+        if t:                       # image prompt: the projected image tokens and the two segments' weights, (1, 0) until set (ops.ip_weights)
+            self.ip_ctx = self.io_tensor(False, 3, (b, t, c.context_dim), torch.float16)
+            self.ip_w = [self.io_tensor(False, 4 + lvl, ((c.latent_h >> lvl) * (c.latent_w >> lvl), 2), torch.float32) for lvl in range(4)]
         return self
 
 
@@ -452,6 +488,61 @@ class ControlHint(Graph):
         c, b = self.cfg, self.batch
         self.hint = self.io_tensor(False, 0, (b, 8 * c.latent_h, 8 * c.latent_w, 3), torch.uint8)
         self.out = self.io_tensor(True, 0, (b, c.latent_h, c.latent_w, c.model_channels), torch.float16)
+        return self
+
+
+class ImageEncoder(Graph):
+    """HF CLIPVisionModelWithProjection: uint8 [B, S, S, 3], resized and cropped by the caller -> image_embeds fp16
+    [B, proj_dim].  Parameters by HF's names; set_param flattens `patch_embedding.weight` [W, 3, p, p] to [W, 3 p p] and pads it with
+    zeros to the row length the table lists, and gives `class_embedding` [W] its table shape [1, W].  One execute per image prompt."""
+
+    def __init__(self, vision, batch, device='cuda:0'):
+        cfg = sd14_config()
+        cfg.vision = self.vision = VisionConfig.from_buffer_copy(vision)
+        super().__init__(IMAGE_ENCODER, cfg, batch, device)
+        self._shapes = dict(self.param_table())
+
+    def checkpoint_table(self):
+        """(name, shape) as a checkpoint holds them"""
+        v = self.vision
+        fix = {'vision_model.embeddings.patch_embedding.weight': (v.width, 3, v.patch, v.patch), 'vision_model.embeddings.class_embedding': (v.width,)}
+        return [(n, fix.get(n, s)) for n, s in self.param_table()]
+
+    def set_param(self, name, tensor):
+        want = self._shapes.get(name)
+        if want is not None and torch.is_tensor(tensor) and tuple(tensor.shape) != want:
+            t = tensor.detach().cpu()
+            if name.endswith('patch_embedding.weight') and t.dim() == 4 and t.shape[0] == want[0] and t[0].numel() <= want[1]:
+                padded = torch.zeros(want, dtype=t.dtype)
+                padded[:, :t[0].numel()] = t.reshape(t.shape[0], -1)
+                tensor = padded
+            elif name.endswith('class_embedding') and t.numel() == want[1]:
+                tensor = t.reshape(want)
+        super().set_param(name, tensor)
+
+    def finalize(self):
+        super().finalize()
+        v, b = self.vision, self.batch
+        self.img = self.io_tensor(False, 0, (b, v.image_size, v.image_size, 3), torch.uint8)
+        self.out = self.io_tensor(True, 0, (b, v.proj_dim), torch.float16)
+        return self
+
+
+class ImageProj(Graph):
+    """IP-Adapter's ImageProjModel: image_embeds fp16 [B, proj_dim] -> fp16 [B, T, ctx_dim] = LayerNorm(Linear(e).reshape(T, ctx_dim)).
+    bind_output(0, unet.ip_ctx) before finalize() makes it write a UNet's slot (same batch)."""
+
+    def __init__(self, cfg, proj_dim, ip_tokens, batch, device='cuda:0'):
+        c = copy_config(cfg)
+        c.ip_tokens = int(ip_tokens)
+        c.vision = VisionConfig(0, 0, 0, 0, 0, 0, int(proj_dim), 0)
+        self.proj_dim, self.ip_tokens = int(proj_dim), int(ip_tokens)
+        super().__init__(IMAGE_PROJ, c, batch, device)
+
+    def finalize(self):
+        super().finalize()
+        self.embeds = self.io_tensor(False, 0, (self.batch, self.proj_dim), torch.float16)
+        self.out = self.io_tensor(True, 0, (self.batch, self.ip_tokens, self.cfg.context_dim), torch.float16)
         return self
 
 

@@ -366,6 +366,27 @@ def xattn_fold(kv, k_off, v_off, n_img, L, wq, sq, tq, wo, heads, scale=None, re
     return w1, s1, t1, w2
 
 
+def xattn_fold_ip(kv, k_off, v_off, kv_ip, k_off_ip, v_off_ip, n_img, L, T, wq, sq, tq, wo, heads, scale=None):
+    """the fold on two sources per image (sdod_xattn_fold_ip_f16): text K/V [n_img * L, ld] and image-token K/V [n_img * T, ld_ip].
+    Returns (w1 [n_img, 2*heads*80, C], s1, t1 [n_img, 2*heads*80], w2 [n_img, C, 2*heads*80]); segment 0 = text, 1 = image."""
+    lib = _lib.hip()
+    _req(kv, torch.float16, 'kv'); _req(kv_ip, torch.float16, 'kv_ip'); _req(wq, torch.float16, 'wq'); _req(wo, torch.float16, 'wo')
+    _req(sq, torch.float32, 'sq'); _req(tq, torch.float32, 'tq')
+    c = wq.shape[0]; d = c // heads
+    if kv.shape[0] < n_img * L or kv_ip.shape[0] < n_img * T:
+        raise ValueError(f'kv needs {n_img * L} rows and kv_ip {n_img * T}, got {kv.shape[0]} and {kv_ip.shape[0]}')
+    if scale is None:
+        scale = d ** -0.5
+    nk = heads * 80 * 2
+    w1 = torch.empty(n_img, nk, c, dtype=torch.float16, device=kv.device)
+    w2 = torch.empty(n_img, c, nk, dtype=torch.float16, device=kv.device)
+    s1 = torch.empty(n_img, nk, dtype=torch.float32, device=kv.device); t1 = torch.empty_like(s1)
+    check(lib.sdod_xattn_fold_ip_f16(_p(kv), kv.shape[-1], k_off, v_off, _p(kv_ip), kv_ip.shape[-1], k_off_ip, v_off_ip, n_img, L, T,
+                                     _p(wq), wq.shape[1], _p(sq), _p(tq), _p(wo), wo.shape[1], heads, d, scale, _p(w1), _p(s1), _p(t1), _p(w2),
+                                     _stream()))
+    return w1, s1, t1, w2
+
+
 def attention_strided(q, k, v, out, batch, heads, lq, lk, d, ldq, ldk, ldv, ldo, scale, causal=False):
     """raw form for packed qkv buffers: pointers may be column offsets into wider rows"""
     lib = _lib.hip()
@@ -499,6 +520,62 @@ def region_weights(masks_u8, out=None):
         if o.numel() != (h >> lvl) * (w >> lvl) * k:
             raise ValueError(f'out[{lvl}] holds {o.numel()} floats, the level needs {(h >> lvl) * (w >> lvl) * k}')
     check(lib.sdod_region_weights_f32(_p(masks_u8), k, h, w, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _stream()))
+    return out
+
+
+def ip_weights(scale, h, w, mask_u8=None, out=None, device='cuda:0'):
+    """the weights of the text and image-token segments at the four UNet levels, fp32 [h/ds * w/ds, 2] for ds = 1, 2, 4, 8
+    (sdod_ip_weights_f32): column 0 is 1, column 1 scale * S / (255 (8 ds)^2) with S the sum of mask_u8 [8h, 8w] over the level
+    pixel, or scale everywhere without a mask.  out: the four destinations (UNet.ip_w)."""
+    lib = _lib.hip()
+    scale = float(scale)
+    if not (scale >= 0.0 and scale != float('inf')):
+        raise ValueError(f'scale must be finite and >= 0, got {scale}')
+    if mask_u8 is not None:
+        _req(mask_u8, torch.uint8, 'mask')
+        if tuple(mask_u8.shape) != (8 * h, 8 * w):
+            raise ValueError(f'mask must be [{8 * h}, {8 * w}], got {tuple(mask_u8.shape)}')
+        device = mask_u8.device
+    if out is None:
+        out = [torch.empty((h // ds) * (w // ds), 2, dtype=torch.float32, device=device) for ds in (1, 2, 4, 8)]
+    for lvl, o in enumerate(out):
+        _req(o, torch.float32, f'out[{lvl}]')
+        if o.numel() != (h >> lvl) * (w >> lvl) * 2:
+            raise ValueError(f'out[{lvl}] holds {o.numel()} floats, the level needs {(h >> lvl) * (w >> lvl) * 2}')
+    check(lib.sdod_ip_weights_f32(None if mask_u8 is None else _p(mask_u8), scale, h, w, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _stream()))
+    return out
+
+
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def patch_embed(img_u8, patch, mean=CLIP_MEAN, std=CLIP_STD):
+    """uint8 [n, S, S, 3] -> fp16 [n * (S / patch)^2, kpad], the rows of a ViT's patch-embedding GEMM (sdod_patch_embed_u8_f16):
+    column c p p + dy p + dx = fp16((u / 255 - mean_c) / std_c), zero from 3 p p up to kpad = the next multiple of 64"""
+    lib = _lib.hip()
+    _req(img_u8, torch.uint8, 'img')
+    if img_u8.dim() != 4 or img_u8.shape[1] != img_u8.shape[2] or img_u8.shape[3] != 3:
+        raise ValueError(f'img must be [n, S, S, 3], got {tuple(img_u8.shape)}')
+    n, s = img_u8.shape[0], img_u8.shape[1]
+    kpad = (3 * patch * patch + 63) // 64 * 64
+    out = torch.empty(n * (s // patch) ** 2, kpad, dtype=torch.float16, device=img_u8.device)
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    check(lib.sdod_patch_embed_u8_f16(_p(img_u8), _p(out), n, s, int(patch), kpad, m3, s3, _stream()))
+    return out
+
+
+def vit_tokens(patches, class_embedding, position_embedding, ln_weight, ln_bias, eps=1e-5):
+    """patches fp16 [n, P, W] -> fp16 [n, P + 1, W]: LayerNorm of (class token | patches) + positions (sdod_vit_tokens_f16)"""
+    lib = _lib.hip()
+    for t, dt, nm in ((patches, torch.float16, 'patches'), (class_embedding, torch.float16, 'class_embedding'),
+                      (position_embedding, torch.float16, 'position_embedding'), (ln_weight, torch.float32, 'ln_weight'), (ln_bias, torch.float32, 'ln_bias')):
+        _req(t, dt, nm)
+    n, p, w = patches.shape
+    if class_embedding.numel() != w or tuple(position_embedding.shape) != (p + 1, w) or ln_weight.numel() != w or ln_bias.numel() != w:
+        raise ValueError('class_embedding [W], position_embedding [P + 1, W], ln_weight and ln_bias [W] must match patches [n, P, W]')
+    out = torch.empty(n, p + 1, w, dtype=torch.float16, device=patches.device)
+    check(lib.sdod_vit_tokens_f16(_p(patches), _p(class_embedding), _p(position_embedding), _p(ln_weight), _p(ln_bias), _p(out), n, p, w, float(eps), _stream()))
     return out
 
 

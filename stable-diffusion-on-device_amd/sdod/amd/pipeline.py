@@ -14,6 +14,7 @@ from . import engine as E
 from . import ops
 from . import prompts as PR
 from . import regions as RG
+from . import ip_adapter as IP
 from . import upscale as UP
 from .host import DpmSolver
 from .samplers import K_SAMPLERS, K_SCHEDULES, PLMS_ORDERS, KSchedule, PlmsSchedule
@@ -40,12 +41,17 @@ class Txt2Img:
     adapter_channels = 3
     upscaler = None     # the ESRGAN x4 upscaler (Txt2Img(..., upscaler=True): sdod.amd.upscale.Upscaler), or None
     tiling = 0          # seamless tiling: the wrap bits the UNet and the VAE decoder were built with (bit 0 = x, bit 1 = y)
+    ip_tokens = 0       # image prompts: image tokens per image the UNet was built for (Txt2Img(..., ip_adapter=True)), 0 = none
+    image_proj = None   # ... the IMAGE_PROJ graph, whose output IS unet.ip_ctx, and image_encoder, the CLIP vision tower (or None)
+    image_encoder = None
+    ip_proj_dim = 0
+    ip_image_size = None
     regions = 0         # regional prompts: prompts per image the UNet was built for (Txt2Img(..., regions=k)), 0 = none
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
-                 adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False):
+                 adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False, ip_adapter=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -107,7 +113,15 @@ class Txt2Img:
         with_vae_encoder, upscaler, every sampler and the eager, graphed and pipelined entry points; a captured trajectory picks up new
         masks without a recapture.  With prompt_chunks > 1, cfg_split, hires_hw, controlnet, adapter, tiling, inpaint_unet, model='sd21'
         or uint8 weights: ValueError before any device work (regions.regions_check_build).  False: nothing is constructed or sized
-        differently."""
+        differently.
+        ip_adapter=True: image prompts (IP-Adapter for SD 1.x; DESIGN.md 6l, sdod/amd/ip_adapter.py).  state_dicts['ip_adapter'] or
+        models_dir/ip_adapter.sdodw holds the image projection and every block's to_k_ip / to_v_ip; state_dicts['image_encoder'] /
+        models_dir/image_encoder.sdodw, when present, the CLIP vision tower.  The UNet is built on a config copy with ip_tokens;
+        set_image_prompt(image_u8 | embeds=, weight, mask_u8) conditions every entry point and sampler until clear_image_prompt(), and
+        a captured trajectory picks up a new image, weight or mask without a recapture.  Works with loras, with_vae_encoder, upscaler,
+        rectangular latent_hw and images_per_gpu > 1 (one image prompt per image).  Not with regions, prompt_chunks > 1, cfg_split,
+        hires_hw, controlnet, adapter, tiling, inpaint_unet, model='sd21' or uint8 weights: ValueError before any device work
+        (ip_adapter.ip_check_build).  False: nothing is constructed or sized differently."""
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         latent_h, latent_w = check_latent_hw(latent_hw)
         adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_unet, model)
@@ -117,6 +131,10 @@ class Txt2Img:
             hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts.get('unet', {}).values())))      # (uint8 codes decide it, as below)
         self.regions = RG.regions_check_build(regions, self.prompt_chunks, cfg_split, hires_hw, controlnet, adapter, tiling, inpaint_unet,
                                               model, quant_asked)
+        quant_ip = bool(ip_adapter) and (weight_quant or (weight_quant is None and state_dicts is not None and any(
+            hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts.get('unet', {}).values())))
+        if IP.ip_check_build(ip_adapter, regions, self.prompt_chunks, cfg_split, hires_hw, controlnet, adapter, tiling, inpaint_unet, model, quant_ip):
+            self.ip_tokens, self.ip_proj_dim, ip_vision = IP.ip_sources(state_dicts, models_dir)
         up_args = upscaler_check_build(upscaler, tiling, hires_hw if hires_hw is not None else latent_hw, state_dicts, models_dir)
         if hires_hw is not None:
             check_latent_hw(hires_hw, 'hires_hw')
@@ -172,6 +190,9 @@ class Txt2Img:
             unet_cfg = E.copy_config(unet_cfg)
             unet_cfg.context_len = PR.CHUNK_LEN * self.regions
             unet_cfg.regions = self.regions
+        if self.ip_tokens:               # the image tokens and the two segments' weights are inputs of the UNet alone
+            unet_cfg = E.copy_config(unet_cfg)
+            unet_cfg.ip_tokens = self.ip_tokens
         vae_cfg = self.cfg
         if self.tiling:                  # the UNet and the VAE decoder take the circular border; every other graph has no border to wrap
             unet_cfg, vae_cfg = E.copy_config(unet_cfg), E.copy_config(self.cfg)
@@ -211,6 +232,17 @@ class Txt2Img:
             self.control_hint.finalize()
             self._temb_stage = torch.zeros((self.unet.batch, self.unet.temb_width + self.controlnet.temb_width), dtype=torch.float16,
                                            device=self.device)
+        if self.ip_tokens:
+            # the projection runs on the (unconditional = zeros ; conditional) rows of the UNet's batch and writes unet.ip_ctx itself
+            self.image_proj = E.ImageProj(self.cfg, self.ip_proj_dim, self.ip_tokens, 2 * self.n, device)
+            self._load(self.image_proj, 'ip_adapter', 'ip_adapter')
+            self.image_proj.bind_output(0, self.unet.ip_ctx)
+            self.image_proj.finalize()
+            if ip_vision is not None:
+                self.image_encoder = E.ImageEncoder(E.VisionConfig(*ip_vision), self.n, device)
+                self._load(self.image_encoder, 'image_encoder', 'image_encoder')
+                self.image_encoder.finalize()
+                self.ip_image_size = int(ip_vision[0])
         if up_args is not None:
             self.upscaler = UP.Upscaler(device=device, use_hip_graph=use_hip_graph, **up_args)
         self._loras = bool(loras)
@@ -223,10 +255,13 @@ class Txt2Img:
                                  prompt_chunks=prompt_chunks, loras=loras)
 
     def _load(self, g, key, stem):
+        ip_unet = g is self.unet and self.ip_tokens      # its to_k_ip / to_v_ip come from the adapter's container, by the UNet's names
         if self._sd is not None:
-            g.load_state_dict(self._sd[key])
+            g.load_state_dict({**self._sd[key], **self._sd['ip_adapter']} if ip_unet else self._sd[key])
         else:
             g.load_file(f'{self._dir}/{stem}.sdodw')
+            if ip_unet:
+                g.load_file(f'{self._dir}/ip_adapter.sdodw')
 
     # ------------------------------------------------------------------ LoRA adapters
     def set_loras(self, adapters, strict=True):
@@ -324,6 +359,46 @@ class Txt2Img:
         self._require_controlnet()
         self.unet.control_scale.zero_()
         self._control_on = False
+
+    # ------------------------------------------------------------------ image prompts (IP-Adapter)
+    def image_embeds(self, image_u8):
+        """CLIP image_embeds fp16 [n, proj_dim] of uint8 images [n, S, S, 3] (resized and cropped by the caller): one execute of the
+        image encoder.  What set_image_prompt(image_u8) conditions on; set_image_prompt(embeds=...) with them gives the same images."""
+        image_u8, _, _, _ = IP.ip_check_args(self, image_u8, None, 1.0, None)
+        self.image_encoder.img.copy_(image_u8.to(self.device))
+        self.image_encoder.execute(self.use_hip_graph)
+        return self.image_encoder.out.clone()
+
+    def set_image_prompt(self, image_u8=None, weight=1.0, mask_u8=None, *, embeds=None):
+        """image_u8: uint8 [n, S, S, 3], one image per image of the batch, resized and cropped by the caller to the encoder's size (224)
+        -- or embeds: precomputed CLIP image_embeds, fp16 / fp32 [n, proj_dim].  weight: IP-Adapter's scale, a finite number >= 0.
+        mask_u8: optional uint8 [8h, 8w] at image resolution, where the image prompt applies (255 = fully).  The encoder (for
+        image_u8) and the image projection run once, here: the conditional rows of the UNet's image tokens take image_proj(embeds),
+        the unconditional rows image_proj(zeros), as IP-Adapter's get_image_embeds does; one launch writes the four levels' weights
+        (ops.ip_weights).  Tokens and weights are inputs of the UNet at fixed addresses: every entry point and sampler is conditioned
+        from here on, and a captured trajectory picks the new ones up without a recapture.  ValueError for wrong shapes or dtypes,
+        both or neither of image_u8 / embeds, a bad weight, or image_u8 without an image encoder (ip_adapter.ip_check_args), before
+        any device work; RuntimeError without ip_adapter=True."""
+        image_u8, embeds, weight, mask_u8 = IP.ip_check_args(self, image_u8, embeds, weight, mask_u8)
+        n = self.n
+        if image_u8 is not None:
+            self.image_encoder.img.copy_(image_u8.to(self.device))
+            self.image_encoder.execute(self.use_hip_graph)
+            embeds = self.image_encoder.out
+        self.image_proj.embeds[:n].zero_()
+        self.image_proj.embeds[n:].copy_(embeds.to(self.device))
+        self.image_proj.execute(self.use_hip_graph)
+        h, w = self._latent_shape[-2:]
+        ops.ip_weights(weight, h, w, None if mask_u8 is None else mask_u8.to(self.device), out=self.unet.ip_w, device=self.device)
+        self._ctx_fresh = True     # the image tokens' K / V and the fold are static launches of the UNet, like the text's
+
+    def clear_image_prompt(self):
+        """no image prompt, the state after construction: weights (1, 0), the image segment contributes exact zeros"""
+        if not self.ip_tokens:
+            raise RuntimeError('this pipeline was built without ip_adapter=True: Txt2Img(..., ip_adapter=True) is needed for image prompts')
+        for w in self.unet.ip_w:
+            w.zero_()
+            w[:, 0] = 1.0
 
     # ------------------------------------------------------------------ regional prompts
     def set_regions(self, masks_u8):

@@ -91,6 +91,21 @@ def names(path):
     return out
 
 
+def shapes(path):
+    """{name: dims} of a container, from its header alone (no payload is read)"""
+    with open(path, 'rb') as f:
+        head = f.read(16)
+        assert head[:8] == MAGIC, 'bad magic'
+        out = {}
+        for _ in range(struct.unpack_from('<Q', head, 8)[0]):
+            nl = struct.unpack('<I', f.read(4))[0]
+            name = f.read(nl).decode()
+            nd = struct.unpack('<II', f.read(8))[1]
+            out[name] = tuple(struct.unpack('<' + 'Q' * nd, f.read(8 * nd)))
+            f.read(16)
+    return out
+
+
 def load(path):
     """Inverse of save(); returns {name: tensor or QuantU8}."""
     out = {}

@@ -8,6 +8,7 @@ every process builds the same launch lists without timing anything.
 
 usage (GPU box):  python tools/make_tune_cache.py gpurun_out/gfx950.tune [--quick | --only-quant | --only-rows3 | --only-ln | --only-new]
                   python tools/make_tune_cache.py out/gfx950_regions.tune --only-regions    (-> tune/gfx950_regions.tune)
+                  python tools/make_tune_cache.py out/gfx950_ip.tune --only-ip              (-> tune/gfx950_ip.tune)
 NEVER run under a profiler (timing noise would be baked into the picks)."""
 import os
 import sys
@@ -29,7 +30,8 @@ only_new = '--only-new' in sys.argv       # keep EVERY shipped pick, time only t
 only_vae_enc = '--only-vae-encoder' in sys.argv  # keep EVERY shipped pick, time the VAE encoder's new shapes (img2img; key flag bit 26 = pad_mode)
 only_rect = '--only-rect' in sys.argv      # keep EVERY shipped pick, time the sd14 shapes at 64 x 96, 96 x 64 and 96 x 96 (rectangular sizes, the hires pass)
 only_regions = '--only-regions' in sys.argv  # keep EVERY pick of gfx950.tune and gfx950_control.tune, time the regional-prompt UNets' new shapes, write ONLY those
-only_new = only_new or only_vae_enc or only_rect or only_regions
+only_ip = '--only-ip' in sys.argv          # keep EVERY pick of the three shipped tables, time the new shapes of image prompts, write ONLY those
+only_new = only_new or only_vae_enc or only_rect or only_regions or only_ip
 if os.path.exists(out):
     os.remove(out)
 os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -57,9 +59,10 @@ if only_quant or only_rows3 or only_ln or only_new or only_n160 or only_geglu or
                 drop = (int(v[10]) & (1 << 29)) if only_quant else (v[0] == '1' and v[6] == '1' and v[8] == '3' and int(v[9]) % 3 == 0)
             if not drop:
                 g.write(line)
-    if only_regions:   # the second table's picks too: the output is what NEITHER table holds
-        with open(shipped.replace('.tune', '_control.tune')) as f, open(out, 'a') as g:
-            g.writelines(line for line in f if len(line.split()) == 15)
+    if only_regions or only_ip:   # the later tables' picks too: the output is what NONE of them holds
+        for suffix in ('_control.tune',) + (('_regions.tune',) if only_ip else ()):
+            with open(shipped.replace('.tune', suffix)) as f, open(out, 'a') as g:
+                g.writelines(line for line in f if len(line.split()) == 15)
         with open(out) as f:
             known = set(f.read().splitlines())
 os.environ['SDOD_TUNE_CACHE'] = out
@@ -103,6 +106,37 @@ if only_regions:
             build(E.UNet, c, 2, 1234, f'sd14 unet {h}x{w} b2, {k} regions')
     for k in (2, 3):
         build(E.TextEncoder, E.sd14_config(16, 16), 2 * k, 1237, f'clip-L b{2 * k}')
+    with open(out) as f:
+        new = [line for line in f.read().splitlines() if line not in known]
+    with open(out, 'w') as f:
+        f.write(''.join(line + '\n' for line in new))
+    print(f'done: {out} ({len(new)} new shapes)')
+    sys.exit(0)
+
+if only_ip:
+    # the sizes tests/test_ipadapter_gpu.py and tools/ipadapter_bench.py build: UNets with 4 and 16 image tokens at 16 x 16 and 8 x 16
+    # (batch 2; batch 4 for two images per GPU), 64 x 64 with 4; the image projection and the image encoders, ViT-H/14 included
+    def ip_unet(h, w, t, b):
+        c = E.sd14_config(h, w)
+        c.ip_tokens = t
+        build(E.UNet, c, b, 1234, f'sd14 unet {h}x{w} b{b}, {t} image tokens')
+    for h, w in ((16, 16), (8, 16)):
+        for t in (4, 16):
+            ip_unet(h, w, t, 2)
+    ip_unet(16, 16, 4, 4)
+    ip_unet(64, 64, 4, 2)
+    c16 = E.sd14_config(16, 16)
+    for proj, t, b in ((128, 4, 2), (128, 16, 2), (128, 4, 4), (1024, 4, 2)):
+        build(lambda cfg, batch: E.ImageProj(cfg, proj, t, batch), c16, b, 1240, f'image projection {proj} -> {t} tokens b{b}')
+    for v, b in (((28, 14, 320, 2, 4, 1280, 128, 0), 1), ((28, 14, 320, 2, 4, 1280, 128, 0), 2), ((56, 14, 128, 2, 2, 512, 64, 1), 2)):
+        g = E.ImageEncoder(E.VisionConfig(*v), b)
+        g.load_state_dict(Wt.synthetic_state_dict(g.checkpoint_table(), seed=1241)); g.finalize()
+        print(f'[{time.time() - T0:6.1f}s] image encoder {v} b{b}: {g.stats()["launches"]} launches', flush=True)
+        del g
+    g = E.ImageEncoder(E.vit_h14_config(), 1)
+    g.load_state_dict(Wt.synthetic_state_dict(g.checkpoint_table(), seed=1242, dtype=torch.float16)); g.finalize()
+    print(f'[{time.time() - T0:6.1f}s] image encoder ViT-H/14 b1: {g.stats()["launches"]} launches', flush=True)
+    del g
     with open(out) as f:
         new = [line for line in f.read().splitlines() if line not in known]
     with open(out, 'w') as f:
