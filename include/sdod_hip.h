@@ -80,7 +80,12 @@ typedef struct sdod_gemm_desc {
      * ln: the rows of A are LayerNorm-ed on the fly (rows mode, K = normalised width, no split-K): the kernel sums
      *        x and x^2 of every row while the slabs pass through LDS and the epilogue applies
      *        out = rstd_m * (acc - mean_m * ln_s[n]) + bias[n]; the LayerNorm weight is pre-multiplied into W, ln_s[n] =
-     *        sum_k W'[n][k] and bias[n] = sum_k beta[k] W[n][k] (+ linear bias) come from sdod_ln_fold_f16. */
+     *        sum_k W'[n][k] and bias[n] = sum_k beta[k] W[n][k] (+ linear bias) come from sdod_ln_fold_f16.
+     *        rstd_m = 1 / sqrt(var_m + ln_eps) with the ONE-PASS variance var_m = sum x^2 / K - mean_m^2 in fp32, clamped at 0
+     *        (the row passes through LDS once).  Contract: the result is within the Linear kernels' tolerance (rel-L2 3e-3
+     *        against fp64) for rows with |row mean| / row std <= 100; beyond that the cancellation in var_m grows with the
+     *        square of the ratio and the output is only guaranteed finite.  sdod_layer_norm_f16 is two-pass and has no such
+     *        limit: LayerNorm rows far from zero mean go through it (tests/test_row_kernels_gpu.py). */
     int geglu;
     int k_tail;                    /* 0 = no tail segment; else 9*(c0+c1) */
     const void* t0;
@@ -89,7 +94,7 @@ typedef struct sdod_gemm_desc {
     const void* bias2;
     int ln;
     const void* ln_s;              /* fp32 [N] */
-    float ln_eps;
+    float ln_eps;                  /* added to the one-pass variance under the square root (see `ln` above for the contract) */
     int phase;                     /* split-K only: 0 = GEMM + reduce (default), 1 = GEMM slabs only, 2 = reduce + epilogue only
                                     * (lets a launch list time / profile the two kernels separately) */
     /* --- int8 weight streaming (LDS-DMA kernel family only; BASELINE config 5, the reference's `quantize=8` path,

@@ -2,7 +2,11 @@
 
 Checker: plain PyTorch fp32 on the CPU of the same op on the same fp16-rounded inputs.
 Tolerances (stated, fp16 in/out with fp32 accumulation): rel-L2 <= 2e-3 per kernel,
-max-abs <= 2e-2 * max|ref|; integer / exact paths are compared bit-for-bit."""
+max-abs <= 2e-2 * max|ref|; integer / exact paths are compared bit-for-bit.
+
+The kernels that reduce along a row (LayerNorm stand-alone and folded into the GEMMs, softmax_rows, the score GEMM's softmax
+epilogue) and the activation functions meet only Gaussian rows of unit scale here; tests/test_row_kernels_gpu.py holds them to
+fp64 on the rows that can see eps, a lost row maximum, misplaced statistics, flushed subnormals and a wrong coefficient."""
 import os
 
 import numpy as np
