@@ -111,11 +111,20 @@ typedef struct sdod_model_config {
     int context_len;     /* 77: the text encoder's positions (its position table is [context_len][ctx_dim]) and the UNet's
                           * cross-attention keys.  A UNET graph takes any length >= 1 (77 k for k prompt chunks); above 80 keys
                           * its transformer blocks run the three-launch cross-attention instead of the folded form */
-    int num_heads;       /* 8 (SD1.x: head dim = C/8); 0 = use head_dim */
-    int head_dim;        /* 64 (SD2.x); ignored when num_heads > 0 */
+    int num_heads;       /* 8 (SD1.x: head dim = C/8); 0 = use head_dim; negative is an error */
+    int head_dim;        /* 64 (SD2.x); ignored when num_heads > 0.
+                          * One of the two decides the head geometry of every transformer of a UNET / CONTROLNET graph, whose widths
+                          * are C = model_channels, 2 model_channels and 4 model_channels.  Creating such a graph is
+                          * LIBSDOD_INVALID_ARGUMENT, with a message that names the field, unless at every C
+                          *   num_heads > 0:                 C % num_heads == 0 and C / num_heads is a head dim the attention kernel takes;
+                          *   num_heads == 0, head_dim > 0:  C % head_dim == 0 and head_dim is one the attention kernel takes
+                          * (sdod_attention_head_dim_ok, include/sdod_hip.h: 40, 64, 80, 160).  So num_heads = 8 needs model_channels
+                          * 320; head_dim 64 takes every model_channels (a multiple of 64); head_dim 40, 80 or 160 takes the multiples
+                          * of 320.  Every accepted geometry runs: where the folded cross-attention does not take a level
+                          * (sdod_xattn_fold_ok) the builder uses Linear + attention + Linear.  The other kinds do not read the fields */
     int vocab_size;      /* 49408 */
     int text_layers;     /* 12 */
-    int text_heads;      /* 12 */
+    int text_heads;      /* 12; TEXT_ENCODER: positive, and context_dim / text_heads must be 64 (anything else is INVALID_ARGUMENT) */
     int vae_channels;    /* 128 */
     int linear_proj;     /* 0: transformer proj_in / proj_out are 1x1 convs [C,C,1,1] (SD1.x); 1: Linear [C,C] (SD2.x
                           * `use_linear_in_transformer`) -- same arithmetic, different checkpoint shapes */

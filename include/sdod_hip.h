@@ -277,6 +277,9 @@ SDOD_API int sdod_layer_norm_f16(const void* x, void* y, const float* weight, co
 SDOD_API int sdod_attention_f16(const void* q, const void* k, const void* v, void* out, int batch, int heads,
                                 int lq, int lk, int d, int ldq, int ldk, int ldv, int ldo, float scale, int causal,
                                 void* stream);
+/* 1 when the call above takes head dim d, else 0: the one statement of the set, which the graph engine asks when a graph is
+ * created (sdod_model_config.num_heads / head_dim, include/sdod_engine.h).  Host-only. */
+SDOD_API int sdod_attention_head_dim_ok(int d);
 
 /* Folded cross-attention, the once-per-prompt part.  The text context is constant over the sampler run, so to_q and to_out can
  * be multiplied into K and V: scores_h = LN(x) . W1_h with W1_h = Wq_h^T K_h^T, out = [P_1 | .. | P_H] . [W2_1 ; .. ; W2_H] with
@@ -289,6 +292,14 @@ SDOD_API int sdod_attention_f16(const void* q, const void* k, const void* v, voi
 SDOD_API int sdod_xattn_fold_f16(const void* kv, int ld_kv, int k_off, int v_off, int n_img, int L, const void* wq, int ldq,
                                  const void* sq, const void* tq, const void* wo, int ldwo, int heads, int d, float scale, void* w1,
                                  void* s1, void* t1, void* w2, void* stream);
+/* The folded form's whole contract, 1 or 0.  Host-only; the three fold entry points REQUIRE through it and the graph builder
+ * decides through it (0: Linear + attention + Linear), so a shape that passes never fails at execute.
+ *   the launch:     heads >= 1; 8 <= d <= 160 with d % 8 == 0; 1 <= l_keys <= 80 (for sdod_xattn_fold_ip_f16 the text keys; its
+ *                   image tokens are 1 .. 16); heads * d a multiple of 80 (W1 / W2 are built as 80-channel tiles)
+ *   the two GEMMs:  heads a multiple of 4 (heads * 80 columns in 64-deep K slabs and whole 160-column softmax tiles); heads * d a
+ *                   multiple of 64 (the score GEMM's K); rows_per_image (the pixels of one image) a multiple of 32
+ * rows_per_image = 0 asks for the launch alone, which is what a caller that runs the GEMMs itself on other terms needs. */
+SDOD_API int sdod_xattn_fold_ok(int heads, int d, int l_keys, int rows_per_image);
 
 /* The same for regional prompts: kv holds n_img * regions segments of L rows (image-major), one per (image, region prompt).  w1 /
  * s1 / t1 are what the call above writes for n_img * regions images, bit for bit: for image b, [regions][heads*80] rows.  w2 for

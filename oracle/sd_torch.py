@@ -314,10 +314,10 @@ class AutoencoderKLDecode(nn.Module):
     """`first_stage_model.{post_quant_conv, decoder}`; decode(z) = decoder(post_quant_conv(z / 0.18215))."""
     scale_factor = 0.18215
 
-    def __init__(self):
+    def __init__(self, ch=128):
         super().__init__()
         self.post_quant_conv = nn.Conv2d(4, 4, 1)
-        self.decoder = VaeDecoder()
+        self.decoder = VaeDecoder(ch=ch)
 
     def forward(self, z):
         return self.decoder(self.post_quant_conv(z * (1.0 / self.scale_factor)))

@@ -669,13 +669,30 @@ __global__ __launch_bounds__(256) void xattn_fold_kernel(const FoldP p) {
 
 } // namespace
 
+// the head dims the fused attention kernel is instantiated for (the `switch (d)` below): the ONE list.  Host-only.
+extern "C" int sdod_attention_head_dim_ok(int d) { return d == 40 || d == 64 || d == 80 || d == 160 ? 1 : 0; }
+
+// the folded cross-attention's contract (include/sdod_hip.h).  Host-only.
+extern "C" int sdod_xattn_fold_ok(int heads, int d, int l_keys, int rows_per_image) {
+    // the fold launch: d zero-padded to the MFMA's 32 within kFoldKMax columns of LDS and read in 16-byte pieces; 80 key slots per
+    // head; W1 / W2 are written as 80-channel tiles (tiles_c = heads * d / 80)
+    if (heads <= 0 || d <= 0 || d > kFoldKMax || d % 8 != 0 || l_keys <= 0 || l_keys > 80) return 0;
+    const long long C = (long long)heads * d, NK = (long long)heads * 80;
+    if (C % 80 != 0) return 0;
+    if (rows_per_image == 0) return 1;
+    // the two GEMMs of every evaluation: K = heads * d of the score GEMM and K = heads * 80 of the second one in 64-deep slabs
+    // (the latter also makes N = heads * 80 of the score GEMM a multiple of 160: whole softmax groups per tile), per-image
+    // weights on tiles of at least 32 rows
+    return rows_per_image > 0 && rows_per_image % 32 == 0 && NK % 320 == 0 && C % 64 == 0 ? 1 : 0;
+}
+
 extern "C" int sdod_attention_f16(const void* q, const void* k, const void* v, void* out, int batch, int heads, int lq,
                                   int lk, int d, int ldq, int ldk, int ldv, int ldo, float scale, int causal,
                                   void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(q && k && v && out, "null pointer");
     SDOD_REQUIRE(batch > 0 && heads > 0 && lq > 0 && lk > 0, "bad shape");
-    SDOD_REQUIRE(d == 40 || d == 64 || d == 80 || d == 160, "head dim must be one of 40, 64, 80, 160");
+    SDOD_REQUIRE(sdod_attention_head_dim_ok(d), "head dim must be one of 40, 64, 80, 160");
     SDOD_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0, "row strides must keep 16-byte alignment");
     SDOD_REQUIRE(ldq >= heads * d && ldk >= heads * d && ldv >= heads * d && ldo >= heads * d, "row stride < heads*d");
     SDOD_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0 && ((uintptr_t)out & 7) == 0, "misaligned pointer");
@@ -734,9 +751,11 @@ int xattn_fold_launch(const void* kv, int ld_kv, int k_off, int v_off, int n_img
     SDOD_REQUIRE(n_img <= (1 << 20), "bad shape (too many images)");
     n_img *= regions; // (image, region) segments of L rows
     SDOD_REQUIRE(kv && wq && sq && tq && wo && w1 && s1 && t1 && w2, "null pointer");
-    SDOD_REQUIRE(n_img > 0 && heads > 0 && d > 0 && d <= kFoldKMax && d % 8 == 0 && L > 0 && L <= 80, "bad shape (d <= 160, d % 8 == 0, L <= 80)");
+    // (rows_per_image 0: the launch's own part of the contract; the builder asks with the rows of its two GEMMs)
+    SDOD_REQUIRE(n_img > 0 && sdod_xattn_fold_ok(heads, d, L, 0), "bad shape (d <= 160, d % 8 == 0, L <= 80, heads * d a multiple of 80)");
+    SDOD_REQUIRE((long long)heads * d <= (1 << 24), "bad shape (heads * d too large)");
     const int C = heads * d, NK = heads * 80;
-    SDOD_REQUIRE(C % 80 == 0 && ldq >= C && ldwo >= C && ld_kv >= C, "heads * d must be a multiple of 80; row strides >= heads * d");
+    SDOD_REQUIRE(ldq >= C && ldwo >= C && ld_kv >= C, "row strides >= heads * d");
     SDOD_REQUIRE(ld_kv % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0 && ldq % 8 == 0 && ldwo % 8 == 0 &&
                      (((uintptr_t)kv | (uintptr_t)wq | (uintptr_t)wo | (uintptr_t)w1 | (uintptr_t)w2) & 15) == 0,
                  "operands must keep 16-byte alignment");

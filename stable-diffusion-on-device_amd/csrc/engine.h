@@ -301,6 +301,11 @@ private:
         flush_pending();
         drain_parked();
     }
+    // heads and head dim of a transformer on C channels, from cfg_.num_heads / cfg_.head_dim: the one place that divides by them.
+    // Throws INVALID_ARGUMENT naming the field for a geometry no attention kernel runs (include/sdod_engine.h at the fields).
+    struct HeadGeom { int heads, d; };
+    HeadGeom head_geometry(int C) const;
+    void check_head_geometry() const; // every transformer width of a UNET / CONTROLNET graph: MC, 2 MC, 4 MC
     Act spatial_transformer(const std::string& pfx, const Act& x, const Act& ctx);
     Act unet_conv_in(const float* x_in, const float* cond_in); // input_blocks.0.0 in its three forms
     // input_blocks.1 .. 11 and middle_block.0/1/2 behind input_blocks.0 (h): the half the UNet and the ControlNet share.  hs != null

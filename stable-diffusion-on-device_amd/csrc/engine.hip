@@ -88,6 +88,8 @@ Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapt
     SDOD_REQUIRE(batch > 0 && batch <= 64, "batch must be in [1, 64]");
     SDOD_REQUIRE(cfg.model_channels > 0 && cfg.model_channels % 64 == 0, "model_channels must be a multiple of 64");
     SDOD_REQUIRE(cfg.context_dim % 64 == 0, "context_dim must be a multiple of 64");
+    // the kinds that build transformers: one of num_heads / head_dim decides, and only a geometry some attention kernel runs
+    if (kind == SDOD_GRAPH_UNET || kind == SDOD_GRAPH_CONTROLNET) check_head_geometry();
     SDOD_REQUIRE(cfg.context_len >= 1 && cfg.context_len <= 4096, "context_len must be in [1, 4096]");
     SDOD_REQUIRE(cfg.concat_channels >= 0, "concat_channels must not be negative");
     SDOD_REQUIRE(acfg.adapter_reps >= 0 && acfg.adapter_reps <= 2, "adapter_reps must be 0, 1 or 2");

@@ -94,10 +94,34 @@ Act Graph::res_block(const std::string& pfx, const Act& x, const Act* x2, int co
     return out;
 }
 
+Graph::HeadGeom Graph::head_geometry(int C) const {
+    const int nh = cfg_.num_heads, hd = cfg_.head_dim;
+    const std::string at = " (transformer on " + std::to_string(C) + " channels)";
+    SDOD_REQUIRE(nh >= 0, "num_heads must not be negative (0 = head_dim decides)");
+    HeadGeom g;
+    if (nh > 0) { // num_heads decides, head_dim is ignored
+        SDOD_REQUIRE(C % nh == 0, "num_heads must divide the channels of every transformer" + at);
+        g.heads = nh;
+        g.d = C / nh;
+        SDOD_REQUIRE(sdod_attention_head_dim_ok(g.d), "num_heads gives head dim " + std::to_string(g.d) + ", which no attention kernel takes (40, 64, 80, 160)" + at);
+    } else {
+        SDOD_REQUIRE(hd > 0, "head_dim must be positive when num_heads is 0 (one of num_heads / head_dim decides the head geometry)");
+        SDOD_REQUIRE(C % hd == 0, "head_dim must divide the channels of every transformer" + at);
+        SDOD_REQUIRE(sdod_attention_head_dim_ok(hd), "head_dim must be one the attention kernel takes (40, 64, 80, 160)");
+        g.heads = C / hd;
+        g.d = hd;
+    }
+    return g;
+}
+
+void Graph::check_head_geometry() const {
+    for (int m : {1, 2, 4}) (void)head_geometry(m * cfg_.model_channels);
+}
+
 Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& ctx) {
     const int C = x.c, cd = ctx.c;
-    const int heads = cfg_.num_heads > 0 ? cfg_.num_heads : C / cfg_.head_dim;
-    const int d = C / heads;
+    const HeadGeom hg = head_geometry(C);
+    const int heads = hg.heads, d = hg.d;
     const int rows = x.rows(), L = x.h * x.w, B = x.n;
     const std::string tb = pfx + ".transformer_blocks.0";
     quant_rows(rows);
@@ -194,7 +218,7 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
     // sum_r w_r(pixel) attn(x, K_r, V_r).  Folded: the score GEMM's 80-column groups are laid out [region][head][80], its epilogue
     // multiplies each group by its region's weight at the row's pixel and the second GEMM sums over regions through its K axis --
     // the same launches as the plain fold, both GEMMs regions_ times as wide.  Otherwise one attention launch per (image, region)
-    // and a blend launch (correct, not fast: only levels of fewer than 32 pixels, or not a multiple of 32, come here).
+    // and a blend launch (correct, not fast: only levels whose pixels are no multiple of 32, or whose head geometry the fold declines, come here).
     // IMAGE PROMPT (ip_tokens_ > 0): the same two forms with two segments per image, the text keys of kv_all_ and the
     // IPT image tokens of ip_kv_all_ (same column layout: this block's K | V at my_kv), weights (1, s(pixel)): to_out sees
     // attn(q, K_text, V_text) + s attn(q, K_img, V_img).  Only the fold launch differs (two sources of different lengths).
@@ -209,7 +233,8 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
         rgw = IPT > 0 ? ip_w_[lvl] : region_w_[lvl];
     }
     const int NK = heads * 80;
-    const bool xfold = xfold_on && fold && Lkeys <= 80 && NK % 320 == 0 && L % 32 == 0 && d <= 160 && d % 4 == 0;
+    // sdod_xattn_fold_ok is the fold's whole contract, the launch's and the two GEMMs': what it declines takes the forms below
+    const bool xfold = xfold_on && fold && sdod_xattn_fold_ok(heads, d, Lkeys, L) != 0;
     // either form leaves its last GEMM to be emitted once its destination is known: t2 = a[rows][K] . w^T + o2b + t1
     struct { f16* a; int K; const f16* w; GemmOpt o; } xo;
     xo.o.bias = o2b; xo.o.residual = t1.p;
@@ -348,11 +373,14 @@ Act Graph::unet_conv_in(const float* x_in, const float* cond_in) {
         f16* cols = alloc((size_t)B * H * Wd * 64);
         if (wr != 0) { // the wrapped im2col reads NHWC fp16: sdod_latent_im2col_f16 as the two launches it fuses
             Act xl = act(B, H, Wd, LC);
-            emit([=](hipStream_t st) { check_rc(sdod_latent_prep_f16(x_in, nullptr, nullptr, xl.p, B, LC, H * Wd, 1.0f, st)); });
-            emit([=](hipStream_t st) { check_rc(sdod_im2col3x3_small_wrap_f16(xl.p, cols, B, H, Wd, LC, 64, wr, st)); });
+            emit([=](hipStream_t st) { check_rc(sdod_latent_prep_f16(x_in, nullptr, nullptr, xl.p, B, LC, H * Wd, 1.0f, st)); }, "latent_prep", 0,
+                 (double)B * H * Wd * LC * 6);
+            emit([=](hipStream_t st) { check_rc(sdod_im2col3x3_small_wrap_f16(xl.p, cols, B, H, Wd, LC, 64, wr, st)); }, "im2col_wrap", 0,
+                 (double)B * H * Wd * (LC + 64) * 2);
             release(xl);
         } else {
-            emit([=](hipStream_t st) { check_rc(sdod_latent_im2col_f16(x_in, cols, B, H, Wd, LC, 64, 1.0f, st)); });
+            emit([=](hipStream_t st) { check_rc(sdod_latent_im2col_f16(x_in, cols, B, H, Wd, LC, 64, 1.0f, st)); }, "latent_im2col", 0,
+                 (double)B * H * Wd * (LC * 4 + 64 * 2));
         }
         { GemmOpt o; o.bias = cib; linear(cols, B * H * Wd, 64, ciw, MC, h.p, o); }
         release(cols);
@@ -1127,7 +1155,7 @@ Act Graph::clip_block(const std::string& pfx, bool oc, Act x, int heads, int int
 void Graph::build_clip() {
     const int B = batch_, L = cfg_.context_len, D = cfg_.context_dim, heads = cfg_.text_heads, NL = cfg_.text_layers;
     const int rows = B * L, inter = 4 * D;
-    SDOD_REQUIRE(D % heads == 0 && D / heads == 64, "text encoder head dim must be 64");
+    SDOD_REQUIRE(heads > 0 && D % heads == 0 && D / heads == 64, "text_heads must be positive and divide context_dim into heads of 64");
     int32_t* ids = (int32_t*)io_alloc(inputs_, (size_t)rows * sizeof(int32_t));
     f16* out = (f16*)io_alloc(outputs_, (size_t)rows * D * sizeof(f16));
     // two checkpoint dialects of the same pre-LN causal transformer (sdod_model_config.text_arch): HF CLIPTextModel names with

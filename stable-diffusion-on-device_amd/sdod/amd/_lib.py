@@ -141,6 +141,8 @@ def _declare(lib):
         'sdod_compose_linear_f16': (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P]),
         'sdod_lora_merge_f16': (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_float, c_int, c_int, P]),
         'sdod_attention_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P]),
+        'sdod_attention_head_dim_ok': (c_int, [c_int]),
+        'sdod_xattn_fold_ok': (c_int, [c_int, c_int, c_int, c_int]),
         'sdod_xattn_fold_f16': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
         'sdod_xattn_fold_regions_f16': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
         'sdod_region_weights_f32': (c_int, [P, c_int, c_int, c_int, P, P, P, P, P]),
@@ -213,6 +215,7 @@ HIP_SYMBOLS = [
     'sdod_add_control_f16',
     'sdod_gemm_region_f16', 'sdod_xattn_fold_regions_f16', 'sdod_region_weights_f32', 'sdod_region_blend_f16',
     'sdod_xattn_fold_ip_f16', 'sdod_ip_weights_f32', 'sdod_patch_embed_u8_f16', 'sdod_vit_tokens_f16',
+    'sdod_attention_head_dim_ok', 'sdod_xattn_fold_ok',
 ]
 
 

@@ -70,6 +70,12 @@ NHWC_CASES = [  # n, hw, c, groups, dtype, path
     (2, 256, 320, 32, torch.float32, 2),
     (1, 16384, 512, 32, torch.float32, 3),
     (1, 65536, 128, 32, torch.float32, 3),    # > 128 statistics chunks: the collapse launch, slab 256 Ki
+    # fewer than 8 channels per group (model_channels 64 / 128 / 192, tests/test_engine_widths_gpu.py): a 16-byte piece of a pixel
+    # row covers several groups, so the (image, group) kernel works on 2- or 4-channel vectors
+    (2, 1024, 64, 32, torch.float16, 1),      # 2 channels per group: one 2-vector per pixel, 1024 threads
+    (2, 1024, 128, 32, torch.float16, 1),     # 4 channels per group: one 4-vector per pixel
+    (2, 256, 192, 32, torch.float16, 1),      # 6 channels per group: three 2-vectors per pixel, 341 pixels per pass
+    (2, 16, 192, 32, torch.float16, 1),       # ... and on the 4x4 map: the 256-thread form
 ]
 
 

@@ -100,8 +100,11 @@ def test_a_concat_width_the_input_convolution_cannot_take_is_refused():
             E.UNet(E.sd14_config(16, 16, concat_channels=cc), 2)
     cfg = E.sd14_config(16, 16, concat_channels=5)
     cfg.model_channels = 192                  # the im2col + GEMM branch has no second source
-    with pytest.raises(SdodError):
+    cfg.num_heads, cfg.head_dim = 0, 64       # (a head geometry this width admits: the refusal is the input convolution's)
+    with pytest.raises(SdodError, match='concat_channels'):
         E.UNet(cfg, 2)
+    cfg.concat_channels = 0
+    assert dict(E.UNet(cfg, 2).param_table())['input_blocks.0.0.weight'] == (192, 4, 3, 3)
 
 
 def test_model_config_mirror_has_the_size_the_library_fills():
