@@ -649,6 +649,42 @@ typedef struct sdod_k_step_args {
     float guidance, d0, d1, a, b, cprev, u, stage_scale;
 } sdod_k_step_args;
 SDOD_API int sdod_k_step(const sdod_k_step_args* a, void* stream);
+
+/* sdod_k_step on a MultiDiffusion canvas (Bar-Tal et al. 2023; host loop: sdod/amd/pipeline.py, sample_panorama; host tables:
+ * sdod/amd/panorama.py): the UNet ran on ny * nx overlapping windows [wh][ww] of ONE canvas latent x [c][H][W]; window w = iy * nx + ix
+ * covers rows oy[iy] .. + wh and columns ox[ix] .. + ww (with wrap_x the columns modulo W) and lies in chunk w / n of the predictions,
+ * unconditional row w % n, conditional row n + w % n.  Per canvas element, with the covering windows taken in ascending w:
+ *   acc = 0 ;  acc = acc + wgt[window pixel] * CFG_w     [CFG_w: sdod_cfg_combine of window w's pair at that window pixel]
+ *   e   = acc / wsum[canvas pixel]                        [one IEEE-correct fp32 division]
+ *   den = d0 * x + d1 * e ;  x' = a * x + b * den (+ cprev * den_prev) (+ u * nu) ;  den_prev <- den ;  x <- x'     [as sdod_k_step]
+ * then x_stage (window w, both of its rows) = stage_scale * x' at every window pixel that covers the element, and temb_row into
+ * temb_dst[temb_reps][..].  Every product, sum and quotient is rounded on its own in fp32 (no FMA contraction).  The rows of a partly
+ * filled last chunk (ny * nx < chunks * n) are neither read nor written.  nu: `noise` fp32 [c][H][W], or when NULL drawn in the kernel,
+ * exactly the values of sdod_randn_f32(count = c * H * W, seed, stream_id = ((3 + noise_level) << 32) | image_index0); with u == 0 no
+ * noise is drawn or read.  eps == NULL is the start form: x <- a * x, then the staging (b, cprev and u must be 0).
+ * wsum is the host's sum of wgt over the covering windows in the same order (panorama.weight_sum); a pixel no window covers has
+ * wsum 0 and gets 0 / 0.  Refused with INVALID_ARGUMENT before any launch: a NULL x / wgt / wsum; x, den_prev, noise or x_stage not
+ * 16-byte aligned, wgt or wsum not 4-byte, eps not 2-byte aligned; a non-finite scalar; c * wh * ww or c * H * W not a multiple of 4;
+ * wh, ww, W or an origin not a multiple of 4; ny or nx outside [1, SDOD_PANO_MAX_AXIS]; an origin outside the canvas (oy + wh > H;
+ * ox + ww > W without wrap, ox >= W with it); ww > W with wrap; ny * nx > chunks * n; cprev != 0 without den_prev.  den_prev, noise,
+ * x_stage, temb_row may be NULL. */
+#define SDOD_PANO_MAX_AXIS 32
+typedef struct sdod_k_step_windows_args {
+    const void* eps;        /* fp16 [chunks][2n][wh * ww][c], or NULL: the start form */
+    float* x;               /* fp32 [c][H][W], updated in place */
+    float* den_prev;        /* fp32 [c][H][W] or NULL: read when cprev != 0, then replaced by this step's den */
+    const float* noise;     /* fp32 [c][H][W] or NULL (drawn in the kernel); touched only when u != 0 */
+    const float* wgt;       /* fp32 [wh * ww]: the weight of a window pixel */
+    const float* wsum;      /* fp32 [H * W]: the sum of the covering windows' weights */
+    float* x_stage;         /* fp32 [chunks][2n][c][wh * ww] or NULL */
+    const void* temb_row;   /* fp16 [temb_width] or NULL */
+    void* temb_dst;         /* fp16 [temb_reps][temb_width] */
+    uint64_t seed, image_index0;
+    int c, H, W, wh, ww, ny, nx, wrap_x, n, chunks, mode, noise_level, temb_width, temb_reps;
+    int oy[SDOD_PANO_MAX_AXIS], ox[SDOD_PANO_MAX_AXIS];
+    float guidance, d0, d1, a, b, cprev, u, stage_scale;
+} sdod_k_step_windows_args;
+SDOD_API int sdod_k_step_windows(const sdod_k_step_windows_args* a, void* stream);
 /* Inpainting's latent keep-mask: mask_u8 uint8 [n][factor * h_lat][factor * w_lat] (255 = repaint, 0 = keep) -> keep fp32
  * [n][h_lat][w_lat] = float(16320 - S) / 16320.0f with S the integer sum of the latent pixel's 8 x 8 block (16320 = 64 * 255; one
  * correctly rounded fp32 division).  factor must be 8 (the VAE's scale); mask_u8 8-byte aligned. */

@@ -7,7 +7,7 @@
 //   image_to_u8         context.cpp:392-395
 // and the PLMS/DDIM arithmetic of config 1's CPU reference (ldm PLMSSampler; not in /root/reference), with ldm's masked DDIM
 // blend for inpainting (ddim_inpaint_step, mask_to_latent, image_composite), and the k-diffusion samplers' step in its linear form
-// (k_step: Euler, Euler ancestral, DPM++ 2M).
+// (k_step: Euler, Euler ancestral, DPM++ 2M; k_step_windows: the same step on a MultiDiffusion canvas, behind the windows' average).
 #include "common.h"
 #include <atomic>
 #include <cmath>
@@ -1171,6 +1171,79 @@ __global__ void k_step_kernel(const sdod_k_step_args a) {
     }
 }
 
+// the windows of a MultiDiffusion canvas that cover the four columns x0 .. x0 + 3 of row y, in ascending w = iy * nx + ix; f(w, p): p =
+// the window pixel of column x0.  W, ww and every origin are multiples of 4 (checked by the host), so the four columns share their
+// windows and lie side by side in each; with wrap_x a window's columns run modulo W and ww <= W, so it holds a column at most once.
+template <typename F>
+SDOD_DEVICE void for_covering_windows(const sdod_k_step_windows_args& a, int y, int x0, F f) {
+    for (int iy = 0; iy < a.ny; ++iy) {
+        const int ly = y - a.oy[iy];
+        if (ly < 0 || ly >= a.wh) continue;
+        for (int ix = 0; ix < a.nx; ++ix) {
+            int lx = x0 - a.ox[ix];
+            if (a.wrap_x && lx < 0) lx += a.W;
+            if (lx < 0 || lx >= a.ww) continue;
+            f(iy * a.nx + ix, ly * a.ww + lx);
+        }
+    }
+}
+
+// k_step_kernel on a MultiDiffusion canvas (include/sdod_hip.h: sdod_k_step_windows): e = (sum over the covering windows, ascending,
+// of wgt * CFG_w) / wsum, then k_step_kernel's den, x', den_prev <- den, x <- x'; x_stage of every covering window (both rows) <-
+// stage_scale * x', and the time row.  eps NULL: the start form.  Thread = four consecutive canvas elements of one row = one Philox
+// block of the canvas's noise stream; x, den_prev, noise and the staged windows move as 16-byte lanes.
+__global__ void k_step_windows_kernel(const sdod_k_step_windows_args a) {
+    const int hw = a.H * a.W, whw = a.wh * a.ww;
+    const size_t nblk = (size_t)a.c * hw / 4, nt = temb_work(a); // c * H * W % 4 == 0, pointers 16-byte aligned (checked by the host)
+    const size_t chunk_eps = (size_t)2 * a.n * whw * a.c;       // elements of one chunk of eps, and of x_stage
+    GRID_STRIDE(t, nblk + nt) {
+        if (t >= nblk) {
+            broadcast_row((f16*)a.temb_dst, (const f16*)a.temb_row, a.temb_width, t - nblk);
+            continue;
+        }
+        const size_t o = 4 * t;
+        const int ch = (int)(o / hw), pix = (int)(o - (size_t)ch * hw); // W % 4 == 0: pix .. pix + 3 lie in one row
+        const int y = pix / a.W, x0 = pix - y * a.W;
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + o);
+        f32x4 out, den = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (a.eps) {
+            f32x4 dp = f32x4{0.f, 0.f, 0.f, 0.f};
+            f32x4 nu = f32x4{0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (a.cprev != 0.0f) dp = *reinterpret_cast<const f32x4*>(a.den_prev + o);
+            if (a.u != 0.0f) nu = noise4(a.noise, o, t, a.seed, ((uint64_t)(3 + a.noise_level) << 32) | a.image_index0);
+            for_covering_windows(a, y, x0, [&](int w, int p) {
+                const f16* e = (const f16*)a.eps + (size_t)(w / a.n) * chunk_eps;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    acc[q] = add_rn(acc[q], mul_rn(a.wgt[p + q], guided_eps(e, w % a.n, ch, p + q, a.n, a.c, whw, 1, a.guidance, a.mode)));
+            });
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float e = div_rn(acc[q], a.wsum[pix + q]);
+                const float d = lincomb4v(a.d0, xv[q], a.d1, e, false, 0.f, 0.f, false, 0.f, 0.f, 1.0f);
+                den[q] = d;
+                out[q] = lincomb4v(a.a, xv[q], a.b, d, a.cprev != 0.0f, a.cprev, dp[q], a.u != 0.0f, a.u, nu[q], 1.0f);
+            }
+            if (a.den_prev) *reinterpret_cast<f32x4*>(a.den_prev + o) = den;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) out[q] = div_rn(mul_rn(a.a, xv[q]), 1.0f); // lincomb4([x], [a], 1)
+        }
+        *reinterpret_cast<f32x4*>(a.x + o) = out;
+        if (a.x_stage) {
+            f32x4 st;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) st[q] = mul_rn(a.stage_scale, out[q]);
+            for_covering_windows(a, y, x0, [&](int w, int p) {
+                float* dst = a.x_stage + (size_t)(w / a.n) * chunk_eps + ((size_t)(w % a.n) * a.c + ch) * whw + p;
+                *reinterpret_cast<f32x4*>(dst) = st;                                // the window's unconditional row
+                *reinterpret_cast<f32x4*>(dst + (size_t)a.n * a.c * whw) = st;      // and its conditional row
+            });
+        }
+    }
+}
+
 #define LAUNCH(kernel, work, st, ...)                                                            \
     do {                                                                                         \
         SDOD_LAUNCH(kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)(st), __VA_ARGS__); \
@@ -1618,6 +1691,36 @@ extern "C" int sdod_k_step(const sdod_k_step_args* a, void* stream) {
     SDOD_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->den_prev | (uintptr_t)a->noise | (uintptr_t)a->x_stage) & 15) == 0 &&
                      ((uintptr_t)a->eps_nhwc & 1) == 0, "misaligned pointer (x, den_prev, noise, x_stage: 16 bytes)");
     LAUNCH(k_step_kernel, work, stream, *a);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_k_step_windows(const sdod_k_step_windows_args* a, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(a && a->x && a->wgt && a->wsum && a->c > 0 && a->H > 0 && a->W > 0 && a->wh > 0 && a->ww > 0 && a->n > 0 && a->chunks > 0 &&
+                     (a->mode == 0 || a->mode == 1) && (a->wrap_x == 0 || a->wrap_x == 1), "bad argument");
+    SDOD_REQUIRE(std::isfinite(a->guidance) && std::isfinite(a->d0) && std::isfinite(a->d1) && std::isfinite(a->a) && std::isfinite(a->b) &&
+                     std::isfinite(a->cprev) && std::isfinite(a->u) && std::isfinite(a->stage_scale), "non-finite scalar");
+    // every count the kernel forms stays an int: one canvas or one chunk of 2^31 elements is no latent
+    SDOD_REQUIRE((uint64_t)a->c * a->H * a->W < (1ull << 31) && (uint64_t)2 * a->n * a->c * a->wh * a->ww < (1ull << 31), "canvas or chunk too large");
+    SDOD_REQUIRE(((size_t)a->c * a->wh * a->ww) % 4 == 0 && ((size_t)a->c * a->H * a->W) % 4 == 0, "c * wh * ww and c * H * W must be multiples of 4");
+    SDOD_REQUIRE(a->wh % 4 == 0 && a->ww % 4 == 0 && a->W % 4 == 0, "wh, ww and W must be multiples of 4");
+    SDOD_REQUIRE(a->ny >= 1 && a->ny <= SDOD_PANO_MAX_AXIS && a->nx >= 1 && a->nx <= SDOD_PANO_MAX_AXIS, "ny, nx must be in [1, SDOD_PANO_MAX_AXIS]");
+    SDOD_REQUIRE(!a->wrap_x || a->ww <= a->W, "a wrapped window cannot be wider than the canvas");
+    for (int i = 0; i < a->ny; ++i)
+        SDOD_REQUIRE(a->oy[i] >= 0 && a->oy[i] % 4 == 0 && a->oy[i] <= a->H - a->wh, "a y origin is outside the canvas or no multiple of 4");
+    for (int i = 0; i < a->nx; ++i)
+        SDOD_REQUIRE(a->ox[i] >= 0 && a->ox[i] % 4 == 0 && (a->wrap_x ? a->ox[i] < a->W : a->ox[i] <= a->W - a->ww),
+                     "an x origin is outside the canvas or no multiple of 4");
+    SDOD_REQUIRE((int64_t)a->ny * a->nx <= (int64_t)a->chunks * a->n, "more windows than chunks * n rows");
+    SDOD_REQUIRE(a->cprev == 0.0f || a->den_prev, "cprev needs den_prev");
+    SDOD_REQUIRE(a->eps || (a->b == 0.0f && a->cprev == 0.0f && a->u == 0.0f), "the start form (eps NULL) takes a alone: b, cprev, u must be 0");
+    SDOD_REQUIRE(a->u == 0.0f || a->noise || a->noise_level >= 0, "negative noise level");
+    SDOD_REQUIRE(!a->temb_row || (a->temb_dst && a->temb_width > 0 && a->temb_reps > 0), "bad time-conditioning argument");
+    SDOD_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->den_prev | (uintptr_t)a->noise | (uintptr_t)a->x_stage) & 15) == 0 &&
+                     (((uintptr_t)a->wgt | (uintptr_t)a->wsum) & 3) == 0 && ((uintptr_t)a->eps & 1) == 0,
+                 "misaligned pointer (x, den_prev, noise, x_stage: 16 bytes; wgt, wsum: 4)");
+    LAUNCH(k_step_windows_kernel, (size_t)a->c * a->H * a->W / 4 + temb_work(*a), stream, *a);
     return 0;
     SDOD_CATCH
 }

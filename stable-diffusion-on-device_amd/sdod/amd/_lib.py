@@ -77,6 +77,19 @@ class KStepArgs(ctypes.Structure):
                [(k, ctypes.c_float) for k in ('guidance', 'd0', 'd1', 'a', 'b', 'cprev', 'u', 'stage_scale')]
 
 
+PANO_MAX_AXIS = 32      # SDOD_PANO_MAX_AXIS (include/sdod_hip.h)
+
+
+class KStepWindowsArgs(ctypes.Structure):
+    """mirror of `struct sdod_k_step_windows_args` (include/sdod_hip.h)"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ('eps', 'x', 'den_prev', 'noise', 'wgt', 'wsum', 'x_stage', 'temb_row', 'temb_dst')] + \
+               [('seed', ctypes.c_uint64), ('image_index0', ctypes.c_uint64)] + \
+               [(k, ctypes.c_int) for k in ('c', 'H', 'W', 'wh', 'ww', 'ny', 'nx', 'wrap_x', 'n', 'chunks', 'mode', 'noise_level',
+                                            'temb_width', 'temb_reps')] + \
+               [('oy', ctypes.c_int * PANO_MAX_AXIS), ('ox', ctypes.c_int * PANO_MAX_AXIS)] + \
+               [(k, ctypes.c_float) for k in ('guidance', 'd0', 'd1', 'a', 'b', 'cprev', 'u', 'stage_scale')]
+
+
 class GemmDesc(ctypes.Structure):
     """mirror of `struct sdod_gemm_desc` (include/sdod_hip.h)"""
     _fields_ = [
@@ -181,6 +194,7 @@ def _declare(lib):
         'sdod_dpm_step': (c_int, [ctypes.POINTER(DpmStepArgs), P]),
         'sdod_ddim_inpaint_step': (c_int, [ctypes.POINTER(DdimInpaintStepArgs), P]),
         'sdod_k_step': (c_int, [ctypes.POINTER(KStepArgs), P]),
+        'sdod_k_step_windows': (c_int, [ctypes.POINTER(KStepWindowsArgs), P]),
         'sdod_mask_to_latent_f32': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
         'sdod_image_composite_u8': (c_int, [P, P, P, P, c_int, c_size_t, c_float, c_float, c_int, P]),
         'sdod_nchw_f32_to_nhwc_f16': (c_int, [P, P, c_int, c_int, c_int, c_float, P]),
@@ -216,6 +230,7 @@ HIP_SYMBOLS = [
     'sdod_gemm_region_f16', 'sdod_xattn_fold_regions_f16', 'sdod_region_weights_f32', 'sdod_region_blend_f16',
     'sdod_xattn_fold_ip_f16', 'sdod_ip_weights_f32', 'sdod_patch_embed_u8_f16', 'sdod_vit_tokens_f16',
     'sdod_attention_head_dim_ok', 'sdod_xattn_fold_ok',
+    'sdod_k_step_windows',
 ]
 
 

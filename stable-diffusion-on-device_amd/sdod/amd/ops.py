@@ -1019,6 +1019,51 @@ def k_step(eps_nhwc, x, coef, guidance=1.0, den_prev=None, noise=None, seed=0, n
     check(lib.sdod_k_step(ctypes.byref(a), _stream()))
 
 
+def k_step_windows(eps, x, coef, wgt, wsum, window_hw, oy, ox, n, chunks=1, wrap_x=False, guidance=1.0, den_prev=None, noise=None, seed=0,
+                   noise_level=0, image_index=0, mode=1, stage=None):
+    """k_step on a MultiDiffusion canvas in one launch (include/sdod_hip.h: sdod_k_step_windows).  x fp32 [1, c, H, W] (or [c, H, W]): the
+    canvas, updated in place; eps fp16 [chunks, 2n, wh, ww, c] (one chunk: [2n, wh, ww, c], the UNet's own output): the predictions of
+    the len(oy) * len(ox) windows of window_hw = (wh, ww) at origins oy x ox, window w = iy * len(ox) + ix in chunk w // n, rows w % n
+    and n + w % n; wgt fp32 [wh, ww] and wsum fp32 [H, W] from sdod.amd.panorama (window_weights, weight_sum).  e = sum_w wgt CFG_w /
+    wsum over the covering windows in ascending w, then k_step's update with coef = KSchedule.coef(...), den_prev and noise (canvas
+    shaped; None: Philox stream ((3 + noise_level) << 32) | image_index of `seed`).  stage = (x_dst, temb_row, temb_dst): x_dst fp32
+    [chunks, 2n, c, wh, ww] receives stage_scale * x' in both rows of every window, rows of no window keep their bytes.  eps None: the
+    start form, x <- a x and the staging."""
+    lib = _lib.hip()
+    _req(x, torch.float32, 'x'); _req(wgt, torch.float32, 'wgt'); _req(wsum, torch.float32, 'wsum')
+    c, H, W = (int(v) for v in x.shape[-3:])
+    wh, ww = (int(v) for v in window_hw)
+    assert x.numel() == c * H * W and wgt.numel() == wh * ww and wsum.numel() == H * W, (x.shape, wgt.shape, wsum.shape)
+    a = _lib.KStepWindowsArgs()
+    per_chunk = 2 * int(n) * c * wh * ww
+    if eps is not None:
+        _req(eps, torch.float16, 'eps')
+        assert eps.numel() == int(chunks) * per_chunk, (eps.shape, chunks, n, c, wh, ww)
+        a.eps = _p(eps)
+    a.x, a.wgt, a.wsum = _p(x), _p(wgt), _p(wsum)
+    for t, name in ((den_prev, 'den_prev'), (noise, 'noise')):
+        if t is not None:
+            _req(t, torch.float32, name)
+            assert t.numel() == x.numel(), (name, t.shape, x.shape)
+    a.den_prev, a.noise = _p(den_prev), _p(noise)
+    a.seed, a.noise_level, a.image_index0 = int(seed) & (2 ** 64 - 1), int(noise_level), int(image_index) & (2 ** 64 - 1)
+    a.c, a.H, a.W, a.wh, a.ww, a.n, a.chunks, a.mode, a.wrap_x = c, H, W, wh, ww, int(n), int(chunks), mode, 1 if wrap_x else 0
+    a.ny, a.nx = len(oy), len(ox)                 # (the library refuses a count above the tables' size; the tables take what fits)
+    for dst, src in ((a.oy, oy), (a.ox, ox)):
+        for i, v in enumerate(list(src)[:_lib.PANO_MAX_AXIS]):
+            dst[i] = int(v)
+    a.guidance = guidance
+    a.d0, a.d1, a.a, a.b = coef.get('d0', 1.0), coef.get('d1', 0.0), coef.get('a', 0.0), coef.get('b', 0.0)
+    a.cprev, a.u, a.stage_scale = coef.get('cprev', 0.0), coef.get('u', 0.0), coef.get('stage_scale', 0.0)
+    if stage is not None:
+        x_dst, temb_row, temb_dst = stage
+        _req(x_dst, torch.float32, 'x_dst'); _req(temb_row, torch.float16, 'temb_row'); _req(temb_dst, torch.float16, 'temb_dst')
+        assert x_dst.numel() == int(chunks) * per_chunk and temb_dst.numel() % temb_row.numel() == 0, (x_dst.shape, chunks, n)
+        a.x_stage = _p(x_dst)
+        a.temb_row, a.temb_dst, a.temb_width, a.temb_reps = _p(temb_row), _p(temb_dst), temb_row.numel(), temb_dst.numel() // temb_row.numel()
+    check(lib.sdod_k_step_windows(ctypes.byref(a), _stream()))
+
+
 def mask_to_latent(mask_u8, factor=8):
     """inpainting's latent keep-mask (sdod_mask_to_latent_f32): uint8 [n, 8H, 8W] (255 = repaint, 0 = keep) -> fp32 [n, H, W],
     keep = (16320 - sum of the 8 x 8 block) / 16320"""

@@ -16,6 +16,7 @@ from . import prompts as PR
 from . import regions as RG
 from . import ip_adapter as IP
 from . import upscale as UP
+from . import panorama as PN
 from .host import DpmSolver
 from .samplers import K_SAMPLERS, K_SCHEDULES, PLMS_ORDERS, KSchedule, PlmsSchedule
 
@@ -47,11 +48,16 @@ class Txt2Img:
     ip_proj_dim = 0
     ip_image_size = None
     regions = 0         # regional prompts: prompts per image the UNet was built for (Txt2Img(..., regions=k)), 0 = none
+    canvas_hw = None    # MultiDiffusion panoramas: the canvas latent's (H, W) (Txt2Img(..., canvas_hw=)), or None; canvas_vae: its decoder
+    canvas_wrap = False
+    canvas_vae = None
+    _pano = None        # {(oy, ox, weights kind): the window plan and its device tables}, created with its first entry
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
-                 adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False, ip_adapter=False):
+                 adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False, ip_adapter=False, canvas_hw=None,
+                 canvas_wrap=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -121,9 +127,20 @@ class Txt2Img:
         a captured trajectory picks up a new image, weight or mask without a recapture.  Works with loras, with_vae_encoder, upscaler,
         rectangular latent_hw and images_per_gpu > 1 (one image prompt per image).  Not with regions, prompt_chunks > 1, cfg_split,
         hires_hw, controlnet, adapter, tiling, inpaint_unet, model='sd21' or uint8 weights: ValueError before any device work
-        (ip_adapter.ip_check_build).  False: nothing is constructed or sized differently."""
+        (ip_adapter.ip_check_build).  False: nothing is constructed or sized differently.
+        canvas_hw=(H, W), latent_hw's size rule, each side at least the window's: MultiDiffusion panoramas (DESIGN.md 6n,
+        sdod/amd/panorama.py).  latent_hw is then the window -- the UNet keeps its native size -- and images_per_gpu = n the number of
+        windows per UNet evaluation; self.canvas_vae = E.VaeDecoder(cfg at the canvas size, 1) is built from the same 'vae' weights, for
+        sample_panorama() / decode_canvas() / generate_panorama() / generate_panorama_graphed().  canvas_wrap=True: the windows wrap
+        around the canvas in x and the canvas decoder takes the circular border in x (cfg.tiling = 1): a 360-degree panorama; the UNet's
+        convolutions stay plain, a window is a crop.  Works with loras, prompt_chunks, model='sd21' and weight_quant.  Not with
+        cfg_split, inpaint_unet, hires_hw, adapter, controlnet, regions, ip_adapter, tiling or upscaler: ValueError before any device
+        work (panorama.panorama_check_build).  None: nothing is constructed or sized differently."""
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         latent_h, latent_w = check_latent_hw(latent_hw)
+        self.canvas_hw = PN.panorama_check_build(canvas_hw, canvas_wrap, (latent_h, latent_w), cfg_split, inpaint_unet, hires_hw, adapter,
+                                                 controlnet, regions, ip_adapter, tiling, upscaler)
+        self.canvas_wrap = bool(canvas_wrap)
         adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_unet, model)
         control_check_build(controlnet, cfg_split, hires_hw, inpaint_unet, adapter, tiling, model)
         self.tiling = tiling_check_build(tiling, with_vae_encoder, inpaint_unet, hires_hw, adapter)
@@ -206,12 +223,17 @@ class Txt2Img:
             acfg = E.copy_config(self.cfg)
             acfg.adapter_hint_channels = self.adapter_channels
             self.adapter = E.Adapter(acfg, 1, device)
+        if self.canvas_hw is not None:   # the canvas decoder: the same model at the canvas size, its x border circular under canvas_wrap
+            ccfg = E.sd21_config(*self.canvas_hw) if model == 'sd21' else E.sd14_config(*self.canvas_hw)
+            if self.canvas_wrap:
+                ccfg.tiling = 1
+            self.canvas_vae = E.VaeDecoder(ccfg, 1, device) if with_vae else None
         self._temb_graphs = {}
         self._sd = state_dicts
         self._dir = models_dir
         for g, key, stem in ((self.unet, 'unet', 'unet'), (self.vae, 'vae', 'vae_decoder'), (self.text, 'text', 'text_encoder'),
                              (self.encoder, 'vae_enc', 'vae_encoder'), (self.masked_encoder, 'vae_enc', 'vae_encoder'),
-                             (self.adapter, 'adapter', 'adapter')):
+                             (self.adapter, 'adapter', 'adapter'), (self.canvas_vae, 'vae', 'vae_decoder')):
             if g is None:
                 continue
             self._load(g, key, stem)
@@ -703,6 +725,96 @@ class Txt2Img:
                        seed=seed, noise_level=i, image_index=image_index, mode=1,
                        stage=(self.unet.x, temb[i + 1], self._temb_dst) if i + 1 < steps else None)
         return x
+
+    # ------------------------------------------------------------------ MultiDiffusion panoramas
+    def _panorama_plan(self, x_T, sampler, steps, schedule, eta, stride, weights, step_noise):
+        """the argument checks of the panorama entry points (no device work before them), then the window plan of (stride, weights):
+        origins, chunk count and -- made once per plan -- the device tables wgt [wh, ww] and wsum [H, W] and, for more than one chunk,
+        the zero-filled staging buffer [chunks, 2n, 4, wh, ww] and the prediction buffer [chunks, 2n, wh, ww, 4]"""
+        c, wh, ww = self._latent_shape
+        oy, ox, chunks = PN.panorama_check_args(self.canvas_hw, (wh, ww), self.canvas_wrap, self.n, x_T, sampler, stride, weights)
+        k_check_args(sampler, steps, schedule, eta, step_noise, (c,) + tuple(self.canvas_hw), 1)
+        key = (tuple(oy), tuple(ox), weights)
+        if self._pano is None:
+            self._pano = {}
+        if key not in self._pano:
+            wgt = PN.window_weights((wh, ww), weights)
+            plan = dict(oy=oy, ox=ox, chunks=chunks, wgt=torch.from_numpy(wgt).to(self.device),
+                        wsum=torch.from_numpy(PN.weight_sum(self.canvas_hw, (wh, ww), oy, ox, wgt, self.canvas_wrap)).to(self.device))
+            if chunks > 1:       # zero-filled: the spare rows of a partly filled last chunk evaluate zeros, step after step
+                plan['stage'] = torch.zeros((chunks,) + tuple(self.unet.x.shape), dtype=torch.float32, device=self.device)
+                plan['eps'] = torch.zeros((chunks,) + tuple(self.unet.eps.shape), dtype=torch.float16, device=self.device)
+            self._pano[key] = plan
+        return self._pano[key]
+
+    def _panorama_eps(self, plan):
+        """the windows' predictions [chunks, 2n, wh, ww, 4]: one chunk -- the staged inputs are unet.x, the result unet.eps; more --
+        per chunk its staged rows into unet.x, the UNet, unet.eps out (the time row and the context are the same for every chunk)"""
+        if plan['chunks'] == 1:
+            return self._unet_eps()
+        for k in range(plan['chunks']):
+            self.unet.x.copy_(plan['stage'][k])
+            plan['eps'][k].copy_(self._unet_eps())
+        return plan['eps']
+
+    def sample_panorama(self, ctx2, x_T, sampler='dpmpp_2m', steps=20, guidance=7.5, *, schedule='discrete', eta=1.0, stride=None,
+                        weights='uniform', seed=0, image_index=0, step_noise=None):
+        """MultiDiffusion on the canvas of Txt2Img(canvas_hw=): x_T fp32 [1, 4, H, W] unit-variance noise -> the canvas latent [1, 4, H, W].
+        sample_k's loop with ops.k_step_windows in the place of ops.k_step: the UNet evaluates the overlapping windows of the canvas
+        (latent_hw each, `stride` apart -- an int or (sy, sx), default half the window; panorama.plan_windows), n = images_per_gpu per
+        evaluation; per step ONE launch averages the windows' guided predictions per canvas pixel with `weights` ('uniform' or
+        'gaussian': panorama.window_weights), applies the sampler step on the canvas and scatters c_in * x' into the windows.  One
+        history and one noise stream for the whole canvas: euler_a's noise of step i is step_noise[i] (fp32 [steps - 1, 1, 4, H, W]) or
+        Philox stream ((3 + i) << 32) | image_index of `seed` over the canvas.  With all windows in one evaluation a step is the UNet
+        replay plus that launch; with more, two device copies per further evaluation.  Only the k-samplers: 'plms' and 'dpm' raise
+        ValueError, as every other argument error does before any device work."""
+        plan = self._panorama_plan(x_T, sampler, steps, schedule, eta, stride, weights, step_noise)
+        sch = KSchedule(steps, schedule)
+        temb = self.time_embeddings(sch.times)                             # row i <-> step i
+        self._set_context(ctx2)
+        x = x_T.to(self.device, torch.float32).clone()
+        if step_noise is not None:
+            step_noise = step_noise.to(self.device, torch.float32).contiguous()
+        den_prev = torch.empty_like(x) if sampler == 'dpmpp_2m' else None
+        x_stage = self.unet.x if plan['chunks'] == 1 else plan['stage']
+        grid = dict(wgt=plan['wgt'], wsum=plan['wsum'], window_hw=self._latent_shape[1:], oy=plan['oy'], ox=plan['ox'], n=self.n,
+                    chunks=plan['chunks'], wrap_x=self.canvas_wrap)
+        ops.k_step_windows(None, x, dict(a=float(sch.sigmas[0]), stage_scale=sch.c_in(0)), stage=(x_stage, temb[0], self._temb_dst), **grid)
+        for i in range(steps):
+            cf = sch.coef(sampler, i, eta, self.v_prediction, 0)
+            ops.k_step_windows(self._panorama_eps(plan), x, cf, guidance=guidance, den_prev=den_prev,
+                               noise=step_noise[i] if step_noise is not None and cf['u'] != 0.0 else None,
+                               seed=seed, noise_level=i, image_index=image_index, mode=1,
+                               stage=(x_stage, temb[i + 1], self._temb_dst) if i + 1 < steps else None, **grid)
+        return x
+
+    def decode_canvas(self, latent):
+        """the canvas latent fp32 [1, 4, H, W] -> uint8 [1, 8H, 8W, 3] through self.canvas_vae (its x border circular under canvas_wrap),
+        ldm's 255 * clamp((x + 1) / 2, 0, 1)"""
+        self.canvas_vae.z.copy_(latent)
+        self.canvas_vae.execute(self.use_hip_graph)
+        return ops.image_to_u8(self.canvas_vae.img, 0.5, 0.5, 1)
+
+    def generate_panorama(self, ctx2, x_T, sampler='dpmpp_2m', steps=20, guidance=7.5, *, schedule='discrete', eta=1.0, stride=None,
+                          weights='uniform', seed=0, image_index=0, step_noise=None):
+        """decode_canvas(sample_panorama(...)): uint8 [1, 8H, 8W, 3]"""
+        z = self.sample_panorama(ctx2, x_T, sampler, steps, guidance, schedule=schedule, eta=eta, stride=stride, weights=weights, seed=seed,
+                                 image_index=image_index, step_noise=step_noise)
+        return self.decode_canvas(z)
+
+    def generate_panorama_graphed(self, ctx2, x_T, sampler='dpmpp_2m', steps=20, guidance=7.5, *, schedule='discrete', eta=1.0, stride=None,
+                                  weights='uniform', seed=0, image_index=0, step_noise=None):
+        """generate_panorama() with the whole trajectory -- every chunk's UNet evaluation and copies, the canvas steps, the canvas
+        decode -- replayed as ONE device graph (_replay), captured once per (sampler, steps, guidance, schedule, eta, stride, weights).
+        euler_a's step noise is a static input, the caller's or drawn on the eager path's streams: the result equals
+        generate_panorama() with the same arguments, bit for bit."""
+        plan = self._panorama_plan(x_T, sampler, steps, schedule, eta, stride, weights, step_noise)
+        kw = dict(sampler=sampler, steps=steps, guidance=guidance, schedule=schedule, eta=eta, stride=stride, weights=weights)
+        key = ('panorama', sampler, int(steps), float(guidance), schedule, float(eta), tuple(plan['oy']), tuple(plan['ox']), weights)
+        inputs = dict(ctx2=_copied(ctx2), x_T=_copied(x_T, torch.float32))
+        if sampler == 'euler_a':
+            inputs['step_noise'] = _step_noise(step_noise, (int(steps) - 1,) + tuple(x_T.shape), seed, 0, image_index)
+        return self._replay(key, lambda **s: self.generate_panorama(**s, **kw), inputs)
 
     def _sample(self, sampler, ctx2, x_T, steps, guidance, *, schedule='discrete', eta=1.0, seed=0, image_index=0, step_noise=None):
         """a whole trajectory from unit-variance noise x_T: 'plms', 'dpm' (the keyword arguments play no part) or a k-sampler from its
