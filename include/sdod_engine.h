@@ -301,6 +301,19 @@ typedef struct {
  * untouched.  Synchronises `stream` before it returns. */
 SDOD_API int sdod_graph_set_loras(void* graph, const sdod_lora_entry* entries, int count, void* stream);
 
+/* ---- FreeU (Si et al., CVPR 2024): a switch, not a configuration -- it adds no parameter and composes with every
+ * UNET graph the create functions make (control inputs, adapter inputs, regions, image prompts, wrap, concat_channels, weight_quant).
+ * sdod_graph_enable_freeu (kind UNET, before sdod_graph_finalize; anything else is INVALID_ARGUMENT): in ldm's UNetModel.forward, where
+ * the decoder is about to concatenate h and the popped skip tensor hs_ and both have 4 MC channels (stage 1: b1, s1) or both 2 MC
+ * (stage 2: b2, s2), the graph runs sdod_freeu_f16 (include/sdod_hip.h) on the two: two launches per site, labels freeu_filter and
+ * freeu_scale, six sites for the SD 1.x / 2.x shape (output_blocks 0 .. 4 and 7), behind the control additions where there are any.
+ * The graph gets one more input behind every other one, slot sdod_graph_freeu_input: fp32 [SDOD_FREEU_PARAMS] = {b1, s1, b2, s2,
+ * version, 0, 0, 0}, {1, 1, 1, 1, 2, ...} after finalize -- the identity, at which the launches end without reading or writing a
+ * tensor and out0 has the bits of the graph without the switch.  The kernels read it on the device: a captured hipGraph follows new
+ * values.  A graph without the switch is what it was: same launch list, arena and inputs; its sdod_graph_freeu_input is -1. */
+SDOD_API int sdod_graph_enable_freeu(void* graph);
+SDOD_API int sdod_graph_freeu_input(void* graph, int* index);
+
 #ifdef __cplusplus
 }
 #endif

@@ -388,6 +388,26 @@ typedef struct sdod_control_seg {
     size_t count;  /* halves */
 } sdod_control_seg;
 SDOD_API int sdod_add_control_f16(const sdod_control_seg* segs, int count, const float* scales, void* stream);
+/* ---- FreeU (Si et al., CVPR 2024): what the method does at one decoder site, in place on the two fp16 NHWC tensors
+ * the decoder is about to concatenate, h and skip, both [n][height][width][c].  params is DEVICE memory, fp32
+ * [SDOD_FREEU_PARAMS] = {b1, s1, b2, s2, version (1 or 2), 0, 0, 0}, read by the kernels: a captured launch picks up new values.
+ * stage 1 selects (b, s) = (b1, s1), stage 2 (b2, s2).
+ *   skip: every channel plane v keeps all of its spectrum but the frequency set {0, -1 mod height} x {0, -1 mod width} (the box
+ *         [H/2-1 : H/2+1, W/2-1 : W/2+1] of the published fftshift-ed mask, threshold 1), which is multiplied by s:
+ *           out = fp16(v + (s - 1) / (H W) * Re sum_{(ky,kx) in the set} X[ky,kx] e^{+2 pi i (ky y / H + kx x / W)}),
+ *         X the plane's DFT; fp32 sums in a fixed order, twiddles from sincospi, one rounding to fp16.
+ *   h:    channels [0, c / 2) are multiplied by a factor, channels [c / 2, c) keep their bits.  version 1: factor = b, the result
+ *         fp16((float)h * b).  version 2, per image: m[p] = fp32 mean over all c channels of pixel p, factor[p] =
+ *         (b - 1) (m[p] - min m) / (max m - min m) + 1 -- and factor = 1 where max m == min m (a 1 x 1 map, a constant mean), the
+ *         one departure from the published code, which divides 0 by 0 there.
+ * Two launches, no atomics, the same bits every run: phases bit 0 = launch A (the filter, and the means of h into scratch, fp32
+ * [n][height * width], which version 2 needs), bit 1 = launch B (min / max of the means and the scaling); 3 = both, in that order.
+ * With s == 1 the filter's workgroups, with b == 1 the means' and launch B's, read params and end: nothing is read or written.
+ * c % 128 == 0, height and width in [1, 1024], n in [1, 65535], h and skip 16-byte and params and scratch 4-byte aligned, all
+ * non-null, stage 1 or 2; otherwise INVALID_ARGUMENT before any launch, the tensors untouched.  h, skip and scratch must not overlap. */
+#define SDOD_FREEU_PARAMS 8
+SDOD_API int sdod_freeu_f16(void* h, void* skip, int n, int height, int width, int c, const float* params, int stage, float* scratch,
+                            int phases, void* stream);
 SDOD_API int sdod_im2col3x3_small_f16(const void* x, void* y, int n_img, int h, int w, int c, int kpad, void* stream);
 /* the same kernel with a circular border: wrap bit 0 = columns (x) wrap, bit 1 = rows (y) wrap; a wrapped tap reads pixel
  * (y mod h, x mod w) of its own image.  wrap = 0 is sdod_im2col3x3_small_f16, bit for bit. */

@@ -173,6 +173,196 @@ __global__ void add_control_kernel(const ControlTable t, const float* scales) {
     }
 }
 
+// ---- FreeU (include/sdod_hip.h): two launches per decoder site, both read b / s / version from device memory.
+// Launch A is heterogeneous.  Workgroups [0, filter_groups) own (image, 32 channels) of the skip tensor: seven fp32 sums per channel
+// give the four complex DFT coefficients of the frequency set {0, -1} x {0, -1} (the DC one is real), a second pass over the same
+// pixels -- L2-resident by then -- adds (s - 1) / HW times their inverse transform.  A thread is 8 channels (16 bytes) of every
+// (NT / 4)th pixel, so the sums of a channel meet in a fixed butterfly over the 16 lanes of a wave that share it and then in a fixed
+// order over the NT / 64 waves: no atomics, the same bits every run.  NT = 256, 512 or 1024 threads by the map's size (the host's
+// choice, a function of H W alone): the kernel is a chain of dependent loads per thread, so a large map wants it short.  The
+// twiddles are an fp32 table in LDS built with sincospif (exact at the quarter turns, 2 ulp elsewhere).  The other workgroups write
+// the per-pixel channel mean of h (one wave per pixel) for version 2.  Launch B re-derives min / max of those means per image and
+// scales channels [0, C / 2) of h.
+constexpr int kFreeuCb = 32;            // channels per filter workgroup: 4 lanes of 16 bytes
+constexpr int kFreeuMaxSide = 1024;     // the twiddle table's rows
+constexpr int kFreeuMeanPix = 16;       // pixels per mean workgroup, dealt to its waves in turn
+constexpr int kFreeuScaleLanes = 1024;  // 16-byte lanes per launch-B workgroup
+struct FreeuP {
+    f16* h;
+    f16* skip;
+    const float* params; // b1, s1, b2, s2, version
+    float* scratch;      // [n][H * W] channel means of h
+    int n, H, W, C, stage; // stage 0 / 1 selects (b1, s1) / (b2, s2)
+    unsigned filter_groups;
+};
+
+// sum over the 16 lanes of a wave that share lane & 3, in every one of them: two rotations inside the 16-lane rows, then the rows
+// (common.h: quad_rows_sum) -- register moves only, where a __shfl_xor butterfly would be four LDS round trips per value
+SDOD_DEVICE float mod4_lanes_sum(float v) {
+    v += dpp_move<0x124>(v); // row_ror:4
+    v += dpp_move<0x128>(v); // row_ror:8
+    return quad_rows_sum(v);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void freeu_a_kernel(const FreeuP p) {
+    constexpr int NW = NT / 64;
+    const float b = p.params[2 * p.stage], s = p.params[2 * p.stage + 1];
+    const bool v2 = p.params[4] >= 1.5f;
+    const int tid = threadIdx.x, HW = p.H * p.W, C = p.C;
+    if (blockIdx.x >= p.filter_groups) { // ---- channel means of h
+        if (b == 1.f || !v2) return;
+        const int wave = tid >> 6, lane = tid & 63;
+        const size_t total = (size_t)p.n * HW;
+        const size_t first = (size_t)(blockIdx.x - p.filter_groups) * kFreeuMeanPix;
+        for (int k = wave; k < kFreeuMeanPix; k += NW) {
+            const size_t px = first + k;
+            if (px >= total) return; // (wave-uniform)
+            const f16* row = p.h + px * C;
+            float acc = 0.f;
+            for (int c8 = lane; c8 < C / 8; c8 += 64) {
+                const f16x8 v = ldg8(row + c8 * 8);
+                acc += (((float)v[0] + (float)v[1]) + ((float)v[2] + (float)v[3])) + (((float)v[4] + (float)v[5]) + ((float)v[6] + (float)v[7]));
+            }
+            acc = wave_sum(acc);
+            if (lane == 0) p.scratch[px] = div_rn(acc, (float)C);
+        }
+        return;
+    }
+    if (s == 1.f) return;
+    // ---- Fourier filter of (image, 32 channels) of skip
+    __shared__ float tw[4][kFreeuMaxSide]; // cos, sin of 2 pi x / W; cos, sin of 2 pi y / H
+    __shared__ float part[NW][7][kFreeuCb];
+    __shared__ float coef[7][kFreeuCb];
+    const int W = p.W, H = p.H;
+    for (int i = tid; i < W + H; i += NT) {
+        const bool row = i >= W;
+        float sn, cs;
+        sincospif(row ? div_rn(2.0f * (float)(i - W), (float)H) : div_rn(2.0f * (float)i, (float)W), &sn, &cs);
+        tw[row ? 2 : 0][row ? i - W : i] = cs;
+        tw[row ? 3 : 1][row ? i - W : i] = sn;
+    }
+    __syncthreads();
+    const int cblocks = C / kFreeuCb;
+    const int img = blockIdx.x / cblocks, cb = blockIdx.x - img * cblocks;
+    const int l4 = tid & 3, pg = tid >> 2;
+    f16* base = p.skip + (size_t)img * HW * C + cb * kFreeuCb + l4 * 8;
+    float a[7][8];
+#pragma unroll
+    for (int j = 0; j < 7; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[j][e] = 0.f;
+    for (int px = pg; px < HW; px += NT / 4) {
+        const int y = px / W, x = px - y * W;
+        const float cx = tw[0][x], sx = tw[1][x], cy = tw[2][y], sy = tw[3][y];
+        const float cc = cy * cx - sy * sx, ss = sy * cx + cy * sx; // cos, sin of the summed angle
+        const f16x8 v = ldg8(base + (size_t)px * C);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float f = (float)v[e];
+            a[0][e] += f;
+            a[1][e] = fmaf(f, cx, a[1][e]);
+            a[2][e] = fmaf(f, sx, a[2][e]);
+            a[3][e] = fmaf(f, cy, a[3][e]);
+            a[4][e] = fmaf(f, sy, a[4][e]);
+            a[5][e] = fmaf(f, cc, a[5][e]);
+            a[6][e] = fmaf(f, ss, a[6][e]);
+        }
+    }
+    // the 16 lanes of a wave that hold the same channels (equal lane & 3), then the four waves
+#pragma unroll
+    for (int j = 0; j < 7; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[j][e] = mod4_lanes_sum(a[j][e]);
+    if ((tid & 63) < 4) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) part[tid >> 6][j][l4 * 8 + e] = a[j][e];
+    }
+    __syncthreads();
+    if (tid < 7 * kFreeuCb) {
+        const int j = tid / kFreeuCb, c = tid - j * kFreeuCb;
+        // a side of length 1 has the one frequency 0: its "-1" terms are not in the set
+        const bool in_set = j == 0 || ((j == 1 || j == 2) ? W > 1 : (j == 3 || j == 4) ? H > 1 : (W > 1 && H > 1));
+        const float g = div_rn(s - 1.0f, (float)HW);
+        float sum = part[0][j][c];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) sum += part[w][j][c];
+        coef[j][c] = in_set ? g * sum : 0.f;
+    }
+    __syncthreads();
+    float k[7][8];
+#pragma unroll
+    for (int j = 0; j < 7; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) k[j][e] = coef[j][l4 * 8 + e];
+    for (int px = pg; px < HW; px += NT / 4) {
+        const int y = px / W, x = px - y * W;
+        const float cx = tw[0][x], sx = tw[1][x], cy = tw[2][y], sy = tw[3][y];
+        const float cc = cy * cx - sy * sx, ss = sy * cx + cy * sx;
+        f16* q = base + (size_t)px * C;
+        const f16x8 v = ldg8(q);
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float d = k[0][e];
+            d = fmaf(k[1][e], cx, d);
+            d = fmaf(k[2][e], sx, d);
+            d = fmaf(k[3][e], cy, d);
+            d = fmaf(k[4][e], sy, d);
+            d = fmaf(k[5][e], cc, d);
+            d = fmaf(k[6][e], ss, d);
+            o[e] = (f16)((float)v[e] + d);
+        }
+        stg8(q, o);
+    }
+}
+
+__global__ __launch_bounds__(256) void freeu_b_kernel(const FreeuP p) {
+    const float b = p.params[2 * p.stage];
+    if (b == 1.f) return;
+    const bool v2 = p.params[4] >= 1.5f;
+    const int tid = threadIdx.x, HW = p.H * p.W, C = p.C, img = blockIdx.y;
+    const float* m = p.scratch + (size_t)img * HW;
+    float mn = 0.f, range = 0.f;
+    if (v2) { // min / max of the image's means: order-free, so every workgroup of the image finds the same two values
+        __shared__ float red[2][4];
+        float lo = INFINITY, hi = -INFINITY;
+        for (int i = tid; i < HW; i += 256) {
+            const float v = m[i];
+            lo = fminf(lo, v);
+            hi = fmaxf(hi, v);
+        }
+        lo = -wave_max(-lo);
+        hi = wave_max(hi);
+        if ((tid & 63) == 0) {
+            red[0][tid >> 6] = lo;
+            red[1][tid >> 6] = hi;
+        }
+        __syncthreads();
+        mn = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
+        range = sub_rn(fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3])), mn);
+    }
+    const int lanes = C / 16; // 16-byte lanes of channels [0, C / 2) of one pixel
+    const size_t total = (size_t)HW * lanes;
+    const size_t i0 = (size_t)blockIdx.x * kFreeuScaleLanes;
+    const size_t i1 = i0 + kFreeuScaleLanes < total ? i0 + kFreeuScaleLanes : total;
+    for (size_t i = i0 + tid; i < i1; i += 256) {
+        const size_t px = i / lanes;
+        const int c8 = (int)(i - px * lanes);
+        float f = b;
+        // the published code divides 0 / 0 where every mean is the same; here that case is factor 1
+        if (v2) f = range > 0.f ? add_rn(mul_rn(sub_rn(b, 1.0f), div_rn(sub_rn(m[px], mn), range)), 1.0f) : 1.0f;
+        f16* q = p.h + ((size_t)img * HW + px) * C + c8 * 8;
+        const f16x8 v = ldg8(q);
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (f16)mul_rn((float)v[e], f);
+        stg8(q, o);
+    }
+}
+
 // ---- Regional prompts (include/sdod_hip.h).  Masks uint8 [k][8h][8w] -> per-pixel region weights of the four UNet
 // levels in one launch.  A workgroup owns one pixel of the coarsest level (64 x 64 image pixels = 8 x 8 latent pixels): the sums of
 // the finest level come from the image bytes (thread = a quarter of a latent pixel, two 8-byte rows), every coarser level from the
@@ -1332,6 +1522,40 @@ extern "C" int sdod_add_control_f16(const sdod_control_seg* segs, int count, con
     t.first[count] = (unsigned)groups;
     SDOD_LAUNCH(add_control_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, t, scales);
     SDOD_HIP_CHECK(hipGetLastError());
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_freeu_f16(void* h, void* skip, int n, int height, int width, int c, const float* params, int stage, float* scratch, int phases,
+                              void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(h && skip && params && scratch, "null pointer");
+    SDOD_REQUIRE(n >= 1 && n <= 65535, "n must be in [1, 65535]");
+    SDOD_REQUIRE(height >= 1 && width >= 1 && height <= kFreeuMaxSide && width <= kFreeuMaxSide, "height and width must be in [1, 1024]");
+    SDOD_REQUIRE(c >= 128 && c % 128 == 0, "c must be a positive multiple of 128");
+    SDOD_REQUIRE(stage == 1 || stage == 2, "stage must be 1 (b1, s1) or 2 (b2, s2)");
+    SDOD_REQUIRE(phases >= 1 && phases <= 3, "phases must be 1 (launch A), 2 (launch B) or 3 (both)");
+    SDOD_REQUIRE((((uintptr_t)h | (uintptr_t)skip) & 15) == 0, "misaligned pointer (16 bytes)");
+    SDOD_REQUIRE((((uintptr_t)params | (uintptr_t)scratch) & 3) == 0, "misaligned pointer (params, scratch: 4 bytes)");
+    const size_t hw = (size_t)height * width;
+    const size_t filter_groups = (size_t)n * (c / kFreeuCb), mean_groups = ((size_t)n * hw + kFreeuMeanPix - 1) / kFreeuMeanPix;
+    const size_t scale_groups = (hw * (c / 16) + kFreeuScaleLanes - 1) / kFreeuScaleLanes;
+    SDOD_REQUIRE(filter_groups + mean_groups <= 0x7fffffffu && scale_groups <= 0x7fffffffu, "too many elements for one launch");
+    FreeuP p{};
+    p.h = (f16*)h; p.skip = (f16*)skip; p.params = params; p.scratch = scratch;
+    p.n = n; p.H = height; p.W = width; p.C = c; p.stage = stage - 1;
+    p.filter_groups = (unsigned)filter_groups;
+    if (phases & 1) {
+        const dim3 grid((unsigned)(filter_groups + mean_groups));
+        if (hw <= 64) SDOD_LAUNCH(freeu_a_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        else if (hw <= 128) SDOD_LAUNCH(freeu_a_kernel<512>, grid, dim3(512), 0, (hipStream_t)stream, p);
+        else SDOD_LAUNCH(freeu_a_kernel<1024>, grid, dim3(1024), 0, (hipStream_t)stream, p);
+        SDOD_HIP_CHECK(hipGetLastError());
+    }
+    if (phases & 2) {
+        SDOD_LAUNCH(freeu_b_kernel, dim3((unsigned)scale_groups, (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
+        SDOD_HIP_CHECK(hipGetLastError());
+    }
     return 0;
     SDOD_CATCH
 }

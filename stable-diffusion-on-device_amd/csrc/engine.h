@@ -87,6 +87,10 @@ public:
     void keep_base();
     size_t base_bytes() const { return base_copy_ ? weight_bytes_ : 0; }
     void set_loras(const sdod_lora_entry* entries, int count, hipStream_t st);
+    // FreeU (include/sdod_engine.h): enable_freeu() before finalize() makes build_unet() emit sdod_freeu_f16 at the decoder sites
+    // the channel rule selects and gives the graph its parameter input, slot freeu_input() (-1 without the switch)
+    void enable_freeu();
+    int freeu_input() const { return freeu_ ? freeu_input_ : -1; }
     // skip_static: the inputs marked "static across a sampler run" (UNet: the text context) are unchanged since the
     // previous execute(), so the launches that depend only on them (all cross-attention K/V projections) are skipped
     void execute(hipStream_t st, bool use_hip_graph, bool skip_static = false);
@@ -109,6 +113,9 @@ private:
     int ip_tokens_ = 0;                  // image prompt of the UNET graph (sdod_graph_create_ip): image tokens per image; 0 = none
     const float* ip_w_[4] = {};          // ... its four weight inputs [pixels][2], level ds = 1, 2, 4, 8 (set by build_unet())
     f16* ip_kv_all_ = nullptr;           // ... and the image tokens' K / V of every transformer, [B * ip_tokens][kv_total_], persistent
+    bool freeu_ = false;                 // FreeU of the UNET graph (enable_freeu()): the decoder sites run sdod_freeu_f16 ...
+    int freeu_input_ = -1;               // ... on this input slot, fp32 [SDOD_FREEU_PARAMS], behind every other input
+    void freeu_site(const Act& h, const Act& skip, const float* params, int stage);
     bool has_kv() const { return kind_ == SDOD_GRAPH_UNET || kind_ == SDOD_GRAPH_CONTROLNET; } // owns kv_all_ and the static K/V GEMM
     int batch_;
     int wrap_ = 0; // seamless tiling (UNET, VAE_DECODER): bit 0 = x wraps, bit 1 = y wraps; conv() turns it into sdod_gemm_desc::pad_mode

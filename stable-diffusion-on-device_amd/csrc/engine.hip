@@ -1159,6 +1159,13 @@ void Graph::keep_base() {
     keep_base_ = true;
 }
 
+void Graph::enable_freeu() {
+    SDOD_REQUIRE(kind_ == SDOD_GRAPH_UNET, "FreeU applies to the UNET graph only");
+    SDOD_REQUIRE(!finalized_, "enable_freeu() must be called before finalize()");
+    SDOD_REQUIRE(cfg_.latent_h <= 2048 && cfg_.latent_w <= 2048, "FreeU needs latent_h and latent_w <= 2048 (sdod_freeu_f16 takes sides up to 1024)");
+    freeu_ = true;
+}
+
 void Graph::set_loras(const sdod_lora_entry* entries, int count, hipStream_t st) {
     SDOD_REQUIRE(count >= 0 && (count == 0 || entries != nullptr), "bad entry list");
     SDOD_REQUIRE(finalized_, "graph not finalized");
@@ -1669,6 +1676,22 @@ extern "C" int sdod_graph_keep_base(void* graph) {
     SDOD_TRY
     SDOD_REQUIRE(graph != nullptr, "null graph");
     static_cast<Graph*>(graph)->keep_base();
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_enable_freeu(void* graph) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr, "null graph");
+    static_cast<Graph*>(graph)->enable_freeu();
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_freeu_input(void* graph, int* index) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr && index != nullptr, "null argument");
+    *index = static_cast<Graph*>(graph)->freeu_input();
     return 0;
     SDOD_CATCH
 }

@@ -539,6 +539,17 @@ void Graph::build_unet() {
             ip_w_[l] = wp;
         }
     }
+    // FreeU: b1, s1, b2, s2 and the version, fp32, behind every other input; the identity until the caller writes them
+    const float* freeu_params = nullptr;
+    if (freeu_) {
+        if (mode_ == REAL) freeu_input_ = (int)inputs_.size();
+        float* fp = (float*)io_alloc(inputs_, SDOD_FREEU_PARAMS * sizeof(float));
+        if (mode_ == REAL) {
+            const float init[SDOD_FREEU_PARAMS] = {1.f, 1.f, 1.f, 1.f, 2.f, 0.f, 0.f, 0.f};
+            SDOD_HIP_CHECK(hipMemcpy(fp, init, sizeof(init), hipMemcpyHostToDevice));
+        }
+        freeu_params = fp;
+    }
     f16* e_out = (f16*)io_alloc(outputs_, (size_t)B * H * Wd * LC * sizeof(f16));
     Act ctx;
     ctx.p = ctx_in; ctx.n = B; ctx.h = 1; ctx.w = CL; ctx.c = cd;
@@ -578,6 +589,9 @@ void Graph::build_unet() {
             const std::string pfx = "output_blocks." + std::to_string(oidx++);
             Act skip = hs.back();
             hs.pop_back();
+            // FreeU's channel rule on the two tensors about to be concatenated: 4 MC | 4 MC is stage 1, 2 MC | 2 MC stage 2 (the SD
+            // shape: output_blocks 0 .. 4 and 7).  The control additions, if any, have run; emit() settles what is pending on h.
+            if (freeu_ && h.c == skip.c && (h.c == 4 * MC || h.c == 2 * MC)) freeu_site(h, skip, freeu_params, h.c == 4 * MC ? 1 : 2);
             Act r = res_block(pfx + ".0", h, &skip, kChMult[level] * MC, emb_all, emb_ld, emb_off);
             release(h); release(skip);
             ch = kChMult[level] * MC;
@@ -609,6 +623,22 @@ void Graph::build_unet() {
     release(g);
     if (mode_ == DECLARE) kv_total_ = kv_off_;
     else if (emb_off != emb_total_ || kv_off_ != kv_total_) throw Error(INTERNAL_ERROR, "UNet conditioning bookkeeping mismatch");
+}
+
+// one FreeU site: launch A (skip's low-pass, h's channel means), launch B (h's backbone factor); the means live in the arena between them
+void Graph::freeu_site(const Act& h, const Act& skip, const float* params, int stage) {
+    if (h.n != skip.n || h.h != skip.h || h.w != skip.w) throw Error(INTERNAL_ERROR, "FreeU site: backbone and skip differ in shape");
+    float* means = reinterpret_cast<float*>(alloc((size_t)h.rows() * 2));
+    f16* hp = h.p;
+    f16* sp = skip.p;
+    const int n = h.n, hh = h.h, ww = h.w, c = h.c;
+    const std::string shape = "n" + std::to_string(n) + " hw" + std::to_string(hh * ww) + " c" + std::to_string(c) + " stage" + std::to_string(stage);
+    const double numel = (double)h.numel();
+    emit([=](hipStream_t st) { check_rc(sdod_freeu_f16(hp, sp, n, hh, ww, c, params, stage, means, 1, st)); }, "freeu_filter", 0,
+         numel * 6 + (double)h.rows() * 4, shape);
+    emit([=](hipStream_t st) { check_rc(sdod_freeu_f16(hp, sp, n, hh, ww, c, params, stage, means, 2, st)); }, "freeu_scale", 0,
+         numel * 2 + (double)h.rows() * 4, shape);
+    release(means);
 }
 
 // (prefix, cout) of every ResBlock in the order build_unet() visits them: the column layout of the TEMB graph's output

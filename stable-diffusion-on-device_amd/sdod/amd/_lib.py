@@ -175,6 +175,7 @@ def _declare(lib):
         'sdod_adapter_stage_f16': (c_int, [P, P, c_size_t, c_float, P]),
         'sdod_add_feature_f16': (c_int, [P, P, c_size_t, c_int, P]),
         'sdod_add_control_f16': (c_int, [ctypes.POINTER(ControlSeg), c_int, P, P]),
+        'sdod_freeu_f16': (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P]),
         'sdod_im2col3x3_small_f16': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
         'sdod_im2col3x3_small_wrap_f16': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
         'sdod_latent_im2col_f16': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
@@ -231,6 +232,7 @@ HIP_SYMBOLS = [
     'sdod_xattn_fold_ip_f16', 'sdod_ip_weights_f32', 'sdod_patch_embed_u8_f16', 'sdod_vit_tokens_f16',
     'sdod_attention_head_dim_ok', 'sdod_xattn_fold_ok',
     'sdod_k_step_windows',
+    'sdod_freeu_f16',
 ]
 
 

@@ -37,8 +37,11 @@ class ModelConfig(ctypes.Structure):
     # Image prompts (`struct sdod_ip_config`, next to the struct like the others): image tokens per image of a UNet, which then has the
     # to_k_ip / to_v_ip parameters and the UNet.ip_ctx / UNet.ip_w inputs; 0 = the plain graph through the old creation entry points.
     ip_tokens = 0
+    # FreeU (sdod_graph_enable_freeu, a switch on the created graph, not a configuration struct): 1 makes a UNet run the FreeU launches at
+    # its decoder sites and gives it the UNet.freeu parameter input; composes with every attribute above; 0 = the graph as it was.
+    freeu = 0
     _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'tiling', 'control_inputs', 'control_temb', 'regions',
-                       'ip_tokens')
+                       'ip_tokens', 'freeu')
 
     @classmethod
     def from_buffer_copy(cls, source, offset=0):
@@ -113,6 +116,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_keep_base', 'sdod_graph_base_bytes', 'sdod_graph_set_loras', 'sdod_graph_create_upscaler',
     'sdod_graph_create_control', 'sdod_graph_bind_output', 'sdod_graph_create_regions',
     'sdod_graph_create_ip', 'sdod_graph_create_vision',
+    'sdod_graph_enable_freeu', 'sdod_graph_freeu_input',
 ]
 
 
@@ -153,6 +157,8 @@ def _engine():
         lib.sdod_graph_keep_base.argtypes = [P]
         lib.sdod_graph_base_bytes.argtypes = [P, ctypes.POINTER(ctypes.c_size_t)]
         lib.sdod_graph_set_loras.argtypes = [P, ctypes.POINTER(LoraEntry), I, P]
+        lib.sdod_graph_enable_freeu.argtypes = [P]
+        lib.sdod_graph_freeu_input.argtypes = [P, ctypes.POINTER(I)]
         lib._sdod_engine_typed = True
     return lib
 
@@ -232,6 +238,8 @@ class Graph:
                 check(self._lib.sdod_graph_create_ex(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(acfg), batch))
             else:       # no adapter anywhere: the entry point, and the graph, of every build before it
                 check(self._lib.sdod_graph_create(ctypes.byref(self._h), kind, ctypes.byref(cfg), batch))
+            if kind == UNET and int(getattr(cfg, 'freeu', 0)):   # a switch on whichever graph was created above
+                self.enable_freeu()
         self.finalized = False
 
     def _on_device(self):
@@ -296,6 +304,17 @@ class Graph:
         (costs base_bytes() of device memory)"""
         check(self._lib.sdod_graph_keep_base(self._h))
         return self
+
+    def enable_freeu(self):
+        """before finalize(), UNET graphs only: the graph runs FreeU at its decoder sites and gets the parameter input UNet.freeu"""
+        check(self._lib.sdod_graph_enable_freeu(self._h))
+        return self
+
+    def freeu_input(self):
+        """index of the FreeU parameter input, -1 for a graph without the switch"""
+        i = ctypes.c_int()
+        check(self._lib.sdod_graph_freeu_input(self._h, ctypes.byref(i)))
+        return i.value
 
     def base_bytes(self):
         n = ctypes.c_size_t()
@@ -424,6 +443,9 @@ class UNet(Graph):
         if t:                       # image prompt: the projected image tokens and the two segments' weights, (1, 0) until set (ops.ip_weights)
             self.ip_ctx = self.io_tensor(False, 3, (b, t, c.context_dim), torch.float16)
             self.ip_w = [self.io_tensor(False, 4 + lvl, ((c.latent_h >> lvl) * (c.latent_w >> lvl), 2), torch.float32) for lvl in range(4)]
+        fi = self.freeu_input()
+        if fi >= 0:                 # FreeU: (b1, s1, b2, s2, version, 0, 0, 0) behind every other input, the identity until set (freeu.params)
+            self.freeu = self.io_tensor(False, fi, (8,), torch.float32)
         return self
 
 

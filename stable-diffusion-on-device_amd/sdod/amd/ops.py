@@ -502,6 +502,27 @@ def add_control(hs, rs, scales):
     return hs
 
 
+def freeu(h, skip, params, stage, scratch=None, phases=3):
+    """FreeU at one decoder site, in place on the fp16 NHWC tensors h and skip, both [n, H, W, C] (sdod_freeu_f16: the two launches a
+    UNet graph with the FreeU switch makes there).  params: fp32 device tensor [8] = (b1, s1, b2, s2, version, 0, 0, 0), read by the
+    kernels; stage 1 uses (b1, s1), stage 2 (b2, s2).  scratch: fp32 device tensor of n * H * W elements (the channel means version 2
+    needs), allocated when None.  The pointer, size and alignment checks are the library's."""
+    lib = _lib.hip()
+    _req(h, torch.float16, 'h'); _req(skip, torch.float16, 'skip'); _req(params, torch.float32, 'params')
+    if h.dim() != 4 or h.shape != skip.shape:
+        raise ValueError(f'h and skip must be [n, H, W, C] tensors of one shape, not {tuple(h.shape)} and {tuple(skip.shape)}')
+    if params.numel() != 8:
+        raise ValueError(f'params must hold 8 floats (b1, s1, b2, s2, version, 0, 0, 0), not {params.numel()}')
+    n, hh, ww, c = h.shape
+    if scratch is None:
+        scratch = torch.empty(max(n * hh * ww, 1), dtype=torch.float32, device=h.device)
+    _req(scratch, torch.float32, 'scratch')
+    if scratch.numel() < n * hh * ww:
+        raise ValueError(f'scratch must hold n * H * W = {n * hh * ww} floats, not {scratch.numel()}')
+    check(lib.sdod_freeu_f16(_p(h), _p(skip), n, hh, ww, c, _p(params), int(stage), _p(scratch), int(phases), _stream()))
+    return h, skip
+
+
 def region_weights(masks_u8, out=None):
     """region masks uint8 [k, 8h, 8w] -> the blend weights of the four UNet levels, fp32 [h/ds * w/ds, k] for ds = 1, 2, 4, 8
     (sdod_region_weights_f32: integer box sums, one division; region 0 where nothing covers a pixel).  out: the four destinations."""

@@ -15,6 +15,7 @@ from . import ops
 from . import prompts as PR
 from . import regions as RG
 from . import ip_adapter as IP
+from . import freeu as FU
 from . import upscale as UP
 from . import panorama as PN
 from .host import DpmSolver
@@ -51,13 +52,14 @@ class Txt2Img:
     canvas_hw = None    # MultiDiffusion panoramas: the canvas latent's (H, W) (Txt2Img(..., canvas_hw=)), or None; canvas_vae: its decoder
     canvas_wrap = False
     canvas_vae = None
+    freeu = False       # FreeU: the UNet was built with the switch and has the unet.freeu parameter input (Txt2Img(..., freeu=True))
     _pano = None        # {(oy, ox, weights kind): the window plan and its device tables}, created with its first entry
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
                  adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False, ip_adapter=False, canvas_hw=None,
-                 canvas_wrap=False):
+                 canvas_wrap=False, freeu=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -135,7 +137,15 @@ class Txt2Img:
         around the canvas in x and the canvas decoder takes the circular border in x (cfg.tiling = 1): a 360-degree panorama; the UNet's
         convolutions stay plain, a window is a crop.  Works with loras, prompt_chunks, model='sd21' and weight_quant.  Not with
         cfg_split, inpaint_unet, hires_hw, adapter, controlnet, regions, ip_adapter, tiling or upscaler: ValueError before any device
-        work (panorama.panorama_check_build).  None: nothing is constructed or sized differently."""
+        work (panorama.panorama_check_build).  None: nothing is constructed or sized differently.
+        freeu=True: FreeU (sdod/amd/freeu.py).  The UNet graph -- whichever one the other arguments select; the hires
+        pipeline's too -- runs two more launches at each of its six decoder sites and gets one input, unet.freeu = (b1, s1, b2, s2,
+        version, 0, 0, 0), the identity until set_freeu() and after clear_freeu(): at the identity the launches end without touching a
+        tensor and the images are the plain pipeline's, bit for bit.  The kernels read the block on the device, so every entry point
+        and sampler follows it and a captured trajectory picks up new values without a recapture.  It needs no weights and composes
+        with every other argument.  Anything but True / False: ValueError before any device work (freeu.freeu_check_build).  False:
+        nothing is constructed or sized differently."""
+        self.freeu = FU.freeu_check_build(freeu)
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         latent_h, latent_w = check_latent_hw(latent_hw)
         self.canvas_hw = PN.panorama_check_build(canvas_hw, canvas_wrap, (latent_h, latent_w), cfg_split, inpaint_unet, hires_hw, adapter,
@@ -210,6 +220,9 @@ class Txt2Img:
         if self.ip_tokens:               # the image tokens and the two segments' weights are inputs of the UNet alone
             unet_cfg = E.copy_config(unet_cfg)
             unet_cfg.ip_tokens = self.ip_tokens
+        if self.freeu:                   # a switch on the UNet graph, whatever else it was configured with
+            unet_cfg = E.copy_config(unet_cfg)
+            unet_cfg.freeu = 1
         vae_cfg = self.cfg
         if self.tiling:                  # the UNet and the VAE decoder take the circular border; every other graph has no border to wrap
             unet_cfg, vae_cfg = E.copy_config(unet_cfg), E.copy_config(self.cfg)
@@ -274,7 +287,7 @@ class Txt2Img:
             self.hires = Txt2Img(state_dicts=state_dicts, models_dir=models_dir, images_per_gpu=images_per_gpu, latent_hw=hires_hw,
                                  device=device, use_hip_graph=use_hip_graph, tokenizer=None, with_text_encoder=False, model=model,
                                  with_vae=with_vae, cfg_split=False, weight_quant=weight_quant, with_vae_encoder=False, inpaint_unet=False,
-                                 prompt_chunks=prompt_chunks, loras=loras)
+                                 prompt_chunks=prompt_chunks, loras=loras, freeu=freeu)
 
     def _load(self, g, key, stem):
         ip_unet = g is self.unet and self.ip_tokens      # its to_k_ip / to_v_ip come from the adapter's container, by the UNet's names
@@ -421,6 +434,27 @@ class Txt2Img:
         for w in self.unet.ip_w:
             w.zero_()
             w[:, 0] = 1.0
+
+    # ------------------------------------------------------------------ FreeU
+    def set_freeu(self, b1, b2, s1, s2, version=2):
+        """the four FreeU numbers in the published argument order -- b1, b2: backbone factors of stage 1 (the 4 MC sites: 1/8 and 1/4
+        of the latent) and stage 2 (the 2 MC site at 1/2); s1, s2: the skip tensors' low-frequency scales there -- and the version:
+        2 (the authors' current code and the front ends' default) modulates the factor by the per-pixel channel mean, 1 multiplies by b.
+        freeu.preset(version, model) has the README's values, e.g. set_freeu(*freeu.preset(2, 'sd14')).  One copy into unet.freeu (and
+        the hires pipeline's): every later evaluation uses them, eager or captured.  ValueError for a non-finite number, one outside
+        [0, 10] or a version other than 1 or 2 (freeu.freeu_check_args), before any device work; RuntimeError without freeu=True."""
+        FU.require(self)
+        block = FU.freeu_check_args(b1, b2, s1, s2, version)
+        self.unet.freeu.copy_(torch.tensor(block, dtype=torch.float32))
+        if self.hires is not None:
+            self.hires.set_freeu(b1, b2, s1, s2, version)
+
+    def clear_freeu(self):
+        """the identity, the state after construction: the FreeU launches end without reading or writing a tensor"""
+        FU.require(self)
+        self.unet.freeu.copy_(torch.tensor(FU.IDENTITY, dtype=torch.float32))
+        if self.hires is not None:
+            self.hires.clear_freeu()
 
     # ------------------------------------------------------------------ regional prompts
     def set_regions(self, masks_u8):
