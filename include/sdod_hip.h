@@ -321,10 +321,15 @@ SDOD_API int sdod_xattn_fold_ip_f16(const void* kv, int ld_kv, int k_off, int v_
 /* Row softmax on fp16 [M][N] in place semantics allowed (y may equal x); fp32 math. */
 SDOD_API int sdod_softmax_rows_f16(const void* x, void* y, int m, int n, void* stream);
 
-/* Elementwise / glue (fp16 unless stated) */
-SDOD_API int sdod_geglu_f16(const void* x, void* y, int m, int c, void* stream); /* x:[M][2c] -> y = x[:, :c]*gelu(x[:, c:]) */
-SDOD_API int sdod_act_f16(const void* x, void* y, size_t n, int act, void* stream);
-SDOD_API int sdod_add_f16(const void* a, const void* b, void* y, size_t n, void* stream);
+/* Elementwise / glue (fp16 unless stated).
+ * The 16-byte-lane entry points -- sdod_geglu_f16, sdod_act_f16, sdod_add_f16, sdod_concat_channels_f16, sdod_embedding_f16 (table,
+ * pos, y) and, further down, sdod_avg_pool2_f16, sdod_adapter_stage_f16, sdod_add_feature_f16 -- move every fp16 operand as 8 halves
+ * at a time: counts and channel widths are multiples of 8 and every fp16 pointer is 16-byte aligned (16-byte aligned pointers).  A
+ * pointer that is not is refused with INVALID_ARGUMENT ("misaligned pointer") before any launch, the destination untouched.  y may
+ * be x (or a, or b) itself; any other overlap is undefined. */
+SDOD_API int sdod_geglu_f16(const void* x, void* y, int m, int c, void* stream); /* x:[M][2c] -> y = x[:, :c]*gelu(x[:, c:]); c % 8 == 0 */
+SDOD_API int sdod_act_f16(const void* x, void* y, size_t n, int act, void* stream); /* n % 8 == 0 */
+SDOD_API int sdod_add_f16(const void* a, const void* b, void* y, size_t n, void* stream); /* y = fp16((float)a + (float)b); n % 8 == 0 */
 /* ---- Regional prompts.  Region masks -> per-pixel blend weights of the four UNet levels, one launch.
  * masks: uint8 [regions][8 h][8 w] at image resolution (255 = fully inside; soft and overlapping masks allowed), h x w the latent
  * size, both multiples of 8.  For ds = 1, 2, 4, 8: s_r = the integer sum of mask r over the (8 ds)^2 image pixels of a level pixel,
@@ -355,6 +360,8 @@ SDOD_API int sdod_patch_embed_u8_f16(const uint8_t* img, void* out, int n, int i
                                      void* stream);
 SDOD_API int sdod_vit_tokens_f16(const void* patches, const void* class_embedding, const void* position_embedding, const float* ln_weight,
                                  const float* ln_bias, void* out, int n, int num_patches, int width, float eps, void* stream);
+/* y[r] = (a[r] | b[r]): a fp16 [rows][c0], b fp16 [rows][c1] -> y fp16 [rows][c0 + c1], a copy of the bits.  c0 % 8 == 0, c1 % 8 == 0,
+ * 16-byte aligned pointers (see "Elementwise / glue" above). */
 SDOD_API int sdod_concat_channels_f16(const void* a, const void* b, void* y, size_t rows, int c0, int c1, void* stream);
 /* ---- T2I-Adapter structural control (graph kind SDOD_GRAPH_ADAPTER of include/sdod_engine.h).  Each of the four
  * checks its arguments and returns INVALID_ARGUMENT before any launch, the destination untouched; fp32 arithmetic, every operation
@@ -527,12 +534,19 @@ SDOD_API int sdod_latent_resize_f32(const float* src, float* dst, int n, int c, 
 /* Host only: the per-axis table sdod_latent_resize_f32 uses, idx int32 [n_out][4] and w fp32 [n_out][4]; unused slots hold index 0
  * and weight 0. */
 SDOD_API int sdod_latent_resize_taps(int mode, int n_in, int n_out, int32_t* idx, float* w);
+/* y(NHWC fp16)[img][pix][ch] = fp16(fp32(x(NCHW fp32)[img][ch][pix] * scale)): the fp32 product, rounded, is what is rounded to fp16
+ * (nearest even; beyond 65519.99 the infinity of its sign, fp16 subnormals kept) -- two roundings, not one rounding of the exact
+ * product.  No alignment or divisibility requirement. */
 SDOD_API int sdod_nchw_f32_to_nhwc_f16(const float* x, void* y, int n, int c, int hw, float scale, void* stream);
 /* y(NHWC fp16)[img][pix][o] = sum_c w[o][c]*(scale*x(NCHW fp32)[img][c][pix]) + b[o]; w/b fp32 [c][c]/[c] or NULL
- * (identity).  Folds ldm's z/0.18215 and first_stage_model.post_quant_conv into the layout change. */
+ * (identity).  Folds ldm's z/0.18215 and first_stage_model.post_quant_conv into the layout change.  fp32 accumulation from b[o] (or
+ * 0) through the channels in order, one fp16 rounding; c <= 16.  With w and b both NULL the result is sdod_nchw_f32_to_nhwc_f16's
+ * bit for bit, the sign of a zero included. */
 SDOD_API int sdod_latent_prep_f16(const float* x, const float* w, const float* b, void* y, int n, int c, int hw,
                                   float scale, void* stream);
 SDOD_API int sdod_nhwc_f16_to_nchw_f32(const void* x, float* y, int n, int c, int hw, void* stream);
+/* y[r][j] = fp16((float)table[ids[r]][j] + (float)pos[r % seq][j]): table fp16 [vocab][c], pos fp16 [seq][c], ids int32 [rows] (each in
+ * [0, vocab): not checked) -> y fp16 [rows][c].  c % 8 == 0; table, pos and y 16-byte aligned pointers, ids 4-byte. */
 SDOD_API int sdod_embedding_f16(const int32_t* ids, const void* table, const void* pos, void* y, int rows, int seq,
                                 int c, void* stream);
 /* Long, weighted prompts: the cross-attention context of P prompts from their K text-encoder chunks, in one launch.
@@ -575,7 +589,9 @@ SDOD_API int sdod_dpm_update(float* x, const float* eps, float* y_prev, size_t c
 /* ldm DDIM/PLMS step (eta=0): x0 = (x - sqrt(1-abar_t)*e)/sqrt(abar_t); x = sqrt(abar_prev)*x0 + dir_coef*e */
 SDOD_API int sdod_ddim_step_f32(float* x, const float* e, size_t count, float sqrt_one_minus_at, float sqrt_at,
                                 float sqrt_a_prev, float dir_coef, void* stream);
-/* out = (c0*e0 + c1*e1 + c2*e2 + c3*e3)/div, left to right (PLMS Adams-Bashforth combinations); e1..e3 may be NULL */
+/* out = (c0*e0 + c1*e1 + c2*e2 + c3*e3)/div, left to right (PLMS Adams-Bashforth combinations); e1..e3 may be NULL, each on its
+ * own (a NULL term is left out whatever its coefficient; e2 may be given without e1).  Every product, sum and the quotient is
+ * rounded on its own in fp32.  div == 0 is refused with INVALID_ARGUMENT, out untouched.  out may be any of the inputs. */
 SDOD_API int sdod_lincomb4_f32(float* out, const float* e0, const float* e1, const float* e2, const float* e3,
                                float c0, float c1, float c2, float c3, float div, size_t count, void* stream);
 
@@ -716,7 +732,10 @@ SDOD_API int sdod_image_composite_u8(const void* img, const uint8_t* init_u8, co
                                      float a, float b, int mode, void* stream);
 /* img: fp16 NHWC [n][hw][3] -> uint8 HWC per image, f = a*v+b, truncating cast:
  *   mode 0: clamp(255*f, 0, 255)   (context.cpp:392-395; a=1,b=0 is the reference's already-[0,1] convention)
- *   mode 1: 255*clamp(f, 0, 1)     (ldm txt2img with a=0.5, b=0.5) */
+ *   mode 1: 255*clamp(f, 0, 1)     (ldm txt2img with a=0.5, b=0.5)
+ * fp32 throughout, the product a*v, the sum with b and the product with 255 each rounded on its own; clamp(f, lo, hi) is
+ * fminf(fmaxf(f, lo), hi), which returns the bound when f is NaN.  So in both modes a NaN pixel (or a NaN f, as from a = 0 on an
+ * infinite pixel) gives 0, f = +inf gives 255, f = -inf gives 0, and -0 gives 0: every fp16 bit pattern has a defined byte. */
 SDOD_API int sdod_image_to_u8(const void* img, uint8_t* out, size_t count, float a, float b, int mode, void* stream);
 
 SDOD_API const char* sdod_hip_last_error(void);

@@ -25,6 +25,13 @@ SDOD_DEVICE float mul_rn(float a, float b) { return a * b; }
 SDOD_DEVICE float add_rn(float a, float b) { return a + b; }
 SDOD_DEVICE float sub_rn(float a, float b) { return a - b; }
 SDOD_DEVICE float div_rn(float a, float b) { return a / b; }
+// fp16 of an fp32 PRODUCT, in two roundings.  contract(off) does not cover this: the compiler selects v_fma_mixlo_f16 for
+// fptrunc(fmul), which rounds the exact product ONCE to fp16 -- about one result in 10^4 then differs from the fp32 product rounded
+// to fp16, which is what include/sdod_hip.h states.  The empty asm pins the fp32 product in a register.
+SDOD_DEVICE f16 f16_rn(float v) {
+    asm("" : "+v"(v));
+    return (f16)v;
+}
 
 inline int grid_for(size_t work, int block = 256) {
     size_t b = (work + block - 1) / block;
@@ -683,7 +690,7 @@ __global__ void nchw_to_nhwc_kernel(const float* x, f16* y, int n, int c, int hw
         const size_t t = i / c;
         const int pix = (int)(t % hw);
         const int img = (int)(t / hw);
-        y[i] = (f16)(x[((size_t)img * c + ch) * hw + pix] * scale);
+        y[i] = f16_rn(x[((size_t)img * c + ch) * hw + pix] * scale);
     }
 }
 
@@ -700,9 +707,11 @@ __global__ void latent_prep_kernel(const float* x, const float* w, const float* 
         if (w) {
             for (int ch = 0; ch < c; ++ch) acc += w[o * c + ch] * (x[((size_t)img * c + ch) * hw + pix] * scale);
         } else {
-            acc += x[((size_t)img * c + o) * hw + pix] * scale;
+            // without w and b this is nchw_to_nhwc_kernel bit for bit: no 0.f + v in front of the rounding, which would turn -0 into +0
+            const float v = x[((size_t)img * c + o) * hw + pix] * scale;
+            acc = b ? acc + v : v;
         }
-        y[i] = (f16)acc;
+        y[i] = f16_rn(acc);
     }
 }
 
@@ -1443,6 +1452,7 @@ __global__ void k_step_windows_kernel(const sdod_k_step_windows_args a) {
 extern "C" int sdod_geglu_f16(const void* x, void* y, int m, int c, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(x && y && m > 0 && c > 0 && c % 8 == 0, "bad argument");
+    SDOD_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "misaligned pointer (16 bytes)");
     LAUNCH(geglu_kernel, (size_t)m * (c / 8), stream, (const f16*)x, (f16*)y, m, c);
     return 0;
     SDOD_CATCH
@@ -1451,6 +1461,7 @@ extern "C" int sdod_geglu_f16(const void* x, void* y, int m, int c, void* stream
 extern "C" int sdod_act_f16(const void* x, void* y, size_t n, int act, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(x && y && n > 0 && n % 8 == 0, "bad argument (count must be a multiple of 8)");
+    SDOD_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "misaligned pointer (16 bytes)");
     if (act == ACT_RELU) LAUNCH(relu_kernel, n / 8, stream, (const f16*)x, (f16*)y, n / 8);
     else LAUNCH(act_kernel, n / 8, stream, (const f16*)x, (f16*)y, n / 8, act);
     return 0;
@@ -1610,6 +1621,7 @@ extern "C" int sdod_region_blend_f16(const void* a, size_t region_stride, const 
 extern "C" int sdod_add_f16(const void* a, const void* b, void* y, size_t n, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(a && b && y && n > 0 && n % 8 == 0, "bad argument (count must be a multiple of 8)");
+    SDOD_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) == 0, "misaligned pointer (16 bytes)");
     LAUNCH(add_kernel, n / 8, stream, (const f16*)a, (const f16*)b, (f16*)y, n / 8);
     return 0;
     SDOD_CATCH
@@ -1618,6 +1630,7 @@ extern "C" int sdod_add_f16(const void* a, const void* b, void* y, size_t n, voi
 extern "C" int sdod_concat_channels_f16(const void* a, const void* b, void* y, size_t rows, int c0, int c1, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(a && b && y && rows > 0 && c0 > 0 && c1 > 0 && c0 % 8 == 0 && c1 % 8 == 0, "bad argument");
+    SDOD_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) == 0, "misaligned pointer (16 bytes)");
     LAUNCH(concat_kernel, rows * ((c0 + c1) / 8), stream, (const f16*)a, (const f16*)b, (f16*)y, rows, c0, c1);
     return 0;
     SDOD_CATCH
@@ -1810,7 +1823,9 @@ extern "C" int sdod_nhwc_f16_to_nchw_f32(const void* x, float* y, int n, int c, 
 extern "C" int sdod_embedding_f16(const int32_t* ids, const void* table, const void* pos, void* y, int rows, int seq, int c,
                                   void* stream) {
     SDOD_TRY
-    SDOD_REQUIRE(ids && table && pos && y && rows > 0 && seq > 0 && c % 8 == 0, "bad argument");
+    SDOD_REQUIRE(ids && table && pos && y && rows > 0 && seq > 0 && c > 0 && c % 8 == 0, "bad argument");
+    SDOD_REQUIRE((((uintptr_t)table | (uintptr_t)pos | (uintptr_t)y) & 15) == 0 && ((uintptr_t)ids & 3) == 0,
+                 "misaligned pointer (table, pos, y: 16 bytes)");
     LAUNCH(embedding_kernel, (size_t)rows * (c / 8), stream, ids, (const f16*)table, (const f16*)pos, (f16*)y, rows, seq, c);
     return 0;
     SDOD_CATCH

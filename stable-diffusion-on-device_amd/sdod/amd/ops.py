@@ -31,6 +31,20 @@ def _req(t, dtype=None, name='tensor'):
     return t
 
 
+def _req_out(out, like, numel, name='out'):
+    """a caller's destination (or second operand) of a kernel that takes bare pointers: fp16, contiguous, of exactly `numel` elements
+    and on the device of `like`, whose own _req follows and settles that this is the GPU.  Raises before the library is loaded."""
+    if out.dtype != torch.float16:
+        raise ValueError(f'{name} must be {torch.float16}, got {out.dtype}')
+    if not out.is_contiguous():
+        raise ValueError(f'{name} must be contiguous')
+    if out.numel() != numel:
+        raise ValueError(f'{name} must hold {numel} elements, got {out.numel()}')
+    if out.device != like.device:
+        raise ValueError(f'{name} must live on {like.device}, got {out.device}')
+    return out
+
+
 def _ld(t, dtype, name, width, mult=8):
     """Row stride (elements) of a GEMM matrix operand of `width` columns: a contiguous tensor is dense (the width, whatever its
     shape); a 2-D view with unit column stride (a column range of wider rows) gives its row stride, which must be a multiple
@@ -395,8 +409,10 @@ def attention_strided(q, k, v, out, batch, heads, lq, lk, d, ldq, ldk, ldv, ldo,
 
 
 def softmax_rows(x, out=None):
-    lib = _lib.hip()
+    if out is not None:
+        _req_out(out, x, x.numel())
     _req(x, torch.float16, 'x')
+    lib = _lib.hip()
     n = x.shape[-1]; m = x.numel() // n
     if out is None:
         out = torch.empty_like(x)
@@ -405,8 +421,10 @@ def softmax_rows(x, out=None):
 
 
 def geglu(x, out=None):
-    lib = _lib.hip()
+    if out is not None:
+        _req_out(out, x, x.numel() // 2)
     _req(x, torch.float16, 'x')
+    lib = _lib.hip()
     c = x.shape[-1] // 2; m = x.numel() // (2 * c)
     if out is None:
         out = torch.empty(x.shape[:-1] + (c,), dtype=torch.float16, device=x.device)
@@ -415,8 +433,10 @@ def geglu(x, out=None):
 
 
 def activation(x, act, out=None):
-    lib = _lib.hip()
+    if out is not None:
+        _req_out(out, x, x.numel())
     _req(x, torch.float16, 'x')
+    lib = _lib.hip()
     if out is None:
         out = torch.empty_like(x)
     check(lib.sdod_act_f16(_p(x), _p(out), x.numel(), ACT[act], _stream()))
@@ -424,8 +444,11 @@ def activation(x, act, out=None):
 
 
 def add(a, b, out=None):
+    _req_out(b, a, a.numel(), 'b')
+    if out is not None:
+        _req_out(out, a, a.numel())
+    _req(a, torch.float16, 'a')
     lib = _lib.hip()
-    _req(a, torch.float16, 'a'); _req(b, torch.float16, 'b')
     if out is None:
         out = torch.empty_like(a)
     check(lib.sdod_add_f16(_p(a), _p(b), _p(out), a.numel(), _stream()))
