@@ -300,6 +300,22 @@ typedef struct {
  * graph with a kept base and weight_quant = 0, known parameter of a supported kind, rank, finite scale): on a failure the arena is
  * untouched.  Synchronises `stream` before it returns. */
 SDOD_API int sdod_graph_set_loras(void* graph, const sdod_lora_entry* entries, int count, void* stream);
+/* The same for every adapter family: an entry is a plain LoRA pair, a LoHa quadruple (sdod_loha_merge_f16) or a LoKr
+ * pair (sdod_lokr_merge_f16; a = b = 1 adds a full canonical delta), host factors in canonical layout.  Same contract as
+ * sdod_graph_set_loras, which is this call with kind = SDOD_NET_LORA: everything validated before the arena is touched, one upload of
+ * all factors, one merge launch per entry, entries naming the same parameter accumulate in the order given whatever their kinds,
+ * folds re-run, static launches marked stale, no address moves.  LoKr: a must divide the weight's rows and b its input channels. */
+enum { SDOD_NET_LORA = 0, SDOD_NET_LOHA = 1, SDOD_NET_LOKR = 2 };
+typedef struct {
+    const char* name;
+    int kind;         /* SDOD_NET_* */
+    int dtype;        /* SDOD_F16 or SDOD_F32 host factors (rounded to fp16 on the host) */
+    const void* f[4]; /* LORA: up, down | LOHA: w1a, w1b, w2a, w2b | LOKR: w1 [a][b], w2 [n / a][cin / b](, [3][3]) */
+    int rank;         /* LORA, LOHA: 1 .. 128 */
+    int a, b;         /* LOKR */
+    float scale;
+} sdod_network_entry;
+SDOD_API int sdod_graph_set_networks(void* graph, const sdod_network_entry* entries, int count, void* stream);
 
 /* ---- FreeU (Si et al., CVPR 2024): a switch, not a configuration -- it adds no parameter and composes with every
  * UNET graph the create functions make (control inputs, adapter inputs, regions, image prompts, wrap, concat_channels, weight_quant).

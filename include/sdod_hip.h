@@ -266,6 +266,21 @@ SDOD_API int sdod_compose_linear_f16(const void* p, int ldp, const void* w, int 
  * summation order); scale = 0 leaves W bit-identical. */
 SDOD_API int sdod_lora_merge_f16(void* w, int n, int k, int ldw, const void* up, const void* down, int rank, float scale,
                                  int conv_cin, int geglu, void* stream);
+/* The LyCORIS families on the same packed matrix, with the same maps, column block, alignment rules, determinism and scale = 0
+ * behaviour as sdod_lora_merge_f16; every argument error is INVALID_ARGUMENT before any device call.
+ * LoHa (Hadamard product of two low-rank products):
+ *   W'[row(o)][col(j)] = fp16(fma(scale, (sum_r w1a[o][r] w1b[r][j]) * (sum_r w2a[o][r] w2b[r][j]), float(W)))
+ * each sum accumulated in fp32 on the matrix cores, the two multiplied in fp32, one rounding.  w1a, w2a: fp16 [n][rank]; w1b, w2b:
+ * fp16 [rank][k] (a 3x3 convolution: [rank][cin][3][3]), canonical order; rank in [1, 128]. */
+SDOD_API int sdod_loha_merge_f16(void* w, int n, int k, int ldw, const void* w1a, const void* w1b, const void* w2a, const void* w2b,
+                                 int rank, float scale, int conv_cin, int geglu, void* stream);
+/* LoKr (Kronecker product):
+ *   W'[row(o)][col(i, t)] = fp16(fma(scale, float(w1[o / c][i / d]) * float(w2[o % c][i % d][t]), float(W)))
+ * with c = n / a, d = cin / b; cin = k and one tap (t = 0) for a Linear or 1x1 weight, cin = conv_cin and nine taps for a 3x3 one.
+ * w1: fp16 [a][b]; w2: fp16 [c][d] or [c][d][3][3], canonical.  o and i are CANONICAL indices (with geglu the row split applies to
+ * the canonical row).  Any a >= 1 dividing n and b >= 1 dividing cin; a = b = 1 adds the full canonical delta w2. */
+SDOD_API int sdod_lokr_merge_f16(void* w, int n, int k, int ldw, const void* w1, int a, int b, const void* w2, float scale,
+                                 int conv_cin, int geglu, void* stream);
 /* LayerNorm over the last dim of fp16 [M][C] rows, fp32 weight/bias (either may be NULL); C % 8 == 0, C <= 3072. */
 SDOD_API int sdod_layer_norm_f16(const void* x, void* y, const float* weight, const float* bias, int m, int c,
                                  float eps, void* stream);

@@ -86,7 +86,8 @@ public:
     // arena from it -- restore, merge each entry into its packed location, fold and compose again -- without moving a pointer
     void keep_base();
     size_t base_bytes() const { return base_copy_ ? weight_bytes_ : 0; }
-    void set_loras(const sdod_lora_entry* entries, int count, hipStream_t st);
+    void set_loras(const sdod_lora_entry* entries, int count, hipStream_t st); // set_networks with kind = LORA
+    void set_networks(const sdod_network_entry* entries, int count, hipStream_t st);
     // FreeU (include/sdod_engine.h): enable_freeu() before finalize() makes build_unet() emit sdod_freeu_f16 at the decoder sites
     // the channel rule selects and gives the graph its parameter input, slot freeu_input() (-1 without the switch)
     void enable_freeu();

@@ -1146,7 +1146,7 @@ void Graph::run_folds(hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------ LoRA adapters
-// What a graph derives from its weights, and therefore what set_loras() has to redo after the arena changed:
+// What a graph derives from its weights, and therefore what set_loras() / set_networks() have to redo after the arena changed:
 //   * in the arena itself, by finalize(): LayerNorm gamma multiplied into the consuming Linear (fold_jobs_) and
 //     ff.net.2 -> proj_out / conv_out -> quant_conv composed into one matrix (compose_jobs_), each with derived fp32 vectors
 //     (s, t, composed bias) in buffers of their own -- run_folds() rewrites all of them from the pre-fold arena;
@@ -1168,19 +1168,29 @@ void Graph::enable_freeu() {
 
 void Graph::set_loras(const sdod_lora_entry* entries, int count, hipStream_t st) {
     SDOD_REQUIRE(count >= 0 && (count == 0 || entries != nullptr), "bad entry list");
+    std::vector<sdod_network_entry> net((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const sdod_lora_entry& e = entries[i];
+        net[i] = sdod_network_entry{e.name, SDOD_NET_LORA, e.dtype, {e.up, e.down, nullptr, nullptr}, e.rank, 0, 0, e.scale};
+    }
+    set_networks(net.data(), count, st);
+}
+
+void Graph::set_networks(const sdod_network_entry* entries, int count, hipStream_t st) {
+    SDOD_REQUIRE(count >= 0 && (count == 0 || entries != nullptr), "bad entry list");
     SDOD_REQUIRE(finalized_, "graph not finalized");
     SDOD_REQUIRE(base_copy_ != nullptr, "the graph was finalized without keep_base(): merge on the host and rebuild it");
     SDOD_REQUIRE(cfg_.weight_quant == 0, "LoRA adapters need fp16 weights (weight_quant = 0): integer codes cannot take a delta");
     struct Merge {
         f16* w;
-        int n, k, ldw, cin, geglu, rank;
-        size_t up_off, down_off; // halves into the staging buffer
+        int kind, n, k, ldw, cin, geglu, rank, a, b, factors;
+        size_t off[4], cnt[4]; // halves into the staging buffer, halves of each factor
         float scale;
     };
     std::vector<Merge> merges;
     size_t halves = 0;
     for (int i = 0; i < count; ++i) {
-        const sdod_lora_entry& e = entries[i];
+        const sdod_network_entry& e = entries[i];
         SDOD_REQUIRE(e.name != nullptr, "entry " + std::to_string(i) + ": null name");
         const std::string name = e.name;
         auto it = pindex_.find(name);
@@ -1189,24 +1199,44 @@ void Graph::set_loras(const sdod_lora_entry* entries, int count, hipStream_t st)
         SDOD_REQUIRE(p.kind == PK_LINEAR || p.kind == PK_CONV1 || p.kind == PK_LINEAR_GEGLU || p.kind == PK_CONV3,
                      "'" + name + "' is not a LoRA target (3x3 / 1x1 convolution, Linear or GEGLU projection weights only)");
         SDOD_REQUIRE(!p.quant, "'" + name + "' is kept as uint8 codes");
+        SDOD_REQUIRE(e.kind == SDOD_NET_LORA || e.kind == SDOD_NET_LOHA || e.kind == SDOD_NET_LOKR,
+                     "'" + name + "': kind must be SDOD_NET_LORA, SDOD_NET_LOHA or SDOD_NET_LOKR");
         SDOD_REQUIRE(e.dtype == SDOD_F16 || e.dtype == SDOD_F32, "'" + name + "': dtype must be SDOD_F16 or SDOD_F32");
-        SDOD_REQUIRE(e.up != nullptr && e.down != nullptr, "'" + name + "': null factor");
-        SDOD_REQUIRE(e.rank >= 1 && e.rank <= 128, "'" + name + "': rank must be in [1, 128]");
         Merge m{};
+        m.kind = e.kind;
+        m.factors = e.kind == SDOD_NET_LOHA ? 4 : 2;
+        for (int j = 0; j < m.factors; ++j) SDOD_REQUIRE(e.f[j] != nullptr, "'" + name + "': null factor");
         m.w = reinterpret_cast<f16*>(p.dev);
         m.n = (int)p.shape[0];
         m.cin = p.kind == PK_CONV3 ? (int)p.shape[1] : 0;
         m.k = p.kind == PK_CONV3 ? 9 * (int)p.shape[1] : (int)p.shape[1];
         m.ldw = p.ld > 0 ? p.ld : m.k;
         m.geglu = p.kind == PK_LINEAR_GEGLU ? 1 : 0;
-        m.rank = e.rank;
         m.scale = e.scale;
-        m.up_off = halves;
-        halves += align_up((size_t)m.n * m.rank, 8); // every factor starts on a 16-byte boundary
-        m.down_off = halves;
-        halves += align_up((size_t)m.rank * m.k, 8);
+        if (e.kind == SDOD_NET_LOKR) {
+            SDOD_REQUIRE(e.a >= 1 && e.b >= 1 && m.n % e.a == 0 && (m.cin > 0 ? m.cin : m.k) % e.b == 0,
+                         "'" + name + "': the LoKr factor w1 [a][b] must divide the weight's rows and input channels");
+            m.a = e.a;
+            m.b = e.b;
+            m.cnt[0] = (size_t)e.a * e.b;
+            m.cnt[1] = (size_t)(m.n / e.a) * (m.k / e.b);
+        } else {
+            SDOD_REQUIRE(e.rank >= 1 && e.rank <= 128, "'" + name + "': rank must be in [1, 128]");
+            m.rank = e.rank;
+            for (int j = 0; j < m.factors; j += 2) {
+                m.cnt[j] = (size_t)m.n * m.rank;
+                m.cnt[j + 1] = (size_t)m.rank * m.k;
+            }
+        }
+        for (int j = 0; j < m.factors; ++j) {
+            m.off[j] = halves;
+            halves += align_up(m.cnt[j], 8); // every factor starts on a 16-byte boundary
+        }
         try {
-            lora_merge_require(m.w, m.n, m.k, m.ldw, e.up, e.down, m.rank, m.scale, m.cin, m.geglu);
+            if (m.kind == SDOD_NET_LORA) lora_merge_require(m.w, m.n, m.k, m.ldw, e.f[0], e.f[1], m.rank, m.scale, m.cin, m.geglu);
+            else if (m.kind == SDOD_NET_LOHA)
+                loha_merge_require(m.w, m.n, m.k, m.ldw, e.f[0], e.f[1], e.f[2], e.f[3], m.rank, m.scale, m.cin, m.geglu);
+            else lokr_merge_require(m.w, m.n, m.k, m.ldw, e.f[0], m.a, m.b, e.f[1], m.scale, m.cin, m.geglu);
         } catch (const Error& err) {
             throw Error(err.code, "'" + name + "': " + err.what());
         }
@@ -1216,14 +1246,12 @@ void Graph::set_loras(const sdod_lora_entry* entries, int count, hipStream_t st)
     std::vector<f16> host(halves, (f16)0.0f);
     for (int i = 0; i < count; ++i) {
         const Merge& m = merges[i];
-        auto put = [&](const void* src, size_t off, size_t cnt) {
-            f16* dst = host.data() + off;
-            if (entries[i].dtype == SDOD_F16) std::memcpy(dst, src, cnt * sizeof(f16));
+        for (int j = 0; j < m.factors; ++j) {
+            f16* dst = host.data() + m.off[j];
+            if (entries[i].dtype == SDOD_F16) std::memcpy(dst, entries[i].f[j], m.cnt[j] * sizeof(f16));
             else
-                for (size_t j = 0; j < cnt; ++j) dst[j] = (f16) static_cast<const float*>(src)[j];
-        };
-        put(entries[i].up, m.up_off, (size_t)m.n * m.rank);
-        put(entries[i].down, m.down_off, (size_t)m.rank * m.k);
+                for (size_t x = 0; x < m.cnt[j]; ++x) dst[x] = (f16) static_cast<const float*>(entries[i].f[j])[x];
+        }
     }
     struct Staging { // freed on every exit path
         f16* p = nullptr;
@@ -1235,8 +1263,13 @@ void Graph::set_loras(const sdod_lora_entry* entries, int count, hipStream_t st)
     }
     SDOD_HIP_CHECK(hipMemcpyAsync(weight_base_, base_copy_, weight_bytes_, hipMemcpyDeviceToDevice, st));
     static_stale_ = true; // from here on the arena no longer matches what the static launches last saw
-    for (const Merge& m : merges)
-        check_rc(sdod_lora_merge_f16(m.w, m.n, m.k, m.ldw, dev.p + m.up_off, dev.p + m.down_off, m.rank, m.scale, m.cin, m.geglu, st));
+    for (const Merge& m : merges) {
+        const f16* f[4] = {dev.p + m.off[0], dev.p + m.off[1], dev.p + m.off[2], dev.p + m.off[3]};
+        if (m.kind == SDOD_NET_LORA) check_rc(sdod_lora_merge_f16(m.w, m.n, m.k, m.ldw, f[0], f[1], m.rank, m.scale, m.cin, m.geglu, st));
+        else if (m.kind == SDOD_NET_LOHA)
+            check_rc(sdod_loha_merge_f16(m.w, m.n, m.k, m.ldw, f[0], f[1], f[2], f[3], m.rank, m.scale, m.cin, m.geglu, st));
+        else check_rc(sdod_lokr_merge_f16(m.w, m.n, m.k, m.ldw, f[0], m.a, m.b, f[1], m.scale, m.cin, m.geglu, st));
+    }
     run_folds(st);
     SDOD_HIP_CHECK(hipStreamSynchronize(st));
 }
@@ -1708,6 +1741,14 @@ extern "C" int sdod_graph_set_loras(void* graph, const sdod_lora_entry* entries,
     SDOD_TRY
     SDOD_REQUIRE(graph != nullptr, "null graph");
     static_cast<Graph*>(graph)->set_loras(entries, count, (hipStream_t)stream);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_set_networks(void* graph, const sdod_network_entry* entries, int count, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr, "null graph");
+    static_cast<Graph*>(graph)->set_networks(entries, count, (hipStream_t)stream);
     return 0;
     SDOD_CATCH
 }

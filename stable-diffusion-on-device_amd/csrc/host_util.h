@@ -55,6 +55,11 @@ int gemm_tuner_tiles(int* out, int cap);
 // before it touches the weight arena.
 void lora_merge_require(const void* w, int n, int k, int ldw, const void* up, const void* down, int rank, float scale, int conv_cin,
                         int geglu);
+// ... and those of sdod_loha_merge_f16 / sdod_lokr_merge_f16 (lycoris.hip), for Graph::set_networks
+void loha_merge_require(const void* w, int n, int k, int ldw, const void* w1a, const void* w1b, const void* w2a, const void* w2b, int rank,
+                        float scale, int conv_cin, int geglu);
+void lokr_merge_require(const void* w, int n, int k, int ldw, const void* w1, int a, int b, const void* w2, float scale, int conv_cin,
+                        int geglu);
 
 } // namespace sdod
 

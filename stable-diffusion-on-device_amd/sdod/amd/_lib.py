@@ -153,6 +153,8 @@ def _declare(lib):
         'sdod_ln_fold_f16': (c_int, [P, c_int, c_int, c_int, P, P, P, P, P, P]),
         'sdod_compose_linear_f16': (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P]),
         'sdod_lora_merge_f16': (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_float, c_int, c_int, P]),
+        'sdod_loha_merge_f16': (c_int, [P, c_int, c_int, c_int, P, P, P, P, c_int, c_float, c_int, c_int, P]),
+        'sdod_lokr_merge_f16': (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, c_float, c_int, c_int, P]),
         'sdod_attention_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P]),
         'sdod_attention_head_dim_ok': (c_int, [c_int]),
         'sdod_xattn_fold_ok': (c_int, [c_int, c_int, c_int, c_int]),
@@ -233,6 +235,7 @@ HIP_SYMBOLS = [
     'sdod_attention_head_dim_ok', 'sdod_xattn_fold_ok',
     'sdod_k_step_windows',
     'sdod_freeu_f16',
+    'sdod_loha_merge_f16', 'sdod_lokr_merge_f16',
 ]
 
 

@@ -109,6 +109,15 @@ class LoraEntry(ctypes.Structure):
                 ('rank', ctypes.c_int), ('scale', ctypes.c_float)]
 
 
+class NetworkEntry(ctypes.Structure):
+    """mirror of `sdod_network_entry`"""
+    _fields_ = [('name', ctypes.c_char_p), ('kind', ctypes.c_int), ('dtype', ctypes.c_int), ('f', ctypes.c_void_p * 4),
+                ('rank', ctypes.c_int), ('a', ctypes.c_int), ('b', ctypes.c_int), ('scale', ctypes.c_float)]
+
+
+NET_LORA, NET_LOHA, NET_LOKR = 0, 1, 2
+
+
 ENGINE_SYMBOLS = [
     'sdod_model_config_sd14', 'sdod_model_config_sd21', 'sdod_graph_create', 'sdod_graph_create_ex', 'sdod_graph_create_wrap', 'sdod_graph_destroy', 'sdod_graph_num_params', 'sdod_graph_param_info',
     'sdod_graph_set_param', 'sdod_graph_param_device', 'sdod_graph_load_file', 'sdod_graph_finalize', 'sdod_graph_io', 'sdod_graph_execute', 'sdod_graph_check',
@@ -117,6 +126,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_create_control', 'sdod_graph_bind_output', 'sdod_graph_create_regions',
     'sdod_graph_create_ip', 'sdod_graph_create_vision',
     'sdod_graph_enable_freeu', 'sdod_graph_freeu_input',
+    'sdod_graph_set_networks',
 ]
 
 
@@ -157,6 +167,7 @@ def _engine():
         lib.sdod_graph_keep_base.argtypes = [P]
         lib.sdod_graph_base_bytes.argtypes = [P, ctypes.POINTER(ctypes.c_size_t)]
         lib.sdod_graph_set_loras.argtypes = [P, ctypes.POINTER(LoraEntry), I, P]
+        lib.sdod_graph_set_networks.argtypes = [P, ctypes.POINTER(NetworkEntry), I, P]
         lib.sdod_graph_enable_freeu.argtypes = [P]
         lib.sdod_graph_freeu_input.argtypes = [P, ctypes.POINTER(I)]
         lib._sdod_engine_typed = True
@@ -346,6 +357,56 @@ class Graph:
         with self._on_device():
             check(self._lib.sdod_graph_set_loras(self._h, arr, len(entries),
                                                  ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if torch.cuda.is_available() else None)))
+
+    def set_networks(self, entries):
+        """set_loras for every adapter family (sdod/amd/lycoris.py).  An entry is one of
+            (param_name, up, down, scale)                          plain LoRA, as set_loras takes it
+            ('loha', param_name, w1a, w1b, w2a, w2b, scale)        W + scale * (w1a @ w1b) * (w2a @ w2b);  w*a [out, rank], w*b [rank, in]
+                                                                   or [rank, cin, kh, kw]
+            ('lokr', param_name, w1, w2, scale)                    W + scale * kron(w1, w2);  w1 [a, b], w2 [out / a, in / b] or
+                                                                   [out / a, cin / b, kh, kw]; a = b = 1 adds the full delta w2
+        with torch CPU tensors in canonical layout.  Entries naming the same weight accumulate in the order given; [] restores the base
+        weights.  ValueError for factors that do not give the weight's shape, before the library is called."""
+        shapes = None
+        keep, arr = [], (NetworkEntry * max(len(entries), 1))()
+        for i, e in enumerate(entries):
+            if len(e) == 4:
+                kind, name, factors, scale = NET_LORA, e[0], e[1:3], e[3]
+            elif len(e) == 7 and e[0] == 'loha':
+                kind, name, factors, scale = NET_LOHA, e[1], e[2:6], e[6]
+            elif len(e) == 5 and e[0] == 'lokr':
+                kind, name, factors, scale = NET_LOKR, e[1], e[2:4], e[4]
+            else:
+                raise ValueError("an entry is (name, up, down, scale), ('loha', name, w1a, w1b, w2a, w2b, scale) or ('lokr', name, w1, w2, scale)")
+            if not all(torch.is_tensor(t) and t.dim() >= 2 for t in factors):
+                raise ValueError(f'{name}: the factors must be tensors of at least two dimensions')
+            if shapes is None:
+                shapes = dict(self.param_table())
+            dt = torch.float16 if all(t.dtype == torch.float16 for t in factors) else torch.float32
+            factors = [t.detach().cpu().to(dt).contiguous() for t in factors]
+            rank = a = b = 0
+            shape = shapes.get(name, ())
+            known = len(shape) >= 2                      # (an unknown name or a vector is the library's to refuse)
+            fan_in = int(np.prod(shape[1:])) if known else 0
+            what = ' x '.join(str(tuple(t.shape)) for t in factors)
+            if kind == NET_LOKR:
+                w1, w2 = factors
+                a, b = (int(v) for v in w1.shape[:2])
+                if w1.dim() != 2 or a < 1 or b < 1:
+                    raise ValueError(f'{name}: w1 must be a non-empty [a, b] matrix, got {tuple(w1.shape)}')
+                if known and (shape[0] % a or shape[1] % b or w2.shape[0] * a != shape[0] or w2.numel() * a * b != shape[0] * fan_in):
+                    raise ValueError(f'{name}: the Kronecker factors {what} do not give a {tuple(shape)} weight')
+            else:
+                rank = int(factors[1].shape[0])
+                for up, down in zip(factors[0::2], factors[1::2]):
+                    if down.shape[0] != rank or (known and (up.numel() != shape[0] * rank or up.shape[0] != shape[0] or down.numel() != rank * fan_in)):
+                        raise ValueError(f'{name}: factors {what} do not give a {tuple(shape)} weight')
+            keep += factors
+            ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in factors])
+            arr[i] = NetworkEntry(name.encode(), kind, 1 if dt == torch.float32 else 0, ptrs, rank, a, b, float(scale))
+        with self._on_device():
+            check(self._lib.sdod_graph_set_networks(self._h, arr, len(entries),
+                                                    ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if torch.cuda.is_available() else None)))
 
     def bind_output(self, index, tensor):
         """before finalize(): output `index` is written straight into `tensor` (device memory of the same size that outlives the

@@ -21,8 +21,10 @@ W + strength * alpha / rank * up @ down.  `<module>` is the diffusers / HF modul
 
 Refused, with the reason in the error: `time_emb_proj` (the time conditioning reaches the UNet graph already projected, by the TEMB
 graph), `conv_in` / `conv_out` (the input convolution is packed for its own kernel, the output convolution is not a usual target),
-`time_embedding`, the OpenCLIP text tower of sd21, and every non-LoRA variant (LoHa `hada_*`, LoKr `lokr_*`, DoRA `dora_scale`,
-`lora_mid`)."""
+`time_embedding`, the OpenCLIP text tower of sd21, and -- by THIS reader, which is the plain-LoRA one -- every module that holds
+tensors of another family (LoHa `hada_*`, LoKr `lokr_*`, a Tucker core `lora_mid`, a full `diff`, DoRA `dora_scale`).  lycoris.py reads
+those files, with the same module keys, and is what Txt2Img.set_loras uses; only `dora_scale`, `diff_b` and the norm-layer tensors stay
+refused there."""
 import math
 import re
 

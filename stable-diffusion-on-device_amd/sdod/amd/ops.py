@@ -328,6 +328,49 @@ def lora_merge(w, up, down, scale, *, ld=None, conv_cin=None, geglu=False):
     return w
 
 
+def _packed_ld(w, k, ld):
+    if ld is not None:
+        return int(ld)
+    return w.stride(0) if w.dim() == 2 and w.shape[0] > 1 else k
+
+
+def loha_merge(w, w1a, w1b, w2a, w2b, scale, *, ld=None, conv_cin=None, geglu=False):
+    """w += scale * (w1a @ w1b) * (w2a @ w2b) (Hadamard product) in place on a PACKED fp16 weight matrix (sdod_loha_merge_f16): w, ld,
+    conv_cin and geglu as in lora_merge; w1a, w2a [n, rank] and w1b, w2b [rank, k] ([rank, cin, 3, 3]) are fp16 device tensors in
+    canonical order.  Returns w."""
+    lib = _lib.hip()
+    for t, nme in ((w, 'w'), (w1a, 'w1a'), (w1b, 'w1b'), (w2a, 'w2a'), (w2b, 'w2b')):
+        if not t.is_cuda or t.dtype != torch.float16:
+            raise ValueError(f'{nme} must be an fp16 tensor on the GPU')
+        if t is not w:
+            _req(t, torch.float16, nme)
+    if w1a.dim() != 2 or w2a.shape != w1a.shape or w2b.shape != w1b.shape or w.stride(-1) != 1:
+        raise ValueError('w1a and w2a must be [n, rank], w1b and w2b of one shape, and the columns of w contiguous')
+    n, rank = w1a.shape
+    k = w1b.numel() // rank if rank else (w1b.shape[-1] if w1b.dim() > 1 else 0)
+    check(lib.sdod_loha_merge_f16(_p(w), n, k, _packed_ld(w, k, ld), _p(w1a), _p(w1b), _p(w2a), _p(w2b), rank, float(scale),
+                                  int(conv_cin or 0), 1 if geglu else 0, _stream()))
+    return w
+
+
+def lokr_merge(w, w1, w2, scale, *, ld=None, conv_cin=None, geglu=False):
+    """w += scale * kron(w1, w2) in place on a PACKED fp16 weight matrix (sdod_lokr_merge_f16): w, ld, conv_cin and geglu as in
+    lora_merge; w1 [a, b] and w2 [c, d] ([c, d, 3, 3] with conv_cin = b * d) are fp16 device tensors in canonical order; the matrix
+    has a * c rows.  Returns w."""
+    lib = _lib.hip()
+    for t, nme in ((w, 'w'), (w1, 'w1'), (w2, 'w2')):
+        if not t.is_cuda or t.dtype != torch.float16:
+            raise ValueError(f'{nme} must be an fp16 tensor on the GPU')
+    _req(w1, torch.float16, 'w1'); _req(w2, torch.float16, 'w2')
+    if w1.dim() != 2 or w2.dim() < 2 or w.stride(-1) != 1:
+        raise ValueError('w1 must be [a, b], w2 [c, d] or [c, d, 3, 3], and the columns of w contiguous')
+    a, b = w1.shape
+    n, k = a * w2.shape[0], b * (w2.numel() // w2.shape[0])
+    check(lib.sdod_lokr_merge_f16(_p(w), n, k, _packed_ld(w, k, ld), _p(w1), a, b, _p(w2), float(scale), int(conv_cin or 0),
+                                  1 if geglu else 0, _stream()))
+    return w
+
+
 def layer_norm(x, weight, bias, eps=1e-5, out=None):
     lib = _lib.hip()
     _req(x, torch.float16, 'x')

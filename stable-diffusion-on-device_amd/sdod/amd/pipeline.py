@@ -300,8 +300,9 @@ class Txt2Img:
 
     # ------------------------------------------------------------------ LoRA adapters
     def set_loras(self, adapters, strict=True):
-        """adapters: [(path_or_dict, strength)] or [(path_or_dict, strength_unet, strength_text)] -- kohya-style LoRA files
-        (sdod/amd/lora.py: read_lora, map_key).  All of them are applied together, summed, to the base weights of the UNet and the text
+        """adapters: [(path_or_dict, strength)] or [(path_or_dict, strength_unet, strength_text)] -- kohya-style LoRA files and
+        LyCORIS files (LoHa, LoKr, Tucker-cored and full-diff modules, also mixed in one file: sdod/amd/lycoris.py: read_network; module
+        names: lora.map_key).  All of them are applied together, summed, to the base weights of the UNet and the text
         encoder, in place on the device: every address, the launch lists and every captured graph (generate_graphed's trajectories
         included: their first evaluation re-derives the cross-attention operands inside the capture) stay valid.  [] restores the base
         model.  A context encoded BEFORE a text-encoder adapter was set or cleared is stale: encode the prompt again.
@@ -309,7 +310,7 @@ class Txt2Img:
         without loras=True; ValueError, before any device work, for a bad strength, uint8 weights, or text-encoder modules on a
         pipeline without a text encoder (a cfg_split rank built with with_text_encoder=False).  With hires_hw the UNet modules are
         applied to both UNets, the text-encoder modules to the base pipeline's alone (the hires pipeline has no text encoder)."""
-        from . import lora as L
+        from . import lycoris as L
         if not self._loras:
             raise RuntimeError('this pipeline was built without loras=True: merge on the host (lora.merged_state_dict) and build a new one')
         parsed = []
@@ -324,19 +325,20 @@ class Txt2Img:
         if self.cfg.weight_quant != 0:
             raise ValueError('LoRA adapters need fp16 weights: this pipeline keeps uint8 codes (weight_quant); merge on the host instead')
         lists, skipped = {'unet': [], 'text': []}, []
+        shapes = {'unet': dict(self.unet.param_table()), 'text': dict(self.text.param_table()) if self.text is not None else {}} if parsed else None
         for src, s_unet, s_text in parsed:
-            ent, skip = L.entries_for(src, self.model, s_unet, s_text, strict=strict)
+            ent, skip = L.entries_for(src, self.model, s_unet, s_text, strict=strict, shapes=shapes)
             lists['unet'] += ent['unet']
             lists['text'] += ent['text']
             skipped += skip
         if lists['text'] and self.text is None:
             raise ValueError('the adapters hold text-encoder modules and this pipeline has no text encoder')
-        self.unet.set_loras(lists['unet'])
+        self.unet.set_networks(lists['unet'])
         if self.hires is not None:       # the second pass runs the same model: its UNet takes the same adapters
-            self.hires.unet.set_loras(lists['unet'])
+            self.hires.unet.set_networks(lists['unet'])
             self.hires._ctx_fresh = True
         if self.text is not None:
-            self.text.set_loras(lists['text'])
+            self.text.set_networks(lists['text'])
         self._ctx_fresh = True
         return skipped
 

@@ -12,6 +12,11 @@ device synchronise:
 Writes the result as JSON to --out (profiles/lora_switch.json) and prints it.
 
     python tools/lora_bench.py --out profiles/lora_switch.json
+
+--family loha | lokr measures the same for the LyCORIS families through Graph.set_networks (sdod/amd/lycoris.py): LoHa at the given
+ranks, LoKr at the --splits of w1 (a x b; 1x1 is a full delta), keyed 'AxB' where the LoRA result has the rank; the host route is then
+lycoris.merged_state_dict.  --rebuild-repeats 0 leaves the host route out.  profiles/lycoris_switch.json holds these next to the
+plain-LoRA figures of the commit before and after the families were added.
 """
 import argparse
 import json
@@ -25,7 +30,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, 'stable-diffusion-on-device_amd')]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from sdod.amd import engine as E, lora as L, weights as Wt  # noqa: E402
+from sdod.amd import engine as E, lora as L, lycoris as Ly, weights as Wt  # noqa: E402
 
 SKIP = ('input_blocks.0.0.weight', 'out.2.weight')
 
@@ -38,6 +43,31 @@ def entries(sd, names, rank, seed):
         up = torch.randn(w.shape[0], rank, generator=gen).half()
         down = (torch.randn(rank, *w.shape[1:], generator=gen) * (float(w.std()) / rank ** 0.5)).half()
         out.append((n, up.reshape(w.shape[0], rank, 1, 1) if w.dim() == 4 else up, down, 0.05))
+    return out
+
+
+def loha_entries(sd, names, rank, seed):
+    """each low-rank product has the spread sqrt(std(W)): their Hadamard product has the weight's own"""
+    gen = torch.Generator().manual_seed(seed)
+    out = []
+    for n in names:
+        w = sd[n]
+        f = []
+        for _ in range(2):
+            f.append(torch.randn(w.shape[0], rank, generator=gen).half())
+            f.append((torch.randn(rank, *w.shape[1:], generator=gen) * (float(w.std()) ** 0.5 / rank ** 0.5)).half())
+        out.append(('loha', n, *f, 0.05))
+    return out
+
+
+def lokr_entries(sd, names, a, b, seed):
+    gen = torch.Generator().manual_seed(seed)
+    out = []
+    for n in names:
+        w = sd[n]
+        w1 = torch.randn(a, b, generator=gen).half()
+        w2 = (torch.randn(w.shape[0] // a, w.shape[1] // b, *w.shape[2:], generator=gen) * float(w.std())).half()
+        out.append(('lokr', n, w1, w2, 0.05))
     return out
 
 
@@ -77,6 +107,8 @@ def main():
     ap.add_argument('--rebuild-repeats', type=int, default=3)
     ap.add_argument('--windows', type=int, default=5)
     ap.add_argument('--reps', type=int, default=50)
+    ap.add_argument('--family', choices=('lora', 'loha', 'lokr'), default='lora')
+    ap.add_argument('--splits', nargs='+', default=['4x8', '16x64', '1x1'], metavar='AxB', help='--family lokr: the shapes of w1')
     ap.add_argument('--out', metavar='FILE')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'this benchmark needs a GPU'
@@ -98,6 +130,10 @@ def main():
     res = dict(latent=a.hw, batch=2, adapted_weights=len(names), unet_weight_bytes=g.stats()['weight_bytes'], unet_base_bytes=g.base_bytes(),
                launches=g.stats()['launches'], tune=g.tune_source(), repeats=a.repeats, rebuild_repeats=a.rebuild_repeats,
                step_windows=a.windows, step_replays_per_window=a.reps, ranks={})
+    if a.family != 'lora':
+        res['family'] = a.family
+    set_entries = g.set_loras if a.family == 'lora' else g.set_networks
+    merged = L.merged_state_dict if a.family == 'lora' else Ly.merged_state_dict
     tcfg = E.sd14_config()
     tg = E.TextEncoder(tcfg, 2)
     tg.load_state_dict(Wt.synthetic_state_dict(tg.param_table(), seed=1236))
@@ -113,10 +149,14 @@ def main():
     del scratch, src
     g.set_loras([])                                   # warm-up of the fold / compose launches' second use
     res['clear_ms'] = round(timed(lambda: g.set_loras([]), a.repeats)[0], 3)
-    for rank in a.ranks:
-        ent = entries(sd, names, rank, seed=rank)
-        g.set_loras(ent)                              # warm-up: the merge kernel's first launch
-        total, runs = timed(lambda: g.set_loras(ent), a.repeats)
+    for rank in (a.splits if a.family == 'lokr' else a.ranks):
+        if a.family == 'lokr':
+            ka, kb = (int(v) for v in rank.split('x'))
+            ent = lokr_entries(sd, names, ka, kb, seed=ka * 1000 + kb)
+        else:
+            ent = (entries if a.family == 'lora' else loha_entries)(sd, names, rank, seed=rank)
+        set_entries(ent)                              # warm-up: the merge kernel's first launch
+        total, runs = timed(lambda: set_entries(ent), a.repeats)
         with_lora = step_ms(g, a.windows, a.reps)
         moved = float((g.eps.float() - base_eps.float()).norm() / base_eps.float().norm())
         g.set_loras([])
@@ -125,21 +165,23 @@ def main():
 
         def rebuild():
             g2 = E.UNet(cfg, 2)
-            g2.load_state_dict(L.merged_state_dict(sd, ent))
+            g2.load_state_dict(merged(sd, ent))
             g2.finalize()
             return g2
 
-        t_merge = time.perf_counter()
-        L.merged_state_dict(sd, ent)
-        t_merge = (time.perf_counter() - t_merge) * 1e3
-        reb, reb_runs = timed(rebuild, a.rebuild_repeats)
-        flop = sum(2.0 * sd[n].numel() * rank for n in names)
+        flop = sum(2.0 * sd[n].numel() * (1 if a.family == 'lokr' else rank * (2 if a.family == 'loha' else 1)) for n in names)
         res['ranks'][str(rank)] = dict(
             set_loras_ms=round(total, 3), set_loras_runs_ms=[round(v, 3) for v in runs], merges_ms=round(total - res['clear_ms'], 3),
             refold_ms=round(res['clear_ms'] - res['restore_ms'], 3), merge_gflop=round(flop / 1e9, 1),
-            rebuild_ms=round(reb, 1), rebuild_runs_ms=[round(v, 1) for v in reb_runs], host_merge_ms=round(t_merge, 1),
-            rebuild_over_set_loras=round(reb / total, 1), unet_step_ms_with_lora=with_lora, unet_step_ms_after_clear=after,
+            unet_step_ms_with_lora=with_lora, unet_step_ms_after_clear=after,
             output_moved_rel_l2=round(moved, 4), eps_after_clear_bit_equal=same)
+        if a.rebuild_repeats > 0:
+            t_merge = time.perf_counter()
+            merged(sd, ent)
+            t_merge = (time.perf_counter() - t_merge) * 1e3
+            reb, reb_runs = timed(rebuild, a.rebuild_repeats)
+            res['ranks'][str(rank)].update(rebuild_ms=round(reb, 1), rebuild_runs_ms=[round(v, 1) for v in reb_runs], host_merge_ms=round(t_merge, 1),
+                                           rebuild_over_set_loras=round(reb / total, 1))
         print(f'rank {rank}:', json.dumps(res['ranks'][str(rank)]), flush=True)
     g.check()
     text = json.dumps(res, indent=1)
