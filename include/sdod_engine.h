@@ -197,6 +197,18 @@ typedef struct sdod_control_config {
     int control_temb;   /* TEMB graph: 1 = the time conditioning of a CONTROLNET graph ([B][30 MC]); 0 = the UNet's */
 } sdod_control_config;
 SDOD_API int sdod_graph_create_control(void** graph, int kind, const sdod_model_config* cfg, const sdod_control_config* control, int batch);
+/* Latent Consistency Models: the guidance-scale embedding of a full LCM checkpoint, TEMB graph only.  With
+ * time_cond_proj_dim = D > 0 the graph gets a second input, in1 = w fp32 [B] (the guidance scale of each row), and the parameter
+ * `time_embed.cond_proj.weight` [model_channels][D] (no bias; diffusers: time_embedding.cond_proj.weight), and computes
+ *   feat = timestep_features(t) + guidance_features(w) @ cond_proj^T      [sdod_guidance_features_f16, then one GEMM whose residual
+ *                                                                          epilogue adds the timestep features]
+ * in front of the time MLP; the rest of the graph is unchanged, and a zero cond_proj gives the plain graph's output bit for bit.
+ * D must be a positive multiple of 16 (at most 4096; with uint8 weights a multiple of 64); on any other kind, or with
+ * sdod_control_config.control_temb, it is refused.  lcm == NULL or D == 0 builds exactly what sdod_graph_create builds. */
+typedef struct sdod_lcm_config {
+    int time_cond_proj_dim; /* width of the guidance-scale features: 256 for LCM_Dreamshaper_v7; 0 = none */
+} sdod_lcm_config;
+SDOD_API int sdod_graph_create_lcm(void** graph, int kind, const sdod_model_config* cfg, const sdod_lcm_config* lcm, int batch);
 /* Regional prompts, UNET graph only.  cfg->context_len must be 77 * regions: in2 holds, per image, the encodings of
  * `regions` prompts one behind the other.  Behind every other input the graph gets four inputs region_w[level], fp32
  * [H / ds * W / ds][regions] for ds = 1, 2, 4, 8 (what sdod_region_weights_f32 writes), shared by all images of the batch and

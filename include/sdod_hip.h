@@ -578,6 +578,12 @@ SDOD_API int sdod_embedding_f16(const int32_t* ids, const void* table, const voi
 SDOD_API int sdod_context_assemble_f16(const void* enc, const float* w, void* out, int P, int K, int T, int D, void* stream);
 /* context.cpp:257-274: out[i][j]=cos(t_i*f_j), out[i][half+j]=sin(t_i*f_j), f_j=exp(-ln(1e4)*j/half); fp16 out */
 SDOD_API int sdod_timestep_features_f16(const float* t, void* y, int n, int dim, void* stream);
+/* The guidance-scale embedding of a full LCM checkpoint (diffusers get_guidance_scale_embedding; host form: sdod/amd/samplers.py,
+ * guidance_embedding): v = (w_i - 1) * 1000, f_j = exp(-ln(1e4) * j / (half - 1)), out[i][j] = sin(v * f_j), out[i][half + j] =
+ * cos(v * f_j) with half = dim / 2 -- sine first and the divisor half - 1, both unlike sdod_timestep_features_f16.  w fp32 [n], out
+ * fp16 [n][dim].  The argument reaches 14 000 rad at w = 15 and goes through the range-reduced sinf / cosf; f_j is rounded once
+ * from fp64, v and the product are fp32.  dim must be even and at least 4. */
+SDOD_API int sdod_guidance_features_f16(const float* w, void* y, int n, int dim, void* stream);
 
 /* Inputs of one guided UNet evaluation in one launch (host loop: context.cpp:348-349): x (fp32, lat_count values = n
  * images) -> x_dst written `reps` times back to back; temb_row (fp16, temb_width) -> temb_dst, `temb_reps` rows. */
@@ -700,6 +706,35 @@ typedef struct sdod_k_step_args {
     float guidance, d0, d1, a, b, cprev, u, stage_scale;
 } sdod_k_step_args;
 SDOD_API int sdod_k_step(const sdod_k_step_args* a, void* stream);
+
+/* One step of a Latent Consistency Model (Luo et al. 2023; host tables: sdod/amd/samplers.py, LcmSchedule.coef; host loop:
+ * sdod/amd/pipeline.py, sample_lcm) behind a UNet evaluation in one launch.  In the unscaled latent x:
+ *   e   = CFG(eps) when guided != 0                             [sdod_cfg_combine]
+ *         float(eps[img]) when guided == 0: one row per image   [sdod_nhwc_f16_to_nchw_f32; guidance, mode, uncond_first are ignored]
+ *   den = d0 * x + d1 * e                                       [sdod_lincomb4_f32([x, e], [d0, d1], 1): the x0 prediction]
+ *   x'  = a * x + b * den (+ u * nu)                            [sdod_lincomb4_f32, left to right; the x term is left out when a == 0, the
+ *                                                                nu term when u == 0]
+ *   den_out <- den (when den_out is given);  x <- x'
+ * then the next evaluation's inputs: x_stage[r] = x' UNSCALED (the model sees x itself) and temb_row into temb_dst[temb_reps][..] as
+ * sdod_stage_unet_inputs does.  Every product and sum is rounded on its own in fp32 (no FMA contraction): the bits of those separate
+ * launches.  nu: `noise` fp32 [n][c][hw], or when NULL drawn in the kernel, image i's values exactly those of sdod_randn_f32(count =
+ * c * hw, seed, stream_id = ((3 + noise_level) << 32) | (image_index0 + i)); with u == 0 no noise is drawn or read.
+ * Refused with INVALID_ARGUMENT before any launch: a NULL eps_nhwc or x; n, c or hw below 1; c * hw not a multiple of 4; x, den_out,
+ * noise or x_stage not 16-byte aligned; a non-finite scalar; guided with a mode other than 0 or 1; temb_row without temb_dst; x_stage
+ * without stage_reps.  den_out, noise, x_stage, temb_row may be NULL. */
+typedef struct sdod_lcm_step_args {
+    const void* eps_nhwc;   /* fp16 [guided ? 2n : n][hw][c] */
+    float* x;               /* fp32 [n][c][hw], updated in place */
+    float* den_out;         /* fp32 [n][c][hw] or NULL: this step's x0 prediction */
+    const float* noise;     /* fp32 [n][c][hw] or NULL (drawn in the kernel); touched only when u != 0 */
+    float* x_stage;         /* fp32 [stage_reps][n][c][hw] or NULL */
+    const void* temb_row;   /* fp16 [temb_width] or NULL */
+    void* temb_dst;         /* fp16 [temb_reps][temb_width] */
+    uint64_t seed, image_index0;
+    int n, c, hw, guided, uncond_first, mode, noise_level, stage_reps, temb_width, temb_reps;
+    float guidance, d0, d1, a, b, u;
+} sdod_lcm_step_args;
+SDOD_API int sdod_lcm_step(const sdod_lcm_step_args* a, void* stream);
 
 /* sdod_k_step on a MultiDiffusion canvas (Bar-Tal et al. 2023; host loop: sdod/amd/pipeline.py, sample_panorama; host tables:
  * sdod/amd/panorama.py): the UNet ran on ny * nx overlapping windows [wh][ww] of ONE canvas latent x [c][H][W]; window w = iy * nx + ix

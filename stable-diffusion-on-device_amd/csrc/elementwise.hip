@@ -807,6 +807,31 @@ __global__ void timestep_features_kernel(const float* t, f16* y, int n, int dim)
     }
 }
 
+// the guidance-scale embedding of a full LCM checkpoint (include/sdod_hip.h: sdod_guidance_features_f16).  arg = (w - 1) * 1000 * f_j
+// reaches 14 000 rad at w = 15: it goes through sinf / cosf, whose range reduction (Payne-Hanek above the Cody-Waite range) keeps
+// their error at ulps of the RESULT; __sinf / __cosf hand the bare argument to the hardware, which is only valid within +-256
+// revolutions.  f_j is formed in fp64 and rounded once (one exp per thread, once per schedule), so that the error of the argument is
+// the three fp32 roundings of f_j, v and their product.  Rows are ld halves apart (ld >= dim, even); thread (row, j) writes the
+// columns j and half + j, or -- j >= half -- zeros into the two padding columns dim + 2 (j - half) and the next.
+__global__ void guidance_features_kernel(const float* w, f16* y, int n, int dim, int ld) {
+    const int half = dim / 2, per = ld / 2;
+    const size_t total = (size_t)n * per;
+    GRID_STRIDE(i, total) {
+        const int row = (int)(i / per), j = (int)(i - (size_t)row * per);
+        f16* yr = y + (size_t)row * ld;
+        if (j >= half) {
+            yr[dim + 2 * (j - half)] = (f16)0.0f;
+            yr[dim + 2 * (j - half) + 1] = (f16)0.0f;
+            continue;
+        }
+        const float f = (float)exp(-(double)j * 9.210340371976184 / (double)(half - 1)); // ln(10000)
+        const float v = mul_rn(sub_rn(w[row], 1.0f), 1000.0f);
+        const float arg = mul_rn(v, f);
+        yr[j] = (f16)sinf(arg);
+        yr[half + j] = (f16)cosf(arg);
+    }
+}
+
 // fp16 rows, fp32 math; each thread keeps <= NCH chunks of its row in registers (NCH = 4: rows up to 8192 columns, the
 // SD v1 VAE attention at 64x64; NCH = 8: up to 16384, the 96x96 latent of SD v2.1-768)
 template <int NCH>
@@ -1370,6 +1395,46 @@ __global__ void k_step_kernel(const sdod_k_step_args a) {
     }
 }
 
+// One step of a Latent Consistency Model behind a UNet evaluation in ONE launch (include/sdod_hip.h: sdod_lcm_step): e = cfg_kernel's
+// guidance of the pair (guided) or nhwc_to_nchw_kernel's conversion of the image's one row (unguided), den = lincomb4([x, e], [d0, d1], 1)
+// (the x0 prediction), x' = lincomb4([x, den, nu], [a, b, u], 1) with the x term left out when a == 0 and the nu term when u == 0 (as
+// lincomb4_kernel leaves out a NULL term), den_out <- den, x <- x', x_stage <- x' unscaled and the time row (stage_unet_inputs_kernel).
+// Thread = four consecutive elements of one image = one Philox block of its noise stream (as k_step_kernel); x, den_out, noise and
+// x_stage move as 16-byte lanes.
+__global__ void lcm_step_kernel(const sdod_lcm_step_args a) {
+    const size_t per = (size_t)a.c * a.hw, nblk = per / 4; // per % 4 == 0, pointers 16-byte aligned (checked by the host)
+    const size_t lat = (size_t)a.n * per, nlat = (size_t)a.n * nblk, nt = temb_work(a);
+    const f16* eps = (const f16*)a.eps_nhwc;
+    GRID_STRIDE(t, nlat + nt) {
+        if (t >= nlat) {
+            broadcast_row((f16*)a.temb_dst, (const f16*)a.temb_row, a.temb_width, t - nlat);
+            continue;
+        }
+        const int img = (int)(t / nblk);
+        const size_t j = t - (size_t)img * nblk;
+        const size_t o = (size_t)img * per + 4 * j;
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + o);
+        f32x4 out, den, nu = f32x4{0.f, 0.f, 0.f, 0.f};
+        const bool has_nu = a.u != 0.0f;
+        if (has_nu) nu = noise4(a.noise, o, j, a.seed, ((uint64_t)(3 + a.noise_level) << 32) | (a.image_index0 + img));
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const size_t e_i = 4 * j + q;
+            const size_t ch = e_i / a.hw, pix = e_i - ch * a.hw;
+            const float e = a.guided ? guided_eps(eps, img, ch, pix, a.n, a.c, a.hw, a.uncond_first, a.guidance, a.mode)
+                                     : (float)eps[((size_t)img * a.hw + pix) * a.c + ch];
+            const float d = lincomb4v(a.d0, xv[q], a.d1, e, false, 0.f, 0.f, false, 0.f, 0.f, 1.0f);
+            den[q] = d;
+            if (a.a != 0.0f) out[q] = lincomb4v(a.a, xv[q], a.b, d, has_nu, a.u, nu[q], false, 0.f, 0.f, 1.0f);
+            else if (has_nu) out[q] = lincomb4v(a.b, d, a.u, nu[q], false, 0.f, 0.f, false, 0.f, 0.f, 1.0f); // lincomb4([den, nu], [b, u], 1)
+            else out[q] = div_rn(mul_rn(a.b, d), 1.0f);                                                           // lincomb4([den], [b], 1)
+        }
+        if (a.den_out) *reinterpret_cast<f32x4*>(a.den_out + o) = den;
+        *reinterpret_cast<f32x4*>(a.x + o) = out;
+        stage_latent(a.x_stage, a.stage_reps, lat, o, out);
+    }
+}
+
 // the windows of a MultiDiffusion canvas that cover the four columns x0 .. x0 + 3 of row y, in ascending w = iy * nx + ix; f(w, p): p =
 // the window pixel of column x0.  W, ww and every origin are multiples of 4 (checked by the host), so the four columns share their
 // windows and lie side by side in each; with wrap_x a window's columns run modulo W and ww <= W, so it holds a column at most once.
@@ -1855,6 +1920,20 @@ extern "C" int sdod_timestep_features_f16(const float* t, void* y, int n, int di
     SDOD_CATCH
 }
 
+void sdod::guidance_features_ld(const float* w, void* y, int n, int dim, int ld, hipStream_t stream) {
+    SDOD_REQUIRE(w && y && n > 0, "bad argument");
+    SDOD_REQUIRE(dim >= 4 && dim % 2 == 0, "dim must be even and at least 4 (the frequencies' divisor is dim / 2 - 1)");
+    SDOD_REQUIRE(ld >= dim && ld % 2 == 0, "ld must be even and at least dim");
+    LAUNCH(guidance_features_kernel, (size_t)n * (ld / 2), stream, w, (f16*)y, n, dim, ld);
+}
+
+extern "C" int sdod_guidance_features_f16(const float* w, void* y, int n, int dim, void* stream) {
+    SDOD_TRY
+    sdod::guidance_features_ld(w, y, n, dim, dim, (hipStream_t)stream);
+    return 0;
+    SDOD_CATCH
+}
+
 extern "C" int sdod_softmax_rows_f16(const void* x, void* y, int m, int n, void* stream) {
     SDOD_TRY
     SDOD_REQUIRE(x && y && m > 0 && n > 0 && n % 8 == 0 && n <= 16384, "softmax rows need N % 8 == 0 and N <= 16384");
@@ -1930,6 +2009,22 @@ extern "C" int sdod_k_step(const sdod_k_step_args* a, void* stream) {
     SDOD_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->den_prev | (uintptr_t)a->noise | (uintptr_t)a->x_stage) & 15) == 0 &&
                      ((uintptr_t)a->eps_nhwc & 1) == 0, "misaligned pointer (x, den_prev, noise, x_stage: 16 bytes)");
     LAUNCH(k_step_kernel, work, stream, *a);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_lcm_step(const sdod_lcm_step_args* a, void* stream) {
+    SDOD_TRY
+    SDOD_REQUIRE(a && a->eps_nhwc && a->x && a->n > 0 && a->c > 0 && a->hw > 0, "bad argument");
+    SDOD_REQUIRE(!a->guided || a->mode == 0 || a->mode == 1, "mode must be 0 or 1");
+    SDOD_REQUIRE(((size_t)a->c * a->hw) % 4 == 0, "c * hw must be a multiple of 4");
+    SDOD_REQUIRE(std::isfinite(a->guidance) && std::isfinite(a->d0) && std::isfinite(a->d1) && std::isfinite(a->a) && std::isfinite(a->b) &&
+                     std::isfinite(a->u), "non-finite scalar");
+    SDOD_REQUIRE(a->u == 0.0f || a->noise || a->noise_level >= 0, "negative noise level");
+    const size_t work = step_work(a, (size_t)a->n * a->c * a->hw / 4);
+    SDOD_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->den_out | (uintptr_t)a->noise | (uintptr_t)a->x_stage) & 15) == 0 &&
+                     ((uintptr_t)a->eps_nhwc & 1) == 0, "misaligned pointer (x, den_out, noise, x_stage: 16 bytes)");
+    LAUNCH(lcm_step_kernel, work, stream, *a);
     return 0;
     SDOD_CATCH
 }

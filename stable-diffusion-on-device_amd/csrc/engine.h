@@ -73,7 +73,7 @@ class Graph {
 public:
     Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg = sdod_adapter_config{0, 0, 0}, int wrap = 0,
           const sdod_upscaler_config& ucfg = sdod_upscaler_config{0, 0, 0}, const sdod_control_config* ccfg = nullptr, int regions = 0,
-          int ip_tokens = 0, const sdod_vision_config* vcfg = nullptr);
+          int ip_tokens = 0, const sdod_vision_config* vcfg = nullptr, int cond_proj_dim = 0);
     ~Graph();
     Graph(const Graph&) = delete;
 
@@ -114,6 +114,7 @@ private:
     int ip_tokens_ = 0;                  // image prompt of the UNET graph (sdod_graph_create_ip): image tokens per image; 0 = none
     const float* ip_w_[4] = {};          // ... its four weight inputs [pixels][2], level ds = 1, 2, 4, 8 (set by build_unet())
     f16* ip_kv_all_ = nullptr;           // ... and the image tokens' K / V of every transformer, [B * ip_tokens][kv_total_], persistent
+    int cond_proj_dim_ = 0;              // LCM guidance embedding of the TEMB graph (sdod_graph_create_lcm): width of the features; 0 = none
     bool freeu_ = false;                 // FreeU of the UNET graph (enable_freeu()): the decoder sites run sdod_freeu_f16 ...
     int freeu_input_ = -1;               // ... on this input slot, fp32 [SDOD_FREEU_PARAMS], behind every other input
     void freeu_site(const Act& h, const Act& skip, const float* params, int stage);

@@ -38,8 +38,15 @@ static void parallel_for(int64_t n, F&& fn) {
 
 // ------------------------------------------------------------------------------------------ lifecycle
 Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg, int wrap, const sdod_upscaler_config& ucfg,
-             const sdod_control_config* ccfg, int regions, int ip_tokens, const sdod_vision_config* vcfg)
-    : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), regions_(regions), ip_tokens_(ip_tokens), batch_(batch), wrap_(wrap) {
+             const sdod_control_config* ccfg, int regions, int ip_tokens, const sdod_vision_config* vcfg, int cond_proj_dim)
+    : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), regions_(regions), ip_tokens_(ip_tokens), cond_proj_dim_(cond_proj_dim), batch_(batch),
+      wrap_(wrap) {
+    if (cond_proj_dim != 0) {
+        SDOD_REQUIRE(kind == SDOD_GRAPH_TEMB, "time_cond_proj_dim applies to the TEMB graph only");
+        SDOD_REQUIRE(cond_proj_dim > 0 && cond_proj_dim <= 4096 && cond_proj_dim % 16 == 0, "time_cond_proj_dim must be a positive multiple of 16 (at most 4096)");
+        SDOD_REQUIRE(!(ccfg && ccfg->control_temb), "a ControlNet's time conditioning (control_temb) takes no time_cond_proj_dim");
+        SDOD_REQUIRE(cfg.weight_quant == 0 || cond_proj_dim % 64 == 0, "time_cond_proj_dim with uint8 weights must be a multiple of 64");
+    }
     SDOD_REQUIRE(ip_tokens == 0 || ((kind == SDOD_GRAPH_UNET || kind == SDOD_GRAPH_IMAGE_PROJ) && ip_tokens >= 1 && ip_tokens <= 16 && regions == 0),
                  "ip_tokens: the UNET and IMAGE_PROJ graphs only, 1 .. 16, not with regions");
     const bool vision_kind = kind == SDOD_GRAPH_IMAGE_ENCODER || kind == SDOD_GRAPH_IMAGE_PROJ;
@@ -1507,6 +1514,18 @@ extern "C" int sdod_graph_create_control(void** graph, int kind, const sdod_mode
     SDOD_REQUIRE(kind != SDOD_GRAPH_UPSCALER && kind != SDOD_GRAPH_ADAPTER, "this kind has a create function of its own");
     const sdod_control_config none{0, 0};
     *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, control ? control : &none);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_create_lcm(void** graph, int kind, const sdod_model_config* cfg, const sdod_lcm_config* lcm, int batch) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph && cfg, "null argument");
+    *graph = nullptr;
+    SDOD_REQUIRE(kind != SDOD_GRAPH_UPSCALER && kind != SDOD_GRAPH_ADAPTER && kind != SDOD_GRAPH_CONTROLNET && kind != SDOD_GRAPH_CONTROL_HINT &&
+                     kind != SDOD_GRAPH_IMAGE_ENCODER && kind != SDOD_GRAPH_IMAGE_PROJ, "this graph kind has a create function of its own");
+    *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, nullptr, 0, 0, nullptr,
+                       lcm ? lcm->time_cond_proj_dim : 0);
     return 0;
     SDOD_CATCH
 }

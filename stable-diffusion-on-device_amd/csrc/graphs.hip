@@ -767,8 +767,22 @@ void Graph::build_temb() {
         P(rb.first + ".emb_layers.1.weight", {rb.second, EC}, PK_LINEAR, "emb_w");
         P(rb.first + ".emb_layers.1.bias", {rb.second}, PK_VEC, "emb_b");
     }
+    // a full LCM checkpoint's guidance-scale embedding (sdod_graph_create_lcm): in1 = w, and cond_proj [MC][GD] without a bias, its rows
+    // padded to the GEMM's K step where GD is no multiple of it (the padding columns stay zero: allocate_weights clears the arena)
+    const int GD = cond_proj_dim_, GK = (GD + 63) / 64 * 64;
+    const float* w_in = GD ? (const float*)io_alloc(inputs_, (size_t)B * sizeof(float)) : nullptr;
+    const int wc = !GD ? -1 : GK == GD ? P("time_embed.cond_proj.weight", {MC, GD}, PK_LINEAR)
+                                       : Pc("time_embed.cond_proj.weight", {MC, GD}, PK_LINEAR, GK, 0, -1);
     f16* feat = alloc((size_t)B * MC);
+    f16 *gfeat = nullptr, *tfeat = nullptr; // (held to the end like the other intermediates: the GEMM's residual must outlive its launches)
     emit([=](hipStream_t st) { check_rc(sdod_timestep_features_f16(t_in, feat, B, MC, st)); });
+    if (GD) { // feat = timestep_features(t) + guidance_features(w) @ cond_proj^T: the sum rides in the GEMM's residual epilogue
+        gfeat = alloc((size_t)B * GK);
+        emit([=](hipStream_t st) { sdod::guidance_features_ld(w_in, gfeat, B, GD, GK, st); });
+        tfeat = feat;
+        feat = alloc((size_t)B * MC);
+        { GemmOpt o; o.residual = tfeat; linear(gfeat, B, GK, wc, MC, feat, o); }
+    }
     f16* hmid = alloc((size_t)B * EC);
     { GemmOpt o; o.bias = b0; o.act = SDOD_ACT_SILU; linear(feat, B, MC, w0, EC, hmid, o); }
     f16* emb = alloc((size_t)B * EC);
@@ -780,6 +794,7 @@ void Graph::build_temb() {
         linear_raw(emb, B, EC, reinterpret_cast<const f16*>(group_base("emb_w")), EC, total, out, o);
     }
     release(feat); release(hmid); release(emb);
+    if (GD) { release(gfeat); release(tfeat); }
 }
 
 // ------------------------------------------------------------------------------------------------ VAE

@@ -61,6 +61,10 @@ void loha_merge_require(const void* w, int n, int k, int ldw, const void* w1a, c
 void lokr_merge_require(const void* w, int n, int k, int ldw, const void* w1, int a, int b, const void* w2, float scale, int conv_cin,
                         int geglu);
 
+// sdod_guidance_features_f16 (elementwise.hip) into rows `ld` halves apart, columns [dim, ld) written as zeros: the TEMB graph's GEMM
+// operand when dim is no multiple of the GEMM's K step (ld = dim padded to it).  ld >= dim, even.  Throws as the entry point returns.
+void guidance_features_ld(const float* w, void* y, int n, int dim, int ld, hipStream_t stream);
+
 } // namespace sdod
 
 #define SDOD_LAUNCH(kernel, grid, block, smem, stream, ...)                                                          \

@@ -77,6 +77,15 @@ class KStepArgs(ctypes.Structure):
                [(k, ctypes.c_float) for k in ('guidance', 'd0', 'd1', 'a', 'b', 'cprev', 'u', 'stage_scale')]
 
 
+class LcmStepArgs(ctypes.Structure):
+    """mirror of `struct sdod_lcm_step_args` (include/sdod_hip.h)"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ('eps_nhwc', 'x', 'den_out', 'noise', 'x_stage', 'temb_row', 'temb_dst')] + \
+               [('seed', ctypes.c_uint64), ('image_index0', ctypes.c_uint64)] + \
+               [(k, ctypes.c_int) for k in ('n', 'c', 'hw', 'guided', 'uncond_first', 'mode', 'noise_level', 'stage_reps', 'temb_width',
+                                            'temb_reps')] + \
+               [(k, ctypes.c_float) for k in ('guidance', 'd0', 'd1', 'a', 'b', 'u')]
+
+
 PANO_MAX_AXIS = 32      # SDOD_PANO_MAX_AXIS (include/sdod_hip.h)
 
 
@@ -198,6 +207,8 @@ def _declare(lib):
         'sdod_ddim_inpaint_step': (c_int, [ctypes.POINTER(DdimInpaintStepArgs), P]),
         'sdod_k_step': (c_int, [ctypes.POINTER(KStepArgs), P]),
         'sdod_k_step_windows': (c_int, [ctypes.POINTER(KStepWindowsArgs), P]),
+        'sdod_lcm_step': (c_int, [ctypes.POINTER(LcmStepArgs), P]),
+        'sdod_guidance_features_f16': (c_int, [P, P, c_int, c_int, P]),
         'sdod_mask_to_latent_f32': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
         'sdod_image_composite_u8': (c_int, [P, P, P, P, c_int, c_size_t, c_float, c_float, c_int, P]),
         'sdod_nchw_f32_to_nhwc_f16': (c_int, [P, P, c_int, c_int, c_int, c_float, P]),
@@ -236,6 +247,7 @@ HIP_SYMBOLS = [
     'sdod_k_step_windows',
     'sdod_freeu_f16',
     'sdod_loha_merge_f16', 'sdod_lokr_merge_f16',
+    'sdod_lcm_step', 'sdod_guidance_features_f16',
 ]
 
 

@@ -97,13 +97,28 @@ def split_state_dict(sd, tables=None, dtype=torch.float16):
     return out, sorted(k for k in sd if k not in used)
 
 
-def convert(ckpt_path, out_dir, dtype=torch.float16, cfg=None, vae_encoder=False):
+# the one key of a full LCM checkpoint that ldm's naming has no place for: diffusers' name (a UNet already translated to ldm names keeps
+# it, or carries it under ours) -> the TEMB graph's parameter
+LCM_COND_PROJ_KEYS = ('time_embedding.cond_proj.weight', 'model.diffusion_model.time_embedding.cond_proj.weight')
+
+
+def convert(ckpt_path, out_dir, dtype=torch.float16, cfg=None, vae_encoder=False, guidance_embed=False):
     """checkpoint file -> out_dir/{unet,temb,vae_decoder,text_encoder}.sdodw (+ vae_encoder.sdodw with vae_encoder=True);
-    returns the list of files written"""
+    returns the list of files written.  guidance_embed=True: a full LCM checkpoint -- temb.sdodw also gets
+    time_embed.cond_proj.weight [model_channels, 256] (Txt2Img(unguided=True, guidance_embed=True)), read from
+    model.diffusion_model.time_embed.cond_proj.weight or, renamed, from diffusers' time_embedding.cond_proj.weight."""
     tables = parameter_tables(cfg)
     if vae_encoder:
         tables = dict(tables, vae_enc=vae_encoder_table(cfg))
-    parts, _ = split_state_dict(read_checkpoint(ckpt_path), tables, dtype)
+    sd = read_checkpoint(ckpt_path)
+    if guidance_embed:
+        tables = dict(tables, temb=E.Temb(cfg or E.sd14_config(), 1, cond_proj_dim=E.LCM_COND_PROJ_DIM).param_table())
+        ours = GRAPHS['temb'][0] + 'time_embed.cond_proj.weight'
+        for key in LCM_COND_PROJ_KEYS:
+            if ours not in sd and key in sd:
+                sd = dict(sd)
+                sd[ours] = sd[key]
+    parts, _ = split_state_dict(sd, tables, dtype)
     os.makedirs(out_dir, exist_ok=True)
     written = []
     for graph, part in parts.items():
@@ -382,6 +397,9 @@ def main(argv=None):
                                                                 'quant_conv), the img2img path')
     ap.add_argument('--inpaint', action='store_true', help='an inpainting checkpoint (sd-v1-5-inpainting, 512-inpainting-ema): the UNet input '
                                                             'convolution is [320, 9, 3, 3]; implies --vae-encoder (Txt2Img(inpaint_unet=True))')
+    ap.add_argument('--guidance-embed', action='store_true', help='a full LCM checkpoint (LCM_Dreamshaper_v7): temb.sdodw also gets '
+                                                                   'time_embed.cond_proj.weight, renamed from diffusers\' '
+                                                                   'time_embedding.cond_proj.weight (Txt2Img(guidance_embed=True))')
     ap.add_argument('--tokenizer-vocab', help='bpe_simple_vocab_16e6.txt.gz, or a directory with HF vocab.json + merges.txt: '
                                               'also write ctokenizer.txt')
     a = ap.parse_args(argv)
@@ -392,7 +410,8 @@ def main(argv=None):
         cfg = cfg or E.sd14_config()
         cfg.concat_channels = 5
     if a.ckpt:
-        for p in convert(a.ckpt, a.out, torch.float32 if a.fp32 else torch.float16, cfg, vae_encoder=a.vae_encoder or a.inpaint):
+        for p in convert(a.ckpt, a.out, torch.float32 if a.fp32 else torch.float16, cfg, vae_encoder=a.vae_encoder or a.inpaint,
+                         guidance_embed=a.guidance_embed):
             print('wrote', p)
     if a.adapter:
         print('wrote', convert_adapter(a.adapter, a.out, torch.float32 if a.fp32 else torch.float16))

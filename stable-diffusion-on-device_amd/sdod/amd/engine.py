@@ -73,6 +73,15 @@ class IpConfig(ctypes.Structure):
     _fields_ = [('ip_tokens', ctypes.c_int)]
 
 
+LCM_COND_PROJ_DIM = 256     # time_cond_proj_dim of the released full LCM checkpoints (LCM_Dreamshaper_v7): what the converter and
+#                             Txt2Img(guidance_embed=True) build the TEMB graphs with
+
+
+class LcmConfig(ctypes.Structure):
+    """mirror of `struct sdod_lcm_config`"""
+    _fields_ = [('time_cond_proj_dim', ctypes.c_int)]
+
+
 class VisionConfig(ctypes.Structure):
     """mirror of `struct sdod_vision_config`"""
     _fields_ = [(n, ctypes.c_int) for n in ('image_size', 'patch', 'width', 'layers', 'heads', 'mlp_dim', 'proj_dim', 'quick_gelu')]
@@ -127,6 +136,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_create_ip', 'sdod_graph_create_vision',
     'sdod_graph_enable_freeu', 'sdod_graph_freeu_input',
     'sdod_graph_set_networks',
+    'sdod_graph_create_lcm',
 ]
 
 
@@ -146,6 +156,7 @@ def _engine():
         lib.sdod_graph_create_regions.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(RegionConfig), I]
         lib.sdod_graph_create_ip.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(IpConfig), I]
         lib.sdod_graph_create_vision.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(VisionConfig), ctypes.POINTER(IpConfig), I]
+        lib.sdod_graph_create_lcm.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(LcmConfig), I]
         lib.sdod_graph_bind_output.argtypes = [P, I, P, ctypes.c_size_t]
         lib.sdod_graph_destroy.argtypes = [P]
         lib.sdod_graph_num_params.argtypes = [P]
@@ -211,9 +222,10 @@ class Graph:
     Without a GPU only the parameter table can be read (what the checkpoint converter needs); everything that touches
     device memory raises."""
 
-    def __init__(self, kind, cfg, batch, device='cuda:0', wrap=None):
+    def __init__(self, kind, cfg, batch, device='cuda:0', wrap=None, cond_proj_dim=0):
         """wrap: None = the creation entry points of every build before seamless tiling; an int 0..3 goes through
-        sdod_graph_create_wrap (0 builds the plain graph there)"""
+        sdod_graph_create_wrap (0 builds the plain graph there).  cond_proj_dim: a TEMB graph with an LCM checkpoint's guidance-scale
+        embedding goes through sdod_graph_create_lcm; 0 = the entry points as before"""
         self._lib = _engine()
         self._h = ctypes.c_void_p()
         self.kind, self.cfg, self.batch = kind, cfg, batch
@@ -229,8 +241,13 @@ class Graph:
         ip_tokens = int(getattr(cfg, 'ip_tokens', 0)) if kind == UNET else 0
         if ip_tokens and (regions or control or wrap or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_)):
             raise ValueError('a UNet with an image prompt takes no regions, no control inputs, no tiling and no T2I-Adapter configuration')
+        cond_proj_dim = int(cond_proj_dim)
+        if cond_proj_dim and (kind != TEMB or control):
+            raise ValueError("cond_proj_dim applies to the UNet's TEMB graph only, not to a ControlNet's time conditioning (control_temb)")
         with self._on_device():
-            if kind in (IMAGE_ENCODER, IMAGE_PROJ):   # the image side of an image prompt: cfg.vision, and cfg.ip_tokens for the projection
+            if cond_proj_dim:       # the guidance embedding has an entry point of its own; without it nothing changes
+                check(self._lib.sdod_graph_create_lcm(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(LcmConfig(cond_proj_dim)), batch))
+            elif kind in (IMAGE_ENCODER, IMAGE_PROJ):   # the image side of an image prompt: cfg.vision, and cfg.ip_tokens for the projection
                 icfg = IpConfig(int(getattr(cfg, 'ip_tokens', 0)))
                 check(self._lib.sdod_graph_create_vision(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(cfg.vision), ctypes.byref(icfg), batch))
             elif ip_tokens:         # image prompts have an entry point of their own; without them nothing changes
@@ -684,12 +701,17 @@ class Upscaler(Graph):
 
 
 class Temb(Graph):
-    def __init__(self, cfg, batch, device='cuda:0'):
-        super().__init__(TEMB, cfg, batch, device)
+    def __init__(self, cfg, batch, device='cuda:0', cond_proj_dim=0):
+        """cond_proj_dim = D > 0: a full LCM checkpoint's time conditioning -- the graph has the input Temb.w (the guidance scale of each
+        row) and the parameter time_embed.cond_proj.weight [model_channels, D]; 0: the graph as ever"""
+        super().__init__(TEMB, cfg, batch, device, cond_proj_dim=cond_proj_dim)
+        self.cond_proj_dim = int(cond_proj_dim)
 
     def finalize(self):
         super().finalize()
         self.t = self.io_tensor(False, 0, (self.batch,), torch.float32)
+        if self.cond_proj_dim:
+            self.w = self.io_tensor(False, 1, (self.batch,), torch.float32)
         self.width = self._io(True, 0)[1] // (2 * self.batch)
         self.out = self.io_tensor(True, 0, (self.batch, self.width), torch.float16)
         return self

@@ -24,7 +24,13 @@ graph), `conv_in` / `conv_out` (the input convolution is packed for its own kern
 `time_embedding`, the OpenCLIP text tower of sd21, and -- by THIS reader, which is the plain-LoRA one -- every module that holds
 tensors of another family (LoHa `hada_*`, LoKr `lokr_*`, a Tucker core `lora_mid`, a full `diff`, DoRA `dora_scale`).  lycoris.py reads
 those files, with the same module keys, and is what Txt2Img.set_loras uses; only `dora_scale`, `diff_b` and the norm-layer tensors stay
-refused there."""
+refused there.
+
+With time_modules=True (a pipeline built with lora_time_modules=True, whose TEMB graphs keep their base weights) the time conditioning
+is a target too, under a third graph name, 'temb' -- what LCM-LoRA adapts:
+
+    lora_unet_{down_blocks_{i},mid_block,up_blocks_{i}}_resnets_{j}_time_emb_proj   <the ResBlock above>.emb_layers.1
+    lora_unet_time_embedding_linear_1 / _2                                          time_embed.0 / time_embed.2"""
 import math
 import re
 
@@ -123,8 +129,36 @@ def _unet_name(rest):
     return None
 
 
-def map_key(module_key, model='sd14'):
-    """kohya module key -> ('unet' | 'text', graph parameter name).  ValueError, with the reason, for what is not supported."""
+_TIME_MLP = {'time_embedding_linear_1': 'time_embed.0', 'time_embedding_linear_2': 'time_embed.2'}
+
+
+def _time_name(rest):
+    """the TEMB graph's parameter (without .weight) of a module of the time conditioning -- a ResBlock's time_emb_proj, which is
+    `<block>.emb_layers.1` (a row slice of the graph's one fused projection), or the time MLP's two Linears -- or None"""
+    if rest in _TIME_MLP:
+        return _TIME_MLP[rest]
+    m = re.fullmatch(r'(down_blocks_(\d+)|mid_block|up_blocks_(\d+))_resnets_(\d+)_time_emb_proj', rest)
+    if not m:
+        return None
+    j = int(m.group(4))
+    if m.group(2) is not None and int(m.group(2)) <= 3 and j <= 1:
+        return f'input_blocks.{1 + 3 * int(m.group(2)) + j}.0.emb_layers.1'
+    if m.group(1) == 'mid_block' and j <= 1:
+        return f'middle_block.{2 * j}.emb_layers.1'
+    if m.group(3) is not None and int(m.group(3)) <= 3 and j <= 2:
+        return f'output_blocks.{3 * int(m.group(3)) + j}.0.emb_layers.1'
+    return None
+
+
+def map_key(module_key, model='sd14', time_modules=False):
+    """kohya module key -> ('unet' | 'text', graph parameter name).  ValueError, with the reason, for what is not supported.
+    time_modules=True (a pipeline built with lora_time_modules: its TEMB graphs keep their base weights): the modules of the time
+    conditioning -- lora_unet_*_resnets_*_time_emb_proj, lora_unet_time_embedding_linear_1 / _2, what LCM-LoRA adapts next to the
+    usual ones -- map to ('temb', name) instead of being refused."""
+    if time_modules and module_key.startswith('lora_unet_'):
+        name = _time_name(module_key[len('lora_unet_'):])
+        if name is not None:
+            return 'temb', name + '.weight'
     if module_key.startswith('lora_unet_'):
         try:
             name = _unet_name(module_key[len('lora_unet_'):])
@@ -145,24 +179,27 @@ def map_key(module_key, model='sd14'):
     raise ValueError(f'{module_key}: neither a lora_unet_ nor a lora_te_ module')
 
 
-def entries_for(lora, model='sd14', scale_unet=1.0, scale_text=1.0, strict=True):
+def entries_for(lora, model='sd14', scale_unet=1.0, scale_text=1.0, strict=True, time_modules=False):
     """lora: what read_lora takes or returns.  Returns ({'unet': [(param_name, up, down, scale)], 'text': [...]}, skipped): the entry
     lists Graph.set_loras takes, scale = strength * alpha / rank, and the module keys that were skipped.  strict=True raises ValueError
-    listing every unsupported module instead of skipping it."""
+    listing every unsupported module instead of skipping it.  time_modules=True: the modules of the time conditioning (map_key) come
+    back under a third list, 'temb', at the UNet's strength."""
     lora = read_lora(lora)
     out, skipped, why = {'unet': [], 'text': []}, [], []
+    if time_modules:
+        out['temb'] = []
     for module in lora.other:
         skipped.append(module)
         why.append(f'{module}: not a plain LoRA module (LoHa / LoKr / DoRA tensors)')
     for module, (down, up, alpha) in lora.items():
         try:
-            graph, name = map_key(module, model)
+            graph, name = map_key(module, model, time_modules)
         except ValueError as e:
             skipped.append(module)
             why.append(str(e))
             continue
         rank = down.shape[0]
-        strength = scale_unet if graph == 'unet' else scale_text
+        strength = scale_text if graph == 'text' else scale_unet
         out[graph].append((name, up, down, float(strength) * float(alpha) / rank))
     if strict and skipped:
         raise ValueError('unsupported LoRA modules:\n  ' + '\n  '.join(why))

@@ -222,20 +222,24 @@ def reduce_module(mod):
     return ('lokr', torch.ones(1, 1, dtype=torch.float16), t['diff'])
 
 
-def entries_for(src, model='sd14', scale_unet=1.0, scale_text=1.0, strict=True, shapes=None):
+def entries_for(src, model='sd14', scale_unet=1.0, scale_text=1.0, strict=True, shapes=None, time_modules=False):
     """src: what read_network takes or returns.  Returns ({'unet': [entry], 'text': [entry]}, skipped): the entry lists
     Graph.set_networks takes -- (name, up, down, scale), ('loha', name, w1a, w1b, w2a, w2b, scale), ('lokr', name, w1, w2, scale), each a
     NetEntry that keeps the file tensors for merged_state_dict -- with scale = strength * the module's scale, and the module keys that
     were skipped.  shapes: {'unet': {param_name: shape}, 'text': {...}} of the graphs, when known: a LoKr module whose factors do not
-    divide its weight is then refused here.  strict=True raises ValueError listing every unsupported module instead of skipping it."""
+    divide its weight is then refused here.  strict=True raises ValueError listing every unsupported module instead of skipping it.
+    time_modules=True: the modules of the time conditioning (lora.map_key: time_emb_proj, time_embedding_linear_1 / _2) come back under
+    a third list, 'temb', at the UNet's strength, instead of being refused; shapes may then hold a 'temb' table too."""
     net = read_network(src)
     out, skipped, why = {'unet': [], 'text': []}, [], []
+    if time_modules:
+        out['temb'] = []
     for module, reason in net.refused.items():
         skipped.append(module)
         why.append(reason)
     for module, mod in net.items():
         try:
-            graph, name = _lora.map_key(module, model)
+            graph, name = _lora.map_key(module, model, time_modules)
             reduced = reduce_module(mod)
             shape = (shapes or {}).get(graph, {}).get(name)
             if reduced[0] == 'lokr' and shape is not None:
@@ -248,7 +252,7 @@ def entries_for(src, model='sd14', scale_unet=1.0, scale_text=1.0, strict=True, 
             skipped.append(module)
             why.append(str(e))
             continue
-        scale = float(scale_unet if graph == 'unet' else scale_text) * float(mod['scale'])
+        scale = float(scale_text if graph == 'text' else scale_unet) * float(mod['scale'])
         raw = dict(family=mod['family'], tensors=mod['tensors'], scale=scale)
         items = (name, *reduced[1:], scale) if reduced[0] == 'lora' else (reduced[0], name, *reduced[1:], scale)
         out[graph].append(NetEntry(items, raw))

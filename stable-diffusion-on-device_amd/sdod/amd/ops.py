@@ -1106,6 +1106,46 @@ def k_step(eps_nhwc, x, coef, guidance=1.0, den_prev=None, noise=None, seed=0, n
     check(lib.sdod_k_step(ctypes.byref(a), _stream()))
 
 
+def lcm_step(eps_nhwc, x, coef, guidance=None, den_out=None, noise=None, seed=0, noise_level=0, image_index=0, mode=1, uncond_first=True,
+             stage=None):
+    """one Latent Consistency Model step in one launch (include/sdod_hip.h: sdod_lcm_step): e = CFG of the pair eps_nhwc fp16 [2n, ..., c]
+    with `guidance` (mode as cfg_combine), or -- guidance None -- the unguided form, e = eps_nhwc fp16 [n, ..., c] itself; den = d0 x + d1 e
+    (the x0 prediction, written to den_out when given), x <- a x + b den (+ u nu) in place, and -- with stage = (x_dst, temb_row,
+    temb_dst) -- the next evaluation's inputs, x_dst = x unscaled.  coef = LcmSchedule.coef(...): d0, d1, a, b, u.  nu = noise (fp32,
+    x's shape) or, when None, Philox on the device: stream ((3 + noise_level) << 32) | (image_index + i) of `seed` for image i; nothing
+    is drawn or read when u == 0."""
+    lib = _lib.hip()
+    _req(eps_nhwc, torch.float16, 'eps'); _req(x, torch.float32, 'x')
+    a = _lib.LcmStepArgs()
+    if guidance is None:
+        n, c = eps_nhwc.shape[0], eps_nhwc.shape[-1]
+        hw = eps_nhwc.numel() // (n * c)
+        assert x.numel() == n * c * hw, (eps_nhwc.shape, x.shape)
+    else:
+        n, c, hw = _guided_dims(eps_nhwc, x)
+        a.guided, a.guidance = 1, guidance
+    a.eps_nhwc, a.x = _p(eps_nhwc), _p(x)
+    for t, name in ((den_out, 'den_out'), (noise, 'noise')):
+        if t is not None:
+            _req(t, torch.float32, name)
+            assert t.numel() == x.numel(), (name, t.shape, x.shape)
+    a.den_out, a.noise = _p(den_out), _p(noise)
+    a.seed, a.noise_level, a.image_index0 = int(seed) & (2 ** 64 - 1), int(noise_level), int(image_index) & (2 ** 64 - 1)
+    a.n, a.c, a.hw, a.uncond_first, a.mode = n, c, hw, 1 if uncond_first else 0, mode
+    a.d0, a.d1, a.a, a.b, a.u = coef['d0'], coef['d1'], coef['a'], coef['b'], coef['u']
+    _fill_stage(a, x, stage)
+    check(lib.sdod_lcm_step(ctypes.byref(a), _stream()))
+
+
+def guidance_features(w, dim=256):
+    """w fp32 [n] -> fp16 [n, dim]: the guidance-scale embedding of a full LCM checkpoint (include/sdod_hip.h: sdod_guidance_features_f16)"""
+    lib = _lib.hip()
+    _req(w, torch.float32, 'w')
+    out = torch.empty((w.numel(), dim), dtype=torch.float16, device=w.device)
+    check(lib.sdod_guidance_features_f16(_p(w), _p(out), w.numel(), dim, _stream()))
+    return out
+
+
 def k_step_windows(eps, x, coef, wgt, wsum, window_hw, oy, ox, n, chunks=1, wrap_x=False, guidance=1.0, den_prev=None, noise=None, seed=0,
                    noise_level=0, image_index=0, mode=1, stage=None):
     """k_step on a MultiDiffusion canvas in one launch (include/sdod_hip.h: sdod_k_step_windows).  x fp32 [1, c, H, W] (or [c, H, W]): the

@@ -19,7 +19,7 @@ from . import freeu as FU
 from . import upscale as UP
 from . import panorama as PN
 from .host import DpmSolver
-from .samplers import K_SAMPLERS, K_SCHEDULES, PLMS_ORDERS, KSchedule, PlmsSchedule
+from .samplers import K_SAMPLERS, K_SCHEDULES, PLMS_ORDERS, KSchedule, LcmSchedule, PlmsSchedule
 
 
 class Txt2Img:
@@ -54,12 +54,16 @@ class Txt2Img:
     canvas_vae = None
     freeu = False       # FreeU: the UNet was built with the switch and has the unet.freeu parameter input (Txt2Img(..., freeu=True))
     _pano = None        # {(oy, ox, weights kind): the window plan and its device tables}, created with its first entry
+    unguided = False    # LCM: the UNet has one row per image, the conditional one (Txt2Img(..., unguided=True)): only the *_lcm entry points run
+    guidance_embed = False      # ... and the TEMB graphs take the guidance scale w (Txt2Img(..., guidance_embed=True))
+    lora_time_modules = False   # set_loras also adapts the time conditioning: the TEMB graphs keep their base weights
+    _time_networks = ()         # ... the 'temb' entries of the current set_loras, for the TEMB graphs made later
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
                  adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False, ip_adapter=False, canvas_hw=None,
-                 canvas_wrap=False, freeu=False):
+                 canvas_wrap=False, freeu=False, unguided=False, guidance_embed=False, lora_time_modules=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -144,7 +148,24 @@ class Txt2Img:
         tensor and the images are the plain pipeline's, bit for bit.  The kernels read the block on the device, so every entry point
         and sampler follows it and a captured trajectory picks up new values without a recapture.  It needs no weights and composes
         with every other argument.  Anything but True / False: ValueError before any device work (freeu.freeu_check_build).  False:
-        nothing is constructed or sized differently."""
+        nothing is constructed or sized differently.
+        unguided=True: few-step sampling with a full Latent Consistency Model checkpoint (LCM_Dreamshaper_v7), which needs
+        no classifier-free guidance: the UNet is built with images_per_gpu rows, one per image, and evaluates the conditional row of
+        ctx2 alone (ctx2 keeps its [2, L, D] shape: encode_prompt is unchanged).  Only sample_lcm() / generate_lcm() /
+        generate_lcm_graphed() / img2img_lcm() run on such a pipeline; every other sampling entry point needs the pair and raises.  Works
+        with loras, prompt_chunks, rectangular latent_hw, with_vae_encoder, tiling, freeu, upscaler, model='sd21' and weight_quant.  Not
+        with cfg_split, inpaint_unet, hires_hw, adapter, controlnet, regions, ip_adapter or canvas_hw: ValueError before any device
+        work (lcm_check_build).  False: nothing is constructed or sized differently -- and the *_lcm entry points then run guided, in
+        the LCM-LoRA form.
+        guidance_embed=True (needs unguided=True): the checkpoint conditions on the guidance scale w through time_embedding.cond_proj
+        -- the TEMB graphs are built with cond_proj_dim = 256 and read time_embed.cond_proj.weight from state_dicts['temb'] /
+        temb.sdodw (convert(..., guidance_embed=True)), and `guidance` of the *_lcm entry points is w.
+        lora_time_modules=True (needs loras=True): the TEMB graphs keep their base weights too, and set_loras() also adapts
+        lora_unet_*_resnets_*_time_emb_proj and lora_unet_time_embedding_linear_1 / _2 -- what LCM-LoRA (lcm-lora-sdv1-5) holds next to
+        the usual modules -- instead of refusing them.  Off, they are refused as ever."""
+        lcm_check_build(unguided, guidance_embed, lora_time_modules, loras, cfg_split, inpaint_unet, hires_hw, adapter, controlnet, regions,
+                        ip_adapter, canvas_hw)
+        self.unguided, self.guidance_embed, self.lora_time_modules = bool(unguided), bool(guidance_embed), bool(lora_time_modules)
         self.freeu = FU.freeu_check_build(freeu)
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         latent_h, latent_w = check_latent_hw(latent_hw)
@@ -227,7 +248,7 @@ class Txt2Img:
         if self.tiling:                  # the UNet and the VAE decoder take the circular border; every other graph has no border to wrap
             unet_cfg, vae_cfg = E.copy_config(unet_cfg), E.copy_config(self.cfg)
             unet_cfg.tiling = vae_cfg.tiling = self.tiling
-        self.unet = E.UNet(unet_cfg, self.n if cfg_split else 2 * self.n, device)
+        self.unet = E.UNet(unet_cfg, self.n if cfg_split or self.unguided else 2 * self.n, device)
         self.vae = E.VaeDecoder(vae_cfg, 1, device) if with_vae else None
         self.text = E.TextEncoder(self.cfg, 2 * (self.regions or self.prompt_chunks), device) if with_text_encoder else None
         self.encoder = E.VaeEncoder(self.cfg, 1, device) if with_vae_encoder else None
@@ -287,7 +308,7 @@ class Txt2Img:
             self.hires = Txt2Img(state_dicts=state_dicts, models_dir=models_dir, images_per_gpu=images_per_gpu, latent_hw=hires_hw,
                                  device=device, use_hip_graph=use_hip_graph, tokenizer=None, with_text_encoder=False, model=model,
                                  with_vae=with_vae, cfg_split=False, weight_quant=weight_quant, with_vae_encoder=False, inpaint_unet=False,
-                                 prompt_chunks=prompt_chunks, loras=loras, freeu=freeu)
+                                 prompt_chunks=prompt_chunks, loras=loras, freeu=freeu, lora_time_modules=lora_time_modules)
 
     def _load(self, g, key, stem):
         ip_unet = g is self.unet and self.ip_tokens      # its to_k_ip / to_v_ip come from the adapter's container, by the UNet's names
@@ -324,23 +345,54 @@ class Txt2Img:
             parsed.append((a[0], float(strengths[0]), float(strengths[1])))
         if self.cfg.weight_quant != 0:
             raise ValueError('LoRA adapters need fp16 weights: this pipeline keeps uint8 codes (weight_quant); merge on the host instead')
-        lists, skipped = {'unet': [], 'text': []}, []
+        lists, skipped = {'unet': [], 'text': [], 'temb': []}, []
         shapes = {'unet': dict(self.unet.param_table()), 'text': dict(self.text.param_table()) if self.text is not None else {}} if parsed else None
+        if parsed and self.lora_time_modules:
+            shapes['temb'] = self._temb_shapes()
         for src, s_unet, s_text in parsed:
-            ent, skip = L.entries_for(src, self.model, s_unet, s_text, strict=strict, shapes=shapes)
+            if self.lora_time_modules:
+                ent, skip = L.entries_for(src, self.model, s_unet, s_text, strict=strict, shapes=shapes, time_modules=True)
+                lists['temb'] += ent['temb']
+            else:           # (the call, and what it refuses, of every build before lora_time_modules)
+                ent, skip = L.entries_for(src, self.model, s_unet, s_text, strict=strict, shapes=shapes)
             lists['unet'] += ent['unet']
             lists['text'] += ent['text']
             skipped += skip
         if lists['text'] and self.text is None:
             raise ValueError('the adapters hold text-encoder modules and this pipeline has no text encoder')
         self.unet.set_networks(lists['unet'])
+        if self.lora_time_modules:       # the time conditioning: every TEMB graph there is, the cached rows in place, and the list kept
+            self._set_time_networks(lists['temb'])
         if self.hires is not None:       # the second pass runs the same model: its UNet takes the same adapters
             self.hires.unet.set_networks(lists['unet'])
             self.hires._ctx_fresh = True
+            if self.lora_time_modules:
+                self.hires._set_time_networks(lists['temb'])
         if self.text is not None:
             self.text.set_networks(lists['text'])
         self._ctx_fresh = True
         return skipped
+
+    _temb_table = None          # {parameter name: shape} of this pipeline's TEMB graphs, read once (_temb_shapes)
+
+    def _temb_shapes(self):
+        """the parameter table of the TEMB graphs, which is the same at every row count: from one that exists, else from a declared
+        graph (no device memory), and kept"""
+        if self._temb_table is None:
+            g = next((g for k, g in self._temb_graphs.items() if not isinstance(k, tuple)), None)
+            if g is None:
+                g = E.Temb(self.cfg, 1, self.device, cond_proj_dim=E.LCM_COND_PROJ_DIM if self.guidance_embed else 0)
+            self._temb_table = dict(g.param_table())
+        return self._temb_table
+
+    def _set_time_networks(self, entries):
+        """set_loras' part on the time conditioning (lora_time_modules): the entries go to every TEMB graph that exists, every cached
+        time-embedding tensor is recomputed in the same memory, and the list is kept for the TEMB graphs a new schedule length makes"""
+        self._time_networks = tuple(entries)
+        for key, g in self._temb_graphs.items():
+            if not (isinstance(key, tuple) and key[0] == 'control'):      # (the ControlNet's own TEMB graph is not adapted)
+                g.set_networks(list(entries))
+        self._refresh_time_embeddings()
 
     def clear_loras(self):
         """back to the base weights, bit for bit: set_loras([])"""
@@ -582,17 +634,58 @@ class Txt2Img:
             ids[first + 1:] = 0
         return ids
 
-    def time_embeddings(self, times):
+    def _temb_graph(self, rows):
+        """the TEMB graph of `rows` rows, made on first use: with guidance_embed it has the w input and cond_proj, with
+        lora_time_modules it keeps its base weights and starts from the adapters set_loras() holds"""
+        g = self._temb_graphs.get(rows)
+        if g is None:
+            g = E.Temb(self.cfg, rows, self.device, cond_proj_dim=E.LCM_COND_PROJ_DIM) if self.guidance_embed else E.Temb(self.cfg, rows, self.device)
+            self._load(g, 'temb', 'temb')
+            if self.lora_time_modules:
+                g.keep_base()
+            g.finalize()
+            if self._time_networks:
+                g.set_networks(list(self._time_networks))
+            self._temb_graphs[rows] = g
+        return g
+
+    def _time_embeddings_w(self, key, w, out=None):
+        """time_embeddings on a guidance_embed pipeline: every row at guidance scale w; out: recompute into this cached tensor"""
+        if w is None:
+            raise ValueError('this pipeline was built with guidance_embed=True: its time conditioning needs the guidance scale w')
+        ckey = (key, float(w))
+        if out is None and ckey in self._temb_cache:
+            return self._temb_cache[ckey]
+        g = self._temb_graph(len(key))
+        g.t.copy_(torch.tensor(key, dtype=torch.float32))
+        g.w.fill_(float(w))
+        g.execute()
+        if out is None:
+            out = self._temb_cache[ckey] = g.out.clone()
+        else:
+            out.copy_(g.out)
+        return out
+
+    def _refresh_time_embeddings(self):
+        """after the TEMB graphs' weights changed (set_loras with lora_time_modules): every cached tensor recomputed in place, in the
+        same memory, so that what already points at its rows -- a captured trajectory -- follows"""
+        for ckey, out in self._temb_cache.items():
+            if self.guidance_embed:
+                self._time_embeddings_w(ckey[0], ckey[1], out)
+                continue
+            g = self._temb_graph(len(ckey))
+            g.t.copy_(torch.tensor(ckey, dtype=torch.float32))
+            g.execute()
+            out[:, :g.width].copy_(g.out)       # (a ControlNet's own columns ride behind: they are not adapted)
+
+    def time_embeddings(self, times, w=None):
         """[len(times), E] fp16: time-MLP output projected for every ResBlock, for model times `times` (cached per
-        schedule, as context.cpp:257-278 does)"""
+        schedule, as context.cpp:257-278 does).  w: the guidance scale, for a pipeline built with guidance_embed (and only there)."""
         key = tuple(float(t) for t in times)
+        if self.guidance_embed:         # these pipelines' rows depend on the guidance scale too: the key is (times, w)
+            return self._time_embeddings_w(key, w)
         if key not in self._temb_cache:
-            g = self._temb_graphs.get(len(key))
-            if g is None:
-                g = E.Temb(self.cfg, len(key), self.device)
-                self._load(g, 'temb', 'temb')
-                g.finalize()
-                self._temb_graphs[len(key)] = g
+            g = self._temb_graph(len(key))
             g.t.copy_(torch.tensor(key, dtype=torch.float32))
             g.execute()
             if self.controlnet is None:
@@ -626,10 +719,20 @@ class Txt2Img:
             raise RuntimeError('this pipeline was built with inpaint_unet=True: its UNet needs the conditioning channels that '
                                'inpaint_concat() stages; nothing has been staged yet')
 
-    def _set_context(self, ctx2):
+    def _require_pairs(self, name):
+        """every sampling entry point but the LCM ones reads (uncond, cond) pairs: refuse on a pipeline whose UNet has one row per image"""
+        if self.unguided:
+            raise ValueError(f'{name} needs the classifier-free-guidance pair, and this pipeline was built with unguided=True (one UNet row per '
+                             f'image): use sample_lcm / generate_lcm / generate_lcm_graphed / img2img_lcm')
+
+    def _set_context(self, ctx2, lcm=False):
         self._require_cond()
         n = self.n
-        if self.cfg_split:
+        if self.unguided:
+            if not lcm:
+                self._require_pairs('this sampler')
+            self.unet.ctx.copy_(ctx2[1:2].expand(n, -1, -1))          # the conditional row alone
+        elif self.cfg_split:
             self.unet.ctx.copy_(ctx2[self._half:self._half + 1].expand(n, -1, -1))
         else:
             self.unet.ctx[:n].copy_(ctx2[0:1].expand(n, -1, -1))
@@ -678,6 +781,7 @@ class Txt2Img:
 
     # ------------------------------------------------------------------ samplers
     def sample_plms(self, ctx2, x_T, steps=20, guidance=7.5, trace=None):
+        self._require_pairs('sample_plms')
         sch = PlmsSchedule(steps)
         temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
         self._set_context(ctx2)
@@ -720,6 +824,7 @@ class Txt2Img:
 
     def sample_dpm(self, ctx2, x_T, steps=20, guidance=7.5):
         """the reference driver's sampler: DPM-Solver++(2M), CFG as g*e_c + (1-g)*e_u (context.cpp:342-382)"""
+        self._require_pairs('sample_dpm')
         solver = DpmSolver()
         model_ts = solver.prepare(steps)
         temb = self.time_embeddings(model_ts[:steps])
@@ -744,6 +849,7 @@ class Txt2Img:
         for bit): the model sees c_in(i) * x at the fractional time times[i].  euler_a's fresh noise of step i: step_noise[i - first]
         (fp32 [steps - first - 1, n, 4, H, W]; the last step draws none) or Philox on the device, stream ((3 + i) << 32) |
         (image_index + k) of `seed` for image k.  Under cfg_split the step runs redundantly on both ranks behind the exchange."""
+        self._require_pairs('sample_k')
         k_check_args(sampler, steps, schedule, eta, step_noise, self._latent_shape, x.shape[0], first)
         sch = KSchedule(steps, schedule)
         temb = self.time_embeddings(sch.times)                             # row i <-> step i
@@ -761,6 +867,74 @@ class Txt2Img:
                        seed=seed, noise_level=i, image_index=image_index, mode=1,
                        stage=(self.unet.x, temb[i + 1], self._temb_dst) if i + 1 < steps else None)
         return x
+
+    # ------------------------------------------------------------------ few-step sampling (Latent Consistency Models)
+    def sample_lcm(self, ctx2, x, steps=4, guidance=None, *, original_steps=50, strength=1.0, seed=0, image_index=0, step_noise=None,
+                   return_denoised=False):
+        """Multistep consistency sampling (Luo et al. 2023; diffusers' LCMScheduler) over LcmSchedule(steps, original_steps, strength),
+        eps or v models.  x: unit-variance noise x_T, used as it is (the model sees x itself; strength < 1: x already lies at
+        timesteps[0], LcmSchedule.start).  guidance: on a pipeline with the pair, the CFG scale in mode 1 -- the LCM-LoRA form, typically
+        1 to 2, None = 1; on an unguided pipeline with guidance_embed the scale w the checkpoint conditions on (required); on an
+        unguided pipeline without it, None.  One staging launch in front of the loop, then per step the UNet replay and ONE launch
+        (ops.lcm_step = cfg_combine or nhwc_f16_to_nchw_f32 + lincomb4 + lincomb4 + stage_unet_inputs, bit for bit).  The fresh noise
+        behind step i: step_noise[i] (fp32 [steps - 1, n, 4, H, W]; the last step draws none) or Philox on the device, stream
+        ((3 + i) << 32) | (image_index + k) of `seed` for image k.  return_denoised=True: (x, den) with den the last step's x0
+        prediction.  Argument errors raise ValueError before any device work (lcm_check_args)."""
+        g, w = lcm_check_args(self, x, steps, guidance, original_steps, strength, step_noise)
+        sch = LcmSchedule(int(steps), int(original_steps), float(strength))
+        temb = self.time_embeddings(sch.timesteps.astype(np.float32), w)   # row i <-> step i
+        self._set_context(ctx2, lcm=True)
+        x = x.to(self.device, torch.float32).clone()
+        if step_noise is not None:
+            step_noise = step_noise.to(self.device, torch.float32).contiguous()
+        den = torch.empty_like(x) if return_denoised else None
+        ops.stage_unet_inputs(x, self.unet.x, temb[0], self._temb_dst)
+        for i in range(sch.steps):
+            cf = sch.coef(i, self.v_prediction)
+            ops.lcm_step(self._unet_eps(), x, cf, g, den_out=den,
+                         noise=step_noise[i] if step_noise is not None and cf['u'] != 0.0 else None,
+                         seed=seed, noise_level=i, image_index=image_index, mode=1,
+                         stage=(self.unet.x, temb[i + 1], self._temb_dst) if i + 1 < sch.steps else None)
+        return (x, den) if return_denoised else x
+
+    def generate_lcm(self, ctx2, x, steps=4, guidance=None, *, original_steps=50, strength=1.0, seed=0, image_index=0, step_noise=None):
+        """decode(sample_lcm(...), mode 1): uint8 [n, 8H, 8W, 3]"""
+        lcm_check_args(self, x, steps, guidance, original_steps, strength, step_noise)
+        self._require_cond()
+        z = self.sample_lcm(ctx2, x, steps, guidance, original_steps=original_steps, strength=strength, seed=seed, image_index=image_index,
+                            step_noise=step_noise)
+        return self.decode(z, mode=1)
+
+    def generate_lcm_graphed(self, ctx2, x, steps=4, guidance=None, *, original_steps=50, strength=1.0, seed=0, image_index=0,
+                             step_noise=None):
+        """generate_lcm() with the whole trajectory and the decode replayed as ONE device graph, captured once per (steps, guidance,
+        shape, original_steps, strength) from the eager path.  The step noise is a static input, the caller's or drawn on the eager
+        path's streams (_replay): the result equals generate_lcm() with the same arguments, bit for bit, and the graph bakes no seed."""
+        lcm_check_args(self, x, steps, guidance, original_steps, strength, step_noise)
+        self._require_cond()
+        kw = dict(steps=steps, guidance=guidance, original_steps=original_steps, strength=strength)
+        if self.cfg_split:                 # a collective per evaluation cannot live inside one captured graph
+            return self.generate_lcm(ctx2, x, seed=seed, image_index=image_index, step_noise=step_noise, **kw)
+        key = ('lcm', int(steps), None if guidance is None else float(guidance), tuple(x.shape), int(original_steps), float(strength))
+        inputs = dict(ctx2=_copied(ctx2), x=_copied(x, torch.float32))
+        if int(steps) > 1:
+            inputs['step_noise'] = _step_noise(step_noise, (int(steps) - 1,) + tuple(x.shape), seed, 0, image_index)
+        return self._replay(key, lambda **s: self.generate_lcm(**s, **kw), inputs)
+
+    def img2img_lcm(self, ctx2, init_u8, strength=0.5, steps=4, guidance=None, *, original_steps=50, seed=0, noise=None, image_index=0,
+                    step_noise=None):
+        """img2img in few steps: encode the init image as img2img() does (noise = (n1, n2) or Philox streams 1 and 2), noise its
+        clean latent to LcmSchedule(steps, original_steps, strength).timesteps[0] with LcmSchedule.start(), sample_lcm from there,
+        decode to uint8.  Needs with_vae_encoder.  Argument errors raise ValueError before any device work."""
+        if self.encoder is None:
+            raise RuntimeError('Txt2Img(..., with_vae_encoder=True) is needed for img2img')
+        lat = (init_u8.shape[0],) + self._latent_shape
+        lcm_check_args(self, None, steps, guidance, original_steps, strength, step_noise, shape=lat)
+        sch = LcmSchedule(int(steps), int(original_steps), float(strength))
+        x = self.encode(init_u8, seed, image_index, noise=noise, coef=sch.start())
+        z = self.sample_lcm(ctx2, x, steps, guidance, original_steps=original_steps, strength=strength, seed=seed, image_index=image_index,
+                            step_noise=step_noise)
+        return self.decode(z, mode=1)
 
     # ------------------------------------------------------------------ MultiDiffusion panoramas
     def _panorama_plan(self, x_T, sampler, steps, schedule, eta, stride, weights, step_noise):
@@ -804,6 +978,7 @@ class Txt2Img:
         Philox stream ((3 + i) << 32) | image_index of `seed` over the canvas.  With all windows in one evaluation a step is the UNet
         replay plus that launch; with more, two device copies per further evaluation.  Only the k-samplers: 'plms' and 'dpm' raise
         ValueError, as every other argument error does before any device work."""
+        self._require_pairs('sample_panorama')
         plan = self._panorama_plan(x_T, sampler, steps, schedule, eta, stride, weights, step_noise)
         sch = KSchedule(steps, schedule)
         temb = self.time_embeddings(sch.times)                             # row i <-> step i
@@ -834,6 +1009,7 @@ class Txt2Img:
     def generate_panorama(self, ctx2, x_T, sampler='dpmpp_2m', steps=20, guidance=7.5, *, schedule='discrete', eta=1.0, stride=None,
                           weights='uniform', seed=0, image_index=0, step_noise=None):
         """decode_canvas(sample_panorama(...)): uint8 [1, 8H, 8W, 3]"""
+        self._require_pairs('generate_panorama')
         z = self.sample_panorama(ctx2, x_T, sampler, steps, guidance, schedule=schedule, eta=eta, stride=stride, weights=weights, seed=seed,
                                  image_index=image_index, step_noise=step_noise)
         return self.decode_canvas(z)
@@ -844,6 +1020,7 @@ class Txt2Img:
         decode -- replayed as ONE device graph (_replay), captured once per (sampler, steps, guidance, schedule, eta, stride, weights).
         euler_a's step noise is a static input, the caller's or drawn on the eager path's streams: the result equals
         generate_panorama() with the same arguments, bit for bit."""
+        self._require_pairs('generate_panorama_graphed')
         plan = self._panorama_plan(x_T, sampler, steps, schedule, eta, stride, weights, step_noise)
         kw = dict(sampler=sampler, steps=steps, guidance=guidance, schedule=schedule, eta=eta, stride=stride, weights=weights)
         key = ('panorama', sampler, int(steps), float(guidance), schedule, float(eta), tuple(plan['oy']), tuple(plan['ox']), weights)
@@ -897,6 +1074,7 @@ class Txt2Img:
         raises).  'euler' / 'euler_a' / 'dpmpp_2m': sample_k from sigmas[0] * x_T (x_T stays unit-variance noise) on schedule
         'discrete' or 'karras', decode mode 1; eta, seed, image_index, step_noise (fp32 [steps - 1, n, 4, H, W]) are euler_a's noise.
         Argument errors raise ValueError before any device work."""
+        self._require_pairs('generate')
         k_check_args(sampler, steps, schedule, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
         self._require_cond()
         z = self._sample(sampler, ctx2, x_T, steps, guidance, schedule=schedule, eta=eta, seed=seed, image_index=image_index,
@@ -973,6 +1151,7 @@ class Txt2Img:
         same kernels on the same buffers, bit for bit) and cached; ctx2 / x_T are copied into the graph's static inputs.  euler_a's
         step noise is a static input too, the caller's or drawn on the eager path's streams (_replay): the result equals generate() with
         the same arguments."""
+        self._require_pairs('generate_graphed')
         k_check_args(sampler, steps, schedule, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
         self._require_cond()
         kw = dict(steps=steps, guidance=guidance, sampler=sampler, schedule=schedule, eta=eta)
@@ -994,6 +1173,7 @@ class Txt2Img:
     def generate_upscaled(self, ctx2, x_T, steps=20, guidance=7.5, sampler='plms', *, schedule='discrete', eta=1.0, seed=0, image_index=0,
                           step_noise=None):
         """upscale(generate(...)) -- with hires_hw: upscale(generate_hires(...)) with the hires pass's defaults.  generate()'s arguments."""
+        self._require_pairs('generate_upscaled')
         upscale_check_args(self, None)
         kw = dict(steps=steps, guidance=guidance, sampler=sampler, schedule=schedule, eta=eta, seed=seed, image_index=image_index,
                   step_noise=step_noise)
@@ -1007,6 +1187,7 @@ class Txt2Img:
         generate_graphed key from the eager path, so it is the same kernels on the same buffers: the result equals
         generate_upscaled() with the same arguments).  generate_graphed()'s arguments; not with hires_hw (generate_hires_graphed has
         its own noise inputs) or cfg_split: ValueError."""
+        self._require_pairs('generate_upscaled_graphed')
         upscale_check_args(self, None)
         if self.hires is not None or getattr(self, 'cfg_split', False):
             raise ValueError('generate_upscaled_graphed cannot be combined with hires_hw or cfg_split: use generate_upscaled')
@@ -1057,6 +1238,7 @@ class Txt2Img:
 
     def sample_ddim_from(self, ctx2, x, t_enc, steps=50, guidance=7.5, trace=None):
         """ldm DDIMSampler.decode: t_enc DDIM steps (eta = 0, CFG mode 1) from ddim index t_enc - 1 down to 0"""
+        self._require_pairs('sample_ddim_from')
         sch = PlmsSchedule(steps)
         temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
         self._set_context(ctx2)
@@ -1075,6 +1257,7 @@ class Txt2Img:
         sampler None: ldm's DDIM, as ever.  'euler' / 'euler_a' / 'dpmpp_2m': with t_enc = int(strength * steps) and first = steps -
         t_enc the start latent is z0 + sigmas[first] * n2 and sample_k(first=first) makes the t_enc evaluations; step_noise fp32
         [t_enc - 1, n, 4, H, W], row r = step first + r (euler_a); `trace` is not filled."""
+        self._require_pairs('img2img')
         t_enc = img2img_k_check_args(strength, steps, sampler, schedule, eta, step_noise, self._latent_shape, init_u8.shape[0])
         z = self._sample_from(sampler, ctx2, lambda a, b: self.encode(init_u8, seed, image_index, strength, steps, noise, coef=(a, b)),
                               t_enc, steps, guidance, schedule, eta, seed, image_index, step_noise, trace)
@@ -1086,6 +1269,7 @@ class Txt2Img:
         once per (t_enc, steps, guidance, shape) from the eager path.  The noise is always an input of the graph, the caller's or drawn
         on the streams encode() uses (_replay), so the result equals img2img() with the same arguments.  With a k-sampler the key adds
         (sampler, schedule, eta), and euler_a's step noise is one more input of the graph."""
+        self._require_pairs('img2img_graphed')
         t_enc = img2img_k_check_args(strength, steps, sampler, schedule, eta, step_noise, self._latent_shape, init_u8.shape[0])
         kw = dict(strength=strength, steps=steps, guidance=guidance, sampler=sampler, schedule=schedule, eta=eta)
         if self.cfg_split:
@@ -1112,6 +1296,7 @@ class Txt2Img:
         already) and that there is a final noise-free blend, so the kept region of the result is z0 itself.
         One staging launch in front of the loop, then per step the UNet replay and ONE launch (ops.ddim_inpaint_step = cfg_combine
         + ddim_step + the blend + stage_unet_inputs, bit for bit)."""
+        self._require_pairs('sample_ddim_inpaint')
         sch = PlmsSchedule(steps)
         temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
         self._set_context(ctx2)
@@ -1144,6 +1329,7 @@ class Txt2Img:
         image's bit for bit.  composite=False returns the plain decode.  noise = (n1, n2) as encode(); step_noise fp32
         [t_enc - 1, n, 4, H, W] or None (device Philox, see sample_ddim_inpaint).  Argument errors raise ValueError before any
         device work."""
+        self._require_pairs('inpaint')
         t_enc = self._inpaint_args(init_u8, mask_u8, strength, steps, step_noise)
         init_u8 = init_u8.to(self.device).contiguous()
         mask_u8 = mask_u8.to(self.device).contiguous()
@@ -1160,6 +1346,7 @@ class Txt2Img:
         composite), captured once per (t_enc, steps, guidance, composite, shape) from the eager path.  Image, mask and all noise are
         inputs of the graph, the caller's or drawn on the eager path's streams (_replay), so the result equals inpaint() with the same
         arguments.  Eager under cfg_split."""
+        self._require_pairs('inpaint_graphed')
         t_enc = self._inpaint_args(init_u8, mask_u8, strength, steps, step_noise)
         kw = dict(strength=strength, steps=steps, guidance=guidance, composite=composite)
         if self.cfg_split:
@@ -1201,6 +1388,7 @@ class Txt2Img:
         cat(x, c_mask, c_lat) in both guidance halves.  From pure noise x_T the ordinary sampler ('plms' or 'dpm', all steps), decode, and
         with composite=True the integer pixel composite of inpaint() with the unbinarised mask bytes (pixels with mask byte 0 are
         the init image's).  Argument errors raise ValueError before any device work."""
+        self._require_pairs('inpaint_concat')
         self._inpaint_concat_args(init_u8, mask_u8, x_T, steps, sampler, noise)
         init_u8 = init_u8.to(self.device).contiguous()
         mask_u8 = mask_u8.to(self.device).contiguous()
@@ -1214,6 +1402,7 @@ class Txt2Img:
         composite), captured once per (sampler, steps, guidance, composite, shape) from the eager path.  Image, mask, x_T and the noise
         are inputs of the graph, the noise the caller's or drawn on the eager path's stream (_replay), so the result equals
         inpaint_concat() with the same arguments.  Eager under cfg_split."""
+        self._require_pairs('inpaint_concat_graphed')
         self._inpaint_concat_args(init_u8, mask_u8, x_T, steps, sampler, noise)
         kw = dict(steps=steps, guidance=guidance, sampler=sampler, composite=composite)
         if self.cfg_split:
@@ -1238,6 +1427,7 @@ class Txt2Img:
         (fp32 [n, 4, H2, W2]) or Philox family 2 of hires_seed; euler_a's step noise: hires_step_noise (fp32 [t_enc - 1, n, 4, H2, W2],
         row r = step first + r) or families 3 + step of hires_seed.  hires_steps and hires_seed have no defaults here: generate_hires
         owns them (steps and seed + 1).  Argument errors raise ValueError before any device work."""
+        self._require_pairs('hires_from_latent')
         if not isinstance(z_lo, torch.Tensor) or z_lo.dim() != 4 or tuple(z_lo.shape[1:]) != self._latent_shape:
             raise ValueError(f'z_lo must be a tensor [n, {", ".join(str(v) for v in self._latent_shape)}], got {tuple(getattr(z_lo, "shape", ()))}')
         t_enc = hires_check_args(self, z_lo.shape[0], sampler, hires_steps, denoise, upscaler, schedule, eta, hires_noise, hires_step_noise)
@@ -1259,6 +1449,7 @@ class Txt2Img:
         on its result with hires_steps (default: steps) and denoise.  hires_seed defaults to seed + 1: with the same seed pass 2's
         step-noise streams would coincide with pass 1's.  Returns uint8 [n, 8 H2, 8 W2, 3].  Argument errors raise ValueError before
         any device work."""
+        self._require_pairs('generate_hires')
         sched1 = schedule if sampler in K_SAMPLERS else 'discrete'
         hires_steps = steps if hires_steps is None else hires_steps
         k_check_args(sampler, steps, sched1, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
@@ -1277,6 +1468,7 @@ class Txt2Img:
         hires_steps, t_enc, guidance, upscaler, schedule, eta, shape) from the eager path.  ctx2, x_T and all noise are inputs of the
         graph, the caller's or drawn on the eager path's streams (_replay), so the result equals generate_hires() with the same
         arguments."""
+        self._require_pairs('generate_hires_graphed')
         sched1 = schedule if sampler in K_SAMPLERS else 'discrete'
         hires_steps = steps if hires_steps is None else hires_steps
         k_check_args(sampler, steps, sched1, eta, step_noise, self._latent_shape, x_T.shape[0], old_samplers=True)
@@ -1301,6 +1493,7 @@ class Txt2Img:
         gives back (bench.py --overlap-decode: 8.97 vs 9.29 images/s serial, same box).  Returns (uint8 images, event): the
         images are valid once the event has completed and until the decode of the NEXT call starts.  'plms' and 'dpm' only: its
         sampling graph has no noise input."""
+        self._require_pairs('generate_pipelined')
         if sampler not in ('plms', 'dpm'):
             raise ValueError(f"generate_pipelined samples with 'plms' or 'dpm', got {sampler!r}")
         if self.cfg_split:
@@ -1562,6 +1755,59 @@ def k_check_args(sampler, steps, schedule, eta, step_noise, latent, n_images, fi
             raise ValueError(f"step_noise is euler_a's fresh noise; sampler {sampler!r} draws none")
         _want_tensor('step_noise', step_noise, (int(steps) - int(first) - 1, n_images) + tuple(latent), torch.float32,
                      ' (one row per step but the last)')
+
+
+def lcm_check_build(unguided, guidance_embed, lora_time_modules, loras, cfg_split, inpaint_unet, hires_hw, adapter, controlnet, regions,
+                    ip_adapter, canvas_hw):
+    """Txt2Img's unguided / guidance_embed / lora_time_modules: each True or False; unguided with none of cfg_split, inpaint_unet,
+    hires_hw, adapter, controlnet, regions, ip_adapter, canvas_hw (each of them is built on the guidance pair); guidance_embed needs
+    unguided, lora_time_modules needs loras.  Raises ValueError."""
+    for name, v in (('unguided', unguided), ('guidance_embed', guidance_embed), ('lora_time_modules', lora_time_modules)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f'{name} must be True or False, got {v!r}')
+    if unguided:
+        for name, on in (('cfg_split', cfg_split), ('inpaint_unet', inpaint_unet), ('hires_hw', hires_hw is not None), ('adapter', adapter),
+                         ('controlnet', controlnet), ('regions', regions), ('ip_adapter', ip_adapter), ('canvas_hw', canvas_hw is not None)):
+            if on:
+                raise ValueError(f'unguided cannot be combined with {name}: it is built on the (uncond, cond) pair of rows')
+    if guidance_embed and not unguided:
+        raise ValueError('guidance_embed needs unguided=True: a checkpoint with a guidance-scale embedding evaluates one row per image')
+    if lora_time_modules and not loras:
+        raise ValueError('lora_time_modules needs loras=True')
+
+
+def lcm_check_args(pipe, x, steps, guidance, original_steps, strength, step_noise, shape=None):
+    """the argument contract of the LCM entry points (Txt2Img.sample_lcm, generate_lcm, generate_lcm_graphed, img2img_lcm), checked on
+    the host before any device work: steps and original_steps positive integers, strength in (0, 1] and steps no more than the
+    int(original_steps * strength) levels they leave (LcmSchedule); x a tensor [n, *latent] with n the pipeline's images_per_gpu
+    (shape: that shape where there is no x yet, img2img_lcm); step_noise None or an fp32 tensor [steps - 1, n, *latent]; guidance a
+    finite number or None on a pipeline with the guidance pair (None = 1), a finite number on an unguided pipeline with
+    guidance_embed, None on one without.  Returns (CFG scale or None, w or None); raises ValueError."""
+    _want_steps('steps', steps)
+    _want_steps('original_steps', original_steps)
+    if isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating)) or not 0.0 < float(strength) <= 1.0:
+        raise ValueError(f'strength must be in (0, 1], got {strength!r}')
+    LcmSchedule(int(steps), int(original_steps), float(strength))
+    want = (pipe.n,) + tuple(pipe._latent_shape)
+    if shape is None:
+        _want_tensor('x', x, want)
+    elif tuple(shape) != want:
+        raise ValueError(f'this pipeline samples {want[0]} image(s) of latent {want[1:]} at a time, got {tuple(shape)}')
+    if step_noise is not None:
+        _want_tensor('step_noise', step_noise, (int(steps) - 1,) + want, torch.float32, ' (one row per step but the last)')
+    number = guidance is not None and not isinstance(guidance, bool) and isinstance(guidance, (int, float, np.integer, np.floating)) \
+        and bool(np.isfinite(float(guidance)))
+    if guidance is not None and not number:
+        raise ValueError(f'guidance must be a finite number, got {guidance!r}')
+    if not pipe.unguided:
+        return (float(guidance) if number else 1.0), None
+    if pipe.guidance_embed:
+        if not number:
+            raise ValueError('this pipeline was built with guidance_embed=True: guidance is the scale w its checkpoint conditions on, a finite number')
+        return None, float(guidance)
+    if guidance is not None:
+        raise ValueError('this pipeline was built with unguided=True and without guidance_embed: nothing takes a guidance scale, guidance must be None')
+    return None, None
 
 
 def img2img_k_check_args(strength, steps, sampler, schedule, eta, step_noise, latent, n_images):

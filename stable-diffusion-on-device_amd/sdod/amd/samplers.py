@@ -140,3 +140,78 @@ class KSchedule:
                     b = e * (1.0 + 1.0 / (2.0 * r))
                     cprev = -e / (2.0 * r)
         return dict(d0=float(d0), d1=float(d1), a=float(a), b=float(b), cprev=float(cprev), u=float(u), stage_scale=self.c_in(i + 1))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Latent Consistency Models (Luo et al. 2023; the public diffusers LCMScheduler): 2 to 8 evaluations of a distilled checkpoint, each
+# followed by the consistency function's boundary-condition mix and a fresh noising to the next level.  The tables are float64 numpy;
+# the per-element arithmetic runs on the device in one launch per step (include/sdod_hip.h: sdod_lcm_step).
+class LcmSchedule:
+    """The timestep grid and step scalars of an LCM trajectory.  The distillation's `original_steps` training-schedule steps, k =
+    n_train // original_steps apart, cut to their first int(original_steps * strength) and read from the top:
+        origin = arange(1, int(original_steps * strength) + 1) * k - 1 ;  timesteps = origin[::-1][floor(linspace(0, len(origin), steps,
+        endpoint=False))]
+    timesteps: int64 [steps], strictly decreasing; alphas_cumprod: float64, the table PLMS uses.  strength < 1 (img2img): the
+    trajectory starts at the lower level timesteps[0]."""
+
+    def __init__(self, steps=4, original_steps=50, strength=1.0, n_train=1000, timestep_scaling=10.0, sigma_data=0.5):
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
+            raise ValueError(f'steps must be a positive integer, got {steps!r}')
+        if isinstance(original_steps, bool) or not isinstance(original_steps, (int, np.integer)) or not 1 <= original_steps <= n_train:
+            raise ValueError(f'original_steps must be an integer in [1, {n_train}], got {original_steps!r}')
+        if isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating)) or not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f'strength must be in (0, 1], got {strength!r}')
+        k = n_train // int(original_steps)
+        origin = np.arange(1, int(int(original_steps) * float(strength)) + 1, dtype=np.int64) * k - 1
+        if steps > len(origin):
+            raise ValueError(f'steps = {steps} is more than the {len(origin)} levels that original_steps = {original_steps} and strength = '
+                             f'{strength} leave')
+        self.steps, self.original_steps, self.strength = int(steps), int(original_steps), float(strength)
+        self.timestep_scaling, self.sigma_data = float(timestep_scaling), float(sigma_data)
+        self.timesteps = origin[::-1][np.floor(np.linspace(0, len(origin), self.steps, endpoint=False)).astype(np.int64)]
+        self.alphas_cumprod = scaled_linear_alphas_cumprod(n_train).astype(np.float64)
+
+    def scalings(self, i):
+        """(c_skip, c_out) of the consistency function's boundary condition at step i, on s = timestep_scaling * t"""
+        s = self.timestep_scaling * float(self.timesteps[i])
+        sd2 = self.sigma_data * self.sigma_data
+        return sd2 / (s * s + sd2), s / np.sqrt(s * s + sd2)
+
+    def start(self):
+        """(z0_coef, noise_coef) of img2img's start latent at timesteps[0]: x = sqrt(abar) z0 + sqrt(1 - abar) noise"""
+        ab = self.alphas_cumprod[self.timesteps[0]]
+        return float(np.sqrt(ab)), float(np.sqrt(1.0 - ab))
+
+    def coef(self, i, v_prediction=False):
+        """the scalars of step i in the linear form of KSchedule.coef (no history term),
+            den = d0 x + d1 e ;  x' = a x + b den + u nu
+        den: the x0 prediction, eps models ((x - sqrt(1 - abar) e) / sqrt(abar)) or v models (sqrt(abar) x - sqrt(1 - abar) v);
+        x' = sqrt(abar') (c_skip x + c_out den) + sqrt(1 - abar') nu with abar' at timesteps[i + 1]; the last step returns the
+        consistency function's value c_skip x + c_out den and draws nothing (u = 0).  Returns a dict of Python floats."""
+        if not 0 <= i < self.steps:
+            raise ValueError(f'step {i} is outside [0, {self.steps - 1}]')
+        ab = self.alphas_cumprod[self.timesteps[i]]
+        if v_prediction:
+            d0, d1 = np.sqrt(ab), -np.sqrt(1.0 - ab)
+        else:
+            d0, d1 = 1.0 / np.sqrt(ab), -np.sqrt(1.0 - ab) / np.sqrt(ab)
+        c_skip, c_out = self.scalings(i)
+        if i + 1 < self.steps:
+            ab1 = self.alphas_cumprod[self.timesteps[i + 1]]
+            a, b, u = np.sqrt(ab1) * c_skip, np.sqrt(ab1) * c_out, np.sqrt(1.0 - ab1)
+        else:
+            a, b, u = c_skip, c_out, 0.0
+        return dict(d0=float(d0), d1=float(d1), a=float(a), b=float(b), u=float(u))
+
+
+def guidance_embedding(w, dim=256):
+    """the guidance-scale embedding of a full LCM checkpoint (its time_embedding.cond_proj input), float64 [len(w), dim]:
+    v = (w - 1) * 1000, f_j = exp(-j ln(10000) / (dim/2 - 1)), [sin(v f_j) | cos(v f_j)] -- sine first and the divisor dim/2 - 1, both
+    unlike the timestep features (sdod_timestep_features_f16).  The reference of sdod_guidance_features_f16."""
+    if dim < 4 or dim % 2:
+        raise ValueError(f'dim must be even and at least 4, got {dim}')
+    v = (np.atleast_1d(np.asarray(w, dtype=np.float64)) - 1.0) * 1000.0
+    half = dim // 2
+    f = np.exp(-np.arange(half, dtype=np.float64) * np.log(10000.0) / (half - 1))
+    arg = v[:, None] * f[None, :]
+    return np.concatenate([np.sin(arg), np.cos(arg)], axis=1)
