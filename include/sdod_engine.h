@@ -209,6 +209,19 @@ typedef struct sdod_lcm_config {
     int time_cond_proj_dim; /* width of the guidance-scale features: 256 for LCM_Dreamshaper_v7; 0 = none */
 } sdod_lcm_config;
 SDOD_API int sdod_graph_create_lcm(void** graph, int kind, const sdod_model_config* cfg, const sdod_lcm_config* lcm, int batch);
+/* The VAE's middle attention, graphs VAE_DECODER, VAE_ENCODER and VAE_ENCODER_MASKED.  The block has two forms:
+ *   four launches per image -- V^T GEMM, scores GEMM into an L x L fp16 buffer, sdod_softmax_rows_f16, P V GEMM -- which needs
+ *     L = latent_h * latent_w to be a multiple of 64 and <= 16384 (the softmax's widest row);
+ *   fused -- one row-major V Linear and ONE sdod_attention_wide_f16 launch over the whole batch, no L x L and no [C][L] buffer,
+ *     any L -- for 4 * vae_channels in {256, 512} (sdod_attention_wide_dim_ok).
+ * fused_attn = 0: the four-launch form wherever it runs (L <= 16384: launch list, arena and output of every earlier build), the fused
+ * form above 16384 positions when the width allows it; this is also what every other create function builds.  fused_attn = 1: the
+ * fused form at every size; INVALID_ARGUMENT at create for a width the kernel does not take or any other kind.  vae == NULL is
+ * fused_attn = 0.  wrap as in sdod_graph_create_wrap (VAE_DECODER only).  The parameters are the same in both forms. */
+typedef struct sdod_vae_config {
+    int fused_attn;
+} sdod_vae_config;
+SDOD_API int sdod_graph_create_vae(void** graph, int kind, const sdod_model_config* cfg, int wrap, const sdod_vae_config* vae, int batch);
 /* Regional prompts, UNET graph only.  cfg->context_len must be 77 * regions: in2 holds, per image, the encodings of
  * `regions` prompts one behind the other.  Behind every other input the graph gets four inputs region_w[level], fp32
  * [H / ds * W / ds][regions] for ds = 1, 2, 4, 8 (what sdod_region_weights_f32 writes), shared by all images of the batch and

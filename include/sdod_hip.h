@@ -296,6 +296,26 @@ SDOD_API int sdod_attention_f16(const void* q, const void* k, const void* v, voi
  * created (sdod_model_config.num_heads / head_dim, include/sdod_engine.h).  Host-only. */
 SDOD_API int sdod_attention_head_dim_ok(int d);
 
+/* Wide single-head attention (the VAE's middle block): out[b][q][0..d) = softmax(scale * Q K^T) V for ONE head of width
+ * d in {256, 512}, fp16 in and out, fp32 scores / running maximum / running sum / accumulators; the lq x lk score matrix is never
+ * written anywhere.  q: [batch][lq][ldq], k: [batch][lk][ldk], v: [batch][lk][ldv], out: [batch][lq][ldo]: image b starts b * l * ld
+ * halves on.  Row strides in halves, multiples of 8 and >= d; every pointer 16-byte aligned (q / k / v / out may be column offsets
+ * into wider rows); lq and lk any positive lengths (<= 2^20); scale finite and > 0.  Anything else is INVALID_ARGUMENT, no launch.
+ * One launch: a workgroup per 64 query rows walks every key. */
+SDOD_API int sdod_attention_wide_f16(const void* q, const void* k, const void* v, void* out, int batch, int lq, int lk, int d,
+                                     int ldq, int ldk, int ldv, int ldo, float scale, void* stream);
+/* 1 when the call above takes width d (256, 512), else 0.  Host-only. */
+SDOD_API int sdod_attention_wide_dim_ok(int d);
+/* The same with a workspace: where the 64-row query blocks are fewer than the chip's CUs, the keys are split over
+ * sdod_attention_wide_splits() workgroups per query block, which park fp32 partial results in ws, and a second launch merges them.
+ * ws: device memory of at least sdod_attention_wide_ws_bytes() bytes, 16-byte aligned, owned by the caller and free again once
+ * the call's work has run; ws == NULL, or a shape the launcher does not split (splits == 1, ws_bytes == 0), is the call above.
+ * Both queries are host-only; splits is 0 for a shape the kernel does not take. */
+SDOD_API int sdod_attention_wide_ws_f16(const void* q, const void* k, const void* v, void* out, int batch, int lq, int lk, int d,
+                                        int ldq, int ldk, int ldv, int ldo, float scale, void* ws, size_t ws_bytes, void* stream);
+SDOD_API int sdod_attention_wide_splits(int batch, int lq, int lk, int d);
+SDOD_API size_t sdod_attention_wide_ws_bytes(int batch, int lq, int lk, int d);
+
 /* Folded cross-attention, the once-per-prompt part.  The text context is constant over the sampler run, so to_q and to_out can
  * be multiplied into K and V: scores_h = LN(x) . W1_h with W1_h = Wq_h^T K_h^T, out = [P_1 | .. | P_H] . [W2_1 ; .. ; W2_H] with
  * W2_h = V_h Wo_h^T -- two GEMMs per evaluation (sdod_gemm_desc: w_img_stride / vec_img_stride / softmax_cols) instead of

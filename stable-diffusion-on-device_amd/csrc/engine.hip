@@ -38,9 +38,16 @@ static void parallel_for(int64_t n, F&& fn) {
 
 // ------------------------------------------------------------------------------------------ lifecycle
 Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg, int wrap, const sdod_upscaler_config& ucfg,
-             const sdod_control_config* ccfg, int regions, int ip_tokens, const sdod_vision_config* vcfg, int cond_proj_dim)
-    : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), regions_(regions), ip_tokens_(ip_tokens), cond_proj_dim_(cond_proj_dim), batch_(batch),
-      wrap_(wrap) {
+             const sdod_control_config* ccfg, int regions, int ip_tokens, const sdod_vision_config* vcfg, int cond_proj_dim, int fused_attn)
+    : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), regions_(regions), ip_tokens_(ip_tokens), cond_proj_dim_(cond_proj_dim),
+      fused_attn_(fused_attn), batch_(batch), wrap_(wrap) {
+    SDOD_REQUIRE(fused_attn == 0 || fused_attn == 1, "fused_attn must be 0 or 1");
+    if (fused_attn) {
+        SDOD_REQUIRE(kind == SDOD_GRAPH_VAE_DECODER || kind == SDOD_GRAPH_VAE_ENCODER || kind == SDOD_GRAPH_VAE_ENCODER_MASKED,
+                     "fused_attn applies to the VAE_DECODER, VAE_ENCODER and VAE_ENCODER_MASKED graphs only");
+        SDOD_REQUIRE(cfg.vae_channels > 0 && cfg.vae_channels <= 1024 && sdod_attention_wide_dim_ok(4 * cfg.vae_channels),
+                     "fused_attn: vae_channels must be 64 or 128 (the wide attention kernel takes 4 * vae_channels = 256 or 512)");
+    }
     if (cond_proj_dim != 0) {
         SDOD_REQUIRE(kind == SDOD_GRAPH_TEMB, "time_cond_proj_dim applies to the TEMB graph only");
         SDOD_REQUIRE(cond_proj_dim > 0 && cond_proj_dim <= 4096 && cond_proj_dim % 16 == 0, "time_cond_proj_dim must be a positive multiple of 16 (at most 4096)");
@@ -1526,6 +1533,18 @@ extern "C" int sdod_graph_create_lcm(void** graph, int kind, const sdod_model_co
                      kind != SDOD_GRAPH_IMAGE_ENCODER && kind != SDOD_GRAPH_IMAGE_PROJ, "this graph kind has a create function of its own");
     *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, nullptr, 0, 0, nullptr,
                        lcm ? lcm->time_cond_proj_dim : 0);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_create_vae(void** graph, int kind, const sdod_model_config* cfg, int wrap, const sdod_vae_config* vae, int batch) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph && cfg, "null argument");
+    *graph = nullptr;
+    SDOD_REQUIRE(kind == SDOD_GRAPH_VAE_DECODER || kind == SDOD_GRAPH_VAE_ENCODER || kind == SDOD_GRAPH_VAE_ENCODER_MASKED,
+                 "kind must be SDOD_GRAPH_VAE_DECODER, SDOD_GRAPH_VAE_ENCODER or SDOD_GRAPH_VAE_ENCODER_MASKED");
+    *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, wrap, sdod_upscaler_config{0, 0, 0}, nullptr, 0, 0, nullptr, 0,
+                       vae ? vae->fused_attn : 0);
     return 0;
     SDOD_CATCH
 }

@@ -842,13 +842,39 @@ Act Graph::vae_attn_block(const std::string& pfx, const Act& x) {
     const int vw = P(pfx + ".v.weight", {C, C, 1, 1}, PK_CONV1), vb = P(pfx + ".v.bias", {C}, PK_VEC);
     const int pw = P(pfx + ".proj_out.weight", {C, C, 1, 1}, PK_CONV1), pb = P(pfx + ".proj_out.bias", {C}, PK_VEC);
     if (mode_ == DECLARE) return act(x.n, x.h, x.w, C);
-    SDOD_REQUIRE(L % 64 == 0 && L <= 16384, "VAE attention needs H*W % 64 == 0 and <= 16384");
+    // two forms (include/sdod_engine.h, sdod_vae_config): four launches per image through an L x L score buffer wherever that runs
+    // today, the fused wide attention kernel above the softmax's widest row or on request (fused_attn)
+    constexpr int kMaxScoreRow = 16384;
+    const bool fused = fused_attn_ != 0 || L > kMaxScoreRow;
+    if (fused)
+        SDOD_REQUIRE(sdod_attention_wide_dim_ok(C), "vae_channels = " + std::to_string(cfg_.vae_channels) + " above " + std::to_string(kMaxScoreRow) +
+                                                        " positions (latent_h * latent_w): only vae_channels 64 and 128 have the fused VAE attention");
+    else
+        SDOD_REQUIRE(L % 64 == 0, "VAE attention needs H*W % 64 == 0 up to 16384 positions (or fused_attn)");
 
     Act g = group_norm(x, nullptr, nw, nb, 1e-6f, false);
     f16* qk = alloc((size_t)rows * 2 * C);
     { GemmOpt o; o.bias_raw = reinterpret_cast<const float*>(group_base(gb));
       linear_raw(g.p, rows, C, reinterpret_cast<const f16*>(group_base(gw)), C, 2 * C, qk, o); }
     f16* att = alloc((size_t)rows * C);
+    if (fused) {
+        // V row-major over all images, then ONE launch over the batch on the halves of qk: no L x L and no [C][L] buffer
+        f16* v = alloc((size_t)rows * C);
+        { GemmOpt o; o.bias = vb; linear(g.p, rows, C, vw, C, v, o); }
+        release(g);
+        const size_t ws_bytes = sdod_attention_wide_ws_bytes(B, L, L, C); // partial results of the key splits (small L only)
+        f16* ws = ws_bytes ? alloc((ws_bytes + 1) / 2) : nullptr;
+        const float scale = 1.0f / sqrtf((float)C);
+        emit([=](hipStream_t st) { check_rc(sdod_attention_wide_ws_f16(qk, qk + C, v, att, B, L, L, C, 2 * C, 2 * C, C, C, scale, ws, ws_bytes, st)); },
+             "attention_wide", 4.0 * B * (double)L * L * C, 4.0 * rows * C * 2 + 2.0 * (double)ws_bytes,
+             "B" + std::to_string(B) + " L" + std::to_string(L) + " d" + std::to_string(C) + " splits" + std::to_string(sdod_attention_wide_splits(B, L, L, C)));
+        if (ws) release(ws);
+        release(v); release(qk);
+        Act out = act(x.n, x.h, x.w, C);
+        { GemmOpt o; o.bias = pb; o.residual = x.p; linear(att, rows, C, pw, C, out.p, o); }
+        release(att);
+        return out;
+    }
     for (int b = 0; b < B; ++b) {
         const f16* gb_ = g.p + (size_t)b * L * C;
         f16* vt = alloc((size_t)C * L); // V^T [C][L] = Wv . g_b^T + bv   (bias indexed by the output row)

@@ -77,6 +77,11 @@ LCM_COND_PROJ_DIM = 256     # time_cond_proj_dim of the released full LCM checkp
 #                             Txt2Img(guidance_embed=True) build the TEMB graphs with
 
 
+class VaeConfig(ctypes.Structure):
+    """mirror of `struct sdod_vae_config`"""
+    _fields_ = [('fused_attn', ctypes.c_int)]
+
+
 class LcmConfig(ctypes.Structure):
     """mirror of `struct sdod_lcm_config`"""
     _fields_ = [('time_cond_proj_dim', ctypes.c_int)]
@@ -137,6 +142,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_enable_freeu', 'sdod_graph_freeu_input',
     'sdod_graph_set_networks',
     'sdod_graph_create_lcm',
+    'sdod_graph_create_vae',
 ]
 
 
@@ -157,6 +163,7 @@ def _engine():
         lib.sdod_graph_create_ip.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(IpConfig), I]
         lib.sdod_graph_create_vision.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(VisionConfig), ctypes.POINTER(IpConfig), I]
         lib.sdod_graph_create_lcm.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(LcmConfig), I]
+        lib.sdod_graph_create_vae.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), I, ctypes.POINTER(VaeConfig), I]
         lib.sdod_graph_bind_output.argtypes = [P, I, P, ctypes.c_size_t]
         lib.sdod_graph_destroy.argtypes = [P]
         lib.sdod_graph_num_params.argtypes = [P]
@@ -222,8 +229,9 @@ class Graph:
     Without a GPU only the parameter table can be read (what the checkpoint converter needs); everything that touches
     device memory raises."""
 
-    def __init__(self, kind, cfg, batch, device='cuda:0', wrap=None, cond_proj_dim=0):
-        """wrap: None = the creation entry points of every build before seamless tiling; an int 0..3 goes through
+    def __init__(self, kind, cfg, batch, device='cuda:0', wrap=None, cond_proj_dim=0, fused_attn=None):
+        """fused_attn (the VAE kinds): None = the entry points as before; True / False go through sdod_graph_create_vae, True with the
+        fused middle attention at every size, False with the rule of the entry points as before.  wrap: None = the creation entry points of every build before seamless tiling; an int 0..3 goes through
         sdod_graph_create_wrap (0 builds the plain graph there).  cond_proj_dim: a TEMB graph with an LCM checkpoint's guidance-scale
         embedding goes through sdod_graph_create_lcm; 0 = the entry points as before"""
         self._lib = _engine()
@@ -244,8 +252,13 @@ class Graph:
         cond_proj_dim = int(cond_proj_dim)
         if cond_proj_dim and (kind != TEMB or control):
             raise ValueError("cond_proj_dim applies to the UNet's TEMB graph only, not to a ControlNet's time conditioning (control_temb)")
+        if fused_attn is not None and kind not in (VAE_DECODER, VAE_ENCODER, VAE_ENCODER_MASKED):
+            raise ValueError('fused_attn applies to the VAE decoder and encoder graphs only')
         with self._on_device():
-            if cond_proj_dim:       # the guidance embedding has an entry point of its own; without it nothing changes
+            if fused_attn is not None:  # the switch has an entry point of its own; without it nothing changes
+                check(self._lib.sdod_graph_create_vae(ctypes.byref(self._h), kind, ctypes.byref(cfg), int(wrap or 0),
+                                                      ctypes.byref(VaeConfig(1 if fused_attn else 0)), batch))
+            elif cond_proj_dim:     # the guidance embedding has an entry point of its own; without it nothing changes
                 check(self._lib.sdod_graph_create_lcm(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(LcmConfig(cond_proj_dim)), batch))
             elif kind in (IMAGE_ENCODER, IMAGE_PROJ):   # the image side of an image prompt: cfg.vision, and cfg.ip_tokens for the projection
                 icfg = IpConfig(int(getattr(cfg, 'ip_tokens', 0)))
@@ -730,8 +743,11 @@ class TextEncoder(Graph):
 
 
 class VaeDecoder(Graph):
-    def __init__(self, cfg, batch, device='cuda:0', wrap=None):
-        super().__init__(VAE_DECODER, cfg, batch, device, wrap if wrap is not None else (int(getattr(cfg, 'tiling', 0)) or None))
+    def __init__(self, cfg, batch, device='cuda:0', wrap=None, fused_attn=False):
+        """fused_attn=True: the middle attention as one fused launch at every size (sdod_vae_config); False: four launches through
+        an L x L score buffer up to 16384 latent positions, the fused launch above (vae_channels 64 / 128)"""
+        super().__init__(VAE_DECODER, cfg, batch, device, wrap if wrap is not None else (int(getattr(cfg, 'tiling', 0)) or None),
+                         fused_attn=True if fused_attn else None)
 
     def finalize(self):
         super().finalize()
@@ -744,8 +760,8 @@ class VaeDecoder(Graph):
 class VaeEncoder(Graph):
     """first_stage_model.encoder + quant_conv: uint8 image [B, 8H, 8W, 3] -> fp32 moments [B, 8, H, W] (mean | logvar)"""
 
-    def __init__(self, cfg, batch, device='cuda:0'):
-        super().__init__(VAE_ENCODER, cfg, batch, device)
+    def __init__(self, cfg, batch, device='cuda:0', fused_attn=False):
+        super().__init__(VAE_ENCODER, cfg, batch, device, fused_attn=True if fused_attn else None)
 
     def finalize(self):
         super().finalize()
@@ -759,8 +775,8 @@ class MaskedVaeEncoder(Graph):
     """VaeEncoder on inpainting's masked image: uint8 image [B, 8H, 8W, 3] and uint8 mask [B, 8H, 8W] -> fp32 moments [B, 8, H, W] of
     x = 0 where mask >= 128, 2 u / 255 - 1 elsewhere.  Same parameters (and weight files) as VaeEncoder."""
 
-    def __init__(self, cfg, batch, device='cuda:0'):
-        super().__init__(VAE_ENCODER_MASKED, cfg, batch, device)
+    def __init__(self, cfg, batch, device='cuda:0', fused_attn=False):
+        super().__init__(VAE_ENCODER_MASKED, cfg, batch, device, fused_attn=True if fused_attn else None)
 
     def finalize(self):
         super().finalize()

@@ -398,6 +398,46 @@ def attention(q, k, v, heads, scale=None, causal=False, out=None):
     return out
 
 
+def _rows_view(t, name):
+    """a [B, L, d] fp16 device tensor whose rows may sit in wider ones (a column slice of a contiguous [B, L, ld] buffer): its row
+    stride, after checking that image b starts b * L * ld halves on and that the columns are contiguous"""
+    if not t.is_cuda or t.dtype != torch.float16 or t.dim() != 3:
+        raise ValueError(f'{name} must be a [B, L, d] {torch.float16} tensor on the GPU')
+    b, l, _ = t.shape
+    ld = t.stride(1)
+    if t.stride(2) != 1 or (b > 1 and t.stride(0) != l * ld):
+        raise ValueError(f'{name} must have contiguous columns and images L * row-stride apart, got strides {t.stride()}')
+    return ld
+
+
+def attention_wide_splits(b, lq, lk, d):
+    """key splits attention_wide() runs a [b, lq, d] x [b, lk, d] problem with (1 = one launch, no workspace); 0 = a shape it refuses"""
+    return _lib.hip().sdod_attention_wide_splits(b, lq, lk, d)
+
+
+def attention_wide(q, k, v, scale=None, out=None, split=True):
+    """softmax(scale * q k^T) v for ONE head of width d = 256 or 512 (include/sdod_hip.h: sdod_attention_wide_f16): q [B, Lq, d],
+    k / v [B, Lk, d] fp16, contiguous or column slices of wider rows; out likewise (default: a new contiguous tensor).  scale
+    defaults to d ** -0.5.  split=False keeps the one-launch form where the launcher would split the keys over workgroups."""
+    lib = _lib.hip()
+    ldq, ldk, ldv = _rows_view(q, 'q'), _rows_view(k, 'k'), _rows_view(v, 'v')
+    b, lq, d = q.shape
+    lk = k.shape[1]
+    if k.shape != (b, lk, d) or v.shape != (b, lk, d):
+        raise ValueError(f'k and v must be [{b}, Lk, {d}], got {tuple(k.shape)} and {tuple(v.shape)}')
+    if out is None:
+        out = torch.empty(b, lq, d, dtype=torch.float16, device=q.device)
+    elif out.shape != q.shape:
+        raise ValueError(f'out must be {tuple(q.shape)}, got {tuple(out.shape)}')
+    ldo = _rows_view(out, 'out')
+    if scale is None:
+        scale = d ** -0.5
+    nbytes = lib.sdod_attention_wide_ws_bytes(b, lq, lk, d) if split else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+    check(lib.sdod_attention_wide_ws_f16(_p(q), _p(k), _p(v), _p(out), b, lq, lk, d, ldq, ldk, ldv, ldo, scale, _p(ws), nbytes, _stream()))
+    return out
+
+
 def xattn_fold(kv, k_off, v_off, n_img, L, wq, sq, tq, wo, heads, scale=None, regions=None):
     """once-per-prompt part of the folded cross-attention (include/sdod_hip.h: sdod_xattn_fold_f16).  kv: fp16 [n_img * L, ld]
     holding K at column k_off and V at v_off; wq: LayerNorm-folded to_q weight with its fold vectors sq, tq (ln_fold); wo: to_out

@@ -63,7 +63,7 @@ class Txt2Img:
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
                  adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False, ip_adapter=False, canvas_hw=None,
-                 canvas_wrap=False, freeu=False, unguided=False, guidance_embed=False, lora_time_modules=False):
+                 canvas_wrap=False, freeu=False, unguided=False, guidance_embed=False, lora_time_modules=False, vae_attention='auto'):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -162,7 +162,12 @@ class Txt2Img:
         temb.sdodw (convert(..., guidance_embed=True)), and `guidance` of the *_lcm entry points is w.
         lora_time_modules=True (needs loras=True): the TEMB graphs keep their base weights too, and set_loras() also adapts
         lora_unet_*_resnets_*_time_emb_proj and lora_unet_time_embedding_linear_1 / _2 -- what LCM-LoRA (lcm-lora-sdv1-5) holds next to
-        the usual modules -- instead of refusing them.  Off, they are refused as ever."""
+        the usual modules -- instead of refusing them.  Off, they are refused as ever.
+        vae_attention='auto' (default): every VAE graph -- the decoder, the encoders, the hires pass's and the canvas decoder -- runs its
+        middle attention as it always did up to 16384 latent positions and as one fused launch (ops.attention_wide) above,
+        which is what lets canvas_hw=(64, 512), latent_hw=(128, 136) or hires_hw=(160, 160) build.  'fused': the fused launch at every
+        size (no L x L score buffer in the VAE arenas).  Anything else is a ValueError before any device work."""
+        fused_vae = vae_attention_check(vae_attention)
         lcm_check_build(unguided, guidance_embed, lora_time_modules, loras, cfg_split, inpaint_unet, hires_hw, adapter, controlnet, regions,
                         ip_adapter, canvas_hw)
         self.unguided, self.guidance_embed, self.lora_time_modules = bool(unguided), bool(guidance_embed), bool(lora_time_modules)
@@ -249,10 +254,10 @@ class Txt2Img:
             unet_cfg, vae_cfg = E.copy_config(unet_cfg), E.copy_config(self.cfg)
             unet_cfg.tiling = vae_cfg.tiling = self.tiling
         self.unet = E.UNet(unet_cfg, self.n if cfg_split or self.unguided else 2 * self.n, device)
-        self.vae = E.VaeDecoder(vae_cfg, 1, device) if with_vae else None
+        self.vae = E.VaeDecoder(vae_cfg, 1, device, fused_attn=fused_vae) if with_vae else None
         self.text = E.TextEncoder(self.cfg, 2 * (self.regions or self.prompt_chunks), device) if with_text_encoder else None
-        self.encoder = E.VaeEncoder(self.cfg, 1, device) if with_vae_encoder else None
-        self.masked_encoder = E.MaskedVaeEncoder(self.cfg, 1, device) if self.inpaint_unet else None
+        self.encoder = E.VaeEncoder(self.cfg, 1, device, fused_attn=fused_vae) if with_vae_encoder else None
+        self.masked_encoder = E.MaskedVaeEncoder(self.cfg, 1, device, fused_attn=fused_vae) if self.inpaint_unet else None
         if adapter:
             acfg = E.copy_config(self.cfg)
             acfg.adapter_hint_channels = self.adapter_channels
@@ -261,7 +266,7 @@ class Txt2Img:
             ccfg = E.sd21_config(*self.canvas_hw) if model == 'sd21' else E.sd14_config(*self.canvas_hw)
             if self.canvas_wrap:
                 ccfg.tiling = 1
-            self.canvas_vae = E.VaeDecoder(ccfg, 1, device) if with_vae else None
+            self.canvas_vae = E.VaeDecoder(ccfg, 1, device, fused_attn=fused_vae) if with_vae else None
         self._temb_graphs = {}
         self._sd = state_dicts
         self._dir = models_dir
@@ -308,7 +313,7 @@ class Txt2Img:
             self.hires = Txt2Img(state_dicts=state_dicts, models_dir=models_dir, images_per_gpu=images_per_gpu, latent_hw=hires_hw,
                                  device=device, use_hip_graph=use_hip_graph, tokenizer=None, with_text_encoder=False, model=model,
                                  with_vae=with_vae, cfg_split=False, weight_quant=weight_quant, with_vae_encoder=False, inpaint_unet=False,
-                                 prompt_chunks=prompt_chunks, loras=loras, freeu=freeu, lora_time_modules=lora_time_modules)
+                                 prompt_chunks=prompt_chunks, loras=loras, freeu=freeu, lora_time_modules=lora_time_modules, vae_attention=vae_attention)
 
     def _load(self, g, key, stem):
         ip_unet = g is self.unet and self.ip_tokens      # its to_k_ip / to_v_ip come from the adapter's container, by the UNet's names
@@ -1578,6 +1583,13 @@ def check_prompt_chunks(prompt_chunks):
     if isinstance(prompt_chunks, bool) or not isinstance(prompt_chunks, (int, np.integer)) or not 1 <= prompt_chunks <= 4:
         raise ValueError(f'prompt_chunks must be an integer in [1, 4], got {prompt_chunks!r}')
     return int(prompt_chunks)
+
+
+def vae_attention_check(vae_attention):
+    """Txt2Img's vae_attention: 'auto' or 'fused' -> the fused_attn switch of the VAE graphs; anything else is a ValueError"""
+    if isinstance(vae_attention, str) and vae_attention in ('auto', 'fused'):
+        return vae_attention == 'fused'
+    raise ValueError(f"vae_attention must be 'auto' or 'fused', not {vae_attention!r}")
 
 
 def check_latent_hw(latent_hw, name='latent_hw'):
