@@ -355,6 +355,15 @@ SDOD_API int sdod_graph_set_networks(void* graph, const sdod_network_entry* entr
 SDOD_API int sdod_graph_enable_freeu(void* graph);
 SDOD_API int sdod_graph_freeu_input(void* graph, int* index);
 
+/* ---- HyperTile (tfernd/HyperTile): a switch in the same pattern -- no parameter, no input, composes with every create
+ * function.  sdod_graph_enable_hypertile (kinds UNET and CONTROLNET, before sdod_graph_finalize, tile >= 8 latent pixels, max_depth in
+ * [0, 3]; anything else is INVALID_ARGUMENT): every transformer block's self-attention (attn1) whose level the tile rule tiles --
+ * sdod_hypertile_grid (include/sdod_hip.h) on the graph's latent_h x latent_w -- runs sdod_attention_tiled_f16 inside the tiles, one
+ * launch, label attn_tiled_d<d>, in place of the attn_d<d> launch.  The grid is fixed (no random tile swap): a captured trajectory
+ * needs one.  Cross-attention is untouched.  A graph without the switch, or whose rule tiles no level, is what it was: same launch
+ * list, arena and bits. */
+SDOD_API int sdod_graph_enable_hypertile(void* graph, int tile, int max_depth);
+
 #ifdef __cplusplus
 }
 #endif

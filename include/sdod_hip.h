@@ -296,6 +296,23 @@ SDOD_API int sdod_attention_f16(const void* q, const void* k, const void* v, voi
  * created (sdod_model_config.num_heads / head_dim, include/sdod_engine.h).  Host-only. */
 SDOD_API int sdod_attention_head_dim_ok(int d);
 
+/* Tiled self-attention (HyperTile): q, k, v, out are [batch][h * w][ld] token maps and every th x tw tile of the h x w
+ * map is a softmax domain of its own -- out at a pixel = softmax(scale * q . K_tile^T) V_tile over the th * tw pixels of the pixel's
+ * tile.  Rows are read and written at their pixel positions; nothing is gathered or scattered through memory.  Self-attention only
+ * (lq = lk = h * w), no causal form.  Pointer, stride, alignment, d and scale rules are sdod_attention_f16's.  th must divide h and tw
+ * must divide w; batch * h * w must fit an int and (h * w + 260 w) * max(ldk, ldv) stay below 2^30.  Anything else is
+ * INVALID_ARGUMENT before any launch.  The kernel form is chosen exactly as sdod_attention_f16 chooses for batch * (h / th) * (w / tw)
+ * sequences of lq = lk = th * tw, so every tile's result is bit for bit what that call returns on the tile's rows gathered into a
+ * contiguous tensor, and a 1 x 1 grid (th = h, tw = w) equals it on the whole map. */
+SDOD_API int sdod_attention_tiled_f16(const void* q, const void* k, const void* v, void* out, int batch, int heads, int h, int w,
+                                      int th, int tw, int d, int ldq, int ldk, int ldv, int ldo, float scale, void* stream);
+/* HyperTile's tile rule, the one statement of it.  h x w is the level-0 token map (the latent), tile the requested tile side in
+ * latent pixels (>= 8), level the UNet level (its map is (h >> level) x (w >> level)), max_depth in [0, 3] the deepest level that is
+ * tiled.  Per axis the tile COUNT is fixed at level 0 -- nh = h / th0 with th0 the smallest divisor of h that is >= min(tile, h),
+ * likewise nw -- and kept at every level.  *th, *tw = the tile sides at `level`, (h >> level) / nh and (w >> level) / nw, or 0, 0 where
+ * the level is untiled: level > max_depth, nh * nw == 1, or nh / nw not dividing the level's sides.  Host-only. */
+SDOD_API int sdod_hypertile_grid(int h, int w, int tile, int level, int max_depth, int* th, int* tw);
+
 /* Wide single-head attention (the VAE's middle block): out[b][q][0..d) = softmax(scale * Q K^T) V for ONE head of width
  * d in {256, 512}, fp16 in and out, fp32 scores / running maximum / running sum / accumulators; the lq x lk score matrix is never
  * written anywhere.  q: [batch][lq][ldq], k: [batch][lk][ldk], v: [batch][lk][ldv], out: [batch][lq][ldo]: image b starts b * l * ld

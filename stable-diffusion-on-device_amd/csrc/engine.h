@@ -92,6 +92,9 @@ public:
     // the channel rule selects and gives the graph its parameter input, slot freeu_input() (-1 without the switch)
     void enable_freeu();
     int freeu_input() const { return freeu_ ? freeu_input_ : -1; }
+    // HyperTile (include/sdod_engine.h): enable_hypertile() before finalize() makes spatial_transformer() run attn1 inside the tiles
+    // sdod_hypertile_grid gives for its level; no parameter, no input
+    void enable_hypertile(int tile, int max_depth);
     // skip_static: the inputs marked "static across a sampler run" (UNet: the text context) are unchanged since the
     // previous execute(), so the launches that depend only on them (all cross-attention K/V projections) are skipped
     void execute(hipStream_t st, bool use_hip_graph, bool skip_static = false);
@@ -119,6 +122,8 @@ private:
     bool freeu_ = false;                 // FreeU of the UNET graph (enable_freeu()): the decoder sites run sdod_freeu_f16 ...
     int freeu_input_ = -1;               // ... on this input slot, fp32 [SDOD_FREEU_PARAMS], behind every other input
     void freeu_site(const Act& h, const Act& skip, const float* params, int stage);
+    int hypertile_ = 0;                  // HyperTile of the UNET / CONTROLNET graph (enable_hypertile()): tile side in latent pixels, 0 = off ...
+    int hypertile_depth_ = 0;            // ... and the deepest UNet level whose self-attention is tiled
     bool has_kv() const { return kind_ == SDOD_GRAPH_UNET || kind_ == SDOD_GRAPH_CONTROLNET; } // owns kv_all_ and the static K/V GEMM
     int batch_;
     int wrap_ = 0; // seamless tiling (UNET, VAE_DECODER): bit 0 = x wraps, bit 1 = y wraps; conv() turns it into sdod_gemm_desc::pad_mode
@@ -284,6 +289,9 @@ private:
     void dense_conv(sdod_dense_conv_desc d, int w, int bias);
     void attention(const f16* q, const f16* k, const f16* v, f16* out, int B, int heads, int lq, int lk, int d, int ldq,
                    int ldk, int ldv, int ldo, bool causal);
+    // self-attention inside the th x tw tiles of B [h * w][ld] token maps (sdod_attention_tiled_f16): one launch, label attn_tiled_d<d>
+    void attention_tiled(const f16* q, const f16* k, const f16* v, f16* out, int B, int heads, int h, int w, int th, int tw, int d,
+                         int ldq, int ldk, int ldv, int ldo);
 
     // ---- model blocks
     Act res_block(const std::string& pfx, const Act& x, const Act* x2, int cout, const f16* emb_all, int emb_ld, int& emb_off);
@@ -316,7 +324,7 @@ private:
     struct HeadGeom { int heads, d; };
     HeadGeom head_geometry(int C) const;
     void check_head_geometry() const; // every transformer width of a UNET / CONTROLNET graph: MC, 2 MC, 4 MC
-    Act spatial_transformer(const std::string& pfx, const Act& x, const Act& ctx);
+    Act spatial_transformer(const std::string& pfx, const Act& x, const Act& ctx, int level); // level: x is (latent >> level)
     Act unet_conv_in(const float* x_in, const float* cond_in); // input_blocks.0.0 in its three forms
     // input_blocks.1 .. 11 and middle_block.0/1/2 behind input_blocks.0 (h): the half the UNet and the ControlNet share.  hs != null
     // (UNet): every skip tensor is pushed and kept.  hs == null (ControlNet): on_skip(k, t) sees skip tensor k = 1 .. 11 when it is

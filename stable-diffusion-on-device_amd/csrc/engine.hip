@@ -1071,6 +1071,16 @@ void Graph::attention(const f16* q, const f16* k, const f16* v, f16* out, int B,
          "B" + std::to_string(B) + " h" + std::to_string(heads) + " lq" + std::to_string(lq) + " lk" + std::to_string(lk));
 }
 
+void Graph::attention_tiled(const f16* q, const f16* k, const f16* v, f16* out, int B, int heads, int h, int w, int th, int tw, int d,
+                            int ldq, int ldk, int ldv, int ldo) {
+    const float scale = 1.0f / sqrtf((float)d);
+    const double L = (double)h * w, T = (double)th * tw;
+    emit([=](hipStream_t st) { check_rc(sdod_attention_tiled_f16(q, k, v, out, B, heads, h, w, th, tw, d, ldq, ldk, ldv, ldo, scale, st)); },
+         "attn_tiled_d" + std::to_string(d), 4.0 * B * heads * L * T * d, 2.0 * B * heads * d * 4.0 * L,
+         "B" + std::to_string(B) + " h" + std::to_string(heads) + " map" + std::to_string(h) + "x" + std::to_string(w) + " grid" +
+             std::to_string(h / th) + "x" + std::to_string(w / tw) + " tile" + std::to_string(th) + "x" + std::to_string(tw));
+}
+
 // ------------------------------------------------------------------------------------------ finalize / run
 void Graph::build() {
     quant_global(); // (the UNet builder narrows it block by block: quant_rows())
@@ -1178,6 +1188,15 @@ void Graph::enable_freeu() {
     SDOD_REQUIRE(!finalized_, "enable_freeu() must be called before finalize()");
     SDOD_REQUIRE(cfg_.latent_h <= 2048 && cfg_.latent_w <= 2048, "FreeU needs latent_h and latent_w <= 2048 (sdod_freeu_f16 takes sides up to 1024)");
     freeu_ = true;
+}
+
+void Graph::enable_hypertile(int tile, int max_depth) {
+    SDOD_REQUIRE(has_kv(), "HyperTile applies to the UNET and CONTROLNET graphs only");
+    SDOD_REQUIRE(!finalized_, "enable_hypertile() must be called before finalize()");
+    SDOD_REQUIRE(tile >= 8, "HyperTile: tile must be >= 8 latent pixels");
+    SDOD_REQUIRE(max_depth >= 0 && max_depth <= 3, "HyperTile: max_depth must be in [0, 3]");
+    hypertile_ = tile;
+    hypertile_depth_ = max_depth;
 }
 
 void Graph::set_loras(const sdod_lora_entry* entries, int count, hipStream_t st) {
@@ -1755,6 +1774,14 @@ extern "C" int sdod_graph_enable_freeu(void* graph) {
     SDOD_TRY
     SDOD_REQUIRE(graph != nullptr, "null graph");
     static_cast<Graph*>(graph)->enable_freeu();
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_enable_hypertile(void* graph, int tile, int max_depth) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr, "null graph");
+    static_cast<Graph*>(graph)->enable_hypertile(tile, max_depth);
     return 0;
     SDOD_CATCH
 }

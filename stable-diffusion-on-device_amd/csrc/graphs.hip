@@ -118,7 +118,7 @@ void Graph::check_head_geometry() const {
     for (int m : {1, 2, 4}) (void)head_geometry(m * cfg_.model_channels);
 }
 
-Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& ctx) {
+Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& ctx, int level) {
     const int C = x.c, cd = ctx.c;
     const HeadGeom hg = head_geometry(C);
     const int heads = hg.heads, d = hg.d;
@@ -200,7 +200,12 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
       behind_ln(t0, l1w, l1b, o, [&](const f16* a, const GemmOpt& og) {
           linear_raw(a, rows, C, reinterpret_cast<const f16*>(group_base(gq)), C, 3 * C, qkv, og); }); }
     f16* a1 = alloc((size_t)rows * C);
-    attention(qkv, qkv + C, qkv + 2 * C, a1, B, heads, L, L, d, 3 * C, 3 * C, 3 * C, C, false);
+    // HyperTile: where the rule tiles this level attn1 runs inside the tiles, in place on the same packed rows
+    int th = 0, tw = 0;
+    if (hypertile_ > 0) check_rc(sdod_hypertile_grid(cfg_.latent_h, cfg_.latent_w, hypertile_, level, hypertile_depth_, &th, &tw));
+    if (th > 0 && (cfg_.latent_h >> level) == x.h && (cfg_.latent_w >> level) == x.w)
+        attention_tiled(qkv, qkv + C, qkv + 2 * C, a1, B, heads, x.h, x.w, th, tw, d, 3 * C, 3 * C, 3 * C, C);
+    else attention(qkv, qkv + C, qkv + 2 * C, a1, B, heads, L, L, d, 3 * C, 3 * C, 3 * C, C, false);
     release(qkv);
     Act t1 = act(B, 1, L, C);
     { GemmOpt o; o.bias = o1b; o.residual = t0.p; linear(a1, rows, C, o1w, C, t1.p, o); }
@@ -423,7 +428,7 @@ Act Graph::unet_encoder(Act h, const Act& ctx, const f16* emb_all, int emb_ld, i
             if (!hs) release_after_consumer(h); // (the block's input: tail or residual of r's, possibly still split-K, out conv)
             ch = kChMult[level] * MC;
             if (ds <= 4) {
-                Act t = spatial_transformer(pfx + ".1", r, ctx);
+                Act t = spatial_transformer(pfx + ".1", r, ctx, level);
                 release(r);
                 r = t;
             }
@@ -454,7 +459,7 @@ Act Graph::unet_encoder(Act h, const Act& ctx, const f16* emb_all, int emb_ld, i
     // middle (UNet: h is the last skip and stays on the stack until popped)
     Act r1 = res_block("middle_block.0", h, nullptr, ch, emb_all, emb_ld, emb_off);
     if (!hs) release_after_consumer(h);
-    Act t = spatial_transformer("middle_block.1", r1, ctx);
+    Act t = spatial_transformer("middle_block.1", r1, ctx, 3);
     release(r1);
     Act r2 = res_block("middle_block.2", t, nullptr, ch, emb_all, emb_ld, emb_off);
     release_after_consumer(t); // residual of r2's (possibly still split-K) out conv
@@ -597,7 +602,7 @@ void Graph::build_unet() {
             ch = kChMult[level] * MC;
             int sub = 1;
             if (ds <= 4) {
-                Act t = spatial_transformer(pfx + "." + std::to_string(sub++), r, ctx);
+                Act t = spatial_transformer(pfx + "." + std::to_string(sub++), r, ctx, level);
                 release(r);
                 r = t;
             }

@@ -166,6 +166,8 @@ def _declare(lib):
         'sdod_lokr_merge_f16': (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, c_float, c_int, c_int, P]),
         'sdod_attention_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P]),
         'sdod_attention_head_dim_ok': (c_int, [c_int]),
+        'sdod_attention_tiled_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+        'sdod_hypertile_grid': (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
         'sdod_attention_wide_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
         'sdod_attention_wide_ws_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P, c_size_t, P]),
         'sdod_attention_wide_dim_ok': (c_int, [c_int]),
@@ -254,6 +256,7 @@ HIP_SYMBOLS = [
     'sdod_loha_merge_f16', 'sdod_lokr_merge_f16',
     'sdod_lcm_step', 'sdod_guidance_features_f16',
     'sdod_attention_wide_f16', 'sdod_attention_wide_ws_f16', 'sdod_attention_wide_dim_ok', 'sdod_attention_wide_splits', 'sdod_attention_wide_ws_bytes',
+    'sdod_attention_tiled_f16', 'sdod_hypertile_grid',
 ]
 
 

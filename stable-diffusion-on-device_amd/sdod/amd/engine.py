@@ -40,6 +40,9 @@ class ModelConfig(ctypes.Structure):
     # FreeU (sdod_graph_enable_freeu, a switch on the created graph, not a configuration struct): 1 makes a UNet run the FreeU launches at
     # its decoder sites and gives it the UNet.freeu parameter input; composes with every attribute above; 0 = the graph as it was.
     freeu = 0
+    # HyperTile (sdod_graph_enable_hypertile, a switch like freeu): (tile, max_depth) makes a UNet or ControlNet run the self-attention
+    # of the levels the tile rule tiles (sdod/amd/hypertile.py) inside tiles; composes with every attribute above; None = the graph as it was.
+    hypertile = None
     _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'tiling', 'control_inputs', 'control_temb', 'regions',
                        'ip_tokens', 'freeu')
 
@@ -50,6 +53,8 @@ class ModelConfig(ctypes.Structure):
             v = int(getattr(source, n, 0))
             if v:
                 setattr(out, n, v)
+        if getattr(source, 'hypertile', None):
+            out.hypertile = tuple(source.hypertile)
         return out
 
 
@@ -139,7 +144,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_keep_base', 'sdod_graph_base_bytes', 'sdod_graph_set_loras', 'sdod_graph_create_upscaler',
     'sdod_graph_create_control', 'sdod_graph_bind_output', 'sdod_graph_create_regions',
     'sdod_graph_create_ip', 'sdod_graph_create_vision',
-    'sdod_graph_enable_freeu', 'sdod_graph_freeu_input',
+    'sdod_graph_enable_freeu', 'sdod_graph_freeu_input', 'sdod_graph_enable_hypertile',
     'sdod_graph_set_networks',
     'sdod_graph_create_lcm',
     'sdod_graph_create_vae',
@@ -187,6 +192,7 @@ def _engine():
         lib.sdod_graph_set_loras.argtypes = [P, ctypes.POINTER(LoraEntry), I, P]
         lib.sdod_graph_set_networks.argtypes = [P, ctypes.POINTER(NetworkEntry), I, P]
         lib.sdod_graph_enable_freeu.argtypes = [P]
+        lib.sdod_graph_enable_hypertile.argtypes = [P, I, I]
         lib.sdod_graph_freeu_input.argtypes = [P, ctypes.POINTER(I)]
         lib._sdod_engine_typed = True
     return lib
@@ -281,6 +287,8 @@ class Graph:
                 check(self._lib.sdod_graph_create(ctypes.byref(self._h), kind, ctypes.byref(cfg), batch))
             if kind == UNET and int(getattr(cfg, 'freeu', 0)):   # a switch on whichever graph was created above
                 self.enable_freeu()
+            if kind in (UNET, CONTROLNET) and getattr(cfg, 'hypertile', None):
+                self.enable_hypertile(*cfg.hypertile)
         self.finalized = False
 
     def _on_device(self):
@@ -349,6 +357,11 @@ class Graph:
     def enable_freeu(self):
         """before finalize(), UNET graphs only: the graph runs FreeU at its decoder sites and gets the parameter input UNet.freeu"""
         check(self._lib.sdod_graph_enable_freeu(self._h))
+        return self
+
+    def enable_hypertile(self, tile, max_depth=0):
+        """before finalize(), UNET and CONTROLNET graphs only: attn1 of every level the tile rule tiles (hypertile.grid) runs inside tiles"""
+        check(self._lib.sdod_graph_enable_hypertile(self._h, int(tile), int(max_depth)))
         return self
 
     def freeu_input(self):

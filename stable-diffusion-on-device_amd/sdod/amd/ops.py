@@ -410,6 +410,27 @@ def _rows_view(t, name):
     return ld
 
 
+def attention_tiled(q, k, v, heads, hw, tile_hw, out=None, scale=None):
+    """HyperTile self-attention (include/sdod_hip.h: sdod_attention_tiled_f16): q / k / v [B, h * w, heads * d] fp16 token maps,
+    contiguous or column slices of wider rows, hw = (h, w), tile_hw = (th, tw) with th | h and tw | w; every tile is a softmax domain
+    of its own, walked in place.  out likewise (default: a new contiguous tensor).  scale defaults to d ** -0.5."""
+    lib = _lib.hip()
+    ldq, ldk, ldv = _rows_view(q, 'q'), _rows_view(k, 'k'), _rows_view(v, 'v')
+    (h, w), (th, tw) = hw, tile_hw
+    b, l, c = q.shape
+    if k.shape != q.shape or v.shape != q.shape or l != h * w:
+        raise ValueError(f'q, k, v must all be [B, h * w, heads * d] with h * w = {h * w}, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}')
+    if out is None:
+        out = torch.empty(b, l, c, dtype=torch.float16, device=q.device)
+    ldo = _rows_view(out, 'out')
+    if out.shape != q.shape:
+        raise ValueError(f'out must be {tuple(q.shape)}, got {tuple(out.shape)}')
+    d = c // heads
+    check(lib.sdod_attention_tiled_f16(_p(q), _p(k), _p(v), _p(out), b, heads, int(h), int(w), int(th), int(tw), d, ldq, ldk, ldv, ldo,
+                                       d ** -0.5 if scale is None else scale, _stream()))
+    return out
+
+
 def attention_wide_splits(b, lq, lk, d):
     """key splits attention_wide() runs a [b, lq, d] x [b, lk, d] problem with (1 = one launch, no workspace); 0 = a shape it refuses"""
     return _lib.hip().sdod_attention_wide_splits(b, lq, lk, d)

@@ -16,6 +16,7 @@ from . import prompts as PR
 from . import regions as RG
 from . import ip_adapter as IP
 from . import freeu as FU
+from . import hypertile as HT
 from . import upscale as UP
 from . import panorama as PN
 from .host import DpmSolver
@@ -52,6 +53,7 @@ class Txt2Img:
     canvas_hw = None    # MultiDiffusion panoramas: the canvas latent's (H, W) (Txt2Img(..., canvas_hw=)), or None; canvas_vae: its decoder
     canvas_wrap = False
     canvas_vae = None
+    hypertile = None    # HyperTile: (tile, max_depth) of the UNet / ControlNet graphs' switch (Txt2Img(..., hypertile=T))
     freeu = False       # FreeU: the UNet was built with the switch and has the unet.freeu parameter input (Txt2Img(..., freeu=True))
     _pano = None        # {(oy, ox, weights kind): the window plan and its device tables}, created with its first entry
     unguided = False    # LCM: the UNet has one row per image, the conditional one (Txt2Img(..., unguided=True)): only the *_lcm entry points run
@@ -63,7 +65,7 @@ class Txt2Img:
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
                  adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False, ip_adapter=False, canvas_hw=None,
-                 canvas_wrap=False, freeu=False, unguided=False, guidance_embed=False, lora_time_modules=False, vae_attention='auto'):
+                 canvas_wrap=False, freeu=False, unguided=False, guidance_embed=False, lora_time_modules=False, vae_attention='auto', hypertile=None):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -166,12 +168,19 @@ class Txt2Img:
         vae_attention='auto' (default): every VAE graph -- the decoder, the encoders, the hires pass's and the canvas decoder -- runs its
         middle attention as it always did up to 16384 latent positions and as one fused launch (ops.attention_wide) above,
         which is what lets canvas_hw=(64, 512), latent_hw=(128, 136) or hires_hw=(160, 160) build.  'fused': the fused launch at every
-        size (no L x L score buffer in the VAE arenas).  Anything else is a ValueError before any device work."""
+        size (no L x L score buffer in the VAE arenas).  Anything else is a ValueError before any device work.
+        hypertile=T or (T, max_depth): HyperTile (sdod/amd/hypertile.py), an opt-in approximation for large images.  Every
+        UNet and ControlNet graph the pipeline builds -- the base one (and with it every canvas window), the hires pass's -- runs the
+        self-attention of the levels the tile rule tiles inside tiles of about T latent pixels a side (one attn_tiled launch in place
+        of the attn one; levels 0 .. max_depth, default 0).  A graph switch: it works with every entry point, sampler and other
+        argument.  Anything but None, an int >= 8 or such a pair with max_depth in [0, 3]: ValueError before any device work
+        (hypertile.hypertile_check).  None: nothing is constructed or sized differently."""
         fused_vae = vae_attention_check(vae_attention)
         lcm_check_build(unguided, guidance_embed, lora_time_modules, loras, cfg_split, inpaint_unet, hires_hw, adapter, controlnet, regions,
                         ip_adapter, canvas_hw)
         self.unguided, self.guidance_embed, self.lora_time_modules = bool(unguided), bool(guidance_embed), bool(lora_time_modules)
         self.freeu = FU.freeu_check_build(freeu)
+        self.hypertile = HT.hypertile_check(hypertile)
         self.prompt_chunks = check_prompt_chunks(prompt_chunks)
         latent_h, latent_w = check_latent_hw(latent_hw)
         self.canvas_hw = PN.panorama_check_build(canvas_hw, canvas_wrap, (latent_h, latent_w), cfg_split, inpaint_unet, hires_hw, adapter,
@@ -249,6 +258,9 @@ class Txt2Img:
         if self.freeu:                   # a switch on the UNet graph, whatever else it was configured with
             unet_cfg = E.copy_config(unet_cfg)
             unet_cfg.freeu = 1
+        if self.hypertile:               # likewise; the ControlNet's configuration below is a copy of this one and carries it
+            unet_cfg = E.copy_config(unet_cfg)
+            unet_cfg.hypertile = self.hypertile
         vae_cfg = self.cfg
         if self.tiling:                  # the UNet and the VAE decoder take the circular border; every other graph has no border to wrap
             unet_cfg, vae_cfg = E.copy_config(unet_cfg), E.copy_config(self.cfg)
@@ -313,7 +325,8 @@ class Txt2Img:
             self.hires = Txt2Img(state_dicts=state_dicts, models_dir=models_dir, images_per_gpu=images_per_gpu, latent_hw=hires_hw,
                                  device=device, use_hip_graph=use_hip_graph, tokenizer=None, with_text_encoder=False, model=model,
                                  with_vae=with_vae, cfg_split=False, weight_quant=weight_quant, with_vae_encoder=False, inpaint_unet=False,
-                                 prompt_chunks=prompt_chunks, loras=loras, freeu=freeu, lora_time_modules=lora_time_modules, vae_attention=vae_attention)
+                                 prompt_chunks=prompt_chunks, loras=loras, freeu=freeu, lora_time_modules=lora_time_modules, vae_attention=vae_attention,
+                                 hypertile=hypertile)
 
     def _load(self, g, key, stem):
         ip_unet = g is self.unet and self.ip_tokens      # its to_k_ip / to_v_ip come from the adapter's container, by the UNet's names
