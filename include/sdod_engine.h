@@ -261,6 +261,47 @@ typedef struct sdod_vision_config {
 } sdod_vision_config;
 SDOD_API int sdod_graph_create_vision(void** graph, int kind, const sdod_model_config* cfg, const sdod_vision_config* vision, const sdod_ip_config* ip,
                                       int batch);
+/* ---- Graph creation through one record.  sdod_graph_create_opts is the whole of graph creation: every function above is one of its
+ * spellings -- the set of kinds it accepts and a translation of its arguments into this record -- and builds the same graph from the
+ * same values.  All zero (behind `size`) is the graph sdod_graph_create has always built.  A new option is a field appended here.
+ *
+ *   option (fields)                        kinds it applies to                         excludes                  older spelling
+ *   adapter  (adapter_reps, _hint_channels, UNET reads adapter_reps, ADAPTER the other  all but wrap              _ex, _wrap
+ *             _res_blocks)                 two; ADAPTER needs them; others ignore them
+ *   wrap                                   UNET (concat_channels == 0), VAE_DECODER    all but adapter, fused_attn _wrap, _vae
+ *   upscaler (num_blocks, in_h, in_w)      UPSCALER, which needs them                  all                       _upscaler
+ *   control  (control_inputs | control_temb; UNET | TEMB; the kinds themselves         all                       _control
+ *             the kinds CONTROLNET, CONTROL_HINT)
+ *   regions                                UNET, context_len == 77 * regions           all                       _regions
+ *   ip_tokens                              UNET (context_len <= 80), IMAGE_PROJ        all but vision            _ip, _vision
+ *   vision   (image_size .. quick_gelu;    IMAGE_ENCODER (all eight), IMAGE_PROJ       all but ip_tokens         _vision
+ *             the kinds IMAGE_ENCODER, IMAGE_PROJ)  (proj_dim, and needs ip_tokens)
+ *   time_cond_proj_dim                     TEMB                                        all                       _lcm
+ *   fused_attn                             VAE_DECODER, VAE_ENCODER, VAE_ENCODER_MASKED  all but wrap            _vae
+ *
+ * Value ranges are those given at the older structs above.  Two options that exclude each other are LIBSDOD_INVALID_ARGUMENT with a
+ * message naming both, whatever the kind: exactly the pairs adapter + wrap, wrap + fused_attn and ip_tokens + vision can be asked for
+ * together, because those are the pairs the older functions could express and the only ones that are built and tested.  regions,
+ * ip_tokens and control also refuse weight_quant and concat_channels of the model configuration (control: on its own kinds and
+ * control_temb).  sdod_graph_enable_freeu and sdod_graph_enable_hypertile stay switches on the created graph and compose with all of
+ * the above.
+ * size: sizeof(sdod_graph_options) of the caller's build; any other value is INVALID_ARGUMENT.  Fields will only ever be appended, and
+ * a library that has more of them will then accept the smaller sizes of older callers and read the missing fields as zero. */
+typedef struct sdod_graph_options {
+    int size;
+    int adapter_reps, adapter_hint_channels, adapter_res_blocks; /* sdod_adapter_config */
+    int wrap;                                                    /* sdod_graph_create_wrap: bit 0 = x, bit 1 = y */
+    int num_blocks, in_h, in_w;                                  /* sdod_upscaler_config */
+    int control_inputs, control_temb;                            /* sdod_control_config */
+    int regions;                                                 /* sdod_region_config */
+    int ip_tokens;                                               /* sdod_ip_config */
+    int image_size, patch, width, layers, heads, mlp_dim, proj_dim, quick_gelu; /* sdod_vision_config */
+    int time_cond_proj_dim;                                      /* sdod_lcm_config */
+    int fused_attn;                                              /* sdod_vae_config */
+} sdod_graph_options;
+/* options == NULL is all zero.  cfg == NULL is accepted for the kinds that read no field of it, UPSCALER and IMAGE_ENCODER, and stands
+ * for sdod_model_config_sd14's values there, as in sdod_graph_create_upscaler and sdod_graph_create_vision. */
+SDOD_API int sdod_graph_create_opts(void** graph, int kind, const sdod_model_config* cfg, const sdod_graph_options* options, int batch);
 /* Before sdod_graph_finalize: output `index` of the graph is written to device_ptr (memory the caller owns, typically an input slot
  * of another graph, so that nothing is copied between the two per run) instead of a slot the graph allocates.  bytes must equal the
  * output's size and device_ptr be 256-byte aligned, else INVALID_ARGUMENT.  sdod_graph_io then reports device_ptr.  Unbound outputs

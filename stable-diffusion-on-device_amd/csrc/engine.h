@@ -69,11 +69,16 @@ struct IoSlot {
     bool owned = true; // false: an output bound to the caller's memory (bind_output)
 };
 
+// all zero behind the size field: the plain graph of its kind (include/sdod_engine.h at sdod_graph_options)
+inline sdod_graph_options plain_options() {
+    sdod_graph_options o{};
+    o.size = (int)sizeof(o);
+    return o;
+}
+
 class Graph {
 public:
-    Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg = sdod_adapter_config{0, 0, 0}, int wrap = 0,
-          const sdod_upscaler_config& ucfg = sdod_upscaler_config{0, 0, 0}, const sdod_control_config* ccfg = nullptr, int regions = 0,
-          int ip_tokens = 0, const sdod_vision_config* vcfg = nullptr, int cond_proj_dim = 0, int fused_attn = 0);
+    Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_graph_options& options);
     ~Graph();
     Graph(const Graph&) = delete;
 
@@ -108,17 +113,11 @@ private:
     enum Mode { DECLARE, DRY, REAL };
     int kind_;
     sdod_model_config cfg_;
-    sdod_adapter_config acfg_; // T2I-Adapter: all zero = no adapter inputs (UNET), required for kind ADAPTER
-    sdod_upscaler_config ucfg_; // kind UPSCALER only (sdod_graph_create_upscaler); all zero for every other kind
-    sdod_control_config ccfg_{0, 0}; // ControlNet switches of the UNET / TEMB graphs (sdod_graph_create_control); all zero = none
-    int regions_ = 0;                    // regional prompts of the UNET graph (sdod_graph_create_regions): prompts per image; 0 = none
-    const float* region_w_[4] = {};      // ... and its four weight inputs, level ds = 1, 2, 4, 8 (set by build_unet())
-    sdod_vision_config vcfg_{0, 0, 0, 0, 0, 0, 0, 0}; // kinds IMAGE_ENCODER / IMAGE_PROJ (sdod_graph_create_vision); all zero otherwise
-    int ip_tokens_ = 0;                  // image prompt of the UNET graph (sdod_graph_create_ip): image tokens per image; 0 = none
-    const float* ip_w_[4] = {};          // ... its four weight inputs [pixels][2], level ds = 1, 2, 4, 8 (set by build_unet())
+    sdod_graph_options opt_;             // how the graph was asked for (include/sdod_engine.h): all zero = the plain graph of its kind
+    void validate() const;               // every rule of creation: exclusions, each option's kinds and range, the model configuration
+    const float* region_w_[4] = {};      // regional prompts (opt_.regions): the four weight inputs, level ds = 1, 2, 4, 8 (set by build_unet())
+    const float* ip_w_[4] = {};          // image prompt (opt_.ip_tokens): its four weight inputs [pixels][2], level ds = 1, 2, 4, 8 (build_unet())
     f16* ip_kv_all_ = nullptr;           // ... and the image tokens' K / V of every transformer, [B * ip_tokens][kv_total_], persistent
-    int cond_proj_dim_ = 0;              // LCM guidance embedding of the TEMB graph (sdod_graph_create_lcm): width of the features; 0 = none
-    int fused_attn_ = 0;                 // the VAE graphs' middle attention (sdod_graph_create_vae): 1 = the fused form at every size
     bool freeu_ = false;                 // FreeU of the UNET graph (enable_freeu()): the decoder sites run sdod_freeu_f16 ...
     int freeu_input_ = -1;               // ... on this input slot, fp32 [SDOD_FREEU_PARAMS], behind every other input
     void freeu_site(const Act& h, const Act& skip, const float* params, int stage);
@@ -126,7 +125,6 @@ private:
     int hypertile_depth_ = 0;            // ... and the deepest UNet level whose self-attention is tiled
     bool has_kv() const { return kind_ == SDOD_GRAPH_UNET || kind_ == SDOD_GRAPH_CONTROLNET; } // owns kv_all_ and the static K/V GEMM
     int batch_;
-    int wrap_ = 0; // seamless tiling (UNET, VAE_DECODER): bit 0 = x wraps, bit 1 = y wraps; conv() turns it into sdod_gemm_desc::pad_mode
     Mode mode_ = DECLARE;
     bool finalized_ = false;
 

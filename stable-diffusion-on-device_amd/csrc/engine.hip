@@ -37,87 +37,11 @@ static void parallel_for(int64_t n, F&& fn) {
 }
 
 // ------------------------------------------------------------------------------------------ lifecycle
-Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_adapter_config& acfg, int wrap, const sdod_upscaler_config& ucfg,
-             const sdod_control_config* ccfg, int regions, int ip_tokens, const sdod_vision_config* vcfg, int cond_proj_dim, int fused_attn)
-    : kind_(kind), cfg_(cfg), acfg_(acfg), ucfg_(ucfg), regions_(regions), ip_tokens_(ip_tokens), cond_proj_dim_(cond_proj_dim),
-      fused_attn_(fused_attn), batch_(batch), wrap_(wrap) {
-    SDOD_REQUIRE(fused_attn == 0 || fused_attn == 1, "fused_attn must be 0 or 1");
-    if (fused_attn) {
-        SDOD_REQUIRE(kind == SDOD_GRAPH_VAE_DECODER || kind == SDOD_GRAPH_VAE_ENCODER || kind == SDOD_GRAPH_VAE_ENCODER_MASKED,
-                     "fused_attn applies to the VAE_DECODER, VAE_ENCODER and VAE_ENCODER_MASKED graphs only");
-        SDOD_REQUIRE(cfg.vae_channels > 0 && cfg.vae_channels <= 1024 && sdod_attention_wide_dim_ok(4 * cfg.vae_channels),
-                     "fused_attn: vae_channels must be 64 or 128 (the wide attention kernel takes 4 * vae_channels = 256 or 512)");
-    }
-    if (cond_proj_dim != 0) {
-        SDOD_REQUIRE(kind == SDOD_GRAPH_TEMB, "time_cond_proj_dim applies to the TEMB graph only");
-        SDOD_REQUIRE(cond_proj_dim > 0 && cond_proj_dim <= 4096 && cond_proj_dim % 16 == 0, "time_cond_proj_dim must be a positive multiple of 16 (at most 4096)");
-        SDOD_REQUIRE(!(ccfg && ccfg->control_temb), "a ControlNet's time conditioning (control_temb) takes no time_cond_proj_dim");
-        SDOD_REQUIRE(cfg.weight_quant == 0 || cond_proj_dim % 64 == 0, "time_cond_proj_dim with uint8 weights must be a multiple of 64");
-    }
-    SDOD_REQUIRE(ip_tokens == 0 || ((kind == SDOD_GRAPH_UNET || kind == SDOD_GRAPH_IMAGE_PROJ) && ip_tokens >= 1 && ip_tokens <= 16 && regions == 0),
-                 "ip_tokens: the UNET and IMAGE_PROJ graphs only, 1 .. 16, not with regions");
-    const bool vision_kind = kind == SDOD_GRAPH_IMAGE_ENCODER || kind == SDOD_GRAPH_IMAGE_PROJ;
-    SDOD_REQUIRE(vision_kind == (vcfg != nullptr), "the IMAGE_ENCODER and IMAGE_PROJ graphs, and only they, are created by sdod_graph_create_vision");
-    if (vcfg) {
-        vcfg_ = *vcfg;
-        cfg_.weight_quant = 0; // always fp16 weights
-        SDOD_REQUIRE(vcfg_.proj_dim >= 64 && vcfg_.proj_dim <= 4096 && vcfg_.proj_dim % 64 == 0, "proj_dim must be a multiple of 64 in [64, 4096]");
-        if (kind == SDOD_GRAPH_IMAGE_ENCODER) {
-            SDOD_REQUIRE(vcfg_.patch >= 1 && vcfg_.patch <= 64 && vcfg_.image_size >= vcfg_.patch && vcfg_.image_size <= 1024 && vcfg_.image_size % vcfg_.patch == 0,
-                         "image_size must be a multiple of patch (patch <= 64, image_size <= 1024)");
-            SDOD_REQUIRE(vcfg_.width >= 64 && vcfg_.width <= 3072 && vcfg_.width % 64 == 0 && vcfg_.mlp_dim >= 64 && vcfg_.mlp_dim % 64 == 0 && vcfg_.mlp_dim <= 16384,
-                         "width and mlp_dim must be multiples of 64 (width <= 3072, mlp_dim <= 16384)");
-            SDOD_REQUIRE(vcfg_.layers >= 1 && vcfg_.layers <= 64 && vcfg_.heads >= 1 && vcfg_.width % vcfg_.heads == 0 &&
-                             (vcfg_.width / vcfg_.heads == 64 || vcfg_.width / vcfg_.heads == 80),
-                         "layers in [1, 64]; the head dim width / heads must be 64 or 80");
-            SDOD_REQUIRE(vcfg_.quick_gelu == 0 || vcfg_.quick_gelu == 1, "quick_gelu must be 0 or 1");
-        } else {
-            SDOD_REQUIRE(ip_tokens >= 1, "the IMAGE_PROJ graph needs ip_tokens");
-        }
-    }
-    SDOD_REQUIRE(regions == 0 || (kind == SDOD_GRAPH_UNET && regions >= 2 && regions <= 4), "regions: the UNET graph only, 2 .. 4");
-    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_IMAGE_PROJ, "unknown graph kind");
-    const bool control_kind = kind == SDOD_GRAPH_CONTROLNET || kind == SDOD_GRAPH_CONTROL_HINT;
-    SDOD_REQUIRE(!control_kind || ccfg, "the CONTROLNET and CONTROL_HINT graphs are created by sdod_graph_create_control");
-    if (ccfg) {
-        ccfg_ = *ccfg;
-        SDOD_REQUIRE((ccfg_.control_inputs == 0 || ccfg_.control_inputs == 1) && (ccfg_.control_temb == 0 || ccfg_.control_temb == 1),
-                     "control_inputs and control_temb must be 0 or 1");
-        SDOD_REQUIRE(ccfg_.control_inputs == 0 || kind == SDOD_GRAPH_UNET, "control_inputs applies to the UNET graph only");
-        SDOD_REQUIRE(ccfg_.control_temb == 0 || kind == SDOD_GRAPH_TEMB, "control_temb applies to the TEMB graph only");
-        if (control_kind || ccfg_.control_temb) {
-            SDOD_REQUIRE(cfg.concat_channels == 0 && cfg.weight_quant == 0, "a control graph takes no concat_channels and no weight_quant");
-            SDOD_REQUIRE(kind != SDOD_GRAPH_CONTROLNET || batch % 2 == 0, "the CONTROLNET graph needs an even batch (the two guidance halves)");
-        }
-    }
-    if (kind == SDOD_GRAPH_UPSCALER) {
-        SDOD_REQUIRE(ucfg.num_blocks != 0 || ucfg.in_h != 0 || ucfg.in_w != 0, "the UPSCALER graph is created by sdod_graph_create_upscaler");
-        SDOD_REQUIRE(ucfg.num_blocks >= 1 && ucfg.num_blocks <= 23, "num_blocks must be in [1, 23]");
-        SDOD_REQUIRE(ucfg.in_h >= 8 && ucfg.in_h <= 1024 && ucfg.in_h % 8 == 0 && ucfg.in_w >= 8 && ucfg.in_w <= 1024 && ucfg.in_w % 8 == 0,
-                     "in_h and in_w must be multiples of 8 in [8, 1024]");
-        cfg_.weight_quant = 0; // the upscaler's weights are always fp16
-    } else {
-        SDOD_REQUIRE(ucfg.num_blocks == 0 && ucfg.in_h == 0 && ucfg.in_w == 0, "an upscaler configuration needs kind SDOD_GRAPH_UPSCALER");
-    }
-    SDOD_REQUIRE(batch > 0 && batch <= 64, "batch must be in [1, 64]");
-    SDOD_REQUIRE(cfg.model_channels > 0 && cfg.model_channels % 64 == 0, "model_channels must be a multiple of 64");
-    SDOD_REQUIRE(cfg.context_dim % 64 == 0, "context_dim must be a multiple of 64");
-    // the kinds that build transformers: one of num_heads / head_dim decides, and only a geometry some attention kernel runs
-    if (kind == SDOD_GRAPH_UNET || kind == SDOD_GRAPH_CONTROLNET) check_head_geometry();
-    SDOD_REQUIRE(cfg.context_len >= 1 && cfg.context_len <= 4096, "context_len must be in [1, 4096]");
-    SDOD_REQUIRE(cfg.concat_channels >= 0, "concat_channels must not be negative");
-    SDOD_REQUIRE(acfg.adapter_reps >= 0 && acfg.adapter_reps <= 2, "adapter_reps must be 0, 1 or 2");
-    SDOD_REQUIRE(wrap >= 0 && wrap <= 3, "wrap must be 0 .. 3 (bit 0 = x, bit 1 = y)");
-    if (wrap != 0) // the encoder, adapter and inpainting input convolutions keep their zero border
-        SDOD_REQUIRE((kind == SDOD_GRAPH_UNET || kind == SDOD_GRAPH_VAE_DECODER) && cfg.concat_channels == 0,
-                     "wrap applies to the UNET (without concat_channels) and VAE_DECODER graphs only");
-    if (kind == SDOD_GRAPH_UNET && acfg.adapter_reps > 0)
-        SDOD_REQUIRE(batch % acfg.adapter_reps == 0, "adapter_reps must divide the batch");
-    if (kind == SDOD_GRAPH_ADAPTER) {
-        SDOD_REQUIRE(acfg.adapter_hint_channels == 1 || acfg.adapter_hint_channels == 3, "adapter_hint_channels must be 1 or 3");
-        SDOD_REQUIRE(acfg.adapter_res_blocks >= 0 && acfg.adapter_res_blocks <= 8, "adapter_res_blocks must be in [1, 8] (0 = 2)");
-        cfg_.weight_quant = 0; // the adapter's weights are always fp16
-    }
+Graph::Graph(int kind, const sdod_model_config& cfg, int batch, const sdod_graph_options& options)
+    : kind_(kind), cfg_(cfg), opt_(options), batch_(batch) {
+    validate();
+    if (kind == SDOD_GRAPH_IMAGE_ENCODER || kind == SDOD_GRAPH_IMAGE_PROJ || kind == SDOD_GRAPH_UPSCALER || kind == SDOD_GRAPH_ADAPTER)
+        cfg_.weight_quant = 0; // these kinds always keep fp16 weights
     mode_ = DECLARE;
     arena_reset();
     build();
@@ -145,6 +69,105 @@ Graph::~Graph() {
     (void)hipFree(kv_all_);
     (void)hipFree(ip_kv_all_);
     for (void* d : derived_) (void)hipFree(d);
+}
+
+// Every rule of graph creation, in one place (the table at sdod_graph_options, include/sdod_engine.h): the option groups that exclude
+// each other, then per option the kinds it applies to and its range, then the model configuration.  The create functions of the C
+// ABI add nothing to it but the kinds each of them accepts.
+void Graph::validate() const {
+    const int kind = kind_, batch = batch_;
+    const sdod_model_config& cfg = cfg_;
+    const sdod_graph_options& o = opt_;
+    SDOD_REQUIRE(o.size == (int)sizeof(sdod_graph_options), "sdod_graph_options.size must be sizeof(sdod_graph_options)");
+    const bool vision_kind = kind == SDOD_GRAPH_IMAGE_ENCODER || kind == SDOD_GRAPH_IMAGE_PROJ;
+    const bool control_kind = kind == SDOD_GRAPH_CONTROLNET || kind == SDOD_GRAPH_CONTROL_HINT;
+    const bool upscaler = o.num_blocks != 0 || o.in_h != 0 || o.in_w != 0;
+    const bool vision = o.image_size != 0 || o.patch != 0 || o.width != 0 || o.layers != 0 || o.heads != 0 || o.mlp_dim != 0 || o.proj_dim != 0 ||
+                        o.quick_gelu != 0;
+    // the groups, and the only pairs that one of the create functions has ever been able to ask for together
+    enum { A, W, U, C, L, F, R, I, V, GROUPS };
+    const struct { const char* name; bool set; } group[GROUPS] = {
+        {"adapter", o.adapter_reps != 0 || o.adapter_hint_channels != 0 || o.adapter_res_blocks != 0}, {"wrap", o.wrap != 0}, {"upscaler", upscaler},
+        {"control", control_kind || o.control_inputs != 0 || o.control_temb != 0}, {"time_cond_proj_dim", o.time_cond_proj_dim != 0},
+        {"fused_attn", o.fused_attn != 0}, {"regions", o.regions != 0}, {"ip_tokens", o.ip_tokens != 0}, {"vision", vision_kind || vision}};
+    for (int i = 0; i < GROUPS; ++i)
+        for (int j = i + 1; j < GROUPS; ++j) {
+            const bool together = (i == A && j == W) || (i == W && j == F) || (i == I && j == V);
+            SDOD_REQUIRE(together || !(group[i].set && group[j].set),
+                         std::string("the options ") + group[i].name + " and " + group[j].name + " exclude each other");
+        }
+    SDOD_REQUIRE(o.fused_attn == 0 || o.fused_attn == 1, "fused_attn must be 0 or 1");
+    if (o.fused_attn) {
+        SDOD_REQUIRE(kind == SDOD_GRAPH_VAE_DECODER || kind == SDOD_GRAPH_VAE_ENCODER || kind == SDOD_GRAPH_VAE_ENCODER_MASKED,
+                     "fused_attn applies to the VAE_DECODER, VAE_ENCODER and VAE_ENCODER_MASKED graphs only");
+        SDOD_REQUIRE(cfg.vae_channels > 0 && cfg.vae_channels <= 1024 && sdod_attention_wide_dim_ok(4 * cfg.vae_channels),
+                     "fused_attn: vae_channels must be 64 or 128 (the wide attention kernel takes 4 * vae_channels = 256 or 512)");
+    }
+    if (o.time_cond_proj_dim != 0) {
+        SDOD_REQUIRE(kind == SDOD_GRAPH_TEMB, "time_cond_proj_dim applies to the TEMB graph only");
+        SDOD_REQUIRE(o.time_cond_proj_dim > 0 && o.time_cond_proj_dim <= 4096 && o.time_cond_proj_dim % 16 == 0,
+                     "time_cond_proj_dim must be a positive multiple of 16 (at most 4096)");
+        SDOD_REQUIRE(cfg.weight_quant == 0 || o.time_cond_proj_dim % 64 == 0, "time_cond_proj_dim with uint8 weights must be a multiple of 64");
+    }
+    SDOD_REQUIRE(o.ip_tokens == 0 || ((kind == SDOD_GRAPH_UNET || kind == SDOD_GRAPH_IMAGE_PROJ) && o.ip_tokens >= 1 && o.ip_tokens <= 16),
+                 "ip_tokens: the UNET and IMAGE_PROJ graphs only, 1 .. 16");
+    if (o.ip_tokens != 0 && kind == SDOD_GRAPH_UNET) {
+        SDOD_REQUIRE(cfg.weight_quant == 0 && cfg.concat_channels == 0, "image prompts take no weight_quant and no concat_channels");
+        SDOD_REQUIRE(cfg.context_len <= 80, "image prompts: context_len must be <= 80");
+    }
+    SDOD_REQUIRE(vision_kind || !vision, "a vision configuration needs kind SDOD_GRAPH_IMAGE_ENCODER or SDOD_GRAPH_IMAGE_PROJ");
+    if (vision_kind) {
+        SDOD_REQUIRE(o.proj_dim >= 64 && o.proj_dim <= 4096 && o.proj_dim % 64 == 0, "proj_dim must be a multiple of 64 in [64, 4096]");
+        if (kind == SDOD_GRAPH_IMAGE_ENCODER) {
+            SDOD_REQUIRE(o.patch >= 1 && o.patch <= 64 && o.image_size >= o.patch && o.image_size <= 1024 && o.image_size % o.patch == 0,
+                         "image_size must be a multiple of patch (patch <= 64, image_size <= 1024)");
+            SDOD_REQUIRE(o.width >= 64 && o.width <= 3072 && o.width % 64 == 0 && o.mlp_dim >= 64 && o.mlp_dim % 64 == 0 && o.mlp_dim <= 16384,
+                         "width and mlp_dim must be multiples of 64 (width <= 3072, mlp_dim <= 16384)");
+            SDOD_REQUIRE(o.layers >= 1 && o.layers <= 64 && o.heads >= 1 && o.width % o.heads == 0 &&
+                             (o.width / o.heads == 64 || o.width / o.heads == 80),
+                         "layers in [1, 64]; the head dim width / heads must be 64 or 80");
+            SDOD_REQUIRE(o.quick_gelu == 0 || o.quick_gelu == 1, "quick_gelu must be 0 or 1");
+        } else {
+            SDOD_REQUIRE(o.ip_tokens >= 1, "the IMAGE_PROJ graph needs ip_tokens");
+        }
+    }
+    SDOD_REQUIRE(o.regions == 0 || (kind == SDOD_GRAPH_UNET && o.regions >= 2 && o.regions <= 4), "regions: the UNET graph only, 2 .. 4");
+    SDOD_REQUIRE(o.regions == 0 || cfg.context_len == 77 * o.regions, "regional prompts: context_len must be 77 * regions");
+    SDOD_REQUIRE(kind >= SDOD_GRAPH_UNET && kind <= SDOD_GRAPH_IMAGE_PROJ, "unknown graph kind");
+    SDOD_REQUIRE((o.control_inputs == 0 || o.control_inputs == 1) && (o.control_temb == 0 || o.control_temb == 1),
+                 "control_inputs and control_temb must be 0 or 1");
+    SDOD_REQUIRE(o.control_inputs == 0 || kind == SDOD_GRAPH_UNET, "control_inputs applies to the UNET graph only");
+    SDOD_REQUIRE(o.control_temb == 0 || kind == SDOD_GRAPH_TEMB, "control_temb applies to the TEMB graph only");
+    if (control_kind || o.control_temb) {
+        SDOD_REQUIRE(cfg.concat_channels == 0 && cfg.weight_quant == 0, "a control graph takes no concat_channels and no weight_quant");
+        SDOD_REQUIRE(kind != SDOD_GRAPH_CONTROLNET || batch % 2 == 0, "the CONTROLNET graph needs an even batch (the two guidance halves)");
+    }
+    if (kind == SDOD_GRAPH_UPSCALER) {
+        SDOD_REQUIRE(upscaler, "the UPSCALER graph is created by sdod_graph_create_upscaler");
+        SDOD_REQUIRE(o.num_blocks >= 1 && o.num_blocks <= 23, "num_blocks must be in [1, 23]");
+        SDOD_REQUIRE(o.in_h >= 8 && o.in_h <= 1024 && o.in_h % 8 == 0 && o.in_w >= 8 && o.in_w <= 1024 && o.in_w % 8 == 0,
+                     "in_h and in_w must be multiples of 8 in [8, 1024]");
+    } else {
+        SDOD_REQUIRE(!upscaler, "an upscaler configuration needs kind SDOD_GRAPH_UPSCALER");
+    }
+    SDOD_REQUIRE(batch > 0 && batch <= 64, "batch must be in [1, 64]");
+    SDOD_REQUIRE(cfg.model_channels > 0 && cfg.model_channels % 64 == 0, "model_channels must be a multiple of 64");
+    SDOD_REQUIRE(cfg.context_dim % 64 == 0, "context_dim must be a multiple of 64");
+    // the kinds that build transformers: one of num_heads / head_dim decides, and only a geometry some attention kernel runs
+    if (kind == SDOD_GRAPH_UNET || kind == SDOD_GRAPH_CONTROLNET) check_head_geometry();
+    SDOD_REQUIRE(cfg.context_len >= 1 && cfg.context_len <= 4096, "context_len must be in [1, 4096]");
+    SDOD_REQUIRE(cfg.concat_channels >= 0, "concat_channels must not be negative");
+    SDOD_REQUIRE(o.adapter_reps >= 0 && o.adapter_reps <= 2, "adapter_reps must be 0, 1 or 2");
+    SDOD_REQUIRE(o.wrap >= 0 && o.wrap <= 3, "wrap must be 0 .. 3 (bit 0 = x, bit 1 = y)");
+    if (o.wrap != 0) // the encoder, adapter and inpainting input convolutions keep their zero border
+        SDOD_REQUIRE((kind == SDOD_GRAPH_UNET || kind == SDOD_GRAPH_VAE_DECODER) && cfg.concat_channels == 0,
+                     "wrap applies to the UNET (without concat_channels) and VAE_DECODER graphs only");
+    if (kind == SDOD_GRAPH_UNET && o.adapter_reps > 0)
+        SDOD_REQUIRE(batch % o.adapter_reps == 0, "adapter_reps must divide the batch");
+    if (kind == SDOD_GRAPH_ADAPTER) {
+        SDOD_REQUIRE(o.adapter_hint_channels == 1 || o.adapter_hint_channels == 3, "adapter_hint_channels must be 1 or 3");
+        SDOD_REQUIRE(o.adapter_res_blocks >= 0 && o.adapter_res_blocks <= 8, "adapter_res_blocks must be in [1, 8] (0 = 2)");
+    }
 }
 
 // ------------------------------------------------------------------------------------------ parameters
@@ -978,7 +1001,7 @@ Act Graph::conv(const Act& x, const Act* x2, int w, int cout, int ksize, int str
     const int ups = upsample ? 1 : 0;
     const int hup = x.h << ups, wup = x.w << ups;
     // seamless tiling: every 3x3 symmetric-pad convolution of a wrapped graph takes the circular border on the wrapped axes
-    const int pad_mode = o.pad_mode == 0 && ksize == 3 && wrap_ != 0 ? (wrap_ == 3 ? 2 : wrap_ == 1 ? 3 : 4) : o.pad_mode;
+    const int pad_mode = o.pad_mode == 0 && ksize == 3 && opt_.wrap != 0 ? (opt_.wrap == 3 ? 2 : opt_.wrap == 1 ? 3 : 4) : o.pad_mode;
     const int pad_sum = pad_mode == 1 ? 1 : 2 * (ksize / 2); // pad_mode 1: ldm's encoder Downsample, F.pad(x, (0, 1, 0, 1)) + pad 0
     const int ho = (hup + pad_sum - ksize) / stride + 1, wo = (wup + pad_sum - ksize) / stride + 1;
     Act y;
@@ -1127,8 +1150,8 @@ void Graph::finalize() {
     SDOD_HIP_CHECK(hipMemset(fix_counters_, 0, sdod_gemm_fixup_counters() * sizeof(unsigned)));
     if (has_kv() && kv_total_ > 0)
         SDOD_HIP_CHECK(hipMalloc((void**)&kv_all_, (size_t)batch_ * cfg_.context_len * kv_total_ * sizeof(f16)));
-    if (ip_tokens_ > 0 && kv_total_ > 0)
-        SDOD_HIP_CHECK(hipMalloc((void**)&ip_kv_all_, (size_t)batch_ * ip_tokens_ * kv_total_ * sizeof(f16)));
+    if (opt_.ip_tokens > 0 && kv_total_ > 0)
+        SDOD_HIP_CHECK(hipMalloc((void**)&ip_kv_all_, (size_t)batch_ * opt_.ip_tokens * kv_total_ * sizeof(f16)));
     mode_ = REAL;
     arena_reset();
     ops_.clear();
@@ -1494,106 +1517,145 @@ extern "C" void sdod_model_config_sd21(sdod_model_config* cfg) {
     cfg->text_heads = 16;
 }
 
-extern "C" int sdod_graph_create(void** graph, int kind, const sdod_model_config* cfg, int batch) {
-    SDOD_TRY
-    SDOD_REQUIRE(graph != nullptr && cfg != nullptr, "null argument");
+// ---- graph creation.  sdod_graph_create_opts is the whole of it; each older function is the set of kinds it accepts and a translation
+// of its arguments into the record.  Graph::validate() holds every other rule.
+using sdod::plain_options;
+
+// every create function starts here: the handle is null until a graph exists
+static void begin_create(void** graph, bool args = true) {
+    SDOD_REQUIRE(graph != nullptr && args, "null argument");
     *graph = nullptr;
-    *graph = new Graph(kind, *cfg, batch);
+}
+
+// the common path.  An absent model configuration is SD 1.4's, for the two kinds that read no field of it
+static void create(void** graph, int kind, const sdod_model_config* cfg, const sdod_graph_options& options, int batch) {
+    sdod_model_config base{};
+    sdod_model_config_sd14(&base);
+    SDOD_REQUIRE(cfg != nullptr || kind == SDOD_GRAPH_UPSCALER || kind == SDOD_GRAPH_IMAGE_ENCODER, "null argument");
+    *graph = new Graph(kind, cfg ? *cfg : base, batch, options);
+}
+
+// the kinds that the functions older than they are refuse, in the words they have always used
+static void refuse_vision_kinds(int kind) {
+    SDOD_REQUIRE(kind != SDOD_GRAPH_IMAGE_ENCODER && kind != SDOD_GRAPH_IMAGE_PROJ,
+                 "the IMAGE_ENCODER and IMAGE_PROJ graphs, and only they, are created by sdod_graph_create_vision");
+}
+static void refuse_control_kinds(int kind) {
+    SDOD_REQUIRE(kind != SDOD_GRAPH_CONTROLNET && kind != SDOD_GRAPH_CONTROL_HINT,
+                 "the CONTROLNET and CONTROL_HINT graphs are created by sdod_graph_create_control");
+}
+static void set_adapter(sdod_graph_options& o, const sdod_adapter_config* adapter) {
+    if (!adapter) return;
+    o.adapter_reps = adapter->adapter_reps;
+    o.adapter_hint_channels = adapter->adapter_hint_channels;
+    o.adapter_res_blocks = adapter->adapter_res_blocks;
+}
+
+extern "C" int sdod_graph_create_opts(void** graph, int kind, const sdod_model_config* cfg, const sdod_graph_options* options, int batch) {
+    SDOD_TRY
+    begin_create(graph);
+    create(graph, kind, cfg, options ? *options : plain_options(), batch);
     return 0;
     SDOD_CATCH
 }
 
+extern "C" int sdod_graph_create(void** graph, int kind, const sdod_model_config* cfg, int batch) {
+    return sdod_graph_create_wrap(graph, kind, cfg, nullptr, 0, batch);
+}
+
 extern "C" int sdod_graph_create_ex(void** graph, int kind, const sdod_model_config* cfg, const sdod_adapter_config* adapter, int batch) {
-    SDOD_TRY
-    SDOD_REQUIRE(graph != nullptr && cfg != nullptr, "null argument");
-    *graph = nullptr;
-    *graph = new Graph(kind, *cfg, batch, adapter ? *adapter : sdod_adapter_config{0, 0, 0});
-    return 0;
-    SDOD_CATCH
+    return sdod_graph_create_wrap(graph, kind, cfg, adapter, 0, batch);
 }
 
 extern "C" int sdod_graph_create_wrap(void** graph, int kind, const sdod_model_config* cfg, const sdod_adapter_config* adapter, int wrap,
                                       int batch) {
     SDOD_TRY
-    SDOD_REQUIRE(graph != nullptr && cfg != nullptr, "null argument");
-    *graph = nullptr;
-    *graph = new Graph(kind, *cfg, batch, adapter ? *adapter : sdod_adapter_config{0, 0, 0}, wrap);
+    begin_create(graph, cfg != nullptr);
+    refuse_vision_kinds(kind);
+    refuse_control_kinds(kind);
+    sdod_graph_options o = plain_options();
+    set_adapter(o, adapter);
+    o.wrap = wrap;
+    create(graph, kind, cfg, o, batch);
     return 0;
     SDOD_CATCH
 }
 
 extern "C" int sdod_graph_create_upscaler(void** graph, const sdod_upscaler_config* ucfg, int batch) {
     SDOD_TRY
-    SDOD_REQUIRE(graph != nullptr, "null argument");
-    *graph = nullptr;
+    begin_create(graph);
     SDOD_REQUIRE(ucfg != nullptr, "null upscaler configuration");
-    sdod_model_config cfg{};
-    sdod_model_config_sd14(&cfg); // (no field applies to this kind; the constructor's common checks want a valid one)
-    *graph = new Graph(SDOD_GRAPH_UPSCALER, cfg, batch, sdod_adapter_config{0, 0, 0}, 0, *ucfg);
+    sdod_graph_options o = plain_options();
+    o.num_blocks = ucfg->num_blocks;
+    o.in_h = ucfg->in_h;
+    o.in_w = ucfg->in_w;
+    create(graph, SDOD_GRAPH_UPSCALER, nullptr, o, batch);
     return 0;
     SDOD_CATCH
 }
 
 extern "C" int sdod_graph_create_control(void** graph, int kind, const sdod_model_config* cfg, const sdod_control_config* control, int batch) {
     SDOD_TRY
-    SDOD_REQUIRE(graph && cfg, "null argument");
+    begin_create(graph, cfg != nullptr);
     SDOD_REQUIRE(kind != SDOD_GRAPH_UPSCALER && kind != SDOD_GRAPH_ADAPTER, "this kind has a create function of its own");
-    const sdod_control_config none{0, 0};
-    *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, control ? control : &none);
+    refuse_vision_kinds(kind);
+    sdod_graph_options o = plain_options();
+    if (control) { // (NULL = zeros: the control kinds need no switch)
+        o.control_inputs = control->control_inputs;
+        o.control_temb = control->control_temb;
+    }
+    create(graph, kind, cfg, o, batch);
     return 0;
     SDOD_CATCH
 }
 
 extern "C" int sdod_graph_create_lcm(void** graph, int kind, const sdod_model_config* cfg, const sdod_lcm_config* lcm, int batch) {
     SDOD_TRY
-    SDOD_REQUIRE(graph && cfg, "null argument");
-    *graph = nullptr;
+    begin_create(graph, cfg != nullptr);
     SDOD_REQUIRE(kind != SDOD_GRAPH_UPSCALER && kind != SDOD_GRAPH_ADAPTER && kind != SDOD_GRAPH_CONTROLNET && kind != SDOD_GRAPH_CONTROL_HINT &&
                      kind != SDOD_GRAPH_IMAGE_ENCODER && kind != SDOD_GRAPH_IMAGE_PROJ, "this graph kind has a create function of its own");
-    *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, nullptr, 0, 0, nullptr,
-                       lcm ? lcm->time_cond_proj_dim : 0);
+    sdod_graph_options o = plain_options();
+    if (lcm) o.time_cond_proj_dim = lcm->time_cond_proj_dim; // (NULL or 0 = the plain graph)
+    create(graph, kind, cfg, o, batch);
     return 0;
     SDOD_CATCH
 }
 
 extern "C" int sdod_graph_create_vae(void** graph, int kind, const sdod_model_config* cfg, int wrap, const sdod_vae_config* vae, int batch) {
     SDOD_TRY
-    SDOD_REQUIRE(graph && cfg, "null argument");
-    *graph = nullptr;
+    begin_create(graph, cfg != nullptr);
     SDOD_REQUIRE(kind == SDOD_GRAPH_VAE_DECODER || kind == SDOD_GRAPH_VAE_ENCODER || kind == SDOD_GRAPH_VAE_ENCODER_MASKED,
                  "kind must be SDOD_GRAPH_VAE_DECODER, SDOD_GRAPH_VAE_ENCODER or SDOD_GRAPH_VAE_ENCODER_MASKED");
-    *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, wrap, sdod_upscaler_config{0, 0, 0}, nullptr, 0, 0, nullptr, 0,
-                       vae ? vae->fused_attn : 0);
+    sdod_graph_options o = plain_options();
+    o.wrap = wrap;
+    if (vae) o.fused_attn = vae->fused_attn;
+    create(graph, kind, cfg, o, batch);
     return 0;
     SDOD_CATCH
 }
 
 extern "C" int sdod_graph_create_regions(void** graph, int kind, const sdod_model_config* cfg, const sdod_region_config* regions, int batch) {
     SDOD_TRY
-    SDOD_REQUIRE(graph && cfg, "null argument");
-    *graph = nullptr;
+    begin_create(graph, cfg != nullptr);
     SDOD_REQUIRE(regions != nullptr && kind == SDOD_GRAPH_UNET, "regional prompts: a region configuration and kind SDOD_GRAPH_UNET");
-    SDOD_REQUIRE(regions->regions >= 2 && regions->regions <= 4, "regions must be in [2, 4]");
-    SDOD_REQUIRE(cfg->context_len == 77 * regions->regions, "regional prompts: context_len must be 77 * regions");
-    *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, nullptr, regions->regions);
+    SDOD_REQUIRE(regions->regions >= 2 && regions->regions <= 4, "regions must be in [2, 4]"); // (no "0 = plain" here)
+    sdod_graph_options o = plain_options();
+    o.regions = regions->regions;
+    create(graph, kind, cfg, o, batch);
     return 0;
     SDOD_CATCH
 }
 
 extern "C" int sdod_graph_create_ip(void** graph, int kind, const sdod_model_config* cfg, const sdod_ip_config* ip, int batch) {
     SDOD_TRY
-    SDOD_REQUIRE(graph && cfg, "null argument");
-    *graph = nullptr;
+    begin_create(graph, cfg != nullptr);
     SDOD_REQUIRE(kind != SDOD_GRAPH_UPSCALER && kind != SDOD_GRAPH_ADAPTER && kind != SDOD_GRAPH_CONTROLNET && kind != SDOD_GRAPH_CONTROL_HINT,
                  "this graph kind has a create function of its own");
-    const int T = ip ? ip->ip_tokens : 0;
-    if (T != 0) {
-        SDOD_REQUIRE(kind == SDOD_GRAPH_UNET, "image prompts: kind SDOD_GRAPH_UNET");
-        SDOD_REQUIRE(T >= 1 && T <= 16, "ip_tokens must be in [1, 16]");
-        SDOD_REQUIRE(cfg->weight_quant == 0 && cfg->concat_channels == 0, "image prompts take no weight_quant and no concat_channels");
-        SDOD_REQUIRE(cfg->context_len <= 80, "image prompts: context_len must be <= 80");
-    }
-    *graph = new Graph(kind, *cfg, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, nullptr, 0, T);
+    sdod_graph_options o = plain_options();
+    if (ip) o.ip_tokens = ip->ip_tokens; // (NULL or 0 = the plain graph)
+    SDOD_REQUIRE(o.ip_tokens == 0 || kind == SDOD_GRAPH_UNET, "image prompts: kind SDOD_GRAPH_UNET");
+    refuse_vision_kinds(kind);
+    create(graph, kind, cfg, o, batch);
     return 0;
     SDOD_CATCH
 }
@@ -1601,16 +1663,21 @@ extern "C" int sdod_graph_create_ip(void** graph, int kind, const sdod_model_con
 extern "C" int sdod_graph_create_vision(void** graph, int kind, const sdod_model_config* cfg, const sdod_vision_config* vision, const sdod_ip_config* ip,
                                         int batch) {
     SDOD_TRY
-    SDOD_REQUIRE(graph, "null argument");
-    *graph = nullptr;
+    begin_create(graph);
     SDOD_REQUIRE(vision && (kind == SDOD_GRAPH_IMAGE_ENCODER || kind == SDOD_GRAPH_IMAGE_PROJ),
                  "a vision configuration and kind SDOD_GRAPH_IMAGE_ENCODER or SDOD_GRAPH_IMAGE_PROJ");
     SDOD_REQUIRE(kind == SDOD_GRAPH_IMAGE_ENCODER || (cfg && ip), "the IMAGE_PROJ graph needs the model configuration (context_dim) and ip_tokens");
-    sdod_model_config base;
-    sdod_model_config_sd14(&base);
-    if (cfg) base = *cfg;
-    *graph = new Graph(kind, base, batch, sdod_adapter_config{0, 0, 0}, 0, sdod_upscaler_config{0, 0, 0}, nullptr, 0,
-                       kind == SDOD_GRAPH_IMAGE_PROJ ? ip->ip_tokens : 0, vision);
+    sdod_graph_options o = plain_options();
+    o.image_size = vision->image_size;
+    o.patch = vision->patch;
+    o.width = vision->width;
+    o.layers = vision->layers;
+    o.heads = vision->heads;
+    o.mlp_dim = vision->mlp_dim;
+    o.proj_dim = vision->proj_dim;
+    o.quick_gelu = vision->quick_gelu;
+    if (kind == SDOD_GRAPH_IMAGE_PROJ) o.ip_tokens = ip->ip_tokens; // (the encoder has no tokens: its ip is not read)
+    create(graph, kind, cfg, o, batch);
     return 0;
     SDOD_CATCH
 }

@@ -143,7 +143,7 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
     quant_global(); // (one encoding policy for the whole group: its GEMM runs on M = 77 rows per prompt)
     P(tb + ".attn2.to_k.weight", {C, cd}, PK_LINEAR, "attn2_kv_all");
     P(tb + ".attn2.to_v.weight", {C, cd}, PK_LINEAR, "attn2_kv_all");
-    if (ip_tokens_ > 0) { // image prompt: the image tokens' projections, one group and one static GEMM like the text's (ip_kv_all_gemm)
+    if (opt_.ip_tokens > 0) { // image prompt: the image tokens' projections, one group and one static GEMM like the text's (ip_kv_all_gemm)
         P(tb + ".attn2.to_k_ip.weight", {C, cd}, PK_LINEAR, "attn2_kv_ip_all");
         P(tb + ".attn2.to_v_ip.weight", {C, cd}, PK_LINEAR, "attn2_kv_ip_all");
     }
@@ -219,16 +219,16 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
     // Needs the LayerNorm fold (fp16 weights), heads * 80 columns tiled by the 160-wide GEMM tiles and the 64-deep K slabs,
     // image rows a multiple of 32.  SDOD_XATTN_FOLD=0 keeps the three-launch form (A/B switch).
     static const bool xfold_on = [] { const char* e = std::getenv("SDOD_XATTN_FOLD"); return !(e && e[0] == '0'); }();
-    // REGIONAL PROMPTS (regions_ > 0): the context holds regions_ prompts of Lk keys per image and the block's output is
+    // REGIONAL PROMPTS (opt_.regions > 0): the context holds opt_.regions prompts of Lk keys per image and the block's output is
     // sum_r w_r(pixel) attn(x, K_r, V_r).  Folded: the score GEMM's 80-column groups are laid out [region][head][80], its epilogue
     // multiplies each group by its region's weight at the row's pixel and the second GEMM sums over regions through its K axis --
-    // the same launches as the plain fold, both GEMMs regions_ times as wide.  Otherwise one attention launch per (image, region)
+    // the same launches as the plain fold, both GEMMs opt_.regions times as wide.  Otherwise one attention launch per (image, region)
     // and a blend launch (correct, not fast: only levels whose pixels are no multiple of 32, or whose head geometry the fold declines, come here).
-    // IMAGE PROMPT (ip_tokens_ > 0): the same two forms with two segments per image, the text keys of kv_all_ and the
+    // IMAGE PROMPT (opt_.ip_tokens > 0): the same two forms with two segments per image, the text keys of kv_all_ and the
     // IPT image tokens of ip_kv_all_ (same column layout: this block's K | V at my_kv), weights (1, s(pixel)): to_out sees
     // attn(q, K_text, V_text) + s attn(q, K_img, V_img).  Only the fold launch differs (two sources of different lengths).
-    const int IPT = ip_tokens_;
-    const int RG = IPT > 0 ? 2 : regions_, NR = RG > 0 ? RG : 1;
+    const int IPT = opt_.ip_tokens;
+    const int RG = IPT > 0 ? 2 : opt_.regions, NR = RG > 0 ? RG : 1;
     const int Lkeys = IPT > 0 ? ctx.w : ctx.w / NR; // keys per prompt
     const float* rgw = nullptr;   // this level's weights, fp32 [L][RG]
     if (RG > 0) {
@@ -358,7 +358,7 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
 // input_blocks.0.0, the 3x3 convolution on the fp32 NCHW latent (build_unet() has checked the sizes)
 Act Graph::unet_conv_in(const float* x_in, const float* cond_in) {
     const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, LC = cfg_.latent_channels, MC = cfg_.model_channels;
-    const int CC = cfg_.concat_channels, CI = LC + CC, wr = wrap_;
+    const int CC = cfg_.concat_channels, CI = LC + CC, wr = opt_.wrap;
     const int ciw = P("input_blocks.0.0.weight", {MC, CI, 3, 3}, PK_CONV3_SMALL), cib = P("input_blocks.0.0.bias", {MC}, PK_VEC);
     Act h = act(B, H, Wd, MC);
     const f16* wp = W<f16>(ciw);
@@ -407,14 +407,14 @@ void Graph::kv_all_gemm(const f16* ctx_in) {
 void Graph::ip_kv_all_gemm(const f16* ip_ctx_in) {
     if (mode_ == DECLARE || kv_total_ <= 0) return;
     to_static_ = true;
-    linear_raw(ip_ctx_in, batch_ * ip_tokens_, cfg_.context_dim, reinterpret_cast<const f16*>(group_base("attn2_kv_ip_all")), cfg_.context_dim,
+    linear_raw(ip_ctx_in, batch_ * opt_.ip_tokens, cfg_.context_dim, reinterpret_cast<const f16*>(group_base("attn2_kv_ip_all")), cfg_.context_dim,
                kv_total_, mode_ == REAL ? ip_kv_all_ : const_cast<f16*>(ip_ctx_in) /* placeholder during the sizing pass */, GemmOpt{});
     to_static_ = false;
 }
 
 Act Graph::unet_encoder(Act h, const Act& ctx, const f16* emb_all, int emb_ld, int& emb_off, const f16* const* feat_in, std::vector<Act>* hs,
                         const std::function<void(int, const Act&)>& on_skip) {
-    const int MC = cfg_.model_channels, AR = acfg_.adapter_reps;
+    const int MC = cfg_.model_channels, AR = opt_.adapter_reps;
     int ch = MC, ds = 1, idx = 1, k = 1;
     auto skip = [&](const Act& t) {
         if (hs) hs->push_back(t);
@@ -495,30 +495,30 @@ void Graph::build_unet() {
     f16* ctx_in = (f16*)io_alloc(inputs_, (size_t)B * CL * cd * sizeof(f16));
     const float* cond_in = CC > 0 ? (const float*)io_alloc(inputs_, (size_t)B * CC * H * Wd * sizeof(float)) : nullptr;
     // T2I-Adapter features: one slot per level behind the other inputs, shared by the AR guidance copies of the batch
-    const int AR = acfg_.adapter_reps;
+    const int AR = opt_.adapter_reps;
     const f16* feat_in[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int l = 0; AR > 0 && l < 4; ++l)
         feat_in[l] = (const f16*)io_alloc(inputs_, (size_t)(B / AR) * (H >> l) * (Wd >> l) * kChMult[l] * MC * sizeof(f16));
     // ControlNet residuals: 13 slots in skip order and their fp32 scales, behind every other input
     const f16* ctrl_in[13] = {};
     const float* ctrl_scale = nullptr;
-    if (ccfg_.control_inputs) {
+    if (opt_.control_inputs) {
         for (int k = 0; k < 13; ++k) ctrl_in[k] = (const f16*)io_alloc(inputs_, control_residual_numel(k) * sizeof(f16));
         ctrl_scale = (const float*)io_alloc(inputs_, 13 * sizeof(float));
     }
     // regional prompts: the blend weights of the four levels, fp32 [H / ds * W / ds][regions], behind every other
     // input and shared by all images; "region 0 everywhere" until the caller writes them (sdod_region_weights_f32)
     for (int l = 0; l < 4; ++l) region_w_[l] = nullptr;
-    if (regions_ > 0) {
-        SDOD_REQUIRE(CL == 77 * regions_, "regional prompts: context_len must be 77 * regions");
-        SDOD_REQUIRE(AR == 0 && !ccfg_.control_inputs && CC == 0 && wrap_ == 0 && !quant_mode(),
+    if (opt_.regions > 0) {
+        SDOD_REQUIRE(CL == 77 * opt_.regions, "regional prompts: context_len must be 77 * regions");
+        SDOD_REQUIRE(AR == 0 && !opt_.control_inputs && CC == 0 && opt_.wrap == 0 && !quant_mode(),
                      "regional prompts exclude adapter inputs, control inputs, concat_channels, wrap and weight_quant");
         for (int l = 0; l < 4; ++l) {
-            const size_t n = (size_t)(H >> l) * (Wd >> l) * regions_;
+            const size_t n = (size_t)(H >> l) * (Wd >> l) * opt_.regions;
             float* wp = (float*)io_alloc(inputs_, n * sizeof(float));
             if (mode_ == REAL) {
                 std::vector<float> init(n, 0.f);
-                for (size_t i = 0; i < n; i += regions_) init[i] = 1.f;
+                for (size_t i = 0; i < n; i += opt_.regions) init[i] = 1.f;
                 SDOD_HIP_CHECK(hipMemcpy(wp, init.data(), n * sizeof(float), hipMemcpyHostToDevice));
             }
             region_w_[l] = wp;
@@ -528,11 +528,11 @@ void Graph::build_unet() {
     // the four levels, fp32 [H / ds * W / ds][2], behind every other input; (1, 0) -- no image prompt -- until the caller writes them
     const f16* ip_ctx_in = nullptr;
     for (int l = 0; l < 4; ++l) ip_w_[l] = nullptr;
-    if (ip_tokens_ > 0) {
+    if (opt_.ip_tokens > 0) {
         SDOD_REQUIRE(CL <= 80, "image prompts: context_len must be <= 80");
-        SDOD_REQUIRE(AR == 0 && !ccfg_.control_inputs && CC == 0 && wrap_ == 0 && !quant_mode() && regions_ == 0,
+        SDOD_REQUIRE(AR == 0 && !opt_.control_inputs && CC == 0 && opt_.wrap == 0 && !quant_mode() && opt_.regions == 0,
                      "image prompts exclude adapter inputs, control inputs, concat_channels, wrap, weight_quant and regions");
-        ip_ctx_in = (const f16*)io_alloc(inputs_, (size_t)B * ip_tokens_ * cd * sizeof(f16));
+        ip_ctx_in = (const f16*)io_alloc(inputs_, (size_t)B * opt_.ip_tokens * cd * sizeof(f16));
         for (int l = 0; l < 4; ++l) {
             const size_t n = (size_t)(H >> l) * (Wd >> l) * 2;
             float* wp = (float*)io_alloc(inputs_, n * sizeof(float));
@@ -565,14 +565,14 @@ void Graph::build_unet() {
     int emb_off = 0;
     kv_off_ = 0;
     kv_all_gemm(ctx_in);
-    if (ip_tokens_ > 0) ip_kv_all_gemm(ip_ctx_in);
+    if (opt_.ip_tokens > 0) ip_kv_all_gemm(ip_ctx_in);
 
     Act h = unet_conv_in(x_in, cond_in);
     std::vector<Act> hs;
     hs.push_back(h);
     h = unet_encoder(h, ctx, emb_all, emb_ld, emb_off, AR > 0 ? feat_in : nullptr, &hs, nullptr);
     int ch = h.c, ds = 8;
-    if (ccfg_.control_inputs) {
+    if (opt_.control_inputs) {
         // cldm's ControlledUnetModel: h + control[12] and, where the decoder pops them, hs[k] + control[k].  Every encoder launch has
         // been recorded by now, so the twelve skips take their residual in place, here, in the one launch that also updates h.
         // emit() settles first: a split-K reduce still pending on h (or one that reads a skip tensor as its residual) runs in front
@@ -665,7 +665,7 @@ std::vector<std::pair<std::string, int>> Graph::unet_res_blocks() const {
 
 std::vector<std::pair<std::string, int>> Graph::temb_blocks() const {
     auto v = unet_res_blocks();
-    if (ccfg_.control_temb || kind_ == SDOD_GRAPH_CONTROLNET) v.resize(10); // a ControlNet has the 8 input and 2 middle ResBlocks only
+    if (opt_.control_temb || kind_ == SDOD_GRAPH_CONTROLNET) v.resize(10); // a ControlNet has the 8 input and 2 middle ResBlocks only
     return v;
 }
 
@@ -774,7 +774,7 @@ void Graph::build_temb() {
     }
     // a full LCM checkpoint's guidance-scale embedding (sdod_graph_create_lcm): in1 = w, and cond_proj [MC][GD] without a bias, its rows
     // padded to the GEMM's K step where GD is no multiple of it (the padding columns stay zero: allocate_weights clears the arena)
-    const int GD = cond_proj_dim_, GK = (GD + 63) / 64 * 64;
+    const int GD = opt_.time_cond_proj_dim, GK = (GD + 63) / 64 * 64;
     const float* w_in = GD ? (const float*)io_alloc(inputs_, (size_t)B * sizeof(float)) : nullptr;
     const int wc = !GD ? -1 : GK == GD ? P("time_embed.cond_proj.weight", {MC, GD}, PK_LINEAR)
                                        : Pc("time_embed.cond_proj.weight", {MC, GD}, PK_LINEAR, GK, 0, -1);
@@ -850,7 +850,7 @@ Act Graph::vae_attn_block(const std::string& pfx, const Act& x) {
     // two forms (include/sdod_engine.h, sdod_vae_config): four launches per image through an L x L score buffer wherever that runs
     // today, the fused wide attention kernel above the softmax's widest row or on request (fused_attn)
     constexpr int kMaxScoreRow = 16384;
-    const bool fused = fused_attn_ != 0 || L > kMaxScoreRow;
+    const bool fused = opt_.fused_attn != 0 || L > kMaxScoreRow;
     if (fused)
         SDOD_REQUIRE(sdod_attention_wide_dim_ok(C), "vae_channels = " + std::to_string(cfg_.vae_channels) + " above " + std::to_string(kMaxScoreRow) +
                                                         " positions (latent_h * latent_w): only vae_channels 64 and 128 have the fused VAE attention");
@@ -926,7 +926,7 @@ void Graph::build_vae() {
     int ch = VC * kChMult[3];
     const int ciw = P("decoder.conv_in.weight", {ch, LC, 3, 3}, PK_CONV3_SMALL), cib = P("decoder.conv_in.bias", {ch}, PK_VEC);
     f16* cols = alloc((size_t)B * H * Wd * 64);
-    const int wr = wrap_;
+    const int wr = opt_.wrap;
     emit([=](hipStream_t st) { check_rc(sdod_im2col3x3_small_wrap_f16(zl.p, cols, B, H, Wd, LC, 64, wr, st)); });
     Act h = act(B, H, Wd, ch);
     { GemmOpt o; o.bias = cib; linear(cols, B * H * Wd, 64, ciw, ch, h.p, o); }
@@ -1035,7 +1035,7 @@ void Graph::build_vae_encoder(bool masked) {
 // launch (the GEMM epilogue has no such code, see SDOD_ACT_RELU).  The graph runs once per hint, not once per step.
 void Graph::build_adapter() {
     const int B = batch_, H = cfg_.latent_h, Wd = cfg_.latent_w, MC = cfg_.model_channels;
-    const int HC = acfg_.adapter_hint_channels, NRB = acfg_.adapter_res_blocks > 0 ? acfg_.adapter_res_blocks : 2;
+    const int HC = opt_.adapter_hint_channels, NRB = opt_.adapter_res_blocks > 0 ? opt_.adapter_res_blocks : 2;
     SDOD_REQUIRE(H >= 8 && Wd >= 8 && H % 8 == 0 && Wd % 8 == 0, "the adapter needs latent_h and latent_w to be multiples of 8, at least 8");
     const int cin = 64 * HC;
     const int ch[4] = {kChMult[0] * MC, kChMult[1] * MC, kChMult[2] * MC, kChMult[3] * MC};
@@ -1122,7 +1122,7 @@ void Graph::dense_conv(sdod_dense_conv_desc d, int w, int bias) {
 // add launch: 15 launches per block.  conv_first keeps a dense copy of its output for conv_body's skip; nearest-2x is folded into
 // conv_up1 / conv_up2 (the dense-block kernel with cin = 64); conv_last (64 -> 3) is the gather GEMM.  15 num_blocks + 6 launches.
 void Graph::build_upscaler() {
-    const int B = batch_, H = ucfg_.in_h, Wd = ucfg_.in_w, NB = ucfg_.num_blocks;
+    const int B = batch_, H = opt_.in_h, Wd = opt_.in_w, NB = opt_.num_blocks;
     constexpr int NF = 64, GC = 32, LD = NF + 4 * GC;
     const uint8_t* img_in = (const uint8_t*)io_alloc(inputs_, (size_t)B * H * Wd * 3);
     f16* img_out = (f16*)io_alloc(outputs_, (size_t)B * (4 * H) * (4 * Wd) * 3 * sizeof(f16));
@@ -1263,8 +1263,8 @@ void Graph::build_clip() {
 // into visual_projection, which reads the class rows only (row stride (P + 1) W) and writes the output slot.
 void Graph::build_image_encoder() {
     static const float kMean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, kStd[3] = {0.26862954f, 0.26130258f, 0.27577711f}; // CLIP's
-    const int B = batch_, S = vcfg_.image_size, p = vcfg_.patch, D = vcfg_.width, g = S / p, NP = g * g, L = NP + 1;
-    const int KP = (3 * p * p + 63) / 64 * 64, PD = vcfg_.proj_dim;
+    const int B = batch_, S = opt_.image_size, p = opt_.patch, D = opt_.width, g = S / p, NP = g * g, L = NP + 1;
+    const int KP = (3 * p * p + 63) / 64 * 64, PD = opt_.proj_dim;
     const uint8_t* img = (const uint8_t*)io_alloc(inputs_, (size_t)B * S * S * 3);
     f16* out = (f16*)io_alloc(outputs_, (size_t)B * PD * sizeof(f16));
     const std::string em = "vision_model.embeddings.";
@@ -1284,9 +1284,9 @@ void Graph::build_image_encoder() {
         emit([=](hipStream_t st) { check_rc(sdod_vit_tokens_f16(pt, cp, pp, wp, bp, xp, B, NP, D, 1e-5f, st)); }, "vit_tokens", 0, 4.0 * B * L * D);
     }
     release(pt);
-    for (int l = 0; l < vcfg_.layers; ++l)
-        x = clip_block("vision_model.encoder.layers." + std::to_string(l), false, x, vcfg_.heads, vcfg_.mlp_dim, false,
-                       vcfg_.quick_gelu ? SDOD_ACT_QUICK_GELU : SDOD_ACT_GELU);
+    for (int l = 0; l < opt_.layers; ++l)
+        x = clip_block("vision_model.encoder.layers." + std::to_string(l), false, x, opt_.heads, opt_.mlp_dim, false,
+                       opt_.quick_gelu ? SDOD_ACT_QUICK_GELU : SDOD_ACT_GELU);
     const int fw = P("vision_model.post_layernorm.weight", {D}, PK_VEC), fb = P("vision_model.post_layernorm.bias", {D}, PK_VEC);
     const int vp = P("visual_projection.weight", {PD, D}, PK_LINEAR);
     { GemmOpt o; o.ln_w = fw; o.ln_b = fb; o.lda = L * D; linear(x.p, B, D, vp, PD, out, o); }
@@ -1295,7 +1295,7 @@ void Graph::build_image_encoder() {
 
 // IP-Adapter's ImageProjModel: LayerNorm(Linear(image_embeds).reshape(T, ctx_dim)) -- a GEMM and a LayerNorm launch into the output slot
 void Graph::build_image_proj() {
-    const int B = batch_, PD = vcfg_.proj_dim, T = ip_tokens_, cd = cfg_.context_dim;
+    const int B = batch_, PD = opt_.proj_dim, T = opt_.ip_tokens, cd = cfg_.context_dim;
     const f16* in = (const f16*)io_alloc(inputs_, (size_t)B * PD * sizeof(f16));
     f16* out = (f16*)io_alloc(outputs_, (size_t)B * T * cd * sizeof(f16));
     const int w = P("proj.weight", {T * cd, PD}, PK_LINEAR), b = P("proj.bias", {T * cd}, PK_VEC);

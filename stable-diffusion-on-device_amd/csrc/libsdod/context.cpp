@@ -68,7 +68,7 @@ void Context::init(unsigned steps) {
                           {&vae_, SDOD_GRAPH_VAE_DECODER, 1, "vae_decoder"}};
     for (const Item& it : items) {
         logger_.info(std::string("Attempting to load a model: ") + it.stem + ".sdodw");
-        it.slot->reset(new Graph(it.kind, cfg_, it.batch));
+        it.slot->reset(new Graph(it.kind, cfg_, it.batch, plain_options()));
         (*it.slot)->load_file(weight_path(it.stem), "");
         (*it.slot)->finalize();
         logger_.info(std::string("Model ") + it.stem + " loaded");
@@ -104,7 +104,7 @@ void Context::prepare_schedule(unsigned steps) {
     SDOD_HIP_CHECK(hipSetDevice(device_));
     model_ts_ = solver_->prepare(steps); // dpm_solver.cpp:100-131
     // context.cpp:257-278: sinusoidal features + time-embedding MLP for the first `steps` model times, cached
-    temb_.reset(new Graph(SDOD_GRAPH_TEMB, cfg_, (int)steps));
+    temb_.reset(new Graph(SDOD_GRAPH_TEMB, cfg_, (int)steps, plain_options()));
     temb_->load_file(weight_path("temb"), "");
     temb_->finalize();
     const IoSlot in = temb_->io(false, 0), out = temb_->io(true, 0);

@@ -19,43 +19,40 @@ class ModelConfig(ctypes.Structure):
         'latent_channels', 'latent_h', 'latent_w', 'model_channels', 'context_dim', 'context_len', 'num_heads',
         'head_dim', 'vocab_size', 'text_layers', 'text_heads', 'vae_channels', 'linear_proj', 'text_arch', 'weight_quant',
         'concat_channels')]
-    # T2I-Adapter (`struct sdod_adapter_config`, which travels NEXT to the model config: the struct above keeps its size): plain
-    # attributes of the instance, 0 = no adapter.  Every copy made from a ModelConfig carries them: from_buffer_copy() and copy_config().
-    adapter_reps = 0
-    adapter_hint_channels = 0
-    adapter_res_blocks = 0
-    # Seamless tiling (the `wrap` argument of sdod_graph_create_wrap, which also travels next to the struct): bit 0 = the x axis wraps,
-    # bit 1 = the y axis wraps; read by UNet and VaeDecoder only, 0 = the plain graphs through the old creation entry points.
-    tiling = 0
-    # ControlNet (`struct sdod_control_config`, next to the struct like the others): control_inputs = 1 gives a UNet the 13 residual
-    # inputs and control_scale, control_temb = 1 makes a Temb the time conditioning of a ControlNet graph; 0 = the plain graphs.
-    control_inputs = 0
-    control_temb = 0
-    # Regional prompts (`struct sdod_region_config`, next to the struct like the others): prompts per image of a UNet, whose context_len
-    # is then 77 * regions and which gets the four UNet.region_w inputs; 0 = the plain graph through the old creation entry points.
-    regions = 0
-    # Image prompts (`struct sdod_ip_config`, next to the struct like the others): image tokens per image of a UNet, which then has the
-    # to_k_ip / to_v_ip parameters and the UNet.ip_ctx / UNet.ip_w inputs; 0 = the plain graph through the old creation entry points.
-    ip_tokens = 0
-    # FreeU (sdod_graph_enable_freeu, a switch on the created graph, not a configuration struct): 1 makes a UNet run the FreeU launches at
-    # its decoder sites and gives it the UNet.freeu parameter input; composes with every attribute above; 0 = the graph as it was.
-    freeu = 0
-    # HyperTile (sdod_graph_enable_hypertile, a switch like freeu): (tile, max_depth) makes a UNet or ControlNet run the self-attention
-    # of the levels the tile rule tiles (sdod/amd/hypertile.py) inside tiles; composes with every attribute above; None = the graph as it was.
-    hypertile = None
-    _ADAPTER_FIELDS = ('adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'tiling', 'control_inputs', 'control_temb', 'regions',
-                       'ip_tokens', 'freeu')
+    # What travels NEXT to the struct, which keeps its size: plain attributes of the instance, here with their defaults (= nothing asked
+    # for).  Every copy made from a ModelConfig carries them: from_buffer_copy() and copy_config().
+    _SIDE = {
+        # T2I-Adapter (sdod_graph_options.adapter_*): adapter_reps on a UNet's config, the other two on an Adapter's
+        'adapter_reps': 0, 'adapter_hint_channels': 0, 'adapter_res_blocks': 0,
+        # Seamless tiling (sdod_graph_options.wrap): bit 0 = the x axis wraps, bit 1 = the y axis; read by UNet and VaeDecoder only
+        'tiling': 0,
+        # ControlNet: control_inputs = 1 gives a UNet the 13 residual inputs and control_scale, control_temb = 1 makes a Temb the time
+        # conditioning of a ControlNet graph
+        'control_inputs': 0, 'control_temb': 0,
+        # Regional prompts: prompts per image of a UNet, whose context_len is then 77 * regions and which gets the UNet.region_w inputs
+        'regions': 0,
+        # Image prompts: image tokens per image of a UNet, which then has the to_k_ip / to_v_ip parameters and UNet.ip_ctx / UNet.ip_w
+        'ip_tokens': 0,
+        # FreeU (sdod_graph_enable_freeu, a switch on the created graph): 1 makes a UNet run the FreeU launches at its decoder sites and
+        # gives it the UNet.freeu parameter input; composes with every attribute above
+        'freeu': 0,
+        # HyperTile (sdod_graph_enable_hypertile, a switch like freeu): (tile, max_depth) makes a UNet or ControlNet run the self-attention
+        # of the levels the tile rule tiles (sdod/amd/hypertile.py) inside tiles; composes with every attribute above
+        'hypertile': None,
+    }
 
     @classmethod
     def from_buffer_copy(cls, source, offset=0):
         out = type(ctypes.Structure).from_buffer_copy(cls, source, offset)   # (a method of the ctypes metaclass: no super() reaches it)
-        for n in cls._ADAPTER_FIELDS:          # (a raw buffer has none: the class defaults, 0, stay)
-            v = int(getattr(source, n, 0))
+        for n, default in cls._SIDE.items():   # (a raw buffer has none: the class defaults stay)
+            v = getattr(source, n, default)
             if v:
-                setattr(out, n, v)
-        if getattr(source, 'hypertile', None):
-            out.hypertile = tuple(source.hypertile)
+                setattr(out, n, int(v) if default == 0 else tuple(v))
         return out
+
+
+for _n, _default in ModelConfig._SIDE.items():
+    setattr(ModelConfig, _n, _default)
 
 
 class AdapterConfig(ctypes.Structure):
@@ -107,6 +104,14 @@ class UpscalerConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ('num_blocks', 'in_h', 'in_w')]
 
 
+class GraphOptions(ctypes.Structure):
+    """mirror of `struct sdod_graph_options`: what Graph creates every graph from; the structs above are its older spellings"""
+    _fields_ = [(n, ctypes.c_int) for n in (
+        'size', 'adapter_reps', 'adapter_hint_channels', 'adapter_res_blocks', 'wrap', 'num_blocks', 'in_h', 'in_w', 'control_inputs',
+        'control_temb', 'regions', 'ip_tokens', 'image_size', 'patch', 'width', 'layers', 'heads', 'mlp_dim', 'proj_dim', 'quick_gelu',
+        'time_cond_proj_dim', 'fused_attn')]
+
+
 TILING_WRAP = {False: 0, True: 3, 'xy': 3, 'x': 1, 'y': 2}
 
 
@@ -147,7 +152,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_enable_freeu', 'sdod_graph_freeu_input', 'sdod_graph_enable_hypertile',
     'sdod_graph_set_networks',
     'sdod_graph_create_lcm',
-    'sdod_graph_create_vae',
+    'sdod_graph_create_vae', 'sdod_graph_create_opts',
 ]
 
 
@@ -169,6 +174,7 @@ def _engine():
         lib.sdod_graph_create_vision.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(VisionConfig), ctypes.POINTER(IpConfig), I]
         lib.sdod_graph_create_lcm.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(LcmConfig), I]
         lib.sdod_graph_create_vae.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), I, ctypes.POINTER(VaeConfig), I]
+        lib.sdod_graph_create_opts.argtypes = [ctypes.POINTER(P), I, ctypes.POINTER(ModelConfig), ctypes.POINTER(GraphOptions), I]
         lib.sdod_graph_bind_output.argtypes = [P, I, P, ctypes.c_size_t]
         lib.sdod_graph_destroy.argtypes = [P]
         lib.sdod_graph_num_params.argtypes = [P]
@@ -236,55 +242,41 @@ class Graph:
     device memory raises."""
 
     def __init__(self, kind, cfg, batch, device='cuda:0', wrap=None, cond_proj_dim=0, fused_attn=None):
-        """fused_attn (the VAE kinds): None = the entry points as before; True / False go through sdod_graph_create_vae, True with the
-        fused middle attention at every size, False with the rule of the entry points as before.  wrap: None = the creation entry points of every build before seamless tiling; an int 0..3 goes through
-        sdod_graph_create_wrap (0 builds the plain graph there).  cond_proj_dim: a TEMB graph with an LCM checkpoint's guidance-scale
-        embedding goes through sdod_graph_create_lcm; 0 = the entry points as before"""
+        """One sdod_graph_options record, filled from the side attributes of `cfg` that `kind` reads and from the three arguments, goes to
+        sdod_graph_create_opts.  wrap: None or 0 = the plain border, 1..3 = the wrap bits.  cond_proj_dim: a TEMB graph with an LCM
+        checkpoint's guidance-scale embedding; 0 = none.  fused_attn (the VAE kinds only): True = the fused middle attention at every
+        size; False or None = the size rule."""
         self._lib = _engine()
         self._h = ctypes.c_void_p()
         self.kind, self.cfg, self.batch = kind, cfg, batch
         self.device = torch.device(device)
-        acfg = AdapterConfig(*(int(getattr(cfg, n, 0)) for n, _ in AdapterConfig._fields_))
-        ccfg = ControlConfig(int(getattr(cfg, 'control_inputs', 0)) if kind == UNET else 0, int(getattr(cfg, 'control_temb', 0)) if kind == TEMB else 0)
-        control = kind in (CONTROLNET, CONTROL_HINT) or ccfg.control_inputs or ccfg.control_temb
-        if control and (wrap or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_)):
+
+        def side(name, *kinds):
+            return int(getattr(cfg, name, 0)) if kind in kinds else 0
+        adapter = [int(getattr(cfg, n, 0)) for n, _ in AdapterConfig._fields_]
+        o = GraphOptions(size=ctypes.sizeof(GraphOptions), wrap=int(wrap or 0), time_cond_proj_dim=int(cond_proj_dim), fused_attn=1 if fused_attn else 0,
+                         control_inputs=side('control_inputs', UNET), control_temb=side('control_temb', TEMB), regions=side('regions', UNET),
+                         ip_tokens=side('ip_tokens', UNET, IMAGE_PROJ))
+        control = kind in (CONTROLNET, CONTROL_HINT) or o.control_inputs or o.control_temb
+        if control and (wrap or any(adapter)):
             raise ValueError('a ControlNet graph, or a UNet with control inputs, takes neither tiling nor a T2I-Adapter configuration')
-        regions = int(getattr(cfg, 'regions', 0)) if kind == UNET else 0
-        if regions and (control or wrap or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_)):
+        if o.regions and (control or wrap or any(adapter)):
             raise ValueError('a UNet with regions takes no control inputs, no tiling and no T2I-Adapter configuration')
-        ip_tokens = int(getattr(cfg, 'ip_tokens', 0)) if kind == UNET else 0
-        if ip_tokens and (regions or control or wrap or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_)):
+        if kind == UNET and o.ip_tokens and (o.regions or control or wrap or any(adapter)):
             raise ValueError('a UNet with an image prompt takes no regions, no control inputs, no tiling and no T2I-Adapter configuration')
-        cond_proj_dim = int(cond_proj_dim)
-        if cond_proj_dim and (kind != TEMB or control):
+        if o.time_cond_proj_dim and (kind != TEMB or control):
             raise ValueError("cond_proj_dim applies to the UNet's TEMB graph only, not to a ControlNet's time conditioning (control_temb)")
         if fused_attn is not None and kind not in (VAE_DECODER, VAE_ENCODER, VAE_ENCODER_MASKED):
             raise ValueError('fused_attn applies to the VAE decoder and encoder graphs only')
+        if kind in (UNET, ADAPTER):
+            o.adapter_reps, o.adapter_hint_channels, o.adapter_res_blocks = adapter
+        if kind == UPSCALER:            # (an Upscaler's cfg is its UpscalerConfig; no ModelConfig field applies)
+            o.num_blocks, o.in_h, o.in_w = cfg.num_blocks, cfg.in_h, cfg.in_w
+        if kind in (IMAGE_ENCODER, IMAGE_PROJ):
+            for n, _ in VisionConfig._fields_:
+                setattr(o, n, getattr(cfg.vision, n))
         with self._on_device():
-            if fused_attn is not None:  # the switch has an entry point of its own; without it nothing changes
-                check(self._lib.sdod_graph_create_vae(ctypes.byref(self._h), kind, ctypes.byref(cfg), int(wrap or 0),
-                                                      ctypes.byref(VaeConfig(1 if fused_attn else 0)), batch))
-            elif cond_proj_dim:     # the guidance embedding has an entry point of its own; without it nothing changes
-                check(self._lib.sdod_graph_create_lcm(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(LcmConfig(cond_proj_dim)), batch))
-            elif kind in (IMAGE_ENCODER, IMAGE_PROJ):   # the image side of an image prompt: cfg.vision, and cfg.ip_tokens for the projection
-                icfg = IpConfig(int(getattr(cfg, 'ip_tokens', 0)))
-                check(self._lib.sdod_graph_create_vision(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(cfg.vision), ctypes.byref(icfg), batch))
-            elif ip_tokens:         # image prompts have an entry point of their own; without them nothing changes
-                icfg = IpConfig(ip_tokens)
-                check(self._lib.sdod_graph_create_ip(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(icfg), batch))
-            elif regions:           # regional prompts have an entry point of their own; without them nothing changes
-                rcfg = RegionConfig(regions)
-                check(self._lib.sdod_graph_create_regions(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(rcfg), batch))
-            elif control:             # the ControlNet kinds and switches have an entry point of their own; without them nothing changes
-                check(self._lib.sdod_graph_create_control(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(ccfg), batch))
-            elif kind == UPSCALER:    # its configuration is the UpscalerConfig itself; no ModelConfig field applies
-                check(self._lib.sdod_graph_create_upscaler(ctypes.byref(self._h), ctypes.byref(cfg), batch))
-            elif wrap is not None:
-                check(self._lib.sdod_graph_create_wrap(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(acfg), int(wrap), batch))
-            elif kind == ADAPTER or any(getattr(acfg, n) for n, _ in AdapterConfig._fields_):
-                check(self._lib.sdod_graph_create_ex(ctypes.byref(self._h), kind, ctypes.byref(cfg), ctypes.byref(acfg), batch))
-            else:       # no adapter anywhere: the entry point, and the graph, of every build before it
-                check(self._lib.sdod_graph_create(ctypes.byref(self._h), kind, ctypes.byref(cfg), batch))
+            check(self._lib.sdod_graph_create_opts(ctypes.byref(self._h), kind, None if kind == UPSCALER else ctypes.byref(cfg), ctypes.byref(o), batch))
             if kind == UNET and int(getattr(cfg, 'freeu', 0)):   # a switch on whichever graph was created above
                 self.enable_freeu()
             if kind in (UNET, CONTROLNET) and getattr(cfg, 'hypertile', None):

@@ -189,13 +189,12 @@ class Txt2Img:
         adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_unet, model)
         control_check_build(controlnet, cfg_split, hires_hw, inpaint_unet, adapter, tiling, model)
         self.tiling = tiling_check_build(tiling, with_vae_encoder, inpaint_unet, hires_hw, adapter)
-        quant_asked = bool(regions) and (weight_quant or (weight_quant is None and state_dicts is not None and any(
-            hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts.get('unet', {}).values())))      # (uint8 codes decide it, as below)
+        if weight_quant is None:     # uint8 codes in the UNet checkpoint (weights.QuantU8, the reference's QNN encoding) decide it
+            weight_quant = state_dicts is not None and any(hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts.get('unet', {}).values())
         self.regions = RG.regions_check_build(regions, self.prompt_chunks, cfg_split, hires_hw, controlnet, adapter, tiling, inpaint_unet,
-                                              model, quant_asked)
-        quant_ip = bool(ip_adapter) and (weight_quant or (weight_quant is None and state_dicts is not None and any(
-            hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts.get('unet', {}).values())))
-        if IP.ip_check_build(ip_adapter, regions, self.prompt_chunks, cfg_split, hires_hw, controlnet, adapter, tiling, inpaint_unet, model, quant_ip):
+                                              model, bool(regions) and weight_quant)
+        if IP.ip_check_build(ip_adapter, regions, self.prompt_chunks, cfg_split, hires_hw, controlnet, adapter, tiling, inpaint_unet, model,
+                             bool(ip_adapter) and weight_quant):
             self.ip_tokens, self.ip_proj_dim, ip_vision = IP.ip_sources(state_dicts, models_dir)
         up_args = upscaler_check_build(upscaler, tiling, hires_hw if hires_hw is not None else latent_hw, state_dicts, models_dir)
         if hires_hw is not None:
@@ -208,15 +207,12 @@ class Txt2Img:
         self.model = model
         self.v_prediction = model == 'sd21'
         self.cfg = E.sd21_config(latent_h, latent_w) if model == 'sd21' else E.sd14_config(latent_h, latent_w)
-        # int8 weight streaming (BASELINE config 5): when the UNet checkpoint holds affine-uint8 tensors (weights.QuantU8, the
-        # reference's QNN encoding) they stay uint8 in HBM and the GEMMs expand them on the fly; weight_quant=False keeps the
-        # round-1 behaviour (dequantise once at load, fp16 in HBM)
+        # int8 weight streaming (BASELINE config 5): when the UNet checkpoint holds affine-uint8 tensors they stay uint8 in HBM and the
+        # GEMMs expand them on the fly; weight_quant=False keeps the round-1 behaviour (dequantise once at load, fp16 in HBM)
         self.inpaint_unet = bool(inpaint_unet)
         if self.inpaint_unet:
             self.cfg.concat_channels = 5         # mask (1) | latent of the masked image (4), ldm's c_concat
         self._cond_staged = False
-        if weight_quant is None:
-            weight_quant = state_dicts is not None and any(hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts['unet'].values())
         # weight_quant='auto' (or 2): stream the codes only where that is not slower than fp16 (sdod_model_config.weight_quant = 2)
         self.cfg.weight_quant = 2 if weight_quant in ('auto', 2) else 1 if weight_quant else 0
         # latency mode: the two halves of the classifier-free-guidance batch run on TWO GPUs -- even rank =
@@ -237,33 +233,20 @@ class Txt2Img:
             self._pair_staged = dist.get_backend() == 'gloo'         # gloo gathers on the host (rehearsals); RCCL on device
         self.use_hip_graph = use_hip_graph
         self.tokenizer = tokenizer
-        unet_cfg = self.cfg
-        if self.prompt_chunks > 1:       # the text encoder keeps 77 (its position table); only the UNet sees the longer context
-            unet_cfg = E.copy_config(self.cfg)
-            unet_cfg.context_len = PR.CHUNK_LEN * self.prompt_chunks
-        if adapter:                      # only the UNet graph takes the feature slots: one per level, shared by the two guidance halves
-            unet_cfg = E.copy_config(unet_cfg)
-            unet_cfg.adapter_reps = 2
+        # What the UNet graph alone sees, on one copy of the configuration (the ControlNet's, below, is a copy of this one): the k-fold
+        # context of regions or prompt chunks (the text encoder keeps 77, its position table), the adapter's feature slots shared by
+        # the two guidance halves, the 13 control slots, the region and image-prompt inputs, the FreeU and HyperTile switches
+        unet_cfg = E.copy_config(self.cfg)
+        if self.regions or self.prompt_chunks > 1:
+            unet_cfg.context_len = PR.CHUNK_LEN * (self.regions or self.prompt_chunks)
+        unet_cfg.adapter_reps, unet_cfg.control_inputs = 2 if adapter else 0, 1 if controlnet else 0
+        unet_cfg.regions, unet_cfg.ip_tokens = int(self.regions), int(self.ip_tokens)
+        unet_cfg.freeu, unet_cfg.hypertile = 1 if self.freeu else 0, self.hypertile
+        if adapter:
             self.adapter_channels = int(adapter_channels)
-        if controlnet:                   # 13 residual slots and their scales, filled by the control graph built below
-            unet_cfg = E.copy_config(unet_cfg)
-            unet_cfg.control_inputs = 1
-        if self.regions:                 # k prompts per image: only the UNet sees the k-fold context and has the weight inputs
-            unet_cfg = E.copy_config(unet_cfg)
-            unet_cfg.context_len = PR.CHUNK_LEN * self.regions
-            unet_cfg.regions = self.regions
-        if self.ip_tokens:               # the image tokens and the two segments' weights are inputs of the UNet alone
-            unet_cfg = E.copy_config(unet_cfg)
-            unet_cfg.ip_tokens = self.ip_tokens
-        if self.freeu:                   # a switch on the UNet graph, whatever else it was configured with
-            unet_cfg = E.copy_config(unet_cfg)
-            unet_cfg.freeu = 1
-        if self.hypertile:               # likewise; the ControlNet's configuration below is a copy of this one and carries it
-            unet_cfg = E.copy_config(unet_cfg)
-            unet_cfg.hypertile = self.hypertile
         vae_cfg = self.cfg
         if self.tiling:                  # the UNet and the VAE decoder take the circular border; every other graph has no border to wrap
-            unet_cfg, vae_cfg = E.copy_config(unet_cfg), E.copy_config(self.cfg)
+            vae_cfg = E.copy_config(self.cfg)
             unet_cfg.tiling = vae_cfg.tiling = self.tiling
         self.unet = E.UNet(unet_cfg, self.n if cfg_split or self.unguided else 2 * self.n, device)
         self.vae = E.VaeDecoder(vae_cfg, 1, device, fused_attn=fused_vae) if with_vae else None

@@ -21,13 +21,18 @@ SWITCHED = ['unet_sd14', 'unet_sd21']
 
 
 def cases(E):
-    """name -> (constructor, input attributes, output attributes).  sd14 UNet at 16x16: levels 0 and 1 take the folded cross-attention
+    """name -> (constructor, input attributes -- or (attribute, values) -- and output attributes).  sd14 UNet at 16x16: levels 0 and 1 take the folded cross-attention
     (L = 256, 64), levels 2, 3 and the middle the plain one with composition (L = 16, 4); sd21 at 32x32 folds at level 2 only."""
     def sd14(hw, wq=0, **kw):
         cfg = E.sd14_config(hw, hw, **kw)
         cfg.weight_quant = wq
         return cfg
+    def side(cfg, **attrs):       # the attributes that travel next to the struct (ModelConfig): options of the graph, not of the model
+        for n, v in attrs.items():
+            setattr(cfg, n, v)
+        return cfg
     unet_io = (['x', 'temb', 'ctx'], ['eps'])
+    vision = E.VisionConfig(28, 14, 128, 2, 2, 256, 64, 1)
     out = {
         'unet_sd14': (lambda: E.UNet(sd14(16), 2),) + unet_io,
         'unet_sd14_wq1': (lambda: E.UNet(sd14(16, 1), 2),) + unet_io,
@@ -46,6 +51,21 @@ def cases(E):
         'adapter_hint1': (lambda: E.Adapter(sd14(16, adapter_hint_channels=1), 1), ['hint'], ['out']),
         'adapter_hint3': (lambda: E.Adapter(sd14(16, adapter_hint_channels=3), 1), ['hint'], ['out']),
         'upscaler_nb1': (lambda: E.Upscaler(1, (16, 16), 1), ['img'], ['out']),
+        # every option of graph creation (include/sdod_engine.h at sdod_graph_options) and the two switches, at the smallest sizes that build
+        'unet_sd14_control': (lambda: E.UNet(side(sd14(16), control_inputs=1), 2),
+                              ['x', 'temb', 'ctx', 'control_res', ('control_scale', [0.25 + 0.125 * k for k in range(13)])], ['eps']),
+        'unet_sd14_regions2': (lambda: E.UNet(side(sd14(16), context_len=154, regions=2), 2), ['x', 'temb', 'ctx', 'region_w'], ['eps']),
+        'unet_sd14_ip4': (lambda: E.UNet(side(sd14(16), ip_tokens=4), 2), ['x', 'temb', 'ctx', 'ip_ctx', 'ip_w'], ['eps']),
+        'unet_sd14_freeu': (lambda: E.UNet(side(sd14(16), freeu=1), 2), ['x', 'temb', 'ctx', ('freeu', [1.2, 0.9, 1.4, 0.2, 2, 0, 0, 0])], ['eps']),
+        'unet_sd14_hypertile8': (lambda: E.UNet(side(sd14(16), hypertile=(8, 0)), 2),) + unet_io,
+        'controlnet_sd14': (lambda: E.ControlNet(sd14(16), 2), ['x', 'temb', 'ctx', 'hint'], ['out']),
+        'control_hint_sd14': (lambda: E.ControlHint(sd14(16), 1), ['hint'], ['out']),
+        'temb_sd14_control': (lambda: E.Temb(side(sd14(16), control_temb=1), 2), ['t'], ['out']),
+        'temb_sd14_cond256': (lambda: E.Temb(sd14(16), 2, cond_proj_dim=256), ['t', ('w', [7.5, 3.0])], ['out']),
+        'vae_decoder_fused': (lambda: E.VaeDecoder(sd14(8), 1, fused_attn=True), ['z'], ['img']),
+        'vae_encoder_fused': (lambda: E.VaeEncoder(sd14(8), 1, fused_attn=True), ['img'], ['moments']),
+        'image_encoder_small': (lambda: E.ImageEncoder(vision, 1), ['img'], ['out']),
+        'image_proj': (lambda: E.ImageProj(sd14(16), 64, 4, 2), ['embeds'], ['out']),
     }
     return out
 
@@ -53,14 +73,17 @@ def cases(E):
 def tensors(g, names):
     out = []
     for n in names:
-        v = getattr(g, n)
+        v = getattr(g, n[0] if isinstance(n, tuple) else n)
         out += list(v) if isinstance(v, (list, tuple)) else [v]
     return out
 
 
 def fill(g, names, torch, seed):
     gen = torch.Generator().manual_seed(seed)
-    for t in tensors(g, names):
+    for n in names:
+        if isinstance(n, tuple):          # (name, values): a parameter block whose values mean something (scales, FreeU's factors)
+            getattr(g, n[0]).copy_(torch.tensor(n[1], dtype=torch.float32))
+    for t in tensors(g, [n for n in names if not isinstance(n, tuple)]):
         if t.dtype == torch.uint8:
             v = torch.randint(0, 256, t.shape, generator=gen, dtype=torch.uint8)
         elif t.dtype == torch.int32:      # token ids
