@@ -405,6 +405,16 @@ SDOD_API int sdod_graph_freeu_input(void* graph, int* index);
  * list, arena and bits. */
 SDOD_API int sdod_graph_enable_hypertile(void* graph, int tile, int max_depth);
 
+/* ---- Self-Attention Guidance (Hong et al., ICCV 2023): a switch in the same pattern.  sdod_graph_enable_sag (kind UNET,
+ * before sdod_graph_finalize; anything else is INVALID_ARGUMENT): behind the qkv GEMM of middle_block.1's attn1 the graph launches
+ * sdod_attention_mass_f16 (include/sdod_hip.h) on the same packed rows, label attn_mass_d<d>, next to the unchanged attention launch
+ * (with HyperTile on the graph the mass is still taken over the whole middle map).  The graph gets one more output behind every other
+ * one, slot sdod_graph_sag_output: fp32 [batch][latent_h / 8 * latent_w / 8], the mass of every image's keys (it is not an output
+ * sdod_graph_bind_output takes).  out0 keeps its bits.  A graph without the switch is what it was: same launch list, arena, inputs and
+ * outputs; its sdod_graph_sag_output is -1. */
+SDOD_API int sdod_graph_enable_sag(void* graph);
+SDOD_API int sdod_graph_sag_output(void* graph, int* index);
+
 #ifdef __cplusplus
 }
 #endif

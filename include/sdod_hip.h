@@ -333,7 +333,34 @@ SDOD_API int sdod_attention_wide_ws_f16(const void* q, const void* k, const void
 SDOD_API int sdod_attention_wide_splits(int batch, int lq, int lk, int d);
 SDOD_API size_t sdod_attention_wide_ws_bytes(int batch, int lq, int lk, int d);
 
-/* Folded cross-attention, the once-per-prompt part.  The text context is constant over the sampler run, so to_q and to_out can
+/* Attention mass (Self-Attention Guidance): mass_out[b][j] = (1 / heads) * sum_h sum_i softmax_i(scale q_h k_h^T)[i][j],
+ * fp32 [batch][lk] -- the softmax probability key j collects, averaged over heads and summed over queries; sum_j mass = lq.  QK^T by
+ * MFMA with fp32 accumulation, fp32 softmax, probabilities fp32 to the end; no lq x lk buffer exists: the score tiles are computed
+ * twice.  Pointer, stride, alignment, d and scale rules are sdod_attention_f16's (q, k may be column offsets into packed qkv rows);
+ * lq, lk in [1, 4096], batch <= 1024, heads <= 64; no causal form.  Anything else is INVALID_ARGUMENT before any launch.
+ * ws: device memory of at least sdod_attention_mass_ws_bytes() bytes (0 for a shape the call refuses), 16-byte aligned, owned by the
+ * caller and free again once the call's work has run: one partial row per (batch, head, 64-query block), which a second launch adds
+ * in index order.  No atomics: two calls on the same inputs give the same bits. */
+SDOD_API int sdod_attention_mass_f16(const void* q, const void* k, float* mass_out, int batch, int heads, int lq, int lk, int d, int ldq,
+                                     int ldk, float scale, void* ws, size_t ws_bytes, void* stream);
+SDOD_API size_t sdod_attention_mass_ws_bytes(int batch, int heads, int lq, int lk);
+/* SAG's degraded UNet input in one launch (diffusers StableDiffusionSAGPipeline.sag_masking with pred_x0 and add_noise folded in):
+ *   x = x_stage / stage_scale ;  x0 = (x - b * e_u) / a
+ *   D = blur9(x0) where mass[img][(y >> 3) * (w / 8) + (x >> 3)] > 1.0 (strictly), x0 elsewhere
+ *   out = stage_scale * (a * D + b * e_u)
+ * blur9: separable 9-tap filter with REFLECT padding, row pass then column pass, fp32; taps: 9 weights on the HOST (diffusers'
+ * gaussian_blur_2d: exp(-0.5 k^2 / sigma^2) / sum, computed in double by the caller).  x_stage, out: fp32 NCHW [n][c][h][w], distinct;
+ * eps_u: fp16 NHWC [n][h][w][c]; mass: fp32 [n][(h / 8) * (w / 8)].  h, w multiples of 8 in [8, 4096]; a, stage_scale finite and
+ * non-zero. */
+SDOD_API int sdod_sag_degrade_f32(const float* x_stage, const void* eps_u, const float* mass, float* out, int n, int c, int h, int w,
+                                  float a, float b, float stage_scale, const float* taps, void* stream);
+/* SAG's third term folded into the pair prediction, in place: eps_pair fp16 [2][count] (the uncond half first when uncond_first != 0),
+ * eps_d fp16 [count]; cond <- fp16(cond + (s / g) * (uncond - eps_d)) in fp32, uncond untouched.  CFG of the result with scale g, in
+ * either mode of sdod_cfg_combine, is e_u + g (e_c - e_u) + s (e_u - e_d).  g == 0 or a non-finite s / g is INVALID_ARGUMENT;
+ * s / g == 0 launches nothing and leaves every bit as it was. */
+SDOD_API int sdod_sag_fold_f16(void* eps_pair, const void* eps_d, size_t count, int uncond_first, float s, float g, void* stream);
+
+/* Folded cross-attention, the once-per-prompt part. The text context is constant over the sampler run, so to_q and to_out can
  * be multiplied into K and V: scores_h = LN(x) . W1_h with W1_h = Wq_h^T K_h^T, out = [P_1 | .. | P_H] . [W2_1 ; .. ; W2_H] with
  * W2_h = V_h Wo_h^T -- two GEMMs per evaluation (sdod_gemm_desc: w_img_stride / vec_img_stride / softmax_cols) instead of
  * Linear + attention + Linear (the reference's /attn2/to_q, /attn2/MatMul, /attn2/to_out.0 ops, analyze_results.py:69-79).

@@ -100,6 +100,10 @@ public:
     // HyperTile (include/sdod_engine.h): enable_hypertile() before finalize() makes spatial_transformer() run attn1 inside the tiles
     // sdod_hypertile_grid gives for its level; no parameter, no input
     void enable_hypertile(int tile, int max_depth);
+    // Self-Attention Guidance (include/sdod_engine.h): enable_sag() before finalize() makes spatial_transformer() launch
+    // sdod_attention_mass_f16 behind middle_block.1's qkv GEMM and gives the graph one more output, slot sag_output() (-1 without)
+    void enable_sag();
+    int sag_output() const { return sag_ ? sag_output_ : -1; }
     // skip_static: the inputs marked "static across a sampler run" (UNet: the text context) are unchanged since the
     // previous execute(), so the launches that depend only on them (all cross-attention K/V projections) are skipped
     void execute(hipStream_t st, bool use_hip_graph, bool skip_static = false);
@@ -123,6 +127,9 @@ private:
     void freeu_site(const Act& h, const Act& skip, const float* params, int stage);
     int hypertile_ = 0;                  // HyperTile of the UNET / CONTROLNET graph (enable_hypertile()): tile side in latent pixels, 0 = off ...
     int hypertile_depth_ = 0;            // ... and the deepest UNet level whose self-attention is tiled
+    bool sag_ = false;                   // SAG of the UNET graph (enable_sag()): the attention mass of middle_block.1's attn1 ...
+    int sag_output_ = -1;                // ... on this output slot, fp32 [batch][L_mid], behind every other output
+    float* sag_mass_ = nullptr;
     bool has_kv() const { return kind_ == SDOD_GRAPH_UNET || kind_ == SDOD_GRAPH_CONTROLNET; } // owns kv_all_ and the static K/V GEMM
     int batch_;
     Mode mode_ = DECLARE;
@@ -290,6 +297,9 @@ private:
     // self-attention inside the th x tw tiles of B [h * w][ld] token maps (sdod_attention_tiled_f16): one launch, label attn_tiled_d<d>
     void attention_tiled(const f16* q, const f16* k, const f16* v, f16* out, int B, int heads, int h, int w, int th, int tw, int d,
                          int ldq, int ldk, int ldv, int ldo);
+
+    // the attention mass of q, k (sdod_attention_mass_f16) into mass[B][lk]; its partial rows live in the arena for the launch: label attn_mass_d<d>
+    void attention_mass(const f16* q, const f16* k, float* mass, int B, int heads, int lq, int lk, int d, int ldq, int ldk);
 
     // ---- model blocks
     Act res_block(const std::string& pfx, const Act& x, const Act* x2, int cout, const f16* emb_all, int emb_ld, int& emb_off);

@@ -1104,6 +1104,17 @@ void Graph::attention_tiled(const f16* q, const f16* k, const f16* v, f16* out, 
              std::to_string(h / th) + "x" + std::to_string(w / tw) + " tile" + std::to_string(th) + "x" + std::to_string(tw));
 }
 
+void Graph::attention_mass(const f16* q, const f16* k, float* mass, int B, int heads, int lq, int lk, int d, int ldq, int ldk) {
+    const float scale = 1.0f / sqrtf((float)d);
+    const size_t ws_bytes = sdod_attention_mass_ws_bytes(B, heads, lq, lk);
+    SDOD_REQUIRE(ws_bytes > 0, "SAG: the middle map must have at most 4096 tokens");
+    void* ws = alloc(ws_bytes / sizeof(f16));
+    emit([=](hipStream_t st) { check_rc(sdod_attention_mass_f16(q, k, mass, B, heads, lq, lk, d, ldq, ldk, scale, ws, ws_bytes, st)); },
+         "attn_mass_d" + std::to_string(d), 4.0 * B * heads * (double)lq * lk * d, 2.0 * B * heads * d * (lq + (double)lk) + 4.0 * B * lk,
+         "B" + std::to_string(B) + " h" + std::to_string(heads) + " lq" + std::to_string(lq) + " lk" + std::to_string(lk));
+    release(ws);
+}
+
 // ------------------------------------------------------------------------------------------ finalize / run
 void Graph::build() {
     quant_global(); // (the UNet builder narrows it block by block: quant_rows())
@@ -1220,6 +1231,12 @@ void Graph::enable_hypertile(int tile, int max_depth) {
     SDOD_REQUIRE(max_depth >= 0 && max_depth <= 3, "HyperTile: max_depth must be in [0, 3]");
     hypertile_ = tile;
     hypertile_depth_ = max_depth;
+}
+
+void Graph::enable_sag() {
+    SDOD_REQUIRE(kind_ == SDOD_GRAPH_UNET, "SAG applies to the UNET graph only");
+    SDOD_REQUIRE(!finalized_, "enable_sag() must be called before finalize()");
+    sag_ = true;
 }
 
 void Graph::set_loras(const sdod_lora_entry* entries, int count, hipStream_t st) {
@@ -1849,6 +1866,22 @@ extern "C" int sdod_graph_enable_hypertile(void* graph, int tile, int max_depth)
     SDOD_TRY
     SDOD_REQUIRE(graph != nullptr, "null graph");
     static_cast<Graph*>(graph)->enable_hypertile(tile, max_depth);
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_enable_sag(void* graph) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr, "null graph");
+    static_cast<Graph*>(graph)->enable_sag();
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_sag_output(void* graph, int* index) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr && index != nullptr, "null argument");
+    *index = static_cast<Graph*>(graph)->sag_output();
     return 0;
     SDOD_CATCH
 }

@@ -206,6 +206,8 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
     if (th > 0 && (cfg_.latent_h >> level) == x.h && (cfg_.latent_w >> level) == x.w)
         attention_tiled(qkv, qkv + C, qkv + 2 * C, a1, B, heads, x.h, x.w, th, tw, d, 3 * C, 3 * C, 3 * C, C);
     else attention(qkv, qkv + C, qkv + 2 * C, a1, B, heads, L, L, d, 3 * C, 3 * C, 3 * C, C, false);
+    // SAG: the middle block's attention mass from the same packed rows -- over the whole map, tiled or not
+    if (sag_ && pfx == "middle_block.1") attention_mass(qkv, qkv + C, sag_mass_, B, heads, L, L, d, 3 * C, 3 * C);
     release(qkv);
     Act t1 = act(B, 1, L, C);
     { GemmOpt o; o.bias = o1b; o.residual = t0.p; linear(a1, rows, C, o1w, C, t1.p, o); }
@@ -556,6 +558,11 @@ void Graph::build_unet() {
         freeu_params = fp;
     }
     f16* e_out = (f16*)io_alloc(outputs_, (size_t)B * H * Wd * LC * sizeof(f16));
+    // SAG: the attention mass of the middle block, fp32 [B][H / 8 * W / 8], behind every other output
+    if (sag_) {
+        if (mode_ == REAL) sag_output_ = (int)outputs_.size();
+        sag_mass_ = (float*)io_alloc(outputs_, (size_t)B * (H / 8) * (Wd / 8) * sizeof(float));
+    }
     Act ctx;
     ctx.p = ctx_in; ctx.n = B; ctx.h = 1; ctx.w = CL; ctx.c = cd;
     (void)EC;

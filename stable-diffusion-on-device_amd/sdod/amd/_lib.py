@@ -173,6 +173,10 @@ def _declare(lib):
         'sdod_attention_wide_dim_ok': (c_int, [c_int]),
         'sdod_attention_wide_splits': (c_int, [c_int, c_int, c_int, c_int]),
         'sdod_attention_wide_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+        'sdod_attention_mass_f16': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P, c_size_t, P]),
+        'sdod_attention_mass_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+        'sdod_sag_degrade_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, ctypes.POINTER(c_float), P]),
+        'sdod_sag_fold_f16': (c_int, [P, P, c_size_t, c_int, c_float, c_float, P]),
         'sdod_xattn_fold_ok': (c_int, [c_int, c_int, c_int, c_int]),
         'sdod_xattn_fold_f16': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
         'sdod_xattn_fold_regions_f16': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
@@ -257,6 +261,7 @@ HIP_SYMBOLS = [
     'sdod_lcm_step', 'sdod_guidance_features_f16',
     'sdod_attention_wide_f16', 'sdod_attention_wide_ws_f16', 'sdod_attention_wide_dim_ok', 'sdod_attention_wide_splits', 'sdod_attention_wide_ws_bytes',
     'sdod_attention_tiled_f16', 'sdod_hypertile_grid',
+    'sdod_attention_mass_f16', 'sdod_attention_mass_ws_bytes', 'sdod_sag_degrade_f32', 'sdod_sag_fold_f16',
 ]
 
 

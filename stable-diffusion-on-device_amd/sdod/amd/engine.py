@@ -150,6 +150,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_create_control', 'sdod_graph_bind_output', 'sdod_graph_create_regions',
     'sdod_graph_create_ip', 'sdod_graph_create_vision',
     'sdod_graph_enable_freeu', 'sdod_graph_freeu_input', 'sdod_graph_enable_hypertile',
+    'sdod_graph_enable_sag', 'sdod_graph_sag_output',
     'sdod_graph_set_networks',
     'sdod_graph_create_lcm',
     'sdod_graph_create_vae', 'sdod_graph_create_opts',
@@ -200,6 +201,8 @@ def _engine():
         lib.sdod_graph_enable_freeu.argtypes = [P]
         lib.sdod_graph_enable_hypertile.argtypes = [P, I, I]
         lib.sdod_graph_freeu_input.argtypes = [P, ctypes.POINTER(I)]
+        lib.sdod_graph_enable_sag.argtypes = [P]
+        lib.sdod_graph_sag_output.argtypes = [P, ctypes.POINTER(I)]
         lib._sdod_engine_typed = True
     return lib
 
@@ -356,6 +359,18 @@ class Graph:
         check(self._lib.sdod_graph_enable_hypertile(self._h, int(tile), int(max_depth)))
         return self
 
+    def enable_sag(self):
+        """before finalize(), UNET graphs only: the graph launches the attention-mass kernel in its middle block and gets the output
+        UNet.sag_mass"""
+        check(self._lib.sdod_graph_enable_sag(self._h))
+        return self
+
+    def sag_output(self):
+        """index of the attention-mass output, -1 for a graph without the switch"""
+        i = ctypes.c_int()
+        check(self._lib.sdod_graph_sag_output(self._h, ctypes.byref(i)))
+        return i.value
+
     def freeu_input(self):
         """index of the FreeU parameter input, -1 for a graph without the switch"""
         i = ctypes.c_int()
@@ -511,8 +526,12 @@ class Graph:
 
 
 class UNet(Graph):
-    def __init__(self, cfg, batch, device='cuda:0', wrap=None):
+    def __init__(self, cfg, batch, device='cuda:0', wrap=None, sag=False):
+        """sag=True: Self-Attention Guidance's switch (sdod_graph_enable_sag) -- the finalized graph has .sag_mass, fp32
+        [batch, latent_h / 8 * latent_w / 8], the attention mass of middle_block.1's attn1"""
         super().__init__(UNET, cfg, batch, device, wrap if wrap is not None else (int(getattr(cfg, 'tiling', 0)) or None))
+        if sag:
+            self.enable_sag()
 
     def finalize(self):
         super().finalize()
@@ -542,6 +561,9 @@ class UNet(Graph):
         fi = self.freeu_input()
         if fi >= 0:                 # FreeU: (b1, s1, b2, s2, version, 0, 0, 0) behind every other input, the identity until set (freeu.params)
             self.freeu = self.io_tensor(False, fi, (8,), torch.float32)
+        si = self.sag_output()
+        if si >= 0:                 # SAG: the middle block's attention mass behind every other output
+            self.sag_mass = self.io_tensor(True, si, (b, (c.latent_h // 8) * (c.latent_w // 8)), torch.float32)
         return self
 
 

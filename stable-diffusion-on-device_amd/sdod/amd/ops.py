@@ -431,6 +431,69 @@ def attention_tiled(q, k, v, heads, hw, tile_hw, out=None, scale=None):
     return out
 
 
+def attention_mass(q, k, heads, scale=None, out=None):
+    """Self-Attention Guidance's attention mass (include/sdod_hip.h: sdod_attention_mass_f16): q [B, Lq, heads * d], k [B, Lk, heads * d]
+    fp16, contiguous or column slices of wider rows (the packed qkv tensor) -> fp32 [B, Lk], the softmax probability every key collects,
+    averaged over heads and summed over queries.  scale defaults to d ** -0.5.  Bit-reproducible call to call."""
+    lib = _lib.hip()
+    ldq, ldk = _rows_view(q, 'q'), _rows_view(k, 'k')
+    b, lq, c = q.shape
+    lk = k.shape[1]
+    if k.shape != (b, lk, c) or heads <= 0 or c % heads:
+        raise ValueError(f'q and k must be [B, L, heads * d] of one batch and width, got {tuple(q.shape)} and {tuple(k.shape)} with {heads} heads')
+    if out is None:
+        out = torch.empty(b, lk, dtype=torch.float32, device=q.device)
+    _req(out, torch.float32, 'out')
+    if out.shape != (b, lk):
+        raise ValueError(f'out must be {(b, lk)}, got {tuple(out.shape)}')
+    d = c // heads
+    ws_bytes = lib.sdod_attention_mass_ws_bytes(b, heads, lq, lk)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)   # (freed on this stream: the caching allocator orders it)
+    check(lib.sdod_attention_mass_f16(_p(q), _p(k), _p(out), b, heads, lq, lk, d, ldq, ldk, d ** -0.5 if scale is None else scale, _p(ws),
+                                      ws.numel(), _stream()))
+    return out
+
+
+def sag_taps(sigma=1.0, radius=4):
+    """the normalised Gaussian taps of diffusers' gaussian_blur_2d (kernel_size 2 * radius + 1), computed in double"""
+    import math
+    pdf = [math.exp(-0.5 * (k / sigma) ** 2) for k in range(-radius, radius + 1)]
+    total = math.fsum(pdf)
+    return [v / total for v in pdf]
+
+
+_SAG_TAPS = (ctypes.c_float * 9)(*sag_taps())
+
+
+def sag_degrade(x_stage, eps_u, mass, a, b, stage_scale=1.0, out=None):
+    """SAG's degraded UNet input (include/sdod_hip.h: sdod_sag_degrade_f32): x_stage fp32 [n, c, h, w] holding stage_scale * x, eps_u the
+    fp16 NHWC prediction [n, h, w, c] of the uncond rows, mass fp32 [n, h / 8 * w / 8] -> stage_scale * (a * D + b * eps_u), where
+    D = blur9((x - b * eps_u) / a) at the pixels whose middle-map key has mass > 1 and the unblurred prediction elsewhere."""
+    lib = _lib.hip()
+    _req(x_stage, torch.float32, 'x_stage'); _req(eps_u, torch.float16, 'eps_u'); _req(mass, torch.float32, 'mass')
+    n, c, h, w = x_stage.shape
+    if eps_u.shape != (n, h, w, c) or mass.numel() != n * (h // 8) * (w // 8):
+        raise ValueError(f'eps_u must be {(n, h, w, c)} and mass hold {n} x {(h // 8) * (w // 8)} values, got {tuple(eps_u.shape)} and {tuple(mass.shape)}')
+    if out is None:
+        out = torch.empty_like(x_stage)
+    _req(out, torch.float32, 'out')
+    if out.shape != x_stage.shape:
+        raise ValueError(f'out must be {tuple(x_stage.shape)}, got {tuple(out.shape)}')
+    check(lib.sdod_sag_degrade_f32(_p(x_stage), _p(eps_u), _p(mass), _p(out), n, c, h, w, a, b, stage_scale, _SAG_TAPS, _stream()))
+    return out
+
+
+def sag_fold(eps_pair, eps_d, s, g, uncond_first=True):
+    """SAG's third term folded into the pair prediction in place (include/sdod_hip.h: sdod_sag_fold_f16): eps_pair fp16 [2n, ...],
+    eps_d fp16 [n, ...]; the cond rows become cond + (s / g) * (uncond - eps_d).  g == 0 is refused; s == 0 changes nothing."""
+    lib = _lib.hip()
+    _req(eps_pair, torch.float16, 'eps_pair'); _req(eps_d, torch.float16, 'eps_d')
+    if eps_pair.numel() != 2 * eps_d.numel():
+        raise ValueError(f'eps_pair must hold twice the values of eps_d, got {tuple(eps_pair.shape)} and {tuple(eps_d.shape)}')
+    check(lib.sdod_sag_fold_f16(_p(eps_pair), _p(eps_d), eps_d.numel(), 1 if uncond_first else 0, s, g, _stream()))
+    return eps_pair
+
+
 def attention_wide_splits(b, lq, lk, d):
     """key splits attention_wide() runs a [b, lq, d] x [b, lk, d] problem with (1 = one launch, no workspace); 0 = a shape it refuses"""
     return _lib.hip().sdod_attention_wide_splits(b, lq, lk, d)

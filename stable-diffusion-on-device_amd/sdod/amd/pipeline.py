@@ -17,6 +17,7 @@ from . import regions as RG
 from . import ip_adapter as IP
 from . import freeu as FU
 from . import hypertile as HT
+from . import sag as SG
 from . import upscale as UP
 from . import panorama as PN
 from .host import DpmSolver
@@ -60,12 +61,17 @@ class Txt2Img:
     guidance_embed = False      # ... and the TEMB graphs take the guidance scale w (Txt2Img(..., guidance_embed=True))
     lora_time_modules = False   # set_loras also adapts the time conditioning: the TEMB graphs keep their base weights
     _time_networks = ()         # ... the 'temb' entries of the current set_loras, for the TEMB graphs made later
+    sag_unet = None     # Self-Attention Guidance: the second UNet graph, one row per image (Txt2Img(..., sag=True)), or None
+    _sag_scale = 0.0            # ... set_sag's scale; 0 = off, the SAG pass is skipped
+    _sag_eval = None            # ... (a, b, stage_scale, g) of the next evaluation, set by the sampler just before _unet_eps()
+    _sag_ctx_fresh = True       # ... the second graph's own static-unchanged state
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
                  adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False, ip_adapter=False, canvas_hw=None,
-                 canvas_wrap=False, freeu=False, unguided=False, guidance_embed=False, lora_time_modules=False, vae_attention='auto', hypertile=None):
+                 canvas_wrap=False, freeu=False, unguided=False, guidance_embed=False, lora_time_modules=False, vae_attention='auto', hypertile=None,
+                 sag=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -174,8 +180,21 @@ class Txt2Img:
         self-attention of the levels the tile rule tiles inside tiles of about T latent pixels a side (one attn_tiled launch in place
         of the attn one; levels 0 .. max_depth, default 0).  A graph switch: it works with every entry point, sampler and other
         argument.  Anything but None, an int >= 8 or such a pair with max_depth in [0, 3]: ValueError before any device work
-        (hypertile.hypertile_check).  None: nothing is constructed or sized differently."""
+        (hypertile.hypertile_check).  None: nothing is constructed or sized differently.
+        sag=True: Self-Attention Guidance (sdod/amd/sag.py).  The pair UNet is built with the engine's switch (one more
+        launch, attn_mass_d<d>, and the output unet.sag_mass) and self.sag_unet = E.UNet(the same config, n rows) from the same 'unet'
+        weights: a second copy of them, sag_unet.stats() more device memory.  Off until set_sag(scale); after clear_sag() the SAG pass
+        is skipped and the images are the plain pipeline's, bit for bit.  While it is on, sample_plms and sample_k (and generate,
+        generate_graphed, generate_pipelined and img2img with a k-sampler on top of them) run it in every evaluation; sample_dpm, the DDIM
+        img2img / inpainting loops and the LCM entry points raise ValueError.  Composes with freeu (set_freeu writes both graphs),
+        hypertile, prompt_chunks, rectangular latent_hw, with_vae_encoder and upscaler.  Not with cfg_split, unguided, inpaint_unet,
+        hires_hw, canvas_hw, loras, controlnet, adapter, regions, ip_adapter, tiling, model='sd21' or uint8 weights: ValueError before
+        any device work (sag.sag_check_build).  False: nothing is constructed or sized differently."""
         fused_vae = vae_attention_check(vae_attention)
+        if weight_quant is None:     # uint8 codes in the UNet checkpoint (weights.QuantU8, the reference's QNN encoding) decide it
+            weight_quant = state_dicts is not None and any(hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts.get('unet', {}).values())
+        sag = SG.sag_check_build(sag, cfg_split, unguided, inpaint_unet, hires_hw, canvas_hw, loras, controlnet, adapter, regions, ip_adapter,
+                                 tiling, model, bool(weight_quant))
         lcm_check_build(unguided, guidance_embed, lora_time_modules, loras, cfg_split, inpaint_unet, hires_hw, adapter, controlnet, regions,
                         ip_adapter, canvas_hw)
         self.unguided, self.guidance_embed, self.lora_time_modules = bool(unguided), bool(guidance_embed), bool(lora_time_modules)
@@ -189,8 +208,6 @@ class Txt2Img:
         adapter_check_build(adapter, adapter_channels, cfg_split, hires_hw, inpaint_unet, model)
         control_check_build(controlnet, cfg_split, hires_hw, inpaint_unet, adapter, tiling, model)
         self.tiling = tiling_check_build(tiling, with_vae_encoder, inpaint_unet, hires_hw, adapter)
-        if weight_quant is None:     # uint8 codes in the UNet checkpoint (weights.QuantU8, the reference's QNN encoding) decide it
-            weight_quant = state_dicts is not None and any(hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts.get('unet', {}).values())
         self.regions = RG.regions_check_build(regions, self.prompt_chunks, cfg_split, hires_hw, controlnet, adapter, tiling, inpaint_unet,
                                               model, bool(regions) and weight_quant)
         if IP.ip_check_build(ip_adapter, regions, self.prompt_chunks, cfg_split, hires_hw, controlnet, adapter, tiling, inpaint_unet, model,
@@ -248,7 +265,11 @@ class Txt2Img:
         if self.tiling:                  # the UNet and the VAE decoder take the circular border; every other graph has no border to wrap
             vae_cfg = E.copy_config(self.cfg)
             unet_cfg.tiling = vae_cfg.tiling = self.tiling
-        self.unet = E.UNet(unet_cfg, self.n if cfg_split or self.unguided else 2 * self.n, device)
+        if sag:     # the pair graph with the switch, and the graph of the degraded latents: one row per image, the same switches
+            self.unet = E.UNet(unet_cfg, 2 * self.n, device, sag=True)
+            self.sag_unet = E.UNet(unet_cfg, self.n, device)
+        else:
+            self.unet = E.UNet(unet_cfg, self.n if cfg_split or self.unguided else 2 * self.n, device)
         self.vae = E.VaeDecoder(vae_cfg, 1, device, fused_attn=fused_vae) if with_vae else None
         self.text = E.TextEncoder(self.cfg, 2 * (self.regions or self.prompt_chunks), device) if with_text_encoder else None
         self.encoder = E.VaeEncoder(self.cfg, 1, device, fused_attn=fused_vae) if with_vae_encoder else None
@@ -267,7 +288,7 @@ class Txt2Img:
         self._dir = models_dir
         for g, key, stem in ((self.unet, 'unet', 'unet'), (self.vae, 'vae', 'vae_decoder'), (self.text, 'text', 'text_encoder'),
                              (self.encoder, 'vae_enc', 'vae_encoder'), (self.masked_encoder, 'vae_enc', 'vae_encoder'),
-                             (self.adapter, 'adapter', 'adapter'), (self.canvas_vae, 'vae', 'vae_decoder')):
+                             (self.adapter, 'adapter', 'adapter'), (self.canvas_vae, 'vae', 'vae_decoder'), (self.sag_unet, 'unet', 'unet')):
             if g is None:
                 continue
             self._load(g, key, stem)
@@ -501,6 +522,8 @@ class Txt2Img:
         FU.require(self)
         block = FU.freeu_check_args(b1, b2, s1, s2, version)
         self.unet.freeu.copy_(torch.tensor(block, dtype=torch.float32))
+        if self.sag_unet is not None:
+            self.sag_unet.freeu.copy_(self.unet.freeu)
         if self.hires is not None:
             self.hires.set_freeu(b1, b2, s1, s2, version)
 
@@ -508,8 +531,36 @@ class Txt2Img:
         """the identity, the state after construction: the FreeU launches end without reading or writing a tensor"""
         FU.require(self)
         self.unet.freeu.copy_(torch.tensor(FU.IDENTITY, dtype=torch.float32))
+        if self.sag_unet is not None:
+            self.sag_unet.freeu.copy_(self.unet.freeu)
         if self.hires is not None:
             self.hires.clear_freeu()
+
+    # ------------------------------------------------------------------ Self-Attention Guidance
+    def set_sag(self, scale=SG.DEFAULT_SCALE):
+        """turn Self-Attention Guidance on at `scale` (s of e_u + g (e_c - e_u) + s (e_u - e_d); the paper's and the front ends' default
+        0.75): every later evaluation of sample_plms / sample_k runs the SAG pass.  The scale is a launch argument, so a trajectory
+        captured by a *_graphed method is keyed by it.  0 is clear_sag().  ValueError for anything but a finite number in [0, 10]
+        (sag.sag_check_args), before any device work; RuntimeError without sag=True."""
+        SG.require(self)
+        self._sag_scale = SG.sag_check_args(scale)
+
+    def clear_sag(self):
+        """scale 0, the state after construction: the SAG pass is skipped and the images are the plain pipeline's, bit for bit"""
+        SG.require(self)
+        self._sag_scale = 0.0
+
+    def _sag_refuse(self, name):
+        """the entry points whose evaluations the SAG pass is not wired into refuse while it is on"""
+        if self._sag_scale:
+            raise ValueError(f'{name} does not run Self-Attention Guidance (SAG is wired into sample_plms and sample_k): clear_sag() first')
+
+    def _sag_stage(self, a, b, stage_scale, guidance):
+        """the sampler, just before _unet_eps(): x = a x0 + b eps at this evaluation, unet.x holds stage_scale * x, g the CFG scale"""
+        if self._sag_scale:
+            if not guidance:
+                raise ValueError('Self-Attention Guidance folds its term through the guidance scale: guidance must not be 0')
+            self._sag_eval = (float(a), float(b), float(stage_scale), float(guidance))
 
     # ------------------------------------------------------------------ regional prompts
     def set_regions(self, masks_u8):
@@ -741,6 +792,9 @@ class Txt2Img:
         if self.controlnet is not None:
             self.controlnet.ctx.copy_(self.unet.ctx)
             self._control_ctx_fresh = True
+        if self.sag_unet is not None:   # the degraded latents are evaluated under the uncond context
+            self.sag_unet.ctx.copy_(self.unet.ctx[:n])
+            self._sag_ctx_fresh = True
         self._ctx_fresh = True     # the next UNet execute must redo the cross-attention K/V projections
 
     def _exchange_halves(self, mine):
@@ -768,6 +822,18 @@ class Txt2Img:
                 self._control_ctx_fresh = False
         self.unet.execute(self.use_hip_graph, static_unchanged=not self._ctx_fresh)
         self._ctx_fresh = False
+        if self._sag_scale:
+            # SAG, behind the pair evaluation: the uncond rows' x0 blurred where the middle block's attention mass is above 1 and
+            # renoised, straight into the second graph's x; its time rows; its evaluation; s (e_u - e_d) folded into the cond rows
+            if self._sag_eval is None:
+                raise ValueError('this evaluation does not run Self-Attention Guidance (SAG is wired into sample_plms and sample_k): clear_sag() first')
+            (a, b, stage_scale, g), self._sag_eval = self._sag_eval, None
+            n, su = self.n, self.sag_unet
+            ops.sag_degrade(self.unet.x[:n], self.unet.eps[:n], self.unet.sag_mass[:n], a, b, stage_scale, out=su.x)
+            su.temb.copy_(self.unet.temb[:n])
+            su.execute(self.use_hip_graph, static_unchanged=not self._sag_ctx_fresh)
+            self._sag_ctx_fresh = False
+            ops.sag_fold(self.unet.eps, su.eps, self._sag_scale, g)
         return self._exchange_halves(self.unet.eps) if self.cfg_split else self.unet.eps
 
     def _eps(self, x, temb_row, guidance, mode, v_coef=None):
@@ -798,6 +864,7 @@ class Txt2Img:
                 # and the staging of the next evaluation's inputs (ops.plms_update = the four separate launches, bit for bit)
                 if not staged:
                     ops.stage_unet_inputs(x, self.unet.x, temb[index], self._temb_dst)
+                self._sag_stage(*sch.v_to_eps_coef(index), 1.0, guidance)
                 eps = self._unet_eps()
                 k = min(len(old), 3)
                 coefs, div = PLMS_ORDERS[k]
@@ -810,10 +877,12 @@ class Txt2Img:
                     trace.append((int(step), index))
                 continue
             # first step (pseudo improved Euler, two evaluations): the separate launches
+            self._sag_stage(*sch.v_to_eps_coef(index), 1.0, guidance)
             e_t = self._eps(x, temb[index], guidance, mode=1, v_coef=vc)
             x_pred = x.clone()
             ops.ddim_step(x_pred, e_t, **sch.coef(index))
             nxt = max(index - 1, 0)
+            self._sag_stage(*sch.v_to_eps_coef(nxt), 1.0, guidance)
             e_next = self._eps(x_pred, temb[nxt], guidance, mode=1, v_coef=sch.v_to_eps_coef(nxt) if self.v_prediction else None)
             e_prime = ops.lincomb4([e_t, e_next], [1.0, 1.0], 2.0)
             ops.ddim_step(x, e_prime, **sch.coef(index))
@@ -826,6 +895,7 @@ class Txt2Img:
     def sample_dpm(self, ctx2, x_T, steps=20, guidance=7.5):
         """the reference driver's sampler: DPM-Solver++(2M), CFG as g*e_c + (1-g)*e_u (context.cpp:342-382)"""
         self._require_pairs('sample_dpm')
+        self._sag_refuse('sample_dpm')
         solver = DpmSolver()
         model_ts = solver.prepare(steps)
         temb = self.time_embeddings(model_ts[:steps])
@@ -863,6 +933,7 @@ class Txt2Img:
                    stage=(self.unet.x, temb[first], self._temb_dst))
         for i in range(first, steps):
             cf = sch.coef(sampler, i, eta, self.v_prediction, first)
+            self._sag_stage(1.0, sch.sigmas[i], sch.c_in(i), guidance)
             ops.k_step(self._unet_eps(), x, cf, guidance, den_prev=den_prev,
                        noise=step_noise[i - first] if step_noise is not None and cf['u'] != 0.0 else None,
                        seed=seed, noise_level=i, image_index=image_index, mode=1,
@@ -881,6 +952,7 @@ class Txt2Img:
         behind step i: step_noise[i] (fp32 [steps - 1, n, 4, H, W]; the last step draws none) or Philox on the device, stream
         ((3 + i) << 32) | (image_index + k) of `seed` for image k.  return_denoised=True: (x, den) with den the last step's x0
         prediction.  Argument errors raise ValueError before any device work (lcm_check_args)."""
+        self._sag_refuse('sample_lcm')
         g, w = lcm_check_args(self, x, steps, guidance, original_steps, strength, step_noise)
         sch = LcmSchedule(int(steps), int(original_steps), float(strength))
         temb = self.time_embeddings(sch.timesteps.astype(np.float32), w)   # row i <-> step i
@@ -980,6 +1052,7 @@ class Txt2Img:
         replay plus that launch; with more, two device copies per further evaluation.  Only the k-samplers: 'plms' and 'dpm' raise
         ValueError, as every other argument error does before any device work."""
         self._require_pairs('sample_panorama')
+        self._sag_refuse('sample_panorama')
         plan = self._panorama_plan(x_T, sampler, steps, schedule, eta, stride, weights, step_noise)
         sch = KSchedule(steps, schedule)
         temb = self.time_embeddings(sch.times)                             # row i <-> step i
@@ -1092,6 +1165,8 @@ class Txt2Img:
             self._traj = {}
         if self._control_on:                    # a capture made with the control graph in it is another trajectory than one without
             key = (key, 'control')
+        if self._sag_scale:                     # ... and so is one with the SAG pass in it, whose scale is a launch argument
+            key = (key, 'sag', self._sag_scale)
         if key not in self._traj:
             statics = [torch.zeros(tuple(shape), dtype=dtype, device=self.device) for shape, dtype in inputs]
             pipes = [self] if self.hires is None else [self, self.hires]
@@ -1240,6 +1315,7 @@ class Txt2Img:
     def sample_ddim_from(self, ctx2, x, t_enc, steps=50, guidance=7.5, trace=None):
         """ldm DDIMSampler.decode: t_enc DDIM steps (eta = 0, CFG mode 1) from ddim index t_enc - 1 down to 0"""
         self._require_pairs('sample_ddim_from')
+        self._sag_refuse('sample_ddim_from (DDIM img2img)')
         sch = PlmsSchedule(steps)
         temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
         self._set_context(ctx2)
@@ -1298,6 +1374,7 @@ class Txt2Img:
         One staging launch in front of the loop, then per step the UNet replay and ONE launch (ops.ddim_inpaint_step = cfg_combine
         + ddim_step + the blend + stage_unet_inputs, bit for bit)."""
         self._require_pairs('sample_ddim_inpaint')
+        self._sag_refuse('sample_ddim_inpaint')
         sch = PlmsSchedule(steps)
         temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
         self._set_context(ctx2)
@@ -1429,6 +1506,7 @@ class Txt2Img:
         row r = step first + r) or families 3 + step of hires_seed.  hires_steps and hires_seed have no defaults here: generate_hires
         owns them (steps and seed + 1).  Argument errors raise ValueError before any device work."""
         self._require_pairs('hires_from_latent')
+        self._sag_refuse('hires_from_latent')
         if not isinstance(z_lo, torch.Tensor) or z_lo.dim() != 4 or tuple(z_lo.shape[1:]) != self._latent_shape:
             raise ValueError(f'z_lo must be a tensor [n, {", ".join(str(v) for v in self._latent_shape)}], got {tuple(getattr(z_lo, "shape", ()))}')
         t_enc = hires_check_args(self, z_lo.shape[0], sampler, hires_steps, denoise, upscaler, schedule, eta, hires_noise, hires_step_noise)

@@ -67,6 +67,8 @@ def cases(E):
         'image_encoder_small': (lambda: E.ImageEncoder(vision, 1), ['img'], ['out']),
         'image_proj': (lambda: E.ImageProj(sd14(16), 64, 4, 2), ['embeds'], ['out']),
     }
+    if hasattr(E.Graph, 'enable_sag'):    # a switch by constructor argument: a tree from before it prints every other case and not this one
+        out['unet_sd14_sag'] = (lambda: E.UNet(sd14(16), 2, sag=True), ['x', 'temb', 'ctx'], ['eps', 'sag_mass'])
     return out
 
 
