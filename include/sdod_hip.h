@@ -250,8 +250,12 @@ SDOD_API int sdod_ln_fold_f16(void* w, int n, int k, int ldw, const float* gamma
                               float* s_out, float* t_out, void* stream);
 /* Composes two Linear layers that follow each other with nothing in between, y = P (W x + bw) + bp, into one (one-time, at
  * graph build): c[o][k] = sum_j p[o][j] w[j][k] (fp32 accumulate, rounded to fp16 once), bias_out[o] = sum_j p[o][j] bw[j]
- * + bp[o].  p: fp16 [n_out][ldp] (n_mid columns), w: fp16 [n_mid][ldw] (k columns), c: fp16 [n_out][ldc]; c must not alias
- * p or w.  The UNet uses it for transformer_blocks.0.ff.net.2 -> proj_out (analyze_results.py:69-79 lists them as two ops). */
+ * + bp[o].  p: fp16 [n_out][ldp] (n_mid columns), w: fp16 [n_mid][ldw] (k columns), c: fp16 [n_out][ldc], of which only columns
+ * [0, k) are written.  w must not overlap the span c is written in (first to last written element; INVALID_ARGUMENT if it does:
+ * every output row reads all of w).  p may share c's rows as a column block at columns >= k -- the graph engine keeps
+ * [P W | P] in one [n_out][ldc] matrix and composes from a copy of the W block -- but must not touch the k written columns
+ * (only c == p is refused).  bias_w / bias_p NULL count as zero; bias_out NULL: no bias is written.
+ * The UNet uses it for transformer_blocks.0.ff.net.2 -> proj_out (analyze_results.py:69-79 lists them as two ops). */
 SDOD_API int sdod_compose_linear_f16(const void* p, int ldp, const void* w, int ldw, void* c, int ldc, int n_out, int n_mid, int k,
                                      const float* bias_w, const float* bias_p, float* bias_out, void* stream);
 /* Low-rank (LoRA) update of a packed fp16 weight matrix, in place:

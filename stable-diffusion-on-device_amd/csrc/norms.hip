@@ -1395,7 +1395,12 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(f16* w, int N, int K, int 
     for (int k = threadIdx.x; k < K; k += 256) {
         const float wv = (float)row[k];
         t += beta[k] * wv;
-        const f16 folded = (f16)(wv * gamma[k]);
+        float prod = wv * gamma[k];
+        // pins the fp32 product in a register (as f16_rn in elementwise.hip): for fptrunc(fmul) the compiler selects
+        // v_fma_mixlo_f16 with a +0 addend, which rounds the exact product once and turns a -0.0 weight into +0.0 -- neither
+        // is the fp16(W * gamma) the header states
+        asm volatile("" : "+v"(prod));
+        const f16 folded = (f16)prod;
         row[k] = folded;
         sacc += (float)folded;
     }
@@ -1724,6 +1729,13 @@ extern "C" int sdod_compose_linear_f16(const void* p, int ldp, const void* w, in
     SDOD_TRY
     SDOD_REQUIRE(p && w && c && n_out > 0 && n_mid > 0 && k > 0 && ldp >= n_mid && ldw >= k && ldc >= k, "bad argument");
     SDOD_REQUIRE(c != w && c != p, "the composed matrix must not alias its factors");
+    {
+        // every output row reads every row of w while other workgroups store theirs: w may not touch the span c is written in,
+        // first to last element.  (p may: the engine keeps it in c's own rows, at columns >= k, which no thread writes.)
+        const uintptr_t c0 = (uintptr_t)c, c1 = c0 + ((size_t)(n_out - 1) * ldc + k) * sizeof(f16);
+        const uintptr_t w0 = (uintptr_t)w, w1 = w0 + ((size_t)(n_mid - 1) * ldw + k) * sizeof(f16);
+        SDOD_REQUIRE(w1 <= c0 || c1 <= w0, "the composed matrix must not overlap w (compose from a copy of the block)");
+    }
     SDOD_LAUNCH(compose_linear_kernel, dim3((k + 255) / 256, n_out), dim3(256), 0, (hipStream_t)stream, (const f16*)p, ldp, (const f16*)w, ldw,
                 (f16*)c, ldc, n_out, n_mid, k, bias_w, bias_p, bias_out);
     SDOD_HIP_CHECK(hipGetLastError());
