@@ -415,6 +415,18 @@ SDOD_API int sdod_graph_enable_hypertile(void* graph, int tile, int max_depth);
 SDOD_API int sdod_graph_enable_sag(void* graph);
 SDOD_API int sdod_graph_sag_output(void* graph, int* index);
 
+/* ---- Reference-only control (the reference_only preprocessor of A1111's ControlNet extension): a switch in the same
+ * pattern.  sdod_graph_enable_reference (kind UNET, before sdod_graph_finalize, anchors 1 or 2 with batch - anchors a positive multiple
+ * of anchors, on a graph without HyperTile, SAG, adapter inputs, control inputs, regions, image prompts or concat_channels; anything
+ * else is INVALID_ARGUMENT, and so are the HyperTile and SAG switches after this one): the last `anchors` rows of the graph's batch are
+ * the reference's, and every transformer block's self-attention (attn1) runs sdod_attention_shared_f16 (include/sdod_hip.h), one
+ * launch, label attn_shared_d<d>, in place of the attn_d<d> launch: the first batch - anchors rows form `anchors` consecutive groups
+ * and group g also attends to the keys of anchor row g.  The graph gets one more input behind every other one (FreeU's included):
+ * reference_self_w, fp32 [anchors], the weight of the self-only result in each group; 1 after finalize, at which every row has the bits
+ * of the graph without the switch.  The kernel reads it on the device: a captured hipGraph follows new values.  Cross-attention is
+ * untouched.  A graph without the switch is what it was: same launch list, arena, inputs and bits. */
+SDOD_API int sdod_graph_enable_reference(void* graph, int anchors);
+
 #ifdef __cplusplus
 }
 #endif

@@ -310,6 +310,17 @@ SDOD_API int sdod_attention_head_dim_ok(int d);
  * contiguous tensor, and a 1 x 1 grid (th = h, tw = w) equals it on the whole map. */
 SDOD_API int sdod_attention_tiled_f16(const void* q, const void* k, const void* v, void* out, int batch, int heads, int h, int w,
                                       int th, int tw, int d, int ldq, int ldk, int ldv, int ldo, float scale, void* stream);
+/* Shared-key self-attention (reference-only control): q, k, v, out are [batch][l][ld] and the last `anchors` (1 or 2)
+ * sequences are anchors.  The batch - anchors main sequences form `anchors` equal consecutive groups, and a sequence of group g gets
+ *   out = w_g * softmax(scale q K_own^T) V_own + (1 - w_g) * softmax(scale q [K_own ; K_anc]^T) [V_own ; V_anc]
+ * with K_anc / V_anc the rows of sequence batch - anchors + g, read where they lie.  The anchor sequences attend to their own keys.
+ * self_w: `anchors` fp32 values in DEVICE memory, read by the kernel (a captured launch follows a new value).  w_g = 1 is plain
+ * self-attention -- those sequences and the anchors are bit for bit sdod_attention_f16's result on the same buffers -- and w_g = 0
+ * the shared softmax alone.  Pointer, stride, alignment, d and scale rules are sdod_attention_f16's; a null self_w, anchors outside
+ * {1, 2} or batch - anchors not a positive multiple of anchors is INVALID_ARGUMENT before any launch.  One launch.  For 0 < w_g < 1
+ * the kernel parks an intermediate in the sequence's own out rows: out must not alias k or v (q is fine, as for the call above). */
+SDOD_API int sdod_attention_shared_f16(const void* q, const void* k, const void* v, void* out, int batch, int heads, int l, int d,
+                                       int ldq, int ldk, int ldv, int ldo, float scale, int anchors, const float* self_w, void* stream);
 /* HyperTile's tile rule, the one statement of it.  h x w is the level-0 token map (the latent), tile the requested tile side in
  * latent pixels (>= 8), level the UNet level (its map is (h >> level) x (w >> level)), max_depth in [0, 3] the deepest level that is
  * tiled.  Per axis the tile COUNT is fixed at level 0 -- nh = h / th0 with th0 the smallest divisor of h that is >= min(tile, h),

@@ -1,7 +1,8 @@
-// attention_kernel.h -- the fused attention kernel (attention.hip has the design notes) and its dispatch, shared by the two files that
-// instantiate it: attention.hip (sdod_attention_f16: a sequence is Lk consecutive rows) and attention_tiled.hip
-// (sdod_attention_tiled_f16: a sequence is one th x tw tile of an h x w token map, walked in place).  Which of the two is a template
-// parameter, TILED: it changes how a row index becomes an address and nothing else.
+// attention_kernel.h -- the fused attention kernel (attention.hip has the design notes) and its dispatch, shared by the three files that
+// instantiate it: attention.hip (sdod_attention_f16: a sequence is Lk consecutive rows), attention_tiled.hip
+// (sdod_attention_tiled_f16: a sequence is one th x tw tile of an h x w token map, walked in place) and attention_shared.hip
+// (sdod_attention_shared_f16: a sequence walks its own keys and then an anchor sequence's).  Which of the three is a template
+// parameter: TILED changes how a row index becomes an address and nothing else, SHARED which key tiles the loop visits (below).
 #pragma once
 #include "common.h"
 #include "sdod_hip.h"
@@ -33,6 +34,13 @@ struct AttnTP : AttnP {
     int th, tw;        // tile sides
     int ntx, ntiles;   // tiles per map row; tiles per image
     int step_y[2], step_x[2]; // (64 * KVS) / tw and (64 * KVS) % tw for KVS = 1, 2
+};
+// SHARED (attention_shared.hip has the design notes): the last `anchors` of the B sequences are anchor sequences and the B - anchors
+// main ones form `anchors` consecutive groups of `per`; a main sequence of group a walks its own Lk keys and then the Lk keys of
+// sequence B - anchors + a, and blends the softmax over the first segment with the softmax over both by self_w[a].
+struct AttnSP : AttnP {
+    int anchors, per;
+    const float* self_w; // device memory, [anchors]: read by the kernel, so a captured launch follows the value
 };
 SDOD_DEVICE int tile_row(const AttnTP& p, int j) {
     const int y = j / p.tw;
@@ -67,8 +75,10 @@ SDOD_DEVICE void static_for(F&& f) {
 // (own LDS stages), and merge their (max, sum, O) through LDS at the end.  For the launches whose grid is one workgroup per CU
 // (d = 80 at 32x32: 256 workgroups) the tile loop is a latency-bound chain on one wave per SIMD; a second group halves the
 // chain and doubles the waves that hide it, at the same K/V traffic.
-template <int D, int QT, bool TR, int KVS = 1, bool TILED = false>
-__global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_kernel(const std::conditional_t<TILED, AttnTP, AttnP> p) {
+template <int D, int QT, bool TR, int KVS = 1, bool TILED = false, bool SHARED = false>
+__global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_kernel(
+    const std::conditional_t<TILED, AttnTP, std::conditional_t<SHARED, AttnSP, AttnP>> p) {
+    static_assert(!(TILED && SHARED), "one variant at a time");
     constexpr int DP = ((D + 31) / 32) * 32; // QK^T contraction, padded to MFMA K=32
     constexpr int KSTEPS = DP / 32;
     constexpr int DV = ((D + 15) / 16) * 16; // PV output columns, padded to 16
@@ -114,7 +124,7 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
 
     // TILED: b is an (image, tile) pair -- the query blocks of one (image, tile, head) are consecutive logical ids just the same, so
     // a tile's K/V stream through one L2 -- and row0 the tile's first pixel, in rows of the token map; there is no causal form
-    const int causal = TILED ? 0 : p.causal;
+    const int causal = (TILED || SHARED) ? 0 : p.causal;
     size_t row0 = 0;
     if constexpr (TILED) {
         const int img = b / p.ntiles, tl = b - img * p.ntiles;
@@ -123,6 +133,22 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
     }
     const f16* kbase = p.k + (TILED ? row0 : (size_t)b * p.Lk) * p.ldk + h * D;
     const f16* vbase = p.v + (TILED ? row0 : (size_t)b * p.Lk) * p.ldv + h * D;
+
+    // SHARED: this workgroup's blend weight and where its second key segment lies, in rows behind its own first key (the anchors
+    // are the last sequences: never negative).  All of it is workgroup-uniform: w == 1 and the anchor sequences themselves walk one
+    // segment -- the plain kernel's loop, bit for bit -- and w == 0 walks two without a snapshot.
+    float self_w = 1.f;
+    size_t seg_rows = 0;
+    if constexpr (SHARED) {
+        const int nmain = p.B - p.anchors;
+        if (b < nmain) {
+            const int ga = b / p.per;
+            self_w = p.self_w[ga];
+            seg_rows = (size_t)(nmain + ga - b) * p.Lk;
+        }
+    }
+    const bool two_segments = SHARED && self_w != 1.f;
+    const bool blend = two_segments && self_w != 0.f;
 
     // zero the padded columns of both stages once (they are never overwritten by the staging stores)
     {
@@ -192,7 +218,8 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
             vptr0[i] = vbase + (size_t)row * p.ldv + ch * 8;
         }
     }
-    auto load_tile = [&](int t) {
+    // t: the tile inside its segment; seg: the segment's first key, in rows behind kbase / vbase (SHARED: the anchor's; else 0)
+    auto load_tile = [&](int t, size_t seg = 0) {
         if constexpr (TILED) {
             auto at = [](const f16* base, unsigned bytes) { return reinterpret_cast<const f16*>(reinterpret_cast<const char*>(base) + bytes); };
             // the same two forms as below: a tile inside the sequence loads unpredicated, a ragged one zero-fills key by key
@@ -226,7 +253,7 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
         // zero fill: the lanes past the tile's 16-byte pieces keep whatever their registers hold -- store_tile skips them.
         // (The predicated form costs a compare, an exec dance and eight register clears per piece: ~10 % of the loop's VALU.)
         if (t * KT + KT <= p.Lk) {
-            const size_t ko = (size_t)t * KT * p.ldk, vo = (size_t)t * KT * p.ldv; // wave-uniform: one 64-bit add per load
+            const size_t ko = ((size_t)t * KT + seg) * p.ldk, vo = ((size_t)t * KT + seg) * p.ldv; // wave-uniform: one 64-bit add per load
 #pragma unroll
             for (int i = 0; i < LD_IT; ++i) {
                 if (tid + 256 * i < KT * DC) {
@@ -242,8 +269,8 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
             const int row = idx / DC, ch = idx - row * DC;
             const int key = t * KT + row;
             const bool ok = (idx < KT * DC) && (key < p.Lk);
-            rk[i] = ok ? ldg8(kbase + (size_t)key * p.ldk + ch * 8) : zero8();
-            rv[i] = ok ? ldg8(vbase + (size_t)key * p.ldv + ch * 8) : zero8();
+            rk[i] = ok ? ldg8(kbase + (seg + key) * p.ldk + ch * 8) : zero8();
+            rv[i] = ok ? ldg8(vbase + (seg + key) * p.ldv + ch * 8) : zero8();
         }
     };
     auto store_tile = [&](int st) {
@@ -472,13 +499,100 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
     __syncthreads();
     const int NTG = (NT + KVS - 1) / KVS; // every group runs the same number of iterations (the barriers are workgroup-wide)
     int thr = INT_MIN;                    // DEFER: the vote threshold of softmax_pv (INT_MIN: a group's first tile)
-    for (int it = 0; it < NTG; ++it) {
-        const int t = it * KVS + grp;
+    // SHARED: the segments are walked one after the other, NTG rounds each, and EACH is dealt to the groups from its own tile 0, so
+    // that every group stands at the segment boundary in the same round (it == NTG) and the blend's snapshot is taken there.  t
+    // counts inside the segment -- the ragged tile and its mask are the segment's -- and seg moves the loads to the anchor's rows.
+    // thr stays INT_MIN until the group has really run a tile: with one tile per segment, group 1's first is the anchor's.
+    const int NIT = two_segments ? 2 * NTG : NTG;
+    // SHARED, 0 < w < 1: w * (the normalised softmax over the own segment), parked in the workgroup's OWN output rows as fp16 -- every
+    // lane writes the pieces it will overwrite in the epilogue and reads them back there itself, so the snapshot costs no LDS and no
+    // register across the anchor segment, and nothing at all where blend is false (DESIGN.md 6t weighs the alternatives).
+    auto snapshot_store = [&](int a, float l, auto&& value) {
+        const float f = l > 0.f ? self_w / l : 0.f;
+        if (qrow[a] < p.Lq) {
+            f16* op = p.out + ((size_t)b * p.Lq + qrow[a]) * p.ldo + h * D;
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) {
+                const int dv0 = dt * 16 + g * 4;
+                if (dv0 < D) {
+                    f16x4 hv;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) hv[r] = (f16)(value(dt, r) * f);
+                    *reinterpret_cast<f16x4*>(op + dv0) = hv;
+                }
+            }
+        }
+    };
+    auto snapshot = [&](int it) {
+        if constexpr (KVS == 1) {
+#pragma unroll
+            for (int a = 0; a < QT; ++a) {
+                const float l = SUM_BY_MFMA ? __shfl(o[a][D / 16][D % 4], ((D % 16) / 4) * 16 + li) : quad_rows_sum(l_run[a]);
+                snapshot_store(a, l, [&](int dt, int r) { return o[a][dt][r]; });
+            }
+        } else {
+            // two groups: the own segment's softmax is the merge of their states.  Group 1 parks its (m, l, O) in the stage it read
+            // last round (free since that round's barrier; the round's prefetch went to the other one), group 0 combines them on the
+            // fly without touching its own state, and a second barrier keeps group 1's next store_tile behind group 0's reads.
+            static_assert(QT == 1 && !SUM_BY_MFMA, "the key/value split runs d = 80 with one query tile");
+            static_assert((size_t)(2 + NDT * 4) * 256 * sizeof(float) <= (size_t)STAGE * sizeof(f16), "snapshot merge fits one stage");
+            float* mrg = reinterpret_cast<float*>(reinterpret_cast<f16*>(smem_raw) + (size_t)(2 + ((it & 1) ^ 1)) * STAGE);
+            if (grp == 1) {
+                mrg[0 * 256 + tid] = m_run[0];
+                mrg[1 * 256 + tid] = l_run[0];
+#pragma unroll
+                for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) mrg[(2 + dt * 4 + r) * 256 + tid] = o[0][dt][r];
+            }
+            __syncthreads();
+            if (grp == 0) {
+                const float m1 = mrg[0 * 256 + tid], l1 = mrg[1 * 256 + tid];
+                const float m = fmaxf(m_run[0], m1);
+                const float a0 = __builtin_amdgcn_exp2f(m_run[0] - m), a1 = __builtin_amdgcn_exp2f(m1 - m);
+                const float l = quad_rows_sum(l_run[0] * a0 + l1 * a1);
+                snapshot_store(0, l, [&](int dt, int r) { return o[0][dt][r] * a0 + mrg[(2 + dt * 4 + r) * 256 + tid] * a1; });
+            }
+            __syncthreads();
+            // the merge ran over the stage's padded K columns, which no store_tile writes: group 1 sets them again (V has none at
+            // d = 80); its next store_tile into the stage and the reads behind this round's barrier find them as the prologue left them
+            static_assert(DV == D && DEFER, "the lent stage has padded K columns only");
+            if (grp == 1) {
+                constexpr int KPADC = (DP - D) / 8;
+                f16* sK = smem + ((it & 1) ^ 1) * STAGE;
+                for (int idx = tid; idx < KT * KPADC; idx += 256) {
+                    const int row = idx / KPADC, ch = idx - row * KPADC;
+                    f16x8 pad = zero8();
+                    if (ch == 0) pad[0] = (f16)-1.0f;
+                    *reinterpret_cast<f16x8*>(sK + row * KSTR + D + ch * 8) = pad;
+                }
+            }
+        }
+    };
+    for (int it = 0; it < NIT; ++it) {
+        const bool anchor_seg = SHARED && it >= NTG;
+        const int t = (anchor_seg ? it - NTG : it) * KVS + grp;
         const int cur = it & 1;
-        const bool has_next = t + KVS < NT;
+        // the tile this group runs in the next round
+        int t_next = t + KVS;
+        size_t seg_next = 0;
+        bool has_next = t_next < NT;
+        if constexpr (SHARED) {
+            const bool next_anchor = it + 1 >= NTG;
+            t_next = (next_anchor ? it + 1 - NTG : it + 1) * KVS + grp;
+            seg_next = next_anchor ? seg_rows : 0;
+            has_next = it + 1 < NIT && t_next < NT;
+            if (blend && it == NTG) snapshot(it);
+        }
         const f16* sK = smem + cur * STAGE;
         const f16* sV = sK + KT * KSTR;
-        if (t >= NT) { // (KVS > 1: a ragged last round)
+        if (t >= NT) { // (KVS > 1: a ragged last round; SHARED: of either segment, and the group's next tile is not staged yet)
+            if constexpr (SHARED) {
+                if (has_next) {
+                    load_tile(t_next, seg_next);
+                    store_tile(cur ^ 1);
+                }
+            }
             __syncthreads();
             continue;
         }
@@ -496,7 +610,7 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
         // the next tile's K/V are requested HERE, behind the fragment reads and the QK^T issue: requested at the top of the
         // iteration, the compiler's wait-count pass (it cannot count loads under divergent predicates) put a vmcnt(0) in front
         // of the first MFMA, i.e. the full global-load latency on the critical path of every tile
-        if (has_next && !(abl & 1)) load_tile(t + KVS);
+        if (has_next && !(abl & 1)) load_tile(t_next, seg_next);
         static_for<QT>([&](auto a_c) { softmax_pv(a_c, t, thr, s[decltype(a_c)::value], vfr, sV); });
         // (opaque to the compiler: a threshold it can see change after the first iteration makes it peel that iteration,
         // and the peeled copy costs d = 80 its register budget -- spills)
@@ -531,11 +645,14 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
             const float m1 = mrg[(a * (2 + NDT * 4) + 0) * 256 + tid], l1 = mrg[(a * (2 + NDT * 4) + 1) * 256 + tid];
             const float m = fmaxf(m_run[a], m1);
             const float a0 = __builtin_amdgcn_exp2f(m_run[a] - m), a1 = __builtin_amdgcn_exp2f(m1 - m);
-            l_run[a] = l_run[a] * a0 + l1 * a1;
+            // (the fused multiply-add is spelled out: which of the two products the compiler contracts is otherwise its choice per
+            // instantiation, and the SHARED kernel must return the plain one's bits where it walks one segment)
+            l_run[a] = __builtin_fmaf(l_run[a], a0, l1 * a1);
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o[a][dt][r] = o[a][dt][r] * a0 + mrg[(a * (2 + NDT * 4) + 2 + dt * 4 + r) * 256 + tid] * a1;
+                for (int r = 0; r < 4; ++r)
+                    o[a][dt][r] = __builtin_fmaf(o[a][dt][r], a0, mrg[(a * (2 + NDT * 4) + 2 + dt * 4 + r) * 256 + tid] * a1);
             m_run[a] = m;
         }
     }
@@ -559,8 +676,25 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
                 const int dv0 = dt * 16 + g * 4;
                 if (dv0 < D) {
                     f16x4 hv;
+                    if (SHARED && blend) { // w * softmax(own) V, parked here by snapshot(), + (1 - w) * softmax(both) V
+                        const f16x4 own = *reinterpret_cast<const f16x4*>(op + dv0);
+                        const float rest = (1.f - self_w) * inv;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) hv[r] = (f16)(o[a][dt][r] * inv);
+                        for (int r = 0; r < 4; ++r) hv[r] = (f16)((float)own[r] + o[a][dt][r] * rest);
+                    } else if constexpr (SHARED && KVS > 1) {
+                        // the plain split kernel rounds the product to fp32 and then to fp16; beside the blend branch the compiler
+                        // would fuse some of these into one mixed-precision instruction with ONE rounding, a last-bit difference in
+                        // about one element in 40000.  The product goes through an opaque statement so that both round twice.
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            float prod = o[a][dt][r] * inv;
+                            asm volatile("" : "+v"(prod));
+                            hv[r] = (f16)prod;
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) hv[r] = (f16)(o[a][dt][r] * inv);
+                    }
                     *reinterpret_cast<f16x4*>(op + dv0) = hv;
                 }
             }
@@ -581,22 +715,22 @@ __global__ __launch_bounds__(256 * KVS, (attn_min_waves<D, QT>())) void attn_ker
         SDOD_REQUIRE(std::isfinite(scale) && scale > 0.f, "scale must be finite and > 0");                                             \
     } while (0)
 
-// P is AttnP or AttnTP, and with it the kernel's TILED parameter
+// P is AttnP, AttnTP or AttnSP, and with it the kernel's TILED / SHARED parameters
 template <int D, int QT, bool TR, int KVS = 1, class P>
 hipError_t attn_launch(const P& p, hipStream_t st) {
-    constexpr bool TILED = std::is_same_v<P, AttnTP>;
+    constexpr bool TILED = std::is_same_v<P, AttnTP>, SHARED = std::is_same_v<P, AttnSP>;
     constexpr int DP = ((D + 31) / 32) * 32;
     constexpr int DV = ((D + 15) / 16) * 16;
     constexpr size_t smem = (size_t)KVS * 2 * 64 * (DP + 8 + odd16(DV)) * sizeof(f16);
     static_assert(smem <= 160 * 1024, "LDS");
     static std::atomic<unsigned long long> attr_devs{0};
     if (sdod::first_use_on_device(attr_devs)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kernel<D, QT, TR, KVS, TILED>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kernel<D, QT, TR, KVS, TILED, SHARED>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return e;
     }
     dim3 grid(((p.Lq + 64 * QT - 1) / (64 * QT)) * p.H * p.B);
-    SDOD_LAUNCH((attn_kernel<D, QT, TR, KVS, TILED>), grid, dim3(256 * KVS), smem, st, p);
+    SDOD_LAUNCH((attn_kernel<D, QT, TR, KVS, TILED, SHARED>), grid, dim3(256 * KVS), smem, st, p);
     return hipGetLastError();
 }
 

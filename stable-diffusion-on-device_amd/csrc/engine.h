@@ -104,6 +104,9 @@ public:
     // sdod_attention_mass_f16 behind middle_block.1's qkv GEMM and gives the graph one more output, slot sag_output() (-1 without)
     void enable_sag();
     int sag_output() const { return sag_ ? sag_output_ : -1; }
+    // Reference-only control (include/sdod_engine.h): enable_reference() before finalize() makes spatial_transformer() run every attn1
+    // as sdod_attention_shared_f16 with the batch's last `anchors` rows as anchors, and gives the graph the reference_self_w input
+    void enable_reference(int anchors);
     // skip_static: the inputs marked "static across a sampler run" (UNet: the text context) are unchanged since the
     // previous execute(), so the launches that depend only on them (all cross-attention K/V projections) are skipped
     void execute(hipStream_t st, bool use_hip_graph, bool skip_static = false);
@@ -130,6 +133,8 @@ private:
     bool sag_ = false;                   // SAG of the UNET graph (enable_sag()): the attention mass of middle_block.1's attn1 ...
     int sag_output_ = -1;                // ... on this output slot, fp32 [batch][L_mid], behind every other output
     float* sag_mass_ = nullptr;
+    int reference_ = 0;                  // reference-only control of the UNET graph (enable_reference()): anchor rows at the batch's end, 0 = off ...
+    const float* reference_w_ = nullptr; // ... and the reference_self_w input, fp32 [reference_], behind every other input
     bool has_kv() const { return kind_ == SDOD_GRAPH_UNET || kind_ == SDOD_GRAPH_CONTROLNET; } // owns kv_all_ and the static K/V GEMM
     int batch_;
     Mode mode_ = DECLARE;
@@ -297,6 +302,9 @@ private:
     // self-attention inside the th x tw tiles of B [h * w][ld] token maps (sdod_attention_tiled_f16): one launch, label attn_tiled_d<d>
     void attention_tiled(const f16* q, const f16* k, const f16* v, f16* out, int B, int heads, int h, int w, int th, int tw, int d,
                          int ldq, int ldk, int ldv, int ldo);
+    // self-attention of B sequences whose last `anchors` lend their keys to the others (sdod_attention_shared_f16): label attn_shared_d<d>
+    void attention_shared(const f16* q, const f16* k, const f16* v, f16* out, int B, int heads, int l, int d, int ldq, int ldk, int ldv,
+                          int ldo, int anchors, const float* self_w);
 
     // the attention mass of q, k (sdod_attention_mass_f16) into mass[B][lk]; its partial rows live in the arena for the launch: label attn_mass_d<d>
     void attention_mass(const f16* q, const f16* k, float* mass, int B, int heads, int lq, int lk, int d, int ldq, int ldk);

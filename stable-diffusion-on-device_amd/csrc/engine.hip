@@ -1104,6 +1104,16 @@ void Graph::attention_tiled(const f16* q, const f16* k, const f16* v, f16* out, 
              std::to_string(h / th) + "x" + std::to_string(w / tw) + " tile" + std::to_string(th) + "x" + std::to_string(tw));
 }
 
+void Graph::attention_shared(const f16* q, const f16* k, const f16* v, f16* out, int B, int heads, int l, int d, int ldq, int ldk, int ldv,
+                             int ldo, int anchors, const float* self_w) {
+    const float scale = 1.0f / sqrtf((float)d);
+    // counted at two segments for every main sequence: what self_w = 0 runs
+    const double seqs = 2.0 * (B - anchors) + anchors;
+    emit([=](hipStream_t st) { check_rc(sdod_attention_shared_f16(q, k, v, out, B, heads, l, d, ldq, ldk, ldv, ldo, scale, anchors, self_w, st)); },
+         "attn_shared_d" + std::to_string(d), 4.0 * seqs * heads * (double)l * l * d, 2.0 * heads * d * (double)l * (2.0 * B + 2.0 * seqs),
+         "B" + std::to_string(B) + " h" + std::to_string(heads) + " l" + std::to_string(l) + " anchors" + std::to_string(anchors));
+}
+
 void Graph::attention_mass(const f16* q, const f16* k, float* mass, int B, int heads, int lq, int lk, int d, int ldq, int ldk) {
     const float scale = 1.0f / sqrtf((float)d);
     const size_t ws_bytes = sdod_attention_mass_ws_bytes(B, heads, lq, lk);
@@ -1229,6 +1239,7 @@ void Graph::enable_hypertile(int tile, int max_depth) {
     SDOD_REQUIRE(!finalized_, "enable_hypertile() must be called before finalize()");
     SDOD_REQUIRE(tile >= 8, "HyperTile: tile must be >= 8 latent pixels");
     SDOD_REQUIRE(max_depth >= 0 && max_depth <= 3, "HyperTile: max_depth must be in [0, 3]");
+    SDOD_REQUIRE(reference_ == 0, "HyperTile excludes reference-only control");
     hypertile_ = tile;
     hypertile_depth_ = max_depth;
 }
@@ -1236,7 +1247,20 @@ void Graph::enable_hypertile(int tile, int max_depth) {
 void Graph::enable_sag() {
     SDOD_REQUIRE(kind_ == SDOD_GRAPH_UNET, "SAG applies to the UNET graph only");
     SDOD_REQUIRE(!finalized_, "enable_sag() must be called before finalize()");
+    SDOD_REQUIRE(reference_ == 0, "SAG excludes reference-only control");
     sag_ = true;
+}
+
+void Graph::enable_reference(int anchors) {
+    SDOD_REQUIRE(kind_ == SDOD_GRAPH_UNET, "reference-only control applies to the UNET graph only");
+    SDOD_REQUIRE(!finalized_, "enable_reference() must be called before finalize()");
+    SDOD_REQUIRE(anchors == 1 || anchors == 2, "reference: anchors must be 1 or 2");
+    SDOD_REQUIRE(batch_ > anchors && (batch_ - anchors) % anchors == 0, "reference: batch - anchors must be a positive multiple of anchors");
+    SDOD_REQUIRE(hypertile_ == 0 && !sag_, "reference-only control excludes HyperTile and SAG");
+    // the inputs that are per guidance copy or per image pair know nothing of the anchor rows
+    SDOD_REQUIRE(opt_.adapter_reps == 0 && !opt_.control_inputs && opt_.regions == 0 && opt_.ip_tokens == 0 && cfg_.concat_channels == 0,
+                 "reference-only control excludes adapter inputs, control inputs, regions, image prompts and concat_channels");
+    reference_ = anchors;
 }
 
 void Graph::set_loras(const sdod_lora_entry* entries, int count, hipStream_t st) {
@@ -1874,6 +1898,14 @@ extern "C" int sdod_graph_enable_sag(void* graph) {
     SDOD_TRY
     SDOD_REQUIRE(graph != nullptr, "null graph");
     static_cast<Graph*>(graph)->enable_sag();
+    return 0;
+    SDOD_CATCH
+}
+
+extern "C" int sdod_graph_enable_reference(void* graph, int anchors) {
+    SDOD_TRY
+    SDOD_REQUIRE(graph != nullptr, "null graph");
+    static_cast<Graph*>(graph)->enable_reference(anchors);
     return 0;
     SDOD_CATCH
 }

@@ -205,6 +205,8 @@ Act Graph::spatial_transformer(const std::string& pfx, const Act& x, const Act& 
     if (hypertile_ > 0) check_rc(sdod_hypertile_grid(cfg_.latent_h, cfg_.latent_w, hypertile_, level, hypertile_depth_, &th, &tw));
     if (th > 0 && (cfg_.latent_h >> level) == x.h && (cfg_.latent_w >> level) == x.w)
         attention_tiled(qkv, qkv + C, qkv + 2 * C, a1, B, heads, x.h, x.w, th, tw, d, 3 * C, 3 * C, 3 * C, C);
+    // reference-only control: the batch's last rows are the reference's, and their K / V are already in qkv
+    else if (reference_ > 0) attention_shared(qkv, qkv + C, qkv + 2 * C, a1, B, heads, L, d, 3 * C, 3 * C, 3 * C, C, reference_, reference_w_);
     else attention(qkv, qkv + C, qkv + 2 * C, a1, B, heads, L, L, d, 3 * C, 3 * C, 3 * C, C, false);
     // SAG: the middle block's attention mass from the same packed rows -- over the whole map, tiled or not
     if (sag_ && pfx == "middle_block.1") attention_mass(qkv, qkv + C, sag_mass_, B, heads, L, L, d, 3 * C, 3 * C);
@@ -556,6 +558,16 @@ void Graph::build_unet() {
             SDOD_HIP_CHECK(hipMemcpy(fp, init, sizeof(init), hipMemcpyHostToDevice));
         }
         freeu_params = fp;
+    }
+    // reference-only control: reference_self_w, fp32 [anchors], behind every other input; 1 -- plain self-attention on
+    // every row -- until the caller writes it
+    if (reference_ > 0) {
+        float* rp = (float*)io_alloc(inputs_, (size_t)reference_ * sizeof(float));
+        if (mode_ == REAL) {
+            const float init[2] = {1.f, 1.f};
+            SDOD_HIP_CHECK(hipMemcpy(rp, init, (size_t)reference_ * sizeof(float), hipMemcpyHostToDevice));
+        }
+        reference_w_ = rp;
     }
     f16* e_out = (f16*)io_alloc(outputs_, (size_t)B * H * Wd * LC * sizeof(f16));
     // SAG: the attention mass of the middle block, fp32 [B][H / 8 * W / 8], behind every other output

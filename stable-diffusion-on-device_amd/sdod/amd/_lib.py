@@ -167,6 +167,7 @@ def _declare(lib):
         'sdod_attention_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P]),
         'sdod_attention_head_dim_ok': (c_int, [c_int]),
         'sdod_attention_tiled_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+        'sdod_attention_shared_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P]),
         'sdod_hypertile_grid': (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
         'sdod_attention_wide_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
         'sdod_attention_wide_ws_f16': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P, c_size_t, P]),
@@ -262,6 +263,7 @@ HIP_SYMBOLS = [
     'sdod_attention_wide_f16', 'sdod_attention_wide_ws_f16', 'sdod_attention_wide_dim_ok', 'sdod_attention_wide_splits', 'sdod_attention_wide_ws_bytes',
     'sdod_attention_tiled_f16', 'sdod_hypertile_grid',
     'sdod_attention_mass_f16', 'sdod_attention_mass_ws_bytes', 'sdod_sag_degrade_f32', 'sdod_sag_fold_f16',
+    'sdod_attention_shared_f16',
 ]
 
 

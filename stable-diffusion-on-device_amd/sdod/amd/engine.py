@@ -150,7 +150,7 @@ ENGINE_SYMBOLS = [
     'sdod_graph_create_control', 'sdod_graph_bind_output', 'sdod_graph_create_regions',
     'sdod_graph_create_ip', 'sdod_graph_create_vision',
     'sdod_graph_enable_freeu', 'sdod_graph_freeu_input', 'sdod_graph_enable_hypertile',
-    'sdod_graph_enable_sag', 'sdod_graph_sag_output',
+    'sdod_graph_enable_sag', 'sdod_graph_sag_output', 'sdod_graph_enable_reference',
     'sdod_graph_set_networks',
     'sdod_graph_create_lcm',
     'sdod_graph_create_vae', 'sdod_graph_create_opts',
@@ -203,6 +203,7 @@ def _engine():
         lib.sdod_graph_freeu_input.argtypes = [P, ctypes.POINTER(I)]
         lib.sdod_graph_enable_sag.argtypes = [P]
         lib.sdod_graph_sag_output.argtypes = [P, ctypes.POINTER(I)]
+        lib.sdod_graph_enable_reference.argtypes = [P, I]
         lib._sdod_engine_typed = True
     return lib
 
@@ -363,6 +364,13 @@ class Graph:
         """before finalize(), UNET graphs only: the graph launches the attention-mass kernel in its middle block and gets the output
         UNet.sag_mass"""
         check(self._lib.sdod_graph_enable_sag(self._h))
+        return self
+
+    def enable_reference(self, anchors):
+        """before finalize(), UNET graphs only: the batch's last `anchors` rows are reference rows, every attn1 of the other rows also
+        attends to their keys (sdod_attention_shared_f16), and the graph gets the input UNet.reference_self_w"""
+        check(self._lib.sdod_graph_enable_reference(self._h, int(anchors)))
+        self.reference = int(anchors)
         return self
 
     def sag_output(self):
@@ -526,12 +534,16 @@ class Graph:
 
 
 class UNet(Graph):
-    def __init__(self, cfg, batch, device='cuda:0', wrap=None, sag=False):
+    def __init__(self, cfg, batch, device='cuda:0', wrap=None, sag=False, reference=0):
         """sag=True: Self-Attention Guidance's switch (sdod_graph_enable_sag) -- the finalized graph has .sag_mass, fp32
-        [batch, latent_h / 8 * latent_w / 8], the attention mass of middle_block.1's attn1"""
+        [batch, latent_h / 8 * latent_w / 8], the attention mass of middle_block.1's attn1.
+        reference=anchors (1 or 2): reference-only control's switch (sdod_graph_enable_reference) -- the last `anchors` of the `batch`
+        rows are reference rows and the finalized graph has .reference_self_w, fp32 [anchors], 1 (plain self-attention) until set"""
         super().__init__(UNET, cfg, batch, device, wrap if wrap is not None else (int(getattr(cfg, 'tiling', 0)) or None))
         if sag:
             self.enable_sag()
+        if reference:
+            self.enable_reference(reference)
 
     def finalize(self):
         super().finalize()
@@ -561,6 +573,11 @@ class UNet(Graph):
         fi = self.freeu_input()
         if fi >= 0:                 # FreeU: (b1, s1, b2, s2, version, 0, 0, 0) behind every other input, the identity until set (freeu.params)
             self.freeu = self.io_tensor(False, fi, (8,), torch.float32)
+        if getattr(self, 'reference', 0):
+            # reference-only control: the groups' self weights behind every other input.  sdod_graph_enable_reference refuses every
+            # graph with an optional input but FreeU's (cond, adapter, control, regions, image prompt), so that is x, temb, ctx
+            # (slots 0 .. 2) and FreeU's block where there is one; io_tensor checks the slot's size against [anchors] fp32
+            self.reference_self_w = self.io_tensor(False, fi + 1 if fi >= 0 else 3, (self.reference,), torch.float32)
         si = self.sag_output()
         if si >= 0:                 # SAG: the middle block's attention mass behind every other output
             self.sag_mass = self.io_tensor(True, si, (b, (c.latent_h // 8) * (c.latent_w // 8)), torch.float32)

@@ -431,6 +431,30 @@ def attention_tiled(q, k, v, heads, hw, tile_hw, out=None, scale=None):
     return out
 
 
+def attention_shared(q, k, v, heads, anchors, self_w, out=None, scale=None):
+    """Shared-key self-attention (include/sdod_hip.h: sdod_attention_shared_f16): q / k / v [B, L, heads * d] fp16, contiguous or column
+    slices of wider rows (the packed qkv tensor); the last `anchors` sequences are anchors and main sequence b of group g attends to
+    its own keys and anchor g's, blended with its self-only result by self_w[g] (fp32 [anchors] on the GPU, read by the kernel).
+    out likewise (default: a new contiguous tensor).  scale defaults to d ** -0.5."""
+    lib = _lib.hip()
+    ldq, ldk, ldv = _rows_view(q, 'q'), _rows_view(k, 'k'), _rows_view(v, 'v')
+    b, l, c = q.shape
+    if k.shape != q.shape or v.shape != q.shape or heads <= 0 or c % heads:
+        raise ValueError(f'q, k, v must all be [B, L, heads * d], got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)} with {heads} heads')
+    _req(self_w, torch.float32, 'self_w')
+    if self_w.shape != (anchors,):
+        raise ValueError(f'self_w must be [{anchors}], got {tuple(self_w.shape)}')
+    if out is None:
+        out = torch.empty(b, l, c, dtype=torch.float16, device=q.device)
+    ldo = _rows_view(out, 'out')
+    if out.shape != q.shape:
+        raise ValueError(f'out must be {tuple(q.shape)}, got {tuple(out.shape)}')
+    d = c // heads
+    check(lib.sdod_attention_shared_f16(_p(q), _p(k), _p(v), _p(out), b, heads, l, d, ldq, ldk, ldv, ldo,
+                                        d ** -0.5 if scale is None else scale, int(anchors), _p(self_w), _stream()))
+    return out
+
+
 def attention_mass(q, k, heads, scale=None, out=None):
     """Self-Attention Guidance's attention mass (include/sdod_hip.h: sdod_attention_mass_f16): q [B, Lq, heads * d], k [B, Lk, heads * d]
     fp16, contiguous or column slices of wider rows (the packed qkv tensor) -> fp32 [B, Lk], the softmax probability every key collects,

@@ -18,6 +18,7 @@ from . import ip_adapter as IP
 from . import freeu as FU
 from . import hypertile as HT
 from . import sag as SG
+from . import reference as RF
 from . import upscale as UP
 from . import panorama as PN
 from .host import DpmSolver
@@ -65,13 +66,17 @@ class Txt2Img:
     _sag_scale = 0.0            # ... set_sag's scale; 0 = off, the SAG pass is skipped
     _sag_eval = None            # ... (a, b, stage_scale, g) of the next evaluation, set by the sampler just before _unet_eps()
     _sag_ctx_fresh = True       # ... the second graph's own static-unchanged state
+    ref_unet = None     # reference-only control: the UNet graph of 2 n + 2 rows with the shared-key switch (Txt2Img(..., reference=True)), or None
+    _ref_on = False             # ... a reference is set: sample_k evaluates ref_unet, the other samplers refuse
+    _ref_eval = None            # ... (sigma, c_in, time row) of the next evaluation, set by sample_k just before _unet_eps()
+    _ref_ctx_fresh = True       # ... the graph's own static-unchanged state
 
     def __init__(self, state_dicts=None, models_dir=None, images_per_gpu=1, latent_hw=64, device='cuda:0', use_hip_graph=True,
                  tokenizer=None, with_text_encoder=True, model='sd14', with_vae=True, cfg_split=False, weight_quant=None,
                  with_vae_encoder=False, inpaint_unet=False, prompt_chunks=1, *, loras=False, hires_hw=None, adapter=False,
                  adapter_channels=3, tiling=False, upscaler=False, controlnet=False, regions=False, ip_adapter=False, canvas_hw=None,
                  canvas_wrap=False, freeu=False, unguided=False, guidance_embed=False, lora_time_modules=False, vae_attention='auto', hypertile=None,
-                 sag=False):
+                 sag=False, reference=False):
         """state_dicts: {'unet': sd, 'temb': sd, 'text': sd, 'vae': sd} in ldm/HF naming (canonical layouts; values may be
         weights.QuantU8 for an int8-weight checkpoint), or models_dir with the .sdodw containers libsdod_setup uses.
         model='sd21': SD v2.1-768 (BASELINE config 5): UNet with 64-wide heads / context 1024, v-prediction, OpenCLIP
@@ -189,12 +194,23 @@ class Txt2Img:
         img2img / inpainting loops and the LCM entry points raise ValueError.  Composes with freeu (set_freeu writes both graphs),
         hypertile, prompt_chunks, rectangular latent_hw, with_vae_encoder and upscaler.  Not with cfg_split, unguided, inpaint_unet,
         hires_hw, canvas_hw, loras, controlnet, adapter, regions, ip_adapter, tiling, model='sd21' or uint8 weights: ValueError before
-        any device work (sag.sag_check_build).  False: nothing is constructed or sized differently."""
+        any device work (sag.sag_check_build).  False: nothing is constructed or sized differently.
+        reference=True (needs with_vae_encoder=True): reference-only control (sdod/amd/reference.py).  Beside the plain pair
+        graph, self.ref_unet = E.UNet(the same config, 2 n + 2 rows, reference=2) is built from the same 'unet' weights: a second copy of
+        them, ref_unet.stats() more device memory.  Off until set_reference(image_u8, fidelity); after clear_reference() the pair graph
+        runs again and the images are the plain pipeline's, bit for bit.  While a reference is set, sample_k (and generate,
+        generate_graphed and img2img with a k-sampler on top of it) evaluates ref_unet, whose last two rows are the noised reference under
+        the uncond and the cond context; every other sampler raises ValueError.  Composes with prompt_chunks, rectangular latent_hw and
+        upscaler.  Not with sag, hypertile, cfg_split, unguided, inpaint_unet, hires_hw, canvas_hw, controlnet, adapter, regions,
+        ip_adapter, freeu, loras (both write the pair graph alone), tiling, model='sd21' or uint8 weights: ValueError before any device
+        work (reference.reference_check_build).  False: nothing is constructed or sized differently."""
         fused_vae = vae_attention_check(vae_attention)
         if weight_quant is None:     # uint8 codes in the UNet checkpoint (weights.QuantU8, the reference's QNN encoding) decide it
             weight_quant = state_dicts is not None and any(hasattr(v, 'payload') and len(v.shape) >= 2 for v in state_dicts.get('unet', {}).values())
         sag = SG.sag_check_build(sag, cfg_split, unguided, inpaint_unet, hires_hw, canvas_hw, loras, controlnet, adapter, regions, ip_adapter,
-                                 tiling, model, bool(weight_quant))
+                                 tiling, model, bool(weight_quant), reference=bool(reference))
+        reference = RF.reference_check_build(reference, with_vae_encoder, sag, hypertile, cfg_split, unguided, inpaint_unet, hires_hw, canvas_hw,
+                                             controlnet, adapter, regions, ip_adapter, freeu, loras, tiling, model, bool(weight_quant))
         lcm_check_build(unguided, guidance_embed, lora_time_modules, loras, cfg_split, inpaint_unet, hires_hw, adapter, controlnet, regions,
                         ip_adapter, canvas_hw)
         self.unguided, self.guidance_embed, self.lora_time_modules = bool(unguided), bool(guidance_embed), bool(lora_time_modules)
@@ -270,6 +286,10 @@ class Txt2Img:
             self.sag_unet = E.UNet(unet_cfg, self.n, device)
         else:
             self.unet = E.UNet(unet_cfg, self.n if cfg_split or self.unguided else 2 * self.n, device)
+        if reference:   # [uncond x n ; cond x n ; ref_u ; ref_c] on a graph of its own; the pair graph above stays what it is
+            self.ref_unet = E.UNet(unet_cfg, 2 * self.n + 2, device, reference=2)
+            self._ref_z = torch.zeros((1,) + (self.cfg.latent_channels, latent_h, latent_w), dtype=torch.float32, device=self.device)
+            self._ref_e = torch.zeros_like(self._ref_z)
         self.vae = E.VaeDecoder(vae_cfg, 1, device, fused_attn=fused_vae) if with_vae else None
         self.text = E.TextEncoder(self.cfg, 2 * (self.regions or self.prompt_chunks), device) if with_text_encoder else None
         self.encoder = E.VaeEncoder(self.cfg, 1, device, fused_attn=fused_vae) if with_vae_encoder else None
@@ -288,7 +308,8 @@ class Txt2Img:
         self._dir = models_dir
         for g, key, stem in ((self.unet, 'unet', 'unet'), (self.vae, 'vae', 'vae_decoder'), (self.text, 'text', 'text_encoder'),
                              (self.encoder, 'vae_enc', 'vae_encoder'), (self.masked_encoder, 'vae_enc', 'vae_encoder'),
-                             (self.adapter, 'adapter', 'adapter'), (self.canvas_vae, 'vae', 'vae_decoder'), (self.sag_unet, 'unet', 'unet')):
+                             (self.adapter, 'adapter', 'adapter'), (self.canvas_vae, 'vae', 'vae_decoder'), (self.sag_unet, 'unet', 'unet'),
+                             (self.ref_unet, 'unet', 'unet')):
             if g is None:
                 continue
             self._load(g, key, stem)
@@ -562,6 +583,43 @@ class Txt2Img:
                 raise ValueError('Self-Attention Guidance folds its term through the guidance scale: guidance must not be 0')
             self._sag_eval = (float(a), float(b), float(stage_scale), float(guidance))
 
+    # ------------------------------------------------------------------ reference-only control
+    def set_reference(self, image_u8, fidelity=0.5, noise=None, seed=0):
+        """turn reference-only control on: image_u8, one uint8 picture [8 H, 8 W, 3], is encoded by the VAE encoder (its posterior sample
+        drawn on streams 1 and 2 of `seed`, as encode() draws) into z_ref; e_ref is `noise` (fp32 [4, H, W]) or drawn on the device,
+        Philox stream family reference.NOISE_FAMILY of `seed`; fidelity (style_fidelity, in [0, 1]) is the weight of the self-only
+        attention on the uncond rows: self_w = (fidelity, 0).  Every later evaluation of sample_k gives the two reference rows
+        (z_ref + sigma_i e_ref) c_in(sigma_i).  ONE e_ref serves every step (diffusers draws a fresh one per step; each step's input has
+        the same distribution), so a captured trajectory depends on neither the step count nor the picture: all three are written in
+        place and a *_graphed trajectory follows a second set_reference without a recapture.  ValueError for bad arguments
+        (reference.reference_check_args) before any device work; RuntimeError without reference=True."""
+        RF.require(self)
+        image_u8, fidelity, noise = RF.reference_check_args(image_u8, fidelity, noise, self._latent_shape)
+        _, z0 = self.encode(image_u8, seed=seed, image_index=0, return_z0=True)
+        self._ref_z.copy_(z0)
+        if noise is None:
+            ops.randn(tuple(self._ref_e.shape), seed, RF.NOISE_FAMILY << 32, self.device, out=self._ref_e)
+        else:
+            self._ref_e.copy_(noise)
+        self.ref_unet.reference_self_w.copy_(torch.tensor([fidelity, 0.0], dtype=torch.float32))
+        self._ref_on = True
+
+    def clear_reference(self):
+        """the state after construction: the plain pair graph evaluates, the images are the plain pipeline's bit for bit"""
+        RF.require(self)
+        self._ref_on = False
+
+    def _ref_refuse(self, name):
+        """the entry points whose evaluations the reference rows are not wired into refuse while a reference is set"""
+        if self._ref_on:
+            raise ValueError(f'{name} does not run reference-only control (it is wired into sample_k): clear_reference() first')
+
+    def _stage_slots(self):
+        """where a sampler stages the pair's x and time rows: the pair graph's slots, or the first 2 n rows of ref_unet's"""
+        if self._ref_on:
+            return self.ref_unet.x[:2 * self.n], self.ref_unet.temb[:2 * self.n]
+        return self.unet.x, self._temb_dst
+
     # ------------------------------------------------------------------ regional prompts
     def set_regions(self, masks_u8):
         """masks_u8: uint8 [regions, 8h, 8w] at image resolution (torch or numpy; 255 = inside, soft and overlapping masks allowed,
@@ -795,6 +853,10 @@ class Txt2Img:
         if self.sag_unet is not None:   # the degraded latents are evaluated under the uncond context
             self.sag_unet.ctx.copy_(self.unet.ctx[:n])
             self._sag_ctx_fresh = True
+        if self.ref_unet is not None:   # the pair's rows, then the reference under the uncond and under the cond context
+            self.ref_unet.ctx[:2 * n].copy_(self.unet.ctx)
+            self.ref_unet.ctx[2 * n:].copy_(ctx2[:2])
+            self._ref_ctx_fresh = True
         self._ctx_fresh = True     # the next UNet execute must redo the cross-attention K/V projections
 
     def _exchange_halves(self, mine):
@@ -811,6 +873,17 @@ class Txt2Img:
 
     def _unet_eps(self):
         """one UNet evaluation of the staged inputs: the fp16 prediction [2n, H, W, 4] = (uncond rows ; cond rows)"""
+        if self._ref_on:
+            # reference-only control: the two reference rows' input (z_ref + sigma e_ref) c_in and time row in two existing launches,
+            # then the graph of 2 n + 2 rows; the reference rows' prediction is dropped
+            if self._ref_eval is None:
+                raise ValueError('this evaluation does not run reference-only control (it is wired into sample_k): clear_reference() first')
+            (sigma, c_in, temb_row), self._ref_eval = self._ref_eval, None
+            r, n2 = self.ref_unet, 2 * self.n
+            ops.stage_unet_inputs(ops.lincomb4([self._ref_z, self._ref_e], [c_in, sigma * c_in], 1.0), r.x[n2:], temb_row, r.temb[n2:])
+            r.execute(self.use_hip_graph, static_unchanged=not self._ref_ctx_fresh)
+            self._ref_ctx_fresh = False
+            return r.eps[:n2]
         if self.controlnet is not None:
             w = self.unet.temb_width
             self.unet.temb.copy_(self._temb_stage[:, :w])
@@ -849,6 +922,7 @@ class Txt2Img:
     # ------------------------------------------------------------------ samplers
     def sample_plms(self, ctx2, x_T, steps=20, guidance=7.5, trace=None):
         self._require_pairs('sample_plms')
+        self._ref_refuse('sample_plms')
         sch = PlmsSchedule(steps)
         temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
         self._set_context(ctx2)
@@ -896,6 +970,7 @@ class Txt2Img:
         """the reference driver's sampler: DPM-Solver++(2M), CFG as g*e_c + (1-g)*e_u (context.cpp:342-382)"""
         self._require_pairs('sample_dpm')
         self._sag_refuse('sample_dpm')
+        self._ref_refuse('sample_dpm')
         solver = DpmSolver()
         model_ts = solver.prepare(steps)
         temb = self.time_embeddings(model_ts[:steps])
@@ -929,15 +1004,18 @@ class Txt2Img:
         if step_noise is not None:
             step_noise = step_noise.to(self.device, torch.float32).contiguous()
         den_prev = torch.empty_like(x) if sampler == 'dpmpp_2m' else None
+        ux, ut = self._stage_slots()
         ops.k_step(None, x, dict(a=float(sch.sigmas[0]) if first == 0 else 1.0, stage_scale=sch.c_in(first)),
-                   stage=(self.unet.x, temb[first], self._temb_dst))
+                   stage=(ux, temb[first], ut))
         for i in range(first, steps):
             cf = sch.coef(sampler, i, eta, self.v_prediction, first)
             self._sag_stage(1.0, sch.sigmas[i], sch.c_in(i), guidance)
+            if self._ref_on:
+                self._ref_eval = (float(sch.sigmas[i]), float(sch.c_in(i)), temb[i])
             ops.k_step(self._unet_eps(), x, cf, guidance, den_prev=den_prev,
                        noise=step_noise[i - first] if step_noise is not None and cf['u'] != 0.0 else None,
                        seed=seed, noise_level=i, image_index=image_index, mode=1,
-                       stage=(self.unet.x, temb[i + 1], self._temb_dst) if i + 1 < steps else None)
+                       stage=(ux, temb[i + 1], ut) if i + 1 < steps else None)
         return x
 
     # ------------------------------------------------------------------ few-step sampling (Latent Consistency Models)
@@ -953,6 +1031,7 @@ class Txt2Img:
         ((3 + i) << 32) | (image_index + k) of `seed` for image k.  return_denoised=True: (x, den) with den the last step's x0
         prediction.  Argument errors raise ValueError before any device work (lcm_check_args)."""
         self._sag_refuse('sample_lcm')
+        self._ref_refuse('sample_lcm')
         g, w = lcm_check_args(self, x, steps, guidance, original_steps, strength, step_noise)
         sch = LcmSchedule(int(steps), int(original_steps), float(strength))
         temb = self.time_embeddings(sch.timesteps.astype(np.float32), w)   # row i <-> step i
@@ -1053,6 +1132,7 @@ class Txt2Img:
         ValueError, as every other argument error does before any device work."""
         self._require_pairs('sample_panorama')
         self._sag_refuse('sample_panorama')
+        self._ref_refuse('sample_panorama')
         plan = self._panorama_plan(x_T, sampler, steps, schedule, eta, stride, weights, step_noise)
         sch = KSchedule(steps, schedule)
         temb = self.time_embeddings(sch.times)                             # row i <-> step i
@@ -1167,6 +1247,8 @@ class Txt2Img:
             key = (key, 'control')
         if self._sag_scale:                     # ... and so is one with the SAG pass in it, whose scale is a launch argument
             key = (key, 'sag', self._sag_scale)
+        if self._ref_on:                        # ... and one that evaluates ref_unet; the picture, noise and fidelity are device memory
+            key = (key, 'reference')
         if key not in self._traj:
             statics = [torch.zeros(tuple(shape), dtype=dtype, device=self.device) for shape, dtype in inputs]
             pipes = [self] if self.hires is None else [self, self.hires]
@@ -1316,6 +1398,7 @@ class Txt2Img:
         """ldm DDIMSampler.decode: t_enc DDIM steps (eta = 0, CFG mode 1) from ddim index t_enc - 1 down to 0"""
         self._require_pairs('sample_ddim_from')
         self._sag_refuse('sample_ddim_from (DDIM img2img)')
+        self._ref_refuse('sample_ddim_from (DDIM img2img)')
         sch = PlmsSchedule(steps)
         temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
         self._set_context(ctx2)
@@ -1375,6 +1458,7 @@ class Txt2Img:
         + ddim_step + the blend + stage_unet_inputs, bit for bit)."""
         self._require_pairs('sample_ddim_inpaint')
         self._sag_refuse('sample_ddim_inpaint')
+        self._ref_refuse('sample_ddim_inpaint')
         sch = PlmsSchedule(steps)
         temb = self.time_embeddings(sch.timesteps.astype(np.float32))     # row k <-> timestep index k
         self._set_context(ctx2)

@@ -13,7 +13,7 @@ MAX_SCALE = 10.0
 
 
 def sag_check_build(sag, cfg_split=False, unguided=False, inpaint_unet=False, hires_hw=None, canvas_hw=None, loras=False, controlnet=False,
-                    adapter=False, regions=False, ip_adapter=False, tiling=False, model='sd14', weight_quant=False):
+                    adapter=False, regions=False, ip_adapter=False, tiling=False, model='sd14', weight_quant=False, reference=False):
     """Txt2Img's `sag` before any device work: False / None -> False, True -> True unless one of the arguments the second UNet graph
     does not follow yet is set, anything else a ValueError.  freeu and hypertile compose: the second graph is built with the same
     switches and set_freeu() writes both."""
@@ -22,7 +22,8 @@ def sag_check_build(sag, cfg_split=False, unguided=False, inpaint_unet=False, hi
     if sag is not True:
         raise ValueError(f'sag must be True or False, got {sag!r} (the scale goes to set_sag)')
     given = dict(cfg_split=cfg_split, unguided=unguided, inpaint_unet=inpaint_unet, hires_hw=hires_hw is not None, canvas_hw=canvas_hw is not None,
-                 loras=loras, controlnet=controlnet, adapter=adapter, regions=regions, ip_adapter=ip_adapter, tiling=tiling)
+                 loras=loras, controlnet=controlnet, adapter=adapter, regions=regions, ip_adapter=ip_adapter, tiling=tiling,
+                 reference=reference)   # (the engine refuses the two switches on one graph: sdod_graph_enable_reference)
     bad = [name for name, v in given.items() if v]
     if model == 'sd21':
         bad.append("model='sd21' (v-prediction)")
